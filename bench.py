@@ -55,7 +55,30 @@ def parse():
     ap.add_argument("--workload", default="dm", choices=["dm", "c5"],
                     help="N > 1 only: dm = dm-only TreePM (the metric's configuration, default); c5 = BASELINE configs[4]-shaped step, "
                          "n^3 gas + n^3 dark matter: sharded TreePM over all + device-resident sharded SPH density and hydro of the gas")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="1 GPU only: after the timed steps, write what the last one computed (GravPM, PM potential, tree "
+                         "acceleration and potential, interaction counts; a fixed sample of %d particles when there are more) as "
+                         "DIR/<name>.npy" % DUMP_SAMPLE)
     return ap.parse_args()
+
+
+DUMP_SAMPLE = 1 << 18    # particles per dumped array: 5 arrays + the index, at most 20 MB in all
+DUMP_SEED = 20240602
+
+
+def dump_outputs(ctx, capi, n, out_dir):
+    """The results of the timed path's last step as a caller of shq_treepm_step receives them (shq_pm_download,
+    shq_grav_short_download), each restricted to the same seeded sample of particles (upload order; `index` lists them)."""
+    gravpm, pm_pot = np.zeros((n, 3)), np.zeros(n)
+    acc, pot, nint = np.zeros((n, 3)), np.zeros(n), np.zeros(n, dtype=np.int64)
+    capi.check(capi.hip.shq_pm_download(ctx.h, capi.ptr(gravpm), capi.ptr(pm_pot)))
+    capi.check(capi.hip.shq_grav_short_download(ctx.h, capi.ptr(acc), capi.ptr(pot), capi.ptr(nint), None))
+    idx = np.arange(n) if n <= DUMP_SAMPLE else np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"index": idx.astype(np.float64), "gravpm": gravpm[idx], "pm_potential": pm_pot[idx],
+              "tree_accel": acc[idx], "tree_potential": pot[idx], "ninteractions": nint[idx].astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline(pos, mass, tree, gp_rel, oldacc, L, acc_gpu=None):
@@ -676,6 +699,8 @@ def launch_ranks(args):
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("SHQ_COMM_FORCE", "0") == "1"):
+        raise SystemExit("bench.py: --dump-outputs is for the one-GPU run")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and os.environ.get("SHQ_COMM_FORCE", "0") != "1":
         sys.exit(launch_ranks(args))
     rank = int(os.environ.get("RANK", "0"))
@@ -799,6 +824,8 @@ def main():
     # deepest pair stack; an overflow in any of the timed steps comes back here as an error
     pair_rec, pair_high, pair_mop = C.c_int64(0), C.c_int64(0), C.c_int64(0)
     capi.check(capi.hip.shq_walk_pair_status(ctx.h, C.byref(pair_rec), C.byref(pair_high), C.byref(pair_mop)))
+    if args.dump_outputs:                    # before the counted step below overwrites the last timed step's results
+        dump_outputs(ctx, capi, n, args.dump_outputs)
     capi.check(capi.hip.shq_set_walk_stats(ctx.h, 1))
     step(gp_rel, one_call=False)
     capi.check(capi.hip.shq_grav_refresh_oldacc(ctx.h, G))   # the OldAcc of the NEXT step, for the checks below

@@ -76,11 +76,9 @@ def test_exchange_in_batches_with_gc():
 
 
 def _ref_keys(P, n, box):
-    import ctypes as C
-    lib = C.CDLL(os.path.join(ROOT, "oracle", "_ref", "libpeano_ref.so"))
-    lib.ref_PEANO.restype = C.c_uint64
-    lib.ref_PEANO.argtypes = [C.c_void_p, C.c_double]
-    return np.array([lib.ref_PEANO(np.ascontiguousarray(P["Pos"][i]).ctypes.data, box) for i in range(n)], dtype=np.uint64)
+    """the reference's PEANO(Pos) of the first n particles (oracle/_ref/libpeano_ref.so, or its stored keys: tests/ref_outputs.py)"""
+    import ref_outputs as ro
+    return ro.peano().keys(P["Pos"][:n], box)
 
 
 def gc_sorted_setup(rng):
@@ -106,7 +104,6 @@ def check_gc_sorted(P, numpart, slots, slot_size, box=25000.0):
     fx.check_after([(P, numpart, slots, slot_size)], 1, 127 * 6)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libpeano_ref.so")), reason="needs the reference's peano key (make -C oracle ref)")
 def test_slots_gc_sorted_reference_fixture():
     P, numpart, slots, slot_size = gc_sorted_setup(np.random.default_rng(5))
     T = oex.Task(P, numpart, slots, slot_size)

@@ -301,7 +301,6 @@ def test_exchange_in_batches_with_gc_equals_oracle(ctx):
     fx.check_after(out, ntask, ntask * 48)
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "libpeano_ref.so")), reason="needs the reference's peano key (make -C oracle ref)")
 def test_slots_gc_sorted_reference_fixture(ctx):
     """tests/test_slotsmanager.cpp:87-115 on the device with the reference's own keys, against the oracle field for field"""
     sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -219,33 +219,22 @@ def test_domain_tree_walks_and_exports_like_the_uploaded_tree(ctx):
     assert np.array_equal(got["NodeList"], otable["NodeList"])
 
 
-def test_domain_maintain_topleaf_equals_reference_keys(ctx):
-    """shq_domain_maintain_topleaf after a drift: every live particle's top leaf is domain_get_topleaf(PEANO(pos)) on a top tree cut
-    in Peano-Hilbert key space, with the reference's own peano.cpp (compiled in place, pinned by its golden keys) as the judge;
-    layoutfunc's targets; inactive dark matter stays when no dark-matter tree is wanted; garbage is left alone"""
-    import ctypes
-    import os
-    import torch
+TOPLEAF_DRIFT = 0.12 * cm.BOX                                 # a long drift: a good part of the particles leaves its leaf
+
+
+def topleaf_case(peano):
+    """the host side of test_domain_maintain_topleaf_equals_reference_keys: the key-space top tree, its leaves' tasks, and the particles
+    of task `me` (pos[mine]: their positions before the drift)"""
     import test_peano_ref_cpu as tp
-    if not os.path.exists(tp.LIB):
-        pytest.skip("no prebuilt reference peano library")
-    lib = ctypes.CDLL(tp.LIB)
-    lib.ref_peano_hilbert_key.restype = ctypes.c_uint64
-    lib.ref_peano_hilbert_key.argtypes = [ctypes.c_int] * 4
-    lib.ref_PEANO.restype = ctypes.c_uint64
-    lib.ref_PEANO.argtypes = [ctypes.c_void_p, ctypes.c_double]
     rng = np.random.default_rng(77)
     nodes = tp.key_space_topnodes(rng, maxdepth=3, psplit=0.6)
-    geo = tp.geo_from_topnodes(nodes, lib)
+    geo = tp.geo_from_topnodes(nodes, peano)
     ntl = sum(1 for nd in nodes if nd["Daughter"] < 0)
     ntask, me = 4, 1
     tl = np.zeros(ntl, dtype=capi.TOPLEAF_DTYPE)
     tl["Task"] = np.arange(ntl) % ntask
-
-    def ref_leaf(p):
-        return np.array([tp.domain_get_topleaf(lib.ref_PEANO(np.ascontiguousarray(x).ctypes.data, cm.BOX), nodes) for x in p], dtype=np.int32)
     pos = rng.random((20000, 3)) * cm.BOX
-    leaf0 = ref_leaf(pos)
+    leaf0 = peano.topleaves("topleaf_initial", pos, cm.BOX, lambda k: tp.domain_get_topleaf(k, nodes))
     mine = np.flatnonzero(tl["Task"][leaf0] == me)
     n = len(mine)
     pman = cm.make_partmanager(np.ascontiguousarray(pos[mine]))
@@ -255,13 +244,28 @@ def test_domain_maintain_topleaf_equals_reference_keys(ctx):
     P["Vel"] = rng.normal(size=(n, 3)) * 1.0
     P["TimeBinGravity"] = rng.integers(19, 23, n)
     P["Flags"][::97] |= 1
+    return nodes, geo, tl, me, pos, leaf0, mine, pman
+
+
+def test_domain_maintain_topleaf_equals_reference_keys(ctx):
+    """shq_domain_maintain_topleaf after a drift: every live particle's top leaf is domain_get_topleaf(PEANO(pos)) on a top tree cut
+    in Peano-Hilbert key space, with the reference's own peano.cpp (compiled in place, pinned by its golden keys; or the top leaves it
+    gave for exactly these positions, tests/ref_outputs.py) as the judge; layoutfunc's targets; inactive dark matter stays when no dark-matter tree
+    is wanted; garbage is left alone"""
+    import torch
+    import ref_outputs as ro
+    import test_peano_ref_cpu as tp
+    peano = ro.peano()
+    nodes, geo, tl, me, _, leaf0, mine, pman = topleaf_case(peano)
+    n = len(mine)
+    P = pman.Base
     pv = pman.view()
     capi.check(capi.hip.shq_particles_upload(ctx.h, C.byref(pv)))
     sq.dynamics_upload(ctx, pman)
     sq.tree_build_domain(ctx, cm.BOX, geo, tl.copy(), me, n + 5)
-    sq.drift(ctx, 0.12 * cm.BOX, cm.BOX)                      # a long drift: a good part of the particles leaves its leaf
+    sq.drift(ctx, TOPLEAF_DRIFT, cm.BOX)
     sq.dynamics_download(ctx, pman)
-    want = ref_leaf(P["Pos"])
+    want = peano.topleaves("topleaf_drifted", P["Pos"], cm.BOX, lambda k: tp.domain_get_topleaf(k, nodes))
     old = leaf0[mine].copy()
     old[5], old[6] = -1, 10**6                                # invalid entries (the FOF exchange overwrites TopLeaf): looked up afresh
     garbage = (P["Flags"] & 1) != 0

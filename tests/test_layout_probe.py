@@ -1,28 +1,19 @@
 """The reference's own struct layouts against the ones the C-ABI views and the Python dtypes assume.
 
-oracle/_ref/layout_probe is oracle/ref_layout_probe.cpp compiled against /root/reference/libgadget/partmanager.h and
-slotsmanager.h as they lie (no stand-ins; `make -C oracle ref`).  It evaluates the view initialisers INTEGRATION.md shows for the
+oracle/_ref/layout_probe is oracle/ref_layout_probe.cpp compiled against the reference's libgadget/partmanager.h and slotsmanager.h
+as they lie (no stand-ins; `make -C oracle ref`); where it has not been built, its stored output stands in for it
+(tests/golden/ref_layout_probe.json, tests/ref_outputs.py).  It evaluates the view initialisers INTEGRATION.md shows for the
 shenqi side and reports where the IsGarbage / Swallowed bits sit."""
-import json
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+import ref_outputs as ro
 from shenqi_amd import capi
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PROBE = os.path.join(ROOT, "oracle", "_ref", "layout_probe")
 
 
 @pytest.fixture(scope="module")
 def layout():
-    if not os.path.exists(PROBE):
-        if os.path.isdir("/root/reference/libgadget"):
-            pytest.fail("oracle/_ref/layout_probe missing although /root/reference is present: run `make -C oracle ref`")
-        pytest.skip("no reference and no prebuilt probe")
-    return json.loads(subprocess.check_output([PROBE]).decode())
+    return ro.layout()
 
 
 def test_particle_data_layout(layout):

@@ -1,11 +1,11 @@
 """The top tree handed to shq_tree_build_domain as geometry against the reference's own key arithmetic.
 
-oracle/_ref/libpeano_ref.so is libgadget/utils/peano.cpp compiled where it lies (`make -C oracle ref`).  It must reproduce the golden
+oracle/_ref/libpeano_ref.so is libgadget/utils/peano.cpp compiled where it lies (`make -C oracle ref`); where it has not been built, the
+keys it gave for the inputs below stand in for it (tests/golden/ref_peano.npz, tests/ref_outputs.py).  It must reproduce the golden
 keys of the reference's tests/test_peano.cpp (tests/golden/peano_keys.json); with it, a top tree cut in Peano-Hilbert key space the way
 domain.cpp does (TopNodes with StartKey / Shift / Daughter / Leaf) is turned into the daughter-per-octant table by the loop of
 INTEGRATION.md (force_create_node_for_topnode's `sub`, forcetree.cpp:881), and for random positions the top leaf found by geometric
 descent through that table (what the device build does) must be domain_get_topleaf(PEANO(pos)) (domain.h:68-76)."""
-import ctypes as C
 import json
 import os
 
@@ -13,32 +13,30 @@ import numpy as np
 import pytest
 
 import common as cm
+import ref_outputs as ro
 from shenqi_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "oracle", "_ref", "libpeano_ref.so")
 BITS = 21
+DESCENT_SEEDS = (1, 2, 3)
 
 
 @pytest.fixture(scope="module")
 def peano():
-    if not os.path.exists(LIB):
-        if os.path.isdir("/root/reference/libgadget"):
-            pytest.fail("oracle/_ref/libpeano_ref.so missing although /root/reference is present: run `make -C oracle ref`")
-        pytest.skip("no reference and no prebuilt peano library")
-    lib = C.CDLL(LIB)
-    lib.ref_peano_hilbert_key.restype = C.c_uint64
-    lib.ref_peano_hilbert_key.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int]
-    lib.ref_PEANO.restype = C.c_uint64
-    lib.ref_PEANO.argtypes = [C.c_void_p, C.c_double]
-    return lib
+    return ro.peano()
+
+
+def golden_positions():
+    """the positions of tests/test_peano.cpp's golden keys (box 4)"""
+    return np.array([[i % 4, (i // 4) % 4, (i // 16) % 4] for i in range(64)], dtype=np.float64)
 
 
 def test_reference_key_reproduces_its_golden_values(peano):
     gold = json.load(open(os.path.join(ROOT, "tests", "golden", "peano_keys.json")))["keys"]
-    for i, g in enumerate(gold):
-        p = np.array([i % 4, (i // 4) % 4, (i // 16) % 4], dtype=np.float64)
-        assert peano.ref_PEANO(p.ctypes.data, 4.0) == g
+    pos = golden_positions()
+    assert len(gold) == len(pos)
+    for p, g in zip(pos, gold):
+        assert peano.key(p, 4.0) == g
 
 
 def key_space_topnodes(rng, maxdepth=3, psplit=0.7):
@@ -75,7 +73,7 @@ def geo_from_topnodes(nodes, peano):
             for j in range(2):
                 for k in range(2):
                     count = i + 2 * j + 4 * k
-                    sub = 7 & peano.ref_peano_hilbert_key((x << 1) + i, (y << 1) + j, (z << 1) + k, bits)
+                    sub = 7 & peano.hilbert_key((x << 1) + i, (y << 1) + j, (z << 1) + k, bits)
                     geo["daughter"][topnode][count] = d + sub
                     fill(d + sub, bits + 1, 2 * x + i, 2 * y + j, 2 * z + k)
 
@@ -90,15 +88,21 @@ def domain_get_topleaf(key, nodes):
     return nodes[no]["Leaf"]
 
 
-@pytest.mark.parametrize("seed", [1, 2, 3])
-def test_geometric_descent_finds_the_reference_topleaf(peano, seed):
+def descent_case(seed):
+    """the top tree and the positions of test_geometric_descent_finds_the_reference_topleaf[seed]"""
     rng = np.random.default_rng(seed)
     nodes = key_space_topnodes(rng)
+    pos = rng.random((4000, 3)) * cm.BOX
+    return nodes, pos
+
+
+@pytest.mark.parametrize("seed", DESCENT_SEEDS)
+def test_geometric_descent_finds_the_reference_topleaf(peano, seed):
+    nodes, pos = descent_case(seed)
     geo = geo_from_topnodes(nodes, peano)
     assert sorted(int(x) for x in geo["leaf"] if x >= 0) == list(range(sum(1 for nd in nodes if nd["Daughter"] < 0)))
     box = cm.BOX
-    pos = rng.random((4000, 3)) * box
     got = cm.topleaf_of(pos, geo, box)
-    want = np.array([domain_get_topleaf(peano.ref_PEANO(np.ascontiguousarray(p).ctypes.data, box), nodes) for p in pos])
+    want = peano.topleaves("descent%d" % seed, pos, box, lambda k: domain_get_topleaf(k, nodes))
     assert np.array_equal(got, want)
     assert len(np.unique(want)) > 8
