@@ -683,6 +683,13 @@ int shq_set_walk_overlap(shq_context *ctx, int mode);
  * it: every task goes to the mop-up pass); pair_stack_cap > 0 = pairs per wave stack (1344 .. 4096; small values force the overflow). */
 int shq_walk_pair_status(shq_context *ctx, int64_t *recovered_launches, int64_t *stack_high_water, int64_t *last_mopped_tasks);
 int shq_set_walk_debug(shq_context *ctx, int pair_spin_max, int pair_stack_cap);
+/* shq_set_tree_debug (tests): initial_node_cap > 0 = node pool of the first attempt of every later shq_tree_build /
+ * shq_tree_build_domain (0: the default 0.6 n + 4096).  A tree that does not fit ends the attempt on the device (nothing is written
+ * past the pool or the frontier, no later level runs); the host doubles the pool and builds again, up to 5 attempts, then returns
+ * SHQ_ERR_NOMEM ("node pool overflow") with no tree installed.  Small values force that retry path; the tree is the same.
+ * shq_tree_build_attempts: attempts the last build made (1 = no retry). */
+int shq_set_tree_debug(shq_context *ctx, int64_t initial_node_cap);
+int shq_tree_build_attempts(shq_context *ctx, int *attempts);
 /* Checker utility: direct summation as the reference's own gravity test does it (force_direct / grav_force,
  * libgadget/tests/test_gravity.cpp:41-76,121-143): accel[ns][3] (host) = acceleration at the ns sample positions (host, [ns][3]) from
  * the first nsrc resident particles and their (2 repeat + 1)^3 periodic images, spline-softened below h.  Partial sums over a

@@ -122,6 +122,18 @@ def tree_build_device(ctx, BoxSize, mask=None, active=None):
     return st
 
 
+def set_tree_debug(ctx, initial_node_cap=0):
+    """shq_set_tree_debug: node pool of the first build attempt (0: the default formula); small values force the retry path."""
+    capi.check(capi.hip.shq_set_tree_debug(ctx.h, int(initial_node_cap)), "shq_set_tree_debug")
+
+
+def tree_build_attempts(ctx):
+    """shq_tree_build_attempts: attempts the last device tree build made (1 = the first node pool was enough)."""
+    a = C.c_int(0)
+    capi.check(capi.hip.shq_tree_build_attempts(ctx.h, C.byref(a)), "shq_tree_build_attempts")
+    return a.value
+
+
 def tree_build_domain(ctx, BoxSize, geo, topleaves, ThisTask, firstnode, mask=None, active=None):
     """shq_tree_build_domain: the device tree under a domain decomposition.  geo: capi.TOPNODE_GEO_DTYPE array, topleaves:
     capi.TOPLEAF_DTYPE array (Task read, treenode written).  Returns (stats, local moments as capi.TOPLEAF_MOMENTS_DTYPE)."""

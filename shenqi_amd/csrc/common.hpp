@@ -313,6 +313,8 @@ struct shq_context {
     std::vector<int32_t> node_rank;  /* caller's node index -> packed index (-1: unreachable); empty = identity */
     bool have_father = false;
     TreeBuildBufs tb;
+    int64_t tb_initial_cap = 0; /* node pool of a build's first attempt (0: 0.6 n + 4096); shq_set_tree_debug */
+    int tb_attempts = 0;        /* attempts the last tree build made (each overflow doubles the pool); shq_tree_build_attempts */
     DevBuf<int32_t> tree_targets; /* own particles in leaf order (SHQ_WALK_TREE_ORDER) */
     int64_t ntree_targets = 0;
     bool have_tree_targets = false;

@@ -39,6 +39,24 @@ def random_positions(u, numpart, box=BOX):
     return pos
 
 
+def clump_positions(n, seed=0, box=BOX, width_cells=6):
+    """Tight clumps of 9-16 particles (clustered halos after many steps): each clump spans `width_cells` cells of the tree's
+    deepest level (Box * 1.001 / 2^21), so the tree makes a chain of single-child nodes about 15 levels long above it - more
+    nodes per particle than the device build's first node-pool guess (tree_build.hip).  Returns (pos [n, 3], mass [n]):
+    unequal masses that a float holds exactly; clump centres uniform in the box."""
+    rng = np.random.default_rng(seed)
+    sizes = rng.integers(9, 17, size=n // 9 + 1)
+    sizes = sizes[:np.searchsorted(np.cumsum(sizes), n, side="right")]
+    short = np.flatnonzero(sizes < 16)[:n - int(sizes.sum())]     # the remainder (< 16) one particle each to clumps of < 16
+    sizes[short] += 1
+    assert sizes.sum() == n and sizes.min() >= 9 and sizes.max() <= 16
+    width = width_cells * box * 1.001 / 2.0**21
+    centres = width + rng.random((len(sizes), 3)) * (box - 2 * width)
+    pos = np.repeat(centres, sizes, axis=0) + (rng.random((n, 3)) - 0.5) * width
+    mass = (1.0 + rng.random(n)).astype(np.float32).astype(np.float64)   # particle_data.Mass is a float
+    return pos, mass
+
+
 def make_partmanager(pos, box=BOX, mass=1.0, ptype=1):
     """setup_particles, tests/test_gravity.cpp:174-195"""
     n = len(pos)

@@ -64,3 +64,17 @@ def test_mask_hmax_update(kind, ncbrt):
     ft.check_hmax(nodes, fn, father_of(tree, n), pos, pman.Base["Hsml"])
     if kind == "flat":
         assert nodes["hmax"][0] >= 0.0584             # test_forcetree.cpp:369
+
+
+def test_clump_input_needs_more_than_the_device_first_pool():
+    """The clumps of test_gpu_treebuild_overflow.py must keep the device build on its retry path: their tree has more nodes than the
+    first node pool of shq_tree_build (0.6 n + 4096, tree_build_impl in shenqi_amd/csrc/tree_build.hip) and fits the host
+    builder's 1.5 n + 4096.  Retuning the generator or that formula must not quietly turn the GPU test into a no-retry build."""
+    n = 200000
+    pos, mass = cm.clump_positions(n, seed=0)
+    pman = cm.make_partmanager(pos)
+    pman.Base["Mass"] = mass
+    tree = sq.force_tree_full(pman)
+    assert 0.6 * n + 4096 < tree.numnodes < 1.5 * n + 4096
+    nreal = ft.check_tree(tree.Nodes_base, tree.firstnode, father_of(tree, n), pos)
+    ft.check_moments(tree.Nodes_base, tree.firstnode, father_of(tree, n), pman.Base["Mass"], cm.BOX, nreal)
