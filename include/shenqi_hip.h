@@ -1176,6 +1176,31 @@ int shq_treepm_last_fused(shq_context *ctx, int *fused);
  * reference has no order between force_tree_full and gravpm_force either (run.cpp:476-538; the PM uses no tree).  Every other consumer
  * of PM results (shq_pm_download, shq_kick_pm, ...) joins it too; shq_drift and a particle upload discard it. */
 int shq_pm_start(shq_context *ctx, const shq_pm_params *pm, double G);
+/* gravpm_force with massive neutrinos (MassiveNuLinRespOn, gravpm.cpp:76-85, 412-435): the PM stops between its forward and inverse
+ * halves, where the reference runs its global_analysis hook (compute_neutrino_power, gravpm.cpp:308-321).
+ *   shq_pm_forward         : the first half on the resident particles - deposit (honouring the type mask below), forward transform, and
+ *                            the raw sums of measure_power_spectrum (as shq_pm_measure_power documents them; shq_pm_download_power returns
+ *                            them whatever shq_pm_measure_power is set to).  Queued on the PM's stream as shq_pm_start queues its PM;
+ *                            shq_pm_download_power joins it.  The density spectrum stays on the device: the context's PENDING spectrum.
+ *   shq_pm_set_mode_factor : table (host, 3 (Nmesh/2)^2 + 1 doubles): T[k2] multiplies every mode of integer k2 of the pending spectrum
+ *                            before the Green's function, (v T) green as potential_transfer does with nufac (gravpm.cpp:412-427); T[0] is
+ *                            not used (the zero mode is removed).  For the pending spectrum only: the finish consumes it.  NULL clears it;
+ *                            a wrong Nmesh is SHQ_ERR_INVALID, no pending spectrum SHQ_ERR_STATE.
+ *   finishing              : with a spectrum pending, the next shq_pm_run or shq_treepm_step does not deposit: Green's function x T, inverse
+ *                            transform, readout (shq_treepm_step then walks as always).  It wants the forward's params, all four fields, or
+ *                            returns SHQ_ERR_STATE.  With shq_pm_measure_power(ctx, 1) it accumulates the P(k) sums of the multiplied
+ *                            density (potential_transfer's; scaling Norm by MtotbyMcdm^2, gravpm.cpp:431-435, stays with the caller).
+ *   discarded by           : shq_drift, a particle upload, and the other users of the mesh - shq_fft_r2c / c2r, shq_pm_apply, shq_pm_start,
+ *                            a slab call of another Nmesh.  The tree walk's mesh scrub (shq_pm_set_mesh_scrub) leaves a pending spectrum alone.
+ * The P(k) sums are accumulated with floating-point atomics, as shq_pm_measure_power's: not bit-reproducible.  Single-GPU PM only. */
+int shq_pm_forward(shq_context *ctx, const shq_pm_params *pm);
+int shq_pm_set_mode_factor(shq_context *ctx, int Nmesh, const double *table);
+/* Deposit type mask (hybrid neutrinos: while hybrid_nu_tracer holds, Type 2 is not deposited, gravpm.cpp:84-85, 459-464): bit t set = particles
+ * of Type t are deposited; the readout still covers every particle (petapm.cpp:1304-1307).  Default SHQ_ALL_TYPES.  Applies to shq_pm_run,
+ * shq_pm_force, shq_pm_start, shq_treepm_step and shq_pm_forward (not to the slab PM).  A mask other than all types with particles uploaded
+ * without their Type (off_type = SHQ_NOFIELD, or shq_particles_set_device) makes those calls return SHQ_ERR_STATE. */
+#define SHQ_ALL_TYPES (-1)
+int shq_pm_set_deposit_types(shq_context *ctx, int typemask);
 /* Debug / parity taps: copy the mesh after deposit (Nmesh^3 doubles, [x][y][z]) and the
  * potential mesh after c2r. Valid after shq_pm_run with keep_meshes set. */
 /* HIP-event durations (ms) of the last shq_pm_run's phases: [0] zero+deposit+convert, [1] r2c,

@@ -334,8 +334,26 @@ def grav_short_tree(ctx, act, pm, tree, AccelStore, rho0, Ti_Current=0, UseGPU=T
     return stats
 
 
-def gravpm_force(ctx, pm, pman, UseGPU=True):
-    capi.check_host(capi.host.shqh_gravpm_force(ctx.h, pman._h, pm["Asmth"], pm["Nmesh"], pm["G"], int(UseGPU)), "gravpm_force")
+def gravpm_force(ctx, pm, pman, UseGPU=True, analysis=None, deposit_types=capi.ALL_TYPES):
+    """analysis(kk, power, nmodes, Norm) -> T: the hook between the PM's forward and inverse halves (petapm's global_analysis,
+    compute_neutrino_power for MassiveNuLinRespOn); it gets the raw P(k) sums of the density and returns T[k2] for k2 = 0 .. 3 (Nmesh/2)^2.
+    deposit_types: the deposit's type mask (bit t = Type t)."""
+    if analysis is None and deposit_types == capi.ALL_TYPES:
+        capi.check_host(capi.host.shqh_gravpm_force(ctx.h, pman._h, pm["Asmth"], pm["Nmesh"], pm["G"], int(UseGPU)), "gravpm_force")
+        return
+
+    def hook(_, nbins, kk, power, nmodes, norm, nmesh, table):
+        try:
+            T = analysis(np.ctypeslib.as_array(kk, (nbins,)).copy(), np.ctypeslib.as_array(power, (nbins,)).copy(),
+                         np.ctypeslib.as_array(nmodes, (nbins,)).copy(), norm)
+            np.ctypeslib.as_array(table, (3 * (nmesh // 2) ** 2 + 1,))[:] = T
+            return 0
+        except Exception:
+            return 1
+
+    fn = capi.GRAVPM_ANALYSIS_FN(hook) if analysis is not None else capi.GRAVPM_ANALYSIS_FN()
+    capi.check_host(capi.host.shqh_gravpm_force_hook(ctx.h, pman._h, pm["Asmth"], pm["Nmesh"], pm["G"], int(UseGPU), fn, None,
+                                                     int(deposit_types)), "gravpm_force")
 
 
 def synth_positions(kind, n, seed=20240601, L=1.0):

@@ -598,6 +598,13 @@ hip.shq_timer_between_ms.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.
 hip.shq_timer_between_ms.restype = C.c_int
 hip.shq_pm_start.argtypes = [_vp, _vp, C.c_double]
 hip.shq_pm_start.restype = C.c_int
+hip.shq_pm_forward.argtypes = [_vp, C.POINTER(PMParams)]
+hip.shq_pm_forward.restype = C.c_int
+hip.shq_pm_set_mode_factor.argtypes = [_vp, C.c_int, _vp]
+hip.shq_pm_set_mode_factor.restype = C.c_int
+hip.shq_pm_set_deposit_types.argtypes = [_vp, C.c_int]
+hip.shq_pm_set_deposit_types.restype = C.c_int
+ALL_TYPES = -1                                     # SHQ_ALL_TYPES
 hip.shq_treepm_last_fused.argtypes = [_vp, C.POINTER(C.c_int)]
 hip.shq_treepm_set_fuse.argtypes = [_vp, C.c_int]
 hip.shq_pm_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 6)]
@@ -673,6 +680,10 @@ host.shqh_make_grav_params.argtypes = [C.c_double, C.c_double, C.c_int, C.c_doub
 host.shqh_grav_short_tree.argtypes = [_vp, _vp, _vp, C.c_double, C.c_int, C.c_double, _vp, C.c_int64, _vp,
                                       C.c_double, C.c_int, C.c_int, C.POINTER(WalkStats)]
 host.shqh_gravpm_force.argtypes = [_vp, _vp, C.c_double, C.c_int, C.c_double, C.c_int]
+# int analysis(userdata, nbins, kk, power, nmodes, Norm, Nmesh, table): gravity.hpp, gravpm_analysis_fn
+GRAVPM_ANALYSIS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int64), C.c_double,
+                                 C.c_int, C.POINTER(C.c_double))
+host.shqh_gravpm_force_hook.argtypes = [_vp, _vp, C.c_double, C.c_int, C.c_double, C.c_int, GRAVPM_ANALYSIS_FN, C.c_void_p, C.c_int]
 host.shqh_synth_positions.argtypes = [C.c_int, C.c_int64, C.c_uint64, C.c_double, _vp]
 host.shqh_synth_positions.restype = None
 host.shqh_synth_positions_range.argtypes = [C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_uint64, C.c_double, _vp]

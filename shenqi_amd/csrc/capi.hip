@@ -403,6 +403,7 @@ extern "C" int shq_particles_upload(shq_context *ctx, const shq_part_view *parts
     SHQ_CHECK(parts->off_pos != SHQ_NOFIELD && parts->off_mass != SHQ_NOFIELD, SHQ_ERR_INVALID, "particle view needs Pos and Mass");
     SHQ_HIP(hipSetDevice(ctx->device));
     SHQ_TRY(shq_join_pm(ctx));
+    shq_pm_discard_spectrum(ctx);
     /* shq_set_inputs_current: the caller vouches that the context holds this very view's particles as they are now */
     if((ctx->inputs_current & SHQ_CURRENT_PARTICLES) && ctx->have_parts && ctx->cur_parts == parts->base && ctx->cur_parts_n == parts->numpart &&
        ctx->numpart == parts->numpart)
@@ -497,6 +498,7 @@ extern "C" int shq_particles_upload(shq_context *ctx, const shq_part_view *parts
     ctx->numpart = n;
     ctx->nlocal = n; /* all particles are this rank's own */
     ctx->have_parts = true;
+    ctx->have_types = parts->off_type != SHQ_NOFIELD;
     ctx->have_tree = false; /* leaf copy refers to the old particles */
     ctx->have_tree_targets = false;
     ctx->tb_built = false;
@@ -873,8 +875,10 @@ extern "C" int shq_particles_set_device(shq_context *ctx, const void *d_posm, in
     ctx->numpart = n;
     ctx->nlocal = nlocal;
     ctx->have_parts = true;
+    ctx->have_types = false; /* every row is Type 1 (fill_u8_kernel above) */
     ctx->have_pm_result = false;
     ctx->pm_prestarted = false;
+    shq_pm_discard_spectrum(ctx);
     return SHQ_OK;
 }
 
@@ -1247,7 +1251,7 @@ extern "C" int shq_pm_run(shq_context *ctx, const shq_pm_params *pm)
 /* The PM reads only the positions (and, when its readout forms OldAcc, FullTreeGravAccel) and writes only the mesh, GravPM, the PM potential
  * and OldAcc: it runs on its own stream behind everything queued so far, and the main stream goes on.  Consumers of its results join it
  * (shq_join_pm). */
-int shq_pm_run_on_pm_stream(shq_context *ctx, const shq_pm_params *pm, bool low_priority)
+int shq_pm_run_on_pm_stream(shq_context *ctx, const shq_pm_params *pm, bool low_priority, bool forward)
 {
     /* low_priority (shq_pm_start): the library's lowest-priority stream, the pair kernel's, idle between two walks.  An FFT pass holds
      * 464 of a SIMD's 512 registers and 141 of a CU's 160 KB of LDS: nothing else starts on a CU while two of its workgroups are resident,
@@ -1258,7 +1262,7 @@ int shq_pm_run_on_pm_stream(shq_context *ctx, const shq_pm_params *pm, bool low_
     SHQ_HIP(hipStreamWaitEvent(ps, ctx->ev_pm_ready, 0));
     hipStream_t main_stream = ctx->stream;
     ctx->stream = ps;
-    const int rc = shq_pm_execute(ctx, pm);
+    const int rc = forward ? shq_pm_execute_forward(ctx, pm) : shq_pm_execute(ctx, pm);
     ctx->stream = main_stream;
     if(rc != SHQ_OK) {
         (void) hipStreamSynchronize(ps);
@@ -1281,6 +1285,7 @@ extern "C" int shq_pm_start(shq_context *ctx, const shq_pm_params *pm, double G)
     SHQ_HIP(hipSetDevice(ctx->device));
     SHQ_TRY(shq_join_pm(ctx));
     SHQ_TRY(shq_walk_check_status(ctx, false));
+    shq_pm_discard_spectrum(ctx); /* a PM of its own: it deposits into the mesh a pending spectrum sits in */
     ctx->readout_oldacc_G = (G > 0 && ctx->numpart > 0 && ctx->treeacc.ptr && ctx->oldacc.ptr) ? G : 0.0;
     const bool oldacc_done = ctx->readout_oldacc_G > 0;
     const int rc = shq_pm_run_on_pm_stream(ctx, pm, true);
@@ -1290,6 +1295,19 @@ extern "C" int shq_pm_start(shq_context *ctx, const shq_pm_params *pm, double G)
     ctx->pm_prestarted_oldacc = oldacc_done;
     ctx->pm_prestarted_nmesh = pm->Nmesh;
     return SHQ_OK;
+}
+
+/* The first half of gravpm_force for a caller with a global_analysis hook (MassiveNuLinRespOn: compute_neutrino_power, gravpm.cpp:76-81):
+ * deposit, forward transform, P(k) sums, queued on the PM's stream as shq_pm_start queues its PM.  shq_pm_download_power joins it; the
+ * spectrum stays pending for shq_pm_set_mode_factor and the finishing shq_pm_run / shq_treepm_step (pm.hip, pm_finish). */
+extern "C" int shq_pm_forward(shq_context *ctx, const shq_pm_params *pm)
+{
+    SHQ_CHECK(ctx && pm, SHQ_ERR_INVALID, "null argument");
+    SHQ_CHECK(ctx->have_parts, SHQ_ERR_STATE, "pm_forward: particles must be uploaded first");
+    SHQ_HIP(hipSetDevice(ctx->device));
+    SHQ_TRY(shq_join_pm(ctx));
+    ctx->pm_prestarted = false;
+    return shq_pm_run_on_pm_stream(ctx, pm, true, true);
 }
 
 /* gravpm_force followed by grav_short_tree for every particle — the force part of a PM step in the reference's own order

@@ -425,6 +425,16 @@ struct shq_context {
     int ps_nbins = 0, ps_bintab_n = 0;
     DevBuf<double> ps_sums;    /* [nbins] power, [nbins] kk, [nbins] modes (u64), norm */
     DevBuf<int32_t> ps_bintab; /* bin of every k2 */
+    /* shq_pm_forward: the density half spectrum of the resident particles, left in `mesh` for the caller's analysis (the neutrino
+     * factor of potential_transfer, gravpm.cpp:412-427) and finished by the next shq_pm_run / shq_treepm_step with these very params */
+    bool pm_spec_pending = false;
+    shq_pm_params pm_spec_params = {};
+    int pm_spec_route = 0;     /* 0: transposing pipeline (layout LX, fft3d.hip), 1: in-place pipeline, 2: hipFFT ([x][y][z'] both) */
+    DevBuf<double> pm_fac;     /* shq_pm_set_mode_factor: T[k2], 3 (Nmesh/2)^2 + 1 entries, for the pending spectrum only */
+    bool pm_fac_set = false;
+    DevBuf<double> pm_fac_one; /* {1.0}: the table of a finish without one */
+    int pm_typemask = -1;      /* shq_pm_set_deposit_types: bit t set = particles of Type t are deposited */
+    bool have_types = false;   /* the resident particles came with their Type (pflags bits 4-7) */
 
     shq_walk_stats last_stats = {};
     int walk_variant = 3;      /* SHQ_WALK_VARIANT: 0 prefetch+leaf4, 1 prefetch+leaf2, 2 leaf4, 3 leaf2 (fastest: no SGPR spills) */
@@ -454,6 +464,12 @@ struct shq_context {
 
 /* capi.hip: make the main stream wait for an outstanding asynchronous PM run */
 int shq_join_pm(shq_context *ctx);
+/* a pending spectrum (shq_pm_forward) and its factor table end when the particles move or another user takes the mesh */
+inline void shq_pm_discard_spectrum(shq_context *ctx)
+{
+    ctx->pm_spec_pending = false;
+    ctx->pm_fac_set = false;
+}
 /* grav_walk.hip */
 /* Device pointer and length of an active list argument of the C-ABI: NULL (all n_all), a host list
  * (uploaded), or one of the SHQ_ACTIVE_RESIDENT / SHQ_SUBLIST_RESIDENT handles. dynamics.hip */
@@ -491,7 +507,8 @@ int shq_launch_grav_walk_ghosts(shq_context *ctx, const shq_grav_params *p, cons
                                 const int32_t *d_qstart, int64_t nq, double *d_acc, double *d_pot, int32_t *d_nint, int update_potential);
 /* pm.hip */
 int shq_pm_execute(shq_context *ctx, const shq_pm_params *pm, bool readout = true);
-int shq_pm_run_on_pm_stream(shq_context *ctx, const shq_pm_params *pm, bool low_priority);
+int shq_pm_execute_forward(shq_context *ctx, const shq_pm_params *pm);
+int shq_pm_run_on_pm_stream(shq_context *ctx, const shq_pm_params *pm, bool low_priority, bool forward = false);
 bool shq_walk_can_fuse_readout(shq_context *ctx, const shq_grav_params *p, const int32_t *d_active, int64_t ntargets, int64_t first);
 bool shq_walk_can_fuse_readout_pre(shq_context *ctx, const shq_grav_params *p, int64_t ntargets);
 void shq_pm_destroy_plans(shq_context *ctx);
@@ -506,6 +523,9 @@ int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bo
                   const double *d_sinctab, double asmth2, double pot_factor);
 int shq_fft3d_run_transposed(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, bool from_i64, double inv_scale,
                              const double *d_sinctab, double asmth2, double pot_factor);
+int shq_fft3d_transposed_part(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, int part, bool from_i64, double inv_scale,
+                              const double *d_sinctab, double asmth2, double pot_factor, const double *d_modefac, int fac_mask,
+                              const int32_t *d_bintab, double *d_ps);
 int shq_fft3d_run_slab(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale,
                        const double *d_sinctab, double asmth2, double pot_factor, int nslab, int y0);
 int shq_fft3d_run_slab_packed(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale,

@@ -504,6 +504,7 @@ extern "C" int shq_drift(shq_context *ctx, double ddrift, double BoxSize, const 
     /* (the tree-order target list survives a drift: it is an order of the same particles, refreshed by the tree builds every few steps) */
     ctx->have_pm_result = false;
     ctx->pm_prestarted = false;
+    shq_pm_discard_spectrum(ctx);
     SHQ_CHECK(h_err != 1, SHQ_ERR_INVALID, "drift: a gas particle reached Hsml <= 0 (drift.cpp:61-63)");
     SHQ_CHECK(h_err != 2, SHQ_ERR_INVALID, "drift: a particle position is not finite (drift.cpp:72-75)");
     SHQ_CHECK(h_err != 3, SHQ_ERR_INVALID, "drift: a black hole would jump further than 0.1 BoxSize to its potential minimum (drift.cpp:40-48)");

@@ -39,8 +39,9 @@ __host__ __device__ constexpr int fft_threads(int N) { return N > 768 ? 512 : 25
  * to Nmesh 768 (a tile + its 48 twiddles take 53 KB of the CU's 160, and the passes fit 168 registers: 3-4 % faster than two in a
  * same-box A/B); the X pass keeps its Green's function factors in LDS and two workgroups (with the factors read from global memory and
  * three workgroups it ran 2.44 against 2.09 ms); above 768 the workgroups have eight waves and the bound stays at two per SIMD
- * (four - a 128-register budget - made the 1200 mesh spill: 208 ms for its five passes instead of 44) */
-__host__ __device__ constexpr int fft_tile_waves(int N, int MODE) { return (MODE != 2 && N <= 768) ? 3 : 2; }
+ * (four - a 128-register budget - made the 1200 mesh spill: 208 ms for its five passes instead of 44).  The two halves of the X pass
+ * (MODES 3 and 4, fft_t_tile) keep the fused pass's two: their P(k) histogram takes 3 N doubles of LDS beside the tile */
+__host__ __device__ constexpr int fft_tile_waves(int N, int MODE) { return ((MODE == 0 || MODE == 1) && N <= 768) ? 3 : 2; }
 #ifndef FFT_T
 #define FFT_T fft_threads(N)
 #endif
@@ -454,6 +455,13 @@ struct GreenArgs {
     double2 *alt;
     int nyl;
     long long qstride, alt_outer;
+    /* the split X pass of the transposing pipeline (fft_t_tile MODES 3 and 4): the caller's factor by integer k2 (entry k2 & fac_mask:
+     * fac_mask = 0 with a one-entry table {1.0} when there is none), and the P(k) sums of powerspectrum_add_mode (ps = null: none) -
+     * ps[0, N) power, [N, 2N) kk, [2N, 3N) modes (u64), ps[3N] norm; the bin of k2 is bintab[k2] (pm.hip, pm_power_prepare) */
+    const double *modefac;
+    int fac_mask;
+    const int32_t *bintab;
+    double *ps;
 };
 
 /* PK 0: in place.  PK 1: results stored into ga.alt in the packed (send) layout.  PK 2: input loaded from ga.alt in that layout. */
@@ -730,7 +738,35 @@ __global__ __launch_bounds__(FFT_T) void fft_t_z_inv(const double2 *__restrict__
 #undef FFT_FETCH
 }
 
-/* Y and X passes on contiguous tiles.  Tile t = (o, zb), o = t / nzb: N rows of 4 columns at src + t * 4 N.  MODE as in fft_pass_strided.
+/* powerspectrum_add_mode (gravpm.cpp:323-356) of one mode into a workgroup's LDS histogram [3][N]: the operations of pm_power_kernel
+ * (pm.hip).  The zero mode sets Norm; pad columns z > N / 2 are not modes. */
+template <int N>
+__device__ __forceinline__ void pk_add(double *hist, const GreenArgs &ga, double2 v, int x, int y, int z, int k2)
+{
+    if(z > N / 2)
+        return;
+    const double m = v.x * v.x + v.y * v.y;
+    if(k2 == 0) {
+        ga.ps[3 * N] = m;
+        return;
+    }
+    const int kint = ga.bintab[k2];
+    if(kint >= N)
+        return;
+    const double f = ga.sinctab[x] * ga.sinctab[y] * ga.sinctab[z];
+    const double w = (z == 0 || z == N / 2) ? 1.0 : 2.0;
+    atomicAdd(&hist[kint], w * m * f * f);
+    atomicAdd(&hist[N + kint], w * sqrt((double) k2));
+    atomicAdd(&hist[2 * N + kint], w);
+}
+
+/* Y and X passes on contiguous tiles.  Tile t = (o, zb), o = t / nzb: N rows of 4 columns at src + t * 4 N.  MODE as in fft_pass_strided,
+ * and the fused X pass (MODE 2) split in two for a caller that needs the density spectrum between them (shq_pm_forward):
+ *   MODE 3: X forward, the spectrum written back as the contiguous tile it came from (LX, dst = src); with ga.ps the P(k) sums of the
+ *           density as the tile is stored.
+ *   MODE 4: reads that tile and multiplies every mode by T[k2], then by MODE 2's Green's factor with MODE 2's arithmetic - (v T) green,
+ *           potential_transfer's order (gravpm.cpp:412-443) - as it lands in LDS; with ga.ps the P(k) sums of v T; then X inverse.
+ *           T = 1 gives MODE 2's bits: v * 1.0 is exact.  T[k2] is fetched with the tile's prefetch.
  * SCATTER: row i of the result goes to dst + ((i * nzb + zb) * N + o) * 4 (the other layout: a 64-byte piece); otherwise the tile is
  * written back where it came from (dst may be src). */
 template <int N, int MODE, bool SCATTER>
@@ -742,14 +778,23 @@ __global__ __launch_bounds__(FFT_T, fft_tile_waves(N, MODE)) void fft_t_tile(con
     constexpr int E = (FFT_C * N + FFT_T - 1) / FFT_T;
     constexpr bool EXACT = E * FFT_T == FFT_C * N;
     double2 *Wl = lds_twiddles<N>(buf, W);
-    double *gax = reinterpret_cast<double *>(Wl + fft_twn(N)); /* MODE 2: the Green's function's per-axis factors (fft_gax_kernel) in LDS */
-    if(MODE == 2) {
+    double *gax = reinterpret_cast<double *>(Wl + fft_twn(N)); /* MODES 2, 4: the Green's function's per-axis factors (fft_gax_kernel) in LDS */
+    if(MODE == 2 || MODE == 4) {
         for(int i = threadIdx.x; i < N; i += FFT_T)
             gax[i] = ga.gaxg[i];
         __syncthreads();
     }
+    /* MODES 3, 4 with ga.ps: the workgroup's P(k) histogram [3][N] behind the tables, flushed once when the workgroup ends */
+    double *hist = MODE == 4 ? gax + N : gax;
+    const bool pk = (MODE == 3 || MODE == 4) && ga.ps;
+    if(pk) {
+        for(int i = threadIdx.x; i < 3 * N; i += FFT_T)
+            hist[i] = 0;
+        __syncthreads();
+    }
     const unsigned vb = xcd_block(blockIdx.x, gridDim.x, xcdk);
     double prx[E], pry[E];
+    double tfac[MODE == 4 ? E : 1]; /* MODE 4: T[k2] of the prefetched tile's modes */
 #define FFT_FETCH(T_)                                                                            \
     {                                                                                            \
         const double2 *b_ = src + (long long) (T_) * (FFT_C * N);                                \
@@ -763,24 +808,68 @@ __global__ __launch_bounds__(FFT_T, fft_tile_waves(N, MODE)) void fft_t_tile(con
             }                                                                                    \
         }                                                                                        \
     }
+    /* MODE 4: T[k2] of tile T_'s modes, gathered after the FFT stages (held across them, these registers made the pass spill) so that
+     * the scattered stores of the current tile hide the gather.  A pad column (z > N / 2) reads entry 0: k2 stays inside the table */
+#define FFT_TFETCH(T_)                                                                           \
+    if(MODE == 4) {                                                                              \
+        const int o_ = (T_) / nzb, zb_ = (T_) - o_ * nzb, y_ = ga.y0 + o_, ky_ = y_ <= N / 2 ? y_ : y_ - N; \
+        _Pragma("unroll") for(int i = 0; i < E; i++)                                             \
+        {                                                                                        \
+            const int e_ = threadIdx.x + i * FFT_T, e = (EXACT || e_ < FFT_C * N) ? e_ : 0;     \
+            const int x_ = e / FFT_C, z_ = zb_ * FFT_C + e % FFT_C, kx_ = x_ <= N / 2 ? x_ : x_ - N; \
+            const int k2_ = z_ <= N / 2 ? kx_ * kx_ + ky_ * ky_ + z_ * z_ : 0;                   \
+            tfac[i] = ga.modefac[k2_ & ga.fac_mask];                                             \
+        }                                                                                        \
+    }
     int t = (int) vb;
     if(t >= ntot)
         return;
     FFT_FETCH(t)
+    FFT_TFETCH(t)
     while(true) {
+        const int o = t / nzb, zb = t - o * nzb;
+        if(MODE == 4) {
+            /* (v T) green: the tile lands multiplied by T, then a rolled sweep over LDS takes its P(k) and applies the fused pass's Green's
+             * factor (below) - the factor's division unrolled over the landing took the pass to 190-256 VGPRs */
+            const int y = ga.y0 + o, z0 = zb * FFT_C;
+            const int ky = y <= N / 2 ? y : y - N;
 #pragma unroll
-        for(int i = 0; i < E; i++) {
-            const int e = threadIdx.x + i * FFT_T;
-            if(EXACT || e < FFT_C * N)
-                buf[(e % FFT_C) * LS + lx<N>(e / FFT_C)] = make_double2(prx[i], pry[i]);
+            for(int i = 0; i < E; i++) {
+                const int e = threadIdx.x + i * FFT_T;
+                if(EXACT || e < FFT_C * N) {
+                    const int x = e / FFT_C, z = z0 + e % FFT_C;
+                    const int kx = x <= N / 2 ? x : x - N;
+                    const double tv = (z <= N / 2 && kx * kx + ky * ky + z * z != 0) ? tfac[i] : 1.0; /* T[0] is not used: the zero mode is removed */
+                    buf[(e % FFT_C) * LS + lx<N>(x)] = make_double2(prx[i] * tv, pry[i] * tv);
+                }
+            }
+            __syncthreads();
+            const double gy = gax[y] * ga.pot_factor, ky2 = (double) ky * (double) ky;
+            for(int e = threadIdx.x; e < FFT_C * N; e += FFT_T) {
+                const int x = e / FFT_C, col = e % FFT_C, z = z0 + col;
+                const int kx = x <= N / 2 ? x : x - N;
+                double2 *p = buf + col * LS + lx<N>(x);
+                const double2 v = *p;
+                if(pk)
+                    pk_add<N>(hist, ga, v, x, y, z, kx * kx + ky * ky + z * z);
+                const double k2 = (double) kx * (double) kx + (ky2 + (double) z * (double) z);
+                const double fac = (k2 == 0.0 || z > N / 2) ? 0.0 : gax[x] * gy * gax[z] / k2;
+                *p = make_double2(v.x * fac, v.y * fac);
+            }
+        } else {
+#pragma unroll
+            for(int i = 0; i < E; i++) {
+                const int e = threadIdx.x + i * FFT_T;
+                if(EXACT || e < FFT_C * N)
+                    buf[(e % FFT_C) * LS + lx<N>(e / FFT_C)] = make_double2(prx[i], pry[i]);
+            }
         }
         __syncthreads();
         const int tn = t + (int) gridDim.x;
         const bool more = tn < ntot;
         const int tf = more ? tn : t;
         FFT_FETCH(tf)
-        const int o = t / nzb, zb = t - o * nzb;
-        if(MODE == 0)
+        if(MODE == 0 || MODE == 3)
             fft_lines<N, -1>(buf, Wl);
         if(MODE == 2) { /* potential_transfer as in fft_pass_strided: line index = kx, o = ky, columns z' = 4 zb .. 4 zb + 3 */
             const int y = ga.y0 + o, z0 = zb * FFT_C;
@@ -796,9 +885,23 @@ __global__ __launch_bounds__(FFT_T, fft_tile_waves(N, MODE)) void fft_t_tile(con
             fft_lines<N, -1>(buf, Wl, green);
             fft_lines<N, +1>(buf, Wl);
         }
-        if(MODE == 1)
+        if(MODE == 1 || MODE == 4)
             fft_lines<N, +1>(buf, Wl);
-        if(SCATTER) {
+        FFT_TFETCH(tf)
+        if(MODE == 3) { /* the spectrum back where the tile came from; the density's P(k) on the way */
+            double2 *ob = dst + (long long) t * (FFT_C * N);
+            const int y = ga.y0 + o;
+            const int ky = y <= N / 2 ? y : y - N;
+            for(int e = threadIdx.x; e < FFT_C * N; e += FFT_T) {
+                const int x = e / FFT_C, z = zb * FFT_C + e % FFT_C;
+                const double2 v = buf[(e % FFT_C) * LS + lx<N>(x)];
+                ob[e] = v;
+                if(pk) {
+                    const int kx = x <= N / 2 ? x : x - N;
+                    pk_add<N>(hist, ga, v, x, y, z, kx * kx + ky * ky + z * z);
+                }
+            }
+        } else if(SCATTER) {
             double2 *ob = dst + ((long long) zb * N + o) * FFT_C;
             const long long rs = (long long) nzb * N * FFT_C;
             for(int e = threadIdx.x; e < FFT_C * N; e += FFT_T) {
@@ -816,6 +919,17 @@ __global__ __launch_bounds__(FFT_T, fft_tile_waves(N, MODE)) void fft_t_tile(con
         t = tn;
     }
 #undef FFT_FETCH
+#undef FFT_TFETCH
+    if(pk) { /* one atomic per non-empty bin, as pm_power_kernel */
+        __syncthreads();
+        unsigned long long *nmodes = reinterpret_cast<unsigned long long *>(ga.ps + 2 * N);
+        for(int i = threadIdx.x; i < N; i += FFT_T)
+            if(hist[2 * N + i] != 0) {
+                atomicAdd(&ga.ps[i], hist[i]);
+                atomicAdd(&ga.ps[N + i], hist[N + i]);
+                atomicAdd(&nmodes[i], (unsigned long long) hist[2 * N + i]);
+            }
+    }
 }
 
 /* exp(-k_i^2 asmth2) sinctab[i]^2 per mesh index: the expression the in-place X pass fills its LDS table with */
@@ -829,26 +943,30 @@ __global__ void fft_gax_kernel(int N, const double *__restrict__ sinctab, double
     }
 }
 
+/* part 0: forward, potential_transfer and inverse (five passes); 1: Z fwd, Y fwd and the X forward half (MODE 3) - the half spectrum is left
+ * in d_mesh in the layout LX; 2: from there the X inverse half (MODE 4), Y inv and Z inv */
 template <int N>
-int run_t(shq_context *ctx, double *d_mesh, double *d_scratch, int zp, bool from_i64, double inv_scale, const GreenArgs &ga)
+int run_t(shq_context *ctx, double *d_mesh, double *d_scratch, int zp, bool from_i64, double inv_scale, const GreenArgs &ga, int part)
 {
     const double2 *W = reinterpret_cast<const double2 *>(ctx->fft_tw.ptr);
     constexpr size_t lds = sizeof(double2) * (FFT_C * fft_ls(N) + fft_twn(N)), lds_x = lds + sizeof(double) * N; /* X pass: + its factor table */
+    constexpr size_t lds_hist = sizeof(double) * 3 * N;                                                          /* MODES 3, 4: + the P(k) histogram */
     const int ztot = (int) (((long long) N * N) / (2 * FFT_C));
     const int zpc = zp / 2, nzb = zpc / FFT_C;
     const int stot = N * nzb;
     double2 *A = reinterpret_cast<double2 *>(d_mesh), *B = reinterpret_cast<double2 *>(d_scratch);
     hipStream_t s = ctx->stream;
-    static unsigned res_z = 0, res_s = 0, res_x = 0;
+    static unsigned res_z = 0, res_s = 0, res_x = 0, res_x3 = 0, res_x4 = 0;
     if(res_s == 0) {
-        const void *fns[6] = {(const void *) fft_t_z_fwd<N, true>, (const void *) fft_t_z_fwd<N, false>, (const void *) fft_t_z_inv<N>,
-                              (const void *) fft_t_tile<N, 0, true>, (const void *) fft_t_tile<N, 2, true>, (const void *) fft_t_tile<N, 1, false>};
+        const void *fns[8] = {(const void *) fft_t_z_fwd<N, true>, (const void *) fft_t_z_fwd<N, false>, (const void *) fft_t_z_inv<N>,
+                              (const void *) fft_t_tile<N, 0, true>, (const void *) fft_t_tile<N, 2, true>, (const void *) fft_t_tile<N, 1, false>,
+                              (const void *) fft_t_tile<N, 3, false>, (const void *) fft_t_tile<N, 4, true>};
         int ncu = 0;
         if(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || ncu < 1)
             ncu = 256;
-        unsigned occ[6];
-        for(int i = 0; i < 6; i++) {
-            const size_t l = i == 4 ? lds_x : lds;
+        unsigned occ[8];
+        for(int i = 0; i < 8; i++) {
+            const size_t l = i == 4 ? lds_x : (i == 6 ? lds + lds_hist : (i == 7 ? lds_x + lds_hist : lds));
             if(l > 48 * 1024)
                 SHQ_HIP(hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int) l));
             int per_cu = 0;
@@ -860,6 +978,8 @@ int run_t(shq_context *ctx, double *d_mesh, double *d_scratch, int zp, bool from
         res_z = res_z < occ[2] ? res_z : occ[2];
         res_s = occ[3] < occ[5] ? occ[3] : occ[5];
         res_x = occ[4];
+        res_x3 = occ[6];
+        res_x4 = occ[7];
     }
     const unsigned gmul = getenv("SHQ_FFT_GRID_MUL") ? (unsigned) atoi(getenv("SHQ_FFT_GRID_MUL")) : 8u;
     auto grid = [&](int tot, unsigned resident) {
@@ -868,14 +988,23 @@ int run_t(shq_context *ctx, double *d_mesh, double *d_scratch, int zp, bool from
     };
     const dim3 gz = grid(ztot, res_z), gs = grid(stot, res_s), gx = grid(stot, res_x);
     const unsigned xcdk = getenv("SHQ_FFT_XCD_K") ? (unsigned) atoi(getenv("SHQ_FFT_XCD_K")) : 8u;
-    if(from_i64)
-        fft_t_z_fwd<N, true><<<gz, dim3(FFT_T), lds, s>>>(d_mesh, B, ztot, zp, W, inv_scale);
+    if(part != 2) {
+        if(from_i64)
+            fft_t_z_fwd<N, true><<<gz, dim3(FFT_T), lds, s>>>(d_mesh, B, ztot, zp, W, inv_scale);
+        else
+            fft_t_z_fwd<N, false><<<gz, dim3(FFT_T), lds, s>>>(d_mesh, B, ztot, zp, W, 1.0);
+        fft_t_tile<N, 0, true><<<gs, dim3(FFT_T), lds, s>>>(B, A, nzb, stot, W, ga, xcdk);
+    }
+    if(part == 0)
+        fft_t_tile<N, 2, true><<<gx, dim3(FFT_T), lds_x, s>>>(A, B, nzb, stot, W, ga, xcdk);
+    else if(part == 1)
+        fft_t_tile<N, 3, false><<<grid(stot, res_x3), dim3(FFT_T), lds + (ga.ps ? lds_hist : 0), s>>>(A, A, nzb, stot, W, ga, xcdk);
     else
-        fft_t_z_fwd<N, false><<<gz, dim3(FFT_T), lds, s>>>(d_mesh, B, ztot, zp, W, 1.0);
-    fft_t_tile<N, 0, true><<<gs, dim3(FFT_T), lds, s>>>(B, A, nzb, stot, W, ga, xcdk);
-    fft_t_tile<N, 2, true><<<gx, dim3(FFT_T), lds_x, s>>>(A, B, nzb, stot, W, ga, xcdk);
-    fft_t_tile<N, 1, false><<<gs, dim3(FFT_T), lds, s>>>(B, B, nzb, stot, W, ga, xcdk);
-    fft_t_z_inv<N><<<gz, dim3(FFT_T), lds, s>>>(B, d_mesh, ztot, zp, W);
+        fft_t_tile<N, 4, true><<<grid(stot, res_x4), dim3(FFT_T), lds_x + (ga.ps ? lds_hist : 0), s>>>(A, B, nzb, stot, W, ga, xcdk);
+    if(part != 1) {
+        fft_t_tile<N, 1, false><<<gs, dim3(FFT_T), lds, s>>>(B, B, nzb, stot, W, ga, xcdk);
+        fft_t_z_inv<N><<<gz, dim3(FFT_T), lds, s>>>(B, d_mesh, ztot, zp, W);
+    }
     SHQ_HIP(hipGetLastError());
     return SHQ_OK;
 }
@@ -1047,6 +1176,17 @@ static int ensure_twiddles(shq_context *ctx, int N)
 int shq_fft3d_run_transposed(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, bool from_i64, double inv_scale,
                              const double *d_sinctab, double asmth2, double pot_factor)
 {
+    return shq_fft3d_transposed_part(ctx, d_mesh, d_scratch, N, zp, 0, from_i64, inv_scale, d_sinctab, asmth2, pot_factor, nullptr, 0, nullptr,
+                                     nullptr);
+}
+
+/* the same in two halves (part 1: forward, the spectrum left in d_mesh; part 2: T, potential_transfer and inverse) - run_t.  modefac / fac_mask,
+ * bintab and ps as in GreenArgs: part 2 needs a factor table (at least the one entry {1.0} with fac_mask = 0) */
+int shq_fft3d_transposed_part(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, int part, bool from_i64, double inv_scale,
+                              const double *d_sinctab, double asmth2, double pot_factor, const double *d_modefac, int fac_mask,
+                              const int32_t *d_bintab, double *d_ps)
+{
+    SHQ_CHECK(part >= 0 && part <= 2 && (part != 2 || d_modefac) && (!d_ps || d_bintab), SHQ_ERR_INVALID, "fft3d: bad part arguments");
     SHQ_CHECK(shq_fft3d_supported(N) && N % (2 * FFT_C) == 0, SHQ_ERR_INVALID, "fft3d: unsupported mesh size %d", N);
     SHQ_CHECK(zp == shq_fft3d_pitch(N) && d_mesh && d_scratch && d_mesh != d_scratch, SHQ_ERR_INVALID, "fft3d: bad pitch or scratch mesh");
     SHQ_TRY(ensure_twiddles(ctx, N));
@@ -1058,6 +1198,10 @@ int shq_fft3d_run_transposed(shq_context *ctx, double *d_mesh, double *d_scratch
     ga.alt = nullptr;
     ga.nyl = 1;
     ga.qstride = ga.alt_outer = 0;
+    ga.modefac = d_modefac;
+    ga.fac_mask = fac_mask;
+    ga.bintab = d_bintab;
+    ga.ps = d_ps;
     if(ctx->fft_gax_n != N || ctx->fft_gax_asmth2 != asmth2 || ctx->fft_gax_src != d_sinctab) {
         SHQ_TRY(ctx->fft_gax.reserve((size_t) N));
         fft_gax_kernel<<<dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, ctx->stream>>>(N, d_sinctab, asmth2, ctx->fft_gax.ptr);
@@ -1067,7 +1211,7 @@ int shq_fft3d_run_transposed(shq_context *ctx, double *d_mesh, double *d_scratch
         ctx->fft_gax_src = d_sinctab;
     }
     ga.gaxg = ctx->fft_gax.ptr;
-#define SHQ_FFT_CASE(NN) case NN: return run_t<NN>(ctx, d_mesh, d_scratch, zp, from_i64, inv_scale, ga)
+#define SHQ_FFT_CASE(NN) case NN: return run_t<NN>(ctx, d_mesh, d_scratch, zp, from_i64, inv_scale, ga, part)
     switch(N) {
         SHQ_FFT_CASE(16); SHQ_FFT_CASE(24); SHQ_FFT_CASE(32); SHQ_FFT_CASE(40); SHQ_FFT_CASE(48); SHQ_FFT_CASE(64);
         SHQ_FFT_CASE(80); SHQ_FFT_CASE(96); SHQ_FFT_CASE(128); SHQ_FFT_CASE(192); SHQ_FFT_CASE(256); SHQ_FFT_CASE(384);
@@ -1110,6 +1254,10 @@ int shq_fft3d_run_slab_packed(shq_context *ctx, double *d_mesh, int N, int zp, i
     ga.alt = reinterpret_cast<double2 *>(d_packed);
     ga.nyl = 1;
     ga.qstride = ga.alt_outer = 0;
+    ga.modefac = nullptr;
+    ga.fac_mask = 0;
+    ga.bintab = nullptr;
+    ga.ps = nullptr;
     if(stage == 13 || stage == 14) {
         SHQ_CHECK(d_packed && nranks >= 1 && N % nranks == 0, SHQ_ERR_INVALID, "fft3d: packed stages need a buffer and a rank count that divides the mesh");
         ga.nyl = N / nranks;

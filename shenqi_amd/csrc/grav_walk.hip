@@ -1483,9 +1483,11 @@ int shq_launch_grav_walk(shq_context *ctx, const shq_grav_params *p, const int32
             dyn_lds = sizeof(double4) * SHQ_LEAF_RING * 8;
     }
     /* clear the PM mesh for the next deposit in this walk's shadow: the last shq_pm_run is through with it (same stream), nothing
-     * else is known to want it (pm_keep copies what it keeps), and the walk is large enough for a task's share to be a few stores */
+     * else is known to want it (pm_keep copies what it keeps), and the walk is large enough for a task's share to be a few stores.
+     * Not while the mesh holds a pending spectrum (shq_pm_forward): the walk between forward and finish of a resident step is this one */
     bool scrubbed = false, swap_meshes = false;
-    if(ctx->pm_scrub && !stats && variant == 3 && ctx->mesh.ptr && ctx->mesh_words > 0 && !ctx->mesh_zeroed && !ctx->pm_overlap) {
+    if(ctx->pm_scrub && !stats && variant == 3 && ctx->mesh.ptr && ctx->mesh_words > 0 && !ctx->mesh_zeroed && !ctx->pm_overlap &&
+       !ctx->pm_spec_pending) {
         const long long n16 = (long long) (ctx->mesh_words / 2);
         const long long per = ((n16 + nwaves - 1) / nwaves + 63) / 64 * 64;
         if(ctx->mesh_words % 2 == 0 && per <= 4096) {

@@ -61,7 +61,8 @@ __global__ void pm_zero_kernel(unsigned long long *mesh, size_t n)
 
 __global__ __launch_bounds__(256) void pm_deposit_kernel(const double4 *__restrict__ posm, const uint8_t *__restrict__ pflags,
                                                          long long n, unsigned long long *mesh, int N, int zp, double cell,
-                                                         double scale, int xshift, int nxalloc, int *oob, unsigned xcdk)
+                                                         double scale, int xshift, int nxalloc, int *oob, unsigned xcdk,
+                                                         unsigned typemask)
 {
     __shared__ unsigned long long tile[DEP_T * DEP_T * DEP_T];
     __shared__ int s_min[3], s_max[3];
@@ -80,7 +81,8 @@ __global__ __launch_bounds__(256) void pm_deposit_kernel(const double4 *__restri
 #pragma unroll
     for(int j = 0; j < DEP_PPT; j++) {
         const long long i = base + (long long) j * 256 + tid;
-        ok[j] = (i < n) && !(pflags && (pflags[i] & 2)); /* Swallowed: RegionInd = -2, gravpm.cpp:176-178 */
+        /* Swallowed: RegionInd = -2, gravpm.cpp:176-178; a Type outside typemask: hybrid_nu_gravpm_is_active, gravpm.cpp:84-85, 459-464 */
+        ok[j] = (i < n) && !(pflags && ((pflags[i] & 2) || !((typemask >> (pflags[i] >> 4)) & 1u)));
         mass[j] = 0;
         if(ok[j]) {
             const double4 p = posm[i];
@@ -210,7 +212,7 @@ __global__ void pm_convert_kernel(double *mesh, size_t n, double inv_scale)
 
 /* potential_transfer, gravpm.cpp:378-444, on the [x][y][z'] half spectrum */
 __global__ __launch_bounds__(256) void pm_green_kernel(double2 *cmesh, int N, int Nc, int zpc, const double *__restrict__ sinctab,
-                                                       double asmth2, double pot_factor)
+                                                       double asmth2, double pot_factor, const double *__restrict__ T = nullptr)
 {
     const size_t total = (size_t) N * N * Nc;
     size_t ip = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -230,6 +232,11 @@ __global__ __launch_bounds__(256) void pm_green_kernel(double2 *cmesh, int N, in
         v.x = 0;
         v.y = 0;
     } else {
+        if(T) { /* shq_pm_set_mode_factor: (v T) green, potential_transfer's order (gravpm.cpp:412-443) */
+            const double t = T[k2];
+            v.x *= t;
+            v.y *= t;
+        }
         double f = 1.0;
         const double smth = exp(-(double) k2 * asmth2) / (double) k2;
         f *= sinctab[x];
@@ -427,20 +434,41 @@ namespace {
  * Each workgroup histograms in LDS and flushes with one atomic per non-empty bin. */
 __global__ __launch_bounds__(256) void pm_power_kernel(const double2 *__restrict__ cmesh, int N, int Nc, int zpc, const double *__restrict__ sinctab,
                                                        const int32_t *__restrict__ bintab, int nbins, double *power, double *kk,
-                                                       unsigned long long *nmodes, double *norm)
+                                                       unsigned long long *nmodes, double *norm, const double *__restrict__ T = nullptr,
+                                                       int nzb = 0)
 {
     extern __shared__ double hist[]; /* [3][nbins]: power, kk, modes */
     for(int i = threadIdx.x; i < 3 * nbins; i += blockDim.x)
         hist[i] = 0;
     __syncthreads();
-    const size_t total = (size_t) N * N * Nc;
+    /* nzb > 0: the spectrum in the transposing pipeline's layout LX = [y][zb][x][4] (shq_pm_forward); T: the modes multiplied by T[k2] first */
+    const size_t total = nzb > 0 ? (size_t) N * nzb * N * 4 : (size_t) N * N * Nc;
     for(size_t ip = (size_t) blockIdx.x * blockDim.x + threadIdx.x; ip < total; ip += (size_t) gridDim.x * blockDim.x) {
-        const int z = (int) (ip % Nc);
-        const size_t xy = ip / Nc;
-        const int y = (int) (xy % N), x = (int) (xy / N);
+        int x, y, z;
+        size_t at;
+        if(nzb > 0) {
+            const size_t r = (ip >> 2) / N;
+            x = (int) ((ip >> 2) % N);
+            y = (int) (r / nzb);
+            z = 4 * (int) (r % nzb) + (int) (ip & 3);
+            at = ip;
+            if(z >= Nc)
+                continue;
+        } else {
+            z = (int) (ip % Nc);
+            const size_t xy = ip / Nc;
+            y = (int) (xy % N);
+            x = (int) (xy / N);
+            at = xy * (size_t) zpc + z;
+        }
         const int kx = x <= N / 2 ? x : x - N, ky = y <= N / 2 ? y : y - N, kz = z;
         const long long k2 = (long long) kx * kx + (long long) ky * ky + (long long) kz * kz;
-        const double2 v = cmesh[xy * (size_t) zpc + z];
+        double2 v = cmesh[at];
+        if(T && k2 != 0) {
+            const double t = T[k2];
+            v.x *= t;
+            v.y *= t;
+        }
         const double m = v.x * v.x + v.y * v.y;
         if(k2 == 0) {
             *norm = m;
@@ -465,7 +493,8 @@ __global__ __launch_bounds__(256) void pm_power_kernel(const double2 *__restrict
     }
 }
 
-int pm_measure_power(shq_context *ctx, int N, int zpc)
+/* the bin table of Nmesh N and the sums zeroed on the stream */
+int pm_power_prepare(shq_context *ctx, int N)
 {
     const int nbins = N; /* powerspectrum_alloc(pm->ps, pm->Nmesh, ...), gravpm.cpp:207 */
     const long long k2max = 3ll * (N / 2) * (N / 2);
@@ -480,53 +509,184 @@ int pm_measure_power(shq_context *ctx, int N, int zpc)
     }
     SHQ_TRY(ctx->ps_sums.reserve(3 * (size_t) nbins + 1));
     SHQ_HIP(hipMemsetAsync(ctx->ps_sums.ptr, 0, sizeof(double) * (3 * (size_t) nbins + 1), ctx->stream));
+    ctx->ps_nbins = nbins;
+    ctx->have_power = true;
+    return SHQ_OK;
+}
+
+/* the sums of the half spectrum in the mesh: pitch zpc ([x][y][z']), or nzb > 0 (layout LX); T (may be null) multiplies the modes first */
+int pm_power_sweep(shq_context *ctx, int N, int zpc, const double *T = nullptr, int nzb = 0)
+{
+    const int nbins = N;
     double *power = ctx->ps_sums.ptr, *kk = power + nbins, *norm = power + 3 * nbins;
     unsigned long long *nmodes = reinterpret_cast<unsigned long long *>(power + 2 * nbins);
     const size_t lds = sizeof(double) * 3 * nbins;
     if(lds > 48 * 1024)
         SHQ_HIP(hipFuncSetAttribute((const void *) pm_power_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
     pm_power_kernel<<<dim3(2048), dim3(256), lds, ctx->stream>>>((const double2 *) ctx->mesh.ptr, N, N / 2 + 1, zpc, ctx->sinctab.ptr,
-                                                                ctx->ps_bintab.ptr, nbins, power, kk, nmodes, norm);
+                                                                ctx->ps_bintab.ptr, nbins, power, kk, nmodes, norm, T, nzb);
     SHQ_HIP(hipGetLastError());
-    ctx->ps_nbins = nbins;
-    ctx->have_power = true;
     return SHQ_OK;
+}
+
+int pm_measure_power(shq_context *ctx, int N, int zpc)
+{
+    SHQ_TRY(pm_power_prepare(ctx, N));
+    return pm_power_sweep(ctx, N, zpc);
 }
 
 } // namespace
 
-int shq_pm_execute(shq_context *ctx, const shq_pm_params *pm, bool readout)
+namespace {
+
+/* every Type deposited (4 bits of Type in pflags) */
+bool pm_all_types(int mask) { return (mask & 0xffff) == 0xffff; }
+
+/* SHQ_PM_PK_SWEEP=1 (A/B knob): on the transposing pipeline the P(k) sums of shq_pm_forward / its finish come from a sweep over the
+ * spectrum (pm_power_kernel) instead of the histogram inside the X passes (fft_t_tile MODES 3, 4) */
+bool pm_pk_sweep()
+{
+    static const bool v = getenv("SHQ_PM_PK_SWEEP") && atoi(getenv("SHQ_PM_PK_SWEEP")) != 0;
+    return v;
+}
+
+/* the scratch mesh of the transposing pipeline, or null when the in-place pipeline runs (any = true: whatever the knob says) */
+double *pm_scratch(shq_context *ctx, int N, int zp, bool any = false)
+{
+    static const size_t scratch_off = getenv("SHQ_FFT_SCRATCH_OFFSET") ? (size_t) atoll(getenv("SHQ_FFT_SCRATCH_OFFSET")) / 8 : 0; /* probe */
+    if((any || ctx->fft_transposed) && zp == shq_fft3d_pitch(N) && ctx->mesh_alt.reserve((size_t) N * N * zp + scratch_off) == SHQ_OK)
+        return ctx->mesh_alt.ptr + scratch_off;
+    return nullptr;
+}
+
+/* zero the mesh (unless the last walk did) and deposit the particles of the deposit's types; the density copy of shq_pm_set_debug */
+int pm_deposit(shq_context *ctx, const shq_pm_params *pm)
 {
     SHQ_CHECK(ctx->have_parts, SHQ_ERR_STATE, "pm: particles must be uploaded first");
     SHQ_CHECK(pm->BoxSize > 0 && pm->Asmth > 0, SHQ_ERR_INVALID, "pm params: BoxSize and Asmth must be > 0");
+    SHQ_CHECK(pm_all_types(ctx->pm_typemask) || ctx->have_types, SHQ_ERR_STATE,
+              "pm: deposit type mask 0x%x, but the particles were uploaded without their Type (off_type)", (unsigned) ctx->pm_typemask);
     const int N = pm->Nmesh;
     /* the mesh may have been cleared in the shadow of the last tree walk (grav_walk.hip, `scrub`) */
     const bool prezeroed = ctx->mesh_zeroed && ctx->pm_nmesh == N;
     SHQ_TRY(pm_prepare(ctx, N));
     const int zp = ctx->pm_zp;
     const size_t padded = (size_t) N * N * zp;
-    const int Nc = N / 2 + 1;
     const double cell = pm->BoxSize / N; /* CellSize */
     const long long n = ctx->numpart;
     /* fixed-point scale: 2^e with e chosen so that the whole mass in one cell cannot overflow */
-    const int e = ctx->pm_log2scale;
-    const double scale = ldexp(1.0, e);
+    const double scale = ldexp(1.0, ctx->pm_log2scale);
     const int threads = 256;
     const size_t dense = (size_t) N * N * N;
-    const double asmth2 = pow((2 * M_PI) * pm->Asmth / N, 2);
-    const double pot_factor = -pm->G / (M_PI * pm->BoxSize);
-
     SHQ_HIP(hipEventRecord(ctx->ev_begin[8], ctx->stream));
     if(!(prezeroed && ctx->mesh_words == padded))
         pm_zero_kernel<<<dim3(2048), dim3(threads), 0, ctx->stream>>>((unsigned long long *) ctx->mesh.ptr, padded);
     if(n > 0)
         pm_deposit_kernel<<<dim3((unsigned) ((n + DEP_CHUNK - 1) / DEP_CHUNK)), dim3(256), 0, ctx->stream>>>(
-            ctx->posm.ptr, ctx->pflags.ptr, n, (unsigned long long *) ctx->mesh.ptr, N, zp, cell, scale, 0, N, ctx->pm_oob.ptr, pm_xcdk(1));
+            ctx->posm.ptr, ctx->pflags.ptr, n, (unsigned long long *) ctx->mesh.ptr, N, zp, cell, scale, 0, N, ctx->pm_oob.ptr, pm_xcdk(1),
+            (unsigned) ctx->pm_typemask);
     if(ctx->pm_keep) {
         SHQ_TRY(ctx->dbg_rho.reserve(dense));
         pm_repitch_kernel<<<dim3((unsigned) ((dense + threads - 1) / threads)), dim3(threads), 0, ctx->stream>>>(
             ctx->mesh.ptr, ctx->dbg_rho.ptr, (size_t) N * N, N, zp, N, 1, 1.0 / scale);
     }
+    return SHQ_OK;
+}
+
+/* the potential copy of shq_pm_set_debug and the readout of GravPM / the PM potential (readout = false: shq_treepm_step's walk does it) */
+int pm_readout(shq_context *ctx, const shq_pm_params *pm, bool readout)
+{
+    const int N = pm->Nmesh, zp = ctx->pm_zp, threads = 256;
+    const size_t dense = (size_t) N * N * N;
+    const long long n = ctx->numpart;
+    const double cell = pm->BoxSize / N;
+    if(ctx->pm_keep) {
+        SHQ_TRY(ctx->dbg_pot.reserve(dense));
+        pm_repitch_kernel<<<dim3((unsigned) ((dense + threads - 1) / threads)), dim3(threads), 0, ctx->stream>>>(
+            ctx->mesh.ptr, ctx->dbg_pot.ptr, (size_t) N * N, N, zp, N, 0, 1.0);
+    }
+    ctx->fuse_cell = cell;
+    ctx->fuse_ffac = -(N / pm->BoxSize);
+    if(n > 0 && readout) { /* !readout: shq_treepm_step, the tree walk's prologue reads the potential mesh */
+        const double ffac = -(N / pm->BoxSize);
+        pm_readout_kernel<<<dim3((unsigned) ((n + threads - 1) / threads)), dim3(threads), 0, ctx->stream>>>(
+            ctx->posm.ptr, ctx->pflags.ptr, n, ctx->mesh.ptr, N, zp, cell, ffac, ctx->gravpm.ptr, ctx->pmpot.ptr, 0, N, ctx->pm_oob.ptr, pm_xcdk(0),
+            ctx->readout_oldacc_G > 0 ? ctx->treeacc.ptr : nullptr, ctx->readout_oldacc_G > 0 ? ctx->oldacc.ptr : nullptr, ctx->readout_oldacc_G);
+    }
+    SHQ_HIP(hipGetLastError());
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[13], ctx->stream));
+    ctx->have_pm_result = true;
+    return SHQ_OK;
+}
+
+/* The second half of a PM whose density spectrum shq_pm_forward left in the mesh: every mode times T[k2] (shq_pm_set_mode_factor; 1 without a
+ * table), potential_transfer, the inverse transform on the route the forward took, the readout.  With shq_pm_measure_power the P(k) sums
+ * of the multiplied density, potential_transfer's (gravpm.cpp:426-430).  Consumes the spectrum and the table. */
+int pm_finish(shq_context *ctx, const shq_pm_params *pm, bool readout)
+{
+    const shq_pm_params &f = ctx->pm_spec_params;
+    SHQ_CHECK(pm->Nmesh == f.Nmesh && pm->BoxSize == f.BoxSize && pm->Asmth == f.Asmth && pm->G == f.G && ctx->pm_nmesh == f.Nmesh, SHQ_ERR_STATE,
+              "pm: the pending spectrum of shq_pm_forward was made with Nmesh %d, BoxSize %g, Asmth %g, G %g: finish it with the same params",
+              f.Nmesh, f.BoxSize, f.Asmth, f.G);
+    const int N = pm->Nmesh, zp = ctx->pm_zp, Nc = N / 2 + 1, threads = 256;
+    const double asmth2 = pow((2 * M_PI) * pm->Asmth / N, 2);
+    const double pot_factor = -pm->G / (M_PI * pm->BoxSize);
+    const double *T = ctx->pm_fac_set ? ctx->pm_fac.ptr : nullptr;
+    const bool measure = ctx->pm_measure_power;
+    if(measure)
+        SHQ_TRY(pm_power_prepare(ctx, N));
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[11], ctx->stream));
+    if(ctx->pm_spec_route == 0) {
+        double *scratch = pm_scratch(ctx, N, zp, true);
+        SHQ_CHECK(scratch, SHQ_ERR_NOMEM, "pm: no scratch mesh for the transposing pipeline");
+        const double *fac = T;
+        if(!T) {
+            static const double one = 1.0;
+            SHQ_TRY(ctx->pm_fac_one.reserve(1));
+            SHQ_HIP(hipMemcpyAsync(ctx->pm_fac_one.ptr, &one, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+            fac = ctx->pm_fac_one.ptr;
+        }
+        const bool sweep = measure && pm_pk_sweep();
+        if(sweep)
+            SHQ_TRY(pm_power_sweep(ctx, N, zp / 2, T, zp / 8));
+        SHQ_TRY(shq_fft3d_transposed_part(ctx, ctx->mesh.ptr, scratch, N, zp, 2, false, 1.0, ctx->sinctab.ptr, asmth2, pot_factor, fac, T ? -1 : 0,
+                                          ctx->ps_bintab.ptr, measure && !sweep ? ctx->ps_sums.ptr : nullptr));
+    } else {
+        if(measure)
+            SHQ_TRY(pm_power_sweep(ctx, N, zp / 2, T));
+        const size_t tot = (size_t) N * N * Nc;
+        pm_green_kernel<<<dim3((unsigned) ((tot + threads - 1) / threads)), dim3(threads), 0, ctx->stream>>>(
+            (double2 *) ctx->mesh.ptr, N, Nc, zp / 2, ctx->sinctab.ptr, asmth2, pot_factor, T);
+        SHQ_HIP(hipGetLastError());
+        if(ctx->pm_spec_route == 1)
+            SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 1, false, 1.0, ctx->sinctab.ptr, asmth2, pot_factor));
+        else {
+            hipfftSetStream(ctx->plan_c2r, ctx->stream);
+            hipfftResult r = hipfftExecZ2D(ctx->plan_c2r, (hipfftDoubleComplex *) ctx->mesh.ptr, (hipfftDoubleReal *) ctx->mesh.ptr);
+            SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "hipfftExecZ2D failed: %d", (int) r);
+        }
+    }
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[12], ctx->stream));
+    shq_pm_discard_spectrum(ctx); /* delta_nu changes every PM step: the table is never used twice */
+    return pm_readout(ctx, pm, readout);
+}
+
+} // namespace
+
+int shq_pm_execute(shq_context *ctx, const shq_pm_params *pm, bool readout)
+{
+    if(ctx->pm_spec_pending)
+        return pm_finish(ctx, pm, readout);
+    SHQ_TRY(pm_deposit(ctx, pm));
+    const int N = pm->Nmesh;
+    const int zp = ctx->pm_zp;
+    const size_t padded = (size_t) N * N * zp;
+    const int Nc = N / 2 + 1;
+    const double scale = ldexp(1.0, ctx->pm_log2scale);
+    const int threads = 256;
+    const double asmth2 = pow((2 * M_PI) * pm->Asmth / N, 2);
+    const double pot_factor = -pm->G / (M_PI * pm->BoxSize);
+
     if(ctx->pm_custom_fft && ctx->pm_measure_power) {
         /* P(k) is taken from the density spectrum, which the fused X pass never writes out: when it is
          * wanted the forward and inverse transforms run separately (6 passes + 2 sweeps instead of 5) */
@@ -544,10 +704,7 @@ int shq_pm_execute(shq_context *ctx, const shq_pm_params *pm, bool readout)
         /* five fused passes: Z fwd (+ int64 -> f64), Y fwd, X fwd + potential_transfer + X inv, Y inv, Z inv */
         /* the transposing pipeline (fft3d.hip) wants a second mesh as scratch: the one shq_treepm_step keeps anyway (between two steps
          * it holds the previous step's potential, which nothing reads any more once that step's walk has gone by on this stream) */
-        double *scratch = nullptr;
-        static const size_t scratch_off = getenv("SHQ_FFT_SCRATCH_OFFSET") ? (size_t) atoll(getenv("SHQ_FFT_SCRATCH_OFFSET")) / 8 : 0; /* probe */
-        if(ctx->fft_transposed && zp == shq_fft3d_pitch(N) && ctx->mesh_alt.reserve(padded + scratch_off) == SHQ_OK)
-            scratch = ctx->mesh_alt.ptr + scratch_off;
+        double *scratch = pm_scratch(ctx, N, zp);
         SHQ_HIP(hipEventRecord(ctx->ev_begin[9], ctx->stream));
         if(scratch)
             SHQ_TRY(shq_fft3d_run_transposed(ctx, ctx->mesh.ptr, scratch, N, zp, true, 1.0 / scale, ctx->sinctab.ptr, asmth2, pot_factor));
@@ -577,22 +734,49 @@ int shq_pm_execute(shq_context *ctx, const shq_pm_params *pm, bool readout)
         SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "hipfftExecZ2D failed: %d", (int) r);
         SHQ_HIP(hipEventRecord(ctx->ev_begin[12], ctx->stream));
     }
-    if(ctx->pm_keep) {
-        SHQ_TRY(ctx->dbg_pot.reserve(dense));
-        pm_repitch_kernel<<<dim3((unsigned) ((dense + threads - 1) / threads)), dim3(threads), 0, ctx->stream>>>(
-            ctx->mesh.ptr, ctx->dbg_pot.ptr, (size_t) N * N, N, zp, N, 0, 1.0);
+    return pm_readout(ctx, pm, readout);
+}
+
+/* The first half of gravpm_force (shq_pm_forward): deposit, forward transform and the raw sums of measure_power_spectrum
+ * (gravpm.cpp:76-81, petapm.cpp:417-426) - where the reference's global_analysis hook runs.  The spectrum stays in the mesh, pending:
+ * the next shq_pm_run / shq_treepm_step finishes it (pm_finish).  Transposing pipeline: the X pass split in two (fft_t_tile MODES 3, 4),
+ * the sums taken as the X forward half stores the spectrum; in-place pipeline and hipFFT: the measure-power route's passes. */
+int shq_pm_execute_forward(shq_context *ctx, const shq_pm_params *pm)
+{
+    shq_pm_discard_spectrum(ctx);
+    SHQ_TRY(pm_deposit(ctx, pm));
+    const int N = pm->Nmesh, zp = ctx->pm_zp;
+    const double inv_scale = ldexp(1.0, -ctx->pm_log2scale);
+    const double asmth2 = pow((2 * M_PI) * pm->Asmth / N, 2);
+    const double pot_factor = -pm->G / (M_PI * pm->BoxSize);
+    SHQ_TRY(pm_power_prepare(ctx, N));
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[9], ctx->stream));
+    double *scratch = ctx->pm_custom_fft ? pm_scratch(ctx, N, zp) : nullptr;
+    int route;
+    if(scratch) {
+        route = 0;
+        const bool sweep = pm_pk_sweep();
+        SHQ_TRY(shq_fft3d_transposed_part(ctx, ctx->mesh.ptr, scratch, N, zp, 1, true, inv_scale, ctx->sinctab.ptr, asmth2, pot_factor, nullptr, 0,
+                                          ctx->ps_bintab.ptr, sweep ? nullptr : ctx->ps_sums.ptr));
+        if(sweep)
+            SHQ_TRY(pm_power_sweep(ctx, N, zp / 2, nullptr, zp / 8));
+    } else if(ctx->pm_custom_fft) {
+        route = 1;
+        SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 0, true, inv_scale, ctx->sinctab.ptr, asmth2, pot_factor));
+        SHQ_TRY(pm_power_sweep(ctx, N, zp / 2));
+    } else {
+        route = 2;
+        pm_convert_kernel<<<dim3(2048), dim3(256), 0, ctx->stream>>>(ctx->mesh.ptr, (size_t) N * N * zp, inv_scale);
+        SHQ_HIP(hipGetLastError());
+        hipfftSetStream(ctx->plan_r2c, ctx->stream);
+        hipfftResult r = hipfftExecD2Z(ctx->plan_r2c, (hipfftDoubleReal *) ctx->mesh.ptr, (hipfftDoubleComplex *) ctx->mesh.ptr);
+        SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "hipfftExecD2Z failed: %d", (int) r);
+        SHQ_TRY(pm_power_sweep(ctx, N, zp / 2));
     }
-    ctx->fuse_cell = cell;
-    ctx->fuse_ffac = -(N / pm->BoxSize);
-    if(n > 0 && readout) { /* !readout: shq_treepm_step, the tree walk's prologue reads the potential mesh */
-        const double ffac = -(N / pm->BoxSize);
-        pm_readout_kernel<<<dim3((unsigned) ((n + threads - 1) / threads)), dim3(threads), 0, ctx->stream>>>(
-            ctx->posm.ptr, ctx->pflags.ptr, n, ctx->mesh.ptr, N, zp, cell, ffac, ctx->gravpm.ptr, ctx->pmpot.ptr, 0, N, ctx->pm_oob.ptr, pm_xcdk(0),
-            ctx->readout_oldacc_G > 0 ? ctx->treeacc.ptr : nullptr, ctx->readout_oldacc_G > 0 ? ctx->oldacc.ptr : nullptr, ctx->readout_oldacc_G);
-    }
-    SHQ_HIP(hipGetLastError());
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[13], ctx->stream));
-    ctx->have_pm_result = true;
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[10], ctx->stream));
+    ctx->pm_spec_pending = true;
+    ctx->pm_spec_params = *pm;
+    ctx->pm_spec_route = route;
     return SHQ_OK;
 }
 
@@ -612,12 +796,40 @@ extern "C" int shq_pm_measure_power(shq_context *ctx, int enable)
     return SHQ_OK;
 }
 
+extern "C" int shq_pm_set_mode_factor(shq_context *ctx, int Nmesh, const double *table)
+{
+    SHQ_CHECK(ctx, SHQ_ERR_INVALID, "null context");
+    if(!table) {
+        ctx->pm_fac_set = false;
+        return SHQ_OK;
+    }
+    SHQ_CHECK(ctx->pm_spec_pending, SHQ_ERR_STATE, "pm_set_mode_factor: no pending spectrum (shq_pm_forward first)");
+    SHQ_CHECK(Nmesh == ctx->pm_spec_params.Nmesh, SHQ_ERR_INVALID, "pm_set_mode_factor: Nmesh %d, the pending spectrum has %d", Nmesh,
+              ctx->pm_spec_params.Nmesh);
+    const size_t nk2 = 3 * (size_t) (Nmesh / 2) * (Nmesh / 2) + 1;
+    SHQ_HIP(hipSetDevice(ctx->device));
+    SHQ_TRY(ctx->pm_fac.reserve(nk2));
+    /* on the main stream, behind any finish that still reads the last table; the host array is free when the call returns */
+    SHQ_HIP(hipMemcpyAsync(ctx->pm_fac.ptr, table, nk2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    SHQ_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->pm_fac_set = true;
+    return SHQ_OK;
+}
+
+extern "C" int shq_pm_set_deposit_types(shq_context *ctx, int typemask)
+{
+    SHQ_CHECK(ctx, SHQ_ERR_INVALID, "null context");
+    ctx->pm_typemask = typemask;
+    return SHQ_OK;
+}
+
 extern "C" int shq_pm_download_power(shq_context *ctx, int size, double *kk, double *power, int64_t *nmodes, double *norm)
 {
     if(ctx)
         SHQ_TRY(shq_join_pm(ctx));
     SHQ_CHECK(ctx && kk && power && nmodes && norm, SHQ_ERR_INVALID, "null argument");
-    SHQ_CHECK(ctx->have_power && ctx->have_pm_result, SHQ_ERR_STATE, "pm_download_power: enable shq_pm_measure_power before the PM run");
+    SHQ_CHECK(ctx->have_power && (ctx->have_pm_result || ctx->pm_spec_pending), SHQ_ERR_STATE,
+              "pm_download_power: enable shq_pm_measure_power before the PM run, or call shq_pm_forward");
     SHQ_CHECK(size == ctx->ps_nbins, SHQ_ERR_INVALID, "pm_download_power: size %d, the spectrum has %d bins (= Nmesh)", size, ctx->ps_nbins);
     const int nb = ctx->ps_nbins;
     std::vector<double> h(3 * (size_t) nb + 1);
@@ -669,6 +881,7 @@ __global__ void fourier_layout_kernel(const double2 *__restrict__ in, double2 *_
 
 int shq_fft_roundtrip_r2c(shq_context *ctx, int N, const double *real, double *complx, bool ref_layout)
 {
+    shq_pm_discard_spectrum(ctx); /* the context's mesh is the work space */
     SHQ_TRY(pm_prepare(ctx, N));
     const int zp = ctx->pm_zp;
     const size_t tot = (size_t) N * N * N, ctot = (size_t) N * N * (N + 2);
@@ -748,6 +961,7 @@ __global__ void pm_transfer_kernel(double2 *spec, int N, int Nc, const double *_
 
 int shq_fft_roundtrip_c2r(shq_context *ctx, int N, const double *complx, double *real, bool ref_layout, const shq_pm_transfer *tf)
 {
+    shq_pm_discard_spectrum(ctx);
     SHQ_TRY(pm_prepare(ctx, N));
     const int zp = ctx->pm_zp;
     const size_t tot = (size_t) N * N * N, ctot = (size_t) N * N * (N + 2);
@@ -818,6 +1032,7 @@ static int slab_sinctab(shq_context *ctx, int N)
 {
     if(ctx->sinctab_n == N)
         return SHQ_OK;
+    shq_pm_discard_spectrum(ctx); /* a pending spectrum's finish reads the table of its own Nmesh */
     SHQ_TRY(ctx->sinctab.reserve(N));
     SHQ_TRY(ctx->pm_oob.reserve(1));
     std::vector<double> tab(N);
@@ -864,7 +1079,7 @@ extern "C" int shq_pm_slab_deposit(shq_context *ctx, const shq_pm_params *pm, in
     if(n > 0)
         pm_deposit_kernel<<<dim3((unsigned) ((n + DEP_CHUNK - 1) / DEP_CHUNK)), dim3(256), 0, ctx->stream>>>(
             ctx->posm.ptr, ctx->pflags.ptr, n, (unsigned long long *) d_mesh_i64, N, N + 2, pm->BoxSize / N, ldexp(1.0, ctx->pm_log2scale),
-            plane0, nalloc, ctx->pm_oob.ptr, pm_xcdk(1));
+            plane0, nalloc, ctx->pm_oob.ptr, pm_xcdk(1), ~0u);
     SHQ_HIP(hipGetLastError());
     return check_oob(ctx, "pm_slab_deposit");
 }
@@ -976,7 +1191,7 @@ extern "C" int shq_pm_slab2_deposit_ghosts(shq_context *ctx, const shq_pm_params
     if(n > 0)
         pm_deposit_kernel<<<dim3((unsigned) ((n + DEP_CHUNK - 1) / DEP_CHUNK)), dim3(256), 0, ctx->stream>>>(
             ctx->posm.ptr, ctx->pflags.ptr, n, (unsigned long long *) d_mesh_i64, N, zp, pm->BoxSize / N, ldexp(1.0, ctx->pm_log2scale),
-            plane0 - xoff, nfit, ctx->pm_oob.ptr, pm_xcdk(1));
+            plane0 - xoff, nfit, ctx->pm_oob.ptr, pm_xcdk(1), ~0u);
     SHQ_HIP(hipGetLastError());
     return check_oob(ctx, "pm_slab2_deposit");
 }

@@ -160,6 +160,8 @@ extern "C" int shq_gas_set_device(shq_context *ctx, const double *d_rows, int64_
     ctx->nlocal = nlocal;
     ctx->have_parts = true;
     ctx->have_pm_result = false;
+    ctx->have_types = true; /* all gas (Type 0) */
+    shq_pm_discard_spectrum(ctx);
     ctx->have_sph = bad == 0;
     ctx->gas_resident = bad == 0;
     ctx->sphrun.phase = 0;

@@ -139,7 +139,8 @@ int grav_short_tree(shq_context *ctx, const ActiveParticles *act, PetaPM *pm, Fo
     return 0;
 }
 
-int gravpm_force(shq_context *ctx, PetaPM *pm, part_manager_type *PartManager, bool UseGPU)
+int gravpm_force(shq_context *ctx, PetaPM *pm, part_manager_type *PartManager, bool UseGPU, gravpm_analysis_fn analysis, void *userdata,
+                 int deposit_types)
 {
     if(!UseGPU) {
         shqh_set_error("gravpm_force: this build has no CPU PM; UseGPU must be true");
@@ -155,7 +156,34 @@ int gravpm_force(shq_context *ctx, PetaPM *pm, part_manager_type *PartManager, b
     pp.G = pm->G;
     shq_part_view pv = make_part_view(P, n);
     std::vector<double> g(3 * (size_t) (n > 0 ? n : 1)), pot((size_t) (n > 0 ? n : 1), 0.0);
-    int rc = shq_pm_force(ctx, &pp, &pv, (double (*)[3]) g.data(), pot.data());
+    int rc = shq_pm_set_deposit_types(ctx, deposit_types);
+    if(rc == SHQ_OK && !analysis)
+        rc = shq_pm_force(ctx, &pp, &pv, (double (*)[3]) g.data(), pot.data());
+    else if(rc == SHQ_OK) {
+        /* petapm_force with global_readout = measure_power_spectrum and global_analysis (gravpm.cpp:76-81, petapm.cpp:417-426) */
+        const int N = pm->Nmesh;
+        std::vector<double> kk(N), power(N), table(3 * (size_t) (N / 2) * (N / 2) + 1, 1.0);
+        std::vector<int64_t> nmodes(N);
+        double norm = 0;
+        rc = shq_particles_upload(ctx, &pv);
+        if(rc == SHQ_OK)
+            rc = shq_pm_forward(ctx, &pp);
+        if(rc == SHQ_OK)
+            rc = shq_pm_download_power(ctx, N, kk.data(), power.data(), nmodes.data(), &norm);
+        if(rc == SHQ_OK && analysis(userdata, N, kk.data(), power.data(), nmodes.data(), norm, N, table.data()) != 0) {
+            shq_pm_set_deposit_types(ctx, SHQ_ALL_TYPES);
+            shq_particles_upload(ctx, &pv); /* drops the pending spectrum */
+            shqh_set_error("gravpm_force: the analysis hook failed");
+            return SHQ_ERR_INVALID;
+        }
+        if(rc == SHQ_OK)
+            rc = shq_pm_set_mode_factor(ctx, N, table.data());
+        if(rc == SHQ_OK)
+            rc = shq_pm_run(ctx, &pp);
+        if(rc == SHQ_OK)
+            rc = shq_pm_download(ctx, (double (*)[3]) g.data(), pot.data());
+    }
+    shq_pm_set_deposit_types(ctx, SHQ_ALL_TYPES);
     if(rc != SHQ_OK) {
         shqh_set_error(shq_last_error());
         return rc;

@@ -57,7 +57,17 @@ void gravpm_init_periodic(PetaPM *pm, double BoxSize, double Asmth, int Nmesh, d
 int grav_short_tree(shq_context *ctx, const ActiveParticles *act, PetaPM *pm, ForceTree *tree,
                     part_manager_type *PartManager, MyFloat (*AccelStore)[3], double rho0,
                     inttime_t Ti_Current, bool UseGPU, int walk_mode, shq_walk_stats *stats);
-int gravpm_force(shq_context *ctx, PetaPM *pm, part_manager_type *PartManager, bool UseGPU);
+/* petapm's global_analysis hook in the shape gravpm_force's MassiveNuLinRespOn branch uses it (compute_neutrino_power, gravpm.cpp:76-81,
+ * 308-321): called between the forward and inverse halves of the PM with the raw P(k) sums of the density (nbins = Nmesh bins, as
+ * shq_pm_download_power returns them), it fills table[k2], k2 = 0 .. 3 (Nmesh/2)^2, with the factor of potential_transfer's modes
+ * (1 + nu_prefac nu_spline(log(sqrt(k2) 2 pi / BoxSize_in_MPC)), gravpm.cpp:412-427; table[0] is not used) and returns 0, or non-zero to
+ * end the call with an error. */
+typedef int (*gravpm_analysis_fn)(void *userdata, int nbins, const double *kk, const double *power, const int64_t *nmodes, double Norm,
+                                  int Nmesh, double *table);
+/* analysis: NULL = the call without neutrinos.  deposit_types: the PM deposit's type mask (SHQ_ALL_TYPES; without Type 2 while the reference's
+ * hybrid_nu_tracer holds, gravpm.cpp:84-85).  Every particle is read out either way. */
+int gravpm_force(shq_context *ctx, PetaPM *pm, part_manager_type *PartManager, bool UseGPU, gravpm_analysis_fn analysis = nullptr,
+                 void *userdata = nullptr, int deposit_types = SHQ_ALL_TYPES);
 
 /* fill the POD the C-ABI takes from the module state (GravTreeParams ctor, gravshort2.hpp:45-54) */
 int make_grav_params(const PetaPM *pm, double BoxSize, double rho0, shq_grav_params *out);

@@ -117,6 +117,15 @@ int shqh_gravpm_force(shq_context *ctx, part_manager_type *pmgr, double Asmth, i
     return gravpm_force(ctx, &pm, pmgr, UseGPU != 0);
 }
 
+/* gravpm_force with the analysis hook and the deposit type mask (a neutrino run) */
+int shqh_gravpm_force_hook(shq_context *ctx, part_manager_type *pmgr, double Asmth, int Nmesh, double G, int UseGPU, gravpm_analysis_fn analysis,
+                           void *userdata, int deposit_types)
+{
+    PetaPM pm;
+    gravpm_init_periodic(&pm, pmgr->BoxSize, Asmth, Nmesh, G);
+    return gravpm_force(ctx, &pm, pmgr, UseGPU != 0, analysis, userdata, deposit_types);
+}
+
 /* Synthetic inputs of SURVEY.md §8(d): kind 0 S-grid, 1 S-uniform, 2 S-cluster
  * (mirrors tests/test_gravity.cpp:316-341 with a 64-bit engine). n3 = particles per dimension
  * for the grid; n = total particles otherwise. */
