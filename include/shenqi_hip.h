@@ -1192,13 +1192,15 @@ int shq_pm_start(shq_context *ctx, const shq_pm_params *pm, double G);
  *                            density (potential_transfer's; scaling Norm by MtotbyMcdm^2, gravpm.cpp:431-435, stays with the caller).
  *   discarded by           : shq_drift, a particle upload, and the other users of the mesh - shq_fft_r2c / c2r, shq_pm_apply, shq_pm_start,
  *                            a slab call of another Nmesh.  The tree walk's mesh scrub (shq_pm_set_mesh_scrub) leaves a pending spectrum alone.
- * The P(k) sums are accumulated with floating-point atomics, as shq_pm_measure_power's: not bit-reproducible.  Single-GPU PM only. */
+ * The P(k) sums are accumulated with floating-point atomics, as shq_pm_measure_power's: not bit-reproducible.  For the undivided PM; the
+ * sharded slab PM splits its X step the same way (shq_pm_slab2_xforward / _xfinish below). */
 int shq_pm_forward(shq_context *ctx, const shq_pm_params *pm);
 int shq_pm_set_mode_factor(shq_context *ctx, int Nmesh, const double *table);
 /* Deposit type mask (hybrid neutrinos: while hybrid_nu_tracer holds, Type 2 is not deposited, gravpm.cpp:84-85, 459-464): bit t set = particles
  * of Type t are deposited; the readout still covers every particle (petapm.cpp:1304-1307).  Default SHQ_ALL_TYPES.  Applies to shq_pm_run,
- * shq_pm_force, shq_pm_start, shq_treepm_step and shq_pm_forward (not to the slab PM).  A mask other than all types with particles uploaded
- * without their Type (off_type = SHQ_NOFIELD, or shq_particles_set_device) makes those calls return SHQ_ERR_STATE. */
+ * shq_pm_force, shq_pm_start, shq_treepm_step, shq_pm_forward and the slab deposits (shq_pm_slab_deposit, shq_pm_slab2_deposit(_ghosts)).
+ * A mask other than all types with particles uploaded without their Type (off_type = SHQ_NOFIELD, or shq_particles_set_device without
+ * shq_particles_set_device_types) makes those calls return SHQ_ERR_STATE. */
 #define SHQ_ALL_TYPES (-1)
 int shq_pm_set_deposit_types(shq_context *ctx, int typemask);
 /* Debug / parity taps: copy the mesh after deposit (Nmesh^3 doubles, [x][y][z]) and the
@@ -1218,8 +1220,11 @@ int shq_pm_set_fft_transposed(shq_context *ctx, int enable);
  * kk[i] += w |k| (mesh units), nmodes[i] += w, and norm = |delta_0|^2 — the sums pm->ps holds before
  * powerspectrum_sum (powerspectrum.cpp:53-88), which the caller applies (MPI reduction, normalisation, units).
  * Costs one extra pass pair per PM run (the fused X pass never materialises the spectrum), so it is off
- * by default.  Single-GPU PM only. */
+ * by default.  The sharded slab PM takes its sums in shq_pm_slab2_xforward / _xfinish (shq_pm_slab_xforward / _xfinish on the torch
+ * route): shq_pm_download_power returns this rank's raw sums after either call, for the caller's all-reduce (powerspectrum_sum). */
 int shq_pm_measure_power(shq_context *ctx, int enable);
+/* the current shq_pm_measure_power setting: 1 on, 0 off, -1 for a null context */
+int shq_pm_get_measure_power(shq_context *ctx);
 int shq_pm_download_power(shq_context *ctx, int size, double *kk, double *power, int64_t *nmodes, double *norm);
 int shq_pm_set_debug(shq_context *ctx, int keep_meshes);
 /* The deposit mesh of the NEXT shq_pm_run is cleared in the shadow of the tree walk: the first production-size shq_grav_short_run
@@ -1253,8 +1258,18 @@ int shq_pm_download_mesh(shq_context *ctx, int which /*0 density,1 potential*/, 
  * shq_tree_build / shq_tree_upload is refused — unless keep_tree != 0, by which the caller states that these are the very
  * positions (same count, same order) the current tree was built from (a force evaluation repeated on frozen positions). */
 int shq_particles_set_device(shq_context *ctx, const void *d_posm, int64_t n, int64_t nlocal, int keep_tree);
+/* The Type of every row of that set: d_types_u8 = uint8[n] in device memory, n = the set's row count (else SHQ_ERR_INVALID).  Sets the
+ * Type bits of the particle flags and keeps the others; the deposit type mask may then leave types out.  shq_particles_set_device resets
+ * every row to Type 1, so a caller issues this again after each set. */
+int shq_particles_set_device_types(shq_context *ctx, const void *d_types_u8, int64_t n);
 int shq_pm_slab_deposit(shq_context *ctx, const shq_pm_params *pm, int plane0, int nplanes, void *d_mesh_i64);
 int shq_pm_slab_green(shq_context *ctx, const shq_pm_params *pm, int y0, int nyl, void *d_spec);
+/* green split for a global_analysis hook (massive neutrinos), on the same layout after the caller's X forward:
+ *   slab_xforward : zeroes the context's P(k) sums and adds this slab's raw sums of the density (shq_pm_download_power reads them).
+ *   slab_xfinish  : table (host, 3 (Nmesh/2)^2 + 1 doubles, NULL for T = 1): (v T) green, potential_transfer's order; with
+ *                   shq_pm_measure_power(ctx, 1) the sums are zeroed again and take those of v T. */
+int shq_pm_slab_xforward(shq_context *ctx, const shq_pm_params *pm, int y0, int nyl, void *d_spec);
+int shq_pm_slab_xfinish(shq_context *ctx, const shq_pm_params *pm, int y0, int nyl, void *d_spec, const double *table);
 int shq_pm_slab_readout(shq_context *ctx, const shq_pm_params *pm, int plane0, int nplanes, const void *d_phi_ext);
 /* The same phases on the bespoke FFT passes (csrc/fft3d.hip), for mesh sizes that have them
  * (shq_pm_slab_pitch != 0): replaces the 2-D r2c / 1-D FFT / c2r of the slab pipeline (heffte's role in
@@ -1283,6 +1298,17 @@ int shq_pm_slab2_fft_yz(shq_context *ctx, int Nmesh, void *d_planes, int nplanes
  * all-to-all), direction 1 starts from d_packed in that layout (what the return all-to-all delivers: rows [source rank][x plane]) */
 int shq_pm_slab2_fft_yz_packed(shq_context *ctx, int Nmesh, void *d_planes, int nplanes, int direction, void *d_packed, int nranks);
 int shq_pm_slab2_xgreen(shq_context *ctx, const shq_pm_params *pm, void *d_spec, int y0, int nyl);
+/* slab2_xgreen in two halves, for a caller with a global_analysis hook (MassiveNuLinRespOn: compute_neutrino_power after
+ * powerspectrum_sum's all-reduce, gravpm.cpp:308-321, powerspectrum.cpp:53-88):
+ *   slab2_xforward : x forward in place; zeroes the context's P(k) sums and adds this slab's raw sums of the density.  Only the rank
+ *                    whose slab holds y = 0 sets Norm; the others leave it 0, so the sum over the ranks is the reference's Norm.
+ *   slab2_xfinish  : table (host, 3 (Nmesh/2)^2 + 1 doubles, NULL for T = 1; T[0] is not used): (v T) green, potential_transfer's
+ *                    order, then x inverse.  T = 1 does slab2_xgreen's arithmetic: the same bits at Nmesh 48 and 128
+ *                    (tests), 2e-15 relative at 768.  With shq_pm_measure_power(ctx, 1) the sums are zeroed
+ *                    again and take those of v T (potential_transfer's; scaling Norm by MtotbyMcdm^2 stays with the caller).
+ * shq_pm_download_power returns this rank's raw sums after either call; the P(k) sums use floating-point atomics: not bit-reproducible. */
+int shq_pm_slab2_xforward(shq_context *ctx, const shq_pm_params *pm, void *d_spec, int y0, int nyl);
+int shq_pm_slab2_xfinish(shq_context *ctx, const shq_pm_params *pm, void *d_spec, int y0, int nyl, const double *table);
 int shq_pm_slab2_readout(shq_context *ctx, const shq_pm_params *pm, int plane0, int nplanes, int xoff, int nalloc,
                          const void *d_phi);
 /* Fixed-point deposit scale 2^e: chosen per context from the local mass sum at particle upload;

@@ -546,10 +546,22 @@ hip.shq_pm_slab2_fft_yz_packed.restype = C.c_int
 hip.shq_pm_slab2_fft_yz.restype = C.c_int
 hip.shq_pm_slab2_xgreen.argtypes = [_vp, C.POINTER(PMParams), _vp, C.c_int, C.c_int]
 hip.shq_pm_slab2_xgreen.restype = C.c_int
+hip.shq_pm_slab2_xforward.argtypes = [_vp, C.POINTER(PMParams), _vp, C.c_int, C.c_int]
+hip.shq_pm_slab2_xforward.restype = C.c_int
+hip.shq_pm_slab2_xfinish.argtypes = [_vp, C.POINTER(PMParams), _vp, C.c_int, C.c_int, _vp]
+hip.shq_pm_slab2_xfinish.restype = C.c_int
+hip.shq_pm_slab_xforward.argtypes = [_vp, C.POINTER(PMParams), C.c_int, C.c_int, _vp]
+hip.shq_pm_slab_xforward.restype = C.c_int
+hip.shq_pm_slab_xfinish.argtypes = [_vp, C.POINTER(PMParams), C.c_int, C.c_int, _vp, _vp]
+hip.shq_pm_slab_xfinish.restype = C.c_int
+hip.shq_particles_set_device_types.argtypes = [_vp, _vp, C.c_int64]
+hip.shq_particles_set_device_types.restype = C.c_int
 hip.shq_pm_slab2_readout.argtypes = [_vp, C.POINTER(PMParams), C.c_int, C.c_int, C.c_int, C.c_int, _vp]
 hip.shq_pm_slab2_readout.restype = C.c_int
 hip.shq_pm_measure_power.argtypes = [_vp, C.c_int]
 hip.shq_pm_measure_power.restype = C.c_int
+hip.shq_pm_get_measure_power.argtypes = [_vp]
+hip.shq_pm_get_measure_power.restype = C.c_int
 hip.shq_pm_download_power.argtypes = [_vp, C.c_int, _vp, _vp, _vp, _vp]
 hip.shq_pm_download_power.restype = C.c_int
 hip.shq_dynamics_upload.argtypes = [_vp, C.POINTER(PartView)]

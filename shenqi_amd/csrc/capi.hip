@@ -882,6 +882,32 @@ extern "C" int shq_particles_set_device(shq_context *ctx, const void *d_posm, in
     return SHQ_OK;
 }
 
+__global__ void set_types_kernel(uint8_t *pflags, const uint8_t *__restrict__ types, long long n)
+{
+    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if(i < n)
+        pflags[i] = (uint8_t) ((pflags[i] & 0x0f) | ((types[i] & 0x0f) << 4));
+}
+
+/* The Type of every row of the device particle set (uint8, device memory, n = the set's row count): the Type nibble of the flags, the
+ * other bits kept.  The PM's deposit type mask (shq_pm_set_deposit_types) may then leave types out.  shq_particles_set_device resets
+ * every row to Type 1: issue this again after each set. */
+extern "C" int shq_particles_set_device_types(shq_context *ctx, const void *d_types_u8, int64_t n)
+{
+    SHQ_CHECK(ctx && (d_types_u8 || n == 0), SHQ_ERR_INVALID, "null argument");
+    SHQ_CHECK(ctx->have_parts, SHQ_ERR_STATE, "particles_set_device_types: no particle set");
+    SHQ_CHECK(n == ctx->numpart, SHQ_ERR_INVALID, "particles_set_device_types: %lld types for a set of %lld rows", (long long) n,
+              (long long) ctx->numpart);
+    SHQ_HIP(hipSetDevice(ctx->device));
+    SHQ_TRY(shq_join_pm(ctx));
+    if(n > 0) {
+        set_types_kernel<<<dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, ctx->stream>>>(ctx->pflags.ptr, (const uint8_t *) d_types_u8, n);
+        SHQ_HIP(hipGetLastError());
+    }
+    ctx->have_types = true;
+    return SHQ_OK;
+}
+
 /* ---- gravity ---------------------------------------------------------------------------- */
 
 extern "C" int shq_grav_short_run(shq_context *ctx, const shq_grav_params *params, const int32_t *active,

@@ -434,6 +434,9 @@ struct shq_context {
     bool pm_fac_set = false;
     DevBuf<double> pm_fac_one; /* {1.0}: the table of a finish without one */
     int pm_typemask = -1;      /* shq_pm_set_deposit_types: bit t set = particles of Type t are deposited */
+    DevBuf<double> slab_fac;   /* shq_pm_slab2_xfinish / shq_pm_slab_xfinish: the caller's T[k2], 3 (Nmesh/2)^2 + 1 entries */
+    bool ps_slab = false;      /* ps_sums hold a slab call's sums (shq_pm_slab2_xforward, ...): shq_pm_download_power may read them
+                                * until shq_pm_discard_spectrum or shq_pm_measure_power(ctx, 0) */
     bool have_types = false;   /* the resident particles came with their Type (pflags bits 4-7) */
 
     shq_walk_stats last_stats = {};
@@ -464,11 +467,13 @@ struct shq_context {
 
 /* capi.hip: make the main stream wait for an outstanding asynchronous PM run */
 int shq_join_pm(shq_context *ctx);
-/* a pending spectrum (shq_pm_forward) and its factor table end when the particles move or another user takes the mesh */
+/* a pending spectrum (shq_pm_forward) and its factor table end when the particles move or another user takes the mesh; so do the
+ * sums a slab X call left for shq_pm_download_power */
 inline void shq_pm_discard_spectrum(shq_context *ctx)
 {
     ctx->pm_spec_pending = false;
     ctx->pm_fac_set = false;
+    ctx->ps_slab = false;
 }
 /* grav_walk.hip */
 /* Device pointer and length of an active list argument of the C-ABI: NULL (all n_all), a host list
@@ -530,6 +535,9 @@ int shq_fft3d_run_slab(shq_context *ctx, double *d_mesh, int N, int zp, int stag
                        const double *d_sinctab, double asmth2, double pot_factor, int nslab, int y0);
 int shq_fft3d_run_slab_packed(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale,
                               const double *d_sinctab, double asmth2, double pot_factor, int nslab, int y0, double *d_packed, int nranks);
+int shq_fft3d_run_slab_x(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale, const double *d_sinctab,
+                         double asmth2, double pot_factor, int nslab, int y0, double *d_packed, int nranks, const double *d_modefac, int fac_mask,
+                         const int32_t *d_bintab, double *d_ps);
 /* sph.hip */
 int shq_sph_prepare(shq_context *ctx, const shq_kick_factors *kf, const shq_hydro_params *hp, const double *d_evp_in);
 int shq_sph_density_device(shq_context *ctx, const shq_density_params *p, const int32_t *d_queue, int64_t nq,

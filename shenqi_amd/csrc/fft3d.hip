@@ -444,7 +444,8 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_z_inv(double *mesh, const int 
 }
 
 /* ---- passes Y and X: complex lines with element stride `es` (in complex units), FFT_C adjacent columns.
- * MODE 0: forward only; 1: inverse only; 2: forward, Green's function, inverse (X pass of the PM). */
+ * MODE 0: forward only; 1: inverse only; 2: forward, Green's function, inverse (X pass of the PM).
+ * MODES 3, 4 (fft_pass_strided only, the X pass of a y-slab): MODE 2 split in two as fft_t_tile's MODES 3, 4 split it (below). */
 struct GreenArgs {
     const double *sinctab; /* 1 / sinc^2(pi k / N) per mesh index */
     const double *gaxg;    /* transposing pipeline: exp(-k_i^2 asmth2) sinctab[i]^2 per mesh index, in global memory (fft_gax_kernel) */
@@ -464,7 +465,36 @@ struct GreenArgs {
     double *ps;
 };
 
-/* PK 0: in place.  PK 1: results stored into ga.alt in the packed (send) layout.  PK 2: input loaded from ga.alt in that layout. */
+/* powerspectrum_add_mode (gravpm.cpp:323-356) of one mode into a workgroup's LDS histogram [3][N]: the operations of pm_power_kernel
+ * (pm.hip).  The zero mode sets Norm; pad columns z > N / 2 are not modes. */
+template <int N>
+__device__ __forceinline__ void pk_add(double *hist, const GreenArgs &ga, double2 v, int x, int y, int z, int k2)
+{
+    if(z > N / 2)
+        return;
+    const double m = v.x * v.x + v.y * v.y;
+    if(k2 == 0) {
+        ga.ps[3 * N] = m;
+        return;
+    }
+    const int kint = ga.bintab[k2];
+    if(kint >= N)
+        return;
+    const double f = ga.sinctab[x] * ga.sinctab[y] * ga.sinctab[z];
+    const double w = (z == 0 || z == N / 2) ? 1.0 : 2.0;
+    atomicAdd(&hist[kint], w * m * f * f);
+    atomicAdd(&hist[N + kint], w * sqrt((double) k2));
+    atomicAdd(&hist[2 * N + kint], w);
+}
+
+/* PK 0: in place.  PK 1: results stored into ga.alt in the packed (send) layout.  PK 2: input loaded from ga.alt in that layout.
+ * The X pass of a y-slab split for a caller that needs the density spectrum between its halves (shq_pm_slab2_xforward / _xfinish):
+ *   MODE 3: X forward, the spectrum written back in place; with ga.ps the P(k) sums of the density as the tile is stored.  y = ga.y0 +
+ *           outer: only the rank whose slab holds y = 0 meets the zero mode and writes Norm (the others leave it 0).
+ *   MODE 4: every mode times T[k2], then MODE 2's Green's factor with MODE 2's arithmetic - (v T) green, potential_transfer's order
+ *           (gravpm.cpp:412-443) - as the tile lands in LDS; with ga.ps the P(k) sums of v T; then X inverse.  T = 1 gives MODE 2's
+ *           bits: v * 1.0 is exact.  T[k2] of the next tile is gathered after the current tile's stages, as fft_t_tile does.
+ * MODES 3, 4 with ga.ps keep a P(k) histogram [3][N] in LDS behind the tables (3 N doubles more), flushed once per workgroup. */
 template <int N, int MODE, int PK = 0>
 __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const long long es, const long long outer_stride,
                                                           const int ntiles, const int ntot, const double2 *__restrict__ W,
@@ -475,17 +505,24 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
     constexpr int E = (FFT_C * N + FFT_T - 1) / FFT_T; /* tile elements per thread */
     constexpr bool EXACT = E * FFT_T == FFT_C * N;
     double2 *Wl = lds_twiddles<N>(buf, W);
-    double *gax = reinterpret_cast<double *>(Wl + fft_twn(N)); /* MODE 2 only: per-axis factor of the Green's function */
-    if(MODE == 2)
+    double *gax = reinterpret_cast<double *>(Wl + fft_twn(N)); /* MODES 2, 4: per-axis factor of the Green's function */
+    if(MODE == 2 || MODE == 4)
         for(int i = threadIdx.x; i < N; i += FFT_T) {
             const int k = i <= N / 2 ? i : i - N;
             const double sc = ga.sinctab[i];
             gax[i] = exp(-(double) k * (double) k * ga.asmth2) * sc * sc;
         }
+    /* MODES 3, 4 with ga.ps: the histogram behind the tables; the barrier after the first tile lands orders the zeroing */
+    double *hist = MODE == 4 ? gax + N : gax;
+    const bool pk = (MODE == 3 || MODE == 4) && ga.ps;
+    if(pk)
+        for(int i = threadIdx.x; i < 3 * N; i += FFT_T)
+            hist[i] = 0;
     /* XCD-chunked workgroup order: neighbouring column tiles share 128-byte lines (a tile row is 64
      * bytes), so they should run on the same XCD at about the same time and find the other half in its L2. */
     const unsigned vb = xcd_block(blockIdx.x, gridDim.x, xcdk);
     double prx[E], pry[E];
+    double tfac[MODE == 4 ? E : 1]; /* MODE 4: T[k2] of the prefetched tile's modes */
 #define FFT_FETCH(BASE, ABASE)                                                                   \
     _Pragma("unroll") for(int i = 0; i < E; i++)                                                 \
     {                                                                                            \
@@ -498,6 +535,18 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
             pry[i] = t_.y;                                                                       \
         }                                                                                        \
     }
+    /* MODE 4: T[k2] of the modes of tile (O_, TL_); a pad column (z > N / 2) reads entry 0, so k2 stays inside the table */
+#define FFT_TFETCH(O_, TL_)                                                                      \
+    if(MODE == 4) {                                                                              \
+        const int y_ = ga.y0 + (O_), ky_ = y_ <= N / 2 ? y_ : y_ - N;                            \
+        _Pragma("unroll") for(int i = 0; i < E; i++)                                             \
+        {                                                                                        \
+            const int e_ = threadIdx.x + i * FFT_T, e = (EXACT || e_ < FFT_C * N) ? e_ : 0;     \
+            const int x_ = e / FFT_C, z_ = (TL_) * FFT_C + e % FFT_C, kx_ = x_ <= N / 2 ? x_ : x_ - N; \
+            const int k2_ = z_ <= N / 2 ? kx_ * kx_ + ky_ * ky_ + z_ * z_ : 0;                   \
+            tfac[i] = ga.modefac[k2_ & ga.fac_mask];                                             \
+        }                                                                                        \
+    }
     int t = (int) vb;
     if(t >= ntot)
         return;
@@ -507,12 +556,43 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
     double2 *base = cm + (long long) outer * outer_stride + (long long) tile * FFT_C;
     double2 *abase = PK ? ga.alt + (long long) outer * ga.alt_outer + (long long) tile * FFT_C : nullptr;
     FFT_FETCH(base, abase)
+    FFT_TFETCH(outer, tile)
     while(true) {
+        if(MODE == 4) {
+            /* (v T) green: the tile lands multiplied by T (T[0] is not used: the zero mode is removed), then a rolled sweep over LDS
+             * takes its P(k) and applies MODE 2's Green's factor */
+            const int y = ga.y0 + outer, z0 = tile * FFT_C;
+            const int ky = y <= N / 2 ? y : y - N;
 #pragma unroll
-        for(int i = 0; i < E; i++) {
-            const int e = threadIdx.x + i * FFT_T;
-            if(EXACT || e < FFT_C * N)
-                buf[(e % FFT_C) * LS + lx<N>(e / FFT_C)] = make_double2(prx[i], pry[i]);
+            for(int i = 0; i < E; i++) {
+                const int e = threadIdx.x + i * FFT_T;
+                if(EXACT || e < FFT_C * N) {
+                    const int x = e / FFT_C, z = z0 + e % FFT_C;
+                    const int kx = x <= N / 2 ? x : x - N;
+                    const double tv = (z <= N / 2 && kx * kx + ky * ky + z * z != 0) ? tfac[i] : 1.0;
+                    buf[(e % FFT_C) * LS + lx<N>(x)] = make_double2(prx[i] * tv, pry[i] * tv);
+                }
+            }
+            __syncthreads();
+            const double gy = gax[y] * ga.pot_factor, ky2 = (double) ky * (double) ky;
+            for(int e = threadIdx.x; e < FFT_C * N; e += FFT_T) {
+                const int x = e / FFT_C, col = e % FFT_C, z = z0 + col;
+                const int kx = x <= N / 2 ? x : x - N;
+                double2 *p = buf + col * LS + lx<N>(x);
+                const double2 v = *p;
+                if(pk)
+                    pk_add<N>(hist, ga, v, x, y, z, kx * kx + ky * ky + z * z);
+                const double k2 = (double) kx * (double) kx + (ky2 + (double) z * (double) z); /* exact: < 2^53 */
+                const double fac = (k2 == 0.0 || z > N / 2) ? 0.0 : gax[x] * gy * gax[z] / k2;
+                *p = make_double2(v.x * fac, v.y * fac);
+            }
+        } else {
+#pragma unroll
+            for(int i = 0; i < E; i++) {
+                const int e = threadIdx.x + i * FFT_T;
+                if(EXACT || e < FFT_C * N)
+                    buf[(e % FFT_C) * LS + lx<N>(e / FFT_C)] = make_double2(prx[i], pry[i]);
+            }
         }
         __syncthreads();
         const int tn = t + (int) gridDim.x;
@@ -521,7 +601,7 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
         double2 *base_n = cm + (long long) outer_n * outer_stride + (long long) tile_n * FFT_C;
         double2 *abase_n = PK ? ga.alt + (long long) outer_n * ga.alt_outer + (long long) tile_n * FFT_C : nullptr;
         FFT_FETCH(base_n, abase_n)
-        if(MODE == 0)
+        if(MODE == 0 || MODE == 3)
             fft_lines<N, -1>(buf, Wl);
         if(MODE == 2) {
             /* potential_transfer, gravpm.cpp:378-444, applied as the forward transform stores its last
@@ -540,15 +620,29 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
             fft_lines<N, -1>(buf, Wl, green);
             fft_lines<N, +1>(buf, Wl);
         }
-        if(MODE == 1)
+        if(MODE == 1 || MODE == 4)
             fft_lines<N, +1>(buf, Wl);
-        for(int e = threadIdx.x; e < FFT_C * N; e += FFT_T) {
-            const int row = e / FFT_C, col = e - row * FFT_C;
-            if(PK == 1)
-                abase[(long long) (row / ga.nyl) * ga.qstride + (long long) (row % ga.nyl) * es + col] = buf[col * LS + lx<N>(row)];
-            else
-                base[(long long) row * es + col] = buf[col * LS + lx<N>(row)];
-        }
+        FFT_TFETCH(outer_n, tile_n)
+        if(MODE == 3) { /* the spectrum back in place; the density's P(k) on the way */
+            const int y = ga.y0 + outer, z0 = tile * FFT_C;
+            const int ky = y <= N / 2 ? y : y - N;
+            for(int e = threadIdx.x; e < FFT_C * N; e += FFT_T) {
+                const int row = e / FFT_C, col = e - row * FFT_C;
+                const double2 v = buf[col * LS + lx<N>(row)];
+                base[(long long) row * es + col] = v;
+                if(pk) {
+                    const int kx = row <= N / 2 ? row : row - N;
+                    pk_add<N>(hist, ga, v, row, y, z0 + col, kx * kx + ky * ky + (z0 + col) * (z0 + col));
+                }
+            }
+        } else
+            for(int e = threadIdx.x; e < FFT_C * N; e += FFT_T) {
+                const int row = e / FFT_C, col = e - row * FFT_C;
+                if(PK == 1)
+                    abase[(long long) (row / ga.nyl) * ga.qstride + (long long) (row % ga.nyl) * es + col] = buf[col * LS + lx<N>(row)];
+                else
+                    base[(long long) row * es + col] = buf[col * LS + lx<N>(row)];
+            }
         if(!more)
             break;
         __syncthreads(); /* everyone has read its results out of LDS before the next tile lands there */
@@ -559,6 +653,17 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
         abase = abase_n;
     }
 #undef FFT_FETCH
+#undef FFT_TFETCH
+    if(pk) { /* one atomic per non-empty bin, as pm_power_kernel */
+        __syncthreads();
+        unsigned long long *nmodes = reinterpret_cast<unsigned long long *>(ga.ps + 2 * N);
+        for(int i = threadIdx.x; i < N; i += FFT_T)
+            if(hist[2 * N + i] != 0) {
+                atomicAdd(&ga.ps[i], hist[i]);
+                atomicAdd(&ga.ps[N + i], hist[N + i]);
+                atomicAdd(&nmodes[i], (unsigned long long) hist[2 * N + i]);
+            }
+    }
 }
 
 /* ---- the transposing pipeline (round 4; the undivided PM of shq_pm_run / shq_treepm_step) ------------------------------------
@@ -736,28 +841,6 @@ __global__ __launch_bounds__(FFT_T) void fft_t_z_inv(const double2 *__restrict__
         t = tn;
     }
 #undef FFT_FETCH
-}
-
-/* powerspectrum_add_mode (gravpm.cpp:323-356) of one mode into a workgroup's LDS histogram [3][N]: the operations of pm_power_kernel
- * (pm.hip).  The zero mode sets Norm; pad columns z > N / 2 are not modes. */
-template <int N>
-__device__ __forceinline__ void pk_add(double *hist, const GreenArgs &ga, double2 v, int x, int y, int z, int k2)
-{
-    if(z > N / 2)
-        return;
-    const double m = v.x * v.x + v.y * v.y;
-    if(k2 == 0) {
-        ga.ps[3 * N] = m;
-        return;
-    }
-    const int kint = ga.bintab[k2];
-    if(kint >= N)
-        return;
-    const double f = ga.sinctab[x] * ga.sinctab[y] * ga.sinctab[z];
-    const double w = (z == 0 || z == N / 2) ? 1.0 : 2.0;
-    atomicAdd(&hist[kint], w * m * f * f);
-    atomicAdd(&hist[N + kint], w * sqrt((double) k2));
-    atomicAdd(&hist[2 * N + kint], w);
 }
 
 /* Y and X passes on contiguous tiles.  Tile t = (o, zb), o = t / nzb: N rows of 4 columns at src + t * 4 N.  MODE as in fft_pass_strided,
@@ -1011,7 +1094,8 @@ int run_t(shq_context *ctx, double *d_mesh, double *d_scratch, int zp, bool from
 
 /* stage 0 / 1 / 2 as shq_fft3d_run on a full cube (nslab = N).  Slab stages for a distributed mesh:
  * 10: Z forward + Y forward on `nslab` x-planes [nslab][N][zp];  11: Y inverse + Z inverse on them;
- * 12: X forward + potential_transfer + X inverse on a y-slab [N][nslab][zpc] (lines along the slowest axis). */
+ * 12: X forward + potential_transfer + X inverse on a y-slab [N][nslab][zpc] (lines along the slowest axis);
+ * 15, 16: stage 12 split in two - X forward with the P(k) sums (MODE 3), then T, potential_transfer and X inverse (MODE 4). */
 template <int N>
 int run_n(shq_context *ctx, double *d_mesh, int zp, int stage, bool from_i64, double inv_scale, const GreenArgs &ga, int nslab)
 {
@@ -1062,6 +1146,36 @@ int run_n(shq_context *ctx, double *d_mesh, int zp, int stage, bool from_i64, do
     const unsigned xcdk = getenv("SHQ_FFT_XCD_K") ? (unsigned) atoi(getenv("SHQ_FFT_XCD_K")) : 8u;
     if(stage == 12) { /* lines along x of a y-slab: element stride nslab * zpc, outer = local y */
         fft_pass_strided<N, 2><<<gs, dim3(FFT_T), lds, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        SHQ_HIP(hipGetLastError());
+        return SHQ_OK;
+    }
+    if(stage == 15 || stage == 16) {
+        /* the split X pass: resident counts of its own (as fft_t_tile's res_x3 / res_x4), so that the histogram's LDS does not shrink
+         * the grids of the passes above */
+        constexpr size_t lds_hist = lds + sizeof(double) * 3 * N;
+        static unsigned res_x3 = 0, res_x4 = 0;
+        if(res_x3 == 0) {
+            const void *fx[2] = {(const void *) fft_pass_strided<N, 3>, (const void *) fft_pass_strided<N, 4>};
+            int ncu = 0;
+            if(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || ncu < 1)
+                ncu = 256;
+            unsigned occ[2];
+            for(int i = 0; i < 2; i++) {
+                if(lds_hist > 48 * 1024)
+                    SHQ_HIP(hipFuncSetAttribute(fx[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_hist));
+                int per_cu = 0;
+                if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fx[i], FFT_T, lds_hist) != hipSuccess || per_cu < 1)
+                    per_cu = 1;
+                occ[i] = (unsigned) per_cu * (unsigned) ncu;
+            }
+            res_x4 = occ[1];
+            res_x3 = occ[0];
+        }
+        const size_t l = ga.ps ? lds_hist : lds;
+        if(stage == 15)
+            fft_pass_strided<N, 3><<<grid(stot, res_x3), dim3(FFT_T), l, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        else
+            fft_pass_strided<N, 4><<<grid(stot, res_x4), dim3(FFT_T), l, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
         SHQ_HIP(hipGetLastError());
         return SHQ_OK;
     }
@@ -1241,9 +1355,21 @@ int shq_fft3d_run_slab(shq_context *ctx, double *d_mesh, int N, int zp, int stag
 int shq_fft3d_run_slab_packed(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale,
                               const double *d_sinctab, double asmth2, double pot_factor, int nslab, int y0, double *d_packed, int nranks)
 {
+    return shq_fft3d_run_slab_x(ctx, d_mesh, N, zp, stage, from_i64, inv_scale, d_sinctab, asmth2, pot_factor, nslab, y0, d_packed, nranks,
+                                nullptr, 0, nullptr, nullptr);
+}
+
+/* every slab stage; stages 15 / 16 (the split X pass of a y-slab) take modefac / fac_mask, bintab and ps as in GreenArgs: stage 16 needs a
+ * factor table (at least the one entry {1.0} with fac_mask = 0) */
+int shq_fft3d_run_slab_x(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale, const double *d_sinctab,
+                         double asmth2, double pot_factor, int nslab, int y0, double *d_packed, int nranks, const double *d_modefac, int fac_mask,
+                         const int32_t *d_bintab, double *d_ps)
+{
+    const bool yslab = stage == 12 || stage == 15 || stage == 16;
     SHQ_CHECK(shq_fft3d_supported(N), SHQ_ERR_INVALID, "fft3d: unsupported mesh size %d", N);
-    SHQ_CHECK(nslab > 0 && nslab <= N && y0 >= 0 && y0 + (stage == 12 ? nslab : 0) <= N, SHQ_ERR_INVALID, "fft3d: bad slab geometry");
+    SHQ_CHECK(nslab > 0 && nslab <= N && y0 >= 0 && y0 + (yslab ? nslab : 0) <= N, SHQ_ERR_INVALID, "fft3d: bad slab geometry");
     SHQ_CHECK(zp >= N + 2 && zp % 8 == 0, SHQ_ERR_INVALID, "fft3d: pitch %d must be a multiple of 8 doubles and >= N+2", zp);
+    SHQ_CHECK((stage != 16 || d_modefac) && (!d_ps || d_bintab), SHQ_ERR_INVALID, "fft3d: bad split X pass arguments");
     SHQ_TRY(ensure_twiddles(ctx, N));
     GreenArgs ga;
     ga.sinctab = d_sinctab;
@@ -1254,10 +1380,10 @@ int shq_fft3d_run_slab_packed(shq_context *ctx, double *d_mesh, int N, int zp, i
     ga.alt = reinterpret_cast<double2 *>(d_packed);
     ga.nyl = 1;
     ga.qstride = ga.alt_outer = 0;
-    ga.modefac = nullptr;
-    ga.fac_mask = 0;
-    ga.bintab = nullptr;
-    ga.ps = nullptr;
+    ga.modefac = d_modefac;
+    ga.fac_mask = fac_mask;
+    ga.bintab = d_bintab;
+    ga.ps = d_ps;
     if(stage == 13 || stage == 14) {
         SHQ_CHECK(d_packed && nranks >= 1 && N % nranks == 0, SHQ_ERR_INVALID, "fft3d: packed stages need a buffer and a rank count that divides the mesh");
         ga.nyl = N / nranks;

@@ -426,6 +426,38 @@ static int pm_prepare(shq_context *ctx, int N)
 
 namespace {
 
+/* one mode into a workgroup's LDS histogram [3][nbins] (power, kk, modes); the zero mode sets Norm (pm_power_kernel below) */
+__device__ __forceinline__ void pm_power_add(double *hist, int nbins, int N, const int32_t *__restrict__ bintab, const double *__restrict__ sinctab,
+                                             double *norm, double2 v, int x, int y, int kz, long long k2)
+{
+    const double m = v.x * v.x + v.y * v.y;
+    if(k2 == 0) {
+        *norm = m;
+        return;
+    }
+    const int kint = bintab[k2];
+    if(kint >= nbins)
+        return;
+    const double f = sinctab[x] * sinctab[y] * sinctab[kz];
+    const double w = (kz == 0 || kz == N / 2) ? 1.0 : 2.0;
+    atomicAdd(&hist[kint], w * m * f * f);
+    atomicAdd(&hist[nbins + kint], w * sqrt((double) k2));
+    atomicAdd(&hist[2 * nbins + kint], w);
+}
+
+/* the workgroup's histogram into the sums: one atomic per non-empty bin */
+__device__ __forceinline__ void pm_power_flush(const double *hist, int nbins, double *power, double *kk, unsigned long long *nmodes)
+{
+    __syncthreads();
+    for(int i = threadIdx.x; i < nbins; i += blockDim.x) {
+        if(hist[2 * nbins + i] != 0) {
+            atomicAdd(&power[i], hist[i]);
+            atomicAdd(&kk[i], hist[nbins + i]);
+            atomicAdd(&nmodes[i], (unsigned long long) hist[2 * nbins + i]);
+        }
+    }
+}
+
 /* powerspectrum_add_mode (libgadget/gravpm.cpp:323-356) through measure_power_spectrum / potential_transfer
  * (:360-376, :430): every mode of the density half spectrum adds w |delta_k|^2 f^2 (f = the CIC
  * deconvolution, w = 1 on the kz = 0 and Nmesh/2 planes, else 2), w and w |k| to bin
@@ -469,28 +501,38 @@ __global__ __launch_bounds__(256) void pm_power_kernel(const double2 *__restrict
             v.x *= t;
             v.y *= t;
         }
-        const double m = v.x * v.x + v.y * v.y;
-        if(k2 == 0) {
-            *norm = m;
-            continue;
-        }
-        const int kint = bintab[k2];
-        if(kint >= nbins)
-            continue;
-        const double f = sinctab[x] * sinctab[y] * sinctab[z];
-        const double w = (kz == 0 || kz == N / 2) ? 1.0 : 2.0;
-        atomicAdd(&hist[kint], w * m * f * f);
-        atomicAdd(&hist[nbins + kint], w * sqrt((double) k2));
-        atomicAdd(&hist[2 * nbins + kint], w);
+        pm_power_add(hist, nbins, N, bintab, sinctab, norm, v, x, y, kz, k2);
     }
+    pm_power_flush(hist, nbins, power, kk, nmodes);
+}
+
+/* the same sums on the transposed spectrum of a y-slab, [ylocal][z' <= N/2][x] (the torch route of the sharded PM, shq_pm_slab_green's
+ * layout); T: the modes multiplied by T[k2] first.  Only the rank whose slab holds y = 0 meets the zero mode and writes Norm. */
+__global__ __launch_bounds__(256) void pm_power_slab_kernel(const double2 *__restrict__ c, int N, int y0, int nyl, const double *__restrict__ sinctab,
+                                                            const int32_t *__restrict__ bintab, double *power, double *kk,
+                                                            unsigned long long *nmodes, double *norm, const double *__restrict__ T)
+{
+    extern __shared__ double hist[];
+    const int nbins = N, Nc = N / 2 + 1;
+    for(int i = threadIdx.x; i < 3 * nbins; i += blockDim.x)
+        hist[i] = 0;
     __syncthreads();
-    for(int i = threadIdx.x; i < nbins; i += blockDim.x) {
-        if(hist[2 * nbins + i] != 0) {
-            atomicAdd(&power[i], hist[i]);
-            atomicAdd(&kk[i], hist[nbins + i]);
-            atomicAdd(&nmodes[i], (unsigned long long) hist[2 * nbins + i]);
+    const size_t total = (size_t) nyl * Nc * N;
+    for(size_t ip = (size_t) blockIdx.x * blockDim.x + threadIdx.x; ip < total; ip += (size_t) gridDim.x * blockDim.x) {
+        const int x = (int) (ip % N);
+        const size_t yz = ip / N;
+        const int z = (int) (yz % Nc), y = y0 + (int) (yz / Nc);
+        const int kx = x <= N / 2 ? x : x - N, ky = y <= N / 2 ? y : y - N;
+        const long long k2 = (long long) kx * kx + (long long) ky * ky + (long long) z * z;
+        double2 v = c[ip];
+        if(T && k2 != 0) {
+            const double t = T[k2];
+            v.x *= t;
+            v.y *= t;
         }
+        pm_power_add(hist, nbins, N, bintab, sinctab, norm, v, x, y, z, k2);
     }
+    pm_power_flush(hist, nbins, power, kk, nmodes);
 }
 
 /* the bin table of Nmesh N and the sums zeroed on the stream */
@@ -796,6 +838,8 @@ extern "C" int shq_pm_measure_power(shq_context *ctx, int enable)
     return SHQ_OK;
 }
 
+extern "C" int shq_pm_get_measure_power(shq_context *ctx) { return ctx ? (ctx->pm_measure_power ? 1 : 0) : -1; }
+
 extern "C" int shq_pm_set_mode_factor(shq_context *ctx, int Nmesh, const double *table)
 {
     SHQ_CHECK(ctx, SHQ_ERR_INVALID, "null context");
@@ -828,8 +872,8 @@ extern "C" int shq_pm_download_power(shq_context *ctx, int size, double *kk, dou
     if(ctx)
         SHQ_TRY(shq_join_pm(ctx));
     SHQ_CHECK(ctx && kk && power && nmodes && norm, SHQ_ERR_INVALID, "null argument");
-    SHQ_CHECK(ctx->have_power && (ctx->have_pm_result || ctx->pm_spec_pending), SHQ_ERR_STATE,
-              "pm_download_power: enable shq_pm_measure_power before the PM run, or call shq_pm_forward");
+    SHQ_CHECK(ctx->have_power && (ctx->have_pm_result || ctx->pm_spec_pending || ctx->ps_slab), SHQ_ERR_STATE,
+              "pm_download_power: enable shq_pm_measure_power before the PM run, or call shq_pm_forward or a slab X forward");
     SHQ_CHECK(size == ctx->ps_nbins, SHQ_ERR_INVALID, "pm_download_power: size %d, the spectrum has %d bins (= Nmesh)", size, ctx->ps_nbins);
     const int nb = ctx->ps_nbins;
     std::vector<double> h(3 * (size_t) nb + 1);
@@ -1067,6 +1111,8 @@ extern "C" int shq_pm_slab_deposit(shq_context *ctx, const shq_pm_params *pm, in
         SHQ_TRY(shq_join_pm(ctx));
     SHQ_CHECK(ctx && pm && d_mesh_i64, SHQ_ERR_INVALID, "null argument");
     SHQ_CHECK(ctx->have_parts, SHQ_ERR_STATE, "pm_slab_deposit: particles must be uploaded first");
+    SHQ_CHECK(pm_all_types(ctx->pm_typemask) || ctx->have_types, SHQ_ERR_STATE,
+              "pm_slab_deposit: deposit type mask 0x%x, but the particles came without their Type", (unsigned) ctx->pm_typemask);
     const int N = pm->Nmesh;
     SHQ_CHECK(N >= 4 && N % 2 == 0 && nplanes > 0 && nplanes <= N && plane0 >= 0 && plane0 < N, SHQ_ERR_INVALID, "bad slab geometry");
     SHQ_HIP(hipSetDevice(ctx->device));
@@ -1079,7 +1125,7 @@ extern "C" int shq_pm_slab_deposit(shq_context *ctx, const shq_pm_params *pm, in
     if(n > 0)
         pm_deposit_kernel<<<dim3((unsigned) ((n + DEP_CHUNK - 1) / DEP_CHUNK)), dim3(256), 0, ctx->stream>>>(
             ctx->posm.ptr, ctx->pflags.ptr, n, (unsigned long long *) d_mesh_i64, N, N + 2, pm->BoxSize / N, ldexp(1.0, ctx->pm_log2scale),
-            plane0, nalloc, ctx->pm_oob.ptr, pm_xcdk(1), ~0u);
+            plane0, nalloc, ctx->pm_oob.ptr, pm_xcdk(1), (unsigned) ctx->pm_typemask);
     SHQ_HIP(hipGetLastError());
     return check_oob(ctx, "pm_slab_deposit");
 }
@@ -1110,7 +1156,7 @@ extern "C" int shq_pm_slab_readout(shq_context *ctx, const shq_pm_params *pm, in
 /* potential_transfer (gravpm.cpp:378-444) on the transposed spectrum of a y-slab:
  * layout [ylocal][z' <= N/2][x], x fastest — the reference's own Fourier layout (petapm.cpp:243-282). */
 __global__ __launch_bounds__(256) void pm_green_slab_kernel(double2 *c, int N, int Nc, int y0, int nyl, const double *__restrict__ sinctab,
-                                                            double asmth2, double pot_factor)
+                                                            double asmth2, double pot_factor, const double *__restrict__ T = nullptr)
 {
     const size_t total = (size_t) nyl * Nc * N;
     const size_t ip = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
@@ -1128,6 +1174,11 @@ __global__ __launch_bounds__(256) void pm_green_slab_kernel(double2 *c, int N, i
         v.x = 0;
         v.y = 0;
     } else {
+        if(T) { /* shq_pm_slab_xfinish: (v T) green, potential_transfer's order (gravpm.cpp:412-443) */
+            const double t = T[k2];
+            v.x *= t;
+            v.y *= t;
+        }
         double f = 1.0;
         const double smth = exp(-(double) k2 * asmth2) / (double) k2;
         f *= sinctab[x];
@@ -1138,6 +1189,85 @@ __global__ __launch_bounds__(256) void pm_green_slab_kernel(double2 *c, int N, i
         v.y *= fac;
     }
     c[ip] = v;
+}
+
+/* The sharded PM with a global_analysis hook (MassiveNuLinRespOn, gravpm.cpp:76-85, 308-321, 412-435): its X step in two halves around
+ * the caller's all-reduce of the sums (powerspectrum_sum) and its table.  Helpers of both routes below. */
+static int slab_x_check(shq_context *ctx, const shq_pm_params *pm, const void *d_spec, int y0, int nyl, bool bespoke)
+{
+    SHQ_CHECK(ctx && pm && d_spec, SHQ_ERR_INVALID, "null argument");
+    const int N = pm->Nmesh;
+    SHQ_CHECK(N >= 4 && N % 2 == 0 && nyl > 0 && y0 >= 0 && y0 + nyl <= N, SHQ_ERR_INVALID, "bad slab geometry");
+    SHQ_CHECK(!bespoke || shq_fft3d_supported(N), SHQ_ERR_INVALID, "pm_slab2: mesh size %d has no bespoke FFT", N);
+    SHQ_TRY(shq_join_pm(ctx));
+    SHQ_HIP(hipSetDevice(ctx->device));
+    return slab_sinctab(ctx, N);
+}
+
+/* the factor table on the device: the caller's T[k2] (3 (N/2)^2 + 1 entries, host), or the one entry {1.0} (*mask = 0) for NULL */
+static int slab_x_table(shq_context *ctx, int N, const double *table, const double **fac, int *mask)
+{
+    if(table) {
+        const size_t nk2 = 3 * (size_t) (N / 2) * (N / 2) + 1;
+        SHQ_TRY(ctx->slab_fac.reserve(nk2));
+        /* on the stream, behind the last finish that read the table; the host array is free when the call returns */
+        SHQ_HIP(hipMemcpyAsync(ctx->slab_fac.ptr, table, nk2 * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        SHQ_HIP(hipStreamSynchronize(ctx->stream));
+        *fac = ctx->slab_fac.ptr;
+        *mask = -1;
+    } else {
+        static const double one = 1.0;
+        SHQ_TRY(ctx->pm_fac_one.reserve(1));
+        SHQ_HIP(hipMemcpyAsync(ctx->pm_fac_one.ptr, &one, sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+        *fac = ctx->pm_fac_one.ptr;
+        *mask = 0;
+    }
+    return SHQ_OK;
+}
+
+/* the sums of the slab's part of the spectrum on the torch route's layout, into the context's zeroed sums */
+static int slab_power_sweep(shq_context *ctx, int N, int y0, int nyl, const void *d_spec, const double *T)
+{
+    double *power = ctx->ps_sums.ptr, *kk = power + N, *norm = power + 3 * N;
+    unsigned long long *nmodes = reinterpret_cast<unsigned long long *>(power + 2 * N);
+    const size_t lds = sizeof(double) * 3 * N;
+    if(lds > 48 * 1024)
+        SHQ_HIP(hipFuncSetAttribute((const void *) pm_power_slab_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+    pm_power_slab_kernel<<<dim3(2048), dim3(256), lds, ctx->stream>>>((const double2 *) d_spec, N, y0, nyl, ctx->sinctab.ptr,
+                                                                     ctx->ps_bintab.ptr, power, kk, nmodes, norm, T);
+    SHQ_HIP(hipGetLastError());
+    return SHQ_OK;
+}
+
+/* torch route: the sums of the density on the transposed spectrum [ylocal][z' <= N/2][x] after the caller's X forward */
+extern "C" int shq_pm_slab_xforward(shq_context *ctx, const shq_pm_params *pm, int y0, int nyl, void *d_spec)
+{
+    SHQ_TRY(slab_x_check(ctx, pm, d_spec, y0, nyl, false));
+    SHQ_TRY(pm_power_prepare(ctx, pm->Nmesh));
+    SHQ_TRY(slab_power_sweep(ctx, pm->Nmesh, y0, nyl, d_spec, nullptr));
+    ctx->ps_slab = true;
+    return SHQ_OK;
+}
+
+/* torch route: (v T) green on that layout (shq_pm_slab_green with the factor); with shq_pm_measure_power the sums of v T */
+extern "C" int shq_pm_slab_xfinish(shq_context *ctx, const shq_pm_params *pm, int y0, int nyl, void *d_spec, const double *table)
+{
+    SHQ_TRY(slab_x_check(ctx, pm, d_spec, y0, nyl, false));
+    const int N = pm->Nmesh, Nc = N / 2 + 1;
+    const double *T = nullptr;
+    int mask = 0;
+    if(table)
+        SHQ_TRY(slab_x_table(ctx, N, table, &T, &mask));
+    if(ctx->pm_measure_power) {
+        SHQ_TRY(pm_power_prepare(ctx, N));
+        SHQ_TRY(slab_power_sweep(ctx, N, y0, nyl, d_spec, T));
+        ctx->ps_slab = true;
+    }
+    const size_t tot = (size_t) nyl * Nc * N;
+    pm_green_slab_kernel<<<dim3((unsigned) ((tot + 255) / 256)), dim3(256), 0, ctx->stream>>>(
+        (double2 *) d_spec, N, Nc, y0, nyl, ctx->sinctab.ptr, pow((2 * M_PI) * pm->Asmth / N, 2), -pm->G / (M_PI * pm->BoxSize), T);
+    SHQ_HIP(hipGetLastError());
+    return SHQ_OK;
 }
 
 extern "C" int shq_pm_slab_green(shq_context *ctx, const shq_pm_params *pm, int y0, int nyl, void *d_spec)
@@ -1173,6 +1303,8 @@ extern "C" int shq_pm_slab2_deposit_ghosts(shq_context *ctx, const shq_pm_params
         SHQ_TRY(shq_join_pm(ctx));
     SHQ_CHECK(ctx && pm && d_mesh_i64, SHQ_ERR_INVALID, "null argument");
     SHQ_CHECK(ctx->have_parts, SHQ_ERR_STATE, "pm_slab2_deposit: particles must be uploaded first");
+    SHQ_CHECK(pm_all_types(ctx->pm_typemask) || ctx->have_types, SHQ_ERR_STATE,
+              "pm_slab2_deposit: deposit type mask 0x%x, but the particles came without their Type", (unsigned) ctx->pm_typemask);
     const int N = pm->Nmesh;
     SHQ_CHECK(shq_fft3d_supported(N), SHQ_ERR_INVALID, "pm_slab2: mesh size %d has no bespoke FFT", N);
     SHQ_CHECK(nplanes > 0 && nplanes <= N && plane0 >= 0 && plane0 < N && xoff >= 0 && xoff + nplanes <= nalloc && nalloc <= N + 8 &&
@@ -1191,7 +1323,7 @@ extern "C" int shq_pm_slab2_deposit_ghosts(shq_context *ctx, const shq_pm_params
     if(n > 0)
         pm_deposit_kernel<<<dim3((unsigned) ((n + DEP_CHUNK - 1) / DEP_CHUNK)), dim3(256), 0, ctx->stream>>>(
             ctx->posm.ptr, ctx->pflags.ptr, n, (unsigned long long *) d_mesh_i64, N, zp, pm->BoxSize / N, ldexp(1.0, ctx->pm_log2scale),
-            plane0 - xoff, nfit, ctx->pm_oob.ptr, pm_xcdk(1), ~0u);
+            plane0 - xoff, nfit, ctx->pm_oob.ptr, pm_xcdk(1), (unsigned) ctx->pm_typemask);
     SHQ_HIP(hipGetLastError());
     return check_oob(ctx, "pm_slab2_deposit");
 }
@@ -1240,6 +1372,37 @@ extern "C" int shq_pm_slab2_xgreen(shq_context *ctx, const shq_pm_params *pm, vo
     SHQ_TRY(slab_sinctab(ctx, N));
     return shq_fft3d_run_slab(ctx, (double *) d_spec, N, shq_fft3d_pitch(N), 12, false, 1.0, ctx->sinctab.ptr,
                               pow((2 * M_PI) * pm->Asmth / N, 2), -pm->G / (M_PI * pm->BoxSize), nyl, y0);
+}
+
+/* the X forward of the y-slab, the spectrum left in place, and this slab's raw P(k) sums (fft_pass_strided MODE 3) */
+extern "C" int shq_pm_slab2_xforward(shq_context *ctx, const shq_pm_params *pm, void *d_spec, int y0, int nyl)
+{
+    SHQ_TRY(slab_x_check(ctx, pm, d_spec, y0, nyl, true));
+    const int N = pm->Nmesh;
+    SHQ_TRY(pm_power_prepare(ctx, N));
+    SHQ_TRY(shq_fft3d_run_slab_x(ctx, (double *) d_spec, N, shq_fft3d_pitch(N), 15, false, 1.0, ctx->sinctab.ptr, pow((2 * M_PI) * pm->Asmth / N, 2),
+                                 -pm->G / (M_PI * pm->BoxSize), nyl, y0, nullptr, 1, nullptr, 0, ctx->ps_bintab.ptr, ctx->ps_sums.ptr));
+    ctx->ps_slab = true;
+    return SHQ_OK;
+}
+
+/* (v T) green and the X inverse of that spectrum (fft_pass_strided MODE 4); with shq_pm_measure_power the sums of v T */
+extern "C" int shq_pm_slab2_xfinish(shq_context *ctx, const shq_pm_params *pm, void *d_spec, int y0, int nyl, const double *table)
+{
+    SHQ_TRY(slab_x_check(ctx, pm, d_spec, y0, nyl, true));
+    const int N = pm->Nmesh;
+    const double *fac = nullptr;
+    int mask = 0;
+    SHQ_TRY(slab_x_table(ctx, N, table, &fac, &mask));
+    const bool measure = ctx->pm_measure_power;
+    if(measure)
+        SHQ_TRY(pm_power_prepare(ctx, N));
+    SHQ_TRY(shq_fft3d_run_slab_x(ctx, (double *) d_spec, N, shq_fft3d_pitch(N), 16, false, 1.0, ctx->sinctab.ptr, pow((2 * M_PI) * pm->Asmth / N, 2),
+                                 -pm->G / (M_PI * pm->BoxSize), nyl, y0, nullptr, 1, fac, mask, ctx->ps_bintab.ptr,
+                                 measure ? ctx->ps_sums.ptr : nullptr));
+    if(measure)
+        ctx->ps_slab = true;
+    return SHQ_OK;
 }
 
 extern "C" int shq_pm_slab2_readout(shq_context *ctx, const shq_pm_params *pm, int plane0, int nplanes, int xoff, int nalloc,

@@ -161,6 +161,26 @@ class Comm:
         dist.all_reduce(t, group=self.group)
         return float(t.item())
 
+    def allreduce_sum_vec(self, a):
+        """Element-wise sum over the ranks of a 1-D numpy array, in its own dtype (float64 or int64); every rank gets the same array."""
+        a = np.ascontiguousarray(a)
+        if not self.multi:
+            return a.copy()
+        t = torch.from_numpy(a.copy())
+        if self.backend == "nccl":
+            t = t.cuda()
+        dist.all_reduce(t, group=self.group)
+        return t.cpu().numpy()
+
+    def allreduce_power(self, sums):
+        """powerspectrum_sum (powerspectrum.cpp:53-88): the raw P(k) sums (kk, power, nmodes, Norm) of every rank added up - kk, power
+        and Norm as float64, nmodes as int64."""
+        kk, power, nmodes, norm = sums
+        nb = len(kk)
+        f = self.allreduce_sum_vec(np.concatenate([np.asarray(kk, np.float64), np.asarray(power, np.float64), [float(norm)]]))
+        m = self.allreduce_sum_vec(np.asarray(nmodes, np.int64))
+        return f[:nb], f[nb:2 * nb], m, float(f[2 * nb])
+
     def barrier(self):
         if self.size > 1:
             dist.barrier(group=self.group)
@@ -304,13 +324,26 @@ def cost_balanced_bounds(comm, drv, subplane=False):
                            plane_cost=COST_MS_PER_CELL * float(drv.N) ** 2, y=drv.local[:, 1] if subplane else None)
 
 
-def exchange_to_owner(comm, decomp, posm):
-    """Domain exchange: send every particle (rows x, y, z, m) to the rank owning its slab."""
+def exchange_to_owner(comm, decomp, posm, types=None):
+    """Domain exchange: send every particle (rows x, y, z, m) to the rank owning its slab.  With types (one integer per row) the
+    rows' types travel with them and (posm, types) comes back."""
     owner = decomp.owner_of(posm[:, 0], posm[:, 1])
     order = torch.argsort(owner, stable=True)
     counts = torch.bincount(owner, minlength=comm.size).tolist()
-    recv, _ = comm.all_to_all_rows(posm[order], counts)
-    return recv
+    if types is None:
+        recv, _ = comm.all_to_all_rows(posm[order], counts)
+        return recv
+    recv, _ = comm.all_to_all_rows(_with_types(posm, types)[order], counts)
+    return _split_types(recv, types.dtype)
+
+
+def _with_types(posm, types):
+    """rows (x, y, z, m, type): the type as a fifth column (exact in float64) so that it travels with its row"""
+    return torch.cat([posm, types.to(device=posm.device, dtype=posm.dtype)[:, None]], dim=1)
+
+
+def _split_types(rows, dtype):
+    return rows[:, :4].contiguous(), rows[:, 4].to(dtype)
 
 
 def ghost_exchange(comm, decomp, posm, halo):
@@ -344,19 +377,43 @@ class SlabPM:
         self.comm, self.ops = comm, ops
         self.N, self.L, self.Asmth, self.G = Nmesh, BoxSize, Asmth, G
         self.d = SlabDecomp(comm, Nmesh, BoxSize, bounds, ycuts)
+        self.power = self.power_finish = None
 
-    def force(self, hooks=()):
+    def force(self, hooks=(), analysis=None, measure_power=False):
         """Runs one PM step for the particles loaded in `ops`; results stay in ops (gravpm, potential).
         hooks: up to two callables that queue work independent of the PM (pieces of the tree walk); the bespoke pipeline
         calls them right after starting its first and its second mesh transpose, so that work runs while the spectrum
-        travels."""
+        travels.
+        analysis: gravpm_force's global_analysis hook (MassiveNuLinRespOn, gravpm.cpp:76-85, 308-321) - the X step splits in two:
+        X forward with this rank's raw P(k) sums, their sum over the ranks (powerspectrum_sum), then on every rank
+        analysis(kk, power, nmodes, norm) -> T (3 (Nmesh/2)^2 + 1 factors by integer k2, or None for 1), and (v T) green + X inverse.
+        measure_power: the finish also takes the sums of v T (potential_transfer's); without analysis the split runs with T = 1.
+        The reduced sums stay on the object, the same on every rank: self.power (the density's) and self.power_finish (v T's, when
+        measuring); each is (kk, power, nmodes, norm), scaling Norm is the caller's.  With analysis the first hook is queued
+        right after the return transpose has started, beside the second: the P(k) round trip waits for the stream, and would wait for
+        a walk piece queued before it."""
+        split = analysis is not None or measure_power
+        self.power = self.power_finish = None
+        xstep = (lambda spec_t, y0, nyl, xfwd, xfin: self._xsplit(spec_t, y0, nyl, xfwd, xfin, analysis, measure_power)) if split else None
         if getattr(self.ops, "pitch", None) is not None and self.ops.pitch() > 0 and os.environ.get("SHQ_SLAB_TORCH_FFT", "0") != "1":
-            return self._force_bespoke(list(hooks))
-        self._force_torch()
+            return self._force_bespoke(list(hooks), xstep)
+        self._force_torch(xstep)
         for h in hooks:
             h()
 
-    def _force_bespoke(self, hooks=()):
+    def _xsplit(self, spec_t, y0, nyl, xforward, xfinish, analysis, measure_power):
+        """the split X step: this rank's sums, their all-reduce, the caller's table, the finish (and its sums, all-reduced)"""
+        self.power = self.comm.allreduce_power(xforward(spec_t, y0, nyl))
+        T = analysis(*self.power) if analysis is not None else None
+        if T is not None:
+            T = np.ascontiguousarray(T, dtype=np.float64)
+            if T.shape != (3 * (self.N // 2) ** 2 + 1,):
+                raise ValueError("analysis must return 3 (Nmesh/2)^2 + 1 factors (got shape %s)" % (T.shape,))
+        fin = xfinish(spec_t, y0, nyl, T, measure_power)
+        if measure_power:
+            self.power_finish = self.comm.allreduce_power(fin)
+
+    def _force_bespoke(self, hooks=(), xstep=None):
         """The slab pipeline on the library's own FFT passes (csrc/fft3d.hip): ONE buffer [nalloc][N][zp] is the
         int64 deposit mesh, the (y, z) half spectrum and the potential, ghost planes in place; the blocks the
         all-to-all delivers are transformed along x as they are (x slowest), fused with the Green's function.
@@ -384,6 +441,9 @@ class SlabPM:
             ops.fft_yz(own, nxl, 0)
         spec = own.view(torch.float64).view(torch.complex128)               # [nxl, N, zpc]
         hooks = list(hooks) + [None, None]
+        first = hooks[0]
+        if xstep is not None:
+            hooks[0] = None          # queued beside hooks[1] instead, behind the return transpose (force())
         if multi:
             if not fused:
                 send = spec.reshape(nxl, P, nyl, zpc).permute(1, 0, 2, 3).reshape(P * nxl, nyl, zpc)   # rows [dest q][x_l]
@@ -396,9 +456,15 @@ class SlabPM:
             if hooks[0]:
                 hooks[0]()
             spec_t = spec
-        ops.xgreen(spec_t, c.rank * nyl, nyl)
+        if xstep is None:
+            ops.xgreen(spec_t, c.rank * nyl, nyl)
+        else:
+            xstep(spec_t, c.rank * nyl, nyl, ops.xforward, ops.xfinish)
+        deferred = first if xstep is not None else None   # behind the return transpose's start, beside the second piece
         if multi:
             pend = c.all_to_all_rows_start(spec_t, self.d.widths, [nxl] * P)                       # rows [src q][x_l]
+            if deferred:
+                deferred()
             if hooks[1]:
                 hooks[1]()
             recv = pend.wait()                                                                     # rows [src q][x_l]
@@ -407,8 +473,11 @@ class SlabPM:
             else:
                 spec.copy_(recv.reshape(P, nxl, nyl, zpc).permute(1, 0, 2, 3).reshape(nxl, N, zpc))
             del recv, pend
-        elif hooks[1]:
-            hooks[1]()
+        else:
+            if deferred:
+                deferred()
+            if hooks[1]:
+                hooks[1]()
         if not fused:
             ops.fft_yz(own, nxl, 1)
         phi = buf.view(torch.float64)
@@ -417,7 +486,7 @@ class SlabPM:
             phi[xoff + nxl:xoff + nxl + pr] = c.shift(phi[xoff:xoff + pr].contiguous(), -1)  # my first 3 (4) -> left rank's right ghosts
         ops.readout2(phi, self.d.plane0, nxl, xoff, nalloc)
 
-    def _force_torch(self):
+    def _force_torch(self, xstep=None):
         """The same pipeline with torch.fft (rocFFT) for mesh sizes without a bespoke transform, and on the
         CPU stand-ins of the gloo tests."""
         c, N, nxl, P = self.comm, self.N, self.d.nxl, self.comm.size
@@ -437,8 +506,11 @@ class SlabPM:
         recv, _ = c.all_to_all_rows(send, [nxl] * P)                                         # rows [src p][x_l] = all x
         spec_t = recv.reshape(N, nyl, Nc).permute(1, 2, 0).contiguous()                      # [y_l][z][x]
         spec_t = torch.fft.fft(spec_t, dim=2)
-        # 3. Green's function / CIC deconvolution on the transposed spectrum
-        self.ops.green(spec_t, c.rank * nyl, nyl)
+        # 3. Green's function / CIC deconvolution on the transposed spectrum (split around the P(k) all-reduce for an analysis hook)
+        if xstep is None:
+            self.ops.green(spec_t, c.rank * nyl, nyl)
+        else:
+            xstep(spec_t, c.rank * nyl, nyl, self.ops.green_forward, self.ops.green_finish)
         # 4. inverse: 1-D along x, transpose back, 2-D c2r
         spec_t = torch.fft.ifft(spec_t, dim=2, norm="forward")
         send = spec_t.permute(2, 0, 1).contiguous()                                          # rows = x planes, in order
@@ -485,14 +557,22 @@ class GpuOps:
         if not self._shared():
             self.ctx.synchronize()
 
-    def set_particles(self, posm_all, nlocal, keep_tree=False):
+    def set_particles(self, posm_all, nlocal, keep_tree=False, types=None):
         """posm_all: device tensor [n, 4] (x, y, z, m), the first nlocal rows are this rank's own.  keep_tree: these are the
-        positions the resident tree was built from (nothing moved since)."""
+        positions the resident tree was built from (nothing moved since).  types: the rows' Types (n integers; without them every
+        row is Type 1 and the deposit type mask must stay SHQ_ALL_TYPES)."""
         t = posm_all.contiguous()
+        ty = None if types is None else types.to(device=t.device, dtype=torch.uint8).contiguous()
         self._before()                  # torch produced t on its stream; the library copies on its own
         capi.check(capi.hip.shq_particles_set_device(self.ctx.h, C.c_void_p(t.data_ptr()), t.shape[0], nlocal, int(keep_tree)))
+        if ty is not None:
+            capi.check(capi.hip.shq_particles_set_device_types(self.ctx.h, C.c_void_p(ty.data_ptr()), ty.shape[0]))
         self._after()
-        self._keep = t
+        self._keep, self._keep_types = t, ty
+
+    def set_deposit_types(self, mask):
+        """shq_pm_set_deposit_types: bit t set = Type t is deposited (capi.ALL_TYPES: all)"""
+        capi.check(capi.hip.shq_pm_set_deposit_types(self.ctx.h, int(mask)))
 
     # ---- phases on the bespoke FFT passes (shq_pm_slab2_*) ----
     def pitch(self):
@@ -527,19 +607,57 @@ class GpuOps:
         assert spec_t.is_contiguous() and spec_t.dtype == torch.complex128
         self._call(capi.hip.shq_pm_slab2_xgreen, C.byref(self.pm), C.c_void_p(spec_t.data_ptr()), y0, nyl)
 
+    def power(self):
+        """this rank's raw P(k) sums of the last X forward / measuring finish: (kk, power, nmodes, norm)"""
+        N = self.N
+        kk, pw, nm, norm = np.zeros(N), np.zeros(N), np.zeros(N, dtype=np.int64), C.c_double()
+        capi.check(capi.hip.shq_pm_download_power(self.ctx.h, N, capi.ptr(kk), capi.ptr(pw), capi.ptr(nm), C.byref(norm)))
+        return kk, pw, nm, norm.value
+
+    def _finish(self, fn, args, table, measure):
+        """the finish with the context's shq_pm_measure_power set to `measure` for the call; the caller's setting is restored after"""
+        tab = None if table is None else np.ascontiguousarray(table, dtype=np.float64)
+        h = self.ctx.h
+        before = int(capi.hip.shq_pm_get_measure_power(h))
+        if before != int(measure):
+            capi.check(capi.hip.shq_pm_measure_power(h, int(measure)))
+        try:
+            self._call(fn, *args, None if tab is None else capi.ptr(tab))
+            return self.power() if measure else None
+        finally:
+            if before != int(measure):
+                capi.check(capi.hip.shq_pm_measure_power(h, before))
+
+    def xforward(self, spec_t, y0, nyl):
+        """X forward of the y-slab in place and this rank's raw P(k) sums of the density (shq_pm_slab2_xforward)"""
+        assert spec_t.is_contiguous() and spec_t.dtype == torch.complex128
+        self._call(capi.hip.shq_pm_slab2_xforward, C.byref(self.pm), C.c_void_p(spec_t.data_ptr()), y0, nyl)
+        return self.power()
+
+    def xfinish(self, spec_t, y0, nyl, table=None, measure=False):
+        """(v T) green and X inverse (shq_pm_slab2_xfinish); with measure the raw sums of v T"""
+        assert spec_t.is_contiguous() and spec_t.dtype == torch.complex128
+        return self._finish(capi.hip.shq_pm_slab2_xfinish, (C.byref(self.pm), C.c_void_p(spec_t.data_ptr()), y0, nyl), table, measure)
+
     def readout2(self, phi, plane0, nxl, xoff, nalloc):
         assert phi.is_contiguous()
         self._call(capi.hip.shq_pm_slab2_readout, C.byref(self.pm), plane0, nxl, xoff, nalloc, C.c_void_p(phi.data_ptr()))
 
+    def hilbert_order(self, posm, L):
+        """the permutation that orders the rows of posm (x, y, z, m) along the Peano-Hilbert curve, on the device (shq_hilbert_order)"""
+        posm = posm.contiguous()
+        n = int(posm.shape[0])
+        order = torch.empty(n, dtype=torch.int64, device=posm.device)
+        if n > 0:
+            self._call(capi.hip.shq_hilbert_order, posm.data_ptr(), n, float(L), order.data_ptr())
+        return order
+
     def hilbert_sorted(self, posm, L):
         """rows of posm (x, y, z, m) along the Peano-Hilbert curve, ordered on the device (shq_hilbert_order)"""
         posm = posm.contiguous()
-        n = int(posm.shape[0])
-        if n == 0:
+        if int(posm.shape[0]) == 0:
             return posm
-        order = torch.empty(n, dtype=torch.int64, device=posm.device)
-        self._call(capi.hip.shq_hilbert_order, posm.data_ptr(), n, float(L), order.data_ptr())
-        return posm[order].contiguous()
+        return posm[self.hilbert_order(posm, L)].contiguous()
 
     def set_deposit_scale(self, total_mass):
         e = 61 - math.frexp(total_mass if total_mass > 0 else 1.0)[1]
@@ -560,6 +678,17 @@ class GpuOps:
     def green(self, spec_t, y0, nyl):
         assert spec_t.is_contiguous() and spec_t.dtype == torch.complex128
         self._call(capi.hip.shq_pm_slab_green, C.byref(self.pm), y0, nyl, C.c_void_p(spec_t.data_ptr()))
+
+    def green_forward(self, spec_t, y0, nyl):
+        """this rank's raw P(k) sums of the transposed density spectrum [y_l][z'][x] (shq_pm_slab_xforward)"""
+        assert spec_t.is_contiguous() and spec_t.dtype == torch.complex128
+        self._call(capi.hip.shq_pm_slab_xforward, C.byref(self.pm), y0, nyl, C.c_void_p(spec_t.data_ptr()))
+        return self.power()
+
+    def green_finish(self, spec_t, y0, nyl, table=None, measure=False):
+        """(v T) green on that layout (shq_pm_slab_xfinish); with measure the raw sums of v T"""
+        assert spec_t.is_contiguous() and spec_t.dtype == torch.complex128
+        return self._finish(capi.hip.shq_pm_slab_xfinish, (C.byref(self.pm), y0, nyl, C.c_void_p(spec_t.data_ptr())), table, measure)
 
     def readout(self, ext, plane0, nxl, pot_right=3):
         assert ext.is_contiguous() and pot_right == 3
@@ -585,11 +714,16 @@ class DistTreePM:
         self.decomp = self.pm.d
         self.halo_factor = halo_factor
         self.tree = None
+        self.local_types = self.types = None
 
-    def setup(self, posm_local, Rcut):
+    def setup(self, posm_local, Rcut, types=None):
         """posm_local: device tensor [nloc, 4] of the particles this rank owns (already exchanged to
-        their owner).  Orders them along a space-filling curve, imports ghosts, builds the tree on the device."""
-        self.local = self.ops.hilbert_sorted(posm_local, self.L)
+        their owner).  Orders them along a space-filling curve, imports ghosts, builds the tree on the device.
+        types: the particles' Types (nloc integers), which then travel with their rows through the ordering and every ghost import
+        (for the deposit type mask, ops.set_deposit_types)."""
+        order = self.ops.hilbert_order(posm_local, self.L)
+        self.local = posm_local.contiguous()[order].contiguous()
+        self.local_types = None if types is None else types.to(posm_local.device)[order].contiguous()
         self.nloc = int(self.local.shape[0])
         self.halo = self.halo_factor * Rcut
         self.ops.set_deposit_scale(self.comm.allreduce_sum(float(self.local[:, 3].sum().item())))
@@ -616,19 +750,26 @@ class DistTreePM:
             capi.check(capi.hip.shq_tree_upload(self.ctx.h, C.byref(tv)))
 
     def _load_particles(self, keep_tree=False):
-        ghosts = ghost_exchange(self.comm, self.decomp, self.local, self.halo)
+        if self.local_types is None:
+            ghosts = ghost_exchange(self.comm, self.decomp, self.local, self.halo)
+            self.types = None
+        else:
+            ghosts, gtypes = _split_types(ghost_exchange(self.comm, self.decomp, _with_types(self.local, self.local_types), self.halo),
+                                          self.local_types.dtype)
+            self.types = torch.cat([self.local_types, gtypes], dim=0).contiguous()
         self.allp = torch.cat([self.local, ghosts], dim=0).contiguous()
         self.nghost = int(ghosts.shape[0])
-        self.ops.set_particles(self.allp, self.nloc, keep_tree)
+        self.ops.set_particles(self.allp, self.nloc, keep_tree, types=self.types)
 
-    def step(self, gp, update_potential=1, walk_mode=0, overlap=None, moved=False):
+    def step(self, gp, update_potential=1, walk_mode=0, overlap=None, moved=False, analysis=None, measure_power=False):
         """One force evaluation: ghost import, PM, walk for the local targets, OldAcc refresh.
         moved: self.local changed since the tree was built (a drift): the ghosts are imported for the new positions and the
         tree is rebuilt.  Without it the step repeats the evaluation on the positions of setup(): the ghost exchange still
         runs (it is part of a step), the tree is kept.
         overlap (default: whenever the transposes are collectives; SHQ_DIST_OVERLAP=0 turns it off): the walk does not need
         the PM result of its own step (OldAcc is the previous step's), so it is cut in two pieces that are queued behind the
-        start of the two mesh transposes: the walk computes while the spectrum travels over xGMI."""
+        start of the two mesh transposes: the walk computes while the spectrum travels over xGMI.
+        analysis, measure_power: as SlabPM.force (massive neutrinos); the reduced sums are in self.pm.power / power_finish."""
         self._load_particles(keep_tree=not moved)
         if moved:
             self._build_tree()
@@ -640,9 +781,9 @@ class DistTreePM:
             def piece(first, count):
                 return lambda: capi.check(capi.hip.shq_grav_short_run_range(self.ctx.h, C.byref(gp), first, count,
                                                                            int(update_potential), walk_mode))
-            self.pm.force([piece(0, half), piece(half, self.nloc - half)])
+            self.pm.force([piece(0, half), piece(half, self.nloc - half)], analysis=analysis, measure_power=measure_power)
         else:
-            self.pm.force()
+            self.pm.force(analysis=analysis, measure_power=measure_power)
             capi.check(capi.hip.shq_grav_short_run(self.ctx.h, C.byref(gp), None, 0, int(update_potential), walk_mode))
         capi.check(capi.hip.shq_grav_refresh_oldacc(self.ctx.h, self.G))
 
