@@ -1348,6 +1348,58 @@ int shq_pm_apply(shq_context *ctx, int Nmesh, const double *complx, const shq_pm
 int shq_fft_r2c_xyz(shq_context *ctx, int Nmesh, const double *real, double *complx);
 int shq_fft_c2r_xyz(shq_context *ctx, int Nmesh, const double *complx, double *real);
 
+/* ---- excursion-set reionisation (EXCUR_REION: calculate_uvbg + petapm_reion, libgadget/uvbg.cpp:474-597, petapm.cpp:495-685) ----
+ * Mirror of UVBGParams (uvbg.cpp:32-56) plus pm_mass->BoxSize; the mesh is UVBGdim^3. */
+typedef struct shq_uvbg_params {
+    double ReionRBubbleMax, ReionRBubbleMin, ReionDeltaRFactor;
+    int32_t ReionFilterType;     /* 0 real-space top-hat, 1 k-space top-hat, 2 Gaussian (filter_pm, uvbg.cpp:218-250) */
+    int32_t RtoMFilterType;      /* 0 top-hat, 1 Gaussian (RtoM, uvbg.cpp:158-176) */
+    double ReionGammaHaloBias, ReionNionPhotPerBary, AlphaUV, EscapeFractionNorm, EscapeFractionScaling;
+    int32_t ReionUseParticleSFR, pad0_;
+    double ReionSFRTimescale;
+    int32_t UVBGdim, pad1_;
+    double BoxSize;
+} shq_uvbg_params;
+/* The caller's cosmology and units as values: CP->Omega0, OmegaBaryon, RhoCrit, HubbleParam, hubble_function(CP, Time). */
+typedef struct shq_uvbg_cosmo {
+    double Time, Omega0, OmegaBaryon, RhoCrit, HubbleParam, hubble;
+    double UnitLength_in_cm, UnitMass_in_g, UnitTime_in_s;
+} shq_uvbg_cosmo;
+/* UVBGgrids' global neutral fractions (uvbg.cpp:424-457) and the number of filter radii the loop ran */
+typedef struct shq_uvbg_result {
+    double volume_weighted_global_xHI, mass_weighted_global_xHI;
+    int32_t nradii, pad_;
+} shq_uvbg_result;
+/* calculate_uvbg for ONE rank (NTask == 1, as shq_fft_r2c): init_particle_uvbg, the deposit of mass, stellar mass x f_esc (Type 4) and,
+ * with ReionUseParticleSFR, Sfr x f_esc (Type 0), one forward transform per field, then for every radius from min(ReionRBubbleMax, BoxSize)
+ * down to the cell size the filter, the inverse transforms and reion_loop_pm, and readout_J21.  Several ranks (the x-slab route:
+ * shq_pm_slab2_* with the caller's transposes once per radius) are not supported yet.
+ *   parts     : Pos, Mass and Type (off_type is required); with shq_set_inputs_current(SHQ_CURRENT_PARTICLES) and this very view resident
+ *               (uploaded with its Type), the resident positions are read instead.  Every particle in [0, numpart) deposits its mass
+ *               (petapm_reion has no regions and no active mask); swallowed particles included.
+ *   fesc      : in / out, one per particle: f_esc of the particle's gas or star slot (SphP / StarP EscapeFraction; others are ignored);
+ *               on return the transformed value init_particle_uvbg leaves there.
+ *   sfr       : SphP.Sfr per particle (read for gas only, and only with ReionUseParticleSFR; may be NULL otherwise).
+ *   local_J21 : out, written for gas; zreion: in / out, for gas (1 / Time - 1 where it was -1 and the particle's J21 rises above 0).
+ * The deposit is the PM's fixed-point CIC (each field with its own scale 2^(61 - e) from its own sum): the grids do not depend on the
+ * particle order.  A negative f_esc after the transform is SHQ_ERR_INVALID before any output is written (the reference ends the run).
+ * Changes no state of the context: it stages positions in buffers of its own, which it frees before it returns; the resident particle
+ * set, a prestarted PM (shq_pm_start), a pending spectrum (shq_pm_forward), the PM mesh, its scrub state and the deposit scale and type
+ * mask all survive the call.  Synchronous. */
+int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *params, const shq_uvbg_cosmo *cosmo, const shq_part_view *parts,
+                       double *fesc, const double *sfr, double *local_J21, double *zreion, shq_uvbg_result *result);
+/* save_uvbg_grids' data: with shq_uvbg_keep_grids(ctx, 1) every later call copies its J21 and xHI grids to host memory of the context
+ * (2 x 4 Nmesh^3 bytes); shq_uvbg_download_grids returns the last call's as dense [x][y][z] float (SHQ_ERR_STATE without one, SHQ_ERR_INVALID
+ * for another Nmesh).  keep_grids(ctx, 0) frees them. */
+int shq_uvbg_keep_grids(shq_context *ctx, int enable);
+int shq_uvbg_download_grids(shq_context *ctx, int Nmesh, float *J21, float *xHI);
+/* HIP-event durations (ms) of the last call: [0] f_esc, deposit and forward transforms, [1] the radius loop, [2] readout, [3] all of it
+ * on the device (uploads and downloads included). */
+int shq_uvbg_phase_ms(shq_context *ctx, double ms[4]);
+/* Host only: filter_pm's factor (uvbg.cpp:218-250) per integer k2 = 0 .. 3 (Nmesh/2)^2 into table (3 (Nmesh/2)^2 + 1 doubles), with the
+ * reference's expressions and libm calls (sinf / cosf / powf in float for the real-space top-hat, pow(M_E, .) for the Gaussian). */
+int shq_uvbg_filter_table(int filter_type, int Nmesh, double BoxSize, double R, double *table);
+
 #ifdef __cplusplus
 }
 #endif

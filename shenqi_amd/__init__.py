@@ -356,6 +356,36 @@ def gravpm_force(ctx, pm, pman, UseGPU=True, analysis=None, deposit_types=capi.A
                                                      int(deposit_types)), "gravpm_force")
 
 
+def calculate_uvbg(ctx, pman, params, cosmo, fesc, sfr, local_J21, zreion, keep_grids=False):
+    """calculate_uvbg (uvbg.cpp:509-597) for one rank on the device.  params: capi.UvbgParams (UVBGParams and BoxSize), cosmo:
+    capi.UvbgCosmo (Time, the cosmology's scalars, hubble_function(CP, Time), units).  fesc (in / out), sfr (read with
+    ReionUseParticleSFR; may be None otherwise), local_J21 (out) and zreion (in / out) are float64 arrays of NumPart: the EXCUR_REION
+    fields of each particle's gas or star slot.  Returns (volume-weighted xHI, mass-weighted xHI, number of radii), UVBGgrids' globals;
+    with keep_grids also the J21 and xHI grids, float32 [UVBGdim]^3, as save_uvbg_grids writes them."""
+    n = pman.NumPart
+    arrs = [fesc, sfr, local_J21, zreion]
+    for a in arrs:
+        if a is not None and (a.dtype != np.float64 or a.shape != (n,) or not a.flags["C_CONTIGUOUS"]):
+            raise ValueError("fesc, sfr, local_J21 and zreion are contiguous float64 arrays of NumPart")
+    pv = pman.view()
+    res = capi.UvbgResult()
+    capi.check(capi.hip.shq_uvbg_keep_grids(ctx.h, int(bool(keep_grids))), "shq_uvbg_keep_grids")
+    try:
+        capi.check(capi.hip.shq_uvbg_calculate(ctx.h, C.byref(params), C.byref(cosmo), C.byref(pv), *[capi.ptr(a) for a in arrs],
+                                               C.byref(res)), "calculate_uvbg")
+        out = (res.volume_weighted_global_xHI, res.mass_weighted_global_xHI, res.nradii)
+        if keep_grids:
+            N = params.UVBGdim
+            J21 = np.empty((N, N, N), dtype=np.float32)
+            xHI = np.empty((N, N, N), dtype=np.float32)
+            capi.check(capi.hip.shq_uvbg_download_grids(ctx.h, N, capi.ptr(J21), capi.ptr(xHI)), "shq_uvbg_download_grids")
+            out += (J21, xHI)
+    finally:
+        if keep_grids:
+            capi.check(capi.hip.shq_uvbg_keep_grids(ctx.h, 0), "shq_uvbg_keep_grids")
+    return out
+
+
 def synth_positions(kind, n, seed=20240601, L=1.0):
     """SURVEY §8(d) synthetic inputs: kind 'grid' | 'uniform' | 'cluster'."""
     k = {"grid": 0, "uniform": 1, "cluster": 2}[kind]

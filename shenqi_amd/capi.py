@@ -617,6 +617,42 @@ hip.shq_pm_set_mode_factor.restype = C.c_int
 hip.shq_pm_set_deposit_types.argtypes = [_vp, C.c_int]
 hip.shq_pm_set_deposit_types.restype = C.c_int
 ALL_TYPES = -1                                     # SHQ_ALL_TYPES
+
+
+class UvbgParams(C.Structure):
+    """shq_uvbg_params: UVBGParams (uvbg.cpp:32-56) plus the mesh's BoxSize"""
+    _fields_ = [
+        ("ReionRBubbleMax", C.c_double), ("ReionRBubbleMin", C.c_double), ("ReionDeltaRFactor", C.c_double),
+        ("ReionFilterType", C.c_int32), ("RtoMFilterType", C.c_int32),
+        ("ReionGammaHaloBias", C.c_double), ("ReionNionPhotPerBary", C.c_double), ("AlphaUV", C.c_double),
+        ("EscapeFractionNorm", C.c_double), ("EscapeFractionScaling", C.c_double),
+        ("ReionUseParticleSFR", C.c_int32), ("pad0_", C.c_int32), ("ReionSFRTimescale", C.c_double),
+        ("UVBGdim", C.c_int32), ("pad1_", C.c_int32), ("BoxSize", C.c_double),
+    ]
+
+
+class UvbgCosmo(C.Structure):
+    """shq_uvbg_cosmo: Time, the cosmology's scalars, hubble_function(CP, Time) and the units"""
+    _fields_ = [(f, C.c_double) for f in ("Time", "Omega0", "OmegaBaryon", "RhoCrit", "HubbleParam", "hubble",
+                                          "UnitLength_in_cm", "UnitMass_in_g", "UnitTime_in_s")]
+
+
+class UvbgResult(C.Structure):
+    _fields_ = [("volume_weighted_global_xHI", C.c_double), ("mass_weighted_global_xHI", C.c_double),
+                ("nradii", C.c_int32), ("pad_", C.c_int32)]
+
+
+hip.shq_uvbg_calculate.argtypes = [_vp, C.POINTER(UvbgParams), C.POINTER(UvbgCosmo), C.POINTER(PartView), _vp, _vp, _vp, _vp,
+                                   C.POINTER(UvbgResult)]
+hip.shq_uvbg_calculate.restype = C.c_int
+hip.shq_uvbg_keep_grids.argtypes = [_vp, C.c_int]
+hip.shq_uvbg_keep_grids.restype = C.c_int
+hip.shq_uvbg_download_grids.argtypes = [_vp, C.c_int, _vp, _vp]
+hip.shq_uvbg_download_grids.restype = C.c_int
+hip.shq_uvbg_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 4)]
+hip.shq_uvbg_phase_ms.restype = C.c_int
+hip.shq_uvbg_filter_table.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, _vp]
+hip.shq_uvbg_filter_table.restype = C.c_int
 hip.shq_treepm_last_fused.argtypes = [_vp, C.POINTER(C.c_int)]
 hip.shq_treepm_set_fuse.argtypes = [_vp, C.c_int]
 hip.shq_pm_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 6)]

@@ -463,6 +463,12 @@ struct shq_context {
 
     /* host staging */
     PinBuf<char> stage;
+
+    /* ---- excursion-set reionisation (uvbg.hip): a call allocates and frees its own device buffers; only this stays behind */
+    bool uvbg_keep = false;               /* shq_uvbg_keep_grids: copy the J21 / xHI grids of every call to the host */
+    int uvbg_n = 0;                       /* Nmesh of the kept grids (0: none) */
+    std::vector<float> uvbg_j21, uvbg_xhi;
+    double uvbg_ms[4] = {0, 0, 0, 0};     /* shq_uvbg_phase_ms */
 };
 
 /* capi.hip: make the main stream wait for an outstanding asynchronous PM run */
@@ -528,6 +534,9 @@ int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bo
                   const double *d_sinctab, double asmth2, double pot_factor);
 int shq_fft3d_run_transposed(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, bool from_i64, double inv_scale,
                              const double *d_sinctab, double asmth2, double pot_factor);
+int shq_fft3d_fill_twiddles(int N, double *d_tw);
+int shq_fft3d_filter_part(shq_context *ctx, const double *d_tw, double *d_mesh, double *d_scratch, double *d_out, int N, int zp, int part,
+                          double inv_scale, const double *d_fac, int fac_mask, int ncell);
 int shq_fft3d_transposed_part(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, int part, bool from_i64, double inv_scale,
                               const double *d_sinctab, double asmth2, double pot_factor, const double *d_modefac, int fac_mask,
                               const int32_t *d_bintab, double *d_ps);

@@ -463,6 +463,7 @@ struct GreenArgs {
     int fac_mask;
     const int32_t *bintab;
     double *ps;
+    int ncell = 1; /* fft_t_tile MODE 5: the int N^3 every mode is divided by (uvbg.cpp:211-215 divide_by_ncell) */
 };
 
 /* powerspectrum_add_mode (gravpm.cpp:323-356) of one mode into a workgroup's LDS histogram [3][N]: the operations of pm_power_kernel
@@ -850,6 +851,8 @@ __global__ __launch_bounds__(FFT_T) void fft_t_z_inv(const double2 *__restrict__
  *   MODE 4: reads that tile and multiplies every mode by T[k2], then by MODE 2's Green's factor with MODE 2's arithmetic - (v T) green,
  *           potential_transfer's order (gravpm.cpp:412-443) - as it lands in LDS; with ga.ps the P(k) sums of v T; then X inverse.
  *           T = 1 gives MODE 2's bits: v * 1.0 is exact.  T[k2] is fetched with the tile's prefetch.
+ *   MODE 5: a sibling of MODE 4 for the excursion-set filters (uvbg.hip): reads that tile, every mode becomes (v / ncell) T[k2] -
+ *           divide_by_ncell, then filter_pm (uvbg.cpp:211-250) - with no Green's function, then X inverse.  The kept tile is not written.
  * SCATTER: row i of the result goes to dst + ((i * nzb + zb) * N + o) * 4 (the other layout: a 64-byte piece); otherwise the tile is
  * written back where it came from (dst may be src). */
 template <int N, int MODE, bool SCATTER>
@@ -877,7 +880,7 @@ __global__ __launch_bounds__(FFT_T, fft_tile_waves(N, MODE)) void fft_t_tile(con
     }
     const unsigned vb = xcd_block(blockIdx.x, gridDim.x, xcdk);
     double prx[E], pry[E];
-    double tfac[MODE == 4 ? E : 1]; /* MODE 4: T[k2] of the prefetched tile's modes */
+    double tfac[MODE == 4 || MODE == 5 ? E : 1]; /* MODES 4, 5: T[k2] of the prefetched tile's modes */
 #define FFT_FETCH(T_)                                                                            \
     {                                                                                            \
         const double2 *b_ = src + (long long) (T_) * (FFT_C * N);                                \
@@ -894,7 +897,7 @@ __global__ __launch_bounds__(FFT_T, fft_tile_waves(N, MODE)) void fft_t_tile(con
     /* MODE 4: T[k2] of tile T_'s modes, gathered after the FFT stages (held across them, these registers made the pass spill) so that
      * the scattered stores of the current tile hide the gather.  A pad column (z > N / 2) reads entry 0: k2 stays inside the table */
 #define FFT_TFETCH(T_)                                                                           \
-    if(MODE == 4) {                                                                              \
+    if(MODE == 4 || MODE == 5) {                                                                 \
         const int o_ = (T_) / nzb, zb_ = (T_) - o_ * nzb, y_ = ga.y0 + o_, ky_ = y_ <= N / 2 ? y_ : y_ - N; \
         _Pragma("unroll") for(int i = 0; i < E; i++)                                             \
         {                                                                                        \
@@ -939,6 +942,16 @@ __global__ __launch_bounds__(FFT_T, fft_tile_waves(N, MODE)) void fft_t_tile(con
                 const double fac = (k2 == 0.0 || z > N / 2) ? 0.0 : gax[x] * gy * gax[z] / k2;
                 *p = make_double2(v.x * fac, v.y * fac);
             }
+        } else if(MODE == 5) {
+            /* value /= total_n_cells, then value *= filter: a division and a multiplication, never contracted */
+#pragma clang fp contract(off)
+            const double nc = (double) ga.ncell;
+#pragma unroll
+            for(int i = 0; i < E; i++) {
+                const int e = threadIdx.x + i * FFT_T;
+                if(EXACT || e < FFT_C * N)
+                    buf[(e % FFT_C) * LS + lx<N>(e / FFT_C)] = make_double2((prx[i] / nc) * tfac[i], (pry[i] / nc) * tfac[i]);
+            }
         } else {
 #pragma unroll
             for(int i = 0; i < E; i++) {
@@ -968,7 +981,7 @@ __global__ __launch_bounds__(FFT_T, fft_tile_waves(N, MODE)) void fft_t_tile(con
             fft_lines<N, -1>(buf, Wl, green);
             fft_lines<N, +1>(buf, Wl);
         }
-        if(MODE == 1 || MODE == 4)
+        if(MODE == 1 || MODE == 4 || MODE == 5)
             fft_lines<N, +1>(buf, Wl);
         FFT_TFETCH(tf)
         if(MODE == 3) { /* the spectrum back where the tile came from; the density's P(k) on the way */
@@ -1027,11 +1040,12 @@ __global__ void fft_gax_kernel(int N, const double *__restrict__ sinctab, double
 }
 
 /* part 0: forward, potential_transfer and inverse (five passes); 1: Z fwd, Y fwd and the X forward half (MODE 3) - the half spectrum is left
- * in d_mesh in the layout LX; 2: from there the X inverse half (MODE 4), Y inv and Z inv */
+ * in d_mesh in the layout LX; 2: from there the X inverse half (MODE 4), Y inv and Z inv; 3: as 2 with MODE 5 (the excursion-set filter,
+ * no Green's function): d_mesh is only read, the Z inverse writes d_out.  W: the twiddles of N (ensure_twiddles, or a caller's own). */
 template <int N>
-int run_t(shq_context *ctx, double *d_mesh, double *d_scratch, int zp, bool from_i64, double inv_scale, const GreenArgs &ga, int part)
+int run_t(shq_context *ctx, const double2 *W, double *d_mesh, double *d_scratch, double *d_out, int zp, bool from_i64, double inv_scale,
+          const GreenArgs &ga, int part)
 {
-    const double2 *W = reinterpret_cast<const double2 *>(ctx->fft_tw.ptr);
     constexpr size_t lds = sizeof(double2) * (FFT_C * fft_ls(N) + fft_twn(N)), lds_x = lds + sizeof(double) * N; /* X pass: + its factor table */
     constexpr size_t lds_hist = sizeof(double) * 3 * N;                                                          /* MODES 3, 4: + the P(k) histogram */
     const int ztot = (int) (((long long) N * N) / (2 * FFT_C));
@@ -1039,16 +1053,16 @@ int run_t(shq_context *ctx, double *d_mesh, double *d_scratch, int zp, bool from
     const int stot = N * nzb;
     double2 *A = reinterpret_cast<double2 *>(d_mesh), *B = reinterpret_cast<double2 *>(d_scratch);
     hipStream_t s = ctx->stream;
-    static unsigned res_z = 0, res_s = 0, res_x = 0, res_x3 = 0, res_x4 = 0;
+    static unsigned res_z = 0, res_s = 0, res_x = 0, res_x3 = 0, res_x4 = 0, res_x5 = 0;
     if(res_s == 0) {
-        const void *fns[8] = {(const void *) fft_t_z_fwd<N, true>, (const void *) fft_t_z_fwd<N, false>, (const void *) fft_t_z_inv<N>,
+        const void *fns[9] = {(const void *) fft_t_z_fwd<N, true>, (const void *) fft_t_z_fwd<N, false>, (const void *) fft_t_z_inv<N>,
                               (const void *) fft_t_tile<N, 0, true>, (const void *) fft_t_tile<N, 2, true>, (const void *) fft_t_tile<N, 1, false>,
-                              (const void *) fft_t_tile<N, 3, false>, (const void *) fft_t_tile<N, 4, true>};
+                              (const void *) fft_t_tile<N, 3, false>, (const void *) fft_t_tile<N, 4, true>, (const void *) fft_t_tile<N, 5, true>};
         int ncu = 0;
         if(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || ncu < 1)
             ncu = 256;
-        unsigned occ[8];
-        for(int i = 0; i < 8; i++) {
+        unsigned occ[9];
+        for(int i = 0; i < 9; i++) {
             const size_t l = i == 4 ? lds_x : (i == 6 ? lds + lds_hist : (i == 7 ? lds_x + lds_hist : lds));
             if(l > 48 * 1024)
                 SHQ_HIP(hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int) l));
@@ -1063,6 +1077,7 @@ int run_t(shq_context *ctx, double *d_mesh, double *d_scratch, int zp, bool from
         res_x = occ[4];
         res_x3 = occ[6];
         res_x4 = occ[7];
+        res_x5 = occ[8];
     }
     const unsigned gmul = getenv("SHQ_FFT_GRID_MUL") ? (unsigned) atoi(getenv("SHQ_FFT_GRID_MUL")) : 8u;
     auto grid = [&](int tot, unsigned resident) {
@@ -1071,7 +1086,7 @@ int run_t(shq_context *ctx, double *d_mesh, double *d_scratch, int zp, bool from
     };
     const dim3 gz = grid(ztot, res_z), gs = grid(stot, res_s), gx = grid(stot, res_x);
     const unsigned xcdk = getenv("SHQ_FFT_XCD_K") ? (unsigned) atoi(getenv("SHQ_FFT_XCD_K")) : 8u;
-    if(part != 2) {
+    if(part == 0 || part == 1) {
         if(from_i64)
             fft_t_z_fwd<N, true><<<gz, dim3(FFT_T), lds, s>>>(d_mesh, B, ztot, zp, W, inv_scale);
         else
@@ -1082,11 +1097,13 @@ int run_t(shq_context *ctx, double *d_mesh, double *d_scratch, int zp, bool from
         fft_t_tile<N, 2, true><<<gx, dim3(FFT_T), lds_x, s>>>(A, B, nzb, stot, W, ga, xcdk);
     else if(part == 1)
         fft_t_tile<N, 3, false><<<grid(stot, res_x3), dim3(FFT_T), lds + (ga.ps ? lds_hist : 0), s>>>(A, A, nzb, stot, W, ga, xcdk);
-    else
+    else if(part == 2)
         fft_t_tile<N, 4, true><<<grid(stot, res_x4), dim3(FFT_T), lds_x + (ga.ps ? lds_hist : 0), s>>>(A, B, nzb, stot, W, ga, xcdk);
+    else
+        fft_t_tile<N, 5, true><<<grid(stot, res_x5), dim3(FFT_T), lds, s>>>(A, B, nzb, stot, W, ga, xcdk);
     if(part != 1) {
         fft_t_tile<N, 1, false><<<gs, dim3(FFT_T), lds, s>>>(B, B, nzb, stot, W, ga, xcdk);
-        fft_t_z_inv<N><<<gz, dim3(FFT_T), lds, s>>>(B, d_mesh, ztot, zp, W);
+        fft_t_z_inv<N><<<gz, dim3(FFT_T), lds, s>>>(B, part == 3 ? d_out : d_mesh, ztot, zp, W);
     }
     SHQ_HIP(hipGetLastError());
     return SHQ_OK;
@@ -1271,19 +1288,63 @@ bool shq_fft3d_supported(int N)
 /* z pitch (in doubles) the bespoke pipeline wants: N/2+1 complex rounded up to a multiple of the tile width FFT_C (4). */
 int shq_fft3d_pitch(int N) { return 2 * (((N / 2 + 1) + FFT_C - 1) / FFT_C * FFT_C); }
 
-static int ensure_twiddles(shq_context *ctx, int N)
+/* the N twiddles exp(-2 pi i k / N) as (re, im) into a device table of 2 N doubles */
+int shq_fft3d_fill_twiddles(int N, double *d_tw)
 {
-    if(ctx->fft_tw_n == N)
-        return SHQ_OK;
-    SHQ_TRY(ctx->fft_tw.reserve(2 * (size_t) N));
     std::vector<double> h(2 * (size_t) N);
     for(int k = 0; k < N; k++) {
         h[2 * k] = cos(2 * M_PI * k / N);
         h[2 * k + 1] = -sin(2 * M_PI * k / N);
     }
-    SHQ_HIP(hipMemcpy(ctx->fft_tw.ptr, h.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
+    SHQ_HIP(hipMemcpy(d_tw, h.data(), sizeof(double) * 2 * N, hipMemcpyHostToDevice));
+    return SHQ_OK;
+}
+
+static int ensure_twiddles(shq_context *ctx, int N)
+{
+    if(ctx->fft_tw_n == N)
+        return SHQ_OK;
+    SHQ_TRY(ctx->fft_tw.reserve(2 * (size_t) N));
+    SHQ_TRY(shq_fft3d_fill_twiddles(N, ctx->fft_tw.ptr));
     ctx->fft_tw_n = N;
     return SHQ_OK;
+}
+
+/* The excursion-set radius loop (uvbg.hip) on the transposing pipeline, touching none of the context's FFT state (its twiddles, the Green's
+ * factor table): d_tw is the caller's own table of N (shq_fft3d_fill_twiddles).  part 1: forward from the int64 deposit in d_mesh
+ * (inv_scale = 2^-e), the half spectrum left in d_mesh; part 3: from that spectrum, every mode times (v / ncell) d_fac[k2 & fac_mask],
+ * then the inverse into d_out (d_mesh is only read). */
+int shq_fft3d_filter_part(shq_context *ctx, const double *d_tw, double *d_mesh, double *d_scratch, double *d_out, int N, int zp, int part,
+                          double inv_scale, const double *d_fac, int fac_mask, int ncell)
+{
+    SHQ_CHECK((part == 1 || (part == 3 && d_fac && d_out && d_out != d_mesh && d_out != d_scratch)) && d_tw && ncell > 0, SHQ_ERR_INVALID,
+              "fft3d: bad filter part arguments");
+    SHQ_CHECK(shq_fft3d_supported(N) && N % (2 * FFT_C) == 0, SHQ_ERR_INVALID, "fft3d: unsupported mesh size %d", N);
+    SHQ_CHECK(zp == shq_fft3d_pitch(N) && d_mesh && d_scratch && d_mesh != d_scratch, SHQ_ERR_INVALID, "fft3d: bad pitch or scratch mesh");
+    GreenArgs ga;
+    ga.sinctab = nullptr;
+    ga.gaxg = nullptr;
+    ga.asmth2 = 0;
+    ga.pot_factor = 0;
+    ga.y0 = 0;
+    ga.alt = nullptr;
+    ga.nyl = 1;
+    ga.qstride = ga.alt_outer = 0;
+    ga.modefac = d_fac;
+    ga.fac_mask = fac_mask;
+    ga.bintab = nullptr;
+    ga.ps = nullptr;
+    ga.ncell = ncell;
+    const double2 *W = reinterpret_cast<const double2 *>(d_tw);
+#define SHQ_FFT_CASE(NN) case NN: return run_t<NN>(ctx, W, d_mesh, d_scratch, d_out, zp, part == 1, inv_scale, ga, part)
+    switch(N) {
+        SHQ_FFT_CASE(16); SHQ_FFT_CASE(24); SHQ_FFT_CASE(32); SHQ_FFT_CASE(40); SHQ_FFT_CASE(48); SHQ_FFT_CASE(64);
+        SHQ_FFT_CASE(80); SHQ_FFT_CASE(96); SHQ_FFT_CASE(128); SHQ_FFT_CASE(192); SHQ_FFT_CASE(256); SHQ_FFT_CASE(384);
+        SHQ_FFT_CASE(512); SHQ_FFT_CASE(768); SHQ_FFT_CASE(960); SHQ_FFT_CASE(1024); SHQ_FFT_CASE(1152); SHQ_FFT_CASE(1200);
+        SHQ_FFT_CASE(1536);
+    }
+#undef SHQ_FFT_CASE
+    return SHQ_ERR_INVALID;
 }
 
 /* forward + potential_transfer + inverse of a full cube through the transposing pipeline: d_scratch is a second mesh of the same size */
@@ -1325,7 +1386,7 @@ int shq_fft3d_transposed_part(shq_context *ctx, double *d_mesh, double *d_scratc
         ctx->fft_gax_src = d_sinctab;
     }
     ga.gaxg = ctx->fft_gax.ptr;
-#define SHQ_FFT_CASE(NN) case NN: return run_t<NN>(ctx, d_mesh, d_scratch, zp, from_i64, inv_scale, ga, part)
+#define SHQ_FFT_CASE(NN) case NN: return run_t<NN>(ctx, reinterpret_cast<const double2 *>(ctx->fft_tw.ptr), d_mesh, d_scratch, d_mesh, zp, from_i64, inv_scale, ga, part)
     switch(N) {
         SHQ_FFT_CASE(16); SHQ_FFT_CASE(24); SHQ_FFT_CASE(32); SHQ_FFT_CASE(40); SHQ_FFT_CASE(48); SHQ_FFT_CASE(64);
         SHQ_FFT_CASE(80); SHQ_FFT_CASE(96); SHQ_FFT_CASE(128); SHQ_FFT_CASE(192); SHQ_FFT_CASE(256); SHQ_FFT_CASE(384);
