@@ -1400,6 +1400,60 @@ int shq_uvbg_phase_ms(shq_context *ctx, double ms[4]);
  * reference's expressions and libm calls (sinf / cosf / powf in float for the real-space top-hat, pow(M_E, .) for the Gaussian). */
 int shq_uvbg_filter_table(int filter_type, int Nmesh, double BoxSize, double R, double *table);
 
+/* ---- helium reionisation by quasar bubbles (do_heiii_reionization / turn_on_quasars, libgadget/cooling_qso_lightup.cpp:225-617) ----
+ * HeIIIionized is bit 2 of the particle flag byte (after IsGarbage and Swallowed, before BHHeated); the context's copy of the flags keeps
+ * it in the same bit. */
+#define SHQ_FLAG_HEIII 4u
+typedef struct shq_heiii_params {
+    double BoxSize, atime;
+    double qso_candidate_min_mass, qso_candidate_max_mass, mean_bubble, var_bubble, heIIIreion_finish_frac;   /* QSOLightupParams */
+    double desired_ion_frac;      /* (*HeIII_intp)(atime): the history table and its interpolation stay with the caller */
+    double qso_inst_heating;      /* Q_inst of the history file, erg */
+    double uu_in_cgs;             /* UnitInternalEnergy_in_cgs */
+    double OmegaBaryon, HubbleParam;
+    double CurrentParticleOffset[3];
+    int64_t n_gas_tot;            /* SlotsManager->info[0].size */
+} shq_heiii_params;
+typedef struct shq_heiii_quasar { /* one FdHelium line (:574-583) */
+    int32_t group, pad_;          /* catalogue index of the lit group, -1 for a draw that lit nothing (position 0, or off the list) */
+    double pos[3];                /* CM - CurrentParticleOffset wrapped into (0, BoxSize]; zeros when group == -1 */
+    double ionfrac;               /* curionfrac after this quasar */
+    int64_t n_ionized;
+} shq_heiii_quasar;
+typedef struct shq_heiii_result {
+    double init_ionfrac, final_ionfrac;
+    int64_t n_candidates;         /* candidate groups built (0 when the box was already ionised enough) */
+    int64_t n_iterations;         /* iterations of the quasar loop = FdHelium lines */
+    int64_t n_flash;              /* particles flash-ionised (desired > heIIIreion_finish_frac) */
+    int64_t n_ionized;            /* particles ionised by quasar bubbles (tot_n_ionized) */
+} shq_heiii_result;
+/* turn_on_quasars for ONE rank.  Candidates are the groups of the RESIDENT FOF catalogue (shq_fof; SHQ_ERR_STATE without one) with
+ * min <= Mass <= max, in catalogue order; TotNgroups is the catalogue's length.  The catalogue is read before anything is uploaded.
+ *   parts / sph : Pos, Type, PI, the flag byte, and what shq_sph_state_upload needs (Hsml, Vel); Density and Entropy through PI.  Uploaded
+ *                 or skipped under shq_set_inputs_current as every one-shot operator.  Every gas particle needs a PI inside the slot array.
+ *   gas_tree    : the gas tree (GASMASK | BHMASK, with father) — required when var_bubble > 0 (SHQ_ERR_INVALID without it), where a negative
+ *                 radius makes membership depend on the tree; may be NULL otherwise (and is then not uploaded).
+ *   rnd_table   : RandTable::Table (rnd_size entries), read on the host only.
+ *   log         : FdHelium lines, log_capacity of them at most (may be NULL); *nlog = n_iterations.
+ * Ionised particles get flag |= SHQ_FLAG_HEIII and Entropy += deltau / uu_in_cgs / entropytou in the caller's records and in the context's
+ * copies; nothing else is written.  The quasar draws and radii are made on the host with glibc's libm, the bubbles are swept on the
+ * device in batches (DESIGN.md §"Helium reionisation").  Synchronous. */
+int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *params, const shq_part_view *parts, const shq_sph_view *sph,
+                           const shq_tree_view *gas_tree, const double *rnd_table, int64_t rnd_size, shq_heiii_quasar *log,
+                           int64_t log_capacity, int64_t *nlog, shq_heiii_result *result);
+/* What the last shq_heiii_reionization did on the device: HIP-event times (ms) of [0] the uploads and the eligible list, [1] the sweeps,
+ * [2] the stop replays, applies and compactions, [3] the whole call; the number of sweeps, the draws and the lit bubbles they covered, the
+ * eligible particles the first sweep tested, and the particle-bubble tests all sweeps made (eligible x lit, summed per sweep); per sweep (the
+ * first SHQ_HEIII_NSTAT) its draws, lit bubbles and eligible particles. */
+#define SHQ_HEIII_NSTAT 32
+typedef struct shq_heiii_stats {
+    double ms[4];
+    int64_t nsweeps, ndraws, nbubbles, neligible, ntests;
+    int32_t sweep_draws[SHQ_HEIII_NSTAT], sweep_lit[SHQ_HEIII_NSTAT];
+    int64_t sweep_eligible[SHQ_HEIII_NSTAT];
+} shq_heiii_stats;
+int shq_heiii_last_stats(shq_context *ctx, shq_heiii_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -386,6 +386,28 @@ def calculate_uvbg(ctx, pman, params, cosmo, fesc, sfr, local_J21, zreion, keep_
     return out
 
 
+def heiii_reionization(ctx, pman, SphP, params, rnd_table, gas_tree=None, log_capacity=None):
+    """turn_on_quasars (cooling_qso_lightup.cpp:489-596) for one rank on the device, on the resident FOF catalogue (shq_fof first).
+    params: capi.HeiiiParams; SphP: the gas slots (SPH_DTYPE, Density and Entropy read through PI); rnd_table: RandTable::Table as
+    float64; gas_tree: the GASMASK | BHMASK ForceTree, needed when var_bubble > 0.  Ionised particles get the HeIIIionized bit and their
+    heating in pman.Base and SphP.  Returns (capi.HeiiiResult, the FdHelium lines as a HEIII_QUASAR_DTYPE array)."""
+    rnd = np.ascontiguousarray(rnd_table, dtype=np.float64)
+    pv, sv = pman.view(), capi.sph_view(SphP)
+    tv = gas_tree.view() if gas_tree is not None else None
+    res = capi.HeiiiResult()
+    nlog = C.c_int64()
+    cap = int(log_capacity) if log_capacity is not None else 0
+    if log_capacity is None:   # the draws are bounded by the candidate count, which only the call knows: ask it once with room for all
+        cap = 1 << 20
+    log = np.zeros(cap, dtype=capi.HEIII_QUASAR_DTYPE)
+    capi.check(capi.hip.shq_heiii_reionization(ctx.h, C.byref(params), C.byref(pv), C.byref(sv), C.byref(tv) if tv is not None else None,
+                                               capi.ptr(rnd), len(rnd), capi.ptr(log), cap, C.byref(nlog), C.byref(res)),
+               "heiii_reionization")
+    if nlog.value > cap:
+        raise ShqError(f"heiii_reionization: {nlog.value} FdHelium lines, room for {cap}")
+    return res, log[:nlog.value].copy()
+
+
 def synth_positions(kind, n, seed=20240601, L=1.0):
     """SURVEY §8(d) synthetic inputs: kind 'grid' | 'uniform' | 'cluster'."""
     k = {"grid": 0, "uniform": 1, "cluster": 2}[kind]

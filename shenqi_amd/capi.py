@@ -653,6 +653,40 @@ hip.shq_uvbg_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 4)]
 hip.shq_uvbg_phase_ms.restype = C.c_int
 hip.shq_uvbg_filter_table.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, _vp]
 hip.shq_uvbg_filter_table.restype = C.c_int
+
+
+FLAG_HEIII = 4                                     # SHQ_FLAG_HEIII: HeIIIionized, bit 2 of the flag byte
+
+
+class HeiiiParams(C.Structure):
+    """shq_heiii_params: QSOLightupParams, the history's target and Q_inst at this step, units, cosmology and the particle offset"""
+    _fields_ = [(f, C.c_double) for f in ("BoxSize", "atime", "qso_candidate_min_mass", "qso_candidate_max_mass", "mean_bubble",
+                                          "var_bubble", "heIIIreion_finish_frac", "desired_ion_frac", "qso_inst_heating", "uu_in_cgs",
+                                          "OmegaBaryon", "HubbleParam")] + [("CurrentParticleOffset", C.c_double * 3), ("n_gas_tot", C.c_int64)]
+
+
+HEIII_QUASAR_DTYPE = np.dtype([("group", "<i4"), ("pad_", "<i4"), ("pos", "<f8", 3), ("ionfrac", "<f8"), ("n_ionized", "<i8")])
+
+
+class HeiiiResult(C.Structure):
+    _fields_ = [("init_ionfrac", C.c_double), ("final_ionfrac", C.c_double), ("n_candidates", C.c_int64), ("n_iterations", C.c_int64),
+                ("n_flash", C.c_int64), ("n_ionized", C.c_int64)]
+
+
+HEIII_NSTAT = 32
+
+
+class HeiiiStats(C.Structure):
+    _fields_ = [("ms", C.c_double * 4), ("nsweeps", C.c_int64), ("ndraws", C.c_int64), ("nbubbles", C.c_int64), ("neligible", C.c_int64),
+                ("ntests", C.c_int64), ("sweep_draws", C.c_int32 * HEIII_NSTAT), ("sweep_lit", C.c_int32 * HEIII_NSTAT),
+                ("sweep_eligible", C.c_int64 * HEIII_NSTAT)]
+
+
+hip.shq_heiii_reionization.argtypes = [_vp, C.POINTER(HeiiiParams), C.POINTER(PartView), C.POINTER(SphView), C.POINTER(TreeView), _vp,
+                                       C.c_int64, _vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(HeiiiResult)]
+hip.shq_heiii_reionization.restype = C.c_int
+hip.shq_heiii_last_stats.argtypes = [_vp, C.POINTER(HeiiiStats)]
+hip.shq_heiii_last_stats.restype = C.c_int
 hip.shq_treepm_last_fused.argtypes = [_vp, C.POINTER(C.c_int)]
 hip.shq_treepm_set_fuse.argtypes = [_vp, C.c_int]
 hip.shq_pm_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 6)]

@@ -463,7 +463,7 @@ extern "C" int shq_particles_upload(shq_context *ctx, const shq_part_view *parts
                 h_pm[3 * k] = g0; h_pm[3 * k + 1] = g1; h_pm[3 * k + 2] = g2;
                 uint8_t fl = 0;
                 if(parts->off_flags != SHQ_NOFIELD)
-                    fl |= (uint8_t) (*field<uint32_t>(parts, i, parts->off_flags) & 3u);
+                    fl |= (uint8_t) (*field<uint32_t>(parts, i, parts->off_flags) & 7u); /* IsGarbage, Swallowed, HeIIIionized */
                 if(parts->off_type != SHQ_NOFIELD)
                     fl |= (uint8_t) ((*field<uint8_t>(parts, i, parts->off_type) & 0xf) << 4);
                 h_flags[k] = fl;

@@ -252,7 +252,7 @@ struct shq_context {
     DevBuf<double> acc;        /* [N][3] walk output (Accel) */
     DevBuf<double> pot;        /* [N] tree potential */
     DevBuf<int32_t> nint;      /* [N] interactions */
-    DevBuf<uint8_t> pflags;    /* bit0 garbage, bit1 swallowed; bits 4-7 type */
+    DevBuf<uint8_t> pflags;    /* bit0 garbage, bit1 swallowed, bit2 HeIIIionized (SHQ_FLAG_HEIII); bits 4-7 type */
     DevBuf<int32_t> active;    /* uploaded active list */
     DevBuf<unsigned long long> top_task; /* resident export detection: entries per destination task */
     DevBuf<int32_t> top_sort;            /* (task, entry) pairs before / after the stable sort */
@@ -469,6 +469,8 @@ struct shq_context {
     int uvbg_n = 0;                       /* Nmesh of the kept grids (0: none) */
     std::vector<float> uvbg_j21, uvbg_xhi;
     double uvbg_ms[4] = {0, 0, 0, 0};     /* shq_uvbg_phase_ms */
+    /* ---- helium reionisation (heiii.hip): a call allocates and frees its own device buffers; only its statistics stay behind */
+    shq_heiii_stats heiii_stats = {};
 };
 
 /* capi.hip: make the main stream wait for an outstanding asynchronous PM run */
