@@ -13,6 +13,12 @@ theta=0.175 Barnes-Hut seeding walk.  For N>1 the box grows with the GPU count a
 particles per GPU (n = 320, 400, 512 per dimension for N = 2, 4, 8; Nmesh = 3 n) and is sharded
 over x-slabs, one per rank (shenqi_amd/dist.py): RCCL all-to-all for the slab-FFT transposes,
 ghost mesh planes and ghost particles for the tree => "scaling": "weak".
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the result line with the figures the timed
+steps leave behind.  --full adds everything that takes work of its own after them: the counted walk launch (kernels.tree_*
+wave figures), the CPU baseline and the force check against it, the distributed-walk, resident-step, time-step, hierarchical,
+FoF and SPH / C3 figures at N = 1; the per-rank walk launch and the direct-summation force check at N > 1; the per-operator
+step of --workload c5.
 """
 import argparse
 import ctypes as C
@@ -45,8 +51,11 @@ def parse():
     ap.add_argument("--ngrid", dest="n", type=int, default=256, help="particles per dimension (default 256 = configs[1])")
     ap.add_argument("--errtol", type=float, default=0.005)
     ap.add_argument("--kind", default="cluster", choices=["cluster", "uniform", "grid"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sph", action="store_true", help="skip the SPH operator figures (kernels.sph_*)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the result line's own figures, also measure and check everything else (see the module docstring); "
+                         "a plain run does only what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the force check against it")
+    ap.add_argument("--no-sph", action="store_true", help="--full: skip the SPH operator figures (kernels.sph_*)")
     ap.add_argument("--sph-ngrid", type=int, default=128,
                     help="gas particles per dimension of the SPH / C3 figures (128 = BASELINE configs[2]; 256 = the particle set of configs[4])")
     ap.add_argument("--walk-mode", type=int, default=0)
@@ -379,6 +388,53 @@ def c3_step(ctx, gas_pos, n1, density_ms, hydro_ms):
             "c3_particle_steps_per_s": 2 * n / (1e-3 * total)}
 
 
+def c5_operator_figures(ctx, ctx_sph, drv, sph, rows, dp, hp, gp_rel, rounds0, sq, capi):
+    """--full figures of --workload c5: per-operator times of one more, untimed step (walk as a single launch) and their rooflines"""
+    t1 = time.perf_counter()
+    drv.step(gp_rel, overlap=False)
+    ctx.synchronize()
+    t_grav = time.perf_counter() - t1
+    st = sq.WalkStats()
+    capi.check(capi.hip.shq_grav_short_download(ctx.h, None, None, None, C.byref(st)))
+    t1 = time.perf_counter()
+    sph.density(rows, dp)
+    ctx_sph.synchronize()
+    t_dens = time.perf_counter() - t1
+    dstat = dict(sph.stats["density"])
+    t1 = time.perf_counter()
+    sph.hydro(rows, hp)
+    ctx_sph.synchronize()
+    t_hyd = time.perf_counter() - t1
+    hstat = dict(sph.stats["hydro"])
+    ngas = int(rows.shape[0])
+    ngb = float(dp.DesNumNgb)
+    dens_s = 1e-3 * dstat["kernel_ms"] / max(1, dstat["iterations"])
+    cand = dstat["ninteractions"] / max(1, ngas) / max(1, dstat["iterations"])
+    dens_bytes = ngas * (cand * 32.0 + ngb * 114.0)
+    hyd_bytes = ngas * ngb * 200.0
+    hyd_s = 1e-3 * hstat["kernel_ms"]
+    walk_s = max(st.kernel_ms * 1e-3, 1e-12)
+    note = "gather / VALU bound: SURVEY 8(d)'s neighbour stream (served from L2 / LDS) over the HBM peak; rank 0"
+    return {
+        "roofline": {"bound": "valu-f64", "kernel": "grav_walk_exact_kernel (rank 0)", "achieved": 45.0 * st.ninteractions / walk_s / 1e12,
+                     "peak": FP64_VECTOR_PEAK_TF, "unit": "TFLOP/s", "frac": 45.0 * st.ninteractions / walk_s / 1e12 / FP64_VECTOR_PEAK_TF,
+                     "traffic": None, "algorithmic_flops": 45.0 * st.ninteractions},
+        "roofline_sph_density": {"bound": "gather-valu (stream from L2/LDS)", "kernel": "sph_density_kernel, one Hsml iteration (rank 0)",
+                                 "achieved": dens_bytes / max(dens_s, 1e-12) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                 "frac": dens_bytes / max(dens_s, 1e-12) / 1e9 / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes": dens_bytes,
+                                 "note": note},
+        "roofline_sph_hydro": {"bound": "gather-valu (stream from L2/LDS)", "kernel": "sph_hydro_kernel (rank 0)",
+                               "achieved": hyd_bytes / max(hyd_s, 1e-12) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": hyd_bytes / max(hyd_s, 1e-12) / 1e9 / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes": hyd_bytes,
+                               "note": note},
+        "kernels": {"treepm_step_ms": 1e3 * t_grav, "tree_walk_ms": float(st.kernel_ms), "tree_interactions_per_target": st.ninteractions / max(1, st.ntargets),
+                    "density_call_ms": 1e3 * t_dens, "density_kernels_ms": dstat["kernel_ms"], "density_iterations": dstat["iterations"],
+                    "density_first_call_import_rounds": rounds0, "hydro_call_ms": 1e3 * t_hyd, "hydro_kernels_ms": hstat["kernel_ms"],
+                    "gas_local": ngas, "gas_ghosts_density": dstat["nghost"], "gas_ghosts_hydro": hstat["nghost"],
+                    "grav_local": int(drv.nloc), "grav_ghosts": int(drv.nghost)},
+    }
+
+
 def run_sharded_c5(args, rank, world, backend, dev, cdev, json_fd, sq, capi, sd, dist, torch):
     """BASELINE configs[4]-shaped step on N ranks (examples/hydro: 2 x n^3, gas + dark matter): sharded TreePM over all particles +
     sharded SPH density (Hsml loop) and hydro force of the gas with the gas resident on the device (dist.DistSPHDevice).  Positions as
@@ -448,33 +504,7 @@ def run_sharded_c5(args, rank, world, backend, dev, cdev, json_fd, sq, capi, sd,
     tt = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     elapsed = float(tt.item())
-    # per-operator figures of one more, untimed step (walk as a single launch)
-    t1 = time.perf_counter()
-    drv.step(gp_rel, overlap=False)
-    ctx.synchronize()
-    t_grav = time.perf_counter() - t1
-    st = sq.WalkStats()
-    capi.check(capi.hip.shq_grav_short_download(ctx.h, None, None, None, C.byref(st)))
-    t1 = time.perf_counter()
-    sph.density(rows, dp)
-    ctx_sph.synchronize()
-    t_dens = time.perf_counter() - t1
-    dstat = dict(sph.stats["density"])
-    t1 = time.perf_counter()
-    sph.hydro(rows, hp)
-    ctx_sph.synchronize()
-    t_hyd = time.perf_counter() - t1
-    hstat = dict(sph.stats["hydro"])
-    ngas = int(rows.shape[0])
-    ngb = float(dp.DesNumNgb)
-    dens_s = 1e-3 * dstat["kernel_ms"] / max(1, dstat["iterations"])
-    cand = dstat["ninteractions"] / max(1, ngas) / max(1, dstat["iterations"])
-    dens_bytes = ngas * (cand * 32.0 + ngb * 114.0)
-    hyd_bytes = ngas * ngb * 200.0
-    hyd_s = 1e-3 * hstat["kernel_ms"]
-    walk_s = max(st.kernel_ms * 1e-3, 1e-12)
     nglobal = 2 * ndm
-    note = "gather / VALU bound: SURVEY 8(d)'s neighbour stream (served from L2 / LDS) over the HBM peak; rank 0"
     out = {
         "metric": "particle-steps/sec (grav+PM+SPH) at 256^3; rms force error vs ref",
         "metric_note": "C5-shaped extra mode (--workload c5): n^3 gas + n^3 dark matter, TreePM over all + SPH density and hydro of the gas",
@@ -484,24 +514,10 @@ def run_sharded_c5(args, rank, world, backend, dev, cdev, json_fd, sq, capi, sd,
         "config": {"workload": "2 x %d^3 gas + dark matter (uniform + shifted copy), Nmesh %d, sharded over %d x-slabs: TreePM over all, "
                                "density (quintic kernel, Hsml loop) + hydro of the gas resident on the device" % (n1, nmesh, world),
                    "particles_total": nglobal, "nmesh": nmesh, "parallelism": "x-slabs x%d, RCCL all-to-all + ghost particles + ghost gas rows" % world},
-        "roofline": {"bound": "valu-f64", "kernel": "grav_walk_exact_kernel (rank 0)", "achieved": 45.0 * st.ninteractions / walk_s / 1e12,
-                     "peak": FP64_VECTOR_PEAK_TF, "unit": "TFLOP/s", "frac": 45.0 * st.ninteractions / walk_s / 1e12 / FP64_VECTOR_PEAK_TF,
-                     "traffic": None, "algorithmic_flops": 45.0 * st.ninteractions},
-        "roofline_sph_density": {"bound": "gather-valu (stream from L2/LDS)", "kernel": "sph_density_kernel, one Hsml iteration (rank 0)",
-                                 "achieved": dens_bytes / max(dens_s, 1e-12) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                 "frac": dens_bytes / max(dens_s, 1e-12) / 1e9 / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes": dens_bytes,
-                                 "note": note},
-        "roofline_sph_hydro": {"bound": "gather-valu (stream from L2/LDS)", "kernel": "sph_hydro_kernel (rank 0)",
-                               "achieved": hyd_bytes / max(hyd_s, 1e-12) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                               "frac": hyd_bytes / max(hyd_s, 1e-12) / 1e9 / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes": hyd_bytes,
-                               "note": note},
-        "kernels": {"treepm_step_ms": 1e3 * t_grav, "tree_walk_ms": float(st.kernel_ms), "tree_interactions_per_target": st.ninteractions / max(1, st.ntargets),
-                    "density_call_ms": 1e3 * t_dens, "density_kernels_ms": dstat["kernel_ms"], "density_iterations": dstat["iterations"],
-                    "density_first_call_import_rounds": rounds0, "hydro_call_ms": 1e3 * t_hyd, "hydro_kernels_ms": hstat["kernel_ms"],
-                    "gas_local": ngas, "gas_ghosts_density": dstat["nghost"], "gas_ghosts_hydro": hstat["nghost"],
-                    "grav_local": int(drv.nloc), "grav_ghosts": int(drv.nghost)},
         "setup_s": {"generate_exchange_tree_first_density": t_setup},
     }
+    if args.full:
+        out.update(c5_operator_figures(ctx, ctx_sph, drv, sph, rows, dp, hp, gp_rel, rounds0, sq, capi))
     ctx_sph.close()
     ctx.close()
     dist.barrier()
@@ -510,6 +526,63 @@ def run_sharded_c5(args, rank, world, backend, dev, cdev, json_fd, sq, capi, sd,
     if rank == 0:
         os.write(json_fd, (json.dumps(out) + "\n").encode())
     os.close(json_fd)
+
+
+def sharded_figures(ctx, drv, gp_rel, rank, world, cdev, nglobal, L, sq, capi, dist, torch):
+    """--full figures of the N > 1 line: the per-rank walk of one more, untimed step, its roofline, and the sampled force check"""
+    # the timed steps cut the walk in two pieces around the mesh transposes; the per-rank walk figures below come from one
+    # more, untimed step with the walk as a single launch
+    drv.step(gp_rel, overlap=False)
+    ctx.synchronize()
+    st = sq.WalkStats()
+    capi.check(capi.hip.shq_grav_short_download(ctx.h, None, None, None, C.byref(st)))
+    loads = torch.tensor([float(drv.nloc), float(drv.nghost), st.kernel_ms], device=cdev, dtype=torch.float64)
+    gathered = [torch.zeros_like(loads) for _ in range(world)]
+    dist.all_gather(gathered, loads)
+    walk_s = max(float(g[2]) for g in gathered) * 1e-3
+    tree_bytes = 68.0 * drv.nloc + 76.0 * drv.tree.numnodes
+    ach = tree_bytes / max(st.kernel_ms * 1e-3, 1e-12) / 1e9
+    out = {
+        "roofline": {"bound": "valu-f64", "kernel": "grav_walk_exact_kernel (rank 0)",
+                     "achieved": 45.0 * st.ninteractions / max(st.kernel_ms * 1e-3, 1e-12) / 1e12, "peak": FP64_VECTOR_PEAK_TF,
+                     "unit": "TFLOP/s", "frac": 45.0 * st.ninteractions / max(st.kernel_ms * 1e-3, 1e-12) / 1e12 / FP64_VECTOR_PEAK_TF,
+                     "traffic": None, "algorithmic_flops": 45.0 * st.ninteractions, "algorithmic_bytes": tree_bytes,
+                     "hbm_algorithmic_GBs": ach,
+                     "note": "FP64-issue bound walk: 45 flop per interaction against the 78.6 TFLOP/s FP64 peak (see the N=1 line)"},
+        "kernels": {"per_rank_local_particles": [int(g[0]) for g in gathered], "per_rank_ghost_particles": [int(g[1]) for g in gathered],
+                    "per_rank_walk_ms": [float(g[2]) for g in gathered], "slowest_walk_ms": walk_s * 1e3},
+    }
+    # sampled force check (the metric's second half on the N > 1 line): total acceleration (tree + PM) of the sharded step at up
+    # to 64 of rank 0's particles against direct summation over ALL particles and their 27 periodic images, every rank summing
+    # its own particles (shq_direct_force_sample, the reference's own check: tests/test_gravity.cpp:41-119, errors in units of the
+    # mean |a_direct|; its limits there: mean < 0.8 ErrTol... for PM + tree against this image sum)
+    try:
+        ns = 64
+        acc_l, _, gpm_l, _ = drv.download()
+        nl = torch.tensor([min(ns, drv.nloc) if rank == 0 else 0], dtype=torch.int64, device=cdev)
+        dist.all_reduce(nl, op=dist.ReduceOp.MAX)
+        ns = int(nl.item())
+        samp = torch.zeros((ns, 3), dtype=torch.float64, device=cdev)
+        if rank == 0:
+            pick = np.linspace(0, drv.nloc - 1, ns).astype(np.int64)
+            samp = drv.local[pick, :3].to(cdev).contiguous()
+        dist.broadcast(samp, 0)
+        sp = np.ascontiguousarray(samp.cpu().numpy())
+        part = np.zeros((ns, 3))
+        capi.check(capi.hip.shq_direct_force_sample(ctx.h, capi.ptr(sp), ns, drv.nloc, L, G, float(gp_rel.ForceSoftening), 1, capi.ptr(part)))
+        tot = torch.from_numpy(part).to(cdev)
+        dist.all_reduce(tot)
+        if rank == 0:
+            direct = tot.cpu().numpy()
+            total = acc_l[pick] + gpm_l[pick]
+            meanacc = np.abs(direct).mean()
+            err = np.abs(direct - total) / meanacc
+            out["force_error"] = {"check": "tree + PM of the sharded step vs direct summation over all %d particles and 27 images at %d targets "
+                                           "of rank 0 (check_accns of tests/test_gravity.cpp:78-119: |a_direct - a| / mean |a_direct|)" % (nglobal, ns),
+                                  "mean": float(err.mean()), "max": float(err.max()), "targets": ns}
+    except Exception as e:  # an extra figure: never fatal
+        out["force_error"] = {"note": "sampled force check skipped: %s" % e}
+    return out
 
 
 def run_sharded(args, rank, local_rank, world):
@@ -613,18 +686,6 @@ def run_sharded(args, rank, local_rank, world):
     tt = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
     dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     elapsed = float(tt.item())
-    # the timed steps cut the walk in two pieces around the mesh transposes; the per-rank walk figures below come from one
-    # more, untimed step with the walk as a single launch
-    drv.step(gp_rel, overlap=False)
-    ctx.synchronize()
-    st = sq.WalkStats()
-    capi.check(capi.hip.shq_grav_short_download(ctx.h, None, None, None, C.byref(st)))
-    loads = torch.tensor([float(drv.nloc), float(drv.nghost), st.kernel_ms], device=cdev, dtype=torch.float64)
-    gathered = [torch.zeros_like(loads) for _ in range(world)]
-    dist.all_gather(gathered, loads)
-    walk_s = max(float(g[2]) for g in gathered) * 1e-3
-    tree_bytes = 68.0 * drv.nloc + 76.0 * drv.tree.numnodes
-    ach = tree_bytes / max(st.kernel_ms * 1e-3, 1e-12) / 1e9
     out = {
         "metric": "particle-steps/sec (grav+PM+SPH) at 256^3; rms force error vs ref",
         "metric_note": "BASELINE.json's metric name; this N-GPU line runs the dm-only TreePM step of config.workload (dm-only as "
@@ -637,46 +698,10 @@ def run_sharded(args, rank, local_rank, world):
                    "particles_total": nglobal, "nmesh": nmesh, "parallelism": "x-slabs x%d, RCCL all-to-all + ghost exchange" % world,
                    "slab_bounds": bounds, "slab_ycuts": ycuts,
                    "slab_bounds_by_count": bounds_count, "walk": "exact (per-target reference opening decisions)"},
-        "roofline": {"bound": "valu-f64", "kernel": "grav_walk_exact_kernel (rank 0)",
-                     "achieved": 45.0 * st.ninteractions / max(st.kernel_ms * 1e-3, 1e-12) / 1e12, "peak": FP64_VECTOR_PEAK_TF,
-                     "unit": "TFLOP/s", "frac": 45.0 * st.ninteractions / max(st.kernel_ms * 1e-3, 1e-12) / 1e12 / FP64_VECTOR_PEAK_TF,
-                     "traffic": None, "algorithmic_flops": 45.0 * st.ninteractions, "algorithmic_bytes": tree_bytes,
-                     "hbm_algorithmic_GBs": ach,
-                     "note": "FP64-issue bound walk: 45 flop per interaction against the 78.6 TFLOP/s FP64 peak (see the N=1 line)"},
-        "kernels": {"per_rank_local_particles": [int(g[0]) for g in gathered], "per_rank_ghost_particles": [int(g[1]) for g in gathered],
-                    "per_rank_walk_ms": [float(g[2]) for g in gathered], "slowest_walk_ms": walk_s * 1e3},
         "setup_s": {"generate_exchange_tree_upload": t_setup},
     }
-    # sampled force check (the metric's second half on the N > 1 line): total acceleration (tree + PM) of the sharded step at up
-    # to 64 of rank 0's particles against direct summation over ALL particles and their 27 periodic images, every rank summing
-    # its own particles (shq_direct_force_sample, the reference's own check: tests/test_gravity.cpp:41-119, errors in units of the
-    # mean |a_direct|; its limits there: mean < 0.8 ErrTol... for PM + tree against this image sum)
-    try:
-        ns = 64
-        acc_l, _, gpm_l, _ = drv.download()
-        nl = torch.tensor([min(ns, drv.nloc) if rank == 0 else 0], dtype=torch.int64, device=cdev)
-        dist.all_reduce(nl, op=dist.ReduceOp.MAX)
-        ns = int(nl.item())
-        samp = torch.zeros((ns, 3), dtype=torch.float64, device=cdev)
-        if rank == 0:
-            pick = np.linspace(0, drv.nloc - 1, ns).astype(np.int64)
-            samp = drv.local[pick, :3].to(cdev).contiguous()
-        dist.broadcast(samp, 0)
-        sp = np.ascontiguousarray(samp.cpu().numpy())
-        part = np.zeros((ns, 3))
-        capi.check(capi.hip.shq_direct_force_sample(ctx.h, capi.ptr(sp), ns, drv.nloc, L, G, float(gp_rel.ForceSoftening), 1, capi.ptr(part)))
-        tot = torch.from_numpy(part).to(cdev)
-        dist.all_reduce(tot)
-        if rank == 0:
-            direct = tot.cpu().numpy()
-            total = acc_l[pick] + gpm_l[pick]
-            meanacc = np.abs(direct).mean()
-            err = np.abs(direct - total) / meanacc
-            out["force_error"] = {"check": "tree + PM of the sharded step vs direct summation over all %d particles and 27 images at %d targets "
-                                           "of rank 0 (check_accns of tests/test_gravity.cpp:78-119: |a_direct - a| / mean |a_direct|)" % (nglobal, ns),
-                                  "mean": float(err.mean()), "max": float(err.max()), "targets": ns}
-    except Exception as e:  # an extra figure: never fatal
-        out["force_error"] = {"note": "sampled force check skipped: %s" % e}
+    if args.full:
+        out.update(sharded_figures(ctx, drv, gp_rel, rank, world, cdev, nglobal, L, sq, capi, dist, torch))
     ctx.close()
     dist.barrier()
     dist.destroy_process_group()
@@ -697,266 +722,13 @@ def launch_ranks(args):
     return subprocess.call(cmd)
 
 
-def main():
-    args = parse()
-    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("SHQ_COMM_FORCE", "0") == "1"):
-        raise SystemExit("bench.py: --dump-outputs is for the one-GPU run")
-    if args.gpus > 1 and "WORLD_SIZE" not in os.environ and os.environ.get("SHQ_COMM_FORCE", "0") != "1":
-        sys.exit(launch_ranks(args))
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    if world > 1 or os.environ.get("SHQ_COMM_FORCE", "0") == "1":   # the latter: one-rank RCCL rehearsal (needs MASTER_ADDR/PORT)
-        return run_sharded(args, rank, local_rank, world)
-    dist = None
-    sys.stdout.flush()   # stdout carries the one JSON line only; anything a library prints goes to stderr
-    json_fd = os.dup(1)
-    os.dup2(2, 1)
-
+def full_figures(args, ctx, out, pman, pos, gp_rel, pmp, n1, L, rank):
+    """--full at N = 1: everything measured or checked after the result line's own figures, added to `out`.  Runs after the
+    counted walk launch, whose OldAcc refresh the CPU baseline's device walk starts from."""
     import shenqi_amd as sq
     from shenqi_amd import capi
-
-    n1 = args.n
     n = n1**3
-    L = 1.0
-    nmesh = 3 * n1 if n1 != 512 else 1024
-    t_setup = time.perf_counter()
-    pos = sq.synth_positions(args.kind, n, seed=20240601 + rank, L=L)
-    pos = pos[sq.hilbert_order(pos, L)]  # Peano-Hilbert order, as the reference keeps its particles (domain.cpp:268)
-    pman = sq.PartManager(n, L)
     P = pman.Base
-    P["Pos"] = pos
-    P["Type"] = 1
-    P["Mass"] = 1.0
-    t_setup = time.perf_counter() - t_setup
-
-    ctx = sq.Context(local_rank if world > 1 else 0)
-    sq.set_gravshort_treepar(ErrTolForceAcc=args.errtol, BHOpeningAngle=0.175, MaxBHOpeningAngle=0.9, TreeUseBH=1, Rcut=6.0)
-    sq.gravshort_set_softenings(L / n1)
-    gp_bh = sq.make_grav_params(L, 1.5, nmesh, G, RHO0)
-    sq.set_gravshort_treepar(ErrTolForceAcc=args.errtol, BHOpeningAngle=0.175, MaxBHOpeningAngle=0.9, TreeUseBH=0, Rcut=6.0)
-    gp_rel = sq.make_grav_params(L, 1.5, nmesh, G, RHO0)
-    pmp = sq.PMParams(nmesh, 0, L, 1.5, G)
-
-    pv = pman.view()
-    t0 = time.perf_counter()
-    capi.check(capi.hip.shq_particles_upload(ctx.h, C.byref(pv)))
-    t_upload = time.perf_counter() - t0
-    # the tree is built on the device (shq_tree_build: bit-identical to the host / reference tree, see
-    # tests/test_gpu_treebuild.py); outside the timed region like the host build it replaces (SURVEY §8(d))
-    try:
-        sq.tree_build_device(ctx, L)         # first call allocates the scratch
-        t0 = time.perf_counter()
-        tb = sq.tree_build_device(ctx, L)
-        t_tree_build = time.perf_counter() - t0
-        numnodes = int(tb.numnodes)
-    except sq.ShqError as e:                 # deeper than 21 levels: host build (8 OpenMP threads' worth) + upload
-        print("device tree build refused (%s): falling back to the host build" % e, file=sys.stderr)
-        t0 = time.perf_counter()
-        host_tree = sq.force_tree_full(pman)
-        tv = host_tree.view()
-        capi.check(capi.hip.shq_tree_upload(ctx.h, C.byref(tv)))
-        t_tree_build = time.perf_counter() - t0
-        numnodes = int(host_tree.numnodes)
-        tb = capi.TreeBuildStats(n, numnodes, 0, 0.0)
-
-    def step(gp, one_call=None):
-        """gravpm_force, then grav_short_tree for every particle with OldAcc = |FullTreeGravAccel of the last step + the new
-        GravPM| / G (the reference's order on a PM step, run.cpp:518-563): as the library's one call (readout and OldAcc refresh
-        ride in the walk's prologue) or, with --separate-calls, as its three separate ones.  Same results bit for bit
-        (tests/test_gpu_gravity.py::test_treepm_step_equals_the_three_separate_calls)."""
-        if one_call is None:
-            one_call = not args.separate_calls and args.walk_mode == 0
-        if one_call:
-            capi.check(capi.hip.shq_treepm_step(ctx.h, C.byref(pmp), C.byref(gp), 1, sq.WALK_EXACT))
-        else:
-            capi.check(capi.hip.shq_pm_run(ctx.h, C.byref(pmp)))
-            capi.check(capi.hip.shq_grav_refresh_oldacc(ctx.h, G))
-            capi.check(capi.hip.shq_grav_short_run(ctx.h, C.byref(gp), None, 0, 1, args.walk_mode))
-
-    # the timed steps run the production walk (no diagnostic counters); the wave-level figures under kernels.tree_* come from
-    # one more, untimed step with the counters on (a separate kernel instantiation: its own row in a profile)
-    capi.check(capi.hip.shq_set_walk_stats(ctx.h, 0))
-    # seeding: PM + Barnes-Hut walk (theta = 0.175) so that the timed walks use the relative criterion
-    t0 = time.perf_counter()
-    step(gp_bh)
-    ctx.synchronize()
-    t_seed = time.perf_counter() - t0
-    for _ in range(args.warmup):
-        step(gp_rel)
-    ctx.synchronize()
-
-    def barrier():
-        if dist is not None:
-            dist.barrier()
-
-    walk_ms, pm_ms = [], []
-    barrier()
-    ctx.synchronize()
-    t0 = time.perf_counter()
-    ctx.timer_begin(0)
-    for _ in range(args.steps):
-        step(gp_rel)
-    ctx.timer_end(0)
-    ctx.synchronize()
-    elapsed = time.perf_counter() - t0
-    barrier()
-    ev_ms = ctx.timer_ms(0)
-    if dist is not None:
-        import torch
-        tt = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt.item())
-
-    # per-kernel durations of the last step (HIP events recorded on the launch stream)
-    st = sq.WalkStats()
-    capi.check(capi.hip.shq_grav_short_download(ctx.h, None, None, None, C.byref(st)))
-    ph = (C.c_double * 6)()
-    capi.check(capi.hip.shq_pm_phase_ms(ctx.h, C.byref(ph)))
-    ph = list(ph)
-    fused = C.c_int(0)
-    capi.check(capi.hip.shq_treepm_last_fused(ctx.h, C.byref(fused)))
-    one_call_route = not args.separate_calls and args.walk_mode == 0
-    step_route = ("shq_treepm_step: PM readout + OldAcc refresh in the walk's task prologue" if fused.value and one_call_route
-                  else "shq_treepm_step: the PM's readout kernel forms OldAcc, then the walk" if one_call_route
-                  else "shq_pm_run + shq_grav_refresh_oldacc + shq_grav_short_run")
-    # the pair kernel's sticky status after the timed loop (no download inside it): launches the mop-up pass had to finish, the
-    # deepest pair stack; an overflow in any of the timed steps comes back here as an error
-    pair_rec, pair_high, pair_mop = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-    capi.check(capi.hip.shq_walk_pair_status(ctx.h, C.byref(pair_rec), C.byref(pair_high), C.byref(pair_mop)))
-    if args.dump_outputs:                    # before the counted step below overwrites the last timed step's results
-        dump_outputs(ctx, capi, n, args.dump_outputs)
-    capi.check(capi.hip.shq_set_walk_stats(ctx.h, 1))
-    step(gp_rel, one_call=False)
-    capi.check(capi.hip.shq_grav_refresh_oldacc(ctx.h, G))   # the OldAcc of the NEXT step, for the checks below
-    stw = sq.WalkStats()
-    capi.check(capi.hip.shq_grav_short_download(ctx.h, None, None, None, C.byref(stw)))
-    for k in ("nnodes_visited", "nwave_interactions", "nwave_node_interactions", "nnode_interactions"):
-        setattr(st, k, getattr(stw, k))
-    counted_walk_ms = float(stw.kernel_ms)
-
-    ncells = float(nmesh) ** 3
-    # ---- algorithmic bytes (DESIGN.md §4, SURVEY.md §8(d)) ------------------------------------------
-    # tree walk: compulsory traffic only (targets in/out + node pool once); the walk is not HBM-bound
-    tree_bytes = 68.0 * n + 76.0 * numnodes
-    # PM as THIS pipeline runs it: zero (8 C write) + deposit (32 N read, 8 cells x 8 B RMW) +
-    # 5 fused FFT passes (read + write of the padded mesh each) + readout (32 N read, 56 cells x 8 B
-    # gathered, 32 N written)
-    zp = 2 * (((nmesh // 2 + 1) + 3) // 4 * 4)
-    mesh_bytes = 8.0 * nmesh * nmesh * zp
-    fft_bytes = 5 * 2 * mesh_bytes
-    deposit_bytes = (32.0 + 128.0) * n
-    readout_bytes = (32.0 + 448.0 + 32.0) * n
-    oldacc_bytes = (24.0 + 8.0) * n                       # the readout kernel also reads FullTreeGravAccel and writes OldAcc
-    pm_bytes = mesh_bytes + deposit_bytes + fft_bytes + readout_bytes
-    # PM with the reference's structure (1 r2c + 4 c2r, separate transfer sweeps), for comparison only
-    pm_bytes_reference_structure = 468.0 * n + 240.0 * ncells
-    walk_s = st.kernel_ms * 1e-3
-    pm_s = ph[5] * 1e-3
-    fft_s = (ph[1] + ph[2] + ph[3]) * 1e-3
-    dominant = "grav_walk_exact_kernel" if walk_s >= pm_s else "pm (deposit + 5 fused FFT passes + readout)"
-    ach = (tree_bytes / walk_s if walk_s >= pm_s else pm_bytes / pm_s) / 1e9
-    # HBM traffic per launch from the committed PMC summary of this same command (profiles/, made with
-    # tools/pmc_summary.py from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes), if present: a counter pass cannot
-    # run inside this process, so these two numbers are the committed measurement of the same kernels on the same workload
-    traffic = traffic_fft = traffic_pair = None
-    valu_busy = None
-    pj = load_profile("bench256_pmc_hbm.json")
-    if pj and n1 == 256 and world == 1:
-        # the production walk: potential on, no prefetch, leaf batch 2, no counters, relative criterion, primary walk
-        key = production_walk_key(pj)
-        if key:
-            traffic = hbm_bytes(pj[key])
-        fk = [k for k in pj if k.startswith("fft_t_")] or [k for k in pj if k.startswith("fft_pass_")]   # transposing / in-place pipeline
-        if len(fk) == 5:
-            traffic_fft = sum(hbm_bytes(pj[k]) for k in fk)
-        pk = [k for k in pj if k.startswith("grav_pair_kernel_live<true>")]
-        traffic_pair = hbm_bytes(pj[pk[0]]) if pk else None
-    sj = load_profile("bench256_pmc_sq.json")
-    if sj:
-        key = production_walk_key(sj)
-        if key and sj[key].get("SQ_BUSY_CYCLES"):
-            e = sj[key]
-            # SQ_INSTS_VALU x 4 cycles per wave instruction over the SIMD cycles the kernel was resident (SQ_BUSY_CYCLES counts per
-            # shader engine: / 32 engines x 1024 SIMDs)
-            valu_busy = e.get("SQ_INSTS_VALU", 0.0) * 4.0 / (e["SQ_BUSY_CYCLES"] / 32.0 * 1024.0)
-    # The dominant kernel, the tree walk, is bound by FP64 issue, not by HBM (0.1 kB of compulsory traffic per
-    # target against ~500 interactions of ~45 flop, SURVEY §8(d)): its roofline is the FP64 vector peak (78.6
-    # TFLOP/s on MI355X; no MFMA instruction is used or usable: bound "valu-f64").  The HBM view of the same launch
-    # stays alongside: algorithmic bytes, measured traffic.
-    walk_flops = 45.0 * st.ninteractions
-    # what one launch of the production walk moves by design: the walk's compulsory bytes, the PM mesh it clears for the next deposit
-    # (the `scrub` in the tasks' prologue), and - only on the fused route - the readout of its own targets (512 B each) + OldAcc
-    pm_cov_bytes = deposit_bytes + fft_bytes + (0.0 if fused.value else readout_bytes + oldacc_bytes)
-    walk_alg = {"tree_walk": tree_bytes, "pm_mesh_cleared_in_the_walk": mesh_bytes,
-                "pm_readout_in_the_prologue": (readout_bytes + oldacc_bytes) if fused.value else 0.0}
-    walk_alg_bytes = sum(walk_alg.values())
-    walk_roofline = {"bound": "valu-f64", "kernel": "grav_walk_exact_kernel", "achieved": walk_flops / max(walk_s, 1e-12) / 1e12,
-                     "peak": FP64_VECTOR_PEAK_TF, "unit": "TFLOP/s",
-                     "frac": walk_flops / max(walk_s, 1e-12) / 1e12 / FP64_VECTOR_PEAK_TF, "traffic": traffic, "traffic_pair_kernel": traffic_pair,
-                     "algorithmic_flops": walk_flops, "algorithmic_bytes": walk_alg_bytes, "algorithmic_bytes_parts": walk_alg,
-                     "hbm_algorithmic_GBs": walk_alg_bytes / max(walk_s, 1e-12) / 1e9,
-                     "valu_busy": valu_busy,
-                     "note": "FP64-issue bound: 45 flop per interaction (SURVEY 8(d)) x interactions / kernel time against the FP64 "
-                             "peak; valu_busy = SQ_INSTS_VALU x 4 / resident SIMD cycles from the committed SQ pass, in which the profiler "
-                             "SERIALISES the main walk and the pair kernel (a counter pass cannot see them overlapped); `traffic` = HBM "
-                             "bytes per launch of the production walk (main walk row only) from the committed FETCH_SIZE / WRITE_SIZE "
-                             "passes, against algorithmic_bytes = the parts listed.  The HBM-bound part "
-                             "of the step is the PM: roofline_pm_fft.  Kernel time = one HIP-event bracket on the walk's stream around "
-                             "grav_walk_exact_kernel and grav_pair_kernel, which runs beside it on a second stream and is waited for "
-                             "before the closing event (both start within 10 us, the pair kernel ends ~0.3 ms after the walk: "
-                             "profiles/README.md); the interactions counted are those of both"}
-    out = {
-        "metric": "particle-steps/sec (grav+PM+SPH) at 256^3; rms force error vs ref",
-        "value": n * world * args.steps / elapsed,
-        "unit": "particle-steps/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": "dm-only %d^3 TreePM (S-%s, Nmesh %d, Asmth 1.5, Rcut 6, ErrTolForceAcc %g, exact window)"
-                               % (n1, args.kind, nmesh, args.errtol),
-                   "particles_per_gpu": n, "nmesh": nmesh, "parallelism": "replicas x%d" % world if world > 1 else "1 GPU",
-                   "walk": "exact (per-target reference opening decisions)", "step_calls": step_route},
-        "roofline": walk_roofline if walk_s >= pm_s else
-                    {"bound": "hbm", "kernel": dominant, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": ach / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes": pm_bytes},
-        "roofline_pm_fft": {"bound": "hbm", "kernel": "fft_t_z_fwd / fft_t_tile x3 / fft_t_z_inv (5 fused passes, transposing pipeline)",
-                            "achieved": fft_bytes / max(fft_s, 1e-12) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                            "frac": fft_bytes / max(fft_s, 1e-12) / 1e9 / HBM_PEAK_GBS, "traffic": traffic_fft,
-                            "algorithmic_bytes": fft_bytes,
-                            "note": "yardstick: tools/copy_probe.hip moves this mesh with 16-byte loads and stores at 5.8 TB/s in contiguous "
-                                    "48 KB tiles (6.4 TB/s for a plain nontemporal copy), 4.6 TB/s with one side in 64-byte pieces, 3.0-3.9 TB/s "
-                                    "with both sides in 64-byte pieces (the in-place passes of rounds 1-3); the transposing pipeline of round 4 "
-                                    "has contiguous tiles on eight of its ten sides: its five passes at the probe's rates would take 6.9 ms"},
-        "kernels": {
-            "tree_walk_ms": st.kernel_ms, "tree_walk_with_counters_ms": counted_walk_ms,
-            "pair_kernel_recovered_launches": int(pair_rec.value), "pair_kernel_stack_high_water": int(pair_high.value),
-            "pair_kernel_lean_records": bool(capi.hip.shq_walk_pair_lean(ctx.h) == 1), "tree_interactions_per_target": st.ninteractions / max(1, st.ntargets),
-            "tree_interactions_per_s": st.ninteractions / max(walk_s, 1e-12),
-            "tree_fp64_frac_of_vector_peak": 45.0 * st.ninteractions / max(walk_s, 1e-12) / 1e12 / FP64_VECTOR_PEAK_TF,
-            "tree_nodes_visited_per_wave": st.nnodes_visited / max(1.0, st.ntargets / 64.0),
-            "tree_lane_efficiency": st.ninteractions / max(1.0, 64.0 * st.nwave_interactions),
-            "tree_node_rounds_per_wave": st.nwave_node_interactions / max(1.0, st.ntargets / 64.0),
-            "tree_particle_rounds_per_wave": (st.nwave_interactions - st.nwave_node_interactions) / max(1.0, st.ntargets / 64.0),
-            "tree_node_interactions_per_target": st.nnode_interactions / max(1, st.ntargets),
-            "tree_algorithmic_GBs": tree_bytes / max(walk_s, 1e-12) / 1e9,
-            # the bespoke pipeline runs forward FFT, Green's function and inverse FFT as five fused passes: one phase
-            "pm_ms": {"zero_and_deposit": ph[0], "fft_pipeline_5_passes_incl_greens_function": ph[1] + ph[2] + ph[3], "readout": ph[4],
-                      "total": ph[5],
-                      "note": "zero: the mesh is cleared in the shadow of the previous walk; readout: 0 when the walk's prologue does it (config.step_calls)"},
-            "tree_wave_figures_from": "the counter launch (one task per wave, no leaf ring): lane efficiency and rounds per wave describe the union walk, not the ring's drain",
-            # the bytes of what pm_ms.total covers: deposit + five passes + (unless the walk's prologue did it) readout and OldAcc; the
-            # clearing of the mesh rides in the walk and is counted there (roofline.algorithmic_bytes_parts)
-            "pm_algorithmic_GBs": pm_cov_bytes / max(pm_s, 1e-12) / 1e9,
-            "pm_frac_of_hbm_peak": pm_cov_bytes / max(pm_s, 1e-12) / 1e9 / HBM_PEAK_GBS,
-            "pm_reference_structure_GBs": pm_bytes_reference_structure / max(pm_s, 1e-12) / 1e9,
-            "event_ms_per_step": ev_ms / args.steps,
-        },
-        "setup_s": {"synthetic_input": t_setup, "upload": t_upload, "tree_build_device": t_tree_build,
-                    "tree_build_device_kernels_ms": float(tb.build_ms), "tree_nodes": numnodes, "tree_depth": int(tb.maxdepth),
-                    "seed_step": t_seed},
-    }
     if rank == 0 and not args.no_cpu_baseline:
         t0 = time.perf_counter()
         tree = sq.force_tree_full(pman)      # host build of the same tree, for the oracle only
@@ -1107,6 +879,273 @@ def main():
         for k in ("roofline_sph_density", "roofline_sph_hydro"):
             out[k] = figs.pop(k)
         out["kernels"].update(figs)
+
+
+def main():
+    args = parse()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("SHQ_COMM_FORCE", "0") == "1"):
+        raise SystemExit("bench.py: --dump-outputs is for the one-GPU run")
+    if args.gpus > 1 and "WORLD_SIZE" not in os.environ and os.environ.get("SHQ_COMM_FORCE", "0") != "1":
+        sys.exit(launch_ranks(args))
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if world > 1 or os.environ.get("SHQ_COMM_FORCE", "0") == "1":   # the latter: one-rank RCCL rehearsal (needs MASTER_ADDR/PORT)
+        return run_sharded(args, rank, local_rank, world)
+    dist = None
+    sys.stdout.flush()   # stdout carries the one JSON line only; anything a library prints goes to stderr
+    json_fd = os.dup(1)
+    os.dup2(2, 1)
+
+    import shenqi_amd as sq
+    from shenqi_amd import capi
+
+    n1 = args.n
+    n = n1**3
+    L = 1.0
+    nmesh = 3 * n1 if n1 != 512 else 1024
+    t_setup = time.perf_counter()
+    pos = sq.synth_positions(args.kind, n, seed=20240601 + rank, L=L)
+    pos = pos[sq.hilbert_order(pos, L)]  # Peano-Hilbert order, as the reference keeps its particles (domain.cpp:268)
+    pman = sq.PartManager(n, L)
+    P = pman.Base
+    P["Pos"] = pos
+    P["Type"] = 1
+    P["Mass"] = 1.0
+    t_setup = time.perf_counter() - t_setup
+
+    ctx = sq.Context(local_rank if world > 1 else 0)
+    sq.set_gravshort_treepar(ErrTolForceAcc=args.errtol, BHOpeningAngle=0.175, MaxBHOpeningAngle=0.9, TreeUseBH=1, Rcut=6.0)
+    sq.gravshort_set_softenings(L / n1)
+    gp_bh = sq.make_grav_params(L, 1.5, nmesh, G, RHO0)
+    sq.set_gravshort_treepar(ErrTolForceAcc=args.errtol, BHOpeningAngle=0.175, MaxBHOpeningAngle=0.9, TreeUseBH=0, Rcut=6.0)
+    gp_rel = sq.make_grav_params(L, 1.5, nmesh, G, RHO0)
+    pmp = sq.PMParams(nmesh, 0, L, 1.5, G)
+
+    pv = pman.view()
+    t0 = time.perf_counter()
+    capi.check(capi.hip.shq_particles_upload(ctx.h, C.byref(pv)))
+    t_upload = time.perf_counter() - t0
+    # the tree is built on the device (shq_tree_build: bit-identical to the host / reference tree, see
+    # tests/test_gpu_treebuild.py); outside the timed region like the host build it replaces (SURVEY §8(d))
+    try:
+        sq.tree_build_device(ctx, L)         # first call allocates the scratch
+        t0 = time.perf_counter()
+        tb = sq.tree_build_device(ctx, L)
+        t_tree_build = time.perf_counter() - t0
+        numnodes = int(tb.numnodes)
+    except sq.ShqError as e:                 # deeper than 21 levels: host build (8 OpenMP threads' worth) + upload
+        print("device tree build refused (%s): falling back to the host build" % e, file=sys.stderr)
+        t0 = time.perf_counter()
+        host_tree = sq.force_tree_full(pman)
+        tv = host_tree.view()
+        capi.check(capi.hip.shq_tree_upload(ctx.h, C.byref(tv)))
+        t_tree_build = time.perf_counter() - t0
+        numnodes = int(host_tree.numnodes)
+        tb = capi.TreeBuildStats(n, numnodes, 0, 0.0)
+
+    def step(gp, one_call=None):
+        """gravpm_force, then grav_short_tree for every particle with OldAcc = |FullTreeGravAccel of the last step + the new
+        GravPM| / G (the reference's order on a PM step, run.cpp:518-563): as the library's one call (readout and OldAcc refresh
+        ride in the walk's prologue) or, with --separate-calls, as its three separate ones.  Same results bit for bit
+        (tests/test_gpu_gravity.py::test_treepm_step_equals_the_three_separate_calls)."""
+        if one_call is None:
+            one_call = not args.separate_calls and args.walk_mode == 0
+        if one_call:
+            capi.check(capi.hip.shq_treepm_step(ctx.h, C.byref(pmp), C.byref(gp), 1, sq.WALK_EXACT))
+        else:
+            capi.check(capi.hip.shq_pm_run(ctx.h, C.byref(pmp)))
+            capi.check(capi.hip.shq_grav_refresh_oldacc(ctx.h, G))
+            capi.check(capi.hip.shq_grav_short_run(ctx.h, C.byref(gp), None, 0, 1, args.walk_mode))
+
+    # the timed steps run the production walk (no diagnostic counters); with --full, the wave-level figures under kernels.tree_* come
+    # from one more, untimed step with the counters on (a separate kernel instantiation: its own row in a profile)
+    capi.check(capi.hip.shq_set_walk_stats(ctx.h, 0))
+    # seeding: PM + Barnes-Hut walk (theta = 0.175) so that the timed walks use the relative criterion
+    t0 = time.perf_counter()
+    step(gp_bh)
+    ctx.synchronize()
+    t_seed = time.perf_counter() - t0
+    for _ in range(args.warmup):
+        step(gp_rel)
+    ctx.synchronize()
+
+    def barrier():
+        if dist is not None:
+            dist.barrier()
+
+    walk_ms, pm_ms = [], []
+    barrier()
+    ctx.synchronize()
+    t0 = time.perf_counter()
+    ctx.timer_begin(0)
+    for _ in range(args.steps):
+        step(gp_rel)
+    ctx.timer_end(0)
+    ctx.synchronize()
+    elapsed = time.perf_counter() - t0
+    barrier()
+    ev_ms = ctx.timer_ms(0)
+    if dist is not None:
+        import torch
+        tt = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
+
+    # per-kernel durations of the last step (HIP events recorded on the launch stream)
+    st = sq.WalkStats()
+    capi.check(capi.hip.shq_grav_short_download(ctx.h, None, None, None, C.byref(st)))
+    ph = (C.c_double * 6)()
+    capi.check(capi.hip.shq_pm_phase_ms(ctx.h, C.byref(ph)))
+    ph = list(ph)
+    fused = C.c_int(0)
+    capi.check(capi.hip.shq_treepm_last_fused(ctx.h, C.byref(fused)))
+    one_call_route = not args.separate_calls and args.walk_mode == 0
+    step_route = ("shq_treepm_step: PM readout + OldAcc refresh in the walk's task prologue" if fused.value and one_call_route
+                  else "shq_treepm_step: the PM's readout kernel forms OldAcc, then the walk" if one_call_route
+                  else "shq_pm_run + shq_grav_refresh_oldacc + shq_grav_short_run")
+    # the pair kernel's sticky status after the timed loop (no download inside it): launches the mop-up pass had to finish, the
+    # deepest pair stack; an overflow in any of the timed steps comes back here as an error
+    pair_rec, pair_high, pair_mop = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+    capi.check(capi.hip.shq_walk_pair_status(ctx.h, C.byref(pair_rec), C.byref(pair_high), C.byref(pair_mop)))
+    if args.dump_outputs:                    # before the counted step below overwrites the last timed step's results
+        dump_outputs(ctx, capi, n, args.dump_outputs)
+    counted = {}
+    if args.full:
+        capi.check(capi.hip.shq_set_walk_stats(ctx.h, 1))
+        step(gp_rel, one_call=False)
+        capi.check(capi.hip.shq_grav_refresh_oldacc(ctx.h, G))   # the OldAcc of the NEXT step, for the checks below
+        stw = sq.WalkStats()
+        capi.check(capi.hip.shq_grav_short_download(ctx.h, None, None, None, C.byref(stw)))
+        counted = {
+            "tree_walk_with_counters_ms": float(stw.kernel_ms),
+            "tree_nodes_visited_per_wave": stw.nnodes_visited / max(1.0, st.ntargets / 64.0),
+            "tree_lane_efficiency": st.ninteractions / max(1.0, 64.0 * stw.nwave_interactions),
+            "tree_node_rounds_per_wave": stw.nwave_node_interactions / max(1.0, st.ntargets / 64.0),
+            "tree_particle_rounds_per_wave": (stw.nwave_interactions - stw.nwave_node_interactions) / max(1.0, st.ntargets / 64.0),
+            "tree_node_interactions_per_target": stw.nnode_interactions / max(1, st.ntargets),
+            "tree_wave_figures_from": "the counter launch (one task per wave, no leaf ring): lane efficiency and rounds per wave describe the "
+                                      "union walk, not the ring's drain"}
+
+    ncells = float(nmesh) ** 3
+    # ---- algorithmic bytes (DESIGN.md §4, SURVEY.md §8(d)) ------------------------------------------
+    # tree walk: compulsory traffic only (targets in/out + node pool once); the walk is not HBM-bound
+    tree_bytes = 68.0 * n + 76.0 * numnodes
+    # PM as THIS pipeline runs it: zero (8 C write) + deposit (32 N read, 8 cells x 8 B RMW) +
+    # 5 fused FFT passes (read + write of the padded mesh each) + readout (32 N read, 56 cells x 8 B
+    # gathered, 32 N written)
+    zp = 2 * (((nmesh // 2 + 1) + 3) // 4 * 4)
+    mesh_bytes = 8.0 * nmesh * nmesh * zp
+    fft_bytes = 5 * 2 * mesh_bytes
+    deposit_bytes = (32.0 + 128.0) * n
+    readout_bytes = (32.0 + 448.0 + 32.0) * n
+    oldacc_bytes = (24.0 + 8.0) * n                       # the readout kernel also reads FullTreeGravAccel and writes OldAcc
+    pm_bytes = mesh_bytes + deposit_bytes + fft_bytes + readout_bytes
+    # PM with the reference's structure (1 r2c + 4 c2r, separate transfer sweeps), for comparison only
+    pm_bytes_reference_structure = 468.0 * n + 240.0 * ncells
+    walk_s = st.kernel_ms * 1e-3
+    pm_s = ph[5] * 1e-3
+    fft_s = (ph[1] + ph[2] + ph[3]) * 1e-3
+    dominant = "grav_walk_exact_kernel" if walk_s >= pm_s else "pm (deposit + 5 fused FFT passes + readout)"
+    ach = (tree_bytes / walk_s if walk_s >= pm_s else pm_bytes / pm_s) / 1e9
+    # HBM traffic per launch from the committed PMC summary of this same command (profiles/, made with
+    # tools/pmc_summary.py from separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes), if present: a counter pass cannot
+    # run inside this process, so these two numbers are the committed measurement of the same kernels on the same workload
+    traffic = traffic_fft = traffic_pair = None
+    valu_busy = None
+    pj = load_profile("bench256_pmc_hbm.json")
+    if pj and n1 == 256 and world == 1:
+        # the production walk: potential on, no prefetch, leaf batch 2, no counters, relative criterion, primary walk
+        key = production_walk_key(pj)
+        if key:
+            traffic = hbm_bytes(pj[key])
+        fk = [k for k in pj if k.startswith("fft_t_")] or [k for k in pj if k.startswith("fft_pass_")]   # transposing / in-place pipeline
+        if len(fk) == 5:
+            traffic_fft = sum(hbm_bytes(pj[k]) for k in fk)
+        pk = [k for k in pj if k.startswith("grav_pair_kernel_live<true>")]
+        traffic_pair = hbm_bytes(pj[pk[0]]) if pk else None
+    sj = load_profile("bench256_pmc_sq.json")
+    if sj:
+        key = production_walk_key(sj)
+        if key and sj[key].get("SQ_BUSY_CYCLES"):
+            e = sj[key]
+            # SQ_INSTS_VALU x 4 cycles per wave instruction over the SIMD cycles the kernel was resident (SQ_BUSY_CYCLES counts per
+            # shader engine: / 32 engines x 1024 SIMDs)
+            valu_busy = e.get("SQ_INSTS_VALU", 0.0) * 4.0 / (e["SQ_BUSY_CYCLES"] / 32.0 * 1024.0)
+    # The dominant kernel, the tree walk, is bound by FP64 issue, not by HBM (0.1 kB of compulsory traffic per
+    # target against ~500 interactions of ~45 flop, SURVEY §8(d)): its roofline is the FP64 vector peak (78.6
+    # TFLOP/s on MI355X; no MFMA instruction is used or usable: bound "valu-f64").  The HBM view of the same launch
+    # stays alongside: algorithmic bytes, measured traffic.
+    walk_flops = 45.0 * st.ninteractions
+    # what one launch of the production walk moves by design: the walk's compulsory bytes, the PM mesh it clears for the next deposit
+    # (the `scrub` in the tasks' prologue), and - only on the fused route - the readout of its own targets (512 B each) + OldAcc
+    pm_cov_bytes = deposit_bytes + fft_bytes + (0.0 if fused.value else readout_bytes + oldacc_bytes)
+    walk_alg = {"tree_walk": tree_bytes, "pm_mesh_cleared_in_the_walk": mesh_bytes,
+                "pm_readout_in_the_prologue": (readout_bytes + oldacc_bytes) if fused.value else 0.0}
+    walk_alg_bytes = sum(walk_alg.values())
+    walk_roofline = {"bound": "valu-f64", "kernel": "grav_walk_exact_kernel", "achieved": walk_flops / max(walk_s, 1e-12) / 1e12,
+                     "peak": FP64_VECTOR_PEAK_TF, "unit": "TFLOP/s",
+                     "frac": walk_flops / max(walk_s, 1e-12) / 1e12 / FP64_VECTOR_PEAK_TF, "traffic": traffic, "traffic_pair_kernel": traffic_pair,
+                     "algorithmic_flops": walk_flops, "algorithmic_bytes": walk_alg_bytes, "algorithmic_bytes_parts": walk_alg,
+                     "hbm_algorithmic_GBs": walk_alg_bytes / max(walk_s, 1e-12) / 1e9,
+                     "valu_busy": valu_busy,
+                     "note": "FP64-issue bound: 45 flop per interaction (SURVEY 8(d)) x interactions / kernel time against the FP64 "
+                             "peak; valu_busy = SQ_INSTS_VALU x 4 / resident SIMD cycles from the committed SQ pass, in which the profiler "
+                             "SERIALISES the main walk and the pair kernel (a counter pass cannot see them overlapped); `traffic` = HBM "
+                             "bytes per launch of the production walk (main walk row only) from the committed FETCH_SIZE / WRITE_SIZE "
+                             "passes, against algorithmic_bytes = the parts listed.  The HBM-bound part "
+                             "of the step is the PM: roofline_pm_fft.  Kernel time = one HIP-event bracket on the walk's stream around "
+                             "grav_walk_exact_kernel and grav_pair_kernel, which runs beside it on a second stream and is waited for "
+                             "before the closing event (both start within 10 us, the pair kernel ends ~0.3 ms after the walk: "
+                             "profiles/README.md); the interactions counted are those of both"}
+    out = {
+        "metric": "particle-steps/sec (grav+PM+SPH) at 256^3; rms force error vs ref",
+        "value": n * world * args.steps / elapsed,
+        "unit": "particle-steps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": "dm-only %d^3 TreePM (S-%s, Nmesh %d, Asmth 1.5, Rcut 6, ErrTolForceAcc %g, exact window)"
+                               % (n1, args.kind, nmesh, args.errtol),
+                   "particles_per_gpu": n, "nmesh": nmesh, "parallelism": "replicas x%d" % world if world > 1 else "1 GPU",
+                   "walk": "exact (per-target reference opening decisions)", "step_calls": step_route},
+        "roofline": walk_roofline if walk_s >= pm_s else
+                    {"bound": "hbm", "kernel": dominant, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": ach / HBM_PEAK_GBS, "traffic": None, "algorithmic_bytes": pm_bytes},
+        "roofline_pm_fft": {"bound": "hbm", "kernel": "fft_t_z_fwd / fft_t_tile x3 / fft_t_z_inv (5 fused passes, transposing pipeline)",
+                            "achieved": fft_bytes / max(fft_s, 1e-12) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": fft_bytes / max(fft_s, 1e-12) / 1e9 / HBM_PEAK_GBS, "traffic": traffic_fft,
+                            "algorithmic_bytes": fft_bytes,
+                            "note": "yardstick: tools/copy_probe.hip moves this mesh with 16-byte loads and stores at 5.8 TB/s in contiguous "
+                                    "48 KB tiles (6.4 TB/s for a plain nontemporal copy), 4.6 TB/s with one side in 64-byte pieces, 3.0-3.9 TB/s "
+                                    "with both sides in 64-byte pieces (the in-place passes of rounds 1-3); the transposing pipeline of round 4 "
+                                    "has contiguous tiles on eight of its ten sides: its five passes at the probe's rates would take 6.9 ms"},
+        "kernels": {
+            "tree_walk_ms": st.kernel_ms,
+            "pair_kernel_recovered_launches": int(pair_rec.value), "pair_kernel_stack_high_water": int(pair_high.value),
+            "pair_kernel_lean_records": bool(capi.hip.shq_walk_pair_lean(ctx.h) == 1), "tree_interactions_per_target": st.ninteractions / max(1, st.ntargets),
+            "tree_interactions_per_s": st.ninteractions / max(walk_s, 1e-12),
+            "tree_fp64_frac_of_vector_peak": 45.0 * st.ninteractions / max(walk_s, 1e-12) / 1e12 / FP64_VECTOR_PEAK_TF,
+            "tree_algorithmic_GBs": tree_bytes / max(walk_s, 1e-12) / 1e9,
+            # the bespoke pipeline runs forward FFT, Green's function and inverse FFT as five fused passes: one phase
+            "pm_ms": {"zero_and_deposit": ph[0], "fft_pipeline_5_passes_incl_greens_function": ph[1] + ph[2] + ph[3], "readout": ph[4],
+                      "total": ph[5],
+                      "note": "zero: the mesh is cleared in the shadow of the previous walk; readout: 0 when the walk's prologue does it (config.step_calls)"},
+            # the bytes of what pm_ms.total covers: deposit + five passes + (unless the walk's prologue did it) readout and OldAcc; the
+            # clearing of the mesh rides in the walk and is counted there (roofline.algorithmic_bytes_parts)
+            "pm_algorithmic_GBs": pm_cov_bytes / max(pm_s, 1e-12) / 1e9,
+            "pm_frac_of_hbm_peak": pm_cov_bytes / max(pm_s, 1e-12) / 1e9 / HBM_PEAK_GBS,
+            "pm_reference_structure_GBs": pm_bytes_reference_structure / max(pm_s, 1e-12) / 1e9,
+            "event_ms_per_step": ev_ms / args.steps,
+            **counted,
+        },
+        "setup_s": {"synthetic_input": t_setup, "upload": t_upload, "tree_build_device": t_tree_build,
+                    "tree_build_device_kernels_ms": float(tb.build_ms), "tree_nodes": numnodes, "tree_depth": int(tb.maxdepth),
+                    "seed_step": t_seed},
+    }
+    if args.full:
+        full_figures(args, ctx, out, pman, pos, gp_rel, pmp, n1, L, rank)
     ctx.close()
     if dist is not None:
         dist.barrier()

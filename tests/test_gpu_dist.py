@@ -410,14 +410,15 @@ def test_bench_driver_command_two_gloo_ranks(ngrid, total, shared):
     """The driver's own multi-GPU command — `python bench.py --gpus 2`, which starts its ranks through torch.distributed.run
     (bench.launch_ranks) — rehearsed on the one-GPU box with SHQ_BENCH_BACKEND=gloo (both ranks share device 0, exchanges staged
     through the host): one JSON line on stdout, whole-job value, weak scaling, the sharded walk's roofline, and the sampled
-    force check of the global particle set against direct summation.  ngrid 26 -> 32^3 particles on a 96 mesh, which has the
+    force check of the global particle set against direct summation (--full).  ngrid 26 -> 32^3 particles on a 96 mesh, which has the
     library's own transforms: there the rebalanced slabs share the plane the cut falls in (config.slab_ycuts)."""
     import json
     import subprocess
     env = dict(os.environ, SHQ_BENCH_BACKEND="gloo", OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--ngrid", str(ngrid), "--steps", "1", "--warmup", "0"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--ngrid", str(ngrid), "--steps", "1", "--warmup", "0",
+                        "--full"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-2000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
@@ -492,14 +493,14 @@ def test_dist_sph_device_resident(world):
 
 def test_bench_c5_mode_two_gloo_ranks():
     """`bench.py --gpus 2 --workload c5`: the C5-shaped step (gas + dark matter: sharded TreePM + device-resident sharded density and
-    hydro) through the driver's launch path, rehearsed over gloo on one GPU: one JSON line with the three operators' rooflines"""
+    hydro) through the driver's launch path, rehearsed over gloo on one GPU: one JSON line with the three operators' rooflines (--full)"""
     import json
     import subprocess
     env = dict(os.environ, SHQ_BENCH_BACKEND="gloo", OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--ngrid", "16", "--steps", "1", "--warmup", "0",
-                        "--workload", "c5"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--workload", "c5", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -516,7 +517,7 @@ def test_bench_c5_mode_one_rank_rccl():
     """`bench.py --workload c5` as a ONE-rank RCCL group (SHQ_COMM_FORCE=1: every exchange of the sharded TreePM and of the
     device-resident sharded SPH is a real RCCL collective on the one GPU - self-copies, so no scaling figure, but the nccl code
     paths of Comm, the device-tensor ghost rows and the stream hand-overs all run): one JSON line, the three operators'
-    rooflines, a force check of the global set against direct summation."""
+    rooflines (--full), a force check of the global set against direct summation."""
     import json
     import socket
     import subprocess
@@ -528,7 +529,7 @@ def test_bench_c5_mode_one_rank_rccl():
                OMP_NUM_THREADS="4", HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("SHQ_BENCH_BACKEND", None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--ngrid", "32", "--steps", "1", "--warmup", "0",
-                        "--workload", "c5"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                        "--workload", "c5", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
     assert len(lines) == 1, lines

@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/profiles_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-B="python3 $ROOT/bench.py"
+B="python3 $ROOT/bench.py --full"
 S="python3 $ROOT/tools/bench_sph.py 128 uniform 2"
 cat_csv() { first=1; for f in "$@"; do if [ $first = 1 ]; then cat "$f"; first=0; else tail -n +2 "$f"; fi; done; }
 one() { find "$1" -name "*$2" | head -1; }

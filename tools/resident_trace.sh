@@ -2,7 +2,7 @@
 # tools/resident_trace.sh : kernel timeline (rocprofv3 --kernel-trace) of the LAST moving-particle step of the bench's resident loop: drift -> {PM on the
 # second stream | tree build} -> walk + pair kernel -> kicks.  Prints every kernel longer than 50 us and the gaps.  GPU box, repo root.
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/resident_trace; mkdir -p $OUT; export TMPDIR=/tmp; cd /tmp; rm -rf $OUT/t
-timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -o k -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-sph > $OUT/t.log 2>&1
+timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -o k -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-sph > $OUT/t.log 2>&1
 f=$(find $OUT/t -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys
