@@ -1454,6 +1454,53 @@ typedef struct shq_heiii_stats {
 } shq_heiii_stats;
 int shq_heiii_last_stats(shq_context *ctx, shq_heiii_stats *stats);
 
+/* ---- lensing potential planes (write_plane's compute, libgadget/plane.cpp:511-600; cutPlaneGaussianGrid and
+ * calculate_lensing_potential, lenstools.cpp:168-319; the PM neutrino correction, plane.cpp:355-475) ----
+ * For ONE rank: the caller sums the planes over ranks (MPI_Reduce) as write_plane does. */
+typedef struct shq_lens_params {
+    int32_t Resolution;           /* PlaneResolution, 2 .. 46340 */
+    int32_t ncuts, nnormals;      /* ncuts == 0: write_plane's default list (plane.cpp:524-530), (0.5 + i) Thickness for
+                                     i < (size_t)(BoxSize / Thickness) (shq_lens_num_cuts) */
+    int32_t exclude_type2;        /* hybrid_nu_tracer(CP, atime): Type 2 particles are skipped */
+    const double *CutPoints;      /* ncuts, internal length units */
+    const int32_t *Normals;       /* nnormals, each 0..2 (repeats allowed, as BuildOutputList allows) */
+    double Thickness;             /* <= 0: BoxSize (plane.cpp:519-522) */
+    double BoxSize;
+    double CurrentParticleOffset[3];
+} shq_lens_params;
+typedef struct shq_lens_cosmo {
+    double atime, comoving_distance, HubbleParam;
+    double omega_source;          /* Omega0 - a^3 Omega_nu_nopart under MassiveNuLinRespOn (lenstools_particle_omega_source); > 0 */
+    int64_t num_particles_tot;    /* global active count (the sum of shq_lens_count_active over ranks); > 0 */
+} shq_lens_cosmo;
+typedef struct shq_lens_numesh {  /* the optional PM neutrino correction (cutPlanePMNeutrinoCorrection) */
+    int32_t Nmesh, x0, nx, pad_;  /* this rank holds mesh planes [x0, x0 + nx) */
+    double inv_fft_norm, mean_mass_cell;
+    const double *real;           /* host, dense [nx][Nmesh][Nmesh] as shq_pm_apply returns it (unscaled) */
+} shq_lens_numesh;
+/* lenstools_particle_is_active's count on this rank: not Swallowed, and not Type 2 under exclude_type2 (garbage particles count). */
+int shq_lens_count_active(shq_context *ctx, const shq_part_view *parts, int exclude_type2, int64_t *count);
+/* The number of cuts a call makes: ncuts, or the default list's length when ncuts == 0. */
+int shq_lens_num_cuts(const shq_lens_params *params, int32_t *ncuts);
+/* Every (cut, normal) plane of write_plane in one call:
+ *   parts  : Pos, Type and the flag word (Mass is not read: the reference counts particles).  With shq_set_inputs_current(
+ *            SHQ_CURRENT_PARTICLES) and this very view resident (uploaded with Type and the flag word), the resident positions, types
+ *            and flags are read and nothing is uploaded.
+ *   nu     : the rank's x-slab of the PM neutrino correction mesh, or NULL for none.  Its projection is indexed
+ *            [global[(normal + 1) % 3]][global[(normal + 2) % 3]]: for normal 1 that is [z][x], the transpose of the particle plane's
+ *            [x][z], as in the reference.
+ *   planes : out [ncuts][nnormals][R][R], the potential planes of this rank (particle plane layout: normal 0 [y][z], 1 [x][z], 2 [x][y]).
+ *   num_particles_plane : out [ncuts][nnormals]; counts : optional out [ncuts][nnormals][R][R] NGP counts (NULL skips them).
+ * SHQ_ERR_INVALID before anything is written for a normal outside 0..2, Resolution < 2, num_particles_tot <= 0, omega_source <= 0, a
+ * correction with a bad Nmesh, x0 or nx, non-finite BoxSize / Thickness / cut points / offsets, or 2^32 particles or more.  The particles
+ * are read once per call; the correction mesh once per distinct normal (for up to 8 cuts).  Changes no state of the context: the
+ * resident set, a prestarted PM, a pending spectrum, the PM mesh, its scrub state and the deposit type mask survive.  Synchronous. */
+int shq_lens_planes(shq_context *ctx, const shq_lens_params *params, const shq_lens_cosmo *cosmo, const shq_part_view *parts,
+                    const shq_lens_numesh *nu, double *planes, int64_t *num_particles_plane, uint32_t *counts);
+/* HIP-event durations (ms) of the last shq_lens_planes: [0] particle staging and binning, [1] the particle planes' 2-D solves, [2] the
+ * correction (mesh upload, projection, solve, bilinear add), [3] all of it on the device, downloads included. */
+int shq_lens_phase_ms(shq_context *ctx, double ms[4]);
+
 #ifdef __cplusplus
 }
 #endif

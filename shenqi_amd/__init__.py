@@ -408,6 +408,50 @@ def heiii_reionization(ctx, pman, SphP, params, rnd_table, gas_tree=None, log_ca
     return res, log[:nlog.value].copy()
 
 
+def lens_count_active(ctx, pman, exclude_type2=False):
+    """plane_count_active_particles' local count (plane.cpp:72-83) on the device: not Swallowed, not Type 2 under exclude_type2"""
+    pv = pman.view()
+    out = C.c_int64()
+    capi.check(capi.hip.shq_lens_count_active(ctx.h, C.byref(pv), int(bool(exclude_type2)), C.byref(out)), "lens_count_active")
+    return out.value
+
+
+def lens_planes(ctx, pman, Resolution, Normals, CutPoints=None, Thickness=0.0, CurrentParticleOffset=(0.0, 0.0, 0.0), exclude_type2=False,
+                atime=1.0, comoving_distance=1.0, HubbleParam=0.7, omega_source=0.3, num_particles_tot=None, nu=None, counts=True):
+    """write_plane's compute (plane.cpp:565-588) for one rank on the device: every (cut, normal) potential plane in one call.
+    CutPoints None or empty: the default list (0.5 + i) Thickness; Thickness <= 0: BoxSize.  num_particles_tot None: this rank's
+    active count (one rank).  nu: None, or dict(Nmesh, x0, real [nx][Nmesh][Nmesh] float64, inv_fft_norm, mean_mass_cell), the rank's
+    x-slab of the PM neutrino correction mesh.  Returns (planes [ncuts][nnormals][R][R] float64, num_particles_plane [ncuts][nnormals]
+    int64, counts [ncuts][nnormals][R][R] uint32 or None)."""
+    normals = np.ascontiguousarray(Normals, dtype=np.int32)
+    cuts = np.ascontiguousarray([] if CutPoints is None else CutPoints, dtype=np.float64)
+    lp = capi.LensParams()
+    lp.Resolution, lp.ncuts, lp.nnormals, lp.exclude_type2 = int(Resolution), len(cuts), len(normals), int(bool(exclude_type2))
+    lp.CutPoints, lp.Normals = capi.ptr(cuts) if len(cuts) else None, capi.ptr(normals) if len(normals) else None
+    lp.Thickness, lp.BoxSize = float(Thickness), pman.BoxSize
+    lp.CurrentParticleOffset[:] = [float(x) for x in CurrentParticleOffset]
+    if num_particles_tot is None:
+        num_particles_tot = lens_count_active(ctx, pman, exclude_type2)
+    lc = capi.LensCosmo(float(atime), float(comoving_distance), float(HubbleParam), float(omega_source), int(num_particles_tot))
+    nm = None
+    if nu is not None:
+        real = np.ascontiguousarray(nu["real"], dtype=np.float64)
+        nm = capi.LensNuMesh(int(nu["Nmesh"]), int(nu["x0"]), real.shape[0] if real.ndim == 3 else 0, 0, float(nu["inv_fft_norm"]),
+                             float(nu["mean_mass_cell"]), real.ctypes.data_as(C.c_void_p))
+        if real.ndim != 3 or real.shape[1:] != (nm.Nmesh, nm.Nmesh):
+            raise ValueError("nu['real'] must be [nx][Nmesh][Nmesh]")
+    nc = C.c_int32()
+    capi.check(capi.hip.shq_lens_num_cuts(C.byref(lp), C.byref(nc)), "lens_planes")
+    R = max(int(Resolution), 0)
+    planes = np.zeros((nc.value, len(normals), R, R))
+    npl = np.zeros((nc.value, len(normals)), dtype=np.int64)
+    cnt = np.zeros((nc.value, len(normals), R, R), dtype=np.uint32) if counts else None
+    pv = pman.view()
+    capi.check(capi.hip.shq_lens_planes(ctx.h, C.byref(lp), C.byref(lc), C.byref(pv), C.byref(nm) if nm is not None else None,
+                                        capi.ptr(planes), capi.ptr(npl), capi.ptr(cnt)), "lens_planes")
+    return planes, npl, cnt
+
+
 def synth_positions(kind, n, seed=20240601, L=1.0):
     """SURVEY §8(d) synthetic inputs: kind 'grid' | 'uniform' | 'cluster'."""
     k = {"grid": 0, "uniform": 1, "cluster": 2}[kind]

@@ -687,6 +687,34 @@ hip.shq_heiii_reionization.argtypes = [_vp, C.POINTER(HeiiiParams), C.POINTER(Pa
 hip.shq_heiii_reionization.restype = C.c_int
 hip.shq_heiii_last_stats.argtypes = [_vp, C.POINTER(HeiiiStats)]
 hip.shq_heiii_last_stats.restype = C.c_int
+
+
+class LensParams(C.Structure):
+    """shq_lens_params: PlaneParams (plane.cpp:25-33) for one call, the box and the particle offset"""
+    _fields_ = [("Resolution", C.c_int32), ("ncuts", C.c_int32), ("nnormals", C.c_int32), ("exclude_type2", C.c_int32),
+                ("CutPoints", C.c_void_p), ("Normals", C.c_void_p), ("Thickness", C.c_double), ("BoxSize", C.c_double),
+                ("CurrentParticleOffset", C.c_double * 3)]
+
+
+class LensCosmo(C.Structure):
+    _fields_ = [("atime", C.c_double), ("comoving_distance", C.c_double), ("HubbleParam", C.c_double), ("omega_source", C.c_double),
+                ("num_particles_tot", C.c_int64)]
+
+
+class LensNuMesh(C.Structure):
+    """shq_lens_numesh: the rank's x-slab [x0, x0 + nx) of the PM neutrino correction mesh, dense [nx][Nmesh][Nmesh]"""
+    _fields_ = [("Nmesh", C.c_int32), ("x0", C.c_int32), ("nx", C.c_int32), ("pad_", C.c_int32), ("inv_fft_norm", C.c_double),
+                ("mean_mass_cell", C.c_double), ("real", C.c_void_p)]
+
+
+hip.shq_lens_count_active.argtypes = [_vp, C.POINTER(PartView), C.c_int, C.POINTER(C.c_int64)]
+hip.shq_lens_count_active.restype = C.c_int
+hip.shq_lens_num_cuts.argtypes = [C.POINTER(LensParams), C.POINTER(C.c_int32)]
+hip.shq_lens_num_cuts.restype = C.c_int
+hip.shq_lens_planes.argtypes = [_vp, C.POINTER(LensParams), C.POINTER(LensCosmo), C.POINTER(PartView), C.POINTER(LensNuMesh), _vp, _vp, _vp]
+hip.shq_lens_planes.restype = C.c_int
+hip.shq_lens_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 4)]
+hip.shq_lens_phase_ms.restype = C.c_int
 hip.shq_treepm_last_fused.argtypes = [_vp, C.POINTER(C.c_int)]
 hip.shq_treepm_set_fuse.argtypes = [_vp, C.c_int]
 hip.shq_pm_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 6)]

@@ -471,6 +471,8 @@ struct shq_context {
     double uvbg_ms[4] = {0, 0, 0, 0};     /* shq_uvbg_phase_ms */
     /* ---- helium reionisation (heiii.hip): a call allocates and frees its own device buffers; only its statistics stay behind */
     shq_heiii_stats heiii_stats = {};
+    /* ---- lensing potential planes (lens.hip): a call allocates and frees its own device buffers; only its times stay behind */
+    double lens_ms[4] = {0, 0, 0, 0};     /* shq_lens_phase_ms */
 };
 
 /* capi.hip: make the main stream wait for an outstanding asynchronous PM run */
