@@ -4,12 +4,14 @@ ARCH ?= gfx950
 CSRC := shenqi_amd/csrc
 LIBDIR := shenqi_amd/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -Iinclude
-HIPSRC := $(CSRC)/capi.hip $(CSRC)/grav_walk.hip $(CSRC)/grav_group.hip $(CSRC)/pm.hip $(CSRC)/sph.hip $(CSRC)/sph_capi.hip $(CSRC)/sph_resident.hip $(CSRC)/fft3d.hip $(CSRC)/tree_build.hip $(CSRC)/dynamics.hip $(CSRC)/timestep.hip $(CSRC)/fof.hip $(CSRC)/exchange.hip $(CSRC)/toptree.hip $(CSRC)/uvbg.hip $(CSRC)/heiii.hip $(CSRC)/lens.hip
+# longest compile first: make -j starts the jobs in this order, and the build is as long as its last job (fft3d.hip alone takes about as
+# long as a quarter of all the others together)
+HIPSRC := $(addprefix $(CSRC)/,$(addsuffix .hip,fft3d exchange fof tree_build sph_winds sph grav_walk heiii toptree dynamics sph_bh sph_ngbsums sph_capi capi uvbg grav_group lens timestep pm sph_resident))
 HIPOBJ := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/%.o,$(HIPSRC))
 
 all: $(LIBDIR)/libshenqi_hip.so host oracle
 
-$(LIBDIR)/%.o: $(CSRC)/%.hip $(CSRC)/common.hpp include/shenqi_hip.h
+$(LIBDIR)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.hpp) include/shenqi_hip.h
 	@mkdir -p $(LIBDIR)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 

@@ -1101,7 +1101,7 @@ extern "C" int shq_grav_short_download(shq_context *ctx, double (*accel)[3], dou
                     gs.lonely[0] / nw / 64., gs.lonely[1] / nw, gs.lonely[2] / nw / 64., gs.lonely[3] / nw);
         }
         float ms = 0;
-        if(stats->ntargets > 0 && hipEventElapsedTime(&ms, ctx->ev_begin[SHQ_NTIMERS - 1], ctx->ev_end[SHQ_NTIMERS - 1]) == hipSuccess)
+        if(stats->ntargets > 0 && hipEventElapsedTime(&ms, ctx->ev_begin[SHQ_T_WALK], ctx->ev_end[SHQ_T_WALK]) == hipSuccess)
             stats->kernel_ms = ms;
         else
             stats->kernel_ms = 0;
@@ -1469,14 +1469,14 @@ extern "C" int shq_pm_phase_ms(shq_context *ctx, double ms[6])
     SHQ_CHECK(ctx->have_pm_result, SHQ_ERR_STATE, "pm_phase_ms before pm_run");
     SHQ_HIP(hipSetDevice(ctx->device));
     SHQ_TRY(shq_join_pm(ctx));
-    SHQ_HIP(hipEventSynchronize(ctx->ev_begin[13]));
+    SHQ_HIP(hipEventSynchronize(ctx->ev_begin[SHQ_T_PM0 + 5]));
     for(int i = 0; i < 5; i++) {
         float f = 0;
-        SHQ_HIP(hipEventElapsedTime(&f, ctx->ev_begin[8 + i], ctx->ev_begin[9 + i]));
+        SHQ_HIP(hipEventElapsedTime(&f, ctx->ev_begin[SHQ_T_PM0 + i], ctx->ev_begin[SHQ_T_PM0 + 1 + i]));
         ms[i] = f;
     }
     float f = 0;
-    SHQ_HIP(hipEventElapsedTime(&f, ctx->ev_begin[8], ctx->ev_begin[13]));
+    SHQ_HIP(hipEventElapsedTime(&f, ctx->ev_begin[SHQ_T_PM0], ctx->ev_begin[SHQ_T_PM0 + 5]));
     ms[5] = f;
     return SHQ_OK;
 }

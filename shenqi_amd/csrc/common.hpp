@@ -168,7 +168,8 @@ __device__ __forceinline__ unsigned xcd_block(unsigned b, unsigned nb, unsigned 
     return super * 8u * K + (within & 7u) * K + (within >> 3);
 }
 
-#define SHQ_NTIMERS 20 /* 0-7 caller, 8-13 PM phases, 14 SPH, 16 tree build, last: walk */
+#define SHQ_NTIMERS 20 /* slots of ev_begin / ev_end: 0-7 are the caller's */
+enum { SHQ_T_PM0 = 8 /* PM phases: SHQ_T_PM0 .. SHQ_T_PM0 + 5 */, SHQ_T_SPH = 14, SHQ_T_TREE = 16, SHQ_T_WALK = SHQ_NTIMERS - 1 };
 
 /* scratch of the device tree build (tree_build.hip) */
 struct TreeBuildBufs {
@@ -372,10 +373,10 @@ struct shq_context {
     DevBuf<uint8_t> bh_u8;     /* minTimeBin[nbh], TimeBinDynFric[nbh], JumpToMinPot[nbh] */
     DevBuf<double> bh_vec;     /* DFAccel, DF_SurroundingVel, DragAccel, MinPotPos, MinPotVel: [5][nbh][3] */
     DevBuf<double4> velp, hydC, hydD, velp_leaf;
-    DevBuf<char> hydrec_leaf;  /* HydRec[] (sph.hip): 128-byte neighbour records for the hydro evaluation */
+    DevBuf<char> hydrec_leaf;  /* HydRec[] (sph_walk.hpp): 128-byte neighbour records for the hydro evaluation */
     DevBuf<double> hsml_leaf;
     DevBuf<int32_t> ngarb_leaf;
-    DevBuf<float4> posf_leaf; /* (x, y, z) rounded to f32 and the f32 pre-test bound of the particle's own Hsml: sph.hip, ngb_walk PRE32 */
+    DevBuf<float4> posf_leaf; /* (x, y, z) rounded to f32 and the f32 pre-test bound of the particle's own Hsml: sph_walk.hpp, ngb_walk PRE32 */
     DevBuf<int32_t> flag_leaf;
     DevBuf<double> s_numngb, s_dhsmldens, s_left, s_right, s_rot, s_gradrho, s_evp_in;
     DevBuf<int32_t> s_todo, s_queue2, s_queue3, s_blockcount;
@@ -573,12 +574,13 @@ int shq_sph_density_reduce(shq_context *ctx, const int32_t *d_place, const void 
 int shq_sph_density_secondary(shq_context *ctx, const shq_density_params *p, const double4 *d_qposm, const double *d_qhsml,
                               const double4 *d_qvelp, const uint8_t *d_qflags, const int4 *d_qseg, int64_t nq, double *d_out,
                               unsigned long long *d_nint);
+/* sph_ngbsums.hip (as are shq_bh_veldisp_device and shq_sph_stellar_density_device at the end) */
 int shq_sph_gradrho_mag(shq_context *ctx, double *d_out);
 int shq_bh_dynfric_device(shq_context *ctx, const shq_kick_factors *kf, double BoxSize, int kernel_type, int typemask, int method,
                           const double *d_potential, const int32_t *d_queue, int64_t nq, double *d_out);
 int shq_wind_veldisp_device(shq_context *ctx, const shq_kick_factors *kf, double BoxSize, double hubble_a2, const int32_t *d_queue, int64_t nq,
                             double *d_dmradius, double *d_vdisp, shq_sph_stats *stats);
-/* black-hole accretion / feedback walks (sph.hip) */
+/* black-hole accretion / feedback walks (sph_bh.hip) */
 struct BhRec {
     double Mass, Density, Mtrack, DFAccel[3], VDisp, KineticFdbkEnergy, Mdot, FeedbackWeightSum;
     int32_t CountProgs, KEflag;
@@ -609,7 +611,7 @@ struct BhWalkArgs {
     long long Ti_Current;
 };
 
-/* wind walks (sph.hip) */
+/* wind walks (sph_winds.hip) */
 struct WindWalkArgs {
     const unsigned long long *ids;
     const double *rnd;
@@ -628,7 +630,7 @@ int shq_winds_evolve_device(shq_context *ctx, const int32_t *d_list, int64_t n, 
 int shq_winds_subgrid_device(shq_context *ctx, const WindWalkArgs *w, const int32_t *d_list, int64_t n, const double *d_stellarmass, const double *d_vdisp,
                              unsigned long long *d_nkicked);
 int shq_wind_resolve_device(shq_context *ctx, const WindWalkArgs *w, long long nk, shq_wind_kick *d_sorted, unsigned long long *d_napplied, int *d_odd, bool apply);
-/* metal return (sph.hip) */
+/* metal return (sph_winds.hip) */
 #define SHQ_NMETALS 9
 struct MetalWalkArgs {
     unsigned long long *cursor;

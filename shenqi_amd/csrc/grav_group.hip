@@ -958,7 +958,7 @@ int shq_launch_grav_walk_group(shq_context *ctx, const shq_grav_params *p, const
 
     /* ---- batches of targets sized so that their lists fit the pool: chunks per target from the last batch (first call: a
      * cautious guess); a batch that does not fit is cut in half and listed again */
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_NTIMERS - 1], ctx->stream));
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_WALK], ctx->stream));
     int64_t done = 0;
     double cpt = ctx->walk_chunks_per_target > 0 ? ctx->walk_chunks_per_target : 8.0 / GS;
     while(done < ntargets) {
@@ -1020,6 +1020,6 @@ int shq_launch_grav_walk_group(shq_context *ctx, const shq_grav_params *p, const
         }
         done += nb;
     }
-    SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_NTIMERS - 1], ctx->stream));
+    SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_T_WALK], ctx->stream));
     return SHQ_OK;
 }

@@ -1522,7 +1522,7 @@ int shq_launch_grav_walk(shq_context *ctx, const shq_grav_params *p, const int32
         }
     }
     const dim3 grid((unsigned) launch_blocks), block(ring ? 512 : threads);
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_NTIMERS - 1], ctx->stream));
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_WALK], ctx->stream));
     if(live) /* what precedes the walk on this stream (the PM, the flags' reset) also precedes the pair kernel on the other */
         SHQ_HIP(hipEventRecord(ctx->ev_pair_fork, ctx->stream));
     if(update_potential) {
@@ -1578,7 +1578,7 @@ int shq_launch_grav_walk(shq_context *ctx, const shq_grav_params *p, const int32
         SHQ_HIP(hipMemcpyAsync(ctx->sp_host.ptr, ctx->sp_flags.ptr + SP_STICKY_ERROR, sizeof(int) * 8, hipMemcpyDeviceToHost, ctx->stream));
         ctx->sp_check_pending = true;
     }
-    SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_NTIMERS - 1], ctx->stream));
+    SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_T_WALK], ctx->stream));
     if(swap_meshes) {
         std::swap(ctx->mesh.ptr, ctx->mesh_alt.ptr);
         std::swap(ctx->mesh.cap, ctx->mesh_alt.cap);

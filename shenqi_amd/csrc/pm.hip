@@ -620,7 +620,7 @@ int pm_deposit(shq_context *ctx, const shq_pm_params *pm)
     const double scale = ldexp(1.0, ctx->pm_log2scale);
     const int threads = 256;
     const size_t dense = (size_t) N * N * N;
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[8], ctx->stream));
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0], ctx->stream));
     if(!(prezeroed && ctx->mesh_words == padded))
         pm_zero_kernel<<<dim3(2048), dim3(threads), 0, ctx->stream>>>((unsigned long long *) ctx->mesh.ptr, padded);
     if(n > 0)
@@ -656,7 +656,7 @@ int pm_readout(shq_context *ctx, const shq_pm_params *pm, bool readout)
             ctx->readout_oldacc_G > 0 ? ctx->treeacc.ptr : nullptr, ctx->readout_oldacc_G > 0 ? ctx->oldacc.ptr : nullptr, ctx->readout_oldacc_G);
     }
     SHQ_HIP(hipGetLastError());
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[13], ctx->stream));
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 5], ctx->stream));
     ctx->have_pm_result = true;
     return SHQ_OK;
 }
@@ -677,7 +677,7 @@ int pm_finish(shq_context *ctx, const shq_pm_params *pm, bool readout)
     const bool measure = ctx->pm_measure_power;
     if(measure)
         SHQ_TRY(pm_power_prepare(ctx, N));
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[11], ctx->stream));
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 3], ctx->stream));
     if(ctx->pm_spec_route == 0) {
         double *scratch = pm_scratch(ctx, N, zp, true);
         SHQ_CHECK(scratch, SHQ_ERR_NOMEM, "pm: no scratch mesh for the transposing pipeline");
@@ -708,7 +708,7 @@ int pm_finish(shq_context *ctx, const shq_pm_params *pm, bool readout)
             SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "hipfftExecZ2D failed: %d", (int) r);
         }
     }
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[12], ctx->stream));
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 4], ctx->stream));
     shq_pm_discard_spectrum(ctx); /* delta_nu changes every PM step: the table is never used twice */
     return pm_readout(ctx, pm, readout);
 }
@@ -732,37 +732,37 @@ int shq_pm_execute(shq_context *ctx, const shq_pm_params *pm, bool readout)
     if(ctx->pm_custom_fft && ctx->pm_measure_power) {
         /* P(k) is taken from the density spectrum, which the fused X pass never writes out: when it is
          * wanted the forward and inverse transforms run separately (6 passes + 2 sweeps instead of 5) */
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[9], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 1], ctx->stream));
         SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 0, true, 1.0 / scale, ctx->sinctab.ptr, asmth2, pot_factor));
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[10], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 2], ctx->stream));
         SHQ_TRY(pm_measure_power(ctx, N, zp / 2));
         const size_t tot = (size_t) N * N * Nc;
         pm_green_kernel<<<dim3((unsigned) ((tot + threads - 1) / threads)), dim3(threads), 0, ctx->stream>>>(
             (double2 *) ctx->mesh.ptr, N, Nc, zp / 2, ctx->sinctab.ptr, asmth2, pot_factor);
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[11], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 3], ctx->stream));
         SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 1, false, 1.0, ctx->sinctab.ptr, asmth2, pot_factor));
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[12], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 4], ctx->stream));
     } else if(ctx->pm_custom_fft) {
         /* five fused passes: Z fwd (+ int64 -> f64), Y fwd, X fwd + potential_transfer + X inv, Y inv, Z inv */
         /* the transposing pipeline (fft3d.hip) wants a second mesh as scratch: the one shq_treepm_step keeps anyway (between two steps
          * it holds the previous step's potential, which nothing reads any more once that step's walk has gone by on this stream) */
         double *scratch = pm_scratch(ctx, N, zp);
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[9], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 1], ctx->stream));
         if(scratch)
             SHQ_TRY(shq_fft3d_run_transposed(ctx, ctx->mesh.ptr, scratch, N, zp, true, 1.0 / scale, ctx->sinctab.ptr, asmth2, pot_factor));
         else
             SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 2, true, 1.0 / scale, ctx->sinctab.ptr, asmth2, pot_factor));
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[10], ctx->stream));
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[11], ctx->stream));
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[12], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 2], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 3], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 4], ctx->stream));
     } else {
         pm_convert_kernel<<<dim3(2048), dim3(threads), 0, ctx->stream>>>(ctx->mesh.ptr, padded, 1.0 / scale);
         SHQ_HIP(hipGetLastError());
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[9], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 1], ctx->stream));
         hipfftSetStream(ctx->plan_r2c, ctx->stream);
         hipfftResult r = hipfftExecD2Z(ctx->plan_r2c, (hipfftDoubleReal *) ctx->mesh.ptr, (hipfftDoubleComplex *) ctx->mesh.ptr);
         SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "hipfftExecD2Z failed: %d", (int) r);
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[10], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 2], ctx->stream));
         {
             const size_t tot = (size_t) N * N * Nc;
             if(ctx->pm_measure_power)
@@ -770,11 +770,11 @@ int shq_pm_execute(shq_context *ctx, const shq_pm_params *pm, bool readout)
             pm_green_kernel<<<dim3((unsigned) ((tot + threads - 1) / threads)), dim3(threads), 0, ctx->stream>>>(
                 (double2 *) ctx->mesh.ptr, N, Nc, zp / 2, ctx->sinctab.ptr, asmth2, pot_factor);
         }
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[11], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 3], ctx->stream));
         hipfftSetStream(ctx->plan_c2r, ctx->stream);
         r = hipfftExecZ2D(ctx->plan_c2r, (hipfftDoubleComplex *) ctx->mesh.ptr, (hipfftDoubleReal *) ctx->mesh.ptr);
         SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "hipfftExecZ2D failed: %d", (int) r);
-        SHQ_HIP(hipEventRecord(ctx->ev_begin[12], ctx->stream));
+        SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 4], ctx->stream));
     }
     return pm_readout(ctx, pm, readout);
 }
@@ -792,7 +792,7 @@ int shq_pm_execute_forward(shq_context *ctx, const shq_pm_params *pm)
     const double asmth2 = pow((2 * M_PI) * pm->Asmth / N, 2);
     const double pot_factor = -pm->G / (M_PI * pm->BoxSize);
     SHQ_TRY(pm_power_prepare(ctx, N));
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[9], ctx->stream));
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 1], ctx->stream));
     double *scratch = ctx->pm_custom_fft ? pm_scratch(ctx, N, zp) : nullptr;
     int route;
     if(scratch) {
@@ -815,7 +815,7 @@ int shq_pm_execute_forward(shq_context *ctx, const shq_pm_params *pm)
         SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "hipfftExecD2Z failed: %d", (int) r);
         SHQ_TRY(pm_power_sweep(ctx, N, zp / 2));
     }
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[10], ctx->stream));
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 2], ctx->stream));
     ctx->pm_spec_pending = true;
     ctx->pm_spec_params = *pm;
     ctx->pm_spec_route = route;

@@ -717,7 +717,7 @@ extern "C" int shq_hier_gravity_levels(shq_context *ctx, const shq_timestep_para
         SHQ_TRY(shq_kick_short(ctx, tab, SHQ_SUBLIST_RESIDENT, 0, 1));
         if(levels) {
             float wms = 0;
-            (void) hipEventElapsedTime(&wms, ctx->ev_begin[SHQ_NTIMERS - 1], ctx->ev_end[SHQ_NTIMERS - 1]);
+            (void) hipEventElapsedTime(&wms, ctx->ev_begin[SHQ_T_WALK], ctx->ev_end[SHQ_T_WALK]);
             levels[nl].timebin = ti;
             levels[nl].walk_mode = ctx->last_walk_mode;
             levels[nl].nparticles = nsub;

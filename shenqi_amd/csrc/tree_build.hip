@@ -762,7 +762,7 @@ static int tree_build_impl(shq_context *ctx, double BoxSize, int mask, const int
     const bool keep_targets = ctx->have_tree_targets && !active && mask == ctx->tree_targets_mask && np == ctx->tree_targets_np &&
                               ctx->tree_targets_age + 1 < ctx->tree_targets_refresh;
     ctx->have_tree_targets = false;
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[16], st));
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_TREE], st));
 
     /* 1. keys */
     const size_t pcap = (size_t) (ncand > 0 ? ncand : 1);
@@ -902,7 +902,7 @@ static int tree_build_impl(shq_context *ctx, double BoxSize, int mask, const int
     SHQ_TRY(ctx->leaf_pidx.reserve((size_t) npad));
     tb_leafcopy_kernel<<<dim3(nblk(npad)), dim3(256), 0, st>>>(n, npad, idx, ctx->posm.ptr, ctx->posm_leaf.ptr, ctx->leaf_pidx.ptr);
     SHQ_HIP(hipGetLastError());
-    SHQ_HIP(hipEventRecord(ctx->ev_end[16], st));
+    SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_T_TREE], st));
     SHQ_HIP(hipStreamSynchronize(st));
 
     ctx->node_order.clear();    /* empty = identity: a downloaded tree is numbered in pool order (filling 7 M entries on the host cost a
@@ -933,7 +933,7 @@ static int tree_build_impl(shq_context *ctx, double BoxSize, int mask, const int
         stats->numnodes = nn;
         stats->maxdepth = maxdepth;
         float ms = 0;
-        (void) hipEventElapsedTime(&ms, ctx->ev_begin[16], ctx->ev_end[16]);
+        (void) hipEventElapsedTime(&ms, ctx->ev_begin[SHQ_T_TREE], ctx->ev_end[SHQ_T_TREE]);
         stats->build_ms = ms;
     }
     return SHQ_OK;

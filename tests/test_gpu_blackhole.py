@@ -1,4 +1,4 @@
-"""GPU parity tests of the black-hole accretion and feedback walks (shq_bh_accretion / shq_bh_feedback, csrc/sph.hip) against the
+"""GPU parity tests of the black-hole accretion and feedback walks (shq_bh_accretion / shq_bh_feedback, csrc/sph_bh.hip) against the
 restatement of libgadget/blackhole.cpp:373-1003 in oracle/blackhole.py (brute-force neighbours).  The reference's tests hold no
 fixture for this module (parity unpinned): besides the restatement the tests check what the walks conserve."""
 import ctypes as C

@@ -1,4 +1,4 @@
-"""GPU parity tests of metal_return's treewalk (shq_metal_return, csrc/sph.hip) against the restatement of
+"""GPU parity tests of metal_return's treewalk (shq_metal_return, csrc/sph_winds.hip) against the restatement of
 libgadget/metal_return.cpp:573-667 in oracle/metal_return.py: stars in queue order, the reference's float / double arithmetic, so the
 comparison is exact up to the last bit of the kernel weight.  No reference fixture exists for the walk (parity unpinned); mass and metal conservation are checked beside it."""
 import ctypes as C

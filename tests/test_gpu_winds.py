@@ -1,4 +1,4 @@
-"""GPU parity tests of the wind walks for new stars (shq_winds_and_feedback, csrc/sph.hip) against the restatement of
+"""GPU parity tests of the wind walks for new stars (shq_winds_and_feedback, csrc/sph_winds.hip) against the restatement of
 libgadget/winds.cpp:227-565 in oracle/winds.py.  No reference fixture exists (parity unpinned); the outcome is order-independent
 by construction (nearest star, then smaller ID), so the comparison is exact."""
 import ctypes as C

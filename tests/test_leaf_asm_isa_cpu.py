@@ -1,6 +1,7 @@
-"""The SPH walk-only kernels load a waiting leaf's records with inline-asm scalar loads the compiler cannot see (csrc/sph.hip, LEAF_ASM).
-That is only sound while nothing copies or spills the destination registers between the loads and the wait in process_pending; this test
-compiles sph.hip to ISA for gfx950 (hipcc cross-compiles on the CPU) and lets tools/check_leaf_asm.py look for exactly that."""
+"""The SPH walk-only kernels load a waiting leaf's records with inline-asm scalar loads the compiler cannot see (csrc/sph_walk.hpp, ngb_walk,
+SPH_LEAF_ASM).  That is only sound while nothing copies or spills the destination registers between the loads and the wait in process_pending;
+this test compiles every file that includes the walk (sph.hip, sph_ngbsums.hip, sph_bh.hip, sph_winds.hip) to ISA for gfx950 (hipcc
+cross-compiles on the CPU) and lets tools/check_leaf_asm.py look for exactly that."""
 import os
 import shutil
 import subprocess

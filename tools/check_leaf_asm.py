@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
-"""tools/check_leaf_asm.py [sph.s] — the SPH walk-only kernels fetch a waiting leaf's records with inline-asm scalar loads that the
-compiler knows nothing about (csrc/sph.hip, LEAF_ASM): between those loads and the `s_waitcnt lgkmcnt(0)` of process_pending nothing may
-copy or spill the destination registers.  This reads the ISA (`hipcc -S --cuda-device-only` of sph.hip, made here when no file is given)
-and fails when, in a kernel that holds such a load block,
+"""tools/check_leaf_asm.py [listing.s] — the SPH walk-only kernels fetch a waiting leaf's records with inline-asm scalar loads that the
+compiler knows nothing about (csrc/sph_walk.hpp, ngb_walk, SPH_LEAF_ASM): between those loads and the `s_waitcnt lgkmcnt(0)` of process_pending
+nothing may copy or spill the destination registers.  This reads the ISA (`hipcc -S --cuda-device-only` of every .hip that includes
+sph_walk.hpp: sph.hip, sph_ngbsums.hip, sph_bh.hip, sph_winds.hip; made here when no file is given) and fails when, in a kernel that holds
+such a load block,
   * a destination register of the block is spilled to a vector lane (`v_writelane_b32 …, sN`) anywhere inside the kernel's loops, or
   * the instructions right behind the block (up to the branch that ends it) read one of its destination registers.
 Runs on the CPU (hipcc cross-compiles); tests/test_leaf_asm_isa_cpu.py calls it."""
@@ -16,11 +17,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def make_isa():
-    out = os.path.join(tempfile.mkdtemp(prefix="leafasm_"), "sph.s")
+    """One listing of every .hip that includes sph_walk.hpp (each instantiates the walk for its own kernels), compiled side by side."""
+    csrc = os.path.join(ROOT, "shenqi_amd", "csrc")
+    srcs = sorted(f for f in os.listdir(csrc) if f.endswith(".hip") and '#include "sph_walk.hpp"' in open(os.path.join(csrc, f)).read())
+    tmp = tempfile.mkdtemp(prefix="leafasm_")
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", "-o", out,
-           os.path.join(ROOT, "shenqi_amd", "csrc", "sph.hip")]
-    subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    jobs = []
+    for f in srcs:
+        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", "-o",
+               os.path.join(tmp, f[:-4] + ".s"), os.path.join(csrc, f)]
+        jobs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)))
+    for cmd, job in jobs:
+        if job.wait() != 0:
+            raise subprocess.CalledProcessError(job.returncode, cmd)
+    out = os.path.join(tmp, "sph_all.s")
+    with open(out, "w") as o:
+        for f in srcs:
+            o.write(open(os.path.join(tmp, f[:-4] + ".s")).read())
     return out
 
 
