@@ -1501,6 +1501,63 @@ int shq_lens_planes(shq_context *ctx, const shq_lens_params *params, const shq_l
  * correction (mesh upload, projection, solve, bilinear add), [3] all of it on the device, downloads included. */
 int shq_lens_phase_ms(shq_context *ctx, double ms[4]);
 
+/* ---- Zel'dovich displacements (displacement_fields, libgenic/zeldovich.cpp:150-264; gaussian_fill / pmic_fill_gaussian_gadget,
+ * zeldovich.cpp:362-383 and libgenic/pmesh.h:64-178; the transfers of zeldovich.cpp:277-334) ----  one rank.
+ * The Gaussian field of (Nmesh, Seed, UnitaryAmplitude, InvertPhase) is filled on the device and stays resident in the context: the
+ * reference fills the same field once per species (genic/main.cpp).  It is discarded by a fill or a displacement call with another key,
+ * by shq_zeldovich_drop_field and by shq_shutdown, and by nothing else. */
+typedef struct shq_zeldovich_params {
+    int32_t Nmesh;               /* even, 4 .. 2048 */
+    int32_t Seed;                /* GenicConfig.Seed */
+    int32_t UnitaryAmplitude, InvertPhase;
+    int32_t ScaleDepVelocity;    /* PowerP.ScaleDepVelocity: VelX/Y/Z from dlogGrowth; otherwise Vel = Disp */
+    int32_t pad_;
+    double BoxSize;
+    double vel_prefac;           /* as zeldovich.cpp:195-208 forms it from hubble_function, F_Omega and UsePeculiarVelocity */
+} shq_zeldovich_params;
+/* Host only: the seed tables [0][0] and [1][1] of pmesh.h:74-90 on one rank (mt19937(Seed), one 32-bit draw per SETSEED,
+ * seed = (unsigned)(0x7fffffff * draw / 2^32), the reference's write order), Nmesh^2 entries each, index i * Nmesh + j. */
+int shq_zeldovich_seed_table(int Nmesh, int Seed, uint32_t *table00, uint32_t *table11);
+/* Host only: the factors of density_transfer and disp_transfer by integer k2 (3 (Nmesh/2)^2 + 1 entries, entry 0 is 0) from the
+ * caller's delta[k2] = DeltaSpec(kmag, ptype) and growth[k2] = dlogGrowth(kmag, ptype), kmag = sqrt(k2) 2 pi / BoxSize:
+ *   dens_fac = exp(-k2 / Nmesh^2) delta / sqrt(BoxSize^3)     (SHQ_TF_RADIAL, zero_mode 0 for shq_pm_apply)
+ *   disp_fac = 1 / (2 pi) / sqrt(BoxSize) / k2 * delta         (SHQ_TF_GRADIENT)
+ *   vel_fac  = the same with growth instead of delta            (SHQ_TF_GRADIENT; NULL skips it, as does growth == NULL)
+ * glibc's exp and sqrt.  shq_zeldovich_displacements forms its gradient factor per mode in the reference's order,
+ * 1 / (2 pi) / sqrt(BoxSize) * kaxis / k2 * delta, which differs from disp_fac * kaxis in the last bit. */
+int shq_zeldovich_factor_tables(int Nmesh, double BoxSize, const double *delta, const double *growth, double *dens_fac, double *disp_fac,
+                                double *vel_fac);
+/* Fill the resident field now (a displacement call does it when it finds none with its key). */
+int shq_zeldovich_fill(shq_context *ctx, int Nmesh, int Seed, int UnitaryAmplitude, int InvertPhase);
+/* Debug: the resident field to the host in the reference's Fourier layout [y][z'][x] (as shq_fft_r2c returns a spectrum and shq_pm_apply
+ * takes one), Nmesh^2 (Nmesh/2 + 1) complex.  SHQ_ERR_STATE without a resident field. */
+int shq_zeldovich_download_field(shq_context *ctx, int Nmesh, double *complx);
+/* Free the resident field. */
+int shq_zeldovich_drop_field(shq_context *ctx);
+/* Debug: columns per launch of the fill (rounded up to 64; 0 restores the default).  The field does not depend on it. */
+int shq_zeldovich_set_fill_chunk(shq_context *ctx, int64_t ncolumns);
+/* displacement_fields in one call:
+ *   delta, growth : host tables by k2 as above; growth may be NULL without ScaleDepVelocity
+ *   pos           : host [n][3], the undisplaced positions, each in [0, BoxSize)
+ *   pos_out       : out [n][3], Pos + Disp after periodic_wrap (may be pos itself)
+ *   vel           : out [n][3];  density : out [n];  disp : out [n][3] or NULL
+ *   maxdisp       : the largest signed Disp component, from 0;  maxvel : the largest |Vel|^2 (the reference prints its root)
+ * SHQ_ERR_INVALID before anything is written for an odd Nmesh or one outside 4 .. 2048, a BoxSize that is not finite and > 0, a position
+ * outside [0, BoxSize) (the reference ends the run: "particle out of cell"), a non-finite table entry, or ScaleDepVelocity with
+ * growth == NULL.  The call owns its work mesh and particle buffers: the resident particle set and tree, the PM mesh and its result, a
+ * pending spectrum and the deposit type mask survive.  A prestarted PM is joined first, because the transforms share the context's
+ * twiddle table with it.  Of the context only the resident field and that table change.  Synchronous. */
+int shq_zeldovich_displacements(shq_context *ctx, const shq_zeldovich_params *params, const double *delta, const double *growth, int64_t n,
+                                const double *pos, double *pos_out, double *vel, double *density, double *disp, double *maxdisp,
+                                double *maxvel);
+/* HIP-event durations (ms) of the last shq_zeldovich_displacements: [0] the fill (exactly 0 when the resident field was reused), [1] the
+ * uploads, transfers, transforms and readouts, [2] the particle loop, [3] all of it on the device, downloads included. */
+int shq_zeldovich_phase_ms(shq_context *ctx, double ms[4]);
+/* Test entry for the sampler: n generators, each seeded with seeds[t] (init_genrand) or, with states != NULL, started from the 624 words
+ * states[t] as they are before their first twist.  raw: out [n][m], the first m 32-bit outputs.  pairs: out [n][m/2][2], the first m/2
+ * SAMPLEs (pmesh.h:55-62) of the same start as (phase, ampl before the log), the ampl == 0 redraw included.  m even, n <= 65536. */
+int shq_zeldovich_column_draws(shq_context *ctx, int n, const uint32_t *seeds, const uint32_t *states, int m, uint32_t *raw, double *pairs);
+
 #ifdef __cplusplus
 }
 #endif

@@ -452,6 +452,93 @@ def lens_planes(ctx, pman, Resolution, Normals, CutPoints=None, Thickness=0.0, C
     return planes, npl, cnt
 
 
+class IDGenerator:
+    """idgen_init on one rank (libgenic/zeldovich.cpp:46-65): the whole Ngrid^3 lattice"""
+
+    def __init__(self, Ngrid, BoxSize):
+        self.Ngrid, self.BoxSize = int(Ngrid), float(BoxSize)
+        self.offset, self.size = (0, 0, 0), (self.Ngrid,) * 3
+        self.NumPart = self.Ngrid**3
+
+
+def idgen_create_id_from_index(idgen, index):
+    """zeldovich.cpp:67-75, for an index or an array of them"""
+    index = np.asarray(index, dtype=np.int64)
+    i = index // (idgen.size[2] * idgen.size[1]) + idgen.offset[0]
+    j = (index % (idgen.size[1] * idgen.size[2])) // idgen.size[2] + idgen.offset[1]
+    k = (index % idgen.size[2]) + idgen.offset[2]
+    return (i.astype(np.uint64) * np.uint64(idgen.Ngrid) * np.uint64(idgen.Ngrid) + j.astype(np.uint64) * np.uint64(idgen.Ngrid)
+            + k.astype(np.uint64) + np.uint64(1))
+
+
+def idgen_create_pos_from_index(idgen, index):
+    """zeldovich.cpp:77-87: [..., 3] positions x * BoxSize / Ngrid"""
+    index = np.asarray(index, dtype=np.int64)
+    x = index // (idgen.size[2] * idgen.size[1]) + idgen.offset[0]
+    y = (index % (idgen.size[1] * idgen.size[2])) // idgen.size[2] + idgen.offset[1]
+    z = (index % idgen.size[2]) + idgen.offset[2]
+    return np.stack([x * idgen.BoxSize / idgen.Ngrid, y * idgen.BoxSize / idgen.Ngrid, z * idgen.BoxSize / idgen.Ngrid], axis=-1)
+
+
+def setup_grid(idgen, shift, mass):
+    """zeldovich.cpp:89-104: the lattice positions plus shift, and the masses"""
+    pos = idgen_create_pos_from_index(idgen, np.arange(idgen.NumPart)) + float(shift)
+    return np.ascontiguousarray(pos), np.full(idgen.NumPart, float(mass))
+
+
+def tabulate_by_k2(fn, Nmesh, BoxSize):
+    """fn(kmag) by integer k2 for shq_pm_apply / displacement_fields: kmag = sqrt(k2) * 2 * M_PI / BoxSize as the zeldovich transfers
+    form it, 3 (Nmesh/2)^2 + 1 entries; entry 0 (never read) is 0.  fn is called once per k2 with a float."""
+    n = 3 * (int(Nmesh) // 2) ** 2 + 1
+    t = np.zeros(n)
+    for k2 in range(1, n):
+        t[k2] = fn(float(np.sqrt(np.float64(k2)) * 2 * np.pi / BoxSize))
+    return t
+
+
+def zeldovich_seed_table(Nmesh, Seed):
+    """the seed tables [0][0] and [1][1] of pmesh.h:74-90 (host only, no device needed): two [Nmesh][Nmesh] uint32 arrays"""
+    t00 = np.zeros((Nmesh, Nmesh), dtype=np.uint32)
+    t11 = np.zeros((Nmesh, Nmesh), dtype=np.uint32)
+    capi.check(capi.hip.shq_zeldovich_seed_table(int(Nmesh), int(Seed), capi.ptr(t00), capi.ptr(t11)), "zeldovich_seed_table")
+    return t00, t11
+
+
+def zeldovich_field(ctx, Nmesh, Seed, UnitaryAmplitude=0, InvertPhase=0):
+    """fill (or reuse) the resident Gaussian field and download it in petapm's Fourier layout: complex [y][z'][x]"""
+    capi.check(capi.hip.shq_zeldovich_fill(ctx.h, int(Nmesh), int(Seed), int(UnitaryAmplitude), int(InvertPhase)), "zeldovich_fill")
+    spec = np.zeros((Nmesh, Nmesh // 2 + 1, Nmesh), dtype=np.complex128)
+    capi.check(capi.hip.shq_zeldovich_download_field(ctx.h, int(Nmesh), capi.ptr(spec)), "zeldovich_download_field")
+    return spec
+
+
+def displacement_fields(ctx, pos, Nmesh, BoxSize, Seed, DeltaSpec, dlogGrowth=None, vel_prefac=1.0, ScaleDepVelocity=False,
+                        UnitaryAmplitude=False, InvertPhase=False, want_disp=True):
+    """displacement_fields (libgenic/zeldovich.cpp:150-264) for one rank on the device.  pos: [n][3] undisplaced positions in
+    [0, BoxSize).  DeltaSpec / dlogGrowth: tables by k2 (tabulate_by_k2) or callables of kmag.  Returns dict(Pos, Vel, Density, Disp,
+    maxdisp, maxvel, phase_ms); the Gaussian field stays resident in ctx for the next species."""
+    pos = np.ascontiguousarray(pos, dtype=np.float64)
+    n = len(pos)
+    delta = tabulate_by_k2(DeltaSpec, Nmesh, BoxSize) if callable(DeltaSpec) else np.ascontiguousarray(DeltaSpec, dtype=np.float64)
+    growth = None
+    if dlogGrowth is not None:
+        growth = tabulate_by_k2(dlogGrowth, Nmesh, BoxSize) if callable(dlogGrowth) else np.ascontiguousarray(dlogGrowth, dtype=np.float64)
+    nk2 = 3 * (int(Nmesh) // 2) ** 2 + 1
+    if len(delta) != nk2 or (growth is not None and len(growth) != nk2):
+        raise ValueError(f"the tables by k2 need {nk2} entries")
+    zp = capi.ZeldovichParams(int(Nmesh), int(Seed), int(bool(UnitaryAmplitude)), int(bool(InvertPhase)), int(bool(ScaleDepVelocity)), 0,
+                              float(BoxSize), float(vel_prefac))
+    out = dict(Pos=np.zeros((n, 3)), Vel=np.zeros((n, 3)), Density=np.zeros(n), Disp=np.zeros((n, 3)) if want_disp else None)
+    maxdisp, maxvel = C.c_double(), C.c_double()
+    capi.check(capi.hip.shq_zeldovich_displacements(ctx.h, C.byref(zp), capi.ptr(delta), capi.ptr(growth), n, capi.ptr(pos), capi.ptr(out["Pos"]),
+                                                    capi.ptr(out["Vel"]), capi.ptr(out["Density"]), capi.ptr(out["Disp"]), C.byref(maxdisp),
+                                                    C.byref(maxvel)), "displacement_fields")
+    ms = (C.c_double * 4)()
+    capi.check(capi.hip.shq_zeldovich_phase_ms(ctx.h, C.byref(ms)), "zeldovich_phase_ms")
+    out.update(maxdisp=maxdisp.value, maxvel=maxvel.value, phase_ms=list(ms))
+    return out
+
+
 def synth_positions(kind, n, seed=20240601, L=1.0):
     """SURVEY §8(d) synthetic inputs: kind 'grid' | 'uniform' | 'cluster'."""
     k = {"grid": 0, "uniform": 1, "cluster": 2}[kind]

@@ -715,6 +715,33 @@ hip.shq_lens_planes.argtypes = [_vp, C.POINTER(LensParams), C.POINTER(LensCosmo)
 hip.shq_lens_planes.restype = C.c_int
 hip.shq_lens_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 4)]
 hip.shq_lens_phase_ms.restype = C.c_int
+
+
+class ZeldovichParams(C.Structure):
+    """shq_zeldovich_params: what displacement_fields reads of GenicConfig, and the caller's vel_prefac"""
+    _fields_ = [("Nmesh", C.c_int32), ("Seed", C.c_int32), ("UnitaryAmplitude", C.c_int32), ("InvertPhase", C.c_int32),
+                ("ScaleDepVelocity", C.c_int32), ("pad_", C.c_int32), ("BoxSize", C.c_double), ("vel_prefac", C.c_double)]
+
+
+hip.shq_zeldovich_seed_table.argtypes = [C.c_int, C.c_int, _vp, _vp]
+hip.shq_zeldovich_seed_table.restype = C.c_int
+hip.shq_zeldovich_factor_tables.argtypes = [C.c_int, C.c_double, _vp, _vp, _vp, _vp, _vp]
+hip.shq_zeldovich_factor_tables.restype = C.c_int
+hip.shq_zeldovich_fill.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int]
+hip.shq_zeldovich_fill.restype = C.c_int
+hip.shq_zeldovich_download_field.argtypes = [_vp, C.c_int, _vp]
+hip.shq_zeldovich_download_field.restype = C.c_int
+hip.shq_zeldovich_drop_field.argtypes = [_vp]
+hip.shq_zeldovich_drop_field.restype = C.c_int
+hip.shq_zeldovich_set_fill_chunk.argtypes = [_vp, C.c_int64]
+hip.shq_zeldovich_set_fill_chunk.restype = C.c_int
+hip.shq_zeldovich_displacements.argtypes = [_vp, C.POINTER(ZeldovichParams), _vp, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp,
+                                            C.POINTER(C.c_double), C.POINTER(C.c_double)]
+hip.shq_zeldovich_displacements.restype = C.c_int
+hip.shq_zeldovich_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 4)]
+hip.shq_zeldovich_phase_ms.restype = C.c_int
+hip.shq_zeldovich_column_draws.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
+hip.shq_zeldovich_column_draws.restype = C.c_int
 hip.shq_treepm_last_fused.argtypes = [_vp, C.POINTER(C.c_int)]
 hip.shq_treepm_set_fuse.argtypes = [_vp, C.c_int]
 hip.shq_pm_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 6)]

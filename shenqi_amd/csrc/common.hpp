@@ -474,6 +474,12 @@ struct shq_context {
     shq_heiii_stats heiii_stats = {};
     /* ---- lensing potential planes (lens.hip): a call allocates and frees its own device buffers; only its times stay behind */
     double lens_ms[4] = {0, 0, 0, 0};     /* shq_lens_phase_ms */
+    /* ---- Zel'dovich displacements (zeldovich.hip): a call allocates and frees its work buffers; the Gaussian field stays resident */
+    DevBuf<double> zel_spec;              /* the filled half spectrum, dense complex [x][y][Nmesh/2 + 1] */
+    bool zel_have = false;
+    int zel_n = 0, zel_seed = 0, zel_unitary = 0, zel_invert = 0; /* its key */
+    int64_t zel_chunk = 0;                /* shq_zeldovich_set_fill_chunk: columns per fill launch (0: the default) */
+    double zel_ms[4] = {0, 0, 0, 0};      /* shq_zeldovich_phase_ms */
 };
 
 /* capi.hip: make the main stream wait for an outstanding asynchronous PM run */
