@@ -1558,6 +1558,57 @@ int shq_zeldovich_phase_ms(shq_context *ctx, double ms[4]);
  * SAMPLEs (pmesh.h:55-62) of the same start as (phase, ampl before the log), the ampl == 0 redraw included.  m even, n <= 65536. */
 int shq_zeldovich_column_draws(shq_context *ctx, int n, const uint32_t *seeds, const uint32_t *states, int m, uint32_t *raw, double *pairs);
 
+/* ---- Glass making (glass_evolve, libgenic/glass.cpp:76-360, with petapm_force's deposit and readout, petapm.cpp:1132-1183, and
+ * powerspectrum_add_mode, gravpm.cpp:323-376) ----  one rank.  The reversed-gravity PM relaxation loop, resident on the device from
+ * the first deposit to the last kick.  Storage types and rounding points are ic_part_data's (allvars.h:8-16): double Pos, float Vel,
+ * float Disp, float Mass; the readout rounds the running Disp to float after each of the eight CIC connections. */
+typedef struct shq_glass_params {
+    int32_t Nmesh;               /* even, 4 .. 2048 */
+    int32_t nsteps;              /* >= 0; setup_glass uses 14.  nsteps steps are nsteps + 1 forces */
+    double BoxSize;
+} shq_glass_params;
+typedef struct shq_glass_step {  /* one per step: what the reference prints and what it hands to powerspectrum_save */
+    double t_f, t_v, t_x;        /* as glass_evolve advances them (the reference prints them divided by 2 pi) */
+    double force_std, vel_std;   /* glass_stats: sqrt(sum Disp^2 / n), sqrt(sum Vel^2 / n) over all three components */
+} shq_glass_step;
+/* glass_evolve:
+ *   pos   : in/out host double [n][3], any finite value.  Positions are never wrapped, on the way in or out: the cell is
+ *           floor(Pos / CellSize) taken modulo Nmesh, the residual comes from the unwrapped quotient (the reference's region is built from
+ *           the particles' min / max and folded into the mesh periodically)
+ *   vel   : in/out host float [n][3];  disp : out host float [n][3], the last force;  mass : in host float [n]
+ *   steps : out [nsteps], or NULL
+ *   kk, power, nmodes, norm : out [nsteps][Nmesh] (norm: [nsteps]), the raw sums of step s's force before powerspectrum_sum, or all
+ *           four NULL.  Every mode is added TWICE, once with the CIC deconvolution weight (measure_power_spectrum) and once with
+ *           weight 1 (potential_transfer, glass.cpp:304), into the same bins: that is what the reference saves, not a choice made here.
+ *           shq_glass_finish_power turns one step's sums into the saved columns.
+ * The force: fixed-point CIC deposit of double(mass), unscaled r2c, every mode but the zero mode times pot_factor * (1.0 / k2) with
+ * pot_factor = pow(2 pi / BoxSize, -2) / totmass (PLUS: inverted gravity; no smoothing, no deconvolution), per axis times
+ * i * (-diff_kernel(k 2 pi / Nmesh) * (Nmesh / BoxSize)), unscaled c2r, CIC gather into float Disp.  totmass is the double sum of the
+ * float masses in particle order, as the reference forms it.
+ * The mesh does not depend on particle order or launch shape, so the call is deterministic, and evolve(a + b) equals evolve(a) followed by
+ * evolve(b) bit for bit in pos, vel and disp.  A permuted particle order gives the permuted result whenever totmass is the same double
+ * (always for equal masses).  The statistics and spectrum sums are accumulated in any order; they do not feed back.
+ * SHQ_ERR_INVALID before anything is written for an odd Nmesh or one outside 4 .. 2048, nsteps < 0, a BoxSize that is not finite and > 0,
+ * a non-finite position, velocity or mass, a position beyond 2^30 cells from the origin, a total mass that is not > 0, n >= 2^32 (also
+ * n < 1), or some but not all of the four spectrum pointers.  Positions outside [0, BoxSize) are valid.
+ * The call owns its two meshes and its particle buffers: the resident particle set and tree, the PM mesh and its result, a pending
+ * spectrum, the resident Zel'dovich field, the deposit type mask and scale and shq_pm_measure_power's setting survive.  A prestarted PM is
+ * joined first, because the transforms share the context's twiddle table with it.  One upload, one download.  Synchronous. */
+int shq_glass_evolve(shq_context *ctx, const shq_glass_params *params, int64_t n, double *pos, float *vel, float *disp, const float *mass,
+                     shq_glass_step *steps, double *kk, double *power, int64_t *nmodes, double *norm);
+/* HIP-event durations (ms) of the last shq_glass_evolve: [0] the upload, [1] all forces (deposit to the third gather), [2] all particle
+ * loops, [3] all of it on the device, the download included. */
+int shq_glass_phase_ms(shq_context *ctx, double ms[4]);
+/* Host only: setup_glass's positions (glass.cpp:49-66) for the whole Ngrid^3 lattice on one rank (ThisTask = 0): the lattice position
+ * of index i (x = i / Ngrid^2, y = (i mod Ngrid^2) / Ngrid, z = i mod Ngrid, times BoxSize / Ngrid) plus, per axis in k order,
+ * shift + BoxSize / Ngrid * 3 * (u - 0.5), u from one serial mt19937(seed) through uniform_real_distribution<double>(0, 1) read as ONE
+ * 32-bit output per draw (raw / 2^32, redrawn if the result is not below 1).  That reading of boost's distribution on a 32-bit engine is
+ * the one the Zel'dovich sampler uses; it has not been checked against a boost build.  pos: out [Ngrid^3][3]. */
+int shq_glass_setup_positions(int Ngrid, double BoxSize, double shift, int seed, double *pos);
+/* Host only: powerspectrum_sum's tail (powerspectrum.cpp:71-87) on one step's raw sums, in place: bins without modes removed, the others
+ * Power / Nmodes / Norm * BoxSize_in_MPC^3 and kk / Nmodes * 2 pi / BoxSize_in_MPC, moved to the front.  *nonzero: how many remain. */
+int shq_glass_finish_power(int size, double BoxSize_in_MPC, double *kk, double *power, int64_t *nmodes, double norm, int *nonzero);
+
 #ifdef __cplusplus
 }
 #endif

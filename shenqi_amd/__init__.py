@@ -539,6 +539,59 @@ def displacement_fields(ctx, pos, Nmesh, BoxSize, Seed, DeltaSpec, dlogGrowth=No
     return out
 
 
+def glass_setup_positions(Ngrid, BoxSize, shift=0.0, seed=0):
+    """setup_glass's perturbed lattice (libgenic/glass.cpp:49-66) for the whole Ngrid^3 lattice on one rank (host only): [Ngrid^3][3]"""
+    pos = np.zeros((int(Ngrid) ** 3, 3))
+    capi.check(capi.hip.shq_glass_setup_positions(int(Ngrid), float(BoxSize), float(shift), int(seed), capi.ptr(pos)), "glass_setup_positions")
+    return pos
+
+
+def glass_finish_power(BoxSize_in_MPC, kk, power, nmodes, norm):
+    """powerspectrum_sum's tail (powerspectrum.cpp:71-87) on one step's raw sums: (kk, power, nmodes) of the non-empty bins"""
+    kk, power = np.array(kk, dtype=np.float64), np.array(power, dtype=np.float64)
+    nmodes = np.array(nmodes, dtype=np.int64)
+    nz = C.c_int(0)
+    capi.check(capi.hip.shq_glass_finish_power(len(kk), float(BoxSize_in_MPC), capi.ptr(kk), capi.ptr(power), capi.ptr(nmodes), float(norm),
+                                               C.byref(nz)), "glass_finish_power")
+    return kk[:nz.value], power[:nz.value], nmodes[:nz.value]
+
+
+def glass_evolve(ctx, Nmesh, BoxSize, pos, vel, mass, nsteps=14, spectra=False, wrap=False):
+    """glass_evolve (libgenic/glass.cpp:76-147) for one rank on the device: nsteps kick-drift-kick steps of reversed gravity, nsteps + 1
+    PM forces.  pos [n][3] float64 (any finite value: positions are not wrapped), vel [n][3] float32, mass [n] float32 or a scalar; the
+    inputs are not modified.  Returns dict(Pos, Vel, Disp, steps, phase_ms) and, with spectra, kk / power / nmodes [nsteps][Nmesh] and
+    norm [nsteps]: the raw sums of every step (glass_finish_power finishes one).  The positions leave the loop unwrapped, as in the
+    reference; wrap=True applies periodic_wrap to the returned Pos, which shq_zeldovich_displacements needs."""
+    pos = np.array(pos, dtype=np.float64, order="C")
+    n = len(pos)
+    vel = np.zeros((n, 3), dtype=np.float32) if vel is None else np.array(vel, dtype=np.float32, order="C")
+    mass = np.full(n, mass, dtype=np.float32) if np.isscalar(mass) else np.ascontiguousarray(mass, dtype=np.float32)
+    if pos.shape != (n, 3) or vel.shape != (n, 3) or mass.shape != (n,):
+        raise ValueError("glass_evolve: pos and vel are [n][3], mass is [n]")
+    nsteps = int(nsteps)
+    disp = np.zeros((n, 3), dtype=np.float32)
+    steps = (capi.GlassStep * max(nsteps, 1))()
+    out = dict(Pos=pos, Vel=vel, Disp=disp)
+    if spectra:
+        out.update(kk=np.zeros((max(nsteps, 0), Nmesh)), power=np.zeros((max(nsteps, 0), Nmesh)),
+                   nmodes=np.zeros((max(nsteps, 0), Nmesh), dtype=np.int64), norm=np.zeros(max(nsteps, 0)))
+    gp = capi.GlassParams(int(Nmesh), nsteps, float(BoxSize))
+    sp = [capi.ptr(out[k]) if spectra else None for k in ("kk", "power", "nmodes", "norm")]
+    capi.check(capi.hip.shq_glass_evolve(ctx.h, C.byref(gp), n, capi.ptr(pos), capi.ptr(vel), capi.ptr(disp), capi.ptr(mass),
+                                         C.cast(steps, C.c_void_p), *sp), "glass_evolve")
+    ms = (C.c_double * 4)()
+    capi.check(capi.hip.shq_glass_phase_ms(ctx.h, C.byref(ms)), "glass_phase_ms")
+    out["steps"] = [dict(t_f=s.t_f, t_v=s.t_v, t_x=s.t_x, force_std=s.force_std, vel_std=s.vel_std) for s in steps[:max(nsteps, 0)]]
+    out["phase_ms"] = list(ms)
+    if wrap:
+        L = float(BoxSize)
+        while (pos >= L).any():
+            pos[pos >= L] -= L
+        while (pos < 0).any():
+            pos[pos < 0] += L
+    return out
+
+
 def synth_positions(kind, n, seed=20240601, L=1.0):
     """SURVEY §8(d) synthetic inputs: kind 'grid' | 'uniform' | 'cluster'."""
     k = {"grid": 0, "uniform": 1, "cluster": 2}[kind]

@@ -742,6 +742,27 @@ hip.shq_zeldovich_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 4)]
 hip.shq_zeldovich_phase_ms.restype = C.c_int
 hip.shq_zeldovich_column_draws.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
 hip.shq_zeldovich_column_draws.restype = C.c_int
+
+
+class GlassParams(C.Structure):
+    """shq_glass_params"""
+    _fields_ = [("Nmesh", C.c_int32), ("nsteps", C.c_int32), ("BoxSize", C.c_double)]
+
+
+class GlassStep(C.Structure):
+    """shq_glass_step: the times and glass_stats of one step"""
+    _fields_ = [("t_f", C.c_double), ("t_v", C.c_double), ("t_x", C.c_double), ("force_std", C.c_double), ("vel_std", C.c_double)]
+
+
+hip.shq_glass_evolve.argtypes = [_vp, C.POINTER(GlassParams), C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+hip.shq_glass_evolve.restype = C.c_int
+hip.shq_glass_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 4)]
+hip.shq_glass_phase_ms.restype = C.c_int
+hip.shq_glass_setup_positions.argtypes = [C.c_int, C.c_double, C.c_double, C.c_int, _vp]
+hip.shq_glass_setup_positions.restype = C.c_int
+hip.shq_glass_finish_power.argtypes = [C.c_int, C.c_double, _vp, _vp, _vp, C.c_double, C.POINTER(C.c_int)]
+hip.shq_glass_finish_power.restype = C.c_int
+
 hip.shq_treepm_last_fused.argtypes = [_vp, C.POINTER(C.c_int)]
 hip.shq_treepm_set_fuse.argtypes = [_vp, C.c_int]
 hip.shq_pm_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 6)]

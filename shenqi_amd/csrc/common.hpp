@@ -480,6 +480,8 @@ struct shq_context {
     int zel_n = 0, zel_seed = 0, zel_unitary = 0, zel_invert = 0; /* its key */
     int64_t zel_chunk = 0;                /* shq_zeldovich_set_fill_chunk: columns per fill launch (0: the default) */
     double zel_ms[4] = {0, 0, 0, 0};      /* shq_zeldovich_phase_ms */
+    /* ---- glass making (glass.hip): a call allocates and frees its own device buffers; only its times stay behind */
+    double glass_ms[4] = {0, 0, 0, 0};    /* shq_glass_phase_ms */
 };
 
 /* capi.hip: make the main stream wait for an outstanding asynchronous PM run */
