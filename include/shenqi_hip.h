@@ -1254,10 +1254,18 @@ int shq_pm_download_mesh(shq_context *ctx, int which /*0 density,1 potential*/, 
 /* Particle set already in HBM: d_posm = double[n][4] rows (x, y, z, m); the first nlocal rows are this
  * rank's own particles (PM deposit/readout and the default walk targets), the rest imported ghosts
  * that only act as sources in the tree; nlocal == 0 is a rank that owns nothing (no targets, no deposit, no readout).
- * Previous-step accelerations are kept when n is unchanged.  The tree of the previous set is dropped — a walk before the next
- * shq_tree_build / shq_tree_upload is refused — unless keep_tree != 0, by which the caller states that these are the very
- * positions (same count, same order) the current tree was built from (a force evaluation repeated on frozen positions). */
-int shq_particles_set_device(shq_context *ctx, const void *d_posm, int64_t n, int64_t nlocal, int keep_tree);
+ * Previous-step accelerations are kept when n is unchanged, and zeroed for every row otherwise.  The tree of the previous set is
+ * dropped — a walk before the next shq_tree_build / shq_tree_upload is refused.  flags (any other bit is SHQ_ERR_INVALID):
+ *   SHQ_SET_KEEP_TREE   : the caller states that these are the very positions (same count, same order) the current tree was built
+ *                         from (a force evaluation repeated on frozen positions): the tree stays.
+ *   SHQ_SET_CARRY_LOCAL : a re-import after a drift.  The caller states that the first nlocal rows are the previous set's own
+ *                         particles in the same order — moved, with whatever ghosts behind them.  When nlocal equals the previous
+ *                         set's, those rows keep FullTreeGravAccel, GravPM, OldAcc, the PM potential and the last walk's results
+ *                         whether or not n changed, and only the rows from nlocal on are zeroed.  With another nlocal, or without a
+ *                         previous set, the flag has no effect. */
+#define SHQ_SET_KEEP_TREE 1
+#define SHQ_SET_CARRY_LOCAL 2
+int shq_particles_set_device(shq_context *ctx, const void *d_posm, int64_t n, int64_t nlocal, int flags);
 /* The Type of every row of that set: d_types_u8 = uint8[n] in device memory, n = the set's row count (else SHQ_ERR_INVALID).  Sets the
  * Type bits of the particle flags and keeps the others; the deposit type mask may then leave types out.  shq_particles_set_device resets
  * every row to Type 1, so a caller issues this again after each set. */

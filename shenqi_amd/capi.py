@@ -937,6 +937,7 @@ host.shqh_hydro_force.argtypes = [_vp, _vp, _vp, _vp, C.c_int64, _vp, C.c_int64,
 
 # ---- multi-GPU slab entry points -------------------------------------------------------------
 hip.shq_particles_set_device.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int]
+SET_KEEP_TREE, SET_CARRY_LOCAL = 1, 2              # SHQ_SET_KEEP_TREE, SHQ_SET_CARRY_LOCAL: that call's flags
 hip.shq_pm_slab_deposit.argtypes = [_vp, C.POINTER(PMParams), C.c_int, C.c_int, _vp]
 hip.shq_pm_slab_green.argtypes = [_vp, C.POINTER(PMParams), C.c_int, C.c_int, _vp]
 hip.shq_pm_slab_readout.argtypes = [_vp, C.POINTER(PMParams), C.c_int, C.c_int, _vp]

@@ -824,29 +824,70 @@ __global__ void fill_u8_kernel(uint8_t *x, long long n, uint8_t v)
         x[i] = v;
 }
 
+namespace {
+/* DevBuf::reserve drops the contents when it grows: this one carries the first `keep` elements over */
+template <typename T> int reserve_keeping(shq_context *ctx, DevBuf<T> &b, size_t n, size_t keep)
+{
+    if(n <= b.cap || keep == 0 || !b.ptr)
+        return b.reserve(n);
+    DevBuf<T> grown;
+    SHQ_TRY(grown.reserve(n));
+    if(hipMemcpyAsync(grown.ptr, b.ptr, sizeof(T) * std::min(keep, b.cap), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+       hipStreamSynchronize(ctx->stream) != hipSuccess) {
+        grown.release();
+        SHQ_CHECK(false, SHQ_ERR_DEVICE, "particles_set_device: copying the kept rows into the grown buffer failed");
+    }
+    b.release();
+    b = grown;
+    return SHQ_OK;
+}
+
+/* rows [from, n) of a per-particle array of `width` values a row */
+template <typename T> int zero_rows(shq_context *ctx, DevBuf<T> &b, int64_t from, int64_t n, int width)
+{
+    if(n > from)
+        SHQ_HIP(hipMemsetAsync(b.ptr + (size_t) width * from, 0, sizeof(T) * width * (size_t) (n - from), ctx->stream));
+    return SHQ_OK;
+}
+} // namespace
+
 /* Device-side particle set for multi-GPU runs: rows (x, y, z, m) already in HBM (e.g. a torch
  * tensor holding local + imported ghost particles); the first nlocal rows are this rank's own. */
-extern "C" int shq_particles_set_device(shq_context *ctx, const void *d_posm, int64_t n, int64_t nlocal, int keep_tree)
+extern "C" int shq_particles_set_device(shq_context *ctx, const void *d_posm, int64_t n, int64_t nlocal, int flags)
 {
     if(ctx)
         ctx->inputs_current = 0; /* the resident set moves: shq_set_inputs_current ends here */
     SHQ_CHECK(ctx && (d_posm || n == 0), SHQ_ERR_INVALID, "null argument");
     SHQ_CHECK(n >= 0 && n < (1ll << 31) && nlocal >= 0 && nlocal <= n, SHQ_ERR_INVALID, "bad particle counts");
+    SHQ_CHECK((flags & ~(SHQ_SET_KEEP_TREE | SHQ_SET_CARRY_LOCAL)) == 0, SHQ_ERR_INVALID, "particles_set_device: unknown flags %d", flags);
+    const bool keep_tree = (flags & SHQ_SET_KEEP_TREE) != 0;
+    /* a re-import: the caller vouches that the first nlocal rows are the previous set's own particles in the same order (moved, with
+     * other ghosts behind them): their previous-step state stays, whatever the row count does */
+    const bool carry = (flags & SHQ_SET_CARRY_LOCAL) != 0 && ctx->have_parts && ctx->nlocal == nlocal && nlocal > 0;
+    const size_t keep = carry ? (size_t) nlocal : 0;
     SHQ_HIP(hipSetDevice(ctx->device));
     SHQ_TRY(shq_join_pm(ctx));
     const size_t cap = (size_t) std::max<int64_t>(n, 1);
     SHQ_TRY(ctx->posm.reserve(cap));
-    SHQ_TRY(ctx->oldacc.reserve(cap));
-    SHQ_TRY(ctx->treeacc.reserve(3 * cap));
-    SHQ_TRY(ctx->gravpm.reserve(3 * cap));
-    SHQ_TRY(ctx->pmpot.reserve(cap));
-    SHQ_TRY(ctx->acc.reserve(3 * cap));
-    SHQ_TRY(ctx->pot.reserve(cap));
-    SHQ_TRY(ctx->nint.reserve(cap));
+    SHQ_TRY(reserve_keeping(ctx, ctx->oldacc, cap, keep));
+    SHQ_TRY(reserve_keeping(ctx, ctx->treeacc, 3 * cap, 3 * keep));
+    SHQ_TRY(reserve_keeping(ctx, ctx->gravpm, 3 * cap, 3 * keep));
+    SHQ_TRY(reserve_keeping(ctx, ctx->pmpot, cap, keep));
+    SHQ_TRY(reserve_keeping(ctx, ctx->acc, 3 * cap, 3 * keep));
+    SHQ_TRY(reserve_keeping(ctx, ctx->pot, cap, keep));
+    SHQ_TRY(reserve_keeping(ctx, ctx->nint, cap, keep));
     SHQ_TRY(ctx->pflags.reserve(cap));
     if(n > 0) {
         SHQ_HIP(hipMemcpyAsync(ctx->posm.ptr, d_posm, sizeof(double4) * n, hipMemcpyDeviceToDevice, ctx->stream));
-        if(ctx->numpart != n) { /* a new particle set: previous-step accelerations no longer apply */
+        if(carry) { /* only the ghost rows are new */
+            SHQ_TRY(zero_rows(ctx, ctx->treeacc, nlocal, n, 3));
+            SHQ_TRY(zero_rows(ctx, ctx->gravpm, nlocal, n, 3));
+            SHQ_TRY(zero_rows(ctx, ctx->oldacc, nlocal, n, 1));
+            SHQ_TRY(zero_rows(ctx, ctx->pmpot, nlocal, n, 1));
+            SHQ_TRY(zero_rows(ctx, ctx->acc, nlocal, n, 3));
+            SHQ_TRY(zero_rows(ctx, ctx->pot, nlocal, n, 1));
+            SHQ_TRY(zero_rows(ctx, ctx->nint, nlocal, n, 1));
+        } else if(ctx->numpart != n) { /* a new particle set: previous-step accelerations no longer apply */
             SHQ_HIP(hipMemsetAsync(ctx->treeacc.ptr, 0, sizeof(double) * 3 * n, ctx->stream));
             SHQ_HIP(hipMemsetAsync(ctx->gravpm.ptr, 0, sizeof(double) * 3 * n, ctx->stream));
             SHQ_HIP(hipMemsetAsync(ctx->oldacc.ptr, 0, sizeof(double) * n, ctx->stream));

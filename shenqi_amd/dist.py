@@ -557,14 +557,17 @@ class GpuOps:
         if not self._shared():
             self.ctx.synchronize()
 
-    def set_particles(self, posm_all, nlocal, keep_tree=False, types=None):
+    def set_particles(self, posm_all, nlocal, keep_tree=False, types=None, carry=False):
         """posm_all: device tensor [n, 4] (x, y, z, m), the first nlocal rows are this rank's own.  keep_tree: these are the
         positions the resident tree was built from (nothing moved since).  types: the rows' Types (n integers; without them every
-        row is Type 1 and the deposit type mask must stay SHQ_ALL_TYPES)."""
+        row is Type 1 and the deposit type mask must stay SHQ_ALL_TYPES).  carry: the first nlocal rows are the previous set's
+        own particles in the same order (a re-import): their previous-step accelerations stay whatever the ghost count does
+        (SHQ_SET_CARRY_LOCAL)."""
         t = posm_all.contiguous()
         ty = None if types is None else types.to(device=t.device, dtype=torch.uint8).contiguous()
+        flags = (capi.SET_KEEP_TREE if keep_tree else 0) | (capi.SET_CARRY_LOCAL if carry else 0)
         self._before()                  # torch produced t on its stream; the library copies on its own
-        capi.check(capi.hip.shq_particles_set_device(self.ctx.h, C.c_void_p(t.data_ptr()), t.shape[0], nlocal, int(keep_tree)))
+        capi.check(capi.hip.shq_particles_set_device(self.ctx.h, C.c_void_p(t.data_ptr()), t.shape[0], nlocal, flags))
         if ty is not None:
             capi.check(capi.hip.shq_particles_set_device_types(self.ctx.h, C.c_void_p(ty.data_ptr()), ty.shape[0]))
         self._after()
@@ -715,6 +718,7 @@ class DistTreePM:
         self.halo_factor = halo_factor
         self.tree = None
         self.local_types = self.types = None
+        self._moved = False
 
     def setup(self, posm_local, Rcut, types=None):
         """posm_local: device tensor [nloc, 4] of the particles this rank owns (already exchanged to
@@ -729,6 +733,26 @@ class DistTreePM:
         self.ops.set_deposit_scale(self.comm.allreduce_sum(float(self.local[:, 3].sum().item())))
         self._load_particles()
         self._build_tree()
+        self._moved = False
+
+    def move(self, posm_local):
+        """New positions (a drift) of the particles this rank owns: device tensor [nloc, 4], the rows of self.local in the same
+        order.  The next step() imports the ghosts for them and rebuilds the tree, and the rows keep their previous-step
+        accelerations.  Every particle must still lie in this rank's slab (with ycuts: on its side of a shared plane): the slab
+        deposit has ghost planes for the CIC cloud only, not for particles of another slab.  That is checked here on the host,
+        before anything is launched; a particle that left goes through exchange_to_owner + setup instead."""
+        if tuple(posm_local.shape) != (self.nloc, 4):
+            raise ValueError("move: expected the %d rows (x, y, z, m) of self.local, got shape %s" % (self.nloc, tuple(posm_local.shape)))
+        host = posm_local.detach().contiguous().cpu()
+        owner = self.decomp.owner_of(host[:, 0], host[:, 1])
+        out = int((owner != self.comm.rank).sum())
+        if out:
+            i = int(torch.nonzero(owner != self.comm.rank)[0])
+            raise ValueError("move: %d of the %d particles left the slab of rank %d (the first: row %d at x = %.17g, y = %.17g, now rank "
+                             "%d's): migration between ranks goes through exchange_to_owner + setup, not through move"
+                             % (out, self.nloc, self.comm.rank, i, float(host[i, 0]), float(host[i, 1]), int(owner[i])))
+        self.local = posm_local.detach().to(self.device).contiguous()
+        self._moved = True
 
     def _build_tree(self):
         """local + ghost particles are resident: build their tree (global root cell) on the device"""
@@ -749,7 +773,7 @@ class DistTreePM:
             tv = self.tree.view()
             capi.check(capi.hip.shq_tree_upload(self.ctx.h, C.byref(tv)))
 
-    def _load_particles(self, keep_tree=False):
+    def _load_particles(self, keep_tree=False, carry=False):
         if self.local_types is None:
             ghosts = ghost_exchange(self.comm, self.decomp, self.local, self.halo)
             self.types = None
@@ -759,20 +783,26 @@ class DistTreePM:
             self.types = torch.cat([self.local_types, gtypes], dim=0).contiguous()
         self.allp = torch.cat([self.local, ghosts], dim=0).contiguous()
         self.nghost = int(ghosts.shape[0])
-        self.ops.set_particles(self.allp, self.nloc, keep_tree, types=self.types)
+        self.ops.set_particles(self.allp, self.nloc, keep_tree, types=self.types, carry=carry)
 
     def step(self, gp, update_potential=1, walk_mode=0, overlap=None, moved=False, analysis=None, measure_power=False):
-        """One force evaluation: ghost import, PM, walk for the local targets, OldAcc refresh.
-        moved: self.local changed since the tree was built (a drift): the ghosts are imported for the new positions and the
-        tree is rebuilt.  Without it the step repeats the evaluation on the positions of setup(): the ghost exchange still
-        runs (it is part of a step), the tree is kept.
-        overlap (default: whenever the transposes are collectives; SHQ_DIST_OVERLAP=0 turns it off): the walk does not need
-        the PM result of its own step (OldAcc is the previous step's), so it is cut in two pieces that are queued behind the
-        start of the two mesh transposes: the walk computes while the spectrum travels over xGMI.
+        """One force evaluation: ghost import, PM, OldAcc, walk for the local targets.
+        moved: self.local changed since the tree was built (a drift; implied after move()): the ghosts are imported for the new
+        positions and the tree is rebuilt.  Without it the step repeats the evaluation on the positions of setup(): the ghost
+        exchange still runs (it is part of a step), the tree is kept.  Either way the local rows keep the accelerations of the
+        previous step, however many ghosts come and go (SHQ_SET_CARRY_LOCAL).
+        Without overlap the order is the reference's (run.cpp:518-523, gravshort2.hpp:111-121): PM, then OldAcc =
+        |FullTreeGravAccel(k-1) + GravPM(k)| / G from the NEW GravPM, then the walk - what shq_treepm_step does on one card.
+        overlap (default: whenever the transposes are collectives; SHQ_DIST_OVERLAP=0 turns it off): the walk is cut in two
+        pieces that are queued behind the start of the two mesh transposes, so that it computes while the spectrum travels over
+        xGMI.  It therefore runs before its own step's PM exists and opens nodes by |FullTreeGravAccel(k-1) + GravPM(k-1)| / G,
+        the OldAcc formed at the end of the previous step: this departs from run.cpp:518-523, which uses the new GravPM.
         analysis, measure_power: as SlabPM.force (massive neutrinos); the reduced sums are in self.pm.power / power_finish."""
-        self._load_particles(keep_tree=not moved)
+        moved = bool(moved) or self._moved
+        self._load_particles(keep_tree=not moved, carry=True)
         if moved:
             self._build_tree()
+            self._moved = False
         if overlap is None:
             overlap = self.comm.multi and os.environ.get("SHQ_DIST_OVERLAP", "1") != "0"
         if overlap and self.nloc >= 512:
@@ -784,15 +814,23 @@ class DistTreePM:
             self.pm.force([piece(0, half), piece(half, self.nloc - half)], analysis=analysis, measure_power=measure_power)
         else:
             self.pm.force(analysis=analysis, measure_power=measure_power)
+            if not overlap:      # a rank too small to cut its walk still computes what the overlap mode computes
+                capi.check(capi.hip.shq_grav_refresh_oldacc(self.ctx.h, self.G))
             capi.check(capi.hip.shq_grav_short_run(self.ctx.h, C.byref(gp), None, 0, int(update_potential), walk_mode))
+        # |FullTreeGravAccel(k) + GravPM(k)| / G: what the next step's walk opens by when that step overlaps
         capi.check(capi.hip.shq_grav_refresh_oldacc(self.ctx.h, self.G))
 
-    def download(self):
+    def download(self, ninteractions=False):
+        """(FullTreeGravAccel, tree potential, GravPM, PM potential) of the local rows; with ninteractions also the last walk's
+        interaction count of every local target, as a fifth entry"""
         n = int(self.allp.shape[0])
         acc = np.zeros((n, 3))
         pot = np.zeros(n)
-        capi.check(capi.hip.shq_grav_short_download(self.ctx.h, capi.ptr(acc), capi.ptr(pot), None, None))
+        nint = np.zeros(n, dtype=np.int64) if ninteractions else None
+        capi.check(capi.hip.shq_grav_short_download(self.ctx.h, capi.ptr(acc), capi.ptr(pot), capi.ptr(nint), None))
         gpm, ppot = self.ops.results(self.nloc)
+        if ninteractions:
+            return acc[: self.nloc], pot[: self.nloc], gpm, ppot, nint[: self.nloc]
         return acc[: self.nloc], pot[: self.nloc], gpm, ppot
 
 

@@ -239,3 +239,31 @@ def test_slab_pm_with_an_empty_slab_gloo():
             assert np.abs(a[:, 4:7] - og[idx]).max() < 1e-11 * np.abs(og).max()
             assert np.abs(a[:, 7] - opot[idx]).max() < 1e-11 * np.abs(opot).max()
         assert seen == n
+
+
+def test_move_refuses_a_particle_outside_the_slab():
+    """DistTreePM.move checks on the host that every row still lies in its rank's slab (with ycuts: on its side of a shared plane)
+    and raises before anything is launched - there is no device here, and the driver has no context; rows inside are accepted"""
+    import types
+    from shenqi_amd import dist as sd
+    cell = BOX / NMESH
+    for ycuts, bad in ((None, [30 * cell + 1e-9, 1.0]),                 # one particle just inside the neighbour's first plane
+                       ([0.0, 5.0, 0.0], [30.5 * cell, 5.0]),           # the shared plane 30, y at the cut: the right-hand rank's
+                       (None, [-1e-9, 1.0])):                           # wraps to the last plane
+        comm = types.SimpleNamespace(size=2, rank=0, multi=True)
+        drv = sd.DistTreePM(comm, None, NMESH, BOX, 1.5, G, torch.device("cpu"), bounds=[0, 30, NMESH], ycuts=ycuts)
+        drv.local = torch.tensor([[1.0, 1.0, 1.0, 1.0], [4.9, 7.0, 2.0, 1.0], [2.0, 2.0, 2.0, 1.0]], dtype=torch.float64)
+        drv.nloc = 3
+        inside = drv.local.clone()
+        inside[1, 0] = 30 * cell - 1e-9                                 # the last plane of rank 0
+        if ycuts is not None:
+            inside[2, :2] = torch.tensor([30.5 * cell, 4.999])          # rank 0's part of the shared plane
+        drv.move(inside)
+        assert drv.local is not inside and torch.equal(drv.local, inside) and drv._moved
+        moved = inside.clone()
+        moved[1, :2] = torch.tensor(bad, dtype=torch.float64)
+        with pytest.raises(ValueError, match="exchange_to_owner"):
+            drv.move(moved)
+        assert torch.equal(drv.local, inside)                           # refused whole: nothing was taken over
+        with pytest.raises(ValueError, match="rows"):
+            drv.move(inside[:2])

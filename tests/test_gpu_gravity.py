@@ -876,8 +876,10 @@ def test_pair_kernel_failures_in_a_resident_loop(ctx):
         assert rcs[-1] == ERR_DEVICE and "pair stack" in capi.hip.shq_last_error().decode(), rcs
         # drained and cleared: the same loop with the stacks restored is the reference loop again
         capi.check(capi.hip.shq_set_walk_debug(ctx.h, 0, 0))
-        while capi.hip.shq_synchronize(ctx.h) != 0:
-            pass
+        rcs = []
+        while len(rcs) < 4 and (not rcs or rcs[-1] != 0):       # each failed launch reports once; three were queued
+            rcs.append(capi.hip.shq_synchronize(ctx.h))
+        assert rcs[-1] == 0, rcs
         start()
         for _ in range(3):
             capi.check(step())
