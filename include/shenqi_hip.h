@@ -956,8 +956,8 @@ int shq_sph_fill_queries(shq_context *ctx, const shq_data_index *table, int64_t 
 
 /* ---- stellar density ------------------------------------------------------------------------------
  * stellar_density() (libgadget/stellar_density2.cpp:306-341): the SPH volume weight sum(m_j / rho_j [* w_k]) of the gas
- * around each star of `queue` (the reference's StarQueue: build_stellar_density_queue, :285-303, stays on the host — it reads
- * the star slots), with its own Hsml iteration over ten trial radii per walk (stellareffhsml, ngbiter, postprocess,
+ * around each star of `queue` (the reference's StarQueue: build_stellar_density_queue, :285-303; for metal_return it is the
+ * queue shq_metal_yields returns), with its own Hsml iteration over ten trial radii per walk (stellareffhsml, ngbiter, postprocess,
  * ngb_narrow_down).  `tree` is the gas tree (GASMASK); gas densities come from the SPH view.  Writes Part[].Hsml of the
  * stars and StarVolumeSPH[PI of the star].  A star with Hsml == 0 is refused (the reference re-seeds it from its father
  * node).  SHQ_ERR_NOCONV beyond MAXITER iterations. */
@@ -1115,14 +1115,14 @@ int shq_winds_subgrid(shq_context *ctx, const shq_part_view *parts, const shq_sp
                       int64_t nlist, const double *StellarMasses, const shq_wind_params *params, const double *rnd_table, int64_t rnd_size, int64_t *nkicked);
 
 /* The treewalk of metal_return() (libgadget/metal_return.cpp:513-530, 573-667), after stellar_density
- * (shq_stellar_density) and with the per-star yields of metal_return_copy (:540-571: the IMF / yield-table integrals stay with the
- * caller): every gas particle inside the kernel of a star of `queue` (r2 > 0, r2 < H^2) receives
+ * (shq_stellar_density) and with the per-star yields of metal_return_copy (:540-571: the IMF / yield-table integrals, which
+ * shq_metal_yields below evaluates on the device): every gas particle inside the kernel of a star of `queue` (r2 > 0, r2 < H^2) receives
  * returnfraction = wk (Mass / Density) / StarVolumeSPH of the star's MassGenerated, MetalGenerated and MetalSpeciesGenerated, unless that
  * would lift it above MaxGasMass: Metals[] (float), Metallicity, Mass (float) and Density are updated with the reference's expressions
  * (:622-660).  The reference serialises the updates of a particle with a spin lock, in whatever order its threads arrive; here the
  * stars reach a particle in queue order (a triple list sorted by particle and queue position, applied by one thread per particle).
  * MassReturn[k] = the mass star queue[k] gave away (metal_return_reduce); the star's own bookkeeping (metal_return_postprocess:
- * Mass -= MassReturn, TotalMassReturned, LastEnrichmentMyr) is three assignments the caller keeps.  All per-star arrays are indexed by
+ * Mass -= MassReturn, TotalMassReturned, LastEnrichmentMyr) is shq_metal_return_postprocess below.  All per-star arrays are indexed by
  * queue position. */
 typedef struct shq_gas_metal_view {
     void *base;
@@ -1134,6 +1134,73 @@ typedef struct shq_gas_metal_view {
 int shq_metal_return(shq_context *ctx, const shq_tree_view *tree, const shq_part_view *parts, const shq_gas_metal_view *gas, const int32_t *queue, int64_t nqueue,
                      const double *StarVolumeSPH, const double *MassGenerated, const double *MetalGenerated, const double *MetalSpeciesGenerated /* [nqueue][nmetals] */,
                      double MaxGasMass, int SPHWeighting, int DensityKernelType, double *MassReturn, int64_t *npairs);
+
+/* ---- stellar yields: metal_return_init and the yields of metal_return_copy (libgadget/metal_return.cpp:157-462, 539-569) ------------
+ * What metal_return() does per active star before its two tree walks: the star's age, the masses of the stars that die during the
+ * step (find_mass_bin_limits), the mass it returns (mass_yield), the maxmassfrac clamp, the queue of the stars with work
+ * (metals_haswork) and, for those, the metal and species yields (metal_yield).  The integrals and roots the reference leaves to an
+ * adaptive Gauss-Kronrod rule (asked for 1e-4) and a TOMS-748 bracket (asked for 5e-3) are evaluated in closed form:
+ * results agree with the reference to its own tolerances, not bit for bit.
+ *
+ * shq_yields_init uploads the caller's tables once (a second call replaces them; the library ships none) and returns maxmassfrac
+ * (:425), evaluated on the host by the routine the kernel uses.  Tables are laid out as libgadget/metal_tables.h has them:
+ * value[mass index * nmet + metallicity index]; the species tables are [nmetals][nmass * nmet].  nmetals must be 9 (NMETALS).
+ * Requirements (SHQ_ERR_INVALID otherwise): agb_masses[0] >= 1 (only the power-law branch of the Chabrier IMF is integrated),
+ * agb_masses[0] <= SNAGBSWITCH <= MAXMASS, increasing axes, and lifetimes that decrease strictly with mass from the first node to
+ * the first node at or above MAXMASS, at every metallicity node.
+ *
+ * The cosmic-time table stands in for atime_to_myr (:170-178): n >= 2 nodes uniform in ln a, a_k = exp(loga0 + k dloga);
+ * T[k] = time in Myr since a_0, dTdloga[k] = UnitTime_in_s / SEC_PER_MEGAYEAR / hubble_function(a_k).  Ages are the integral of the
+ * cubic Hermite interpolant between ln FormationTime and ln atime. */
+typedef struct shq_yield_tables {
+    int32_t life_nmet, life_nmass;
+    const double *lifetime_metallicity, *lifetime_masses, *lifetime;             /* years */
+    int32_t agb_nmet, agb_nmass;
+    const double *agb_metallicities, *agb_masses, *agb_total_mass, *agb_total_metals, *agb_yield;
+    int32_t snii_nmet, snii_nmass;
+    const double *snii_metallicities, *snii_masses, *snii_total_mass, *snii_total_metals, *snii_yield;
+    int32_t nmetals, pad_;
+    double sn1a_total_metals;
+    const double *sn1a_yields;                                                    /* [nmetals] */
+} shq_yield_tables;
+typedef struct shq_cosmic_time_table {
+    int64_t n;
+    double loga0, dloga;
+    const double *T, *dTdloga;
+} shq_cosmic_time_table;
+typedef struct shq_yield_params {
+    double Sn1aN0, HubbleParam, imf_norm /* compute_imf_norm() */, MAXMASS, SNAGBSWITCH;
+} shq_yield_params;
+int shq_yields_init(shq_context *ctx, const shq_yield_tables *tables, const shq_cosmic_time_table *times, const shq_yield_params *params,
+                    double *maxmassfrac);
+
+/* metal_return_init (:410-462) for the stars (Type 4) of the active list (NULL: all particles; others are skipped), then the queue of
+ * metals_haswork (:123-132) in active-list order (a stable compaction: the same list on every run) and metal_return_copy's yields
+ * (:539-569) for its stars.  Reads Part.Mass / Type / PI and the star slots; writes, by star slot, StellarAges, LowDyingMass, HighDyingMass
+ * and MassReturn (slots of stars not in the list are left alone), LastEnrichmentMyr = age into the slots of the stars the maxmassfrac
+ * clamp leaves without work (:445-456; the reference's message() is dropped), and by queue position queue[] (particle indices: the
+ * `queue` of shq_stellar_density and shq_metal_return), MassGenerated, MetalGenerated and MetalSpeciesGenerated[][nmetals] (room for as
+ * many entries as the active list has).  A FormationTime or atime outside the time table: SHQ_ERR_INVALID, *nbad = the number of such
+ * stars (all of the list's stars when it is atime), nothing written.  nbad may be NULL.
+ * The particle and slot records are read where the caller keeps them; the context's resident copies are neither used nor changed, so
+ * the call can stand anywhere inside a shq_set_inputs_current bracket. */
+typedef struct shq_star_yield_view {
+    void *base;
+    size_t elsize;
+    int64_t numslots;
+    size_t off_formationtime, off_lastenrichmentmyr;   /* float */
+    size_t off_totalmassreturned, off_metallicity;     /* double */
+} shq_star_yield_view;
+int shq_metal_yields(shq_context *ctx, const shq_part_view *parts, const shq_star_yield_view *stars, const int32_t *active, int64_t nactive, double atime,
+                     double *StellarAges, double *LowDyingMass, double *HighDyingMass, double *MassReturn, int32_t *queue, int64_t *nqueue,
+                     double *MassGenerated, double *MetalGenerated, double *MetalSpeciesGenerated, int64_t *nbad);
+/* metal_return_postprocess (:581-589) for the stars of `queue`: Part.Mass -= MassReturn[k] (float), TotalMassReturned += MassReturn[k],
+ * LastEnrichmentMyr = StellarAges[slot] (float).  MassReturn is shq_metal_return's output, by queue position; StellarAges is indexed by
+ * star slot.  Where the context holds a copy of these very particles (shq_set_inputs_current), its masses are updated alike. */
+int shq_metal_return_postprocess(shq_context *ctx, const shq_part_view *parts, const shq_star_yield_view *stars, const int32_t *queue, int64_t nqueue,
+                                 const double *MassReturn, const double *StellarAges);
+/* device time of the last shq_metal_yields: ms[0] the first pass (ages, limits, mass return), ms[1] the second (the queue's yields) */
+int shq_metal_yields_last_ms(shq_context *ctx, double ms[2]);
 
 /* ---- long-range PM --------------------------------------------------------------------- */
 

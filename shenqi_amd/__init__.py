@@ -452,6 +452,88 @@ def lens_planes(ctx, pman, Resolution, Normals, CutPoints=None, Thickness=0.0, C
     return planes, npl, cnt
 
 
+def cosmic_time_table(hubble_function, amin, amax, n, UnitTime_in_s, SEC_PER_MEGAYEAR=3.155e13):
+    """The table shq_yields_init takes in place of atime_to_myr (metal_return.cpp:170-178): n nodes uniform in ln a over [amin, amax];
+    dTdloga = UnitTime_in_s / SEC_PER_MEGAYEAR / hubble_function(a), T = its integral from the first node (scipy's quad, node to node).
+    Returns (loga0, dloga, T, dTdloga)."""
+    from scipy.integrate import quad
+    loga0, dloga = np.log(amin), (np.log(amax) - np.log(amin)) / (n - 1)
+    fac = UnitTime_in_s / SEC_PER_MEGAYEAR
+    lna = loga0 + dloga * np.arange(n)
+    dT = np.array([fac / hubble_function(np.exp(x)) for x in lna])
+    steps = [quad(lambda x: fac / hubble_function(np.exp(x)), lna[k], lna[k + 1], epsrel=1e-13, epsabs=0)[0] for k in range(n - 1)]
+    return float(loga0), float(dloga), np.concatenate([[0.0], np.cumsum(steps)]), dT
+
+
+def yields_init(ctx, tables, time_table, Sn1aN0, HubbleParam, imf_norm, MAXMASS=None, SNAGBSWITCH=None):
+    """shq_yields_init: upload the caller's yield tables (a mapping with the array names of libgadget/metal_tables.h, each laid out as
+    there) and cosmic-time table (loga0, dloga, T, dTdloga); returns maxmassfrac (metal_return.cpp:425)."""
+    a = {k: np.ascontiguousarray(tables[k], dtype=np.float64) for k in (
+        "lifetime_metallicity", "lifetime_masses", "lifetime", "agb_metallicities", "agb_masses", "agb_total_mass", "agb_total_metals", "agb_yield",
+        "snii_metallicities", "snii_masses", "snii_total_mass", "snii_total_metals", "snii_yield", "sn1a_yields")}
+    yt = capi.YieldTables()
+    yt.life_nmet, yt.life_nmass = len(a["lifetime_metallicity"]), len(a["lifetime_masses"])
+    yt.agb_nmet, yt.agb_nmass = len(a["agb_metallicities"]), len(a["agb_masses"])
+    yt.snii_nmet, yt.snii_nmass = len(a["snii_metallicities"]), len(a["snii_masses"])
+    if (a["lifetime"].size != yt.life_nmet * yt.life_nmass or a["agb_total_mass"].size != yt.agb_nmet * yt.agb_nmass
+            or a["agb_total_metals"].size != a["agb_total_mass"].size or a["snii_total_mass"].size != yt.snii_nmet * yt.snii_nmass
+            or a["snii_total_metals"].size != a["snii_total_mass"].size or a["agb_yield"].size != len(a["sn1a_yields"]) * a["agb_total_mass"].size
+            or a["snii_yield"].size != len(a["sn1a_yields"]) * a["snii_total_mass"].size):
+        raise ValueError("yields_init: table sizes do not match their axes")
+    for k, v in a.items():
+        if k != "sn1a_yields":
+            setattr(yt, k, v.ctypes.data)
+    yt.nmetals, yt.sn1a_total_metals, yt.sn1a_yields = len(a["sn1a_yields"]), float(np.asarray(tables["sn1a_total_metals"]).ravel()[0]), a["sn1a_yields"].ctypes.data
+    loga0, dloga, T, dT = time_table
+    T, dT = np.ascontiguousarray(T, dtype=np.float64), np.ascontiguousarray(dT, dtype=np.float64)
+    if len(T) != len(dT):
+        raise ValueError("yields_init: T and dTdloga differ in length")
+    ct = capi.CosmicTimeTable(len(T), float(loga0), float(dloga), T.ctypes.data, dT.ctypes.data)
+    yp = capi.YieldParams(float(Sn1aN0), float(HubbleParam), float(imf_norm), float(np.asarray(tables["MAXMASS"] if MAXMASS is None else MAXMASS).ravel()[0]),
+                          float(np.asarray(tables["SNAGBSWITCH"] if SNAGBSWITCH is None else SNAGBSWITCH).ravel()[0]))
+    mmf = C.c_double()
+    capi.check(capi.hip.shq_yields_init(ctx.h, C.byref(yt), C.byref(ct), C.byref(yp), C.byref(mmf)), "yields_init")
+    return mmf.value
+
+
+def metal_yields(ctx, pman, StarP, atime, active=None, out=None):
+    """metal_return_init + the yields of metal_return_copy (metal_return.cpp:410-462, 539-569) on the device: shq_metal_yields.
+    StarP: the star slots (capi.STAR_DTYPE; LastEnrichmentMyr is rewritten where the reference does).  Returns a dict: StellarAges,
+    LowDyingMass, HighDyingMass, MassReturn by star slot (`out`, a dict of such arrays, is updated in place where given: slots of stars
+    outside the list keep their values), queue (particle indices, active-list order), MassGenerated, MetalGenerated,
+    MetalSpeciesGenerated by queue position."""
+    act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+    cnt = pman.NumPart if act is None else len(act)
+    r = {k: (out[k] if out is not None else np.zeros(len(StarP))) for k in ("StellarAges", "LowDyingMass", "HighDyingMass", "MassReturn")}
+    queue = np.zeros(max(cnt, 1), dtype=np.int32)
+    mg, zg, sg = np.zeros(max(cnt, 1)), np.zeros(max(cnt, 1)), np.zeros((max(cnt, 1), 9))
+    nq, nbad = C.c_int64(), C.c_int64()
+    pv, sv = pman.view(), capi.star_yield_view(StarP)
+    rc = capi.hip.shq_metal_yields(ctx.h, C.byref(pv), C.byref(sv), capi.ptr(act), cnt, float(atime), capi.ptr(r["StellarAges"]), capi.ptr(r["LowDyingMass"]),
+                                   capi.ptr(r["HighDyingMass"]), capi.ptr(r["MassReturn"]), capi.ptr(queue), C.byref(nq), capi.ptr(mg), capi.ptr(zg),
+                                   capi.ptr(sg), C.byref(nbad))
+    if rc != 0 and nbad.value:
+        msg = capi.hip.shq_last_error().decode()
+        e = ShqError(f"metal_yields failed with status {rc}: {msg}")
+        e.status, e.nbad = rc, nbad.value
+        raise e
+    capi.check(rc, "metal_yields")
+    n = nq.value
+    r.update(queue=queue[:n].copy(), MassGenerated=mg[:n].copy(), MetalGenerated=zg[:n].copy(), MetalSpeciesGenerated=sg[:n].copy())
+    return r
+
+
+def metal_return_postprocess(ctx, pman, StarP, queue, MassReturn, StellarAges):
+    """metal_return_postprocess (metal_return.cpp:581-589) for the stars of `queue`: Mass, TotalMassReturned, LastEnrichmentMyr"""
+    q = np.ascontiguousarray(queue, dtype=np.int32)
+    mr, ages = np.ascontiguousarray(MassReturn, dtype=np.float64), np.ascontiguousarray(StellarAges, dtype=np.float64)
+    if len(mr) != len(q) or len(ages) != len(StarP):
+        raise ValueError("metal_return_postprocess: MassReturn is indexed by queue position, StellarAges by star slot")
+    pv, sv = pman.view(), capi.star_yield_view(StarP)
+    capi.check(capi.hip.shq_metal_return_postprocess(ctx.h, C.byref(pv), C.byref(sv), capi.ptr(q), len(q), capi.ptr(mr), capi.ptr(ages)),
+               "metal_return_postprocess")
+
+
 class IDGenerator:
     """idgen_init on one rank (libgenic/zeldovich.cpp:46-65): the whole Ngrid^3 lattice"""
 

@@ -763,6 +763,49 @@ hip.shq_glass_setup_positions.restype = C.c_int
 hip.shq_glass_finish_power.argtypes = [C.c_int, C.c_double, _vp, _vp, _vp, C.c_double, C.POINTER(C.c_int)]
 hip.shq_glass_finish_power.restype = C.c_int
 
+
+class YieldTables(C.Structure):
+    """shq_yield_tables: the caller's lifetime / AGB / SNII / SN Ia tables, laid out value[mass index * nmet + metallicity index]"""
+    _fields_ = [("life_nmet", C.c_int32), ("life_nmass", C.c_int32), ("lifetime_metallicity", _vp), ("lifetime_masses", _vp), ("lifetime", _vp),
+                ("agb_nmet", C.c_int32), ("agb_nmass", C.c_int32), ("agb_metallicities", _vp), ("agb_masses", _vp), ("agb_total_mass", _vp),
+                ("agb_total_metals", _vp), ("agb_yield", _vp),
+                ("snii_nmet", C.c_int32), ("snii_nmass", C.c_int32), ("snii_metallicities", _vp), ("snii_masses", _vp), ("snii_total_mass", _vp),
+                ("snii_total_metals", _vp), ("snii_yield", _vp),
+                ("nmetals", C.c_int32), ("pad_", C.c_int32), ("sn1a_total_metals", C.c_double), ("sn1a_yields", _vp)]
+
+
+class CosmicTimeTable(C.Structure):
+    """shq_cosmic_time_table"""
+    _fields_ = [("n", C.c_int64), ("loga0", C.c_double), ("dloga", C.c_double), ("T", _vp), ("dTdloga", _vp)]
+
+
+class YieldParams(C.Structure):
+    """shq_yield_params"""
+    _fields_ = [(k, C.c_double) for k in ("Sn1aN0", "HubbleParam", "imf_norm", "MAXMASS", "SNAGBSWITCH")]
+
+
+class StarYieldView(C.Structure):
+    """shq_star_yield_view"""
+    _fields_ = [("base", C.c_void_p), ("elsize", C.c_size_t), ("numslots", C.c_int64), ("off_formationtime", C.c_size_t),
+                ("off_lastenrichmentmyr", C.c_size_t), ("off_totalmassreturned", C.c_size_t), ("off_metallicity", C.c_size_t)]
+
+
+def star_yield_view(StarP):
+    f = StarP.dtype.fields
+    return StarYieldView(StarP.ctypes.data, StarP.dtype.itemsize, len(StarP), f["FormationTime"][1], f["LastEnrichmentMyr"][1],
+                         f["TotalMassReturned"][1], f["Metallicity"][1])
+
+
+hip.shq_yields_init.argtypes = [_vp, C.POINTER(YieldTables), C.POINTER(CosmicTimeTable), C.POINTER(YieldParams), C.POINTER(C.c_double)]
+hip.shq_yields_init.restype = C.c_int
+hip.shq_metal_yields.argtypes = [_vp, C.POINTER(PartView), C.POINTER(StarYieldView), _vp, C.c_int64, C.c_double, _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int64),
+                                 _vp, _vp, _vp, C.POINTER(C.c_int64)]
+hip.shq_metal_yields.restype = C.c_int
+hip.shq_metal_return_postprocess.argtypes = [_vp, C.POINTER(PartView), C.POINTER(StarYieldView), _vp, C.c_int64, _vp, _vp]
+hip.shq_metal_return_postprocess.restype = C.c_int
+hip.shq_metal_yields_last_ms.argtypes = [_vp, C.POINTER(C.c_double * 2)]
+hip.shq_metal_yields_last_ms.restype = C.c_int
+
 hip.shq_treepm_last_fused.argtypes = [_vp, C.POINTER(C.c_int)]
 hip.shq_treepm_set_fuse.argtypes = [_vp, C.c_int]
 hip.shq_pm_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 6)]

@@ -9,6 +9,7 @@
 #include <string>
 #include <vector>
 #include "../../include/shenqi_hip.h"
+#include "yields_math.hpp"
 
 void shq_set_error(const char *fmt, ...);
 
@@ -482,6 +483,17 @@ struct shq_context {
     double zel_ms[4] = {0, 0, 0, 0};      /* shq_zeldovich_phase_ms */
     /* ---- glass making (glass.hip): a call allocates and frees its own device buffers; only its times stay behind */
     double glass_ms[4] = {0, 0, 0, 0};    /* shq_glass_phase_ms */
+    /* ---- stellar yields (yields.hip): the caller's tables of shq_yields_init and the per-call work arrays */
+    bool yld_have = false;
+    YieldDesc yld_desc = {};
+    std::vector<double> yld_host;         /* the flat table array (yields_math.hpp) as uploaded */
+    DevBuf<double> yld_tab, yld_time;     /* ... on the device; T[n] and dTdloga[n] of the cosmic-time table */
+    int64_t yld_time_n = 0;
+    double yld_loga0 = 0, yld_dloga = 0, yld_amin = 0, yld_amax = 0;
+    DevBuf<double> yld_in, yld_out;       /* by active-list position */
+    DevBuf<int32_t> yld_i32;
+    DevBuf<uint8_t> yld_mark;
+    double yld_ms[2] = {0, 0};            /* shq_metal_yields_last_ms */
 };
 
 /* capi.hip: make the main stream wait for an outstanding asynchronous PM run */
