@@ -37,6 +37,9 @@ void shq_set_error(const char *fmt, ...);
             return rc_;                                                                        \
     } while(0)
 
+/* blocks of t threads that cover n items, one at least: a launch over nothing is one block whose threads all fail `i < n` */
+inline unsigned nblk(long long n, int t = 256) { return n > 0 ? (unsigned) ((n + t - 1) / t) : 1u; }
+
 /* Grow-only device buffer from the library's own pool (never the caller's arena). */
 template <typename T> struct DevBuf {
     T *ptr = nullptr;

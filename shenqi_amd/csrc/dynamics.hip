@@ -21,8 +21,6 @@
 
 namespace {
 
-inline unsigned nblk(long long n, int t = 256) { return (unsigned) ((n + t - 1) / t); }
-
 struct Shift3 { double s[3]; };
 
 struct BhJump { /* black-hole repositioning, drift.cpp:32-53; pidx == nullptr: off */

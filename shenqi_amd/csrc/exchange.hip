@@ -18,8 +18,6 @@
 
 namespace {
 
-inline unsigned nblk(long long n, int t = 256) { return (unsigned) ((n + t - 1) / t); }
-
 struct Leaving {
     const char *parts;
     size_t elsize, off_flags;

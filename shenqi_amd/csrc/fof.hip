@@ -24,8 +24,6 @@
 
 namespace {
 
-inline unsigned nblk(long long n, int t = 256) { return (unsigned) ((n + t - 1) / t); }
-
 __device__ __forceinline__ double nearest(double x, double Box) { return (x > 0.5 * Box) ? (x - Box) : ((x < -0.5 * Box) ? (x + Box) : x); }
 
 struct FofTree {

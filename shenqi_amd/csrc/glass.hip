@@ -11,7 +11,7 @@
  *   drift    Pos[d] += Vel[d] * dt                     double
  *   totmass += Mass                                    double sum of float masses, in particle order, on the host
  * Positions are never wrapped: the cell is floor(Pos / CellSize) modulo Nmesh and the residual comes from the unwrapped quotient
- * (cic_setup, pm_readout.hpp), which is what the reference's min / max region folded periodically into the pencils amounts to.
+ * (cic_setup, cic.hpp), which is what the reference's min / max region folded periodically into the pencils amounts to.
  *
  * A force, with two meshes A and B of the call's own:
  *   A  zeroed, the fixed-point CIC deposit (64-bit integer atomics: the mesh does not depend on particle order or launch shape), the
@@ -31,7 +31,7 @@
  * Of the context only the FFT twiddle table is touched.
  */
 #include "common.hpp"
-#include "pm_readout.hpp"
+#include "mesh_common.hpp"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -52,31 +52,13 @@ __global__ __launch_bounds__(GT) void glass_deposit_kernel(long long n, const do
         return;
     int ic[3];
     double res[3];
-    for(int k = 0; k < 3; k++)
-        cic_setup(pos[3 * p + k], cell, N, ic[k], res[k]);
+    cic_cell3(pos[3 * p], pos[3 * p + 1], pos[3 * p + 2], cell, N, ic, res);
     const double m = (double) mass[p];
-#pragma unroll
-    for(int c = 0; c < 8; c++) {
-        double w = 1.0;
-        size_t lin = 0;
-#pragma unroll
-        for(int k = 0; k < 3; k++) {
-            const int off = (c >> k) & 1;
-            const int t = wrapi(ic[k] + off, N);
-            lin = lin * (size_t) (k == 2 ? zp : N) + (size_t) t;
-            w *= off ? res[k] : (1 - res[k]);
-        }
+    cic_corners(ic, res, N, zp, [&](int, size_t lin, double w) {
+#pragma clang fp contract(off)
         const long long q = __double2ll_rn(w * m * scale);
         atomicAdd(&mesh[lin], (unsigned long long) q);
-    }
-}
-
-/* the fixed-point mesh as doubles, for the hipFFT route (the five-pass pipeline converts in its first pass) */
-__global__ __launch_bounds__(GT) void glass_convert_kernel(double *mesh, size_t n, double inv_scale)
-{
-    const size_t i = (size_t) blockIdx.x * GT + threadIdx.x;
-    if(i < n)
-        mesh[i] = (double) reinterpret_cast<const long long *>(mesh)[i] * inv_scale;
+    });
 }
 
 /* powerspectrum_add_mode (gravpm.cpp:323-356) for both of the reference's callers in one read of the density spectrum [x][y][zpc]:
@@ -92,12 +74,10 @@ __global__ __launch_bounds__(GT) void glass_power_kernel(const double2 *__restri
     __syncthreads();
     const size_t total = (size_t) N * N * Nc;
     for(size_t ip = (size_t) blockIdx.x * GT + threadIdx.x; ip < total; ip += (size_t) gridDim.x * GT) {
-        const int z = (int) (ip % Nc);
-        const size_t xy = ip / Nc;
-        const int y = (int) (xy % N), x = (int) (xy / N);
-        const int kx = x <= N / 2 ? x : x - N, ky = y <= N / 2 ? y : y - N;
-        const long long k2 = (long long) kx * kx + (long long) ky * ky + (long long) z * z;
-        const double2 v = spec[xy * (size_t) zpc + z];
+        const HalfMode md = half_mode(ip, N);
+        const int x = md.x, y = md.y, z = md.z;
+        const long long k2 = md.k2;
+        const double2 v = spec[md.row * (size_t) zpc + z];
         const double m = v.x * v.x + v.y * v.y;
         if(k2 == 0) {
             sums[3 * nbins] = m; /* Norm: both callers write the same value */
@@ -133,11 +113,10 @@ __global__ __launch_bounds__(GT) void glass_transfer_kernel(const double2 *__res
     const size_t ip = (size_t) blockIdx.x * GT + threadIdx.x;
     if(ip >= total)
         return;
-    const int z = (int) (ip % Nc);
-    const size_t row = ip / Nc;
-    const int y = (int) (row % N), x = (int) (row / N);
-    const int kx = x <= N / 2 ? x : x - N, ky = y <= N / 2 ? y : y - N;
-    const long long k2 = (long long) kx * kx + (long long) ky * ky + (long long) z * z;
+    const HalfMode md = half_mode(ip, N);
+    const int x = md.x, y = md.y, z = md.z;
+    const long long k2 = md.k2;
+    const size_t row = md.row;
     double2 v = spec[row * zpc + z];
     if(k2 == 0)
         v = make_double2(0.0, 0.0);
@@ -164,22 +143,12 @@ __global__ __launch_bounds__(GT) void glass_gather_kernel(long long n, const dou
         return;
     int ic[3];
     double res[3];
-    for(int k = 0; k < 3; k++)
-        cic_setup(pos[3 * p + k], cell, N, ic[k], res[k]);
+    cic_cell3(pos[3 * p], pos[3 * p + 1], pos[3 * p + 2], cell, N, ic, res);
     float acc = 0;
-#pragma unroll
-    for(int c = 0; c < 8; c++) {
-        double w = 1.0;
-        size_t lin = 0;
-#pragma unroll
-        for(int k = 0; k < 3; k++) {
-            const int off = (c >> k) & 1;
-            const int t = wrapi(ic[k] + off, N);
-            lin = lin * (size_t) (k == 2 ? zp : N) + (size_t) t;
-            w *= off ? res[k] : (1 - res[k]);
-        }
+    cic_corners(ic, res, N, zp, [&](int, size_t lin, double w) {
+#pragma clang fp contract(off)
         acc = (float) ((double) acc + w * mesh[lin]);
-    }
+    });
     disp[3 * p + axis] = acc;
 }
 
@@ -228,63 +197,6 @@ __global__ __launch_bounds__(GT) void glass_particle_kernel(long long n, double 
             atomicAdd(&stats[threadIdx.x], t);
         }
     }
-}
-
-/* the call's device memory, plans and events: freed / destroyed after the stream has drained, on every way out */
-struct GlassScope {
-    shq_context *ctx;
-    std::vector<void *> bufs;
-    hipfftHandle plan_f = 0, plan_b = 0;
-    bool have_f = false, have_b = false;
-    std::vector<hipEvent_t> ev;
-    explicit GlassScope(shq_context *c) : ctx(c) {}
-    template <typename T> int alloc(T **p, size_t n)
-    {
-        *p = nullptr;
-        hipError_t e = hipMalloc((void **) p, (n ? n : 1) * sizeof(T));
-        if(e != hipSuccess) {
-            shq_set_error("glass: hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-            *p = nullptr;
-            return SHQ_ERR_NOMEM;
-        }
-        bufs.push_back((void *) *p);
-        return SHQ_OK;
-    }
-    int mark(hipStream_t s)
-    {
-        hipEvent_t e = nullptr;
-        SHQ_HIP(hipEventCreate(&e));
-        ev.push_back(e);
-        SHQ_HIP(hipEventRecord(e, s));
-        return SHQ_OK;
-    }
-    double ms(size_t a, size_t b) const
-    {
-        float t = 0;
-        if(hipEventElapsedTime(&t, ev[a], ev[b]) != hipSuccess)
-            t = 0;
-        return t;
-    }
-    ~GlassScope()
-    {
-        (void) hipStreamSynchronize(ctx->stream);
-        for(void *b : bufs)
-            (void) hipFree(b);
-        if(have_f)
-            hipfftDestroy(plan_f);
-        if(have_b)
-            hipfftDestroy(plan_b);
-        for(hipEvent_t e : ev)
-            (void) hipEventDestroy(e);
-    }
-};
-
-inline unsigned nblk(size_t n, int t) { return (unsigned) std::max<size_t>(1, (n + t - 1) / t); }
-
-int glass_check_mesh(int N)
-{
-    SHQ_CHECK(N >= 4 && N % 2 == 0 && N <= 2048, SHQ_ERR_INVALID, "glass: Nmesh must be even and in [4, 2048] (got %d)", N);
-    return SHQ_OK;
 }
 
 /* super lanzcos differencing, glass.cpp:319-327 */
@@ -359,7 +271,7 @@ extern "C" int shq_glass_evolve(shq_context *ctx, const shq_glass_params *p, int
     SHQ_CHECK(ctx && p && pos && vel && disp && mass, SHQ_ERR_INVALID, "glass: null argument");
     /* ---- every check before anything is written */
     const int N = p->Nmesh, nsteps = p->nsteps;
-    SHQ_TRY(glass_check_mesh(N));
+    SHQ_TRY(mesh_check_size(N, "glass"));
     SHQ_CHECK(nsteps >= 0, SHQ_ERR_INVALID, "glass: nsteps %d < 0", nsteps);
     const double L = p->BoxSize;
     SHQ_CHECK(isfinite(L) && L > 0, SHQ_ERR_INVALID, "glass: BoxSize must be finite and > 0");
@@ -406,11 +318,11 @@ extern "C" int shq_glass_evolve(shq_context *ctx, const shq_glass_params *p, int
     const double scale = ldexp(1.0, 61 - ex), inv_scale = ldexp(1.0, ex - 61);
 
     hipStream_t s = ctx->stream;
-    GlassScope sc(ctx);
+    CallScope sc(ctx, "glass");
     SHQ_TRY(sc.mark(s));
-    const bool bespoke = shq_fft3d_supported(N) && N % 8 == 0;
-    const int zp = bespoke ? shq_fft3d_pitch(N) : N + 2;
-    const size_t padded = (size_t) N * N * zp;
+    Fft3dRoute route = fft3d_route(N);
+    const int zp = route.zp;
+    const size_t padded = route.padded;
     const int nbins = N;
     const size_t nsums = 3 * (size_t) nbins + 1;
     const bool spectra = nspec == 4 && nsteps > 0;
@@ -446,36 +358,20 @@ extern "C" int shq_glass_evolve(shq_context *ctx, const shq_glass_params *p, int
     SHQ_HIP(hipMemcpyAsync(d_sinc, sinc.data(), sizeof(double) * N, hipMemcpyHostToDevice, s));
     SHQ_HIP(hipMemsetAsync(d_stats, 0, sizeof(double) * 2 * std::max(nsteps, 1), s));
     SHQ_HIP(hipMemsetAsync(d_B, 0, sizeof(double) * padded, s)); /* the pitch's padding is never written again */
-    if(!bespoke) {
-        hipfftResult r = hipfftPlan3d(&sc.plan_f, N, N, N, HIPFFT_D2Z);
-        SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "glass: hipfftPlan3d(D2Z, %d) failed: %d", N, (int) r);
-        sc.have_f = true;
-        r = hipfftPlan3d(&sc.plan_b, N, N, N, HIPFFT_Z2D);
-        SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "glass: hipfftPlan3d(Z2D, %d) failed: %d", N, (int) r);
-        sc.have_b = true;
-        SHQ_CHECK(hipfftSetStream(sc.plan_f, s) == HIPFFT_SUCCESS && hipfftSetStream(sc.plan_b, s) == HIPFFT_SUCCESS, SHQ_ERR_DEVICE,
-                  "glass: hipfftSetStream failed");
-    }
+    SHQ_TRY(route_plans(sc, route, true, true));
     SHQ_TRY(sc.mark(s)); /* ev[1]: uploaded */
 
     const size_t modes = (size_t) N * N * (N / 2 + 1);
     const size_t lds = sizeof(double) * 3 * nbins; /* <= 48 KiB at Nmesh 2048 */
-    const dim3 gp(nblk((size_t) n, GT)), gm(nblk(modes, GT)), gk(std::min(nblk((size_t) n, GT), 2048u));
+    const dim3 gp(nblk(n, GT)), gm(nblk((long long) modes, GT)), gk(std::min(nblk(n, GT), 2048u));
     /* glass_force (glass.cpp:184-216); sums: where this force's power sums go, or null */
     auto force = [&](double *sums) -> int {
         SHQ_HIP(hipMemsetAsync(d_A, 0, sizeof(double) * padded, s));
         glass_deposit_kernel<<<gp, dim3(GT), 0, s>>>(n, d_pos, d_mass, reinterpret_cast<unsigned long long *>(d_A), N, zp, cellsize, scale);
         SHQ_HIP(hipGetLastError());
-        if(bespoke)
-            SHQ_TRY(shq_fft3d_run(ctx, d_A, N, zp, 0, true, inv_scale, nullptr, 0, 0));
-        else {
-            glass_convert_kernel<<<dim3(nblk(padded, GT)), dim3(GT), 0, s>>>(d_A, padded, inv_scale);
-            SHQ_HIP(hipGetLastError());
-            const hipfftResult r = hipfftExecD2Z(sc.plan_f, (hipfftDoubleReal *) d_A, (hipfftDoubleComplex *) d_A);
-            SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "glass: hipfftExecD2Z failed: %d", (int) r);
-        }
+        SHQ_TRY(route_forward(ctx, sc, route, d_A, true, inv_scale));
         if(sums) {
-            glass_power_kernel<<<dim3((unsigned) std::min<size_t>(1024, nblk(modes, GT))), dim3(GT), lds, s>>>(
+            glass_power_kernel<<<dim3((unsigned) std::min<size_t>(1024, nblk((long long) modes, GT))), dim3(GT), lds, s>>>(
                 reinterpret_cast<const double2 *>(d_A), N, zp / 2, d_sinc, d_bintab, sums);
             SHQ_HIP(hipGetLastError());
         }
@@ -483,12 +379,7 @@ extern "C" int shq_glass_evolve(shq_context *ctx, const shq_glass_params *p, int
             glass_transfer_kernel<<<gm, dim3(GT), 0, s>>>(reinterpret_cast<const double2 *>(d_A), reinterpret_cast<double2 *>(d_B), N, zp / 2,
                                                          d_fac, axis, pot_factor);
             SHQ_HIP(hipGetLastError());
-            if(bespoke)
-                SHQ_TRY(shq_fft3d_run(ctx, d_B, N, zp, 1, false, 1.0, nullptr, 0, 0));
-            else {
-                const hipfftResult r = hipfftExecZ2D(sc.plan_b, (hipfftDoubleComplex *) d_B, (hipfftDoubleReal *) d_B);
-                SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "glass: hipfftExecZ2D failed: %d", (int) r);
-            }
+            SHQ_TRY(route_inverse(ctx, sc, route, d_B));
             glass_gather_kernel<<<gp, dim3(GT), 0, s>>>(n, d_pos, d_B, N, zp, cellsize, d_disp, axis);
             SHQ_HIP(hipGetLastError());
         }

@@ -32,7 +32,7 @@
  * every particle is heated once, from its own slot's Density); the gas tree is assumed to hold every live gas particle, as the tree of
  * run.cpp:482 / 624 does (the walk would miss one that is not in it).
  */
-#include "common.hpp"
+#include "call_scope.hpp"
 #include <rocprim/device/device_partition.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
@@ -245,35 +245,7 @@ struct HitBefore {    /* first hit among the bubbles the loop ran */
     __device__ bool operator()(const int32_t &h) const { return h >= 0 && h < kstop; }
 };
 
-inline unsigned nblk(long long n) { return (unsigned) ((n + HT - 1) / HT); }
-
-/* the call's device buffers and events, freed on every return */
-struct HeScope {
-    std::vector<void *> bufs;
-    hipEvent_t ev[6] = {};
-    template <typename T> int alloc(T **p, size_t n)
-    {
-        *p = nullptr;
-        hipError_t e = hipMalloc((void **) p, sizeof(T) * std::max<size_t>(n, 1));
-        if(e != hipSuccess) {
-            *p = nullptr;
-            shq_set_error("heiii: hipMalloc of %zu bytes failed: %s", sizeof(T) * std::max<size_t>(n, 1), hipGetErrorString(e));
-            return SHQ_ERR_NOMEM;
-        }
-        bufs.push_back((void *) *p);
-        return SHQ_OK;
-    }
-    ~HeScope()
-    {
-        for(void *b : bufs)
-            (void) hipFree(b);
-        for(hipEvent_t e : ev)
-            if(e)
-                (void) hipEventDestroy(e);
-    }
-};
-
-template <typename Pred> int select_indices(shq_context *ctx, HeScope &sc, long long n, Pred pred, int32_t *out, unsigned long long *d_count, int64_t *m)
+template <typename Pred> int select_indices(shq_context *ctx, CallScope &sc, long long n, Pred pred, int32_t *out, unsigned long long *d_count, int64_t *m)
 {
     *m = 0;
     if(n <= 0)
@@ -289,14 +261,6 @@ template <typename Pred> int select_indices(shq_context *ctx, HeScope &sc, long 
     *m = (int64_t) h;
     (void) sc;
     return SHQ_OK;
-}
-
-float ev_ms(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0;
-    if(hipEventElapsedTime(&ms, a, b) != hipSuccess)
-        ms = 0;
-    return ms;
 }
 
 } // namespace
@@ -332,10 +296,8 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
     shq_heiii_stats st;
     memset(&st, 0, sizeof(st));
     hipStream_t s = ctx->stream;
-    HeScope sc;
-    for(hipEvent_t &e : sc.ev)
-        SHQ_HIP(hipEventCreate(&e));
-    SHQ_HIP(hipEventRecord(sc.ev[0], s));
+    CallScope sc(ctx, "heiii");
+    SHQ_TRY(sc.mark(s));
     unsigned long long *d_cnt;
     SHQ_TRY(sc.alloc(&d_cnt, 2));
 
@@ -350,7 +312,7 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
         SHQ_TRY(select_indices(ctx, sc, TotNgroups, InWindow{ctx->fof_groups.ptr, p->qso_candidate_min_mass, p->qso_candidate_max_mass}, gidx, d_cnt, &K));
         SHQ_TRY(sc.alloc(&rows, (size_t) K));
         if(K > 0) {
-            heiii_cand_kernel<<<dim3(nblk(K)), dim3(HT), 0, s>>>(K, gidx, ctx->fof_groups.ptr, rows);
+            heiii_cand_kernel<<<dim3(nblk(K, HT)), dim3(HT), 0, s>>>(K, gidx, ctx->fof_groups.ptr, rows);
             SHQ_HIP(hipGetLastError());
             cand.resize((size_t) K);
             SHQ_HIP(hipMemcpyAsync(cand.data(), rows, sizeof(CandRow) * (size_t) K, hipMemcpyDeviceToHost, s));
@@ -383,7 +345,7 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
         int64_t nf = 0;
         SHQ_TRY(select_indices(ctx, sc, n, Flashable{d_flags}, fidx, d_cnt, &nf));
         if(nf > 0) {
-            heiii_apply_idx_kernel<<<dim3(nblk(nf)), dim3(HT), 0, s>>>(nf, fidx, d_flags, d_entropy, d_density, a3inv, du, d_rows);
+            heiii_apply_idx_kernel<<<dim3(nblk(nf, HT)), dim3(HT), 0, s>>>(nf, fidx, d_flags, d_entropy, d_density, a3inv, du, d_rows);
             SHQ_HIP(hipGetLastError());
         }
         nrows = nf;
@@ -393,7 +355,7 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
     /* ---- gas_ionization_fraction (:330-346) and the bubble-count threshold (:514-518) */
     SHQ_HIP(hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), s));
     if(n > 0) {
-        heiii_count_kernel<<<dim3(nblk(n)), dim3(HT), 0, s>>>(n, d_flags, d_cnt);
+        heiii_count_kernel<<<dim3(nblk(n, HT)), dim3(HT), 0, s>>>(n, d_flags, d_cnt);
         SHQ_HIP(hipGetLastError());
     }
     unsigned long long nion0 = 0;
@@ -427,13 +389,13 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
         SHQ_TRY(sc.alloc(&d_bub, HEIII_MAX_BATCH));
         SHQ_TRY(sc.alloc(&d_counts, HEIII_MAX_BATCH));
         if(m > 0) {
-            heiii_gather_kernel<<<dim3(nblk(m)), dim3(HT), 0, s>>>(m, eidx, ctx->posm.ptr, E[0]);
+            heiii_gather_kernel<<<dim3(nblk(m, HT)), dim3(HT), 0, s>>>(m, eidx, ctx->posm.ptr, E[0]);
             SHQ_HIP(hipGetLastError());
         }
         st.neligible = m;
-        SHQ_HIP(hipEventRecord(sc.ev[1], s));
-        SHQ_HIP(hipEventSynchronize(sc.ev[1]));
-        st.ms[0] = ev_ms(sc.ev[0], sc.ev[1]);
+        SHQ_TRY(sc.mark(s));
+        SHQ_HIP(hipEventSynchronize(sc.ev.back()));
+        st.ms[0] = sc.last_ms();
         int cur = 0;
         bool tree_ready = false;
 
@@ -498,22 +460,22 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
                     const long long nn = ctx->numnodes;
                     SHQ_TRY(sc.alloc(&d_nfather, (size_t) nn));
                     SHQ_HIP(hipMemsetAsync(d_nfather, 0xff, sizeof(int32_t) * (size_t) nn, s));
-                    heiii_node_father_kernel<<<dim3(nblk(nn)), dim3(HT), 0, s>>>(nn, ctx->nodeC.ptr, d_nfather);
+                    heiii_node_father_kernel<<<dim3(nblk(nn, HT)), dim3(HT), 0, s>>>(nn, ctx->nodeC.ptr, d_nfather);
                     SHQ_HIP(hipGetLastError());
                     tree_ready = true;
                 }
                 SHQ_HIP(hipMemcpyAsync(d_bub, hb.data(), sizeof(Bubble) * (size_t) L, hipMemcpyHostToDevice, s));
                 SHQ_HIP(hipMemsetAsync(d_counts, 0, sizeof(unsigned long long) * (size_t) L, s));
-                SHQ_HIP(hipEventRecord(sc.ev[2], s));
-                const unsigned g = std::min<unsigned>(nblk(m), HEIII_SWEEP_BLOCKS);
+                SHQ_TRY(sc.mark(s));
+                const unsigned g = std::min<unsigned>(nblk(m, HT), HEIII_SWEEP_BLOCKS);
                 heiii_sweep_kernel<<<dim3(g), dim3(HT), sizeof(unsigned) * (size_t) L, s>>>(
                     m, E[cur], d_bub, L, p->BoxSize, tree_ready ? ctx->nodeB.ptr : nullptr, d_nfather, tree_ready ? ctx->pfather.ptr : nullptr, d_hit,
                     d_counts);
                 SHQ_HIP(hipGetLastError());
-                SHQ_HIP(hipEventRecord(sc.ev[3], s));
+                SHQ_TRY(sc.mark(s));
                 SHQ_HIP(hipMemcpyAsync(counts.data(), d_counts, sizeof(unsigned long long) * (size_t) L, hipMemcpyDeviceToHost, s));
                 SHQ_HIP(hipStreamSynchronize(s));
-                st.ms[1] += ev_ms(sc.ev[2], sc.ev[3]);
+                st.ms[1] += sc.last_ms();
                 st.ntests += (int64_t) m * L;
             }
             if(st.nsweeps < SHQ_HEIII_NSTAT) {
@@ -560,7 +522,7 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
                 }
             }
             /* ---- flag and heat the particles whose first hit the loop reached; the rest stay eligible */
-            SHQ_HIP(hipEventRecord(sc.ev[2], s));
+            SHQ_TRY(sc.mark(s));
             if(kstop > 0 && m > 0) {
                 size_t tmp = 0;
                 auto flags = rocprim::make_transform_iterator(d_hit, HitBefore{kstop});
@@ -571,7 +533,7 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
                 SHQ_HIP(hipMemcpyAsync(&nsel, d_cnt, sizeof(nsel), hipMemcpyDeviceToHost, s));
                 SHQ_HIP(hipStreamSynchronize(s));
                 if(nsel > 0) {
-                    heiii_apply_rec_kernel<<<dim3(nblk((long long) nsel)), dim3(HT), 0, s>>>((long long) nsel, S, d_flags, d_entropy, d_density, a3inv,
+                    heiii_apply_rec_kernel<<<dim3(nblk((long long) nsel, HT)), dim3(HT), 0, s>>>((long long) nsel, S, d_flags, d_entropy, d_density, a3inv,
                                                                                          du, d_rows + nrows);
                     SHQ_HIP(hipGetLastError());
                 }
@@ -579,9 +541,9 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
                 m -= (int64_t) nsel;
                 cur ^= 1;
             }
-            SHQ_HIP(hipEventRecord(sc.ev[3], s));
-            SHQ_HIP(hipEventSynchronize(sc.ev[3]));
-            st.ms[2] += ev_ms(sc.ev[2], sc.ev[3]);
+            SHQ_TRY(sc.mark(s));
+            SHQ_HIP(hipEventSynchronize(sc.ev.back()));
+            st.ms[2] += sc.last_ms();
             batch = std::min(2 * batch, HEIII_MAX_BATCH);
         }
         SHQ_CHECK(tot_n_ionized == nrows - result->n_flash, SHQ_ERR_STATE, "heiii: %ld particles counted, %ld flagged", (long) tot_n_ionized,
@@ -597,7 +559,7 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
     std::vector<double2> rows((size_t) std::max<int64_t>(nrows, 1));
     if(nrows > 0)
         SHQ_HIP(hipMemcpyAsync(rows.data(), d_rows, sizeof(double2) * (size_t) nrows, hipMemcpyDeviceToHost, s));
-    SHQ_HIP(hipEventRecord(sc.ev[5], s));
+    SHQ_TRY(sc.mark(s));
     SHQ_HIP(hipStreamSynchronize(s));
     for(int64_t r = 0; r < nrows; r++) {
         const int64_t i = (int64_t) rows[(size_t) r].x;
@@ -606,7 +568,7 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
         const int32_t pi = *reinterpret_cast<const int32_t *>(rec + parts->off_pi);
         *reinterpret_cast<double *>(static_cast<char *>(sph->base) + (size_t) pi * sph->elsize + sph->off_entropy) = rows[(size_t) r].y;
     }
-    st.ms[3] = ev_ms(sc.ev[0], sc.ev[5]);
+    st.ms[3] = sc.ms(0, sc.ev.size() - 1);
     ctx->heiii_stats = st;
     return SHQ_OK;
 }

@@ -15,7 +15,7 @@
  * grid3d_ngb, bit for bit.  The bin edges and widths are made on the host with linspace's expressions.
  * The call allocates everything it uses and frees it before it returns: nothing of the context's state is touched.
  */
-#include "common.hpp"
+#include "mesh_common.hpp"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -291,86 +291,12 @@ __global__ __launch_bounds__(LT) void lens_bilinear_kernel(double *dst, int R, c
     }
 }
 
-/* the call's device memory, plans and events: freed / destroyed after the stream has drained, on every way out */
-struct LensScope {
-    shq_context *ctx;
-    std::vector<void *> bufs;
-    std::vector<hipfftHandle> plans;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    explicit LensScope(shq_context *c) : ctx(c) {}
-    template <typename T> int alloc(T **p, size_t n)
-    {
-        *p = nullptr;
-        hipError_t e = hipMalloc((void **) p, (n ? n : 1) * sizeof(T));
-        if(e != hipSuccess) {
-            shq_set_error("lens: hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-            *p = nullptr;
-            return SHQ_ERR_NOMEM;
-        }
-        bufs.push_back((void *) *p);
-        return SHQ_OK;
-    }
-    int plan(int R, hipfftType type, int batch, hipfftHandle *h)
-    {
-        int n[2] = {R, R};
-        const hipfftResult r = hipfftPlanMany(h, 2, n, nullptr, 1, 0, nullptr, 1, 0, type, batch);
-        SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "lens: hipfftPlanMany(%d x %d, batch %d) failed: %d", R, R, batch, (int) r);
-        plans.push_back(*h);
-        SHQ_CHECK(hipfftSetStream(*h, ctx->stream) == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "lens: hipfftSetStream failed");
-        return SHQ_OK;
-    }
-    ~LensScope()
-    {
-        (void) hipStreamSynchronize(ctx->stream);
-        for(void *b : bufs)
-            (void) hipFree(b);
-        for(hipfftHandle h : plans)
-            hipfftDestroy(h);
-        for(hipEvent_t &e : ev)
-            if(e)
-                (void) hipEventDestroy(e);
-    }
-};
-
-/* the particles' positions and flag bytes: the resident set, or staged into the call's own buffers */
-int lens_particles(shq_context *ctx, LensScope &sc, const shq_part_view *parts, const double4 **d_posm, const uint8_t **d_flags)
+/* the particles' positions and flag bytes (stage_part_view); the binning reads IsGarbage and Swallowed, so a staged view needs the flag word */
+int lens_particles(shq_context *ctx, CallScope &sc, const shq_part_view *parts, const double4 **d_posm, const uint8_t **d_flags)
 {
-    const long long n = parts->numpart;
-    SHQ_CHECK(n >= 0 && n < (1ll << 32) && (n == 0 || parts->base), SHQ_ERR_INVALID, "lens: bad particle view (numpart %lld; < 2^32 per rank)", n);
-    const bool resident = (ctx->inputs_current & SHQ_CURRENT_PARTICLES) && ctx->have_parts && ctx->have_types && ctx->cur_parts == parts->base &&
-                          ctx->cur_parts_n == n && ctx->numpart == n;
-    if(resident) {
-        *d_posm = ctx->posm.ptr;
-        *d_flags = ctx->pflags.ptr;
-        return SHQ_OK;
-    }
-    SHQ_CHECK(parts->off_pos != SHQ_NOFIELD && parts->off_type != SHQ_NOFIELD && parts->off_flags != SHQ_NOFIELD, SHQ_ERR_INVALID,
-              "lens: the particle view needs Pos, Type and the flag word");
-    double4 *pm4;
-    uint8_t *fl;
-    SHQ_TRY(sc.alloc(&pm4, (size_t) n));
-    SHQ_TRY(sc.alloc(&fl, (size_t) n));
-    std::vector<double4> h4((size_t) n);
-    std::vector<uint8_t> hf((size_t) n);
-    const char *b = (const char *) parts->base;
-    bool finite = true;
-    for(long long i = 0; i < n; i++) {
-        const char *r = b + (size_t) i * parts->elsize;
-        const double *pos = (const double *) (r + parts->off_pos);
-        h4[i] = make_double4(pos[0], pos[1], pos[2], 0.0);
-        /* the context's flag-byte layout (shq_particles_upload): IsGarbage, Swallowed, HeIIIionized; Type in bits 4-7 */
-        hf[i] = (uint8_t) (((*(const uint8_t *) (r + parts->off_type) & 0xf) << 4) | (*(const uint8_t *) (r + parts->off_flags) & 7u));
-        finite = finite && isfinite(pos[0]) && isfinite(pos[1]) && isfinite(pos[2]);
-    }
-    SHQ_CHECK(finite, SHQ_ERR_INVALID, "lens: non-finite particle position");
-    if(n > 0) {
-        SHQ_HIP(hipMemcpyAsync(pm4, h4.data(), sizeof(double4) * n, hipMemcpyHostToDevice, ctx->stream));
-        SHQ_HIP(hipMemcpyAsync(fl, hf.data(), (size_t) n, hipMemcpyHostToDevice, ctx->stream));
-    }
-    SHQ_HIP(hipStreamSynchronize(ctx->stream)); /* the host vectors go out of scope */
-    *d_posm = pm4;
-    *d_flags = fl;
-    return SHQ_OK;
+    SHQ_CHECK(parts_resident(ctx, parts) || (parts->off_pos != SHQ_NOFIELD && parts->off_type != SHQ_NOFIELD && parts->off_flags != SHQ_NOFIELD),
+              SHQ_ERR_INVALID, "lens: the particle view needs Pos, Type and the flag word");
+    return stage_part_view(ctx, sc, parts, false, d_posm, d_flags);
 }
 
 /* linspace (lenstools.cpp:39-44), entry i */
@@ -423,27 +349,21 @@ int lens_cuts(const shq_lens_params *p, double *th, int64_t *ncuts)
     return SHQ_OK;
 }
 
-float ev_ms(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0;
-    if(hipEventElapsedTime(&ms, a, b) != hipSuccess)
-        ms = 0;
-    return ms;
-}
-
-inline unsigned nblk(long long n, long long cap = 1ll << 30) { return (unsigned) std::max<long long>(1, std::min<long long>((n + LT - 1) / LT, cap)); }
+/* a grid-stride launch: no more than cap blocks */
+inline unsigned nblk_cap(long long n, long long cap) { return (unsigned) std::min<long long>(nblk(n, LT), cap); }
 
 /* calculate_lensing_potential on nplanes real planes [nplanes][R][R] at dens, through the half spectra at spec, into out */
-int lens_solve(LensScope &sc, int R, int nplanes, double *dens, double2 *spec, double *out, const LensSolve *d_sp)
+int lens_solve(CallScope &sc, int R, int nplanes, double *dens, double2 *spec, double *out, const LensSolve *d_sp)
 {
     hipfftHandle f, b;
-    SHQ_TRY(sc.plan(R, HIPFFT_D2Z, nplanes, &f));
-    SHQ_TRY(sc.plan(R, HIPFFT_Z2D, nplanes, &b));
+    int dims[2] = {R, R};
+    SHQ_TRY(sc.plan_many(2, dims, HIPFFT_D2Z, nplanes, &f));
+    SHQ_TRY(sc.plan_many(2, dims, HIPFFT_Z2D, nplanes, &b));
     hipfftResult r = hipfftExecD2Z(f, (hipfftDoubleReal *) dens, (hipfftDoubleComplex *) spec);
     SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "lens: hipfftExecD2Z failed: %d", (int) r);
     const long long nspec = (long long) R * (R / 2 + 1) * nplanes;
     const double g2 = (2.0 * M_PI * 1.0) * (2.0 * M_PI * 1.0); /* (2 pi smooth)^2, smooth = 1 */
-    lens_filter_kernel<<<dim3(nblk(nspec, 4096)), dim3(LT), 0, sc.ctx->stream>>>(spec, R, nplanes, d_sp, g2);
+    lens_filter_kernel<<<dim3(nblk_cap(nspec, 4096)), dim3(LT), 0, sc.ctx->stream>>>(spec, R, nplanes, d_sp, g2);
     SHQ_HIP(hipGetLastError());
     r = hipfftExecZ2D(b, (hipfftDoubleComplex *) spec, (hipfftDoubleReal *) out);
     SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "lens: hipfftExecZ2D failed: %d", (int) r);
@@ -476,7 +396,7 @@ extern "C" int shq_lens_count_active(shq_context *ctx, const shq_part_view *part
 {
     SHQ_CHECK(ctx && parts && count, SHQ_ERR_INVALID, "lens: null argument");
     SHQ_HIP(hipSetDevice(ctx->device));
-    LensScope sc(ctx);
+    CallScope sc(ctx, "lens");
     const double4 *d_posm;
     const uint8_t *d_flags;
     SHQ_TRY(lens_particles(ctx, sc, parts, &d_posm, &d_flags));
@@ -551,10 +471,8 @@ extern "C" int shq_lens_planes(shq_context *ctx, const shq_lens_params *p, const
     for(int64_t k = 0; k < ncuts; k++)
         cutv[k] = p->ncuts > 0 ? p->CutPoints[k] : (.5 + k) * th;
     hipStream_t s = ctx->stream;
-    LensScope sc(ctx);
-    for(hipEvent_t &e : sc.ev)
-        SHQ_HIP(hipEventCreate(&e));
-    SHQ_HIP(hipEventRecord(sc.ev[0], s));
+    CallScope sc(ctx, "lens");
+    SHQ_TRY(sc.mark(s));
 
     /* ---- the particle pass */
     const double4 *d_posm;
@@ -593,7 +511,7 @@ extern "C" int shq_lens_planes(shq_context *ctx, const shq_lens_params *p, const
     if(n > 0)
         lens_bin_kernel<<<dim3(nblk(n)), dim3(LT), 0, s>>>(n, d_posm, d_flags, g, d_cuts, d_counts, d_nact);
     SHQ_HIP(hipGetLastError());
-    SHQ_HIP(hipEventRecord(sc.ev[1], s));
+    SHQ_TRY(sc.mark(s)); /* ev[1]: the particle pass */
 
     /* ---- counts -> density and the plane sums; the 2-D solves of all particle planes in one batch */
     const double H0 = 100 * c->HubbleParam * 3.2407793e-20;
@@ -616,7 +534,7 @@ extern "C" int shq_lens_planes(shq_context *ctx, const shq_lens_params *p, const
     SHQ_TRY(sc.alloc(&d_spec, (size_t) P * R * (R / 2 + 1)));
     SHQ_TRY(sc.alloc(&d_sp, (size_t) P));
     SHQ_HIP(hipMemcpyAsync(d_dnf, dnf.data(), sizeof(double) * P, hipMemcpyHostToDevice, s));
-    lens_density_kernel<<<dim3(nblk((long long) plane, 256), (unsigned) P), dim3(LT), 0, s>>>(d_counts, plane, d_dnf, d_dens, d_psum);
+    lens_density_kernel<<<dim3(nblk_cap((long long) plane, 256), (unsigned) P), dim3(LT), 0, s>>>(d_counts, plane, d_dnf, d_dens, d_psum);
     SHQ_HIP(hipGetLastError());
     std::vector<unsigned long long> psum((size_t) P);
     SHQ_HIP(hipMemcpyAsync(psum.data(), d_psum, sizeof(unsigned long long) * P, hipMemcpyDeviceToHost, s));
@@ -626,7 +544,7 @@ extern "C" int shq_lens_planes(shq_context *ctx, const shq_lens_params *p, const
         sp[q] = {(L / R) * (L / R) / (chi * chi), cosmo_normalization * density_normalization / (double) (R * R), psum[q] == 0, 0};
     SHQ_HIP(hipMemcpyAsync(d_sp, sp.data(), sizeof(LensSolve) * P, hipMemcpyHostToDevice, s));
     SHQ_TRY(lens_solve(sc, R, (int) P, d_dens, d_spec, d_out, d_sp));
-    SHQ_HIP(hipEventRecord(sc.ev[2], s));
+    SHQ_TRY(sc.mark(s)); /* ev[2]: the particle planes solved */
 
     /* ---- the PM neutrino correction: project per distinct normal, solve at Nmesh, add bilinearly */
     if(nu) {
@@ -669,10 +587,10 @@ extern "C" int shq_lens_planes(shq_context *ctx, const shq_lens_params *p, const
             csp[q] = {cellsize * cellsize / (chi * chi), cosmo_normalization * density_normalization / (double) (N * N), 0, 0};
         SHQ_HIP(hipMemcpyAsync(d_csp, csp.data(), sizeof(LensSolve) * P, hipMemcpyHostToDevice, s));
         SHQ_TRY(lens_solve(sc, N, (int) P, d_proj, d_cspec, d_corr, d_csp));
-        lens_bilinear_kernel<<<dim3(nblk((long long) P * plane, 4096)), dim3(LT), 0, s>>>(d_out, R, d_corr, N, P);
+        lens_bilinear_kernel<<<dim3(nblk_cap((long long) P * plane, 4096)), dim3(LT), 0, s>>>(d_out, R, d_corr, N, P);
         SHQ_HIP(hipGetLastError());
     }
-    SHQ_HIP(hipEventRecord(sc.ev[3], s));
+    SHQ_TRY(sc.mark(s)); /* ev[3]: the correction added */
 
     /* ---- out: [cut][requested normal]; repeated normals share their plane */
     for(int64_t k = 0; k < ncuts; k++)
@@ -683,11 +601,11 @@ extern "C" int shq_lens_planes(shq_context *ctx, const shq_lens_params *p, const
                 SHQ_HIP(hipMemcpyAsync(counts + o * plane, d_counts + q * plane, sizeof(uint32_t) * plane, hipMemcpyDeviceToHost, s));
             num_particles_plane[o] = (int64_t) psum[q];
         }
-    SHQ_HIP(hipEventRecord(sc.ev[4], s));
+    SHQ_TRY(sc.mark(s)); /* ev[4]: downloaded */
     SHQ_HIP(hipStreamSynchronize(s));
-    ctx->lens_ms[0] = ev_ms(sc.ev[0], sc.ev[1]);
-    ctx->lens_ms[1] = ev_ms(sc.ev[1], sc.ev[2]);
-    ctx->lens_ms[2] = ev_ms(sc.ev[2], sc.ev[3]);
-    ctx->lens_ms[3] = ev_ms(sc.ev[0], sc.ev[4]);
+    ctx->lens_ms[0] = sc.ms(0, 1);
+    ctx->lens_ms[1] = sc.ms(1, 2);
+    ctx->lens_ms[2] = sc.ms(2, 3);
+    ctx->lens_ms[3] = sc.ms(0, 4);
     return SHQ_OK;
 }

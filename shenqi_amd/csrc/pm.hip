@@ -18,7 +18,7 @@
  *    which the readout kernel applies in real space while gathering: 2 FFTs instead of 5.
  * All arithmetic is f64.
  */
-#include "common.hpp"
+#include "mesh_common.hpp"
 #include "pm_readout.hpp"
 #include <math.h>
 #include <stdlib.h>
@@ -199,15 +199,6 @@ __global__ __launch_bounds__(256) void pm_deposit_kernel(const double4 *__restri
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
     }
-}
-
-__global__ void pm_convert_kernel(double *mesh, size_t n, double inv_scale)
-{
-    size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x;
-    const size_t stride = (size_t) gridDim.x * blockDim.x;
-    long long *im = reinterpret_cast<long long *>(mesh);
-    for(; i < n; i += stride)
-        mesh[i] = (double) im[i] * inv_scale;
 }
 
 /* potential_transfer, gravpm.cpp:378-444, on the [x][y][z'] half spectrum */
@@ -756,7 +747,7 @@ int shq_pm_execute(shq_context *ctx, const shq_pm_params *pm, bool readout)
         SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 3], ctx->stream));
         SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 4], ctx->stream));
     } else {
-        pm_convert_kernel<<<dim3(2048), dim3(threads), 0, ctx->stream>>>(ctx->mesh.ptr, padded, 1.0 / scale);
+        mesh_convert_i64_kernel<<<dim3(2048), dim3(threads), 0, ctx->stream>>>(ctx->mesh.ptr, padded, 1.0 / scale);
         SHQ_HIP(hipGetLastError());
         SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 1], ctx->stream));
         hipfftSetStream(ctx->plan_r2c, ctx->stream);
@@ -808,7 +799,7 @@ int shq_pm_execute_forward(shq_context *ctx, const shq_pm_params *pm)
         SHQ_TRY(pm_power_sweep(ctx, N, zp / 2));
     } else {
         route = 2;
-        pm_convert_kernel<<<dim3(2048), dim3(256), 0, ctx->stream>>>(ctx->mesh.ptr, (size_t) N * N * zp, inv_scale);
+        mesh_convert_i64_kernel<<<dim3(2048), dim3(256), 0, ctx->stream>>>(ctx->mesh.ptr, (size_t) N * N * zp, inv_scale);
         SHQ_HIP(hipGetLastError());
         hipfftSetStream(ctx->plan_r2c, ctx->stream);
         hipfftResult r = hipfftExecD2Z(ctx->plan_r2c, (hipfftDoubleReal *) ctx->mesh.ptr, (hipfftDoubleComplex *) ctx->mesh.ptr);

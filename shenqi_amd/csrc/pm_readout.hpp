@@ -2,32 +2,10 @@
  * real-space image of the reference's k-space difference kernel, see pm.hip), shared by pm_readout_kernel (pm.hip) and by the
  * tree walk's task prologue (grav_walk.hip, shq_treepm_step), so that both produce the same bits. */
 #pragma once
-#include "common.hpp"
+#include "cic.hpp"
 #ifndef SHQ_READOUT_FENCE
 #define SHQ_READOUT_FENCE 1 /* load grouping of the lean readout's common path, see pm_readout_corner: 2 (a stencil at a time, 64 VGPRs) measured no faster than 1 (62) */
 #endif
-
-__device__ __forceinline__ int wrapi(int i, int N) { return i >= N ? i - N : (i < 0 ? i + N : i); }
-/* x-plane index into the (possibly slab-local) mesh: global plane gx -> (gx - xshift) mod N.
- * xshift = 0 for the full periodic mesh; for a slab it is the global index of local plane 0. */
-__device__ __forceinline__ int xloc(int gx, int xshift, int N)
-{
-    int v = (gx - xshift) % N;
-    return v < 0 ? v + N : v;
-}
-
-/* CIC cell + residual: petapm.cpp:1147-1160 */
-__device__ __forceinline__ void cic_setup(double p, double cell, int N, int &ic, double &res)
-{
-    const double tmp = p / cell; /* a true divide, as petapm.cpp:1148, so cells/weights match bit for bit */
-    const double fl = floor(tmp);
-    res = tmp - fl;
-    int i = (int) fl;
-    i %= N;
-    if(i < 0)
-        i += N;
-    ic = i;
-}
 
 /* One corner c = (a, b, e) of the CIC cube: weight, potential and the three differenced force components, accumulated in the
  * order c = 0..7 — THE operation order of the readout (pm_readout_kernel's paired-load path fetches the same values and applies

@@ -13,8 +13,6 @@
 
 namespace {
 
-inline unsigned nblk(long long n, int t = 256) { return (unsigned) ((n + t - 1) / t); }
-
 __global__ void gas_scatter_kernel(long long n, const double *__restrict__ rows, double4 *posm, uint8_t *pflags, double *vel, double *hsml,
                                    double *treeacc, double *gravpm, double *hacc, double *entropy, double *dtentropy, double *delay,
                                    double *density, double *egywt, double *dhsmlegy, double *divvel, double *curlvel, double *maxsig,

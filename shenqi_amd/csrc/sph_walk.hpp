@@ -854,8 +854,6 @@ __device__ __forceinline__ unsigned int heavy_block(const SphDev &a, HbShared &s
     return nint;
 }
 
-inline unsigned nblk(long long n, int t = 256) { return (unsigned) ((n + t - 1) / t); }
-
 inline SphDev make_dev(shq_context *ctx, double Box)
 {
     SphDev a;

@@ -17,8 +17,6 @@
 
 namespace {
 
-inline unsigned nblk(long long n, int t = 256) { return (unsigned) ((n + t - 1) / t); }
-
 constexpr int TB = SHQ_TIMEBINS;
 constexpr long long TIMEBASE = 1ll << TB;
 

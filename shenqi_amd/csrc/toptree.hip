@@ -20,8 +20,6 @@
 
 namespace {
 
-inline unsigned nblk(long long n, int t = 256) { return (unsigned) ((n + t - 1) / t); }
-
 enum { TOP_INTERNAL = 0, TOP_LOCAL_LEAF = 1, TOP_PSEUDO = 2 };
 
 __device__ __forceinline__ double nearest(double x, double Box) /* NEAREST, partmanager.h:99 */

@@ -565,8 +565,6 @@ __global__ void tb_father_kernel(long long np, long long firstnode, const int32_
         out[i] = pfather[i] >= 0 ? (int32_t) (firstnode + pfather[i]) : -1;
 }
 
-inline unsigned nblk(long long n, int t = 256) { return (unsigned) ((n + t - 1) / t); }
-
 int reserve_nodes(shq_context *ctx, size_t cap)
 {
     TreeBuildBufs &b = ctx->tb;

@@ -12,8 +12,7 @@
  * Mesh sizes the bespoke pipeline does not have go through hipFFT plans of the call's own with a filter kernel between them.
  * The call allocates everything it uses and frees it before it returns: nothing of the context's PM state is touched.
  */
-#include "common.hpp"
-#include "pm_readout.hpp"
+#include "mesh_common.hpp"
 #include <future>
 #include <math.h>
 #include <string.h>
@@ -122,19 +121,8 @@ __global__ __launch_bounds__(UV_T) void uvbg_deposit_kernel(long long n, const d
     const double s = gas ? sfr[i] : 0.0;
     int ic[3];
     double res[3];
-    cic_setup(p.x, cell, N, ic[0], res[0]);
-    cic_setup(p.y, cell, N, ic[1], res[1]);
-    cic_setup(p.z, cell, N, ic[2], res[2]);
-#pragma unroll
-    for(int c = 0; c < 8; c++) {
-        double w = 1.0;
-        size_t lin = 0;
-#pragma unroll
-        for(int k = 0; k < 3; k++) {
-            const int off = (c >> k) & 1;
-            lin = lin * (size_t) (k == 2 ? zp : N) + (size_t) wrapi(ic[k] + off, N);
-            w *= off ? res[k] : (1 - res[k]);
-        }
+    cic_cell3(p.x, p.y, p.z, cell, N, ic, res);
+    cic_corners(ic, res, N, zp, [&](int, size_t lin, double w) {
         const long long q0 = __double2ll_rn(w * p.w * sc0);
         if(q0)
             atomicAdd(&m0[lin], (unsigned long long) q0);
@@ -148,15 +136,7 @@ __global__ __launch_bounds__(UV_T) void uvbg_deposit_kernel(long long n, const d
             if(q)
                 atomicAdd(&m2[lin], (unsigned long long) q);
         }
-    }
-}
-
-/* hipFFT route: the int64 deposit to doubles, in place */
-__global__ void uvbg_convert_kernel(double *mesh, size_t n, double inv_scale)
-{
-    long long *im = reinterpret_cast<long long *>(mesh);
-    for(size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x)
-        mesh[i] = (double) im[i] * inv_scale;
+    });
 }
 
 /* hipFFT route: divide_by_ncell then filter_pm on the kept [x][y][z'] half spectrum, into the field's mesh */
@@ -167,9 +147,7 @@ __global__ void uvbg_filter_kernel(const double2 *__restrict__ spec, double2 *ou
     const size_t n = (size_t) N * N * Nc;
     const double nc = (double) ncell;
     for(size_t i = (size_t) blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t) gridDim.x * blockDim.x) {
-        const int z = (int) (i % Nc), y = (int) ((i / Nc) % N), x = (int) (i / ((size_t) Nc * N));
-        const int kx = x <= N / 2 ? x : x - N, ky = y <= N / 2 ? y : y - N;
-        const double T = fac[(kx * kx + ky * ky + z * z) & fac_mask];
+        const double T = fac[(int) half_mode(i, N).k2 & fac_mask];
         const double2 v = spec[i];
         out[i] = make_double2((v.x / nc) * T, (v.y / nc) * T);
     }
@@ -250,59 +228,20 @@ __global__ __launch_bounds__(UV_T) void uvbg_readout_kernel(long long n, const d
     const double4 p = posm[i];
     int ic[3];
     double res[3];
-    cic_setup(p.x, cell, N, ic[0], res[0]);
-    cic_setup(p.y, cell, N, ic[1], res[1]);
-    cic_setup(p.z, cell, N, ic[2], res[2]);
+    cic_cell3(p.x, p.y, p.z, cell, N, ic, res);
     double lj = 0.0; /* init_particle_uvbg's reset */
     double zr = zreion[i];
-    for(int c = 0; c < 8; c++) {
-        const size_t lin = ((size_t) wrapi(ic[0] + (c & 1), N) * N + (size_t) wrapi(ic[1] + ((c >> 1) & 1), N)) * N +
-                           (size_t) wrapi(ic[2] + ((c >> 2) & 1), N);
+    cic_corners(ic, res, N, N, [&](int, size_t lin, double) { /* the grid is dense [N]^3; the weight plays no part */
         const double v = (double) J21[lin];
         if(v > lj) {
             lj = v;
             if(zr == -1)
                 zr = zre_now;
         }
-    }
+    });
     local_J21[i] = lj;
     zreion[i] = zr;
 }
-
-/* the call's device memory and events: freed / destroyed after the stream has drained, on every way out */
-struct UvbgScope {
-    shq_context *ctx;
-    std::vector<void *> bufs;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipfftHandle r2c = 0, c2r = 0;
-    bool plans = false;
-    explicit UvbgScope(shq_context *c) : ctx(c) {}
-    template <typename T> int alloc(T **p, size_t n)
-    {
-        *p = nullptr;
-        hipError_t e = hipMalloc((void **) p, (n ? n : 1) * sizeof(T));
-        if(e != hipSuccess) {
-            shq_set_error("uvbg: hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-            *p = nullptr;
-            return SHQ_ERR_NOMEM;
-        }
-        bufs.push_back((void *) *p);
-        return SHQ_OK;
-    }
-    ~UvbgScope()
-    {
-        (void) hipStreamSynchronize(ctx->stream);
-        for(void *b : bufs)
-            (void) hipFree(b);
-        for(hipEvent_t &e : ev)
-            if(e)
-                (void) hipEventDestroy(e);
-        if(plans) {
-            hipfftDestroy(r2c);
-            hipfftDestroy(c2r);
-        }
-    }
-};
 
 } // namespace
 
@@ -383,10 +322,8 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
     const long long n = parts->numpart;
     SHQ_CHECK(n >= 0 && n < (1ll << 31) && (n == 0 || parts->base), SHQ_ERR_INVALID, "uvbg: bad particle view");
     SHQ_HIP(hipSetDevice(ctx->device));
-    const bool resident = (ctx->inputs_current & SHQ_CURRENT_PARTICLES) && ctx->have_parts && ctx->have_types && ctx->cur_parts == parts->base &&
-                          ctx->cur_parts_n == n && ctx->numpart == n;
-    SHQ_CHECK(resident || (parts->off_pos != SHQ_NOFIELD && parts->off_mass != SHQ_NOFIELD && parts->off_type != SHQ_NOFIELD), SHQ_ERR_INVALID,
-              "uvbg: the particle view needs Pos, Mass and Type");
+    SHQ_CHECK(parts_resident(ctx, parts) || (parts->off_pos != SHQ_NOFIELD && parts->off_mass != SHQ_NOFIELD && parts->off_type != SHQ_NOFIELD),
+              SHQ_ERR_INVALID, "uvbg: the particle view needs Pos, Mass and Type");
     /* the radius schedule of petapm_reion_c2r (petapm.cpp:536-606) */
     std::vector<double> radii;
     const double cell = p->BoxSize / N; /* pm->CellSize, petapm.cpp:205 */
@@ -417,46 +354,17 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
                 (void) shq_uvbg_filter_table(p->ReionFilterType, N, p->BoxSize, radii[r], tabs.data() + (size_t) r * ntab);
         });
     hipStream_t s = ctx->stream;
-    UvbgScope sc(ctx);
-    for(hipEvent_t &e : sc.ev)
-        SHQ_HIP(hipEventCreate(&e));
-    SHQ_HIP(hipEventRecord(sc.ev[0], s));
+    CallScope sc(ctx, "uvbg");
+    SHQ_TRY(sc.mark(s));
 
     /* ---- particles: the resident set, or staged into the call's own buffers */
     const size_t np = (size_t) (n > 0 ? n : 1);
     const double4 *d_posm;
     const uint8_t *d_flags;
-    if(resident) {
-        d_posm = ctx->posm.ptr;
-        d_flags = ctx->pflags.ptr;
-    } else {
-        double4 *pm4;
-        uint8_t *fl;
-        SHQ_TRY(sc.alloc(&pm4, np));
-        SHQ_TRY(sc.alloc(&fl, np));
-        std::vector<double4> h4((size_t) n);
-        std::vector<uint8_t> hf((size_t) n);
-        const char *b = (const char *) parts->base;
-        bool finite = true;
-        for(long long i = 0; i < n; i++) {
-            const char *r = b + (size_t) i * parts->elsize;
-            const double *pos = (const double *) (r + parts->off_pos);
-            h4[i] = make_double4(pos[0], pos[1], pos[2], (double) *(const float *) (r + parts->off_mass));
-            hf[i] = (uint8_t) ((*(const uint8_t *) (r + parts->off_type) & 0xf) << 4);
-            finite = finite && isfinite(pos[0]) && isfinite(pos[1]) && isfinite(pos[2]);
-        }
-        SHQ_CHECK(finite, SHQ_ERR_INVALID, "uvbg: non-finite particle position");
-        if(n > 0) {
-            SHQ_HIP(hipMemcpyAsync(pm4, h4.data(), sizeof(double4) * n, hipMemcpyHostToDevice, s));
-            SHQ_HIP(hipMemcpyAsync(fl, hf.data(), (size_t) n, hipMemcpyHostToDevice, s));
-        }
-        SHQ_HIP(hipStreamSynchronize(s)); /* the host vectors go out of scope */
-        d_posm = pm4;
-        d_flags = fl;
-    }
+    SHQ_TRY(stage_part_view(ctx, sc, parts, true, &d_posm, &d_flags));
     double *d_fesc, *d_sfr = nullptr, *d_lj, *d_zr, *d_part, *d_sums;
     int *d_neg;
-    const int pblocks = (int) std::min<long long>(1024, (n + UV_T - 1) / UV_T > 0 ? (n + UV_T - 1) / UV_T : 1);
+    const int pblocks = (int) std::min(1024u, nblk(n, UV_T));
     SHQ_TRY(sc.alloc(&d_fesc, np));
     SHQ_TRY(sc.alloc(&d_lj, np));
     SHQ_TRY(sc.alloc(&d_zr, np));
@@ -490,9 +398,10 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
 
     /* ---- meshes: per field the deposit / kept spectrum and the real mesh of the radius, one scratch mesh; the grids */
     const int nf = use_sfr ? 3 : 2;
-    const bool bespoke = shq_fft3d_supported(N) && N % 8 == 0;
-    const int zp = bespoke ? shq_fft3d_pitch(N) : N + 2;
-    const size_t padded = (size_t) N * N * zp, dense = (size_t) N * N * N;
+    Fft3dRoute route = fft3d_route(N);
+    const bool bespoke = route.bespoke; /* this side is uvbg's own: the transposing pipeline with the filter in it */
+    const int zp = route.zp;
+    const size_t padded = route.padded, dense = (size_t) N * N * N;
     double *spec[3] = {nullptr, nullptr, nullptr}, *real[3] = {nullptr, nullptr, nullptr}, *scratch = nullptr, *d_tw = nullptr;
     for(int f = 0; f < nf; f++) {
         SHQ_TRY(sc.alloc(&spec[f], padded));
@@ -503,17 +412,8 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
         SHQ_TRY(sc.alloc(&scratch, padded));
         SHQ_TRY(sc.alloc(&d_tw, 2 * (size_t) N));
         SHQ_TRY(shq_fft3d_fill_twiddles(N, d_tw));
-    } else {
-        hipfftResult r = hipfftPlan3d(&sc.r2c, N, N, N, HIPFFT_D2Z);
-        SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "uvbg: hipfftPlan3d(D2Z, %d) failed: %d", N, (int) r);
-        r = hipfftPlan3d(&sc.c2r, N, N, N, HIPFFT_Z2D);
-        if(r != HIPFFT_SUCCESS)
-            hipfftDestroy(sc.r2c);
-        SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "uvbg: hipfftPlan3d(Z2D, %d) failed: %d", N, (int) r);
-        sc.plans = true;
-        hipfftSetStream(sc.r2c, s);
-        hipfftSetStream(sc.c2r, s);
     }
+    SHQ_TRY(route_plans(sc, route, true, true));
     float *d_j21, *d_xhi;
     SHQ_TRY(sc.alloc(&d_j21, dense));
     SHQ_TRY(sc.alloc(&d_xhi, dense));
@@ -529,7 +429,7 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
         inv_scale[f] = ldexp(1.0, ex - 61);
     }
     if(n > 0)
-        uvbg_deposit_kernel<<<dim3((unsigned) ((n + UV_T - 1) / UV_T)), dim3(UV_T), 0, s>>>(
+        uvbg_deposit_kernel<<<dim3(nblk(n, UV_T)), dim3(UV_T), 0, s>>>(
             n, d_posm, d_flags, d_fesc, d_sfr, use_sfr, N, zp, cell, scale[0], scale[1], scale[2], (unsigned long long *) spec[0],
             (unsigned long long *) spec[1], use_sfr ? (unsigned long long *) spec[2] : nullptr);
     SHQ_HIP(hipGetLastError());
@@ -540,12 +440,11 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
         if(bespoke)
             SHQ_TRY(shq_fft3d_filter_part(ctx, d_tw, spec[f], scratch, nullptr, N, zp, 1, inv_scale[f], nullptr, 0, ncell));
         else {
-            uvbg_convert_kernel<<<dim3(2048), dim3(UV_T), 0, s>>>(spec[f], padded, inv_scale[f]);
-            const hipfftResult r = hipfftExecD2Z(sc.r2c, (hipfftDoubleReal *) spec[f], (hipfftDoubleComplex *) spec[f]);
-            SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "uvbg: hipfftExecD2Z failed: %d", (int) r);
+            mesh_convert_i64_kernel<<<dim3(2048), dim3(UV_T), 0, s>>>(spec[f], padded, inv_scale[f]);
+            SHQ_TRY(route_hipfft_forward(sc, route, spec[f]));
         }
     }
-    SHQ_HIP(hipEventRecord(sc.ev[1], s));
+    SHQ_TRY(sc.mark(s)); /* ev[1]: deposited and transformed */
 
     /* ---- the filter tables from the host threads */
     for(auto &t : tables)
@@ -583,8 +482,7 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
                 SHQ_TRY(shq_fft3d_filter_part(ctx, d_tw, spec[f], scratch, real[f], N, zp, 3, 1.0, fac, mask, ncell));
             else {
                 uvbg_filter_kernel<<<dim3(2048), dim3(UV_T), 0, s>>>((const double2 *) spec[f], (double2 *) real[f], N, fac, mask, ncell);
-                const hipfftResult rr = hipfftExecZ2D(sc.c2r, (hipfftDoubleComplex *) real[f], (hipfftDoubleReal *) real[f]);
-                SHQ_CHECK(rr == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "uvbg: hipfftExecZ2D failed: %d", (int) rr);
+                SHQ_TRY(route_hipfft_inverse(sc, route, real[f]));
             }
         }
         c.R = R;
@@ -597,11 +495,11 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
         SHQ_HIP(hipGetLastError());
     }
     uvbg_sum_kernel<<<dim3(1), dim3(UV_T), 0, s>>>(d_part, cblocks, d_sums);
-    SHQ_HIP(hipEventRecord(sc.ev[2], s));
+    SHQ_TRY(sc.mark(s)); /* ev[2]: the radius loop */
 
     /* ---- readout_J21, then the particles' results */
     if(n > 0)
-        uvbg_readout_kernel<<<dim3((unsigned) ((n + UV_T - 1) / UV_T)), dim3(UV_T), 0, s>>>(n, d_posm, d_flags, d_j21, N, cell, 1 / cp->Time - 1,
+        uvbg_readout_kernel<<<dim3(nblk(n, UV_T)), dim3(UV_T), 0, s>>>(n, d_posm, d_flags, d_j21, N, cell, 1 / cp->Time - 1,
                                                                                            d_lj, d_zr);
     SHQ_HIP(hipGetLastError());
     SHQ_HIP(hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, s));
@@ -617,7 +515,7 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
         SHQ_HIP(hipMemcpyAsync(ctx->uvbg_j21.data(), d_j21, sizeof(float) * dense, hipMemcpyDeviceToHost, s));
         SHQ_HIP(hipMemcpyAsync(ctx->uvbg_xhi.data(), d_xhi, sizeof(float) * dense, hipMemcpyDeviceToHost, s));
     }
-    SHQ_HIP(hipEventRecord(sc.ev[3], s));
+    SHQ_TRY(sc.mark(s)); /* ev[3]: read out and downloaded */
     SHQ_HIP(hipStreamSynchronize(s));
     if(ctx->uvbg_keep)
         ctx->uvbg_n = N;
@@ -625,11 +523,8 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
     result->mass_weighted_global_xHI = sums[1] / sums[2];
     result->nradii = nr;
     result->pad_ = 0;
-    float ms = 0;
     const int from[4] = {0, 1, 2, 0}, to[4] = {1, 2, 3, 3};
-    for(int i = 0; i < 4; i++) {
-        SHQ_HIP(hipEventElapsedTime(&ms, sc.ev[from[i]], sc.ev[to[i]]));
-        ctx->uvbg_ms[i] = ms;
-    }
+    for(int i = 0; i < 4; i++)
+        ctx->uvbg_ms[i] = sc.ms(from[i], to[i]);
     return SHQ_OK;
 }

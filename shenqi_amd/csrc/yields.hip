@@ -16,7 +16,6 @@ template <typename T> inline T *sfield(const shq_star_yield_view *v, int64_t slo
 {
     return reinterpret_cast<T *>(static_cast<char *>(v->base) + (size_t) slot * v->elsize + off);
 }
-inline unsigned nblk(int64_t n) { return (unsigned) ((n + 255) / 256); }
 
 enum { YIN_MASS = 0, YIN_FORMATION, YIN_LASTENRICH, YIN_TMR, YIN_METALLICITY, YIN_NCOL };
 enum { YOUT_AGE = 0, YOUT_LOW, YOUT_HIGH, YOUT_MASSRETURN, YOUT_LASTENRICH, YOUT_NCOL };
@@ -378,7 +377,8 @@ extern "C" int shq_metal_return_postprocess(shq_context *ctx, const shq_part_vie
     SHQ_TRY(ctx->yld_i32.reserve(NQ));
     SHQ_HIP(hipMemcpyAsync(ctx->yld_out.ptr, rows.data(), sizeof(double) * rows.size(), hipMemcpyHostToDevice, st));
     SHQ_HIP(hipMemcpyAsync(ctx->yld_i32.ptr, queue, sizeof(int32_t) * NQ, hipMemcpyHostToDevice, st));
-    /* the context's copy of these very particles follows the masses */
+    /* the context's copy of these very particles follows the masses; laxer than parts_resident on purpose: a copy that is not vouched
+     * for is uploaded again before anybody reads it, and the masses need no types */
     const bool resident = ctx->have_parts && ctx->cur_parts == parts->base && ctx->cur_parts_n == n && ctx->numpart == n;
     yields_postprocess_kernel<<<dim3(nblk(nqueue)), dim3(256), 0, st>>>((long long) nqueue, ctx->yld_i32.ptr, ctx->yld_out.ptr, resident ? ctx->posm.ptr : nullptr);
     SHQ_HIP(hipGetLastError());

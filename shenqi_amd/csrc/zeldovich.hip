@@ -22,7 +22,7 @@
  * pm_iterate_one's weights.  A last kernel does the particle loop and the two max reductions.
  * The call owns every buffer it uses; of the context it touches only the resident field and the FFT twiddle table.
  */
-#include "common.hpp"
+#include "mesh_common.hpp"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
@@ -220,11 +220,9 @@ __global__ __launch_bounds__(ZT) void zel_transfer_kernel(const double2 *__restr
     const size_t ip = (size_t) blockIdx.x * ZT + threadIdx.x;
     if(ip >= total)
         return;
-    const int z = (int) (ip % Nc);
-    const size_t row = ip / Nc;
-    const int y = (int) (row % N), x = (int) (row / N);
-    const int kpos[3] = {x <= N / 2 ? x : x - N, y <= N / 2 ? y : y - N, z};
-    const long long k2 = (long long) kpos[0] * kpos[0] + (long long) kpos[1] * kpos[1] + (long long) kpos[2] * kpos[2];
+    const HalfMode md = half_mode(ip, N);
+    const int kpos[3] = {md.kx, md.ky, md.z};
+    const long long k2 = md.k2;
     double2 v = spec[ip];
     if(k2) {
         if(axis < 0) {
@@ -239,7 +237,7 @@ __global__ __launch_bounds__(ZT) void zel_transfer_kernel(const double2 *__restr
             v.y = tmp * fac;
         }
     }
-    out[row * zpc + z] = v;
+    out[md.row * zpc + md.z] = v;
 }
 
 /* pm_iterate_one (petapm.cpp:1153-1177) with the readout functions: out[p] = sum over the 8 connections, in their order, of weight * mesh */
@@ -250,26 +248,16 @@ __global__ __launch_bounds__(ZT) void zel_readout_kernel(long long n, const doub
     const long long p = (long long) blockIdx.x * ZT + threadIdx.x;
     if(p >= n)
         return;
-    int cell[3];
+    /* positions are in [0, BoxSize), so the cell is in [0, N]: N itself where Pos / CellSize rounds up to N, which is cell 0 with
+     * residual 0 (the region's padding cells are the periodic images) */
+    int ic[3];
     double res[3];
-    for(int k = 0; k < 3; k++) {
-        const double tmp = pos[3 * p + k] / cellsize;
-        const double f = floor(tmp);
-        res[k] = tmp - f;
-        cell[k] = (int) f;
-    }
+    cic_cell3(pos[3 * p], pos[3 * p + 1], pos[3 * p + 2], cellsize, N, ic, res);
     double acc = 0;
-    for(int connection = 0; connection < 8; connection++) {
-        double weight = 1.0;
-        int idx[3];
-        for(int k = 0; k < 3; k++) {
-            const int offset = (connection >> k) & 1;
-            const int t = cell[k] + offset;
-            idx[k] = t >= N ? t - N : t; /* the region's padding cells are the periodic images */
-            weight *= offset ? res[k] : (1 - res[k]);
-        }
-        acc += weight * mesh[((size_t) idx[0] * N + idx[1]) * zp + idx[2]];
-    }
+    cic_corners(ic, res, N, zp, [&](int, size_t lin, double weight) {
+#pragma clang fp contract(off)
+        acc += weight * mesh[lin];
+    });
     out[p] = acc;
 }
 
@@ -320,55 +308,6 @@ __global__ __launch_bounds__(ZT) void zel_finalize_kernel(long long n, const dou
         atomicMax(&mx[threadIdx.x], s[threadIdx.x]);
 }
 
-/* the call's device memory, plan and events: freed / destroyed after the stream has drained, on every way out */
-struct ZelScope {
-    shq_context *ctx;
-    std::vector<void *> bufs;
-    hipfftHandle plan = 0;
-    bool have_plan = false;
-    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    explicit ZelScope(shq_context *c) : ctx(c) {}
-    template <typename T> int alloc(T **p, size_t n)
-    {
-        *p = nullptr;
-        hipError_t e = hipMalloc((void **) p, (n ? n : 1) * sizeof(T));
-        if(e != hipSuccess) {
-            shq_set_error("zeldovich: hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-            *p = nullptr;
-            return SHQ_ERR_NOMEM;
-        }
-        bufs.push_back((void *) *p);
-        return SHQ_OK;
-    }
-    ~ZelScope()
-    {
-        (void) hipStreamSynchronize(ctx->stream);
-        for(void *b : bufs)
-            (void) hipFree(b);
-        if(have_plan)
-            hipfftDestroy(plan);
-        for(hipEvent_t &e : ev)
-            if(e)
-                (void) hipEventDestroy(e);
-    }
-};
-
-float ev_ms(hipEvent_t a, hipEvent_t b)
-{
-    float ms = 0;
-    if(hipEventElapsedTime(&ms, a, b) != hipSuccess)
-        ms = 0;
-    return ms;
-}
-
-inline unsigned nblk(size_t n, int t) { return (unsigned) std::max<size_t>(1, (n + t - 1) / t); }
-
-int zel_check_mesh(int N)
-{
-    SHQ_CHECK(N >= 4 && N % 2 == 0 && N <= 2048, SHQ_ERR_INVALID, "zeldovich: Nmesh must be even and in [4, 2048] (got %d)", N);
-    return SHQ_OK;
-}
-
 /* SETSEED and the eight loops of pmesh.h:18-41, 81-90 on one rank (ORegion = the whole mesh) */
 void zel_seed_table(int N, int Seed, uint32_t *t00, uint32_t *t11)
 {
@@ -408,7 +347,7 @@ int zel_ensure_field(shq_context *ctx, int N, int Seed, int unitary, int invert,
     SHQ_TRY(ctx->zel_spec.reserve(NN * Nc * 2));
     std::vector<uint32_t> t00(NN), t11(NN);
     zel_seed_table(N, Seed, t00.data(), t11.data());
-    ZelScope sc(ctx);
+    CallScope sc(ctx, "zeldovich");
     const long long ncol = (long long) NN;
     long long chunk = ctx->zel_chunk > 0 ? ctx->zel_chunk : ZEL_CHUNK;
     chunk = std::min(ncol, (chunk + ZW - 1) / ZW * ZW);
@@ -423,7 +362,7 @@ int zel_ensure_field(shq_context *ctx, int N, int Seed, int unitary, int invert,
     for(int pass = 0; pass < 2; pass++)
         for(long long c0 = 0; c0 < ncol; c0 += chunk) {
             const long long c1 = std::min(ncol, c0 + chunk);
-            const dim3 grid(nblk((size_t) (c1 - c0), ZW));
+            const dim3 grid(nblk(c1 - c0, ZW));
             if(pass == 0)
                 zel_fill_kernel<false><<<grid, dim3(ZW), 0, s>>>(N, c0, c1, d_t00, d_ws, unitary, invert, spec);
             else
@@ -462,7 +401,7 @@ void zel_density_table(int N, double L, const double *delta, double *dens)
 extern "C" int shq_zeldovich_seed_table(int Nmesh, int Seed, uint32_t *table00, uint32_t *table11)
 {
     SHQ_CHECK(table00 && table11, SHQ_ERR_INVALID, "zeldovich: null argument");
-    SHQ_TRY(zel_check_mesh(Nmesh));
+    SHQ_TRY(mesh_check_size(Nmesh, "zeldovich"));
     zel_seed_table(Nmesh, Seed, table00, table11);
     return SHQ_OK;
 }
@@ -472,7 +411,7 @@ extern "C" int shq_zeldovich_factor_tables(int Nmesh, double BoxSize, const doub
 {
 #pragma clang fp contract(off)
     SHQ_CHECK(delta && dens_fac && disp_fac && (!vel_fac || growth), SHQ_ERR_INVALID, "zeldovich: null argument");
-    SHQ_TRY(zel_check_mesh(Nmesh));
+    SHQ_TRY(mesh_check_size(Nmesh, "zeldovich"));
     SHQ_CHECK(isfinite(BoxSize) && BoxSize > 0, SHQ_ERR_INVALID, "zeldovich: BoxSize must be finite and > 0");
     const long long nk2 = 3ll * (Nmesh / 2) * (Nmesh / 2) + 1;
     zel_density_table(Nmesh, BoxSize, delta, dens_fac);
@@ -508,7 +447,7 @@ extern "C" int shq_zeldovich_drop_field(shq_context *ctx)
 extern "C" int shq_zeldovich_fill(shq_context *ctx, int Nmesh, int Seed, int UnitaryAmplitude, int InvertPhase)
 {
     SHQ_CHECK(ctx, SHQ_ERR_INVALID, "null context");
-    SHQ_TRY(zel_check_mesh(Nmesh));
+    SHQ_TRY(mesh_check_size(Nmesh, "zeldovich"));
     SHQ_HIP(hipSetDevice(ctx->device));
     bool filled;
     return zel_ensure_field(ctx, Nmesh, Seed, UnitaryAmplitude != 0, InvertPhase != 0, &filled);
@@ -522,10 +461,10 @@ extern "C" int shq_zeldovich_download_field(shq_context *ctx, int Nmesh, double 
     SHQ_HIP(hipSetDevice(ctx->device));
     const int N = Nmesh, Nc = N / 2 + 1;
     const size_t modes = (size_t) N * N * Nc;
-    ZelScope sc(ctx);
+    CallScope sc(ctx, "zeldovich");
     double2 *d_out;
     SHQ_TRY(sc.alloc(&d_out, modes));
-    zel_layout_kernel<<<dim3(nblk(modes, ZT)), dim3(ZT), 0, ctx->stream>>>(reinterpret_cast<const double2 *>(ctx->zel_spec.ptr), d_out, N, Nc);
+    zel_layout_kernel<<<dim3(nblk((long long) modes, ZT)), dim3(ZT), 0, ctx->stream>>>(reinterpret_cast<const double2 *>(ctx->zel_spec.ptr), d_out, N, Nc);
     SHQ_HIP(hipGetLastError());
     SHQ_HIP(hipMemcpyAsync(complx, d_out, sizeof(double2) * modes, hipMemcpyDeviceToHost, ctx->stream));
     SHQ_HIP(hipStreamSynchronize(ctx->stream));
@@ -546,8 +485,8 @@ extern "C" int shq_zeldovich_column_draws(shq_context *ctx, int n, const uint32_
     SHQ_CHECK(ctx && raw && pairs && (seeds || states), SHQ_ERR_INVALID, "zeldovich: null argument");
     SHQ_CHECK(n >= 1 && n <= 65536 && m >= 2 && m <= (1 << 20) && m % 2 == 0, SHQ_ERR_INVALID, "zeldovich_column_draws: n %d, m %d", n, m);
     SHQ_HIP(hipSetDevice(ctx->device));
-    ZelScope sc(ctx);
-    const unsigned nb = nblk((size_t) n, ZW);
+    CallScope sc(ctx, "zeldovich");
+    const unsigned nb = nblk(n, ZW);
     uint32_t *d_in, *d_ws, *d_raw;
     double *d_pairs;
     const size_t nin = states ? (size_t) n * MT_N : (size_t) n;
@@ -573,7 +512,7 @@ extern "C" int shq_zeldovich_displacements(shq_context *ctx, const shq_zeldovich
     SHQ_CHECK(ctx && p && delta && pos_out && vel && density && maxdisp && maxvel, SHQ_ERR_INVALID, "zeldovich: null argument");
     /* ---- every check before anything is written */
     const int N = p->Nmesh;
-    SHQ_TRY(zel_check_mesh(N));
+    SHQ_TRY(mesh_check_size(N, "zeldovich"));
     const double L = p->BoxSize;
     SHQ_CHECK(isfinite(L) && L > 0 && isfinite(p->vel_prefac), SHQ_ERR_INVALID, "zeldovich: BoxSize must be finite and > 0, vel_prefac finite");
     const int scaledep = p->ScaleDepVelocity != 0;
@@ -590,21 +529,19 @@ extern "C" int shq_zeldovich_displacements(shq_context *ctx, const shq_zeldovich
         ctx->zel_ms[i] = 0;
 
     hipStream_t s = ctx->stream;
-    ZelScope sc(ctx);
-    for(hipEvent_t &e : sc.ev)
-        SHQ_HIP(hipEventCreate(&e));
-    SHQ_HIP(hipEventRecord(sc.ev[0], s));
+    CallScope sc(ctx, "zeldovich");
+    SHQ_TRY(sc.mark(s));
     bool filled = false;
     SHQ_TRY(zel_ensure_field(ctx, N, p->Seed, p->UnitaryAmplitude != 0, p->InvertPhase != 0, &filled));
-    SHQ_HIP(hipEventRecord(sc.ev[1], s));
+    SHQ_TRY(sc.mark(s)); /* ev[1]: the field is resident */
 
     /* ---- tables, particles, the work mesh */
     std::vector<double> dens((size_t) nk2);
     zel_density_table(N, L, delta, dens.data());
     const double c0 = 1. / (2 * M_PI) / libm_sqrt(L);
-    const bool bespoke = shq_fft3d_supported(N) && N % 8 == 0;
-    const int zp = bespoke ? shq_fft3d_pitch(N) : N + 2;
-    const size_t padded = (size_t) N * N * zp;
+    Fft3dRoute route = fft3d_route(N);
+    const int zp = route.zp;
+    const size_t padded = route.padded;
     const int nfields = scaledep ? 7 : 4;
     double *d_dens, *d_delta, *d_growth = nullptr, *d_mesh, *d_pos, *d_fld, *d_out;
     unsigned long long *d_mx;
@@ -625,12 +562,7 @@ extern "C" int shq_zeldovich_displacements(shq_context *ctx, const shq_zeldovich
         SHQ_HIP(hipMemcpyAsync(d_pos, pos, sizeof(double) * 3 * n, hipMemcpyHostToDevice, s));
     SHQ_HIP(hipMemsetAsync(d_mesh, 0, sizeof(double) * padded, s)); /* the pitch's padding is never written again */
     SHQ_HIP(hipMemsetAsync(d_mx, 0, sizeof(unsigned long long) * 2, s));
-    if(!bespoke) {
-        const hipfftResult r = hipfftPlan3d(&sc.plan, N, N, N, HIPFFT_Z2D);
-        SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "zeldovich: hipfftPlan3d(Z2D, %d) failed: %d", N, (int) r);
-        sc.have_plan = true;
-        SHQ_CHECK(hipfftSetStream(sc.plan, s) == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "zeldovich: hipfftSetStream failed");
-    }
+    SHQ_TRY(route_plans(sc, route, false, true));
 
     /* ---- per field: transfer, c2r, readout (zeldovich.cpp:183-192: Density, DispX/Y/Z, VelX/Y/Z) */
     const size_t modes = (size_t) N * N * (N / 2 + 1);
@@ -638,27 +570,22 @@ extern "C" int shq_zeldovich_displacements(shq_context *ctx, const shq_zeldovich
     for(int f = 0; f < nfields; f++) {
         const int axis = f == 0 ? -1 : (f - 1) % 3;
         const double *tab = f == 0 ? d_dens : (f < 4 ? d_delta : d_growth);
-        zel_transfer_kernel<<<dim3(nblk(modes, ZT)), dim3(ZT), 0, s>>>(reinterpret_cast<const double2 *>(ctx->zel_spec.ptr),
+        zel_transfer_kernel<<<dim3(nblk((long long) modes, ZT)), dim3(ZT), 0, s>>>(reinterpret_cast<const double2 *>(ctx->zel_spec.ptr),
                                                                       reinterpret_cast<double2 *>(d_mesh), N, zp / 2, tab, axis, c0);
         SHQ_HIP(hipGetLastError());
-        if(bespoke)
-            SHQ_TRY(shq_fft3d_run(ctx, d_mesh, N, zp, 1, false, 1.0, nullptr, 0, 0));
-        else {
-            const hipfftResult r = hipfftExecZ2D(sc.plan, (hipfftDoubleComplex *) d_mesh, (hipfftDoubleReal *) d_mesh);
-            SHQ_CHECK(r == HIPFFT_SUCCESS, SHQ_ERR_DEVICE, "zeldovich: hipfftExecZ2D failed: %d", (int) r);
-        }
+        SHQ_TRY(route_inverse(ctx, sc, route, d_mesh));
         if(n > 0)
-            zel_readout_kernel<<<dim3(nblk((size_t) n, ZT)), dim3(ZT), 0, s>>>(n, d_pos, d_mesh, N, zp, cellsize, d_fld + (size_t) f * n);
+            zel_readout_kernel<<<dim3(nblk(n, ZT)), dim3(ZT), 0, s>>>(n, d_pos, d_mesh, N, zp, cellsize, d_fld + (size_t) f * n);
         SHQ_HIP(hipGetLastError());
     }
-    SHQ_HIP(hipEventRecord(sc.ev[2], s));
+    SHQ_TRY(sc.mark(s)); /* ev[2]: the fields are read out */
 
     /* ---- the particle loop and the two maxima */
     if(n > 0)
-        zel_finalize_kernel<<<dim3(nblk((size_t) n, ZT)), dim3(ZT), 0, s>>>(n, d_pos, d_fld, scaledep, p->vel_prefac, L, d_out, d_out + 3 * n,
+        zel_finalize_kernel<<<dim3(nblk(n, ZT)), dim3(ZT), 0, s>>>(n, d_pos, d_fld, scaledep, p->vel_prefac, L, d_out, d_out + 3 * n,
                                                                            d_out + 6 * n, d_mx);
     SHQ_HIP(hipGetLastError());
-    SHQ_HIP(hipEventRecord(sc.ev[3], s));
+    SHQ_TRY(sc.mark(s)); /* ev[3]: the particle loop */
     unsigned long long mx[2] = {0, 0};
     SHQ_HIP(hipMemcpyAsync(mx, d_mx, sizeof(mx), hipMemcpyDeviceToHost, s));
     if(n > 0) {
@@ -668,13 +595,13 @@ extern "C" int shq_zeldovich_displacements(shq_context *ctx, const shq_zeldovich
         if(disp)
             SHQ_HIP(hipMemcpyAsync(disp, d_out + 6 * n, sizeof(double) * 3 * n, hipMemcpyDeviceToHost, s));
     }
-    SHQ_HIP(hipEventRecord(sc.ev[4], s));
+    SHQ_TRY(sc.mark(s)); /* ev[4]: downloaded */
     SHQ_HIP(hipStreamSynchronize(s));
     memcpy(maxdisp, &mx[0], sizeof(double));
     memcpy(maxvel, &mx[1], sizeof(double));
-    ctx->zel_ms[0] = filled ? ev_ms(sc.ev[0], sc.ev[1]) : 0.0;
-    ctx->zel_ms[1] = ev_ms(sc.ev[1], sc.ev[2]);
-    ctx->zel_ms[2] = ev_ms(sc.ev[2], sc.ev[3]);
-    ctx->zel_ms[3] = ev_ms(sc.ev[0], sc.ev[4]);
+    ctx->zel_ms[0] = filled ? sc.ms(0, 1) : 0.0;
+    ctx->zel_ms[1] = sc.ms(1, 2);
+    ctx->zel_ms[2] = sc.ms(2, 3);
+    ctx->zel_ms[3] = sc.ms(0, 4);
     return SHQ_OK;
 }

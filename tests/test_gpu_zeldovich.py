@@ -122,22 +122,22 @@ def _tables(N, other=False):
     return (d * zr.tabulate_k2(lambda k: 1.0 / (1.0 + k), N, BOX), g) if other else (d, g)
 
 
-def _pdist(a, b):
+def _pdist(a, b, box=BOX):
     d = np.abs(a - b)
-    return np.minimum(d, BOX - d)
+    return np.minimum(d, box - d)
 
 
-def _compare(got, ref, tag):
+def _compare(got, ref, tag, box=BOX):
     for name in ("Density", "Disp", "Vel"):
         scale = np.abs(ref[name]).max()
         err = np.abs(got[name] - ref[name]).max()
         print(f"{tag} {name}: max |diff| {err:.3e}, max |field| {scale:.3e}")
         assert err < BAR * scale, (tag, name, err, scale)
     dmax = np.abs(ref["Disp"]).max()
-    perr = _pdist(got["Pos"], ref["Pos"]).max()
+    perr = _pdist(got["Pos"], ref["Pos"], box).max()
     print(f"{tag} Pos: periodic distance {perr:.3e}, max |Disp| {dmax:.3e}")
     assert perr < BAR * dmax, (tag, perr)
-    assert np.all((got["Pos"] >= 0) & (got["Pos"] < BOX))
+    assert np.all((got["Pos"] >= 0) & (got["Pos"] < box))
     assert abs(got["maxdisp"] - ref["maxdisp"]) < BAR * dmax
     assert abs(got["maxvel"] - ref["maxvel"]) < BAR * ref["maxvel"]
 
@@ -157,6 +157,22 @@ def test_end_to_end(zctx, N, scaledep):
         assert got["maxvel"] == (got["Vel"] ** 2).sum(axis=1).max() or abs(got["maxvel"] / (got["Vel"] ** 2).sum(axis=1).max() - 1) < 4e-16
         if not scaledep:
             assert np.array_equal(got["Vel"], got["Disp"] * 37.5)
+
+
+@pytest.mark.parametrize("N", [18, 24])
+def test_last_position_below_the_box_edge(zctx, N):
+    """BoxSize 1 and coordinates at nextafter(1, 0): Pos / CellSize rounds up to exactly Nmesh (at 18 and 24, not at 16), which the readout
+    must take as cell 0 with residual 0.  Eight particles, every choice of the axes at the edge, one mesh size per transform route."""
+    edge = np.nextafter(1.0, 0.0)
+    assert edge / (1.0 / N) == N
+    inner = np.array([[0.3, 0.55, 0.71], [0.12, 0.91, 0.47], [0.66, 0.05, 0.38], [0.83, 0.29, 0.14],
+                      [0.41, 0.77, 0.95], [0.58, 0.18, 0.62], [0.07, 0.49, 0.86], [0.24, 0.64, 0.02]])
+    at_edge = np.array([(0, 0, 1), (0, 1, 0), (0, 1, 1), (1, 0, 0), (1, 0, 1), (1, 1, 0), (1, 1, 1), (1, 1, 0)], dtype=bool)
+    pos = np.ascontiguousarray(np.where(at_edge, edge, inner))
+    delta, growth = zr.tabulate_k2(_delta, N, 1.0), zr.tabulate_k2(_growth, N, 1.0)
+    got = sq.displacement_fields(zctx, pos, N, 1.0, 181170, delta, growth, vel_prefac=37.5, ScaleDepVelocity=1)
+    ref = zr.displacement_fields(N, 1.0, 181170, 0, 0, 37.5, 1, delta, growth, pos)
+    _compare(got, ref, f"N {N} box edge", box=1.0)
 
 
 def test_agrees_with_pm_apply(zctx):
