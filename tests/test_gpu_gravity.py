@@ -268,7 +268,9 @@ def test_pm_transposing_fft_pipeline_gives_the_in_place_pipelines_bits(ctx, nmes
     """The five FFT passes of the undivided PM as the transposing pipeline (mesh <-> scratch mesh, contiguous tiles on one side of
     every pass: fft3d.hip) against the in-place pipeline on the same deposit: potential mesh, GravPM and the PM potential bit for bit
     ("bit-pattern-reproducible per FFT plan": the two are the same plan, addressed differently); radix 16 / 4 / 2 / 3 / 5 stage
-    mixes, meshes whose z pitch holds pad columns (16: Nc = 9 in 12) and ones without (24: Nc = 13 in 16)."""
+    mixes, meshes whose z pitch holds pad columns (16: Nc = 9 in 12) and ones without (24: Nc = 13 in 16).  At 512 and 1024 this test
+    only compares the two pipelines, which share every butterfly and twiddle: that the big sizes are CORRECT is checked against an
+    independent reference, at every compiled size, by tests/test_gpu_pm_sheaf.py."""
     big = nmesh > 400                  # 512: the largest mesh on 256-thread workgroups; 1024 (C4's): 512-thread workgroups, > 2^32 bytes
     n = 64**3 + 11 if big else 20**3 + 11
     pos = cm.random_positions(orc.boost_mt19937_uniform(3, 3 * n), n)
