@@ -201,6 +201,18 @@ struct TreeBuildBufs {
     }
 };
 
+/* Launch plan of the bespoke FFT (fft3d.hip) for one mesh size on one context's device: the workgroups resident on the chip at once, per
+ * group of kernels that share a grid.  0: not asked yet - each pipeline fills its half on its first call. */
+struct shq_fft_plan {
+    int N = 0;
+    struct {
+        unsigned res_z = 0, res_s = 0, res_x = 0, res_x3 = 0, res_x4 = 0, res_x5 = 0;
+    } t; /* transposing pipeline */
+    struct {
+        unsigned res_zf = 0, res_zi = 0, res_s = 0, res_x3 = 0, res_x4 = 0;
+    } n; /* in-place pipeline */
+};
+
 struct shq_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -414,6 +426,7 @@ struct shq_context {
     double fft_gax_asmth2 = -1;
     const double *fft_gax_src = nullptr;
     int fft_tw_n = 0;
+    std::vector<shq_fft_plan> fft_plans; /* launch geometry per mesh size used so far, on this context's device */
     DevBuf<double> mesh;       /* padded in-place real/complex mesh: N*N*(N+2) doubles */
     DevBuf<double> sinctab;    /* 1/sinc^2 per mesh index */
     int sinctab_n = 0;
@@ -558,23 +571,49 @@ int shq_build_tree_targets(shq_context *ctx);
 /* fft3d.hip */
 bool shq_fft3d_supported(int N);
 int shq_fft3d_pitch(int N);
-int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale,
-                  const double *d_sinctab, double asmth2, double pot_factor);
-int shq_fft3d_run_transposed(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, bool from_i64, double inv_scale,
-                             const double *d_sinctab, double asmth2, double pot_factor);
+/* what the in-place pipeline runs on d_mesh = [N][N][zp] doubles */
+enum shq_fft_stage {
+    SHQ_FFT_FORWARD,       /* r2c of the full cube: Z, Y and X forward */
+    SHQ_FFT_INVERSE,       /* c2r of the full cube: X, Y and Z inverse */
+    SHQ_FFT_SOLVE,         /* forward, potential_transfer and inverse in five passes (the X pass fused) */
+    /* a distributed mesh: `nslab` x-planes [nslab][N][zp], or a y-slab [N][nslab][zp / 2] complex that starts at mesh row y0 */
+    SHQ_FFT_YZ_FORWARD,        /* Z forward + Y forward on the x-planes */
+    SHQ_FFT_YZ_INVERSE,        /* Y inverse + Z inverse on them */
+    SHQ_FFT_YZ_FORWARD_PACKED, /* as YZ_FORWARD, the Y pass writing the all-to-all layout into `packed` */
+    SHQ_FFT_YZ_INVERSE_PACKED, /* as YZ_INVERSE, the Y pass reading it from there */
+    SHQ_FFT_X_SOLVE,           /* X forward + potential_transfer + X inverse on the y-slab (lines along the slowest axis) */
+    SHQ_FFT_X_FORWARD_SUMS,    /* X_SOLVE split in two: the X forward, the spectrum left in place, with the P(k) sums */
+    SHQ_FFT_X_FINISH,          /* ... then the mode factor, potential_transfer and the X inverse; needs modefac */
+};
+/* what the transposing pipeline runs between d_mesh and a scratch mesh of the same size */
+enum shq_fft_part {
+    SHQ_FFT_T_SOLVE,   /* forward, potential_transfer and inverse (five passes) */
+    SHQ_FFT_T_FORWARD, /* Z, Y and X forward with the P(k) sums: the half spectrum is left in d_mesh in the layout LX */
+    SHQ_FFT_T_FINISH,  /* from there the mode factor, potential_transfer, the X inverse half, Y and Z inverse; needs modefac */
+    SHQ_FFT_T_FILTER,  /* as T_FINISH without the Green's function (the excursion-set filter): every mode times (v / ncell)
+                          modefac[k2 & fac_mask], d_mesh only read, the Z inverse writes `out`; needs modefac, tw and out */
+};
+/* the arguments few calls have */
+struct shq_fft_opts {
+    int nslab = 0, y0 = 0;            /* slab stages: planes or rows of this rank, the mesh row of the y-slab's first */
+    double *packed = nullptr;         /* packed stages: [nranks][nslab][N / nranks][zp / 2] complex */
+    int nranks = 1;
+    const double *modefac = nullptr;  /* the caller's factor by integer k2, entry k2 & fac_mask (none: {1.0} with fac_mask = 0) */
+    int fac_mask = 0;
+    const int32_t *bintab = nullptr;  /* the bin of k2 (pm.hip, pm_power_prepare) */
+    double *ps = nullptr;             /* the P(k) sums of powerspectrum_add_mode; null: none taken */
+    /* transposing pipeline only */
+    const double *tw = nullptr;       /* the caller's own twiddles of N (shq_fft3d_fill_twiddles): the context's are left alone */
+    double *out = nullptr;            /* T_FILTER: where the Z inverse writes */
+    int ncell = 1;                    /* T_FILTER: the int N^3 every mode is divided by */
+};
+/* from_i64: the mesh holds the int64 fixed-point deposit, worth inv_scale per unit.  d_sinctab, asmth2, pot_factor: the Green's function. */
+int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, shq_fft_stage stage, bool from_i64, double inv_scale, const double *d_sinctab,
+                  double asmth2, double pot_factor, const shq_fft_opts &o = {});
+/* d_sinctab null: no Green's function table is built, and with o.tw the call touches none of the context's FFT tables */
+int shq_fft3d_run_transposed(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, shq_fft_part part, bool from_i64, double inv_scale,
+                             const double *d_sinctab, double asmth2, double pot_factor, const shq_fft_opts &o = {});
 int shq_fft3d_fill_twiddles(int N, double *d_tw);
-int shq_fft3d_filter_part(shq_context *ctx, const double *d_tw, double *d_mesh, double *d_scratch, double *d_out, int N, int zp, int part,
-                          double inv_scale, const double *d_fac, int fac_mask, int ncell);
-int shq_fft3d_transposed_part(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, int part, bool from_i64, double inv_scale,
-                              const double *d_sinctab, double asmth2, double pot_factor, const double *d_modefac, int fac_mask,
-                              const int32_t *d_bintab, double *d_ps);
-int shq_fft3d_run_slab(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale,
-                       const double *d_sinctab, double asmth2, double pot_factor, int nslab, int y0);
-int shq_fft3d_run_slab_packed(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale,
-                              const double *d_sinctab, double asmth2, double pot_factor, int nslab, int y0, double *d_packed, int nranks);
-int shq_fft3d_run_slab_x(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale, const double *d_sinctab,
-                         double asmth2, double pot_factor, int nslab, int y0, double *d_packed, int nranks, const double *d_modefac, int fac_mask,
-                         const int32_t *d_bintab, double *d_ps);
 /* sph.hip */
 int shq_sph_prepare(shq_context *ctx, const shq_kick_factors *kf, const shq_hydro_params *hp, const double *d_evp_in);
 int shq_sph_density_device(shq_context *ctx, const shq_density_params *p, const int32_t *d_queue, int64_t nq,

@@ -447,22 +447,22 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_z_inv(double *mesh, const int 
  * MODE 0: forward only; 1: inverse only; 2: forward, Green's function, inverse (X pass of the PM).
  * MODES 3, 4 (fft_pass_strided only, the X pass of a y-slab): MODE 2 split in two as fft_t_tile's MODES 3, 4 split it (below). */
 struct GreenArgs {
-    const double *sinctab; /* 1 / sinc^2(pi k / N) per mesh index */
-    const double *gaxg;    /* transposing pipeline: exp(-k_i^2 asmth2) sinctab[i]^2 per mesh index, in global memory (fft_gax_kernel) */
-    double asmth2, pot_factor;
-    int y0;                /* mesh index of outer = 0 in the X pass (y-slab of a distributed mesh) */
+    const double *sinctab = nullptr; /* 1 / sinc^2(pi k / N) per mesh index */
+    const double *gaxg = nullptr;    /* transposing pipeline: exp(-k_i^2 asmth2) sinctab[i]^2 per mesh index, in global memory (fft_gax_kernel) */
+    double asmth2 = 0, pot_factor = 0;
+    int y0 = 0;                      /* mesh index of outer = 0 in the X pass (y-slab of a distributed mesh) */
     /* PK != 0 (Y pass of a distributed mesh): the transposed side of the pass lives in `alt`, laid out as the all-to-all wants it,
      * [dest rank q][x plane][y inside q's slab][z']: line element y sits at alt + (y / nyl) qstride + outer alt_outer + (y % nyl) es */
-    double2 *alt;
-    int nyl;
-    long long qstride, alt_outer;
+    double2 *alt = nullptr;
+    int nyl = 1;
+    long long qstride = 0, alt_outer = 0;
     /* the split X pass of the transposing pipeline (fft_t_tile MODES 3 and 4): the caller's factor by integer k2 (entry k2 & fac_mask:
      * fac_mask = 0 with a one-entry table {1.0} when there is none), and the P(k) sums of powerspectrum_add_mode (ps = null: none) -
      * ps[0, N) power, [N, 2N) kk, [2N, 3N) modes (u64), ps[3N] norm; the bin of k2 is bintab[k2] (pm.hip, pm_power_prepare) */
-    const double *modefac;
-    int fac_mask;
-    const int32_t *bintab;
-    double *ps;
+    const double *modefac = nullptr;
+    int fac_mask = 0;
+    const int32_t *bintab = nullptr;
+    double *ps = nullptr;
     int ncell = 1; /* fft_t_tile MODE 5: the int N^3 every mode is divided by (uvbg.cpp:211-215 divide_by_ncell) */
 };
 
@@ -1039,12 +1039,71 @@ __global__ void fft_gax_kernel(int N, const double *__restrict__ sinctab, double
     }
 }
 
-/* part 0: forward, potential_transfer and inverse (five passes); 1: Z fwd, Y fwd and the X forward half (MODE 3) - the half spectrum is left
- * in d_mesh in the layout LX; 2: from there the X inverse half (MODE 4), Y inv and Z inv; 3: as 2 with MODE 5 (the excursion-set filter,
- * no Green's function): d_mesh is only read, the Z inverse writes d_out.  W: the twiddles of N (ensure_twiddles, or a caller's own). */
+/* ---- host driver */
+
+/* one kernel at the dynamic LDS size it is launched with */
+struct FftKernel {
+    const void *fn;
+    size_t lds;
+    template <class K>
+    FftKernel(K *kernel, size_t lds_) : fn((const void *) kernel), lds(lds_)
+    {
+    }
+};
+
+/* The workgroups of `threads` threads resident on `ncu` CUs at once, the least over kernels that share a grid; lifts the 48 KB limit of
+ * dynamic LDS on the current device for those that need it.  Without an answer: 1 workgroup per CU. */
+int fft_resident(int ncu, int threads, std::initializer_list<FftKernel> kernels, unsigned *res)
+{
+    *res = ~0u;
+    for(const FftKernel &k : kernels) {
+        if(k.lds > 48 * 1024)
+            SHQ_HIP(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int) k.lds));
+        int per_cu = 0;
+        if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k.fn, threads, k.lds) != hipSuccess || per_cu < 1)
+            per_cu = 1;
+        const unsigned r = (unsigned) per_cu * (unsigned) ncu;
+        *res = r < *res ? r : *res;
+    }
+    return SHQ_OK;
+}
+
+int fft_ncu(const shq_context *ctx)
+{
+    int ncu = 0;
+    if(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || ncu < 1)
+        ncu = 256;
+    return ncu;
+}
+
+/* the context's plan of mesh size N, empty the first time.  The plans of every size used so far stay (uvbg.hip runs a mesh of its own
+ * between PM steps of another); a later push_back may move them, so the reference lasts for one call. */
+shq_fft_plan &fft_plan(shq_context *ctx, int N)
+{
+    for(shq_fft_plan &p : ctx->fft_plans)
+        if(p.N == N)
+            return p;
+    ctx->fft_plans.emplace_back();
+    ctx->fft_plans.back().N = N;
+    return ctx->fft_plans.back();
+}
+
+/* The tuning knobs, read on every call (a live process may change them).  Persistent grids: SHQ_FFT_GRID_MUL times the resident
+ * workgroups, 0 for one workgroup per tile; SHQ_FFT_XCD_K is fft_pass_strided's and fft_t_tile's xcdk. */
+struct FftKnobs {
+    unsigned gmul = getenv("SHQ_FFT_GRID_MUL") ? (unsigned) atoi(getenv("SHQ_FFT_GRID_MUL")) : 8u;
+    unsigned xcdk = getenv("SHQ_FFT_XCD_K") ? (unsigned) atoi(getenv("SHQ_FFT_XCD_K")) : 8u;
+    dim3 grid(int tot, unsigned resident) const
+    {
+        const unsigned cap = gmul == 0 ? (unsigned) tot : resident * gmul;
+        return dim3((unsigned) tot < cap ? (unsigned) tot : cap);
+    }
+};
+
+/* W: the twiddles of N (ensure_twiddles, or a caller's own); d_out: where T_FILTER's Z inverse writes */
 template <int N>
 int run_t(shq_context *ctx, const double2 *W, double *d_mesh, double *d_scratch, double *d_out, int zp, bool from_i64, double inv_scale,
-          const GreenArgs &ga, int part)
+          const GreenArgs &ga, shq_fft_part part)
 {
     constexpr size_t lds = sizeof(double2) * (FFT_C * fft_ls(N) + fft_twn(N)), lds_x = lds + sizeof(double) * N; /* X pass: + its factor table */
     constexpr size_t lds_hist = sizeof(double) * 3 * N;                                                          /* MODES 3, 4: + the P(k) histogram */
@@ -1053,72 +1112,52 @@ int run_t(shq_context *ctx, const double2 *W, double *d_mesh, double *d_scratch,
     const int stot = N * nzb;
     double2 *A = reinterpret_cast<double2 *>(d_mesh), *B = reinterpret_cast<double2 *>(d_scratch);
     hipStream_t s = ctx->stream;
-    static unsigned res_z = 0, res_s = 0, res_x = 0, res_x3 = 0, res_x4 = 0, res_x5 = 0;
-    if(res_s == 0) {
-        const void *fns[9] = {(const void *) fft_t_z_fwd<N, true>, (const void *) fft_t_z_fwd<N, false>, (const void *) fft_t_z_inv<N>,
-                              (const void *) fft_t_tile<N, 0, true>, (const void *) fft_t_tile<N, 2, true>, (const void *) fft_t_tile<N, 1, false>,
-                              (const void *) fft_t_tile<N, 3, false>, (const void *) fft_t_tile<N, 4, true>, (const void *) fft_t_tile<N, 5, true>};
-        int ncu = 0;
-        if(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || ncu < 1)
-            ncu = 256;
-        unsigned occ[9];
-        for(int i = 0; i < 9; i++) {
-            const size_t l = i == 4 ? lds_x : (i == 6 ? lds + lds_hist : (i == 7 ? lds_x + lds_hist : lds));
-            if(l > 48 * 1024)
-                SHQ_HIP(hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int) l));
-            int per_cu = 0;
-            if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fns[i], FFT_T, l) != hipSuccess || per_cu < 1)
-                per_cu = 1;
-            occ[i] = (unsigned) per_cu * (unsigned) ncu;
-        }
-        res_z = occ[0] < occ[1] ? occ[0] : occ[1];
-        res_z = res_z < occ[2] ? res_z : occ[2];
-        res_s = occ[3] < occ[5] ? occ[3] : occ[5];
-        res_x = occ[4];
-        res_x3 = occ[6];
-        res_x4 = occ[7];
-        res_x5 = occ[8];
+    auto &pl = fft_plan(ctx, N).t;
+    if(pl.res_s == 0) {
+        auto p = pl;
+        const int ncu = fft_ncu(ctx);
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_t_z_fwd<N, true>, lds}, {fft_t_z_fwd<N, false>, lds}, {fft_t_z_inv<N>, lds}}, &p.res_z));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_t_tile<N, 2, true>, lds_x}}, &p.res_x));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_t_tile<N, 3, false>, lds + lds_hist}}, &p.res_x3));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_t_tile<N, 4, true>, lds_x + lds_hist}}, &p.res_x4));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_t_tile<N, 5, true>, lds}}, &p.res_x5));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_t_tile<N, 0, true>, lds}, {fft_t_tile<N, 1, false>, lds}}, &p.res_s));
+        pl = p;
     }
-    const unsigned gmul = getenv("SHQ_FFT_GRID_MUL") ? (unsigned) atoi(getenv("SHQ_FFT_GRID_MUL")) : 8u;
-    auto grid = [&](int tot, unsigned resident) {
-        const unsigned cap = gmul == 0 ? (unsigned) tot : resident * gmul;
-        return dim3((unsigned) tot < cap ? (unsigned) tot : cap);
-    };
-    const dim3 gz = grid(ztot, res_z), gs = grid(stot, res_s), gx = grid(stot, res_x);
-    const unsigned xcdk = getenv("SHQ_FFT_XCD_K") ? (unsigned) atoi(getenv("SHQ_FFT_XCD_K")) : 8u;
-    if(part == 0 || part == 1) {
+    const FftKnobs k{};
+    const unsigned xcdk = k.xcdk;
+    const dim3 gz = k.grid(ztot, pl.res_z), gs = k.grid(stot, pl.res_s), gx = k.grid(stot, pl.res_x);
+    if(part == SHQ_FFT_T_SOLVE || part == SHQ_FFT_T_FORWARD) {
         if(from_i64)
             fft_t_z_fwd<N, true><<<gz, dim3(FFT_T), lds, s>>>(d_mesh, B, ztot, zp, W, inv_scale);
         else
             fft_t_z_fwd<N, false><<<gz, dim3(FFT_T), lds, s>>>(d_mesh, B, ztot, zp, W, 1.0);
         fft_t_tile<N, 0, true><<<gs, dim3(FFT_T), lds, s>>>(B, A, nzb, stot, W, ga, xcdk);
     }
-    if(part == 0)
+    if(part == SHQ_FFT_T_SOLVE)
         fft_t_tile<N, 2, true><<<gx, dim3(FFT_T), lds_x, s>>>(A, B, nzb, stot, W, ga, xcdk);
-    else if(part == 1)
-        fft_t_tile<N, 3, false><<<grid(stot, res_x3), dim3(FFT_T), lds + (ga.ps ? lds_hist : 0), s>>>(A, A, nzb, stot, W, ga, xcdk);
-    else if(part == 2)
-        fft_t_tile<N, 4, true><<<grid(stot, res_x4), dim3(FFT_T), lds_x + (ga.ps ? lds_hist : 0), s>>>(A, B, nzb, stot, W, ga, xcdk);
+    else if(part == SHQ_FFT_T_FORWARD)
+        fft_t_tile<N, 3, false><<<k.grid(stot, pl.res_x3), dim3(FFT_T), lds + (ga.ps ? lds_hist : 0), s>>>(A, A, nzb, stot, W, ga, xcdk);
+    else if(part == SHQ_FFT_T_FINISH)
+        fft_t_tile<N, 4, true><<<k.grid(stot, pl.res_x4), dim3(FFT_T), lds_x + (ga.ps ? lds_hist : 0), s>>>(A, B, nzb, stot, W, ga, xcdk);
     else
-        fft_t_tile<N, 5, true><<<grid(stot, res_x5), dim3(FFT_T), lds, s>>>(A, B, nzb, stot, W, ga, xcdk);
-    if(part != 1) {
+        fft_t_tile<N, 5, true><<<k.grid(stot, pl.res_x5), dim3(FFT_T), lds, s>>>(A, B, nzb, stot, W, ga, xcdk);
+    if(part != SHQ_FFT_T_FORWARD) {
         fft_t_tile<N, 1, false><<<gs, dim3(FFT_T), lds, s>>>(B, B, nzb, stot, W, ga, xcdk);
-        fft_t_z_inv<N><<<gz, dim3(FFT_T), lds, s>>>(B, part == 3 ? d_out : d_mesh, ztot, zp, W);
+        fft_t_z_inv<N><<<gz, dim3(FFT_T), lds, s>>>(B, part == SHQ_FFT_T_FILTER ? d_out : d_mesh, ztot, zp, W);
     }
     SHQ_HIP(hipGetLastError());
     return SHQ_OK;
 }
 
-/* stage 0 / 1 / 2 as shq_fft3d_run on a full cube (nslab = N).  Slab stages for a distributed mesh:
- * 10: Z forward + Y forward on `nslab` x-planes [nslab][N][zp];  11: Y inverse + Z inverse on them;
- * 12: X forward + potential_transfer + X inverse on a y-slab [N][nslab][zpc] (lines along the slowest axis);
- * 15, 16: stage 12 split in two - X forward with the P(k) sums (MODE 3), then T, potential_transfer and X inverse (MODE 4). */
+/* nslab: N for the stages of a full cube */
 template <int N>
-int run_n(shq_context *ctx, double *d_mesh, int zp, int stage, bool from_i64, double inv_scale, const GreenArgs &ga, int nslab)
+int run_n(shq_context *ctx, double *d_mesh, int zp, shq_fft_stage stage, bool from_i64, double inv_scale, const GreenArgs &ga, int nslab)
 {
     const double2 *W = reinterpret_cast<const double2 *>(ctx->fft_tw.ptr);
     /* FFT_C padded lines + the twiddle table + (X pass) the sinc table */
     constexpr size_t lds = sizeof(double2) * (FFT_C * fft_ls(N) + fft_twn(N)) + sizeof(double) * N;
+    constexpr size_t lds_hist = lds + sizeof(double) * 3 * N; /* the split X pass with the P(k) histogram */
 #ifndef SHQ_FFT_RELAX /* tile-shape experiments on one mesh size */
     static_assert(N % (2 * FFT_C) == 0, "rows must tile evenly");
 #endif
@@ -1128,158 +1167,124 @@ int run_n(shq_context *ctx, double *d_mesh, int zp, int stage, bool from_i64, do
     const int stot = nslab * ntiles;                                  /* tiles of a strided pass */
     double2 *cm = reinterpret_cast<double2 *>(d_mesh);
     hipStream_t s = ctx->stream;
-    /* persistent grids: as many workgroups as are resident on the chip at once (LDS-limited) */
-    static unsigned res_zf = 0, res_zi = 0, res_s = 0;
-    if(res_s == 0) {
-        const void *fns[8] = {(const void *) fft_pass_z_fwd<N, true>, (const void *) fft_pass_z_fwd<N, false>,
-                              (const void *) fft_pass_z_inv<N>,       (const void *) fft_pass_strided<N, 0>,
-                              (const void *) fft_pass_strided<N, 1>,  (const void *) fft_pass_strided<N, 2>,
-                              (const void *) fft_pass_strided<N, 0, 1>, (const void *) fft_pass_strided<N, 1, 2>};
-        int ncu = 0;
-        if(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || ncu < 1)
-            ncu = 256;
-        unsigned occ[8];
-        for(int i = 0; i < 8; i++) {
-            if(lds > 48 * 1024) /* allow > 48 KB of dynamic LDS */
-                SHQ_HIP(hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-            int per_cu = 0;
-            if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fns[i], FFT_T, lds) != hipSuccess || per_cu < 1)
-                per_cu = 1;
-            occ[i] = (unsigned) per_cu * (unsigned) ncu;
-        }
-        res_zf = occ[0] < occ[1] ? occ[0] : occ[1];
-        res_zi = occ[2];
-        res_s = occ[3] < occ[4] ? occ[3] : occ[4];
-        res_s = res_s < occ[5] ? res_s : occ[5];
-        res_s = res_s < occ[6] ? res_s : occ[6];
-        res_s = res_s < occ[7] ? res_s : occ[7];
+    /* persistent grids: as many workgroups as are resident on the chip at once (LDS-limited); the split X pass has counts of its own
+     * (as fft_t_tile's res_x3 / res_x4), so that the histogram's LDS does not shrink the grids of the other passes */
+    auto &pl = fft_plan(ctx, N).n;
+    if(pl.res_s == 0) {
+        auto p = pl;
+        const int ncu = fft_ncu(ctx);
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_z_fwd<N, true>, lds}, {fft_pass_z_fwd<N, false>, lds}}, &p.res_zf));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_z_inv<N>, lds}}, &p.res_zi));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 3>, lds_hist}}, &p.res_x3));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 4>, lds_hist}}, &p.res_x4));
+        SHQ_TRY(fft_resident(ncu, FFT_T,
+                             {{fft_pass_strided<N, 0>, lds}, {fft_pass_strided<N, 1>, lds}, {fft_pass_strided<N, 2>, lds}, {fft_pass_strided<N, 0, 1>, lds},
+                              {fft_pass_strided<N, 1, 2>, lds}},
+                             &p.res_s));
+        pl = p;
     }
-    const unsigned gmul = getenv("SHQ_FFT_GRID_MUL") ? (unsigned) atoi(getenv("SHQ_FFT_GRID_MUL")) : 8u;
-    auto grid = [&](int tot, unsigned resident) {
-        const unsigned cap = gmul == 0 ? (unsigned) tot : resident * gmul;
-        return dim3((unsigned) tot < cap ? (unsigned) tot : cap);
-    };
-    const dim3 gzf = grid(ztot, res_zf), gzi = grid(ztot, res_zi), gs = grid(stot, res_s);
-    const unsigned xcdk = getenv("SHQ_FFT_XCD_K") ? (unsigned) atoi(getenv("SHQ_FFT_XCD_K")) : 8u;
-    if(stage == 12) { /* lines along x of a y-slab: element stride nslab * zpc, outer = local y */
-        fft_pass_strided<N, 2><<<gs, dim3(FFT_T), lds, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
-        SHQ_HIP(hipGetLastError());
-        return SHQ_OK;
-    }
-    if(stage == 15 || stage == 16) {
-        /* the split X pass: resident counts of its own (as fft_t_tile's res_x3 / res_x4), so that the histogram's LDS does not shrink
-         * the grids of the passes above */
-        constexpr size_t lds_hist = lds + sizeof(double) * 3 * N;
-        static unsigned res_x3 = 0, res_x4 = 0;
-        if(res_x3 == 0) {
-            const void *fx[2] = {(const void *) fft_pass_strided<N, 3>, (const void *) fft_pass_strided<N, 4>};
-            int ncu = 0;
-            if(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->device) != hipSuccess || ncu < 1)
-                ncu = 256;
-            unsigned occ[2];
-            for(int i = 0; i < 2; i++) {
-                if(lds_hist > 48 * 1024)
-                    SHQ_HIP(hipFuncSetAttribute(fx[i], hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds_hist));
-                int per_cu = 0;
-                if(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fx[i], FFT_T, lds_hist) != hipSuccess || per_cu < 1)
-                    per_cu = 1;
-                occ[i] = (unsigned) per_cu * (unsigned) ncu;
-            }
-            res_x4 = occ[1];
-            res_x3 = occ[0];
-        }
-        const size_t l = ga.ps ? lds_hist : lds;
-        if(stage == 15)
-            fft_pass_strided<N, 3><<<grid(stot, res_x3), dim3(FFT_T), l, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
+    const FftKnobs k{};
+    const unsigned xcdk = k.xcdk;
+    const dim3 gzf = k.grid(ztot, pl.res_zf), gzi = k.grid(ztot, pl.res_zi), gs = k.grid(stot, pl.res_s);
+    auto z_forward = [&] {
+        if(from_i64)
+            fft_pass_z_fwd<N, true><<<gzf, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W, inv_scale);
         else
-            fft_pass_strided<N, 4><<<grid(stot, res_x4), dim3(FFT_T), l, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
-        SHQ_HIP(hipGetLastError());
-        return SHQ_OK;
-    }
-    if(stage == 13 || stage == 14) { /* stages 10 / 11 with the Y pass writing / reading the all-to-all layout in ga.alt */
-        if(stage == 13) {
-            if(from_i64)
-                fft_pass_z_fwd<N, true><<<gzf, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W, inv_scale);
-            else
-                fft_pass_z_fwd<N, false><<<gzf, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W, 1.0);
+            fft_pass_z_fwd<N, false><<<gzf, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W, 1.0);
+    };
+    const bool packed = stage == SHQ_FFT_YZ_FORWARD_PACKED || stage == SHQ_FFT_YZ_INVERSE_PACKED; /* the Y pass's other side is ga.alt */
+    const size_t lds_split = ga.ps ? lds_hist : lds;
+    switch(stage) {
+    case SHQ_FFT_X_SOLVE: /* lines along x of a y-slab: element stride nslab * zpc, outer = local y */
+        fft_pass_strided<N, 2><<<gs, dim3(FFT_T), lds, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        break;
+    case SHQ_FFT_X_FORWARD_SUMS:
+        fft_pass_strided<N, 3><<<k.grid(stot, pl.res_x3), dim3(FFT_T), lds_split, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        break;
+    case SHQ_FFT_X_FINISH:
+        fft_pass_strided<N, 4><<<k.grid(stot, pl.res_x4), dim3(FFT_T), lds_split, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        break;
+    case SHQ_FFT_YZ_FORWARD:
+    case SHQ_FFT_YZ_FORWARD_PACKED:
+        z_forward();
+        if(packed)
             fft_pass_strided<N, 0, 1><<<gs, dim3(FFT_T), lds, s>>>(cm, zpc, (long long) N * zpc, ntiles, stot, W, ga, xcdk);
-        } else {
-            fft_pass_strided<N, 1, 2><<<gs, dim3(FFT_T), lds, s>>>(cm, zpc, (long long) N * zpc, ntiles, stot, W, ga, xcdk);
-            fft_pass_z_inv<N><<<gzi, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W);
-        }
-        SHQ_HIP(hipGetLastError());
-        return SHQ_OK;
-    }
-    if(stage == 10 || stage == 11) {
-        if(stage == 10) {
-            if(from_i64)
-                fft_pass_z_fwd<N, true><<<gzf, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W, inv_scale);
-            else
-                fft_pass_z_fwd<N, false><<<gzf, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W, 1.0);
+        else
             fft_pass_strided<N, 0><<<gs, dim3(FFT_T), lds, s>>>(cm, zpc, (long long) N * zpc, ntiles, stot, W, ga, xcdk);
-        } else {
+        break;
+    case SHQ_FFT_YZ_INVERSE:
+    case SHQ_FFT_YZ_INVERSE_PACKED:
+        if(packed)
+            fft_pass_strided<N, 1, 2><<<gs, dim3(FFT_T), lds, s>>>(cm, zpc, (long long) N * zpc, ntiles, stot, W, ga, xcdk);
+        else
+            fft_pass_strided<N, 1><<<gs, dim3(FFT_T), lds, s>>>(cm, zpc, (long long) N * zpc, ntiles, stot, W, ga, xcdk);
+        fft_pass_z_inv<N><<<gzi, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W);
+        break;
+    case SHQ_FFT_FORWARD:
+    case SHQ_FFT_INVERSE:
+    case SHQ_FFT_SOLVE:
+        if(stage != SHQ_FFT_INVERSE) {
+            z_forward();
+            /* Y: outer = x plane (stride N*zpc), element stride zpc */
+            fft_pass_strided<N, 0><<<gs, dim3(FFT_T), lds, s>>>(cm, zpc, (long long) N * zpc, ntiles, stot, W, ga, xcdk);
+        }
+        /* X: outer = y (stride zpc), element stride N*zpc */
+        if(stage == SHQ_FFT_FORWARD)
+            fft_pass_strided<N, 0><<<gs, dim3(FFT_T), lds, s>>>(cm, (long long) N * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        else if(stage == SHQ_FFT_INVERSE)
+            fft_pass_strided<N, 1><<<gs, dim3(FFT_T), lds, s>>>(cm, (long long) N * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        else
+            fft_pass_strided<N, 2><<<gs, dim3(FFT_T), lds, s>>>(cm, (long long) N * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        if(stage != SHQ_FFT_FORWARD) {
             fft_pass_strided<N, 1><<<gs, dim3(FFT_T), lds, s>>>(cm, zpc, (long long) N * zpc, ntiles, stot, W, ga, xcdk);
             fft_pass_z_inv<N><<<gzi, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W);
         }
-        SHQ_HIP(hipGetLastError());
-        return SHQ_OK;
-    }
-    /* Chained middle passes (stage 2, full cube; SHQ_FFT_CHAIN = column tiles per chunk, off by default): Y forward, the fused X
-     * pass and Y inverse all work on lines inside one plane of constant z', so they can run chunk by chunk over z' (a chunk of c
-     * tiles is c x 38 MB at 768^3) in the hope that a chunk written by one pass is still in the 256 MB Infinity Cache when the next
-     * pass reads it.  Measured at 768^3 (one box, FFT pipeline in ms): unchained 9.83; chunks of 2 / 3 / 4 / 6 / 8 tiles 11.85 /
-     * 11.20 / 11.03 / 10.59 / 10.56 — the cache does not absorb the write-then-read traffic of these passes, and every chunk pays
-     * the start and the tail of three more launches.  Kept as a diagnostic knob only. */
-    static const int chain_env = getenv("SHQ_FFT_CHAIN") ? atoi(getenv("SHQ_FFT_CHAIN")) : 0;
-    const int chain = chain_env;
-    if(stage == 2 && nslab == N && chain > 0 && chain < ntiles) {
-        if(from_i64)
-            fft_pass_z_fwd<N, true><<<gzf, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W, inv_scale);
-        else
-            fft_pass_z_fwd<N, false><<<gzf, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W, 1.0);
-        for(int t0 = 0; t0 < ntiles; t0 += chain) {
-            const int tw = t0 + chain <= ntiles ? chain : ntiles - t0;
-            const int ctot = N * tw;
-            const dim3 gc = grid(ctot, res_s);
-            fft_pass_strided<N, 0><<<gc, dim3(FFT_T), lds, s>>>(cm, zpc, (long long) N * zpc, tw, ctot, W, ga, xcdk, t0);
-            fft_pass_strided<N, 2><<<gc, dim3(FFT_T), lds, s>>>(cm, (long long) N * zpc, zpc, tw, ctot, W, ga, xcdk, t0);
-            fft_pass_strided<N, 1><<<gc, dim3(FFT_T), lds, s>>>(cm, zpc, (long long) N * zpc, tw, ctot, W, ga, xcdk, t0);
-        }
-        fft_pass_z_inv<N><<<gzi, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W);
-        SHQ_HIP(hipGetLastError());
-        return SHQ_OK;
-    }
-    if(stage == 0 || stage == 2) {
-        if(from_i64)
-            fft_pass_z_fwd<N, true><<<gzf, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W, inv_scale);
-        else
-            fft_pass_z_fwd<N, false><<<gzf, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W, 1.0);
-        /* Y: outer = x plane (stride N*zpc), element stride zpc */
-        fft_pass_strided<N, 0><<<gs, dim3(FFT_T), lds, s>>>(cm, zpc, (long long) N * zpc, ntiles, stot, W, ga, xcdk);
-    }
-    /* X: outer = y (stride zpc), element stride N*zpc */
-    if(stage == 0)
-        fft_pass_strided<N, 0><<<gs, dim3(FFT_T), lds, s>>>(cm, (long long) N * zpc, zpc, ntiles, stot, W, ga, xcdk);
-    else if(stage == 1)
-        fft_pass_strided<N, 1><<<gs, dim3(FFT_T), lds, s>>>(cm, (long long) N * zpc, zpc, ntiles, stot, W, ga, xcdk);
-    else
-        fft_pass_strided<N, 2><<<gs, dim3(FFT_T), lds, s>>>(cm, (long long) N * zpc, zpc, ntiles, stot, W, ga, xcdk);
-    if(stage == 1 || stage == 2) {
-        fft_pass_strided<N, 1><<<gs, dim3(FFT_T), lds, s>>>(cm, zpc, (long long) N * zpc, ntiles, stot, W, ga, xcdk);
-        fft_pass_z_inv<N><<<gzi, dim3(FFT_T), lds, s>>>(d_mesh, ztot, zp, W);
+        break;
     }
     SHQ_HIP(hipGetLastError());
     return SHQ_OK;
 }
 
+/* mesh sizes with a compiled pipeline (multiples of 8 of the form 2^a 3^b 5^c) */
+#define SHQ_FFT_SIZES(X) \
+    X(16) X(24) X(32) X(40) X(48) X(64) X(80) X(96) X(128) X(192) X(256) X(384) X(512) X(768) X(960) X(1024) X(1152) X(1200) X(1536)
+
+template <int NN>
+struct FftSize {
+    enum { N = NN };
+};
+
+/* f(FftSize<N>()) for a compiled N */
+template <class F>
+int fft_dispatch(int N, F f)
+{
+    switch(N) {
+#define SHQ_FFT_CASE(NN) \
+    case NN: return f(FftSize<NN>());
+        SHQ_FFT_SIZES(SHQ_FFT_CASE)
+#undef SHQ_FFT_CASE
+    }
+    return SHQ_ERR_INVALID;
+}
+
+int ensure_twiddles(shq_context *ctx, int N)
+{
+    if(ctx->fft_tw_n == N)
+        return SHQ_OK;
+    SHQ_TRY(ctx->fft_tw.reserve(2 * (size_t) N));
+    SHQ_TRY(shq_fft3d_fill_twiddles(N, ctx->fft_tw.ptr));
+    ctx->fft_tw_n = N;
+    return SHQ_OK;
+}
+
 } // namespace
 
-/* mesh sizes with a compiled pipeline (multiples of 8 of the form 2^a 3^b 5^c) */
 bool shq_fft3d_supported(int N)
 {
     switch(N) {
-    case 16: case 24: case 32: case 40: case 48: case 64: case 80: case 96: case 128: case 192: case 256: case 384: case 512: case 768:
-    case 960: case 1024: case 1152: case 1200: case 1536:
+#define SHQ_FFT_CASE(NN) case NN:
+        SHQ_FFT_SIZES(SHQ_FFT_CASE)
+#undef SHQ_FFT_CASE
         return true;
     }
     return false;
@@ -1300,164 +1305,73 @@ int shq_fft3d_fill_twiddles(int N, double *d_tw)
     return SHQ_OK;
 }
 
-static int ensure_twiddles(shq_context *ctx, int N)
+/* The transposing pipeline: d_scratch is a second mesh of the same size.  The excursion-set radius loop (uvbg.hip) passes twiddles of
+ * its own and no sinc table, and so touches none of the context's FFT tables (its twiddles, the Green's factor table). */
+int shq_fft3d_run_transposed(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, shq_fft_part part, bool from_i64, double inv_scale,
+                             const double *d_sinctab, double asmth2, double pot_factor, const shq_fft_opts &o)
 {
-    if(ctx->fft_tw_n == N)
-        return SHQ_OK;
-    SHQ_TRY(ctx->fft_tw.reserve(2 * (size_t) N));
-    SHQ_TRY(shq_fft3d_fill_twiddles(N, ctx->fft_tw.ptr));
-    ctx->fft_tw_n = N;
-    return SHQ_OK;
-}
-
-/* The excursion-set radius loop (uvbg.hip) on the transposing pipeline, touching none of the context's FFT state (its twiddles, the Green's
- * factor table): d_tw is the caller's own table of N (shq_fft3d_fill_twiddles).  part 1: forward from the int64 deposit in d_mesh
- * (inv_scale = 2^-e), the half spectrum left in d_mesh; part 3: from that spectrum, every mode times (v / ncell) d_fac[k2 & fac_mask],
- * then the inverse into d_out (d_mesh is only read). */
-int shq_fft3d_filter_part(shq_context *ctx, const double *d_tw, double *d_mesh, double *d_scratch, double *d_out, int N, int zp, int part,
-                          double inv_scale, const double *d_fac, int fac_mask, int ncell)
-{
-    SHQ_CHECK((part == 1 || (part == 3 && d_fac && d_out && d_out != d_mesh && d_out != d_scratch)) && d_tw && ncell > 0, SHQ_ERR_INVALID,
-              "fft3d: bad filter part arguments");
+    if(part == SHQ_FFT_T_FILTER)
+        SHQ_CHECK(o.modefac && o.out && o.out != d_mesh && o.out != d_scratch && o.tw && o.ncell > 0, SHQ_ERR_INVALID,
+                  "fft3d: bad filter part arguments");
+    else
+        SHQ_CHECK(part >= SHQ_FFT_T_SOLVE && part <= SHQ_FFT_T_FINISH && (part != SHQ_FFT_T_FINISH || o.modefac) && (!o.ps || o.bintab),
+                  SHQ_ERR_INVALID, "fft3d: bad part arguments");
     SHQ_CHECK(shq_fft3d_supported(N) && N % (2 * FFT_C) == 0, SHQ_ERR_INVALID, "fft3d: unsupported mesh size %d", N);
     SHQ_CHECK(zp == shq_fft3d_pitch(N) && d_mesh && d_scratch && d_mesh != d_scratch, SHQ_ERR_INVALID, "fft3d: bad pitch or scratch mesh");
-    GreenArgs ga;
-    ga.sinctab = nullptr;
-    ga.gaxg = nullptr;
-    ga.asmth2 = 0;
-    ga.pot_factor = 0;
-    ga.y0 = 0;
-    ga.alt = nullptr;
-    ga.nyl = 1;
-    ga.qstride = ga.alt_outer = 0;
-    ga.modefac = d_fac;
-    ga.fac_mask = fac_mask;
-    ga.bintab = nullptr;
-    ga.ps = nullptr;
-    ga.ncell = ncell;
-    const double2 *W = reinterpret_cast<const double2 *>(d_tw);
-#define SHQ_FFT_CASE(NN) case NN: return run_t<NN>(ctx, W, d_mesh, d_scratch, d_out, zp, part == 1, inv_scale, ga, part)
-    switch(N) {
-        SHQ_FFT_CASE(16); SHQ_FFT_CASE(24); SHQ_FFT_CASE(32); SHQ_FFT_CASE(40); SHQ_FFT_CASE(48); SHQ_FFT_CASE(64);
-        SHQ_FFT_CASE(80); SHQ_FFT_CASE(96); SHQ_FFT_CASE(128); SHQ_FFT_CASE(192); SHQ_FFT_CASE(256); SHQ_FFT_CASE(384);
-        SHQ_FFT_CASE(512); SHQ_FFT_CASE(768); SHQ_FFT_CASE(960); SHQ_FFT_CASE(1024); SHQ_FFT_CASE(1152); SHQ_FFT_CASE(1200);
-        SHQ_FFT_CASE(1536);
-    }
-#undef SHQ_FFT_CASE
-    return SHQ_ERR_INVALID;
-}
-
-/* forward + potential_transfer + inverse of a full cube through the transposing pipeline: d_scratch is a second mesh of the same size */
-int shq_fft3d_run_transposed(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, bool from_i64, double inv_scale,
-                             const double *d_sinctab, double asmth2, double pot_factor)
-{
-    return shq_fft3d_transposed_part(ctx, d_mesh, d_scratch, N, zp, 0, from_i64, inv_scale, d_sinctab, asmth2, pot_factor, nullptr, 0, nullptr,
-                                     nullptr);
-}
-
-/* the same in two halves (part 1: forward, the spectrum left in d_mesh; part 2: T, potential_transfer and inverse) - run_t.  modefac / fac_mask,
- * bintab and ps as in GreenArgs: part 2 needs a factor table (at least the one entry {1.0} with fac_mask = 0) */
-int shq_fft3d_transposed_part(shq_context *ctx, double *d_mesh, double *d_scratch, int N, int zp, int part, bool from_i64, double inv_scale,
-                              const double *d_sinctab, double asmth2, double pot_factor, const double *d_modefac, int fac_mask,
-                              const int32_t *d_bintab, double *d_ps)
-{
-    SHQ_CHECK(part >= 0 && part <= 2 && (part != 2 || d_modefac) && (!d_ps || d_bintab), SHQ_ERR_INVALID, "fft3d: bad part arguments");
-    SHQ_CHECK(shq_fft3d_supported(N) && N % (2 * FFT_C) == 0, SHQ_ERR_INVALID, "fft3d: unsupported mesh size %d", N);
-    SHQ_CHECK(zp == shq_fft3d_pitch(N) && d_mesh && d_scratch && d_mesh != d_scratch, SHQ_ERR_INVALID, "fft3d: bad pitch or scratch mesh");
-    SHQ_TRY(ensure_twiddles(ctx, N));
+    if(!o.tw)
+        SHQ_TRY(ensure_twiddles(ctx, N));
     GreenArgs ga;
     ga.sinctab = d_sinctab;
     ga.asmth2 = asmth2;
     ga.pot_factor = pot_factor;
-    ga.y0 = 0;
-    ga.alt = nullptr;
-    ga.nyl = 1;
-    ga.qstride = ga.alt_outer = 0;
-    ga.modefac = d_modefac;
-    ga.fac_mask = fac_mask;
-    ga.bintab = d_bintab;
-    ga.ps = d_ps;
-    if(ctx->fft_gax_n != N || ctx->fft_gax_asmth2 != asmth2 || ctx->fft_gax_src != d_sinctab) {
-        SHQ_TRY(ctx->fft_gax.reserve((size_t) N));
-        fft_gax_kernel<<<dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, ctx->stream>>>(N, d_sinctab, asmth2, ctx->fft_gax.ptr);
-        SHQ_HIP(hipGetLastError());
-        ctx->fft_gax_n = N;
-        ctx->fft_gax_asmth2 = asmth2;
-        ctx->fft_gax_src = d_sinctab;
+    ga.modefac = o.modefac;
+    ga.fac_mask = o.fac_mask;
+    ga.bintab = o.bintab;
+    ga.ps = o.ps;
+    ga.ncell = o.ncell;
+    if(d_sinctab) {
+        if(ctx->fft_gax_n != N || ctx->fft_gax_asmth2 != asmth2 || ctx->fft_gax_src != d_sinctab) {
+            SHQ_TRY(ctx->fft_gax.reserve((size_t) N));
+            fft_gax_kernel<<<dim3((unsigned) ((N + 255) / 256)), dim3(256), 0, ctx->stream>>>(N, d_sinctab, asmth2, ctx->fft_gax.ptr);
+            SHQ_HIP(hipGetLastError());
+            ctx->fft_gax_n = N;
+            ctx->fft_gax_asmth2 = asmth2;
+            ctx->fft_gax_src = d_sinctab;
+        }
+        ga.gaxg = ctx->fft_gax.ptr;
     }
-    ga.gaxg = ctx->fft_gax.ptr;
-#define SHQ_FFT_CASE(NN) case NN: return run_t<NN>(ctx, reinterpret_cast<const double2 *>(ctx->fft_tw.ptr), d_mesh, d_scratch, d_mesh, zp, from_i64, inv_scale, ga, part)
-    switch(N) {
-        SHQ_FFT_CASE(16); SHQ_FFT_CASE(24); SHQ_FFT_CASE(32); SHQ_FFT_CASE(40); SHQ_FFT_CASE(48); SHQ_FFT_CASE(64);
-        SHQ_FFT_CASE(80); SHQ_FFT_CASE(96); SHQ_FFT_CASE(128); SHQ_FFT_CASE(192); SHQ_FFT_CASE(256); SHQ_FFT_CASE(384);
-        SHQ_FFT_CASE(512); SHQ_FFT_CASE(768); SHQ_FFT_CASE(960); SHQ_FFT_CASE(1024); SHQ_FFT_CASE(1152); SHQ_FFT_CASE(1200);
-        SHQ_FFT_CASE(1536);
-    }
-#undef SHQ_FFT_CASE
-    return SHQ_ERR_INVALID;
+    const double2 *W = reinterpret_cast<const double2 *>(o.tw ? o.tw : ctx->fft_tw.ptr);
+    return fft_dispatch(N, [&](auto n) { return run_t<decltype(n)::N>(ctx, W, d_mesh, d_scratch, o.out, zp, from_i64, inv_scale, ga, part); });
 }
 
-/* stage: 0 forward only (r2c), 1 inverse only (c2r), 2 forward + potential_transfer + inverse.
- * d_mesh: [N][N][zp] doubles in place; from_i64: the mesh holds the int64 fixed-point deposit. */
-int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale,
-                  const double *d_sinctab, double asmth2, double pot_factor)
+/* The in-place pipeline on d_mesh = [N][N][zp] doubles, or on a rank's slab of it */
+int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, shq_fft_stage stage, bool from_i64, double inv_scale, const double *d_sinctab,
+                  double asmth2, double pot_factor, const shq_fft_opts &o)
 {
-    return shq_fft3d_run_slab(ctx, d_mesh, N, zp, stage, from_i64, inv_scale, d_sinctab, asmth2, pot_factor, N, 0);
-}
-
-/* nslab: x-planes (stages 10, 11) or y-rows (stage 12, starting at mesh row y0) of this rank's slab */
-int shq_fft3d_run_slab(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale,
-                       const double *d_sinctab, double asmth2, double pot_factor, int nslab, int y0)
-{
-    return shq_fft3d_run_slab_packed(ctx, d_mesh, N, zp, stage, from_i64, inv_scale, d_sinctab, asmth2, pot_factor, nslab, y0, nullptr, 1);
-}
-
-/* stages 13 / 14: as 10 / 11, the spectrum's transposed side in d_packed = [nranks][nslab][N / nranks][zp / 2] complex */
-int shq_fft3d_run_slab_packed(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale,
-                              const double *d_sinctab, double asmth2, double pot_factor, int nslab, int y0, double *d_packed, int nranks)
-{
-    return shq_fft3d_run_slab_x(ctx, d_mesh, N, zp, stage, from_i64, inv_scale, d_sinctab, asmth2, pot_factor, nslab, y0, d_packed, nranks,
-                                nullptr, 0, nullptr, nullptr);
-}
-
-/* every slab stage; stages 15 / 16 (the split X pass of a y-slab) take modefac / fac_mask, bintab and ps as in GreenArgs: stage 16 needs a
- * factor table (at least the one entry {1.0} with fac_mask = 0) */
-int shq_fft3d_run_slab_x(shq_context *ctx, double *d_mesh, int N, int zp, int stage, bool from_i64, double inv_scale, const double *d_sinctab,
-                         double asmth2, double pot_factor, int nslab, int y0, double *d_packed, int nranks, const double *d_modefac, int fac_mask,
-                         const int32_t *d_bintab, double *d_ps)
-{
-    const bool yslab = stage == 12 || stage == 15 || stage == 16;
+    const bool yslab = stage == SHQ_FFT_X_SOLVE || stage == SHQ_FFT_X_FORWARD_SUMS || stage == SHQ_FFT_X_FINISH;
+    const bool packed = stage == SHQ_FFT_YZ_FORWARD_PACKED || stage == SHQ_FFT_YZ_INVERSE_PACKED;
+    const int nslab = stage <= SHQ_FFT_SOLVE ? N : o.nslab;
     SHQ_CHECK(shq_fft3d_supported(N), SHQ_ERR_INVALID, "fft3d: unsupported mesh size %d", N);
-    SHQ_CHECK(nslab > 0 && nslab <= N && y0 >= 0 && y0 + (yslab ? nslab : 0) <= N, SHQ_ERR_INVALID, "fft3d: bad slab geometry");
+    SHQ_CHECK(nslab > 0 && nslab <= N && o.y0 >= 0 && o.y0 + (yslab ? nslab : 0) <= N, SHQ_ERR_INVALID, "fft3d: bad slab geometry");
     SHQ_CHECK(zp >= N + 2 && zp % 8 == 0, SHQ_ERR_INVALID, "fft3d: pitch %d must be a multiple of 8 doubles and >= N+2", zp);
-    SHQ_CHECK((stage != 16 || d_modefac) && (!d_ps || d_bintab), SHQ_ERR_INVALID, "fft3d: bad split X pass arguments");
+    SHQ_CHECK((stage != SHQ_FFT_X_FINISH || o.modefac) && (!o.ps || o.bintab), SHQ_ERR_INVALID, "fft3d: bad split X pass arguments");
     SHQ_TRY(ensure_twiddles(ctx, N));
     GreenArgs ga;
     ga.sinctab = d_sinctab;
-    ga.gaxg = nullptr;
     ga.asmth2 = asmth2;
     ga.pot_factor = pot_factor;
-    ga.y0 = y0;
-    ga.alt = reinterpret_cast<double2 *>(d_packed);
-    ga.nyl = 1;
-    ga.qstride = ga.alt_outer = 0;
-    ga.modefac = d_modefac;
-    ga.fac_mask = fac_mask;
-    ga.bintab = d_bintab;
-    ga.ps = d_ps;
-    if(stage == 13 || stage == 14) {
-        SHQ_CHECK(d_packed && nranks >= 1 && N % nranks == 0, SHQ_ERR_INVALID, "fft3d: packed stages need a buffer and a rank count that divides the mesh");
-        ga.nyl = N / nranks;
+    ga.y0 = o.y0;
+    ga.alt = reinterpret_cast<double2 *>(o.packed);
+    ga.modefac = o.modefac;
+    ga.fac_mask = o.fac_mask;
+    ga.bintab = o.bintab;
+    ga.ps = o.ps;
+    if(packed) {
+        SHQ_CHECK(o.packed && o.nranks >= 1 && N % o.nranks == 0, SHQ_ERR_INVALID,
+                  "fft3d: packed stages need a buffer and a rank count that divides the mesh");
+        ga.nyl = N / o.nranks;
         ga.alt_outer = (long long) ga.nyl * (zp / 2);
         ga.qstride = (long long) nslab * ga.alt_outer;
     }
-#define SHQ_FFT_CASE(NN) case NN: return run_n<NN>(ctx, d_mesh, zp, stage, from_i64, inv_scale, ga, nslab)
-    switch(N) {
-        SHQ_FFT_CASE(16); SHQ_FFT_CASE(24); SHQ_FFT_CASE(32); SHQ_FFT_CASE(40); SHQ_FFT_CASE(48); SHQ_FFT_CASE(64);
-        SHQ_FFT_CASE(80); SHQ_FFT_CASE(96); SHQ_FFT_CASE(128); SHQ_FFT_CASE(192); SHQ_FFT_CASE(256); SHQ_FFT_CASE(384);
-        SHQ_FFT_CASE(512); SHQ_FFT_CASE(768); SHQ_FFT_CASE(960); SHQ_FFT_CASE(1024); SHQ_FFT_CASE(1152); SHQ_FFT_CASE(1200);
-        SHQ_FFT_CASE(1536);
-    }
-#undef SHQ_FFT_CASE
-    return SHQ_ERR_INVALID;
+    return fft_dispatch(N, [&](auto n) { return run_n<decltype(n)::N>(ctx, d_mesh, zp, stage, from_i64, inv_scale, ga, nslab); });
 }

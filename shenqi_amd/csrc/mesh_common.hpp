@@ -70,7 +70,7 @@ inline int route_hipfft_inverse(CallScope &sc, const Fft3dRoute &r, double *d_me
 inline int route_forward(shq_context *ctx, CallScope &sc, const Fft3dRoute &r, double *d_mesh, bool from_i64, double inv_scale)
 {
     if(r.bespoke)
-        return shq_fft3d_run(ctx, d_mesh, r.N, r.zp, 0, from_i64, inv_scale, nullptr, 0, 0);
+        return shq_fft3d_run(ctx, d_mesh, r.N, r.zp, SHQ_FFT_FORWARD, from_i64, inv_scale, nullptr, 0, 0);
     if(from_i64) {
         mesh_convert_i64_kernel<<<dim3(nblk((long long) r.padded)), dim3(256), 0, ctx->stream>>>(d_mesh, r.padded, inv_scale);
         SHQ_HIP(hipGetLastError());
@@ -82,7 +82,7 @@ inline int route_forward(shq_context *ctx, CallScope &sc, const Fft3dRoute &r, d
 inline int route_inverse(shq_context *ctx, CallScope &sc, const Fft3dRoute &r, double *d_mesh)
 {
     if(r.bespoke)
-        return shq_fft3d_run(ctx, d_mesh, r.N, r.zp, 1, false, 1.0, nullptr, 0, 0);
+        return shq_fft3d_run(ctx, d_mesh, r.N, r.zp, SHQ_FFT_INVERSE, false, 1.0, nullptr, 0, 0);
     return route_hipfft_inverse(sc, r, d_mesh);
 }
 

@@ -682,8 +682,12 @@ int pm_finish(shq_context *ctx, const shq_pm_params *pm, bool readout)
         const bool sweep = measure && pm_pk_sweep();
         if(sweep)
             SHQ_TRY(pm_power_sweep(ctx, N, zp / 2, T, zp / 8));
-        SHQ_TRY(shq_fft3d_transposed_part(ctx, ctx->mesh.ptr, scratch, N, zp, 2, false, 1.0, ctx->sinctab.ptr, asmth2, pot_factor, fac, T ? -1 : 0,
-                                          ctx->ps_bintab.ptr, measure && !sweep ? ctx->ps_sums.ptr : nullptr));
+        shq_fft_opts o;
+        o.modefac = fac;
+        o.fac_mask = T ? -1 : 0;
+        o.bintab = ctx->ps_bintab.ptr;
+        o.ps = measure && !sweep ? ctx->ps_sums.ptr : nullptr;
+        SHQ_TRY(shq_fft3d_run_transposed(ctx, ctx->mesh.ptr, scratch, N, zp, SHQ_FFT_T_FINISH, false, 1.0, ctx->sinctab.ptr, asmth2, pot_factor, o));
     } else {
         if(measure)
             SHQ_TRY(pm_power_sweep(ctx, N, zp / 2, T));
@@ -692,7 +696,7 @@ int pm_finish(shq_context *ctx, const shq_pm_params *pm, bool readout)
             (double2 *) ctx->mesh.ptr, N, Nc, zp / 2, ctx->sinctab.ptr, asmth2, pot_factor, T);
         SHQ_HIP(hipGetLastError());
         if(ctx->pm_spec_route == 1)
-            SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 1, false, 1.0, ctx->sinctab.ptr, asmth2, pot_factor));
+            SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, SHQ_FFT_INVERSE, false, 1.0, ctx->sinctab.ptr, asmth2, pot_factor));
         else {
             hipfftSetStream(ctx->plan_c2r, ctx->stream);
             hipfftResult r = hipfftExecZ2D(ctx->plan_c2r, (hipfftDoubleComplex *) ctx->mesh.ptr, (hipfftDoubleReal *) ctx->mesh.ptr);
@@ -724,14 +728,14 @@ int shq_pm_execute(shq_context *ctx, const shq_pm_params *pm, bool readout)
         /* P(k) is taken from the density spectrum, which the fused X pass never writes out: when it is
          * wanted the forward and inverse transforms run separately (6 passes + 2 sweeps instead of 5) */
         SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 1], ctx->stream));
-        SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 0, true, 1.0 / scale, ctx->sinctab.ptr, asmth2, pot_factor));
+        SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, SHQ_FFT_FORWARD, true, 1.0 / scale, ctx->sinctab.ptr, asmth2, pot_factor));
         SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 2], ctx->stream));
         SHQ_TRY(pm_measure_power(ctx, N, zp / 2));
         const size_t tot = (size_t) N * N * Nc;
         pm_green_kernel<<<dim3((unsigned) ((tot + threads - 1) / threads)), dim3(threads), 0, ctx->stream>>>(
             (double2 *) ctx->mesh.ptr, N, Nc, zp / 2, ctx->sinctab.ptr, asmth2, pot_factor);
         SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 3], ctx->stream));
-        SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 1, false, 1.0, ctx->sinctab.ptr, asmth2, pot_factor));
+        SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, SHQ_FFT_INVERSE, false, 1.0, ctx->sinctab.ptr, asmth2, pot_factor));
         SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 4], ctx->stream));
     } else if(ctx->pm_custom_fft) {
         /* five fused passes: Z fwd (+ int64 -> f64), Y fwd, X fwd + potential_transfer + X inv, Y inv, Z inv */
@@ -740,9 +744,9 @@ int shq_pm_execute(shq_context *ctx, const shq_pm_params *pm, bool readout)
         double *scratch = pm_scratch(ctx, N, zp);
         SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 1], ctx->stream));
         if(scratch)
-            SHQ_TRY(shq_fft3d_run_transposed(ctx, ctx->mesh.ptr, scratch, N, zp, true, 1.0 / scale, ctx->sinctab.ptr, asmth2, pot_factor));
+            SHQ_TRY(shq_fft3d_run_transposed(ctx, ctx->mesh.ptr, scratch, N, zp, SHQ_FFT_T_SOLVE, true, 1.0 / scale, ctx->sinctab.ptr, asmth2, pot_factor));
         else
-            SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 2, true, 1.0 / scale, ctx->sinctab.ptr, asmth2, pot_factor));
+            SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, SHQ_FFT_SOLVE, true, 1.0 / scale, ctx->sinctab.ptr, asmth2, pot_factor));
         SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 2], ctx->stream));
         SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 3], ctx->stream));
         SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_PM0 + 4], ctx->stream));
@@ -789,13 +793,15 @@ int shq_pm_execute_forward(shq_context *ctx, const shq_pm_params *pm)
     if(scratch) {
         route = 0;
         const bool sweep = pm_pk_sweep();
-        SHQ_TRY(shq_fft3d_transposed_part(ctx, ctx->mesh.ptr, scratch, N, zp, 1, true, inv_scale, ctx->sinctab.ptr, asmth2, pot_factor, nullptr, 0,
-                                          ctx->ps_bintab.ptr, sweep ? nullptr : ctx->ps_sums.ptr));
+        shq_fft_opts o;
+        o.bintab = ctx->ps_bintab.ptr;
+        o.ps = sweep ? nullptr : ctx->ps_sums.ptr;
+        SHQ_TRY(shq_fft3d_run_transposed(ctx, ctx->mesh.ptr, scratch, N, zp, SHQ_FFT_T_FORWARD, true, inv_scale, ctx->sinctab.ptr, asmth2, pot_factor, o));
         if(sweep)
             SHQ_TRY(pm_power_sweep(ctx, N, zp / 2, nullptr, zp / 8));
     } else if(ctx->pm_custom_fft) {
         route = 1;
-        SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 0, true, inv_scale, ctx->sinctab.ptr, asmth2, pot_factor));
+        SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, SHQ_FFT_FORWARD, true, inv_scale, ctx->sinctab.ptr, asmth2, pot_factor));
         SHQ_TRY(pm_power_sweep(ctx, N, zp / 2));
     } else {
         route = 2;
@@ -927,7 +933,7 @@ int shq_fft_roundtrip_r2c(shq_context *ctx, int N, const double *real, double *c
     pm_repitch_kernel<<<dim3((unsigned) ((tot + threads - 1) / threads)), dim3(threads), 0, ctx->stream>>>(
         dense.ptr, ctx->mesh.ptr, (size_t) N * N, N, N, zp, 0, 1.0);
     if(ctx->pm_custom_fft)
-        SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 0, false, 1.0, ctx->sinctab.ptr, 0, 0));
+        SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, SHQ_FFT_FORWARD, false, 1.0, ctx->sinctab.ptr, 0, 0));
     else {
         hipfftSetStream(ctx->plan_r2c, ctx->stream);
         hipfftResult r = hipfftExecD2Z(ctx->plan_r2c, (hipfftDoubleReal *) ctx->mesh.ptr, (hipfftDoubleComplex *) ctx->mesh.ptr);
@@ -1027,7 +1033,7 @@ int shq_fft_roundtrip_c2r(shq_context *ctx, int N, const double *complx, double 
     pm_repitch_kernel<<<dim3((unsigned) ((ctot + threads - 1) / threads)), dim3(threads), 0, ctx->stream>>>(
         dense.ptr, ctx->mesh.ptr, (size_t) N * N, N + 2, N + 2, zp, 0, 1.0);
     if(ctx->pm_custom_fft)
-        SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, 1, false, 1.0, ctx->sinctab.ptr, 0, 0));
+        SHQ_TRY(shq_fft3d_run(ctx, ctx->mesh.ptr, N, zp, SHQ_FFT_INVERSE, false, 1.0, ctx->sinctab.ptr, 0, 0));
     else {
         hipfftSetStream(ctx->plan_c2r, ctx->stream);
         hipfftResult r = hipfftExecZ2D(ctx->plan_c2r, (hipfftDoubleComplex *) ctx->mesh.ptr, (hipfftDoubleReal *) ctx->mesh.ptr);
@@ -1334,8 +1340,10 @@ extern "C" int shq_pm_slab2_fft_yz(shq_context *ctx, int Nmesh, void *d_planes, 
     SHQ_HIP(hipSetDevice(ctx->device));
     SHQ_TRY(slab_sinctab(ctx, Nmesh));
     const int zp = shq_fft3d_pitch(Nmesh);
-    return shq_fft3d_run_slab(ctx, (double *) d_planes, Nmesh, zp, direction == 0 ? 10 : 11, direction == 0,
-                              ldexp(1.0, -ctx->pm_log2scale), ctx->sinctab.ptr, 0, 0, nplanes, 0);
+    shq_fft_opts o;
+    o.nslab = nplanes;
+    return shq_fft3d_run(ctx, (double *) d_planes, Nmesh, zp, direction == 0 ? SHQ_FFT_YZ_FORWARD : SHQ_FFT_YZ_INVERSE, direction == 0,
+                         ldexp(1.0, -ctx->pm_log2scale), ctx->sinctab.ptr, 0, 0, o);
 }
 
 /* the same two stages with the pack / unpack of the transposes fused into the Y pass: direction 0 leaves the (y, z) spectrum of the
@@ -1349,8 +1357,12 @@ extern "C" int shq_pm_slab2_fft_yz_packed(shq_context *ctx, int Nmesh, void *d_p
     SHQ_HIP(hipSetDevice(ctx->device));
     SHQ_TRY(slab_sinctab(ctx, Nmesh));
     const int zp = shq_fft3d_pitch(Nmesh);
-    return shq_fft3d_run_slab_packed(ctx, (double *) d_planes, Nmesh, zp, direction == 0 ? 13 : 14, direction == 0, ldexp(1.0, -ctx->pm_log2scale), ctx->sinctab.ptr, 0,
-                                     0, nplanes, 0, (double *) d_packed, nranks);
+    shq_fft_opts o;
+    o.nslab = nplanes;
+    o.packed = (double *) d_packed;
+    o.nranks = nranks;
+    return shq_fft3d_run(ctx, (double *) d_planes, Nmesh, zp, direction == 0 ? SHQ_FFT_YZ_FORWARD_PACKED : SHQ_FFT_YZ_INVERSE_PACKED, direction == 0,
+                         ldexp(1.0, -ctx->pm_log2scale), ctx->sinctab.ptr, 0, 0, o);
 }
 
 /* X forward + potential_transfer + X inverse on the y-slab [N][nyl][zp / 2] (complex) received by the transpose */
@@ -1361,8 +1373,11 @@ extern "C" int shq_pm_slab2_xgreen(shq_context *ctx, const shq_pm_params *pm, vo
     const int N = pm->Nmesh;
     SHQ_HIP(hipSetDevice(ctx->device));
     SHQ_TRY(slab_sinctab(ctx, N));
-    return shq_fft3d_run_slab(ctx, (double *) d_spec, N, shq_fft3d_pitch(N), 12, false, 1.0, ctx->sinctab.ptr,
-                              pow((2 * M_PI) * pm->Asmth / N, 2), -pm->G / (M_PI * pm->BoxSize), nyl, y0);
+    shq_fft_opts o;
+    o.nslab = nyl;
+    o.y0 = y0;
+    return shq_fft3d_run(ctx, (double *) d_spec, N, shq_fft3d_pitch(N), SHQ_FFT_X_SOLVE, false, 1.0, ctx->sinctab.ptr,
+                         pow((2 * M_PI) * pm->Asmth / N, 2), -pm->G / (M_PI * pm->BoxSize), o);
 }
 
 /* the X forward of the y-slab, the spectrum left in place, and this slab's raw P(k) sums (fft_pass_strided MODE 3) */
@@ -1371,8 +1386,13 @@ extern "C" int shq_pm_slab2_xforward(shq_context *ctx, const shq_pm_params *pm, 
     SHQ_TRY(slab_x_check(ctx, pm, d_spec, y0, nyl, true));
     const int N = pm->Nmesh;
     SHQ_TRY(pm_power_prepare(ctx, N));
-    SHQ_TRY(shq_fft3d_run_slab_x(ctx, (double *) d_spec, N, shq_fft3d_pitch(N), 15, false, 1.0, ctx->sinctab.ptr, pow((2 * M_PI) * pm->Asmth / N, 2),
-                                 -pm->G / (M_PI * pm->BoxSize), nyl, y0, nullptr, 1, nullptr, 0, ctx->ps_bintab.ptr, ctx->ps_sums.ptr));
+    shq_fft_opts o;
+    o.nslab = nyl;
+    o.y0 = y0;
+    o.bintab = ctx->ps_bintab.ptr;
+    o.ps = ctx->ps_sums.ptr;
+    SHQ_TRY(shq_fft3d_run(ctx, (double *) d_spec, N, shq_fft3d_pitch(N), SHQ_FFT_X_FORWARD_SUMS, false, 1.0, ctx->sinctab.ptr,
+                          pow((2 * M_PI) * pm->Asmth / N, 2), -pm->G / (M_PI * pm->BoxSize), o));
     ctx->ps_slab = true;
     return SHQ_OK;
 }
@@ -1388,9 +1408,15 @@ extern "C" int shq_pm_slab2_xfinish(shq_context *ctx, const shq_pm_params *pm, v
     const bool measure = ctx->pm_measure_power;
     if(measure)
         SHQ_TRY(pm_power_prepare(ctx, N));
-    SHQ_TRY(shq_fft3d_run_slab_x(ctx, (double *) d_spec, N, shq_fft3d_pitch(N), 16, false, 1.0, ctx->sinctab.ptr, pow((2 * M_PI) * pm->Asmth / N, 2),
-                                 -pm->G / (M_PI * pm->BoxSize), nyl, y0, nullptr, 1, fac, mask, ctx->ps_bintab.ptr,
-                                 measure ? ctx->ps_sums.ptr : nullptr));
+    shq_fft_opts o;
+    o.nslab = nyl;
+    o.y0 = y0;
+    o.modefac = fac;
+    o.fac_mask = mask;
+    o.bintab = ctx->ps_bintab.ptr;
+    o.ps = measure ? ctx->ps_sums.ptr : nullptr;
+    SHQ_TRY(shq_fft3d_run(ctx, (double *) d_spec, N, shq_fft3d_pitch(N), SHQ_FFT_X_FINISH, false, 1.0, ctx->sinctab.ptr,
+                          pow((2 * M_PI) * pm->Asmth / N, 2), -pm->G / (M_PI * pm->BoxSize), o));
     if(measure)
         ctx->ps_slab = true;
     return SHQ_OK;

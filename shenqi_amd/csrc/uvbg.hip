@@ -437,9 +437,11 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
     /* ---- forward transforms, the spectra kept for the whole radius loop */
     const int ncell = N * N * N; /* divide_by_ncell's int total_n_cells */
     for(int f = 0; f < nf; f++) {
-        if(bespoke)
-            SHQ_TRY(shq_fft3d_filter_part(ctx, d_tw, spec[f], scratch, nullptr, N, zp, 1, inv_scale[f], nullptr, 0, ncell));
-        else {
+        if(bespoke) {
+            shq_fft_opts o;
+            o.tw = d_tw;
+            SHQ_TRY(shq_fft3d_run_transposed(ctx, spec[f], scratch, N, zp, SHQ_FFT_T_FORWARD, true, inv_scale[f], nullptr, 0, 0, o));
+        } else {
             mesh_convert_i64_kernel<<<dim3(2048), dim3(UV_T), 0, s>>>(spec[f], padded, inv_scale[f]);
             SHQ_TRY(route_hipfft_forward(sc, route, spec[f]));
         }
@@ -478,9 +480,15 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
         const double *fac = d_tabs + (size_t) r * ntab;
         const int mask = last ? 0 : -1;
         for(int f = 0; f < nf; f++) {
-            if(bespoke)
-                SHQ_TRY(shq_fft3d_filter_part(ctx, d_tw, spec[f], scratch, real[f], N, zp, 3, 1.0, fac, mask, ncell));
-            else {
+            if(bespoke) {
+                shq_fft_opts o;
+                o.tw = d_tw;
+                o.out = real[f];
+                o.modefac = fac;
+                o.fac_mask = mask;
+                o.ncell = ncell;
+                SHQ_TRY(shq_fft3d_run_transposed(ctx, spec[f], scratch, N, zp, SHQ_FFT_T_FILTER, false, 1.0, nullptr, 0, 0, o));
+            } else {
                 uvbg_filter_kernel<<<dim3(2048), dim3(UV_T), 0, s>>>((const double2 *) spec[f], (double2 *) real[f], N, fac, mask, ncell);
                 SHQ_TRY(route_hipfft_inverse(sc, route, real[f]));
             }

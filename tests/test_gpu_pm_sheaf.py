@@ -152,7 +152,7 @@ def test_split_x_pass_with_a_mode_factor(ctx, N):
 
 @pytest.mark.parametrize("N", SLAB_SIZES)
 def test_unsharded_slab_pipeline(ctx, N):
-    """the slab passes on one rank (run_n stages 10, 12, 11): one torch buffer [N][N][zp], xoff = 0, nalloc = N, through deposit,
+    """the slab passes on one rank (run_n stages YZ_FORWARD, X_SOLVE, YZ_INVERSE): one torch buffer [N][N][zp], xoff = 0, nalloc = N, through deposit,
     (y, z) forward, the X pass with the Green's function, (y, z) inverse and the readout - against the reduction and bit-equal to the undivided PM, which
     runs after it, at every size"""
     import torch
@@ -207,3 +207,66 @@ def test_translated_load_crosses_the_last_tiles(ctx, N):
     capi.check(capi.hip.shq_pm_run(ctx.h, C.byref(sq.PMParams(N, 0, float(N), ASMTH_SHORT, G))))
     _check(f"shift {shift} Asmth {ASMTH_SHORT}", N, d, _download(ctx, len(sh.pos)), (rg, rpot))
     del pman
+
+
+# ---- the launch plans a context keeps per mesh size (shq_context::fft_plans)
+
+PLAN_D = (1, 1, 1)
+
+
+def _plan_run(c, N, transposed):
+    """shq_pm_run of the sheaf (N, PLAN_D) on context c, checked against the reduction: what it downloads"""
+    sh, rg, rpot = _case(N, PLAN_D)
+    pman = _upload(c, sh)
+    capi.check(capi.hip.shq_pm_set_fft_transposed(c.h, transposed))
+    capi.check(capi.hip.shq_pm_run(c.h, C.byref(sq.PMParams(N, 0, float(N), ASMTH, G))))
+    got = _download(c, len(sh.pos))
+    _check(f"plans transposed={transposed}", N, PLAN_D, got, (rg, rpot))
+    del pman
+    return got
+
+
+def _same_bits(a, b, what):
+    for x, y, name in zip(a, b, ("GravPM", "PM potential")):
+        assert np.array_equal(x, y), (what, name, float(np.abs(x - y).max()))
+
+
+def _two_contexts(dev_b, transposed):
+    """context A on device 0 and B on dev_b, alive together: A at 16, B at 24, A at 24, B at 16, each bit-equal to a fresh
+    context of its device that has run nothing else"""
+    fresh = {}
+    for dev in {0, dev_b}:
+        for N in (16, 24):
+            with sq.Context(dev) as c:
+                fresh[dev, N] = _plan_run(c, N, transposed)
+    with sq.Context(0) as a, sq.Context(dev_b) as b:
+        for c, dev, N in ((a, 0, 16), (b, dev_b, 24), (a, 0, 24), (b, dev_b, 16)):
+            _same_bits(_plan_run(c, N, transposed), fresh[dev, N], (dev, N, transposed))
+
+
+@pytest.mark.parametrize("transposed", [1, 0], ids=["transposing", "in_place"])
+def test_two_contexts_keep_their_own_launch_plans(transposed):
+    """two contexts alive at once, each at mesh 16 and 24 in turn, on either pipeline.  Both sit on device 0 here, where the
+    plans of one context would serve the other as well: this also passed while the resident-workgroup counts were statics of
+    fft3d.hip, and guards the per-context table from now on."""
+    _two_contexts(0, transposed)
+
+
+def test_one_context_keeps_a_plan_per_mesh_size():
+    """meshes 16, 40, 16 on one context: the third result has the first one's bits.  40 has a radix-5 stage and another LDS size, so
+    a plan reused across sizes would launch with the wrong dynamic LDS at least.  The statics this table replaces were per mesh
+    size too: this passed before it."""
+    with sq.Context(0) as c:
+        first = _plan_run(c, 16, 1)
+        _plan_run(c, 40, 1)
+        _same_bits(_plan_run(c, 16, 1), first, "16 after 40")
+
+
+@pytest.mark.parametrize("transposed", [1, 0], ids=["transposing", "in_place"])
+def test_two_contexts_on_two_devices_keep_their_own_launch_plans(transposed):
+    """the two-context test with the second context on device 1, which got the first device's CU count and no
+    hipFuncSetAttribute call of its own while the counts were statics: the one case here that could fail before the table"""
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs torch.cuda.device_count() > 1: the second context sits on device 1")
+    _two_contexts(1, transposed)
