@@ -1684,6 +1684,63 @@ int shq_glass_setup_positions(int Ngrid, double BoxSize, double shift, int seed,
  * Power / Nmodes / Norm * BoxSize_in_MPC^3 and kk / Nmodes * 2 pi / BoxSize_in_MPC, moved to the front.  *nonzero: how many remain. */
 int shq_glass_finish_power(int size, double BoxSize_in_MPC, double *kk, double *power, int64_t *nmodes, double norm, int *nonzero);
 
+/* ---- Thermal velocities (add_thermal_speeds with init_rng and init_thermalvel, libgenic/thermal.cpp:44-110, as genic/main.cpp:162-187
+ * calls them for warm dark matter and main.cpp:215-228 for neutrino particles) ----  one rank's sub-block of the Ngrid^3 lattice.
+ * The reference reseeds one boost::random::ranlux48 at the start of every grid column (x, y) from a table of seeds and takes three
+ * uniform draws per particle along z: a Fermi-Dirac speed through the inverse cumulative table, then an isotropic direction.  The
+ * columns are independent, so the device runs one engine per lane.
+ * Two readings of boost are taken without a boost build to check them against, and everything below rests on them:
+ *  - boost::random::ranlux48 is std::ranlux48, discard_block<subtract_with_carry<48, 5, 12>, 389, 11> seeded through the LCG
+ *    40014 x mod 2147483563 (boost documents the standard's 10000th value, 249142670248501; the device engine is checked against
+ *    libstdc++'s), and uniform_01<double> on it is one output times 2^-48, exact and below 1, so it never redraws;
+ *  - boost::math::interpolators::makima is the modified Akima slopes (two ghost secants per side, m[-1] = 2 m[0] - m[1], weights
+ *    |m[i+1] - m[i]| + |m[i+1] + m[i]| / 2, slope 0 where both weights vanish; equal to scipy's makima) in a cubic Hermite evaluated as
+ *    t = (p - x[i]) / dx,  F = (1 - t)^2 (y[i] (1 + 2 t) + s[i] (p - x[i])) + t^2 (y[i+1] (3 - 2 t) + dx s[i+1] (t - 1)),
+ *    in the bin i = the last knot with x[i] <= p, at most 1998.  The order of operations inside F is this library's choice. */
+#define SHQ_THERMAL_NKNOTS 2000  /* LENGTH_FERMI_DIRAC_TABLE, thermal.h:10 */
+typedef struct shq_thermal_params {
+    int32_t Ngrid;               /* >= 2: the lattice of this species (All2.Ngrid or All2.NGridNu) */
+    int32_t x0, nx, y0, ny;      /* the rank's sub-block x in [x0, x0 + nx), y in [y0, y0 + ny), every z (idgen_init, zeldovich.cpp:47-65) */
+    int32_t pad_;
+    double v_amp;                /* thermalvel.m_vamp: NU_V0 or WDM_V0 as the caller forms it */
+} shq_thermal_params;
+/* Host only: init_rng (thermal.cpp:77-91).  One ranlux48((uint32_t) Seed) gives Ngrid^2 outputs, i outer and j inner, each truncated
+ * to 32 bits and stored at table[i + Ngrid * j]: the reference's storage order, which shq_thermal_speeds takes as it is.
+ * SHQ_ERR_INVALID for Ngrid outside 1 .. 46340 (Ngrid^2 fits an int) or a NULL table. */
+int shq_thermal_seed_table(int Seed, int Ngrid, uint32_t *table);
+/* Host only: init_thermalvel's tables (thermal.cpp:44-75) for callers without the reference's struct, SHQ_THERMAL_NKNOTS entries each:
+ * max_fd is clipped to 17; vel[i] = min_fd + (max_fd - min_fd) * i / 1999.0; cumprob[i] = the integral of x^2 / (e^x + 1) from min_fd
+ * to vel[i] over its last entry (so cumprob[1999] is exactly 1); *total_frac = that last entry over the integral from 0 to 17.
+ * The integrals are 8-point Gauss-Legendre sums per knot interval, converged far below 1e-12 relative; the reference's adaptive
+ * Gauss-Kronrod rule stops at a looser bound, so its tables differ in the last digits and a reference-side caller passes its own.
+ * SHQ_ERR_INVALID for max_fd <= min_fd (after the clip too), a non-finite bound, or a NULL pointer. */
+int shq_thermal_tables(double max_fd, double min_fd, double *vel, double *cumprob, double *total_frac);
+/* The particle loop of main.cpp:176-184 / 218-226 for one rank:
+ *   seedtable : host [Ngrid^2] as shq_thermal_seed_table stores it.  Local particle i is x = i / (ny Ngrid) + x0,
+ *               y = (i mod (ny Ngrid)) / Ngrid + y0, z = i mod Ngrid; its id is x Ngrid^2 + y Ngrid + z + 1, its column id / Ngrid =
+ *               x Ngrid + y, seeded with seedtable[x Ngrid + y]: draw number y Ngrid + x of the table's stream, the reference's
+ *               transposition kept
+ *   cumprob, fdvel : host [2000], thermalvel.fermi_dirac_cumprob and fermi_dirac_vel
+ *   vel       : in/out host float [n][3], n = nx ny Ngrid, in the rank's particle order
+ *   dvel      : out [n][3] or NULL, the double increments exactly as they are added;  speed : out [n] or NULL, each particle's v
+ * Per particle three draws in this order: p, v = v_amp * F(p);  phi = (2 * M_PI) * u;  theta = acos(2 * u - 1).  The increments are
+ * (v sin theta) cos phi, (v sin theta) sin phi, v cos theta, each added as Vel = (float) ((double) Vel + inc).  No product is fused
+ * into an add, so vel_out == float32(float64(vel_in) + dvel) holds bit for bit.  speed follows the evaluation order above with IEEE
+ * operations only; the increments carry the device's sin, cos and acos.  The makima slopes are made once per call on the host.
+ * SHQ_ERR_INVALID before anything is written for Ngrid < 2 (at Ngrid = 1 the reference indexes past its own table), a sub-block outside
+ * the grid, n != nx ny Ngrid or n >= 2^31, a NULL required pointer, a non-finite v_amp or table entry, cumprob[0] != 0,
+ * cumprob[1999] != 1, or a cumprob or fdvel that is not strictly increasing.
+ * The call owns its buffers: the resident particle set and tree, the PM mesh and its result, a pending spectrum, the resident Zel'dovich
+ * field and the deposit settings survive.  One upload, one download.  Synchronous. */
+int shq_thermal_speeds(shq_context *ctx, const shq_thermal_params *params, const uint32_t *seedtable, const double *cumprob,
+                       const double *fdvel, int64_t n, float *vel, double *dvel, double *speed);
+/* HIP-event durations (ms) of the last shq_thermal_speeds: [0] the upload, [1] the kernel, [2] all of it on the device, the download
+ * included. */
+int shq_thermal_phase_ms(shq_context *ctx, double ms[3]);
+/* Test entry for the engine: n engines (n <= 65536), engine t seeded with seeds[t]; raw: out [n][m], the first m outputs of each
+ * (1 <= m <= 2^20). */
+int shq_thermal_column_draws(shq_context *ctx, int n, const uint32_t *seeds, int m, uint64_t *raw);
+
 #ifdef __cplusplus
 }
 #endif

@@ -674,6 +674,49 @@ def glass_evolve(ctx, Nmesh, BoxSize, pos, vel, mass, nsteps=14, spectra=False, 
     return out
 
 
+def thermal_seed_table(Seed, Ngrid):
+    """init_rng (libgenic/thermal.cpp:77-91; host only): Ngrid^2 uint32 in the reference's storage order, draw (i outer, j inner) at
+    [i + Ngrid * j]; column (x, y) of the lattice is seeded with entry x * Ngrid + y"""
+    table = np.zeros(int(Ngrid) ** 2, dtype=np.uint32)
+    capi.check(capi.hip.shq_thermal_seed_table(int(Seed), int(Ngrid), capi.ptr(table)), "thermal_seed_table")
+    return table
+
+
+def thermal_tables(max_fd, min_fd=0.0):
+    """init_thermalvel's tables (thermal.cpp:44-75; host only): (fermi_dirac_vel [2000], fermi_dirac_cumprob [2000], total_frac)"""
+    vel, cumprob = np.zeros(capi.THERMAL_NKNOTS), np.zeros(capi.THERMAL_NKNOTS)
+    frac = C.c_double()
+    capi.check(capi.hip.shq_thermal_tables(float(max_fd), float(min_fd), capi.ptr(vel), capi.ptr(cumprob), C.byref(frac)), "thermal_tables")
+    return vel, cumprob, frac.value
+
+
+def thermal_speeds(ctx, vel, Ngrid, v_amp, seedtable, cumprob, fdvel, x0=0, nx=None, y0=0, ny=None, want_dvel=False, want_speed=False):
+    """add_thermal_speeds over one rank's particles (genic/main.cpp:176-184, 218-226) on the device.  vel: float32 [n][3] of the
+    sub-block x in [x0, x0 + nx), y in [y0, y0 + ny), every z, in the rank's particle order (the whole lattice by default); it is not
+    modified.  seedtable as thermal_seed_table returns it, cumprob / fdvel as thermal_tables does.  Returns dict(Vel, dvel, speed,
+    phase_ms): the new velocities, and on request the double increments [n][3] and the speeds [n]."""
+    Ngrid = int(Ngrid)
+    nx = Ngrid - int(x0) if nx is None else int(nx)
+    ny = Ngrid - int(y0) if ny is None else int(ny)
+    vel = np.array(vel, dtype=np.float32, order="C")
+    n = len(vel)
+    if vel.shape != (n, 3):
+        raise ValueError("thermal_speeds: vel is [n][3]")
+    seedtable = np.ascontiguousarray(seedtable, dtype=np.uint32).ravel()
+    cumprob = np.ascontiguousarray(cumprob, dtype=np.float64)
+    fdvel = np.ascontiguousarray(fdvel, dtype=np.float64)
+    if len(seedtable) != Ngrid * Ngrid or cumprob.shape != (capi.THERMAL_NKNOTS,) or fdvel.shape != (capi.THERMAL_NKNOTS,):
+        raise ValueError(f"thermal_speeds: the seed table has Ngrid^2 entries, the tables {capi.THERMAL_NKNOTS}")
+    tp = capi.ThermalParams(Ngrid, int(x0), nx, int(y0), ny, 0, float(v_amp))
+    out = dict(Vel=vel, dvel=np.zeros((n, 3)) if want_dvel else None, speed=np.zeros(n) if want_speed else None)
+    capi.check(capi.hip.shq_thermal_speeds(ctx.h, C.byref(tp), capi.ptr(seedtable), capi.ptr(cumprob), capi.ptr(fdvel), n, capi.ptr(vel),
+                                           capi.ptr(out["dvel"]), capi.ptr(out["speed"])), "thermal_speeds")
+    ms = (C.c_double * 3)()
+    capi.check(capi.hip.shq_thermal_phase_ms(ctx.h, C.byref(ms)), "thermal_phase_ms")
+    out["phase_ms"] = list(ms)
+    return out
+
+
 def synth_positions(kind, n, seed=20240601, L=1.0):
     """SURVEY §8(d) synthetic inputs: kind 'grid' | 'uniform' | 'cluster'."""
     k = {"grid": 0, "uniform": 1, "cluster": 2}[kind]

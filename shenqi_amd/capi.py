@@ -763,6 +763,26 @@ hip.shq_glass_setup_positions.restype = C.c_int
 hip.shq_glass_finish_power.argtypes = [C.c_int, C.c_double, _vp, _vp, _vp, C.c_double, C.POINTER(C.c_int)]
 hip.shq_glass_finish_power.restype = C.c_int
 
+THERMAL_NKNOTS = 2000
+
+
+class ThermalParams(C.Structure):
+    """shq_thermal_params: the lattice, the rank's sub-block of columns and thermalvel.m_vamp"""
+    _fields_ = [("Ngrid", C.c_int32), ("x0", C.c_int32), ("nx", C.c_int32), ("y0", C.c_int32), ("ny", C.c_int32), ("pad_", C.c_int32),
+                ("v_amp", C.c_double)]
+
+
+hip.shq_thermal_seed_table.argtypes = [C.c_int, C.c_int, _vp]
+hip.shq_thermal_seed_table.restype = C.c_int
+hip.shq_thermal_tables.argtypes = [C.c_double, C.c_double, _vp, _vp, C.POINTER(C.c_double)]
+hip.shq_thermal_tables.restype = C.c_int
+hip.shq_thermal_speeds.argtypes = [_vp, C.POINTER(ThermalParams), _vp, _vp, _vp, C.c_int64, _vp, _vp, _vp]
+hip.shq_thermal_speeds.restype = C.c_int
+hip.shq_thermal_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 3)]
+hip.shq_thermal_phase_ms.restype = C.c_int
+hip.shq_thermal_column_draws.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp]
+hip.shq_thermal_column_draws.restype = C.c_int
+
 
 class YieldTables(C.Structure):
     """shq_yield_tables: the caller's lifetime / AGB / SNII / SN Ia tables, laid out value[mass index * nmet + metallicity index]"""

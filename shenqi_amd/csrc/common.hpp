@@ -499,6 +499,8 @@ struct shq_context {
     double zel_ms[4] = {0, 0, 0, 0};      /* shq_zeldovich_phase_ms */
     /* ---- glass making (glass.hip): a call allocates and frees its own device buffers; only its times stay behind */
     double glass_ms[4] = {0, 0, 0, 0};    /* shq_glass_phase_ms */
+    /* ---- thermal velocities (thermal.hip): a call allocates and frees its own device buffers; only its times stay behind */
+    double thermal_ms[3] = {0, 0, 0};     /* shq_thermal_phase_ms */
     /* ---- stellar yields (yields.hip): the caller's tables of shq_yields_init and the per-call work arrays */
     bool yld_have = false;
     YieldDesc yld_desc = {};
