@@ -1741,6 +1741,118 @@ int shq_thermal_phase_ms(shq_context *ctx, double ms[3]);
  * (1 <= m <= 2^20). */
 int shq_thermal_column_draws(shq_context *ctx, int n, const uint32_t *seeds, int m, uint64_t *raw);
 
+/* ---- radiative cooling (cooling_direct, libgadget/sfr_eff.cpp:430-481; DoCooling / GetCoolingTime, cooling.cpp:42-163; the rate network,
+ * cooling_rates.cpp:293-305, 499-683, 1101-1214; TableMetalCoolingRate and get_local_UVBG, cooling_uvfluc.cpp:142-214, 321-335) ----------
+ * The library evaluates no rate fit and reads no file: the caller hands over the table block init_cooling_rates builds, the interpolated
+ * UVBG, the metal table and the Zreion table as data.  One engine (csrc/cooling_math.hpp) serves the device and the host entry.
+ * Per particle the outcome is one of four; none ends the call, and a particle whose status is not OK is left exactly as it came: */
+#define SHQ_COOL_OK 0        /* computed */
+#define SHQ_COOL_DEFERRED 1  /* a rate lookup left the table (T >~ 9.8e8 K or T < 1/e K) where the reference calls the fit: the caller's own
+                                cooling_direct takes this particle */
+#define SHQ_COOL_BADINPUT 2  /* non-finite temperature, non-positive or non-finite density or energy */
+#define SHQ_COOL_NOCONV 3    /* MAXITER (1000) iterations of the fixed point or of the bisection, where the reference ends the run */
+#define SHQ_COOL_NSTATUS 4
+#define SHQ_COOL_NRECOMBTAB 1000
+typedef struct shq_cooling_uvbg { /* struct UVBG, cooling.h:9-19 */
+    double J_UV, gJH0, gJHep, gJHe0, epsH0, epsHep, epsHe0, self_shield_dens, zreion;
+} shq_cooling_uvbg;
+typedef struct shq_cooling_tables {
+    const double *rate_tables;    /* [14][1000]: temp_tab as init_cooling_rates lays it out (:989-1024); row 0 (logt) is not read */
+    int32_t cooling;              /* enum CoolingType: 0 KWH92, 1 Enzo2Nyx, 2 Sherwood */
+    int32_t SelfShieldingOn, HeliumHeatOn, pad_;
+    double MinGasTemp, CMBTemperature, HeliumHeatThresh, HeliumHeatAmp, HeliumHeatExp;
+    double rho_crit_baryon;       /* cooling_params.rho_crit_baryon */
+    double fBar;
+    double density_in_phys_cgs, uu_in_cgs, tt_in_s;   /* cooling_units */
+    const double *metal;          /* NetCoolingRate [dims[0]][dims[1]][dims[2]] over (redshift, log10 nH, log10 T), or NULL: no metal cooling */
+    int32_t metal_dims[3], pad2_; /* each >= 2 */
+    double metal_min[3], metal_max[3];
+    const double *zreion;         /* UVF.Table [Nside]^3 or NULL */
+    int32_t zreion_nside, pad3_;
+    double zreion_boxsize;        /* the table's axes run 0 .. BoxSize as init_uvf_table sets them (Step = BoxSize / (Nside - 1)) */
+} shq_cooling_tables;
+/* The per-run data, copied to the device and kept until replaced.  SHQ_ERR_INVALID for a NULL rate block, a non-finite rate entry, a
+ * cooling type outside 0..2, a metal axis shorter than 2 or with max <= min, Nside < 2, or units that are not finite and > 0. */
+int shq_cooling_set_tables(shq_context *ctx, const shq_cooling_tables *tables);
+/* 1 (default): a wave hands a finished lane the next particle of its workgroup's share of the list, as schedule(guided) does in the
+ * reference's loop.  0: one particle per lane.  The results are the same bit for bit. */
+int shq_cooling_set_refill(shq_context *ctx, int on);
+
+/* Array-level queries on internal-unit inputs (physical density, as the reference's callers pass it): */
+#define SHQ_COOL_UNEW 0       /* DoCooling(redshift, u, rho, dt, uvbg, &ne, Z, MinEgySpec, heiii)                       ne in/out */
+#define SHQ_COOL_TCOOL 1      /* GetCoolingTime(redshift, u, rho, uvbg, &ne, Z)                                         ne in/out */
+#define SHQ_COOL_NH0 2        /* GetNeutralFraction(u, rho, uvbg, ne)                                                   ne in */
+#define SHQ_COOL_HE0 3        /* GetHeliumIonFraction(0, u, rho, uvbg, ne)                                              ne in */
+#define SHQ_COOL_HEP 4        /* GetHeliumIonFraction(1, ...) */
+#define SHQ_COOL_HEPP 5       /* GetHeliumIonFraction(2, ...) */
+#define SHQ_COOL_TEMP 6       /* get_temp(rho cgs, u cgs, 1 - HYDROGEN_MASSFRAC, uvbg, &ne), K                          ne in/out */
+#define SHQ_COOL_LAMBDANET 7  /* get_lambdanet of cooling.cpp:42-52, erg / s / g                                        ne in/out */
+/*   rho, u, ne : [n];  Z, heiii (bytes), dt : [n], read by UNEW (Z also by TCOOL and LAMBDANET, heiii also by LAMBDANET), may be NULL
+ *                otherwise and then count as 0
+ *   min_egy_spec : DoCooling's MinEgySpec, internal units;  lmfp_heat : get_long_mean_free_path_heating(z) / (rho_crit_baryon (1+z)^3), added
+ *                to the net rate of particles whose heiii byte is 0
+ *   out, status : [n]; out is written only where status is SHQ_COOL_OK, as is ne;  steps : [n] or NULL, evaluations of ne_internal
+ * shq_cooling_eval needs shq_cooling_set_tables first (SHQ_ERR_STATE) and is synchronous; one upload, one kernel, one download.
+ * shq_cooling_eval_host runs the same engine on the CPU over threads and needs neither a context nor a GPU; its results are those of
+ * the reference's arithmetic with glibc's libm, evaluation for evaluation. */
+int shq_cooling_eval(shq_context *ctx, int what, int64_t n, const double *rho, const double *u, double *ne, const double *Z, const uint8_t *heiii,
+                     const double *dt, const shq_cooling_uvbg *uvbg, double redshift, double min_egy_spec, double lmfp_heat, double *out, int32_t *status,
+                     int32_t *steps);
+int shq_cooling_eval_host(const shq_cooling_tables *tables, int what, int64_t n, const double *rho, const double *u, double *ne, const double *Z,
+                          const uint8_t *heiii, const double *dt, const shq_cooling_uvbg *uvbg, double redshift, double min_egy_spec, double lmfp_heat,
+                          double *out, int32_t *status, int32_t *steps, int nthreads);
+/* cooling_direct (sfr_eff.cpp:430-481) for the active gas of one rank: one call in place of the cooling_direct iterations of
+ * cooling_and_starformation's loop (they are independent of the star-forming ones: cooling_direct writes only its own particle).
+ * Star formation stays with the caller: particles on the effective equation of state are skipped, untouched, and handed back. */
+typedef struct shq_cooling_fields { /* byte offsets in the SPH slot record; all doubles */
+    size_t off_ne, off_metallicity, off_sfr, off_delaytime;
+} shq_cooling_fields;
+#define SHQ_COOL_UVBG_GLOBAL 0   /* every particle sees GlobalUVBG */
+#define SHQ_COOL_UVBG_ZREION 1   /* get_local_UVBG_from_global with the Zreion table of shq_cooling_set_tables: eval_periodic at Pos - offset, the
+                                    rates zero while zreion < redshift */
+#define SHQ_COOL_UVBG_J21 2      /* get_local_UVBG_from_J21: the excursion set's local_J21 and zreion per gas slot */
+typedef struct shq_cooling_step {
+    double redshift, a3inv, hubble;
+    shq_kick_factors kf;                        /* dloga_for_bin is read */
+    double lastred_for_bin[SHQ_TIMEBINS + 1];   /* 1 / exp(loga_from_ti(Ti_Current - dti_from_timebin(bin))) - 1: active particles are drifted to Ti_Current */
+    shq_cooling_uvbg GlobalUVBG;                /* get_global_UVBG(redshift) */
+    int32_t uvbg_mode;                          /* SHQ_COOL_UVBG_* */
+    int32_t StarformationOn;
+    double HIReionTemp, temp_to_u, MinGasTemp;  /* sfr_params */
+    double lmfp_heat;                           /* get_long_mean_free_path_heating(z) / (rho_crit_baryon (1+z)^3), for particles without SHQ_FLAG_HEIII */
+    double CurrentParticleOffset[3];
+    double PhysDensThresh, OverDensThresh;      /* sfr_params, read when no on_eeqos mask is given */
+    /* SHQ_COOL_UVBG_J21 only: */
+    const double *local_J21, *zreion;           /* by gas slot */
+    double J21_coeffs[6];                       /* struct J21_coeffs of get_J21_coeffs(AlphaUV): gJH0, gJHep, gJHe0, epsH0, epsHep, epsHe0 */
+    double ss_greyopac_factor;                  /* pow(greyopac / 2.49e-18, -2./3) of get_self_shield_dens at this redshift */
+    double ss_fbar_factor;                      /* pow(fBar / 0.17, -1./3); the device forms 6.73e-3 * A * pow(G12, 2./3) * C in the reference's order */
+} shq_cooling_step;
+typedef struct shq_cooling_result {
+    int64_t n_status[SHQ_COOL_NSTATUS];  /* cooled particles by outcome */
+    int64_t n_skipped;                   /* not gas, garbage or Mass <= 0 (sfr_eff.cpp:238) */
+    int64_t n_eeqos, n_deferred;         /* entries the two lists would hold */
+    int64_t steps;                       /* evaluations of ne_internal, summed */
+    double kernel_ms;                    /* HIP-event time of the cooling kernel */
+} shq_cooling_result;
+/*   parts / sph : Pos, Mass, Type, PI, the flag byte, TimeBinHydro and what shq_sph_state_upload needs; Density, Entropy, DelayTime through PI.
+ *                 Uploaded, or skipped under shq_set_inputs_current, as in shq_winds_evolve and shq_heiii_reionization.
+ *   list, nlist : the active particles (NULL with nlist == NumPart: all)
+ *   on_eeqos    : bytes by particle index, the caller's sfreff_on_eeqos, or NULL: the device then applies its three clauses (:510-517:
+ *                 Density a3inv >= PhysDensThresh, Density >= OverDensThresh, DelayTime <= 0).  BHFeedbackUseTcool == 2 adds a fourth
+ *                 clause that needs a cooling time per candidate: such a caller MUST pass the mask.
+ *   eeqos, deferred : out, particle indices in list order: those on the effective equation of state, and the cooled ones that came back
+ *                 SHQ_COOL_DEFERRED.  A list shorter than its count is SHQ_ERR_NOMEM after everything else has been written; the result
+ *                 holds the counts.
+ * Skipped particles and those whose status is not OK are bit-unchanged.  Cooled ones get Ne, Entropy = unew / enttou and Sfr = 0 in the
+ * caller's records; the context's Entropy copy is updated alike.  SHQ_ERR_STATE without shq_cooling_set_tables, or for the Zreion mode
+ * without a Zreion table.  Synchronous. */
+int shq_cooling(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_cooling_fields *fields, const int32_t *list, int64_t nlist,
+                const shq_cooling_step *step, const uint8_t *on_eeqos, int32_t *eeqos, int64_t eeqos_capacity, int32_t *deferred, int64_t deferred_capacity,
+                shq_cooling_result *result);
+/* HIP-event time of the last cooling kernel of the context (shq_cooling_eval or shq_cooling), ms, and the engine steps it summed */
+int shq_cooling_last_kernel(shq_context *ctx, double *ms, int64_t *steps);
+
 #ifdef __cplusplus
 }
 #endif

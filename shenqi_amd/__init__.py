@@ -534,6 +534,104 @@ def metal_return_postprocess(ctx, pman, StarP, queue, MassReturn, StellarAges):
                "metal_return_postprocess")
 
 
+def cooling_tables(rate_tables, cooling=2, SelfShieldingOn=1, MinGasTemp=100.0, CMBTemperature=2.7255, HeliumHeatOn=0, HeliumHeatThresh=10.0,
+                   HeliumHeatAmp=1.0, HeliumHeatExp=0.0, rho_crit_baryon=0.0, fBar=0.17, density_in_phys_cgs=1.0, uu_in_cgs=1.0, tt_in_s=1.0,
+                   metal=None, metal_min=None, metal_max=None, zreion=None, zreion_boxsize=0.0):
+    """shq_cooling_tables from the caller's data: rate_tables is init_cooling_rates' temp_tab, [14][1000]; metal the NetCoolingRate table
+    [nz][nnH][nT] with the first and last node of each axis; zreion the UVF table [Nside]^3.  The struct keeps the arrays alive."""
+    t = capi.CoolingTables()
+    keep = [np.ascontiguousarray(rate_tables, dtype=np.float64)]
+    if keep[0].shape != (14, 1000):
+        raise ValueError("cooling_tables: rate_tables must be [14][1000]")
+    t.rate_tables = keep[0].ctypes.data
+    t.cooling, t.SelfShieldingOn, t.HeliumHeatOn = int(cooling), int(SelfShieldingOn), int(HeliumHeatOn)
+    t.MinGasTemp, t.CMBTemperature, t.HeliumHeatThresh, t.HeliumHeatAmp, t.HeliumHeatExp = MinGasTemp, CMBTemperature, HeliumHeatThresh, HeliumHeatAmp, HeliumHeatExp
+    t.rho_crit_baryon, t.fBar = rho_crit_baryon, fBar
+    t.density_in_phys_cgs, t.uu_in_cgs, t.tt_in_s = density_in_phys_cgs, uu_in_cgs, tt_in_s
+    if metal is not None:
+        m = np.ascontiguousarray(metal, dtype=np.float64)
+        if m.ndim != 3:
+            raise ValueError("cooling_tables: the metal table has three axes")
+        keep.append(m)
+        t.metal = m.ctypes.data
+        for d in range(3):
+            t.metal_dims[d], t.metal_min[d], t.metal_max[d] = m.shape[d], metal_min[d], metal_max[d]
+    if zreion is not None:
+        z = np.ascontiguousarray(zreion, dtype=np.float64)
+        if z.ndim != 3 or len(set(z.shape)) != 1:
+            raise ValueError("cooling_tables: the Zreion table is a cube")
+        keep.append(z)
+        t.zreion, t.zreion_nside, t.zreion_boxsize = z.ctypes.data, z.shape[0], zreion_boxsize
+    t._keep = keep
+    return t
+
+
+def cooling_uvbg(**kw):
+    """shq_cooling_uvbg (struct UVBG) from keywords or a mapping's items"""
+    u = capi.CoolingUVBG()
+    for k, v in kw.items():
+        setattr(u, k, float(v))
+    return u
+
+
+def cooling_set_tables(ctx, tables):
+    """shq_cooling_set_tables: copy the per-run cooling data (cooling_tables) to the device"""
+    capi.check(capi.hip.shq_cooling_set_tables(ctx.h, C.byref(tables)), "cooling_set_tables")
+
+
+def cooling_set_refill(ctx, on):
+    capi.check(capi.hip.shq_cooling_set_refill(ctx.h, int(bool(on))), "cooling_set_refill")
+
+
+def _cooling_eval(call, head, what, rho, u, ne, Z, heiii, dt, uvbg, redshift, min_egy_spec, lmfp_heat, tail=()):
+    rho, u = np.ascontiguousarray(rho, dtype=np.float64), np.ascontiguousarray(u, dtype=np.float64)
+    n = len(rho)
+    ne = np.array(np.broadcast_to(np.asarray(ne, dtype=np.float64), (n,)))
+    opt = [None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=t), (n,))) for a, t in ((Z, np.float64), (heiii, np.uint8), (dt, np.float64))]
+    out, status, steps = np.full(n, np.nan), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    capi.check(call(head, capi.COOL_WHAT[what], n, capi.ptr(rho), capi.ptr(u), capi.ptr(ne), capi.ptr(opt[0]), capi.ptr(opt[1]), capi.ptr(opt[2]), C.byref(uvbg),
+                    float(redshift), float(min_egy_spec), float(lmfp_heat), capi.ptr(out), capi.ptr(status), capi.ptr(steps), *tail), "cooling_eval")
+    return out, ne, status, steps
+
+
+def cooling_eval(ctx, what, rho, u, ne, uvbg, redshift, Z=None, heiii=None, dt=None, min_egy_spec=0.0, lmfp_heat=0.0):
+    """shq_cooling_eval: one of "UNEW" (DoCooling), "TCOOL" (GetCoolingTime), "NH0", "HE0", "HEP", "HEPP", "TEMP", "LAMBDANET" for arrays of
+    internal-unit physical densities and energies on the device.  Returns (out, ne after, status, engine steps); out is NaN where the
+    status is not capi.COOL_OK."""
+    return _cooling_eval(capi.hip.shq_cooling_eval, ctx.h, what, rho, u, ne, Z, heiii, dt, uvbg, redshift, min_egy_spec, lmfp_heat)
+
+
+def cooling_eval_host(tables, what, rho, u, ne, uvbg, redshift, Z=None, heiii=None, dt=None, min_egy_spec=0.0, lmfp_heat=0.0, nthreads=0):
+    """shq_cooling_eval_host: cooling_eval on the CPU with the same engine; needs no context and no GPU"""
+    return _cooling_eval(capi.hip.shq_cooling_eval_host, C.byref(tables), what, rho, u, ne, Z, heiii, dt, uvbg, redshift, min_egy_spec, lmfp_heat, (int(nthreads),))
+
+
+def cooling(ctx, pman, SphP, step, active=None, on_eeqos=None):
+    """shq_cooling: cooling_direct (sfr_eff.cpp:430-481) for the active gas on the device.  step: capi.CoolingStep.  Cooled particles get Ne,
+    Entropy and Sfr = 0 in SphP.  Returns (capi.CoolingResult, the particles on the effective equation of state, the deferred ones), both
+    lists in list order."""
+    pv, sv = pman.view(), capi.sph_view(SphP)
+    f = SphP.dtype.fields
+    cf = capi.CoolingFields(f["Ne"][1], f["Metallicity"][1], f["Sfr"][1], f["DelayTime"][1])
+    act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+    cnt = pman.NumPart if act is None else len(act)
+    mask = None if on_eeqos is None else np.ascontiguousarray(on_eeqos, dtype=np.uint8)
+    if mask is not None and len(mask) != pman.NumPart:
+        raise ValueError("cooling: on_eeqos has one byte per particle")
+    eeqos, deferred = np.zeros(max(cnt, 1), dtype=np.int32), np.zeros(max(cnt, 1), dtype=np.int32)
+    res = capi.CoolingResult()
+    capi.check(capi.hip.shq_cooling(ctx.h, C.byref(pv), C.byref(sv), C.byref(cf), capi.ptr(act), cnt, C.byref(step), capi.ptr(mask), capi.ptr(eeqos), cnt,
+                                    capi.ptr(deferred), cnt, C.byref(res)), "cooling")
+    return res, eeqos[:res.n_eeqos].copy(), deferred[:res.n_deferred].copy()
+
+
+def cooling_last_kernel(ctx):
+    """(HIP-event ms, engine steps) of the context's last cooling kernel"""
+    ms, st = C.c_double(), C.c_int64()
+    capi.check(capi.hip.shq_cooling_last_kernel(ctx.h, C.byref(ms), C.byref(st)), "cooling_last_kernel")
+    return ms.value, st.value
+
+
 class IDGenerator:
     """idgen_init on one rank (libgenic/zeldovich.cpp:46-65): the whole Ngrid^3 lattice"""
 

@@ -826,6 +826,58 @@ hip.shq_metal_return_postprocess.restype = C.c_int
 hip.shq_metal_yields_last_ms.argtypes = [_vp, C.POINTER(C.c_double * 2)]
 hip.shq_metal_yields_last_ms.restype = C.c_int
 
+# ---- radiative cooling -------------------------------------------------------------------------
+COOL_OK, COOL_DEFERRED, COOL_BADINPUT, COOL_NOCONV = 0, 1, 2, 3
+COOL_WHAT = {"UNEW": 0, "TCOOL": 1, "NH0": 2, "HE0": 3, "HEP": 4, "HEPP": 5, "TEMP": 6, "LAMBDANET": 7}
+COOL_UVBG_GLOBAL, COOL_UVBG_ZREION, COOL_UVBG_J21 = 0, 1, 2
+
+
+class CoolingUVBG(C.Structure):
+    """shq_cooling_uvbg (struct UVBG)"""
+    _fields_ = [(k, C.c_double) for k in ("J_UV", "gJH0", "gJHep", "gJHe0", "epsH0", "epsHep", "epsHe0", "self_shield_dens", "zreion")]
+
+
+class CoolingTables(C.Structure):
+    """shq_cooling_tables"""
+    _fields_ = [("rate_tables", _vp), ("cooling", C.c_int32), ("SelfShieldingOn", C.c_int32), ("HeliumHeatOn", C.c_int32), ("pad_", C.c_int32),
+                ("MinGasTemp", C.c_double), ("CMBTemperature", C.c_double), ("HeliumHeatThresh", C.c_double), ("HeliumHeatAmp", C.c_double),
+                ("HeliumHeatExp", C.c_double), ("rho_crit_baryon", C.c_double), ("fBar", C.c_double),
+                ("density_in_phys_cgs", C.c_double), ("uu_in_cgs", C.c_double), ("tt_in_s", C.c_double),
+                ("metal", _vp), ("metal_dims", C.c_int32 * 3), ("pad2_", C.c_int32), ("metal_min", C.c_double * 3), ("metal_max", C.c_double * 3),
+                ("zreion", _vp), ("zreion_nside", C.c_int32), ("pad3_", C.c_int32), ("zreion_boxsize", C.c_double)]
+
+
+class CoolingFields(C.Structure):
+    """shq_cooling_fields"""
+    _fields_ = [("off_ne", C.c_size_t), ("off_metallicity", C.c_size_t), ("off_sfr", C.c_size_t), ("off_delaytime", C.c_size_t)]
+
+
+class CoolingStep(C.Structure):
+    """shq_cooling_step"""
+    _fields_ = [("redshift", C.c_double), ("a3inv", C.c_double), ("hubble", C.c_double), ("kf", KickFactors),
+                ("lastred_for_bin", C.c_double * (TIMEBINS + 1)), ("GlobalUVBG", CoolingUVBG), ("uvbg_mode", C.c_int32), ("StarformationOn", C.c_int32),
+                ("HIReionTemp", C.c_double), ("temp_to_u", C.c_double), ("MinGasTemp", C.c_double), ("lmfp_heat", C.c_double),
+                ("CurrentParticleOffset", C.c_double * 3), ("PhysDensThresh", C.c_double), ("OverDensThresh", C.c_double),
+                ("local_J21", _vp), ("zreion", _vp), ("J21_coeffs", C.c_double * 6), ("ss_greyopac_factor", C.c_double), ("ss_fbar_factor", C.c_double)]
+
+
+class CoolingResult(C.Structure):
+    """shq_cooling_result"""
+    _fields_ = [("n_status", C.c_int64 * 4), ("n_skipped", C.c_int64), ("n_eeqos", C.c_int64), ("n_deferred", C.c_int64), ("steps", C.c_int64),
+                ("kernel_ms", C.c_double)]
+
+
+hip.shq_cooling_set_tables.argtypes = [_vp, C.POINTER(CoolingTables)]
+hip.shq_cooling_set_refill.argtypes = [_vp, C.c_int]
+_cool_eval_tail = [C.c_int, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(CoolingUVBG), C.c_double, C.c_double, C.c_double, _vp, _vp, _vp]
+hip.shq_cooling_eval.argtypes = [_vp] + _cool_eval_tail
+hip.shq_cooling_eval_host.argtypes = [C.POINTER(CoolingTables)] + _cool_eval_tail + [C.c_int]
+hip.shq_cooling.argtypes = [_vp, C.POINTER(PartView), C.POINTER(SphView), C.POINTER(CoolingFields), _vp, C.c_int64, C.POINTER(CoolingStep), _vp, _vp, C.c_int64,
+                            _vp, C.c_int64, C.POINTER(CoolingResult)]
+hip.shq_cooling_last_kernel.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+for _f in ("shq_cooling_set_tables", "shq_cooling_set_refill", "shq_cooling_eval", "shq_cooling_eval_host", "shq_cooling", "shq_cooling_last_kernel"):
+    getattr(hip, _f).restype = C.c_int
+
 hip.shq_treepm_last_fused.argtypes = [_vp, C.POINTER(C.c_int)]
 hip.shq_treepm_set_fuse.argtypes = [_vp, C.c_int]
 hip.shq_pm_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 6)]

@@ -243,6 +243,8 @@ extern "C" void shq_shutdown(shq_context *ctx)
     ctx->mesh_words = 0; ctx->mesh_zeroed = false; ctx->mesh_alt.release();
     ctx->zel_spec.release(); ctx->zel_have = false;
     ctx->yld_tab.release(); ctx->yld_time.release(); ctx->yld_in.release(); ctx->yld_out.release(); ctx->yld_i32.release(); ctx->yld_mark.release();
+    ctx->cool_ion.release(); ctx->cool_rates.release(); ctx->cool_metal.release(); ctx->cool_zreion.release(); ctx->cool_d.release(); ctx->cool_i.release();
+    ctx->cool_b.release(); ctx->cool_cnt.release();
     ctx->gravtab.release(); ctx->stage.release();
     ctx->node_hmax.release(); ctx->pfather.release();
     ctx->hsml.release(); ctx->dthsml.release(); ctx->vel.release(); ctx->bin_grav.release(); ctx->bin_hydro.release();

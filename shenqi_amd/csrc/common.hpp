@@ -10,6 +10,7 @@
 #include <vector>
 #include "../../include/shenqi_hip.h"
 #include "yields_math.hpp"
+#include "cooling_math.hpp"
 
 void shq_set_error(const char *fmt, ...);
 
@@ -512,6 +513,20 @@ struct shq_context {
     DevBuf<int32_t> yld_i32;
     DevBuf<uint8_t> yld_mark;
     double yld_ms[2] = {0, 0};            /* shq_metal_yields_last_ms */
+    /* ---- radiative cooling (cooling.hip): the caller's tables of shq_cooling_set_tables and the per-call work arrays */
+    bool cool_have = false;
+    CoolPar cool_par = {};
+    double cool_fbar = 0;
+    DevBuf<double> cool_ion, cool_rates, cool_metal, cool_zreion;   /* [1000][6], [1000][8], the metal table, the Zreion table */
+    int cool_znside = 0;
+    double cool_zbox = 0;
+    int cool_refill = 1;                  /* shq_cooling_set_refill */
+    DevBuf<double> cool_d;                /* per-call doubles */
+    DevBuf<int32_t> cool_i;               /* per-call ints */
+    DevBuf<uint8_t> cool_b;               /* per-call bytes */
+    DevBuf<unsigned long long> cool_cnt;
+    double cool_ms = 0;                   /* shq_cooling_last_kernel */
+    int64_t cool_steps = 0;
 };
 
 /* capi.hip: make the main stream wait for an outstanding asynchronous PM run */
@@ -719,6 +734,30 @@ int shq_bh_accretion_device(shq_context *ctx, const shq_kick_factors *kf, const 
 int shq_bh_feedback_device(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, const int32_t *d_queue, int64_t nq);
 /* the particles marked in `mark` (one byte each), ascending, into d_list (room for n entries); *m = their number (one host round trip) */
 int shq_marked_list(shq_context *ctx, const uint8_t *d_mark, int64_t n, int32_t *d_list, int64_t *m);
+
+/* cooling.hip: the device half of shq_cooling.  Arrays by particle index unless said otherwise. */
+struct CoolPartArgs {
+    const int32_t *list;       /* the particles to cool */
+    const double4 *posm;
+    const uint8_t *pflags, *bin;
+    const double *density, *metallicity, *j21, *zre;
+    double *entropy, *ne;
+    int32_t *status, *steps;   /* by position in list */
+    const double *dloga_for_bin, *lastred_for_bin; /* [SHQ_TIMEBINS + 1] */
+    const double *ztab;
+    int znside, mode;
+    double zbox, offset[3];
+    CoolUV global;
+    double j21c[6], ss_grey, ss_fbar;
+    double redshift, a3inv, hubble, HIReionTemp, temp_to_u, MinGasTemp, lmfp;
+};
+/* by list position (d_list NULL: every particle): the particles to cool and those on the effective equation of state, both in list order */
+int shq_cooling_classify_device(shq_context *ctx, const int32_t *d_list, int64_t cnt, const uint8_t *d_mask, int StarformationOn, double PhysDensThresh,
+                                double OverDensThresh, double a3inv, int32_t *d_cool, int64_t *ncool, int32_t *d_eeqos, int64_t *neeqos);
+int shq_cooling_run_device(shq_context *ctx, const CoolPartArgs *a, int64_t ncool);
+/* cooling_host.hip: the caller's tables as the engine reads them: the scalars, and the two interleaved rate tables */
+int shq_cooling_tables_to_engine(const shq_cooling_tables *t, CoolPar *P, std::vector<double> *ion, std::vector<double> *rates);
+CoolUV shq_cooling_uv(const shq_cooling_uvbg *u);
 /* rows of eight doubles for the particles of d_list: vx, vy, vz, entropy, delay time, mass word of posm, flag byte, `extra` byte (or 0) */
 int shq_rows_gather(shq_context *ctx, const int32_t *d_list, int64_t m, const uint8_t *d_extra, double *d_rows);
 int shq_u64_gather(shq_context *ctx, const int32_t *d_list, int64_t m, const unsigned long long *d_src, unsigned long long *d_out);

@@ -1729,3 +1729,145 @@ extern "C" int shq_winds_subgrid(shq_context *ctx, const shq_part_view *parts, c
         *nkicked = (int64_t) h;
     return SHQ_OK;
 }
+
+/* ---- cooling_direct for the active gas (sfr_eff.cpp:430-481); the kernels are cooling.hip's ------------------------------------------ */
+extern "C" int shq_cooling(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_cooling_fields *fields, const int32_t *list, int64_t nlist,
+                           const shq_cooling_step *step, const uint8_t *on_eeqos, int32_t *eeqos, int64_t eeqos_capacity, int32_t *deferred, int64_t deferred_capacity,
+                           shq_cooling_result *result)
+{
+    SHQ_CHECK(ctx && parts && sph && fields && step && result, SHQ_ERR_INVALID, "null argument");
+    SHQ_CHECK(nlist >= 0 && (nlist == 0 || list || nlist == parts->numpart), SHQ_ERR_INVALID, "cooling: nlist = %ld without a list", (long) nlist);
+    SHQ_CHECK(eeqos_capacity >= 0 && deferred_capacity >= 0 && (eeqos || eeqos_capacity == 0) && (deferred || deferred_capacity == 0), SHQ_ERR_INVALID,
+              "cooling: an output list is NULL");
+    SHQ_CHECK(sph->off_delaytime != SHQ_NOFIELD && parts->off_timebin_hydro != SHQ_NOFIELD && parts->off_flags != SHQ_NOFIELD && parts->off_mass != SHQ_NOFIELD,
+              SHQ_ERR_INVALID, "cooling: needs DelayTime, the hydro time bin, the flag byte and Mass");
+    SHQ_CHECK(fields->off_ne + 8 <= sph->elsize && fields->off_metallicity + 8 <= sph->elsize && fields->off_sfr + 8 <= sph->elsize, SHQ_ERR_INVALID,
+              "cooling: Ne, Metallicity and Sfr must lie inside the slot record");
+    SHQ_CHECK(step->uvbg_mode >= SHQ_COOL_UVBG_GLOBAL && step->uvbg_mode <= SHQ_COOL_UVBG_J21, SHQ_ERR_INVALID, "cooling: uvbg_mode = %d", step->uvbg_mode);
+    SHQ_CHECK(step->uvbg_mode != SHQ_COOL_UVBG_J21 || (step->local_J21 && step->zreion), SHQ_ERR_INVALID, "cooling: the J21 mode needs local_J21 and zreion");
+    SHQ_CHECK(step->hubble > 0 && step->a3inv > 0, SHQ_ERR_INVALID, "cooling: hubble and a3inv must be > 0");
+    SHQ_TRY(winds_list_check(parts, list, nlist, false, "cooling"));
+    SHQ_CHECK(ctx->cool_have, SHQ_ERR_STATE, "cooling: shq_cooling_set_tables first");
+    SHQ_CHECK(step->uvbg_mode != SHQ_COOL_UVBG_ZREION || ctx->cool_znside >= 2, SHQ_ERR_STATE, "cooling: the Zreion mode needs a Zreion table");
+    memset(result, 0, sizeof(*result));
+    SHQ_HIP(hipSetDevice(ctx->device));
+    SHQ_TRY(shq_particles_upload(ctx, parts));
+    SHQ_TRY(sph_upload(ctx, parts, sph));
+    const int64_t n = parts->numpart, cnt = list ? nlist : n;
+    if(cnt == 0)
+        return SHQ_OK;
+    hipStream_t st = ctx->stream;
+    const size_t N = (size_t) n, C = (size_t) cnt;
+    const bool j21 = step->uvbg_mode == SHQ_COOL_UVBG_J21;
+    /* Ne and Metallicity (and the excursion set's two fields) by particle index, as sph_upload lays out the other gas fields */
+    const int ncol = j21 ? 4 : 2;
+    std::vector<double> h((size_t) ncol * N, 0.0);
+    for(int64_t i = 0; i < n; i++) {
+        if(*pfield<uint8_t>(parts, i, parts->off_type) != 0)
+            continue;
+        const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+        SHQ_CHECK(pi >= 0 && pi < sph->numslots, SHQ_ERR_INVALID, "cooling: gas particle %ld with PI outside the SPH slot array", (long) i);
+        h[(size_t) i] = *sfield(sph, pi, fields->off_ne);
+        h[N + (size_t) i] = *sfield(sph, pi, fields->off_metallicity);
+        if(j21) {
+            h[2 * N + (size_t) i] = step->local_J21[pi];
+            h[3 * N + (size_t) i] = step->zreion[pi];
+        }
+    }
+    const size_t NB = 2 * (size_t) (SHQ_TIMEBINS + 1);
+    SHQ_TRY(ctx->cool_d.reserve((size_t) ncol * N + NB));
+    SHQ_TRY(ctx->cool_i.reserve(5 * C));
+    double *d = ctx->cool_d.ptr;
+    SHQ_HIP(hipMemcpyAsync(d, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
+    double *d_bins = d + (size_t) ncol * N;
+    SHQ_HIP(hipMemcpyAsync(d_bins, step->kf.dloga_for_bin, sizeof(double) * (SHQ_TIMEBINS + 1), hipMemcpyHostToDevice, st));
+    SHQ_HIP(hipMemcpyAsync(d_bins + SHQ_TIMEBINS + 1, step->lastred_for_bin, sizeof(double) * (SHQ_TIMEBINS + 1), hipMemcpyHostToDevice, st));
+    int32_t *d_cool = ctx->cool_i.ptr, *d_eeqos = d_cool + C, *d_status = d_eeqos + C, *d_steps = d_status + C, *d_list = nullptr;
+    if(list) {
+        d_list = d_steps + C;
+        SHQ_HIP(hipMemcpyAsync(d_list, list, sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
+    }
+    const uint8_t *d_mask = nullptr;
+    if(on_eeqos) {
+        SHQ_TRY(ctx->bhw_touched.reserve(N));
+        SHQ_HIP(hipMemcpyAsync(ctx->bhw_touched.ptr, on_eeqos, N, hipMemcpyHostToDevice, st));
+        d_mask = ctx->bhw_touched.ptr;
+    }
+    int64_t ncool = 0, neeqos = 0;
+    SHQ_TRY(shq_cooling_classify_device(ctx, d_list, cnt, d_mask, step->StarformationOn, step->PhysDensThresh, step->OverDensThresh, step->a3inv, d_cool, &ncool, d_eeqos,
+                                        &neeqos));
+    CoolPartArgs a;
+    memset(&a, 0, sizeof(a));
+    a.list = d_cool;
+    a.posm = ctx->posm.ptr;
+    a.pflags = ctx->pflags.ptr;
+    a.bin = ctx->bin_hydro.ptr;
+    a.density = ctx->g_density.ptr;
+    a.entropy = ctx->g_entropy.ptr;
+    a.ne = d;
+    a.metallicity = d + N;
+    a.j21 = j21 ? d + 2 * N : nullptr;
+    a.zre = j21 ? d + 3 * N : nullptr;
+    a.status = d_status;
+    a.steps = d_steps;
+    a.dloga_for_bin = d_bins;
+    a.lastred_for_bin = d_bins + SHQ_TIMEBINS + 1;
+    a.ztab = ctx->cool_zreion.ptr;
+    a.znside = ctx->cool_znside;
+    a.zbox = ctx->cool_zbox;
+    a.mode = step->uvbg_mode;
+    for(int j = 0; j < 3; j++)
+        a.offset[j] = step->CurrentParticleOffset[j];
+    const shq_cooling_uvbg &g = step->GlobalUVBG;
+    a.global = CoolUV{g.gJH0, g.gJHep, g.gJHe0, g.epsH0, g.epsHep, g.epsHe0, g.self_shield_dens, g.zreion};
+    for(int j = 0; j < 6; j++)
+        a.j21c[j] = step->J21_coeffs[j];
+    a.ss_grey = step->ss_greyopac_factor;
+    a.ss_fbar = step->ss_fbar_factor;
+    a.redshift = step->redshift;
+    a.a3inv = step->a3inv;
+    a.hubble = step->hubble;
+    a.HIReionTemp = step->HIReionTemp;
+    a.temp_to_u = step->temp_to_u;
+    a.MinGasTemp = step->MinGasTemp;
+    a.lmfp = step->lmfp_heat;
+    SHQ_TRY(shq_cooling_run_device(ctx, &a, ncool));
+    result->kernel_ms = ctx->cool_ms;
+    result->steps = ctx->cool_steps;
+    result->n_eeqos = neeqos;
+    std::vector<int32_t> hcool((size_t) std::max<int64_t>(ncool, 1)), hstat((size_t) std::max<int64_t>(ncool, 1)), heq((size_t) std::max<int64_t>(neeqos, 1));
+    std::vector<double> hent(N), hne(N);
+    if(ncool > 0) {
+        SHQ_HIP(hipMemcpyAsync(hcool.data(), d_cool, sizeof(int32_t) * (size_t) ncool, hipMemcpyDeviceToHost, st));
+        SHQ_HIP(hipMemcpyAsync(hstat.data(), d_status, sizeof(int32_t) * (size_t) ncool, hipMemcpyDeviceToHost, st));
+        SHQ_HIP(hipMemcpyAsync(hent.data(), ctx->g_entropy.ptr, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+        SHQ_HIP(hipMemcpyAsync(hne.data(), d, sizeof(double) * N, hipMemcpyDeviceToHost, st));
+    }
+    if(neeqos > 0)
+        SHQ_HIP(hipMemcpyAsync(heq.data(), d_eeqos, sizeof(int32_t) * (size_t) neeqos, hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipStreamSynchronize(st));
+    for(int64_t k = 0; k < neeqos && k < eeqos_capacity; k++)
+        eeqos[k] = heq[(size_t) k];
+    /* the skipped ones: what the classification dropped */
+    result->n_skipped = cnt - ncool - neeqos;
+    for(int64_t k = 0; k < ncool; k++) {
+        const int64_t i = hcool[(size_t) k];
+        const int s = hstat[(size_t) k];
+        SHQ_CHECK(s >= 0 && s < SHQ_COOL_NSTATUS, SHQ_ERR_DEVICE, "cooling: status %d from the device", s);
+        result->n_status[s]++;
+        if(s == SHQ_COOL_DEFERRED) {
+            if(result->n_deferred < deferred_capacity)
+                deferred[result->n_deferred] = (int32_t) i;
+            result->n_deferred++;
+        }
+        if(s != SHQ_COOL_OK)
+            continue;
+        const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+        *sfield(sph, pi, fields->off_ne) = hne[(size_t) i];
+        *sfield(sph, pi, sph->off_entropy) = hent[(size_t) i];
+        *sfield(sph, pi, fields->off_sfr) = 0;
+    }
+    SHQ_CHECK(neeqos <= eeqos_capacity, SHQ_ERR_NOMEM, "cooling: %ld particles on the effective equation of state, room for %ld", (long) neeqos, (long) eeqos_capacity);
+    SHQ_CHECK(result->n_deferred <= deferred_capacity, SHQ_ERR_NOMEM, "cooling: %ld deferred particles, room for %ld", (long) result->n_deferred, (long) deferred_capacity);
+    return SHQ_OK;
+}
