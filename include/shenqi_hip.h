@@ -530,10 +530,10 @@ int shq_slots_split_particles(shq_context *ctx, const shq_exchange_layout *layou
 int shq_slots_convert(shq_context *ctx, const shq_exchange_layout *layout, void *d_parts, int64_t numpart, int64_t MaxPart, void *const d_slots[6],
                       int64_t slot_size[6], const int64_t slot_maxsize[6], const int32_t *d_index, int64_t n, int ptype);
 
-/* Scope note: star formation itself (the sfr_eff.cpp criteria, cooling, the random draws) is OUT of scope; this entry is
- * kept only as the slot-manager side of it — the one place where slots_convert / slots_split_particle (the
- * row these belong to) have to fill a freshly converted slot from another slot array while both stay in HBM.  The caller decides
- * who forms a star; nothing here evaluates star-formation physics.
+/* Scope note: this entry is the slot-manager side of star formation — the one place where slots_convert / slots_split_particle
+ * (the row these belong to) have to fill a freshly converted slot from another slot array while both stay in HBM.
+ * Nothing here evaluates star-formation physics: who forms a star is decided by the caller, or per particle by the engine of the
+ * "star formation" block at the end of this header (shq_sfr_eval: the sfr_eff.cpp criteria, the eeqos relaxation, the random draws).
  * make_particle_star (libgadget/sfr_eff.cpp:604-630) for the lists of the star-formation merge step (:344-372): entry k converts
  * children[k] (the parent itself, or the particle split off it) to a star at slot firststarslot + k and fills the slot from the
  * PARENT's gas slot as it was before the conversion: FormationTime = Time, LastEnrichmentMyr = TotalMassReturned = 0, BirthDensity,
@@ -1803,7 +1803,7 @@ int shq_cooling_eval_host(const shq_cooling_tables *tables, int what, int64_t n,
                           double *out, int32_t *status, int32_t *steps, int nthreads);
 /* cooling_direct (sfr_eff.cpp:430-481) for the active gas of one rank: one call in place of the cooling_direct iterations of
  * cooling_and_starformation's loop (they are independent of the star-forming ones: cooling_direct writes only its own particle).
- * Star formation stays with the caller: particles on the effective equation of state are skipped, untouched, and handed back. */
+ * Particles on the effective equation of state are skipped, untouched, and handed back as a list: the input of shq_starformation. */
 typedef struct shq_cooling_fields { /* byte offsets in the SPH slot record; all doubles */
     size_t off_ne, off_metallicity, off_sfr, off_delaytime;
 } shq_cooling_fields;
@@ -1840,7 +1840,7 @@ typedef struct shq_cooling_result {
  *   list, nlist : the active particles (NULL with nlist == NumPart: all)
  *   on_eeqos    : bytes by particle index, the caller's sfreff_on_eeqos, or NULL: the device then applies its three clauses (:510-517:
  *                 Density a3inv >= PhysDensThresh, Density >= OverDensThresh, DelayTime <= 0).  BHFeedbackUseTcool == 2 adds a fourth
- *                 clause that needs a cooling time per candidate: such a caller MUST pass the mask.
+ *                 clause that needs a cooling time per candidate: such a caller MUST pass the mask, which shq_sfr_on_eeqos computes.
  *   eeqos, deferred : out, particle indices in list order: those on the effective equation of state, and the cooled ones that came back
  *                 SHQ_COOL_DEFERRED.  A list shorter than its count is SHQ_ERR_NOMEM after everything else has been written; the result
  *                 holds the counts.
@@ -1852,6 +1852,154 @@ int shq_cooling(shq_context *ctx, const shq_part_view *parts, const shq_sph_view
                 shq_cooling_result *result);
 /* HIP-event time of the last cooling kernel of the context (shq_cooling_eval or shq_cooling), ms, and the engine steps it summed */
 int shq_cooling_last_kernel(shq_context *ctx, double *ms, int64_t *steps);
+
+/* ---- star formation on the effective equation of state ("eeqos"; libgadget/sfr_eff.cpp: sfreff_on_eeqos :502-533, the *_sfreff fractions
+ * :536-600, cooling_relaxed :633-668, quicklyastarformation :673-692, starformation :698-767, get_sfr_eeqos :771-809,
+ * get_starformation_rate_full :811-830, get_egyeff :833-846, find_star_mass :970-991, the H2 and self-gravity factors :1009-1080) --------
+ * One engine (csrc/sfr_math.hpp) on top of the cooling engine serves the device and the host entry.  A particle needs between zero and
+ * three GetCoolingTime solves; the statuses are the cooling engine's (SHQ_COOL_*): DEFERRED when a rate lookup left the table in any of
+ * the solves (a BH-heated energy above ~1e8 K can do this; the reference's own starformation() takes the particle), BADINPUT, NOCONV.  A
+ * particle whose status is not OK is not written and forms no star. */
+typedef struct shq_sfr_params { /* what the engine reads of sfr_params */
+    int32_t StarformationCriterion;   /* the reference's enum values: 1 density, 3 H2, 5 self-gravity, 13 convergent flow, 21 continuous cutoff */
+    int32_t BHFeedbackUseTcool;       /* 0..3 */
+    int32_t Generations;              /* >= 1 */
+    int32_t BoostSFDenseGas;
+    int32_t winds_subgrid;            /* WindOn && winds_are_subgrid() */
+    int32_t pad_;
+    double PhysDensThresh, OverDensThresh, EgySpecSN, EgySpecCold, FactorSN, FactorEVP, MaxSfrTimescale, tau_fmol_unit;
+    double QuickLymanAlphaProbability, QuickLymanAlphaTempThresh, avg_baryon_mass, temp_to_u, UnitSfr_in_solar_per_year;
+    double BoostSFOverDenseFactor, GravInternal;
+} shq_sfr_params;
+typedef struct shq_sfr_arrays { /* [n] each */
+    const double *Density, *Entropy, *Ne, *Metallicity, *Mass;
+    const double *Hsml, *DivVel, *CurlVel;   /* read by the H2 / self-gravity factors; NULL counts as 0 */
+    const double *GradRho;                   /* |GradRho|; NULL unless StarformationCriterion has the H2 bits (then SHQ_ERR_INVALID, the reference's endrun) */
+    const double *dloga;                     /* get_dloga_for_bin(TimeBinHydro, Ti_drift) */
+    const double *DelayTime;                 /* NULL: 0 */
+    const uint8_t *timebin;                  /* TimeBinHydro */
+    const uint8_t *flags;                    /* the particle flag byte: bit 3 BHHeated, bits 4-7 Generation */
+    const uint64_t *ID;
+} shq_sfr_arrays;
+typedef struct shq_sfr_eval_step {
+    double redshift, a3inv, hubble;
+    shq_cooling_uvbg GlobalUVBG;   /* read by get_egyeff: the fourth clause of sfreff_on_eeqos, and the EGYEFF query */
+    shq_cooling_uvbg LocalUVBG;    /* get_local_UVBG's result, read by get_sfr_eeqos, cooling_relaxed and the fractions */
+    const double *rnd_table;       /* RandTable::Table: get_random_number(id) = rnd_table[id % rnd_size] */
+    int64_t rnd_size;
+} shq_sfr_eval_step;
+/* what to evaluate */
+#define SHQ_SFR_STARFORM 0    /* starformation() for every particle given; with QuickLymanAlphaProbability > 0 quicklyastarformation and, for a
+                                 hit, the conversion of the parent with sm = Mass: no eeqos physics runs */
+#define SHQ_SFR_EGYEFF 1      /* get_egyeff(redshift, Density, GlobalUVBG): Density is the argument as it stands; its tsfr and egyhot in their rows */
+#define SHQ_SFR_NH0 2         /* get_neutral_fraction_sfreff */
+#define SHQ_SFR_HE0 3         /* get_helium_neutral_fraction_sfreff(0, ...) */
+#define SHQ_SFR_HEP 4         /* ... (1, ...) */
+#define SHQ_SFR_HEPP 5        /* ... (2, ...) */
+#define SHQ_SFR_ON_EEQOS 6    /* sfreff_on_eeqos, all four clauses: bit 0 of the branch byte */
+#define SHQ_SFR_NWHAT 7
+/* rows of out [SHQ_SFR_NOUT][n] */
+#define SHQ_SFR_O_TRELAX 0        /* sfr_eeqos_data: trelax, tsfr, egyhot, egycold, cloudfrac, ne; their initial values when not on the eeqos */
+#define SHQ_SFR_O_TSFR 1
+#define SHQ_SFR_O_EGYHOT 2
+#define SHQ_SFR_O_EGYCOLD 3
+#define SHQ_SFR_O_CLOUDFRAC 4
+#define SHQ_SFR_O_NE_EEQOS 5
+#define SHQ_SFR_O_SMR 6           /* get_starformation_rate_full */
+#define SHQ_SFR_O_SM 7            /* smr * dtime: StellarMass of the subgrid winds */
+#define SHQ_SFR_O_DM 8            /* sum_sm's addend */
+#define SHQ_SFR_O_SFR 9           /* SPHP.Sfr: localsfr's addend */
+#define SHQ_SFR_O_NE 10           /* the record's new Ne, Metallicity, Entropy */
+#define SHQ_SFR_O_METALLICITY 11
+#define SHQ_SFR_O_ENTROPY 12
+#define SHQ_SFR_O_MASS_OF_STAR 13
+#define SHQ_SFR_O_PROB 14
+#define SHQ_SFR_O_QUERY 15        /* the value of EGYEFF / NH0 / HE0 / HEP / HEPP */
+#define SHQ_SFR_O_EGYEFF4 16      /* get_egyeff of the fourth clause (BHFeedbackUseTcool == 2), 0 when it did not run */
+#define SHQ_SFR_O_TCOOL_RELAX 17  /* cooling_relaxed's cooling time, 0 when it did not run */
+#define SHQ_SFR_O_EGYEFF 18       /* cooling_relaxed's egyeff and egycurrent, 0 when it did not run */
+#define SHQ_SFR_O_EGYCURRENT 19
+#define SHQ_SFR_O_TRELAX_USED 20  /* the relaxation time after the tcool < trelax test */
+#define SHQ_SFR_O_DTIME 21        /* dloga / hubble: sum_dtime's addend */
+#define SHQ_SFR_O_FACTOREVP 22    /* get_sfr_eeqos' factorEVP, cooling_relaxed's entropy_to_u, starformation's 1 - exp(-p); 0 when not computed */
+#define SHQ_SFR_O_DENSITYFAC 23
+#define SHQ_SFR_O_FRAC 24
+#define SHQ_SFR_NOUT 25
+/* the decision byte */
+#define SHQ_SFR_NONE 0
+#define SHQ_SFR_CONVERT 1     /* the parent becomes the star */
+#define SHQ_SFR_SPLIT 2       /* Mass >= 1.1 mass_of_star: slots_split_particle(parent, mass_of_star) */
+/* the branch byte: which way the particle went */
+#define SHQ_SFR_B_ON_EEQOS 1u   /* sfreff_on_eeqos */
+#define SHQ_SFR_B_CLAUSE4 2u    /* its fourth clause was evaluated */
+#define SHQ_SFR_B_TCOOL 4u      /* cooling_relaxed computed a cooling time (egycurrent > egyeff inside the BHFeedbackUseTcool clause) */
+#define SHQ_SFR_B_TCOOL_WON 8u  /* tcool < trelax && tcool > 0 */
+#define SHQ_SFR_B_STAR 16u      /* the draw was below prob */
+#define SHQ_SFR_B_RELAXED 32u   /* dloga > 0 && TimeBinHydro: cooling_relaxed ran */
+/*   out         : [SHQ_SFR_NOUT][n]; column k is written only where status[k] is SHQ_COOL_OK, as are the three bytes of k
+ *   flags_out   : the flag byte with BHHeated cleared where cooling_relaxed clears it;  decision : SHQ_SFR_NONE / _CONVERT / _SPLIT
+ *   steps       : [n] or NULL, evaluations of ne_internal over all solves of the particle
+ * shq_sfr_eval needs shq_cooling_set_tables first (SHQ_ERR_STATE) and is synchronous: one upload, one kernel, one download.  The random
+ * table is staged in the context's buffer that the winds and black-hole entries use.  shq_sfr_eval_host runs the same engine on the CPU
+ * over threads and needs neither a context nor a GPU; its results are those of the reference's arithmetic with glibc's libm.
+ * SHQ_ERR_INVALID for Generations < 1, an empty random table, or a NULL GradRho with the H2 bits set. */
+int shq_sfr_eval(shq_context *ctx, const shq_sfr_params *par, int what, int64_t n, const shq_sfr_arrays *in, const shq_sfr_eval_step *step, double *out,
+                 uint8_t *flags_out, uint8_t *decision, uint8_t *branch, int32_t *status, int32_t *steps);
+int shq_sfr_eval_host(const shq_cooling_tables *tables, const shq_sfr_params *par, int what, int64_t n, const shq_sfr_arrays *in, const shq_sfr_eval_step *step,
+                      double *out, uint8_t *flags_out, uint8_t *decision, uint8_t *branch, int32_t *status, int32_t *steps, int nthreads);
+/* 1 (default): a finished lane takes the next particle of its workgroup's share, as in shq_cooling_set_refill.  0: one particle per lane.
+ * Each particle is written by exactly one lane: the results are the same bit for bit. */
+int shq_sfr_set_refill(shq_context *ctx, int on);
+/* HIP-event time of the context's last star-formation kernel, ms, and the engine steps it summed */
+int shq_sfr_last_kernel(shq_context *ctx, double *ms, int64_t *steps);
+
+/* The star-forming branch of cooling_and_starformation (sfr_eff.cpp:252-276) for one rank: one call in place of the reference's
+ * starformation() iterations over the particles on the effective equation of state.  The call chain of a step is
+ *   shq_winds_evolve -> shq_sfr_on_eeqos (BHFeedbackUseTcool == 2 only) -> shq_cooling -> shq_starformation ->
+ *   shq_slots_split_particles -> shq_make_particle_stars;  add_new_particle_to_active / copy_gravaccel_new_particle stay with the caller. */
+typedef struct shq_sfr_fields { /* byte offsets in the SPH slot record; all doubles */
+    size_t off_ne, off_metallicity, off_sfr;
+    size_t off_delaytime;   /* must equal the SPH view's off_delaytime (SHQ_ERR_INVALID otherwise): DelayTime is staged with the view's fields */
+} shq_sfr_fields;
+typedef struct shq_sfr_result {
+    int64_t n_status[SHQ_COOL_NSTATUS];  /* list entries by outcome */
+    int64_t n_skipped;                   /* not gas, garbage or Mass <= 0 */
+    int64_t n_newstars, n_split;         /* entries NewParents would hold, and how many of them split */
+    int64_t n_maybewind, n_deferred;     /* entries the other two lists would hold */
+    int64_t sum_sf_part;                 /* particles that formed stars or were considered for it: the OK ones (quick Lyman-alpha: the hits) */
+    double localsfr, sum_sm, sum_dtime;  /* the reference's three reductions.  The per-particle addends (Sfr, dM, dtime) are formed on the
+                                            device and added here on the host, left to right in list order, so the sums are reproducible
+                                            bit for bit; the reference's OpenMP reduction has no defined order. */
+    int64_t steps;                       /* evaluations of ne_internal, summed */
+    double kernel_ms;                    /* HIP-event time of the kernel */
+} shq_sfr_result;
+/* sfreff_on_eeqos (:502-533) for the particles of a list, all four clauses on the device; the fourth (BHFeedbackUseTcool == 2) is one
+ * get_egyeff solve per particle that passed the first three.  on_eeqos: [numpart] bytes, written for every particle (0 off the list, for
+ * non-gas, garbage and Mass <= 0, and where the solve did not end OK): the form shq_cooling's on_eeqos argument takes.  Views, staging
+ * and shq_set_inputs_current as in shq_cooling; step->StarformationOn (0: every byte is 0, as :506 returns), GlobalUVBG and a3inv are
+ * read.  SHQ_ERR_STATE without shq_cooling_set_tables. */
+int shq_sfr_on_eeqos(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_sfr_params *par, const int32_t *list, int64_t nlist,
+                     const shq_cooling_step *step, uint8_t *on_eeqos);
+/*   parts / sph, fields : as in shq_cooling (uploaded, or taken as they are under shq_set_inputs_current)
+ *   ids          : particle IDs by particle index;  GradRho : |GradRho| by gas slot, NULL unless the H2 bits are set
+ *   list, nlist  : the particles on the effective equation of state, i.e. the eeqos list shq_cooling returned.  With
+ *                  QuickLymanAlphaProbability > 0 instead the active list: the call classifies it itself with quicklyastarformation
+ *                  (:673-692), every hit is a conversion of the parent with sm = Mass, no eeqos physics runs and no record is written.
+ *   step         : the shq_cooling_step of the step: redshift, a3inv, hubble, dloga_for_bin, the UVBG mode and its data
+ *   rnd_table    : RandTable::Table, staged in the context's buffer of the winds and black-hole entries
+ * Out, all in list order; a list shorter than its count is SHQ_ERR_NOMEM after everything else has been written, the result holds the counts:
+ *   NewParents, mass_of_star, split [newstar_capacity] : the particles that form a star; split[k] != 0: slots_split_particle(parent, mass_of_star).
+ *                  The split ones with their masses are the input of shq_slots_split_particles, all of them (children in place of the
+ *                  split parents) that of shq_make_particle_stars.
+ *   MaybeWind, sm [maybewind_capacity] : only with par->winds_subgrid, the particles that formed no star: shq_winds_subgrid's list and
+ *                  StellarMasses.
+ *   deferred [deferred_capacity] : SHQ_COOL_DEFERRED particles, bit-unchanged, for the reference's own starformation().
+ * OK particles get Sfr, Ne, Metallicity, Entropy and the cleared BHHeated bit in the caller's records; the context's Entropy copy is
+ * updated alike.  Everything else is bit-unchanged.  Synchronous. */
+int shq_starformation(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_sfr_fields *fields, const uint64_t *ids, const double *GradRho,
+                      const shq_sfr_params *par, const int32_t *list, int64_t nlist, const shq_cooling_step *step, const double *rnd_table, int64_t rnd_size,
+                      int32_t *NewParents, double *mass_of_star, uint8_t *split, int64_t newstar_capacity, int32_t *MaybeWind, double *sm, int64_t maybewind_capacity,
+                      int32_t *deferred, int64_t deferred_capacity, shq_sfr_result *result);
 
 #ifdef __cplusplus
 }

@@ -632,6 +632,120 @@ def cooling_last_kernel(ctx):
     return ms.value, st.value
 
 
+def sfr_params(**kw):
+    """shq_sfr_params (what the engine reads of sfr_params) from keywords; the reference's defaults where it has one"""
+    p = capi.SfrParams()
+    p.StarformationCriterion, p.Generations, p.FactorSN, p.FactorEVP = 1, 2, 0.1, 1000.0
+    p.QuickLymanAlphaTempThresh, p.BoostSFOverDenseFactor = 1e5, 1000.0
+    for k, v in kw.items():
+        if k not in dict(capi.SfrParams._fields_) or k == "pad_":
+            raise ValueError(f"sfr_params: no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+class SfrResult:
+    """what shq_sfr_eval returns: every row of `out` by name (capi.SFR_OUT), flags, decision, branch, status, steps.  Rows and bytes are
+    NaN / 255 where the status is not capi.COOL_OK."""
+
+    def __init__(self, out, flags, decision, branch, status, steps):
+        self.out, self.flags, self.decision, self.branch, self.status, self.steps = out, flags, decision, branch, status, steps
+        for r, k in enumerate(capi.SFR_OUT):
+            setattr(self, k, out[r])
+
+    def arrays(self):
+        return [self.out, self.flags, self.decision, self.branch, self.status, self.steps]
+
+
+def _sfr_eval(call, head, par, what, parts, uvbg_global, uvbg_local, redshift, a3inv, hubble, rnd_table, tail=()):
+    n = len(parts["Density"])
+    a, keep = capi.SfrArrays(), []
+    for k in capi.SFR_ARRAYS:
+        v = parts.get(k)
+        if v is None:
+            continue
+        t = np.uint64 if k == "ID" else (np.uint8 if k in ("timebin", "flags") else np.float64)
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=t), (n,)))
+        keep.append(v)
+        setattr(a, k, v.ctypes.data)
+    rnd = np.ascontiguousarray(rnd_table, dtype=np.float64)
+    st = capi.SfrEvalStep(float(redshift), float(a3inv), float(hubble), uvbg_global, uvbg_global if uvbg_local is None else uvbg_local, rnd.ctypes.data, len(rnd))
+    out = np.full((len(capi.SFR_OUT), n), np.nan)
+    flags, decision, branch = (np.full(n, 255, dtype=np.uint8) for _ in range(3))
+    status, steps = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    capi.check(call(head, C.byref(par), capi.SFR_WHAT[what], n, C.byref(a), C.byref(st), capi.ptr(out), capi.ptr(flags), capi.ptr(decision), capi.ptr(branch),
+                    capi.ptr(status), capi.ptr(steps), *tail), "sfr_eval")
+    return SfrResult(out, flags, decision, branch, status, steps)
+
+
+def sfr_eval(ctx, par, what, parts, uvbg_global, redshift, a3inv, hubble, rnd_table, uvbg_local=None):
+    """shq_sfr_eval: "STARFORM" (starformation() per particle, or quicklyastarformation under QuickLymanAlphaProbability > 0), "EGYEFF"
+    (get_egyeff), "NH0" / "HE0" / "HEP" / "HEPP" (the *_sfreff fractions) or "ON_EEQOS" (sfreff_on_eeqos, all four clauses) on the device.
+    parts: a mapping with the arrays of capi.SFR_ARRAYS (Hsml, DivVel, CurlVel, GradRho, DelayTime optional).  par: sfr_params().
+    Needs cooling_set_tables first.  Returns an SfrResult."""
+    return _sfr_eval(capi.hip.shq_sfr_eval, ctx.h, par, what, parts, uvbg_global, uvbg_local, redshift, a3inv, hubble, rnd_table)
+
+
+def sfr_eval_host(tables, par, what, parts, uvbg_global, redshift, a3inv, hubble, rnd_table, uvbg_local=None, nthreads=0):
+    """shq_sfr_eval_host: sfr_eval on the CPU with the same engine; needs no context and no GPU"""
+    return _sfr_eval(capi.hip.shq_sfr_eval_host, C.byref(tables), par, what, parts, uvbg_global, uvbg_local, redshift, a3inv, hubble, rnd_table, (int(nthreads),))
+
+
+def sfr_on_eeqos(ctx, pman, SphP, par, step, active=None):
+    """shq_sfr_on_eeqos: sfreff_on_eeqos with all four clauses for the active particles on the device; returns one byte per particle, the
+    form cooling()'s on_eeqos takes"""
+    pv, sv = pman.view(), capi.sph_view(SphP)
+    act = None if active is None else np.ascontiguousarray(active, dtype=np.int32)
+    cnt = pman.NumPart if act is None else len(act)
+    mask = np.zeros(max(pman.NumPart, 1), dtype=np.uint8)
+    capi.check(capi.hip.shq_sfr_on_eeqos(ctx.h, C.byref(pv), C.byref(sv), C.byref(par), capi.ptr(act), cnt, C.byref(step), capi.ptr(mask)), "sfr_on_eeqos")
+    return mask[:pman.NumPart]
+
+
+def starformation(ctx, pman, SphP, par, step, eeqos, ids, rnd_table, GradRho=None, capacity=None):
+    """shq_starformation: the star-forming branch of cooling_and_starformation for the particles of `eeqos` (what cooling() returned; under
+    QuickLymanAlphaProbability > 0 the active list) on the device.  OK particles get Sfr, Ne, Metallicity, Entropy and the cleared BHHeated
+    bit in pman / SphP.  Returns (capi.SfrResultC, (NewParents, mass_of_star, split), (MaybeWind, sm), deferred), all in list order.
+    capacity: room in each list (default: the list's length); the ShqError of a call that ran out of room carries the counts as .result."""
+    pv, sv = pman.view(), capi.sph_view(SphP)
+    f = SphP.dtype.fields
+    sf = capi.SfrFields(f["Ne"][1], f["Metallicity"][1], f["Sfr"][1], f["DelayTime"][1])
+    lst = np.ascontiguousarray(eeqos, dtype=np.int32)
+    ids = np.ascontiguousarray(ids, dtype=np.uint64)
+    rnd = np.ascontiguousarray(rnd_table, dtype=np.float64)
+    if len(ids) != pman.NumPart:
+        raise ValueError("starformation: ids has one entry per particle")
+    grad = None if GradRho is None else np.ascontiguousarray(GradRho, dtype=np.float64)
+    if grad is not None and len(grad) != len(SphP):
+        raise ValueError("starformation: GradRho has one entry per gas slot")
+    cap = len(lst) if capacity is None else int(capacity)
+    m = max(cap, 1)
+    parents, mos, split = np.zeros(m, dtype=np.int32), np.zeros(m), np.zeros(m, dtype=np.uint8)
+    wind, sm, deferred = np.zeros(m, dtype=np.int32), np.zeros(m), np.zeros(m, dtype=np.int32)
+    res = capi.SfrResultC()
+    rc = capi.hip.shq_starformation(ctx.h, C.byref(pv), C.byref(sv), C.byref(sf), capi.ptr(ids), capi.ptr(grad), C.byref(par), capi.ptr(lst), len(lst), C.byref(step),
+                                    capi.ptr(rnd), len(rnd), capi.ptr(parents), capi.ptr(mos), capi.ptr(split), cap, capi.ptr(wind), capi.ptr(sm), cap,
+                                    capi.ptr(deferred), cap, C.byref(res))
+    try:
+        capi.check(rc, "starformation")
+    except capi.ShqError as e:
+        e.result = res      # the counts of a call that ran out of room
+        raise
+    ns, nw, nd = res.n_newstars, res.n_maybewind, res.n_deferred
+    return res, (parents[:ns].copy(), mos[:ns].copy(), split[:ns].copy()), (wind[:nw].copy(), sm[:nw].copy()), deferred[:nd].copy()
+
+
+def sfr_set_refill(ctx, on):
+    capi.check(capi.hip.shq_sfr_set_refill(ctx.h, int(bool(on))), "sfr_set_refill")
+
+
+def sfr_last_kernel(ctx):
+    """(HIP-event ms, engine steps) of the context's last star-formation kernel"""
+    ms, st = C.c_double(), C.c_int64()
+    capi.check(capi.hip.shq_sfr_last_kernel(ctx.h, C.byref(ms), C.byref(st)), "sfr_last_kernel")
+    return ms.value, st.value
+
+
 class IDGenerator:
     """idgen_init on one rank (libgenic/zeldovich.cpp:46-65): the whole Ngrid^3 lattice"""
 

@@ -878,6 +878,61 @@ hip.shq_cooling_last_kernel.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.
 for _f in ("shq_cooling_set_tables", "shq_cooling_set_refill", "shq_cooling_eval", "shq_cooling_eval_host", "shq_cooling", "shq_cooling_last_kernel"):
     getattr(hip, _f).restype = C.c_int
 
+# ---- star formation on the effective equation of state -----------------------------------------
+SFR_WHAT = {"STARFORM": 0, "EGYEFF": 1, "NH0": 2, "HE0": 3, "HEP": 4, "HEPP": 5, "ON_EEQOS": 6}
+SFR_OUT = ("trelax", "tsfr", "egyhot", "egycold", "cloudfrac", "ne_eeqos", "smr", "sm", "dM", "Sfr", "Ne", "Metallicity", "Entropy", "mass_of_star", "prob",
+           "query", "egyeff4", "tcool_relax", "egyeff", "egycurrent", "trelax_used", "dtime", "factorEVP", "densityfac", "frac")
+SFR_NONE, SFR_CONVERT, SFR_SPLIT = 0, 1, 2
+SFR_B_ON_EEQOS, SFR_B_CLAUSE4, SFR_B_TCOOL, SFR_B_TCOOL_WON, SFR_B_STAR, SFR_B_RELAXED = 1, 2, 4, 8, 16, 32
+SFR_FLAG_BHHEATED = 8
+
+
+class SfrParams(C.Structure):
+    """shq_sfr_params"""
+    _fields_ = [(k, C.c_int32) for k in ("StarformationCriterion", "BHFeedbackUseTcool", "Generations", "BoostSFDenseGas", "winds_subgrid", "pad_")] + \
+               [(k, C.c_double) for k in ("PhysDensThresh", "OverDensThresh", "EgySpecSN", "EgySpecCold", "FactorSN", "FactorEVP", "MaxSfrTimescale", "tau_fmol_unit",
+                                          "QuickLymanAlphaProbability", "QuickLymanAlphaTempThresh", "avg_baryon_mass", "temp_to_u", "UnitSfr_in_solar_per_year",
+                                          "BoostSFOverDenseFactor", "GravInternal")]
+
+
+SFR_ARRAYS = ("Density", "Entropy", "Ne", "Metallicity", "Mass", "Hsml", "DivVel", "CurlVel", "GradRho", "dloga", "DelayTime", "timebin", "flags", "ID")
+
+
+class SfrArrays(C.Structure):
+    """shq_sfr_arrays"""
+    _fields_ = [(k, _vp) for k in SFR_ARRAYS]
+
+
+class SfrEvalStep(C.Structure):
+    """shq_sfr_eval_step"""
+    _fields_ = [("redshift", C.c_double), ("a3inv", C.c_double), ("hubble", C.c_double), ("GlobalUVBG", CoolingUVBG), ("LocalUVBG", CoolingUVBG),
+                ("rnd_table", _vp), ("rnd_size", C.c_int64)]
+
+
+class SfrFields(C.Structure):
+    """shq_sfr_fields"""
+    _fields_ = [("off_ne", C.c_size_t), ("off_metallicity", C.c_size_t), ("off_sfr", C.c_size_t), ("off_delaytime", C.c_size_t)]
+
+
+class SfrResultC(C.Structure):
+    """shq_sfr_result"""
+    _fields_ = [("n_status", C.c_int64 * 4), ("n_skipped", C.c_int64), ("n_newstars", C.c_int64), ("n_split", C.c_int64), ("n_maybewind", C.c_int64),
+                ("n_deferred", C.c_int64), ("sum_sf_part", C.c_int64), ("localsfr", C.c_double), ("sum_sm", C.c_double), ("sum_dtime", C.c_double),
+                ("steps", C.c_int64), ("kernel_ms", C.c_double)]
+
+
+hip.shq_sfr_on_eeqos.argtypes = [_vp, C.POINTER(PartView), C.POINTER(SphView), C.POINTER(SfrParams), _vp, C.c_int64, C.POINTER(CoolingStep), _vp]
+hip.shq_starformation.argtypes = [_vp, C.POINTER(PartView), C.POINTER(SphView), C.POINTER(SfrFields), _vp, _vp, C.POINTER(SfrParams), _vp, C.c_int64,
+                                  C.POINTER(CoolingStep), _vp, C.c_int64, _vp, _vp, _vp, C.c_int64, _vp, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(SfrResultC)]
+hip.shq_sfr_on_eeqos.restype = hip.shq_starformation.restype = C.c_int
+_sfr_eval_tail = [C.POINTER(SfrParams), C.c_int, C.c_int64, C.POINTER(SfrArrays), C.POINTER(SfrEvalStep), _vp, _vp, _vp, _vp, _vp, _vp]
+hip.shq_sfr_eval.argtypes = [_vp] + _sfr_eval_tail
+hip.shq_sfr_eval_host.argtypes = [C.POINTER(CoolingTables)] + _sfr_eval_tail + [C.c_int]
+hip.shq_sfr_set_refill.argtypes = [_vp, C.c_int]
+hip.shq_sfr_last_kernel.argtypes = [_vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+for _f in ("shq_sfr_eval", "shq_sfr_eval_host", "shq_sfr_set_refill", "shq_sfr_last_kernel"):
+    getattr(hip, _f).restype = C.c_int
+
 hip.shq_treepm_last_fused.argtypes = [_vp, C.POINTER(C.c_int)]
 hip.shq_treepm_set_fuse.argtypes = [_vp, C.c_int]
 hip.shq_pm_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 6)]

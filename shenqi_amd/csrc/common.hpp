@@ -527,6 +527,10 @@ struct shq_context {
     DevBuf<unsigned long long> cool_cnt;
     double cool_ms = 0;                   /* shq_cooling_last_kernel */
     int64_t cool_steps = 0;
+    /* ---- star formation (sfr.hip): works on the cooling tables and per-call arrays above */
+    int sfr_refill = 1;                   /* shq_sfr_set_refill */
+    double sfr_ms = 0;                    /* shq_sfr_last_kernel */
+    int64_t sfr_steps = 0;
 };
 
 /* capi.hip: make the main stream wait for an outstanding asynchronous PM run */
@@ -755,6 +759,31 @@ struct CoolPartArgs {
 int shq_cooling_classify_device(shq_context *ctx, const int32_t *d_list, int64_t cnt, const uint8_t *d_mask, int StarformationOn, double PhysDensThresh,
                                 double OverDensThresh, double a3inv, int32_t *d_cool, int64_t *ncool, int32_t *d_eeqos, int64_t *neeqos);
 int shq_cooling_run_device(shq_context *ctx, const CoolPartArgs *a, int64_t ncool);
+/* sfr.hip: the device half of shq_starformation and shq_sfr_on_eeqos.  Arrays by particle index unless said otherwise; the members the
+ * local UVBG reads carry CoolPartArgs' names (cooling_uvbg.hpp). */
+struct SfrPartArgs {
+    const int32_t *list;
+    const double4 *posm;
+    const uint8_t *pflags, *bin;
+    const uint8_t *flags;      /* the caller's flag byte: BHHeated and Generation, which the context's copy does not keep */
+    const double *density, *entropy, *delaytime, *hsml, *divvel, *curlvel;
+    const double *ne, *metallicity, *gradrho, *j21, *zre;
+    const unsigned long long *ids;
+    const double *dloga_for_bin;
+    const double *ztab;
+    int znside, mode;
+    double zbox, offset[3];
+    CoolUV global;
+    double j21c[6], ss_grey, ss_fbar;
+    double redshift;
+    /* by position in list */
+    double *out;               /* [SHQ_SFR_NOUT][cnt] */
+    uint8_t *flags_out, *decision, *branch;
+    int32_t *status, *steps;
+    size_t cnt;
+};
+struct SfrStep;
+int shq_sfr_run_device(shq_context *ctx, const SfrPartArgs *a, const shq_sfr_params *par, const SfrStep *step, int64_t cnt);
 /* cooling_host.hip: the caller's tables as the engine reads them: the scalars, and the two interleaved rate tables */
 int shq_cooling_tables_to_engine(const shq_cooling_tables *t, CoolPar *P, std::vector<double> *ion, std::vector<double> *rates);
 CoolUV shq_cooling_uv(const shq_cooling_uvbg *u);

@@ -7,6 +7,7 @@
  * of its first 64 particles is.  With refill off the share is one particle per lane.  Every particle is independent and written by
  * exactly one lane, so which lane takes which particle changes no result. */
 #include "common.hpp"
+#include "cooling_uvbg.hpp"
 #include <string.h>
 #include <algorithm>
 
@@ -44,71 +45,7 @@ struct EvalSrc {
 struct PartSrc {
     CoolPartArgs a;
     __device__ double enttou(long long i) const { return exp(SHQ_COOL_GAMMA_MINUS1 * log(a.density[i] * a.a3inv)) / SHQ_COOL_GAMMA_MINUS1; }
-    /* InterpNLinear<3>::eval_periodic (utils/interp.hpp:93-129) on the Zreion table: Min = 0, Max = BoxSize */
-    __device__ double zreion_at(const double4 &p) const
-    {
-        const int ns = a.znside;
-        const double step = (a.zbox - 0.0) / (ns - 1);
-        const double x[3] = {p.x - a.offset[0], p.y - a.offset[1], p.z - a.offset[2]};
-        long long xi[3];
-        double f[3];
-        for(int d = 0; d < 3; d++) {
-            const double xd = (x[d] - 0.0) / step;
-            const double fl = floor(xd);
-            /* a position far outside the box (or not finite) still lands inside the table */
-            xi[d] = (fl > -1e15 && fl < 1e15) ? (long long) fl : 0;
-            f[d] = xd - (double) xi[d];
-        }
-        double ret = 0;
-        for(int i = 0; i < 8; i++) {
-            double filter = 1.0;
-            long long l = 0;
-            for(int d = 0; d < 3; d++) {
-                const int foffset = (i & (1 << d)) ? 1 : 0;
-                long long x1 = (xi[d] + foffset) % ns;
-                if(x1 < 0)
-                    x1 += ns;
-                filter *= foffset ? f[d] : (1 - f[d]);
-                l = l * ns + x1;
-            }
-            ret += a.ztab[l] * filter;
-        }
-        return ret;
-    }
-    __device__ void local_uvbg(long long i, CoolUV &uv) const
-    {
-        const CoolUV g = a.global;
-        if(a.mode == SHQ_COOL_UVBG_J21) { /* get_local_UVBG_from_J21 (cooling_uvfluc.cpp:167-199) */
-            const double J21 = a.j21[i];
-            uv.zreion = a.zre[i];
-            uv.gJH0 = a.j21c[0] * J21;
-            uv.epsH0 = a.j21c[3] * J21 * 1.60218e-12;
-            uv.gJHe0 = a.j21c[2] * J21;
-            uv.epsHe0 = a.j21c[5] * J21 * 1.60218e-12;
-            uv.gJHep = 0.;
-            uv.epsHep = 0.;
-            /* get_self_shield_dens (cooling_rates.cpp:226-235): the grey-opacity and fBar powers are the caller's */
-            if(uv.gJH0 == 0)
-                uv.self_shield_dens = 1e10;
-            else {
-                const double G12 = uv.gJH0 / 1e-12;
-                uv.self_shield_dens = 6.73e-3 * a.ss_grey * pow(G12, 2. / 3) * a.ss_fbar;
-            }
-            return;
-        }
-        if(a.mode == SHQ_COOL_UVBG_GLOBAL) {
-            uv = g;
-            return;
-        }
-        /* get_local_UVBG_from_global (:142-165) */
-        const double zreion = zreion_at(a.posm[i]);
-        if(zreion < a.redshift) {
-            uv = CoolUV{0, 0, 0, 0, 0, 0, g.self_shield_dens, zreion};
-            return;
-        }
-        uv = g;
-        uv.zreion = zreion;
-    }
+    __device__ void local_uvbg(long long i, CoolUV &uv) const { cool_local_uvbg(a, i, uv); }
     __device__ void load(const CoolPar &P, long long k, CoolIn &in, CoolUV &uv, CoolState &S) const
     {
         const long long i = a.list[k];

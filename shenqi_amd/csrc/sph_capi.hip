@@ -1871,3 +1871,255 @@ extern "C" int shq_cooling(shq_context *ctx, const shq_part_view *parts, const s
     SHQ_CHECK(result->n_deferred <= deferred_capacity, SHQ_ERR_NOMEM, "cooling: %ld deferred particles, room for %ld", (long) result->n_deferred, (long) deferred_capacity);
     return SHQ_OK;
 }
+
+/* ---- the star-forming branch for the particles on the effective equation of state (sfr_eff.cpp:252-276, 698-767); the kernel is sfr.hip's ---- */
+#include "sfr_math.hpp"
+namespace {
+/* what shq_sfr_on_eeqos and shq_starformation share: staging as in shq_cooling, the kernel over the list, the results by list position */
+struct SfrRun {
+    std::vector<double> out;            /* [SHQ_SFR_NOUT][cnt] */
+    std::vector<uint8_t> bytes;         /* flags_out, decision, branch: [3][cnt] */
+    std::vector<int32_t> status;        /* [cnt] */
+    std::vector<int32_t> hlist;         /* the list as particle indices */
+};
+
+int sfr_run(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, size_t off_ne, size_t off_metallicity, const uint64_t *ids, const double *GradRho,
+            const shq_sfr_params *par, int what, const int32_t *list, int64_t nlist, const shq_cooling_step *step, const double *rnd_table, int64_t rnd_size, SfrRun *r)
+{
+    SHQ_CHECK(par->Generations >= 1, SHQ_ERR_INVALID, "star formation: Generations = %d", par->Generations);
+    SHQ_CHECK(par->BHFeedbackUseTcool >= 0 && par->BHFeedbackUseTcool <= 3, SHQ_ERR_INVALID, "star formation: BHFeedbackUseTcool = %d", par->BHFeedbackUseTcool);
+    SHQ_CHECK(nlist >= 0 && (nlist == 0 || list || nlist == parts->numpart), SHQ_ERR_INVALID, "star formation: nlist = %ld without a list", (long) nlist);
+    SHQ_CHECK(sph->off_delaytime != SHQ_NOFIELD && parts->off_timebin_hydro != SHQ_NOFIELD && parts->off_flags != SHQ_NOFIELD && parts->off_mass != SHQ_NOFIELD,
+              SHQ_ERR_INVALID, "star formation: needs DelayTime, the hydro time bin, the flag byte and Mass");
+    SHQ_CHECK(off_ne + 8 <= sph->elsize && off_metallicity + 8 <= sph->elsize, SHQ_ERR_INVALID, "star formation: Ne and Metallicity must lie inside the slot record");
+    SHQ_CHECK(step->uvbg_mode >= SHQ_COOL_UVBG_GLOBAL && step->uvbg_mode <= SHQ_COOL_UVBG_J21, SHQ_ERR_INVALID, "star formation: uvbg_mode = %d", step->uvbg_mode);
+    SHQ_CHECK(step->uvbg_mode != SHQ_COOL_UVBG_J21 || (step->local_J21 && step->zreion), SHQ_ERR_INVALID, "star formation: the J21 mode needs local_J21 and zreion");
+    SHQ_CHECK(step->hubble > 0 && step->a3inv > 0, SHQ_ERR_INVALID, "star formation: hubble and a3inv must be > 0");
+    SHQ_CHECK(what == SHQ_SFR_ON_EEQOS || (rnd_table && rnd_size > 0 && ids), SHQ_ERR_INVALID, "star formation: needs the IDs and a random table");
+    /* "GradRho not allocated but has SFR_CRITERION_MOLECULAR_H2" (sfr_eff.cpp:822-823) */
+    SHQ_CHECK(what == SHQ_SFR_ON_EEQOS || GradRho || (par->StarformationCriterion & 3) != 3, SHQ_ERR_INVALID,
+              "star formation: GradRho is NULL but StarformationCriterion has the H2 bits");
+    SHQ_TRY(winds_list_check(parts, list, nlist, false, "star formation"));
+    SHQ_CHECK(ctx->cool_have, SHQ_ERR_STATE, "star formation: shq_cooling_set_tables first");
+    SHQ_CHECK(step->uvbg_mode != SHQ_COOL_UVBG_ZREION || ctx->cool_znside >= 2, SHQ_ERR_STATE, "star formation: the Zreion mode needs a Zreion table");
+    SHQ_HIP(hipSetDevice(ctx->device));
+    SHQ_TRY(shq_particles_upload(ctx, parts));
+    SHQ_TRY(sph_upload(ctx, parts, sph));
+    const int64_t n = parts->numpart, cnt = list ? nlist : n;
+    r->hlist.resize((size_t) cnt);
+    for(int64_t k = 0; k < cnt; k++)
+        r->hlist[(size_t) k] = list ? list[k] : (int32_t) k;
+    r->out.assign((size_t) SHQ_SFR_NOUT * (size_t) cnt, 0.0);
+    r->bytes.assign(3 * (size_t) cnt, 0);
+    r->status.assign((size_t) cnt, COOL_ST_BADINPUT);
+    ctx->sfr_ms = 0;
+    ctx->sfr_steps = 0;
+    if(cnt == 0)
+        return SHQ_OK;
+    hipStream_t st = ctx->stream;
+    const size_t N = (size_t) n, C = (size_t) cnt;
+    const bool j21 = step->uvbg_mode == SHQ_COOL_UVBG_J21;
+    /* Ne, Metallicity, |GradRho| (and the excursion set's two fields) by particle index, and the caller's flag byte */
+    const int ncol = 5;
+    std::vector<double> h((size_t) ncol * N, 0.0);
+    std::vector<uint8_t> hf(N, 0);
+    for(int64_t i = 0; i < n; i++) {
+        hf[(size_t) i] = *pfield<uint8_t>(parts, i, parts->off_flags);
+        if(*pfield<uint8_t>(parts, i, parts->off_type) != 0)
+            continue;
+        const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+        SHQ_CHECK(pi >= 0 && pi < sph->numslots, SHQ_ERR_INVALID, "star formation: gas particle %ld with PI outside the SPH slot array", (long) i);
+        h[(size_t) i] = *sfield(sph, pi, off_ne);
+        h[N + (size_t) i] = *sfield(sph, pi, off_metallicity);
+        if(GradRho)
+            h[2 * N + (size_t) i] = GradRho[pi];
+        if(j21) {
+            h[3 * N + (size_t) i] = step->local_J21[pi];
+            h[4 * N + (size_t) i] = step->zreion[pi];
+        }
+    }
+    const size_t NB = (size_t) (SHQ_TIMEBINS + 1);
+    SHQ_TRY(ctx->cool_d.reserve((size_t) ncol * N + NB + (size_t) SHQ_SFR_NOUT * C));
+    SHQ_TRY(ctx->cool_i.reserve(3 * C));
+    SHQ_TRY(ctx->cool_b.reserve(N + 3 * C));
+    double *d = ctx->cool_d.ptr;
+    double *d_bins = d + (size_t) ncol * N, *d_out = d_bins + NB;
+    SHQ_HIP(hipMemcpyAsync(d, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, st));
+    SHQ_HIP(hipMemcpyAsync(d_bins, step->kf.dloga_for_bin, sizeof(double) * NB, hipMemcpyHostToDevice, st));
+    SHQ_HIP(hipMemsetAsync(d_out, 0, sizeof(double) * (size_t) SHQ_SFR_NOUT * C, st));
+    uint8_t *b = ctx->cool_b.ptr;
+    SHQ_HIP(hipMemcpyAsync(b, hf.data(), N, hipMemcpyHostToDevice, st));
+    SHQ_HIP(hipMemsetAsync(b + N, 0, 3 * C, st));
+    int32_t *d_list = ctx->cool_i.ptr, *d_status = d_list + C, *d_steps = d_status + C;
+    SHQ_HIP(hipMemcpyAsync(d_list, r->hlist.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
+    const double *d_rnd = nullptr;
+    if(what != SHQ_SFR_ON_EEQOS) {
+        SHQ_TRY(ids_upload(ctx, ids, n));
+        SHQ_TRY(ctx->bhw_rnd.reserve((size_t) rnd_size));
+        SHQ_HIP(hipMemcpyAsync(ctx->bhw_rnd.ptr, rnd_table, sizeof(double) * (size_t) rnd_size, hipMemcpyHostToDevice, st));
+        d_rnd = ctx->bhw_rnd.ptr;
+    }
+    SfrPartArgs a;
+    memset(&a, 0, sizeof(a));
+    a.list = d_list;
+    a.posm = ctx->posm.ptr;
+    a.pflags = ctx->pflags.ptr;
+    a.bin = ctx->bin_hydro.ptr;
+    a.flags = b;
+    a.density = ctx->g_density.ptr;
+    a.entropy = ctx->g_entropy.ptr;
+    a.delaytime = ctx->g_delaytime.ptr;
+    a.hsml = ctx->hsml.ptr;
+    a.divvel = ctx->g_divvel.ptr;
+    a.curlvel = ctx->g_curlvel.ptr;
+    a.ne = d;
+    a.metallicity = d + N;
+    a.gradrho = GradRho ? d + 2 * N : nullptr;
+    a.j21 = j21 ? d + 3 * N : nullptr;
+    a.zre = j21 ? d + 4 * N : nullptr;
+    a.ids = what != SHQ_SFR_ON_EEQOS ? ctx->bhw_ids.ptr : nullptr;
+    a.dloga_for_bin = d_bins;
+    a.ztab = ctx->cool_zreion.ptr;
+    a.znside = ctx->cool_znside;
+    a.zbox = ctx->cool_zbox;
+    a.mode = step->uvbg_mode;
+    for(int j = 0; j < 3; j++)
+        a.offset[j] = step->CurrentParticleOffset[j];
+    a.global = shq_cooling_uv(&step->GlobalUVBG);
+    for(int j = 0; j < 6; j++)
+        a.j21c[j] = step->J21_coeffs[j];
+    a.ss_grey = step->ss_greyopac_factor;
+    a.ss_fbar = step->ss_fbar_factor;
+    a.redshift = step->redshift;
+    a.out = d_out;
+    a.flags_out = b + N;
+    a.decision = b + N + C;
+    a.branch = b + N + 2 * C;
+    a.status = d_status;
+    a.steps = d_steps;
+    a.cnt = C;
+    SfrStep es;
+    memset(&es, 0, sizeof(es));
+    es.redshift = step->redshift;
+    es.a3inv = step->a3inv;
+    es.hubble = step->hubble;
+    es.global = a.global;
+    es.rnd = d_rnd;
+    es.rndsize = (uint64_t) std::max<int64_t>(rnd_size, 1);
+    es.what = what;
+    SHQ_TRY(shq_sfr_run_device(ctx, &a, par, &es, cnt));
+    SHQ_HIP(hipMemcpyAsync(r->out.data(), d_out, sizeof(double) * r->out.size(), hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipMemcpyAsync(r->bytes.data(), b + N, 3 * C, hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipMemcpyAsync(r->status.data(), d_status, sizeof(int32_t) * C, hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipStreamSynchronize(st));
+    for(size_t k = 0; k < C; k++)
+        SHQ_CHECK(r->status[k] >= 0 && r->status[k] < SHQ_COOL_NSTATUS, SHQ_ERR_DEVICE, "star formation: status %d from the device", r->status[k]);
+    return SHQ_OK;
+}
+} // namespace
+
+extern "C" int shq_sfr_on_eeqos(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_sfr_params *par, const int32_t *list, int64_t nlist,
+                                const shq_cooling_step *step, uint8_t *on_eeqos)
+{
+    SHQ_CHECK(ctx && parts && sph && par && step && (on_eeqos || parts->numpart == 0), SHQ_ERR_INVALID, "null argument");
+    if(!step->StarformationOn) { /* "no sfr: normal cooling" (sfr_eff.cpp:506-508) */
+        memset(on_eeqos, 0, (size_t) parts->numpart);
+        return SHQ_OK;
+    }
+    SfrRun r;
+    /* Ne and Metallicity are not read by sfreff_on_eeqos: any offset inside the record will do */
+    SHQ_TRY(sfr_run(ctx, parts, sph, sph->off_entropy, sph->off_entropy, nullptr, nullptr, par, SHQ_SFR_ON_EEQOS, list, nlist, step, nullptr, 0, &r));
+    memset(on_eeqos, 0, (size_t) parts->numpart);
+    const size_t C = r.hlist.size();
+    for(size_t k = 0; k < C; k++)
+        if(r.status[k] == COOL_ST_OK && (r.bytes[2 * C + k] & SHQ_SFR_B_ON_EEQOS))
+            on_eeqos[r.hlist[k]] = 1;
+    return SHQ_OK;
+}
+
+extern "C" int shq_starformation(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_sfr_fields *fields, const uint64_t *ids,
+                                 const double *GradRho, const shq_sfr_params *par, const int32_t *list, int64_t nlist, const shq_cooling_step *step,
+                                 const double *rnd_table, int64_t rnd_size, int32_t *NewParents, double *mass_of_star, uint8_t *split, int64_t newstar_capacity,
+                                 int32_t *MaybeWind, double *sm, int64_t maybewind_capacity, int32_t *deferred, int64_t deferred_capacity, shq_sfr_result *result)
+{
+    SHQ_CHECK(ctx && parts && sph && fields && par && step && result, SHQ_ERR_INVALID, "null argument");
+    SHQ_CHECK(newstar_capacity >= 0 && maybewind_capacity >= 0 && deferred_capacity >= 0 && ((NewParents && mass_of_star && split) || newstar_capacity == 0) &&
+                  ((MaybeWind && sm) || maybewind_capacity == 0) && (deferred || deferred_capacity == 0),
+              SHQ_ERR_INVALID, "starformation: an output list is NULL");
+    SHQ_CHECK(fields->off_sfr + 8 <= sph->elsize, SHQ_ERR_INVALID, "starformation: Sfr must lie inside the slot record");
+    SHQ_CHECK(fields->off_delaytime == sph->off_delaytime, SHQ_ERR_INVALID, "starformation: fields->off_delaytime differs from the SPH view's, whose DelayTime is the one staged");
+    memset(result, 0, sizeof(*result));
+    SfrRun r;
+    SHQ_TRY(sfr_run(ctx, parts, sph, fields->off_ne, fields->off_metallicity, ids, GradRho, par, SHQ_SFR_STARFORM, list, nlist, step, rnd_table, rnd_size, &r));
+    result->kernel_ms = ctx->sfr_ms;
+    result->steps = ctx->sfr_steps;
+    const size_t C = r.hlist.size();
+    const bool quicklya = par->QuickLymanAlphaProbability > 0;
+    std::vector<double> hent;
+    bool touched = false;
+    for(size_t k = 0; k < C; k++) {
+        const int64_t i = r.hlist[k];
+        const int s = r.status[k];
+        const bool live = *pfield<uint8_t>(parts, i, parts->off_type) == 0 && !(*pfield<uint8_t>(parts, i, parts->off_flags) & 1u) &&
+                          *pfield<float>(parts, i, parts->off_mass) > 0;
+        if(!live) { /* sfr_eff.cpp:238; the device refused it as BADINPUT */
+            result->n_skipped++;
+            continue;
+        }
+        result->n_status[s]++;
+        if(s == SHQ_COOL_DEFERRED) {
+            if(result->n_deferred < deferred_capacity)
+                deferred[result->n_deferred] = (int32_t) i;
+            result->n_deferred++;
+        }
+        if(s != SHQ_COOL_OK)
+            continue;
+        const int decision = r.bytes[C + k];
+        if(quicklya && decision == SHQ_SFR_NONE)
+            continue; /* not star forming: the caller cools it */
+        result->sum_sf_part++;
+        result->localsfr += r.out[(size_t) SHQ_SFR_O_SFR * C + k];
+        result->sum_sm += r.out[(size_t) SHQ_SFR_O_DM * C + k];
+        result->sum_dtime += r.out[(size_t) SHQ_SFR_O_DTIME * C + k];
+        if(decision != SHQ_SFR_NONE) {
+            if(result->n_newstars < newstar_capacity) {
+                NewParents[result->n_newstars] = (int32_t) i;
+                mass_of_star[result->n_newstars] = r.out[(size_t) SHQ_SFR_O_MASS_OF_STAR * C + k];
+                split[result->n_newstars] = decision == SHQ_SFR_SPLIT;
+            }
+            result->n_newstars++;
+            result->n_split += decision == SHQ_SFR_SPLIT;
+        }
+        else if(par->winds_subgrid) {
+            if(result->n_maybewind < maybewind_capacity) {
+                MaybeWind[result->n_maybewind] = (int32_t) i;
+                sm[result->n_maybewind] = r.out[(size_t) SHQ_SFR_O_SM * C + k];
+            }
+            result->n_maybewind++;
+        }
+        if(quicklya)
+            continue;
+        const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+        *sfield(sph, pi, fields->off_sfr) = r.out[(size_t) SHQ_SFR_O_SFR * C + k];
+        *sfield(sph, pi, fields->off_ne) = r.out[(size_t) SHQ_SFR_O_NE * C + k];
+        *sfield(sph, pi, fields->off_metallicity) = r.out[(size_t) SHQ_SFR_O_METALLICITY * C + k];
+        *sfield(sph, pi, sph->off_entropy) = r.out[(size_t) SHQ_SFR_O_ENTROPY * C + k];
+        *pfield_w<uint8_t>(parts, i, parts->off_flags) = r.bytes[k];
+        if(!touched) {
+            SHQ_TRY(down(ctx, ctx->g_entropy, hent, (size_t) parts->numpart));
+            SHQ_HIP(hipStreamSynchronize(ctx->stream));
+            touched = true;
+        }
+        hent[(size_t) i] = r.out[(size_t) SHQ_SFR_O_ENTROPY * C + k];
+    }
+    if(touched) { /* the context's Entropy copy, alike */
+        SHQ_HIP(hipMemcpyAsync(ctx->g_entropy.ptr, hent.data(), sizeof(double) * (size_t) parts->numpart, hipMemcpyHostToDevice, ctx->stream));
+        SHQ_HIP(hipStreamSynchronize(ctx->stream));
+    }
+    SHQ_CHECK(result->n_newstars <= newstar_capacity, SHQ_ERR_NOMEM, "starformation: %ld new stars, room for %ld", (long) result->n_newstars, (long) newstar_capacity);
+    SHQ_CHECK(result->n_maybewind <= maybewind_capacity, SHQ_ERR_NOMEM, "starformation: %ld wind candidates, room for %ld", (long) result->n_maybewind,
+              (long) maybewind_capacity);
+    SHQ_CHECK(result->n_deferred <= deferred_capacity, SHQ_ERR_NOMEM, "starformation: %ld deferred particles, room for %ld", (long) result->n_deferred,
+              (long) deferred_capacity);
+    return SHQ_OK;
+}
