@@ -326,7 +326,7 @@ __global__ __launch_bounds__(HB_THREADS) void sph_density_block_kernel(const Sph
 struct PostArgs {
     double Box, DesNumNgb, DesNumNgbBH, MinGasHsml, MaxDev;
     int update_hsml, BlackHoleOn, DoEgyDensity;
-    unsigned long long *hmax_tried; /* the largest Hsml any walk of this loop has run with, as the bits of a non-negative double */
+    unsigned long long *hmax_tried; /* the largest Hsml any walk of this loop has run with or any target ends with, as the bits of a non-negative double */
 };
 
 __global__ void sph_density_post_kernel(const SphDev a, const int32_t *queue, long long nq, const PostArgs p, int32_t *todo)
@@ -391,6 +391,10 @@ __global__ void sph_density_post_kernel(const SphDev a, const int32_t *queue, lo
             done = 1;
         }
         a.hsml[i] = hs;
+        /* a target can end on a radius no walk ran with: the collapsed bracket leaves Right (Box itself for a target alone in the box),
+         * the floors leave MinGasHsml.  The next operator searches with it, so the report covers it too */
+        if(done && p.hmax_tried && (unsigned long long) __double_as_longlong(hs) > *(volatile unsigned long long *) p.hmax_tried)
+            atomicMax(p.hmax_tried, (unsigned long long) __double_as_longlong(hs));
     }
     if(type == 0) {
         if(p.DoEgyDensity) {

@@ -120,10 +120,12 @@ def test_density_hsml_loop_parity(ctx):
     evp, gs = sq.density(ctx, act, 1, 1, 0, None, tree, pman, SphP, BhP)
     assert gs.niterations == oniter
     assert np.abs(P["Hsml"][act] - st.hsml[act]).max() < 1e-12
+    assert np.abs(P["Hsml"][act] / st.hsml[act] - 1).max() < 1e-12
     mask = np.ones(n, dtype=bool)
     mask[act] = False
     assert np.array_equal(P["Hsml"][mask], h_before[mask])
     assert np.abs(SphP["Density"][act] - st.density[act]).max() < 1e-10 * st.density.max()
+    assert np.abs(SphP["Density"][act] / st.density[act] - 1).max() < 1e-11      # per particle: the sparse ones are not hidden by the clump
     assert np.abs(tree.Nodes_base["hmax"] - onodes["hmax"]).max() < 1e-12
 
 
