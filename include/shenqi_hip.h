@@ -263,8 +263,8 @@ int shq_tree_download(shq_context *ctx, int64_t firstnode, shq_node *nodes, int6
  *
  * The top tree arrives as geometry: for every TopNode its eight daughters in octant order `count = i + 2 j + 4 k`
  * (the slot force_create_node_for_topnode puts TopNodes[Daughter + sub] in, sub = 7 & peano_hilbert_key(2x + i, 2y + j, 2z + k,
- * bits) — the reference-side shim fills the table with its own key function), -1 eight times for a leaf, and
- * the leaf's TopLeaves index.  topleaves[].Task says whose each leaf is.
+ * bits) — the reference-side shim fills the table with its own key function, INTEGRATION.md, or takes it from shq_domain_install),
+ * -1 eight times for a leaf, and the leaf's TopLeaves index.  topleaves[].Task says whose each leaf is.
  *
  * shq_tree_build_domain: as shq_tree_build, but every TopNode is a tree node whether or not it holds particles (empty top-level
  * nodes are never removed, forcetree.cpp:1040-1045), a leaf of ThisTask roots an ordinary sub-tree of this rank's particles, a
@@ -302,6 +302,107 @@ int shq_tree_set_topleaf_moments(shq_context *ctx, const shq_topleaf_moments *mo
  * active at Ti_Current (it stays and keeps its leaf).  d_topleaf / d_target are DEVICE arrays of one int per resident particle —
  * d_target is what shq_exchange_plan takes.  *nchanged = particles that left their leaf. */
 int shq_domain_maintain_topleaf(shq_context *ctx, int dmtree, int64_t Ti_Current, int32_t *d_topleaf, int32_t *d_target, int64_t *nchanged);
+
+/* ---- the domain decomposition itself (domain_decompose_full, libgadget/domain.cpp:174-277) -----------------------------------------
+ * The particle loops run on the device, the small serial stages are host functions of the library, the collectives between them are
+ * the caller's (shenqi_amd/dist.py: DistDomain).  Every result is integers; nothing here has a tolerance.
+ *
+ * The reference's key, PEANO() (utils/peano.h:15-21), is a finite automaton over the octants of a position, most significant bit
+ * first: key digit = sub[state][octant], state' = next[state][octant], octant = (xbit << 2) | (ybit << 1) | zbit, state 0 at the root.
+ * The library holds no table of its own: shq_peano_tables_from_key recovers the automaton from a key function the caller hands it
+ * (the reference-side shim passes peano_hilbert_key).  Two octant paths are the same state when the low digits of the keys of all
+ * their two-level continuations agree; the walk from the root closes at 24 states for the reference's curve.  SHQ_ERR_INVALID when
+ * more than SHQ_PEANO_MAXSTATES states appear or when the tables do not reproduce keyfn(x, y, z, 21) on 4096 pseudo-random triples
+ * (the function is no such automaton).  shq_peano_tables is plain data: a caller may store and reload it. */
+#define SHQ_PEANO_MAXSTATES 64
+#define SHQ_PEANO_BITS 21                    /* BITS_PER_DIMENSION */
+#define SHQ_PEANOCELLS (1ull << 63)          /* PEANOCELLS: the key of a garbage sample */
+#define SHQ_ERR_RETRY 6     /* the top tree does not fit MaxTopNodes: nothing was written, call again with more ("retry", domain.cpp:199-214) */
+typedef uint64_t (*shq_peano_keyfn)(int x, int y, int z, int bits);
+typedef struct shq_peano_tables {
+    int32_t nstates;
+    uint8_t next[SHQ_PEANO_MAXSTATES][8];
+    uint8_t sub[SHQ_PEANO_MAXSTATES][8];
+} shq_peano_tables;
+int shq_peano_tables_from_key(shq_peano_keyfn keyfn, shq_peano_tables *out);
+/* peano_hilbert_key(x, y, z, bits) from the tables, on the host (1 <= bits <= 21): what the device kernels compute */
+uint64_t shq_peano_key_host(const shq_peano_tables *tables, int x, int y, int z, int bits);
+/* d_keys[i] = PEANO(pos_i, BoxSize), bit for bit: the same three double operations and truncation to int, then the automaton.
+ * pos_i = the three doubles at d_pos + i * stride_bytes (24 for a packed array, the record size for Pos inside particle_data).
+ * d_keys is what shq_slots_gc_sorted takes.  One particle per lane; the tables sit in LDS, two levels per lookup. */
+int shq_peano_keys(shq_context *ctx, const shq_peano_tables *tables, const void *d_pos, size_t stride_bytes, int64_t n, double BoxSize, uint64_t *d_keys);
+
+/* A device-readable particle_data array as shq_exchange_* take it (bit 0 of the byte at off_flags = IsGarbage), plus Pos. */
+typedef struct shq_domain_parts {
+    const void *d_parts;
+    size_t elsize, off_flags, off_pos;
+    int64_t numpart;
+    double BoxSize;
+} shq_domain_parts;
+/* The subsample of domain_check_for_local_refine_subsample (domain.cpp:1005-1067).  PreSort == 0: the keys of every
+ * SubSampleDistance-th slot (one sample when NumPart is below the distance), garbage samples dropped.  PreSort != 0: all keys, garbage
+ * as PEANOCELLS, sorted, then every SubSampleDistance-th of the live ones (one when fewer live than the distance).  d_samples (device,
+ * room for NumPart / SubSampleDistance + 1 keys) comes out sorted; *nsample = their number.  The sort across ranks is the caller's. */
+int shq_domain_samples(shq_context *ctx, const shq_peano_tables *tables, const shq_domain_parts *parts, int SubSampleDistance, int PreSort,
+                       uint64_t *d_samples, int64_t *nsample);
+/* The local top tree of sorted samples (domain.cpp:1073-1168, then domain_toptree_truncate :892-958), numbered as the reference's
+ * serial loop numbers it (the closed form of the skeleton).  Every sample counts and costs 1.  tree (host, MaxTopNodes
+ * entries) receives the nodes that survive the truncation, *size their number.  SHQ_ERR_RETRY when the skeleton before truncation has
+ * more than MaxTopNodes nodes (domain_toptree_split's "ran out of top nodes"): tree and *size are not written.  nsample == 0 gives the
+ * root alone. */
+typedef struct shq_local_topnode {   /* struct local_topnode_data, domain.cpp:60-70 */
+    uint64_t StartKey;
+    int32_t Shift;
+    int32_t Daughter;
+    int32_t Parent;
+    int32_t pad_;
+    int64_t Count;
+    int64_t Cost;
+} shq_local_topnode;
+int shq_domain_local_toptree(shq_context *ctx, const uint64_t *d_sorted_samples, int64_t nsample, int64_t countlimit, int64_t costlimit, int MaxTopNodes,
+                             shq_local_topnode *tree, int *size);
+/* The serial stages, pure host code (no context):
+ *   shq_domain_toptree_merge   domain_toptree_merge (:1447-1552) of treeB into treeA from the two roots.  Where the reference ends
+ *                              the run (no room for eight more nodes, a corrupt treeB) this returns SHQ_ERR_RETRY / SHQ_ERR_INVALID;
+ *                              treeA is then partly merged and must be discarded.
+ *   shq_domain_toptree_finish  domain_global_refine (:1320-1371; SHQ_ERR_RETRY when out of nodes), the copy into TopNodes (:469-476)
+ *                              and domain_create_topleaves (:801-816).  TopNodes / TopLeaves have room for MaxTopNodes entries.
+ *   shq_domain_balance         domain_assign_topleaves_balanced (:619-761, one segment per task, the sentinel entry TopLeaves[ntopleaves]
+ *                              = {NTask, -1} included: TopLeaves has room for ntopleaves + 1), domain_set_task_leafs (:764-793, Tasks
+ *                              has NTask + 1 entries) and domain_check_memory_bound (:529-585): *status = 1 when the largest load
+ *                              exceeds MaxPart * SetAsideFactor.  As in the reference the loads are summed over TopLeafCount[StartLeaf
+ *                              .. EndLeaf), the counts in their order before the assignment.  SHQ_ERR_INVALID where the reference
+ *                              ends the run (fewer leaves than tasks, not enough segments). */
+typedef struct shq_topnode {   /* struct topnode_data, libgadget/domain.h:12-18 */
+    uint64_t StartKey;
+    int32_t Daughter;
+    int32_t Shift;
+    int32_t Leaf;
+    int32_t pad_;
+} shq_topnode;
+typedef struct shq_task_leafs { /* struct task_data, domain.h:26-29 */
+    int32_t StartLeaf;
+    int32_t EndLeaf;
+} shq_task_leafs;
+int shq_domain_toptree_merge(shq_local_topnode *treeA, int *sizeA, const shq_local_topnode *treeB, int sizeB, int MaxTopNodes);
+int shq_domain_toptree_finish(shq_local_topnode *tree, int *size, int MaxTopNodes, int64_t countlimit, int64_t costlimit, shq_topnode *TopNodes,
+                              shq_topleaf *TopLeaves, int *ntopleaves);
+int shq_domain_balance(shq_topnode *TopNodes, int ntopnodes, shq_topleaf *TopLeaves, int ntopleaves, const int64_t *TopLeafCount, int NTask,
+                       int64_t MaxPart, double SetAsideFactor, shq_task_leafs *Tasks, int *status);
+/* Makes a decomposition the context's current one: uploads the key-space tree (what shq_domain_leaf_counts and
+ * shq_domain_particle_topleaves descend) and fills geo_out (may be NULL; ntopnodes entries), the daughter-per-octant table
+ * shq_tree_build_domain takes: a node's state follows `next` from its parent's, daughter[i + 2 j + 4 k] = Daughter +
+ * sub[state][(i << 2) | (j << 1) | k].  SHQ_ERR_INVALID for a tree that is none (a Daughter that does not lie behind its node, a leaf
+ * without a valid Leaf, an internal node with Shift < 3). */
+int shq_domain_install(shq_context *ctx, const shq_peano_tables *tables, const shq_topnode *TopNodes, int ntopnodes, const shq_topleaf *TopLeaves,
+                       int ntopleaves, shq_topnode_geo *geo_out);
+/* domain_compute_costs (:1374-1429, counts only) before its all-reduce: TopLeafCount[leaf] (host, ntopleaves entries) = live particles
+ * whose domain_get_topleaf(PEANO(Pos)) (domain.h:69-76) is that leaf, on the installed tree. */
+int shq_domain_leaf_counts(shq_context *ctx, const shq_domain_parts *parts, int64_t *TopLeafCount);
+/* The loop of domain.cpp:238-246 and DomainExchangePlan::layoutfunc (:159-164) on the installed tree: d_topleaf[i] = the top leaf of
+ * every live particle, d_target[i] (may be NULL) = that leaf's Task: what shq_exchange_plan takes.  Garbage keeps its old leaf and
+ * gets target -1, as in shq_domain_maintain_topleaf. */
+int shq_domain_particle_topleaves(shq_context *ctx, const shq_domain_parts *parts, int32_t *d_topleaf, int32_t *d_target);
 
 /* Resident drift and kick: with the particles, their velocities and the force
  * arrays in HBM a step is  shq_drift -> shq_tree_build -> shq_pm_run / shq_grav_short_run -> kicks,
@@ -500,8 +601,8 @@ int shq_slots_gc(shq_context *ctx, const shq_exchange_layout *layout, void *d_pa
                  int64_t slot_size[6], const int compact[6]);
 /* slots_gc_sorted (libgadget/slotsmanager.cpp:417-510): the particle array sorted by type, then by Peano-Hilbert key, garbage
  * (TypeKey 255) last and trimmed off; every enabled slot array sorted by its particles' new positions (ReverseLink), unreferenced
- * slots trimmed, PI renumbered.  d_keys[i] = PEANO(Part[i].Pos, BoxSize) comes from the caller (its own key function: the loop at
- * :439-447); equal (type, key) pairs keep their order here (the reference's sort is unstable). */
+ * slots trimmed, PI renumbered.  d_keys[i] = PEANO(Part[i].Pos, BoxSize) comes from the caller (shq_peano_keys, or its own key function: the
+ * loop at :439-447); equal (type, key) pairs keep their order here (the reference's sort is unstable). */
 int shq_slots_gc_sorted(shq_context *ctx, const shq_exchange_layout *layout, void *d_parts, int64_t *numpart, int64_t MaxPart, void *const d_slots[6],
                         int64_t slot_size[6], const uint64_t *d_keys);
 

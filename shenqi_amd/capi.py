@@ -489,6 +489,63 @@ hip.shq_metal_return.argtypes = [_vp, C.POINTER(TreeView), C.POINTER(PartView), 
 hip.shq_metal_return.restype = C.c_int
 hip.shq_domain_maintain_topleaf.argtypes = [_vp, C.c_int, C.c_int64, _vp, _vp, C.POINTER(C.c_int64)]
 hip.shq_domain_maintain_topleaf.restype = C.c_int
+
+
+# the domain decomposition (domain.hip): key tables, keys, samples, local top tree, serial stages, install, leaf counts, top leaves
+class PeanoTables(C.Structure):
+    _fields_ = [("nstates", C.c_int32), ("next", (C.c_uint8 * 8) * 64), ("sub", (C.c_uint8 * 8) * 64)]
+
+
+class DomainParts(C.Structure):
+    _fields_ = [("d_parts", C.c_void_p), ("elsize", C.c_size_t), ("off_flags", C.c_size_t), ("off_pos", C.c_size_t), ("numpart", C.c_int64), ("BoxSize", C.c_double)]
+
+
+PEANO_KEYFN = C.CFUNCTYPE(C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_int)
+ERR_RETRY = 6
+PEANOCELLS = 1 << 63
+LOCAL_TOPNODE_DTYPE = np.dtype([("StartKey", "<u8"), ("Shift", "<i4"), ("Daughter", "<i4"), ("Parent", "<i4"), ("pad_", "<i4"), ("Count", "<i8"), ("Cost", "<i8")])
+TOPNODE_DTYPE = np.dtype([("StartKey", "<u8"), ("Daughter", "<i4"), ("Shift", "<i4"), ("Leaf", "<i4"), ("pad_", "<i4")])
+TOPLEAF_DTYPE = np.dtype([("Task", "<i4"), ("topnode", "<i4"), ("treenode", "<i4")])
+TASK_LEAFS_DTYPE = np.dtype([("StartLeaf", "<i4"), ("EndLeaf", "<i4")])
+hip.shq_peano_tables_from_key.argtypes = [_vp, C.POINTER(PeanoTables)]
+hip.shq_peano_key_host.argtypes = [C.POINTER(PeanoTables), C.c_int, C.c_int, C.c_int, C.c_int]
+hip.shq_peano_key_host.restype = C.c_uint64
+hip.shq_peano_keys.argtypes = [_vp, C.POINTER(PeanoTables), _vp, C.c_size_t, C.c_int64, C.c_double, _vp]
+hip.shq_domain_samples.argtypes = [_vp, C.POINTER(PeanoTables), C.POINTER(DomainParts), C.c_int, C.c_int, _vp, C.POINTER(C.c_int64)]
+hip.shq_domain_local_toptree.argtypes = [_vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int, _vp, C.POINTER(C.c_int)]
+hip.shq_domain_toptree_merge.argtypes = [_vp, C.POINTER(C.c_int), _vp, C.c_int, C.c_int]
+hip.shq_domain_toptree_finish.argtypes = [_vp, C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int64, _vp, _vp, C.POINTER(C.c_int)]
+hip.shq_domain_balance.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int, C.c_int64, C.c_double, _vp, C.POINTER(C.c_int)]
+hip.shq_domain_install.argtypes = [_vp, C.POINTER(PeanoTables), _vp, C.c_int, _vp, C.c_int, _vp]
+hip.shq_domain_leaf_counts.argtypes = [_vp, C.POINTER(DomainParts), _vp]
+hip.shq_domain_particle_topleaves.argtypes = [_vp, C.POINTER(DomainParts), _vp, _vp]
+for _f in ("shq_peano_tables_from_key", "shq_peano_keys", "shq_domain_samples", "shq_domain_local_toptree", "shq_domain_toptree_merge", "shq_domain_toptree_finish",
+           "shq_domain_balance", "shq_domain_install", "shq_domain_leaf_counts", "shq_domain_particle_topleaves"):
+    getattr(hip, _f).restype = C.c_int
+
+
+def peano_tables_from_key(keyfn):
+    """The key automaton of `keyfn` (a ctypes function pointer of the reference's signature, or a Python callable of (x, y, z, bits))."""
+    cb = keyfn if isinstance(keyfn, C._CFuncPtr) else PEANO_KEYFN(keyfn)
+    t = PeanoTables()
+    check(hip.shq_peano_tables_from_key(C.cast(cb, C.c_void_p), C.byref(t)))
+    return t
+
+
+def peano_tables_to_arrays(t):
+    n = int(t.nstates)
+    return np.array([[t.next[s][o] for o in range(8)] for s in range(n)], dtype=np.uint8), np.array([[t.sub[s][o] for o in range(8)] for s in range(n)], dtype=np.uint8)
+
+
+def peano_tables_from_arrays(nxt, sub):
+    """PeanoTables from stored (next, sub) arrays of shape [nstates][8]"""
+    t = PeanoTables()
+    t.nstates = len(nxt)
+    for s in range(len(nxt)):
+        for o in range(8):
+            t.next[s][o] = int(nxt[s][o])
+            t.sub[s][o] = int(sub[s][o])
+    return t
 hip.shq_winds_evolve.argtypes = [_vp, C.POINTER(PartView), C.POINTER(SphView), _vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(KickFactors)]
 hip.shq_winds_subgrid.argtypes = [_vp, C.POINTER(PartView), C.POINTER(SphView), C.c_size_t, _vp, _vp, C.c_int64, _vp, C.POINTER(WindParams), _vp, C.c_int64,
                                   C.POINTER(C.c_int64)]

@@ -255,6 +255,10 @@ extern "C" void shq_shutdown(shq_context *ctx)
     ctx->ex_list.release(); ctx->ex_counts.release(); ctx->ex_i64.release(); ctx->ex_bytes.release(); ctx->ex_u64.release();
     for(auto &b : ctx->ex_val) b.release();
     for(auto &b : ctx->ex_key) b.release();
+    ctx->dd_tab.release(); ctx->dd_nodes.release(); ctx->dd_leaf_task.release(); ctx->dd_u8.release(); ctx->dd_rec.release();
+    for(auto &b : ctx->dd_u64) b.release();
+    for(auto &b : ctx->dd_i64) b.release();
+    for(auto &b : ctx->dd_i32) b.release();
     ctx->fof_parent.release(); ctx->fof_partgrnr.release(); ctx->fof_members.release(); ctx->fof_groups.release(); ctx->fof_biglist.release(); ctx->fof_partial.release();
     for(auto &b : ctx->fof_i32) b.release();
     for(auto &b : ctx->fof_g32) b.release();

@@ -375,6 +375,19 @@ struct shq_context {
     std::vector<shq_exchange_entry> ex_togo;
     int64_t ex_last = -1;
     int ex_ntask = 0;
+    /* domain decomposition (domain.hip): the key automaton as the kernels read it (512 one-level + 4096 two-level entries), the
+     * installed key-space top tree, scratch */
+    DevBuf<uint16_t> dd_tab;
+    shq_peano_tables dd_tab_src = {};
+    bool dd_tab_valid = false;
+    DevBuf<char> dd_nodes;               /* DdNode[ntopnodes] */
+    DevBuf<int32_t> dd_leaf_task;
+    int dd_ntopnodes = 0, dd_ntopleaves = 0;
+    DevBuf<unsigned long long> dd_u64[3];
+    DevBuf<long long> dd_i64[2];
+    DevBuf<int32_t> dd_i32[3];
+    DevBuf<uint8_t> dd_u8;
+    DevBuf<char> dd_rec;
     /* friends-of-friends (fof.hip) */
     DevBuf<int32_t> fof_parent, fof_i32[6], fof_g32[5], fof_partgrnr, fof_members, fof_biglist;
     DevBuf<unsigned long long> fof_u64[4];

@@ -1544,3 +1544,291 @@ class GpuWindOps:
                                             C.byref(na)))
         P["Vel"] = pman.Base["Vel"]
         return na.value
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The domain decomposition itself: domain_decompose_full (libgadget/domain.cpp:174-277).  The particle loops run in `ops` (GpuDomainOps:
+# shq_domain_* on the device; the tests' CPU stand-in: the restated procedures), the small serial stages are host functions, and this
+# class holds what the reference does between them: the policy table, the retry with more top nodes, the global sample sort, the
+# limits, the pairwise combine in the reference's own order (merge order changes the result), the all-reduce of the leaf counts.
+class DistDomain:
+    """One rank of a full domain decomposition.  params: DomainOverDecompositionFactor, TopNodeAllocFactor, SetAsideFactor (1).
+    ops holds the rank's particles and offers samples / local_toptree / merge / finish / install / leaf_counts / balance /
+    particle_topleaves / exchange / gc_sorted and `numpart`.  After decompose(): TopNodes, TopLeaves (with the sentinel entry), Tasks,
+    policy (the index that worked; the next call starts there) and factor (TopNodeAllocFactor as the retries left it)."""
+    NPOLICY = 16
+
+    def __init__(self, comm, ops, params):
+        self.comm, self.ops = comm, ops
+        self.dodf = int(params["DomainOverDecompositionFactor"])
+        self.factor = float(params["TopNodeAllocFactor"])
+        self.setaside = float(params.get("SetAsideFactor", 1.0))
+        self.policy = 0                 # LastSuccessfulPolicy
+        self.TopNodes = self.TopLeaves = self.Tasks = None
+        self.policies = []
+        for i in range(self.NPOLICY):   # domain_policies_init, :378-403
+            d = 256
+            if i > 4 and self.policies[i - 1]["SubSampleDistance"] > 2:
+                d = self.policies[i - 1]["SubSampleDistance"] // 2
+            self.policies.append(dict(PreSort=int(i >= 2), SubSampleDistance=d, NTopLeaves=self.dodf * comm.size * (i + 1)))
+
+    # -- collectives on small host arrays
+    def _cdev(self):
+        return torch.device("cuda") if self.comm.backend == "nccl" else torch.device("cpu")
+
+    def _any(self, flag):
+        return int(self.comm.allreduce_sum_vec(np.array([int(bool(flag))], dtype=np.int64))[0]) > 0
+
+    def _allgather_u64(self, a):
+        """every rank's uint64 array, concatenated in rank order"""
+        if not self.comm.multi:
+            return np.asarray(a, dtype=np.uint64).copy()
+        n = self.comm.allreduce_sum_vec(np.eye(self.comm.size, dtype=np.int64)[self.comm.rank] * len(a))
+        m = int(n.max())
+        mine = torch.zeros(max(m, 1), dtype=torch.int64)
+        mine[:len(a)] = torch.from_numpy(np.asarray(a, dtype=np.uint64).view(np.int64).copy())
+        mine = mine.to(self._cdev())
+        outs = [torch.empty_like(mine) for _ in range(self.comm.size)]
+        dist.all_gather(outs, mine, group=self.comm.group)
+        return np.concatenate([o.cpu().numpy()[:int(c)] for o, c in zip(outs, n)]).view(np.uint64)
+
+    def _send(self, arr, dst):
+        b = torch.from_numpy(np.frombuffer(arr.tobytes(), dtype=np.uint8).copy())
+        dist.send(torch.tensor([len(arr)], dtype=torch.int64).to(self._cdev()), dst, group=self.comm.group)
+        if len(arr):
+            dist.send(b.to(self._cdev()), dst, group=self.comm.group)
+
+    def _recv(self, src, dtype):
+        n = torch.zeros(1, dtype=torch.int64).to(self._cdev())
+        dist.recv(n, src, group=self.comm.group)
+        b = torch.zeros(int(n.item()) * dtype.itemsize, dtype=torch.uint8).to(self._cdev())
+        if int(n.item()):
+            dist.recv(b, src, group=self.comm.group)
+        return np.frombuffer(b.cpu().numpy().tobytes(), dtype=dtype).copy()
+
+    def _bcast(self, arr, dtype):
+        """rank 0's structured array on every rank"""
+        if not self.comm.multi:
+            return arr
+        n = torch.tensor([len(arr) if self.comm.rank == 0 else 0], dtype=torch.int64).to(self._cdev())
+        dist.broadcast(n, 0, group=self.comm.group)
+        b = torch.zeros(int(n.item()) * dtype.itemsize, dtype=torch.uint8)
+        if self.comm.rank == 0:
+            b = torch.from_numpy(np.frombuffer(arr.tobytes(), dtype=np.uint8).copy())
+        b = b.to(self._cdev())
+        dist.broadcast(b, 0, group=self.comm.group)
+        return np.frombuffer(b.cpu().numpy().tobytes(), dtype=dtype).copy()
+
+    # -- domain_nonrecursively_combine_topTree, :1178-1261
+    def _combine(self, tree, MaxTopNodes):
+        comm = self.comm
+        errorflag = 0
+        size = len(tree)
+        sep = 1
+        while sep < comm.size:
+            if comm.rank % sep == 0:
+                if (comm.rank // sep) % 2 == 0:
+                    src = comm.rank + sep
+                    if src < comm.size:
+                        imp = self._recv(src, capi.LOCAL_TOPNODE_DTYPE)
+                        if size + len(imp) > MaxTopNodes:
+                            errorflag = 1
+                        elif len(imp) > 0 and not errorflag:
+                            merged = self.ops.merge(tree, imp, MaxTopNodes)
+                            if merged is None:
+                                errorflag = 1
+                            else:
+                                tree, size = merged, len(merged)
+                else:
+                    dst = comm.rank - sep
+                    if dst >= 0:
+                        self._send(tree, dst)
+                    size = -1
+            sep *= 2
+        tree = self._bcast(tree, capi.LOCAL_TOPNODE_DTYPE)
+        if len(tree) >= MaxTopNodes:
+            errorflag = 1
+        return (None if self._any(errorflag) else tree)
+
+    # -- domain_attempt_decompose / domain_determine_global_toptree, :452-500, :1269-1318
+    def _attempt(self, pol, MaxTopNodes):
+        ops, comm = self.ops, self.comm
+        mine = np.asarray(ops.samples(pol["SubSampleDistance"], pol["PreSort"]), dtype=np.uint64)
+        # mpsort_mpi: sorted across the ranks, every rank keeps as many as it gave
+        allk = np.sort(self._allgather_u64(mine), kind="stable")
+        if comm.multi:
+            n = comm.allreduce_sum_vec(np.eye(comm.size, dtype=np.int64)[comm.rank] * len(mine))
+            off = int(n[:comm.rank].sum())
+            mine = allk[off:off + len(mine)]
+        else:
+            mine = allk
+        # topTree[0].Count == topTree[0].Cost == the rank's samples: the limits of :1287-1291 need no tree
+        limit = len(allk) // pol["NTopLeaves"]
+        tree = ops.local_toptree(mine, limit, limit, MaxTopNodes)
+        if self._any(tree is None):
+            return True
+        tree = self._combine(tree, MaxTopNodes)
+        if tree is None:
+            return True
+        res = ops.finish(tree, MaxTopNodes, limit, limit)
+        if self._any(res is None):
+            return True
+        self.TopNodes, self.TopLeaves = res
+        if len(self.TopLeaves) - 1 < comm.size:
+            raise RuntimeError("Number of Topleaves is less than NTask")
+        return False
+
+    def decompose(self):
+        ops, comm = self.ops, self.comm
+        done = False
+        for i in range(self.policy, self.NPOLICY):
+            pol = self.policies[i]
+            while True:
+                MaxTopNodes = int(self.factor * (ops.numpart + 1))
+                if not self._attempt(pol, MaxTopNodes):
+                    break
+                self.factor *= 1.2
+                if self.factor > 10:
+                    raise RuntimeError("TopNodeAllocFactor = %g, unreasonably large!" % self.factor)
+            # domain_balance, :506-527
+            ops.install(self.TopNodes, self.TopLeaves)
+            count = comm.allreduce_sum_vec(np.asarray(ops.leaf_counts(), dtype=np.int64))
+            self.Tasks, status = ops.balance(self.TopNodes, self.TopLeaves, count, comm.size, self.setaside)
+            if status and i < self.NPOLICY - 1:
+                continue
+            ops.install(self.TopNodes, self.TopLeaves)
+            ops.particle_topleaves()
+            if ops.exchange(comm):
+                if i == self.NPOLICY - 1:
+                    raise RuntimeError("Ran out of policies!")
+                continue
+            self.policy = i
+            done = True
+            break
+        if not done:
+            raise RuntimeError("No suitable domain decomposition policy worked for this particle distribution")
+        ops.gc_sorted()
+        comm.barrier()
+        return self
+
+
+class GpuDomainOps:
+    """DistDomain's operators on the device: parts is a device uint8 tensor of MaxPart particle_data records (layout: the
+    ExchangeLayout DistExchange takes, off_pos / off_topleaf the byte offsets of Pos and TopLeaf), slots / slot_size the per-type slot
+    arrays.  `tables` is the key automaton (capi.peano_tables_from_key of the reference's peano_hilbert_key)."""
+
+    def __init__(self, ctx, tables, layout, off_pos, off_topleaf, BoxSize, parts, numpart, slots, slot_size):
+        self.ctx, self.tables, self.L = ctx, tables, layout
+        self.off_pos, self.off_topleaf, self.box = int(off_pos), int(off_topleaf), float(BoxSize)
+        self.parts, self.numpart, self.slots, self.slot_size = parts, int(numpart), slots, [int(x) for x in slot_size]
+        self.esz = int(layout.part_elsize)
+        self.MaxPart = parts.numel() // self.esz
+        self.keys = None
+
+    def _pv(self):
+        return capi.DomainParts(self.parts.data_ptr(), self.esz, int(self.L.off_flags), self.off_pos, self.numpart, self.box)
+
+    def _sync(self):
+        torch.cuda.current_stream(self.parts.device).synchronize()
+
+    def samples(self, dist_, presort):
+        out = torch.empty(self.numpart // dist_ + 1, dtype=torch.int64, device=self.parts.device)
+        n = C.c_int64()
+        self._sync()
+        capi.check(capi.hip.shq_domain_samples(self.ctx.h, C.byref(self.tables), C.byref(self._pv()), int(dist_), int(presort), out.data_ptr(), C.byref(n)))
+        self.ctx.synchronize()
+        return out[:n.value].cpu().numpy().view(np.uint64)
+
+    def local_toptree(self, lp, countlimit, costlimit, MaxTopNodes):
+        d = torch.from_numpy(np.ascontiguousarray(lp, dtype=np.uint64).view(np.int64).copy()).to(self.parts.device)
+        tree = np.zeros(MaxTopNodes, dtype=capi.LOCAL_TOPNODE_DTYPE)
+        size = C.c_int()
+        self._sync()
+        rc = capi.hip.shq_domain_local_toptree(self.ctx.h, d.data_ptr(), len(lp), int(countlimit), int(costlimit), int(MaxTopNodes), tree.ctypes.data, C.byref(size))
+        if rc == capi.ERR_RETRY:
+            return None
+        capi.check(rc)
+        return tree[:size.value].copy()
+
+    @staticmethod
+    def merge(A, B, MaxTopNodes):
+        buf = np.zeros(MaxTopNodes, dtype=capi.LOCAL_TOPNODE_DTYPE)
+        buf[:len(A)] = A
+        size = C.c_int(len(A))
+        B = np.ascontiguousarray(B)
+        rc = capi.hip.shq_domain_toptree_merge(buf.ctypes.data, C.byref(size), B.ctypes.data, len(B), int(MaxTopNodes))
+        if rc == capi.ERR_RETRY:
+            return None
+        capi.check(rc)
+        return buf[:size.value].copy()
+
+    @staticmethod
+    def finish(T, MaxTopNodes, countlimit, costlimit):
+        buf = np.zeros(MaxTopNodes, dtype=capi.LOCAL_TOPNODE_DTYPE)
+        buf[:len(T)] = T
+        size, nl = C.c_int(len(T)), C.c_int()
+        N = np.zeros(MaxTopNodes, dtype=capi.TOPNODE_DTYPE)
+        L = np.zeros(MaxTopNodes + 1, dtype=capi.TOPLEAF_DTYPE)
+        rc = capi.hip.shq_domain_toptree_finish(buf.ctypes.data, C.byref(size), int(MaxTopNodes), int(countlimit), int(costlimit), N.ctypes.data, L.ctypes.data,
+                                                C.byref(nl))
+        if rc == capi.ERR_RETRY:
+            return None
+        capi.check(rc)
+        return N[:size.value].copy(), L[:nl.value + 1].copy()
+
+    def balance(self, N, L, count, NTask, SetAsideFactor):
+        Tasks = np.zeros(NTask + 1, dtype=capi.TASK_LEAFS_DTYPE)
+        status = C.c_int()
+        count = np.ascontiguousarray(count, dtype=np.int64)
+        capi.check(capi.hip.shq_domain_balance(N.ctypes.data, len(N), L.ctypes.data, len(L) - 1, count.ctypes.data, int(NTask), int(self.MaxPart), float(SetAsideFactor),
+                                               Tasks.ctypes.data, C.byref(status)))
+        return Tasks, int(status.value)
+
+    def install(self, N, L, geo=None):
+        capi.check(capi.hip.shq_domain_install(self.ctx.h, C.byref(self.tables), N.ctypes.data, len(N), L.ctypes.data, len(L) - 1,
+                                               None if geo is None else geo.ctypes.data))
+        self.ntopleaves = len(L) - 1
+
+    def leaf_counts(self):
+        out = np.zeros(self.ntopleaves, dtype=np.int64)
+        self._sync()
+        capi.check(capi.hip.shq_domain_leaf_counts(self.ctx.h, C.byref(self._pv()), out.ctypes.data))
+        return out
+
+    def _topleaf_field(self):
+        """the TopLeaf members of the records as an int32 view [MaxPart]"""
+        return self.parts.view(-1, self.esz)[:, self.off_topleaf:self.off_topleaf + 4]
+
+    def particle_topleaves(self):
+        n, dev = self.numpart, self.parts.device
+        leaf = self._topleaf_field()[:n].contiguous().view(torch.int32).reshape(-1)      # garbage keeps its old leaf
+        self.target = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+        self._sync()
+        capi.check(capi.hip.shq_domain_particle_topleaves(self.ctx.h, C.byref(self._pv()), leaf.data_ptr(), self.target.data_ptr()))
+        self.ctx.synchronize()
+        self._topleaf_field()[:n] = leaf.view(torch.uint8).view(-1, 4)
+        return self.target[:n]
+
+    def exchange(self, comm):
+        """DomainExchangePlan::domain_exchange with the targets of particle_topleaves; 1 where the reference reports "Could not exchange" """
+        def layoutfn(parts, numpart):
+            # layoutfunc (:159-164) every round, arrivals included: their keys name the leaves they were sent for
+            self.numpart = numpart
+            return self.particle_topleaves()
+        try:
+            self.numpart, self.slot_size = DistExchange(comm, self.ctx, self.L).exchange(self.parts, self.numpart, self.slots, self.slot_size, layoutfn)
+        except MemoryError:
+            return 1
+        return 0
+
+    def gc_sorted(self):
+        n, dev = self.numpart, self.parts.device
+        keys = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+        self._sync()
+        capi.check(capi.hip.shq_peano_keys(self.ctx.h, C.byref(self.tables), self.parts.data_ptr() + self.off_pos, self.esz, n, self.box, keys.data_ptr()))
+        np_ = C.c_int64(n)
+        sz = (C.c_int64 * 6)(*self.slot_size)
+        sp = (C.c_void_p * 6)(*[None if s is None else s.data_ptr() for s in self.slots])
+        capi.check(capi.hip.shq_slots_gc_sorted(self.ctx.h, C.byref(self.L), self.parts.data_ptr(), C.byref(np_), self.MaxPart, sp, sz, keys.data_ptr()))
+        self.ctx.synchronize()
+        self.numpart, self.slot_size = int(np_.value), [int(x) for x in sz]
