@@ -2103,6 +2103,101 @@ int shq_starformation(shq_context *ctx, const shq_part_view *parts, const shq_sp
                       int32_t *NewParents, double *mass_of_star, uint8_t *split, int64_t newstar_capacity, int32_t *MaybeWind, double *sm, int64_t maybewind_capacity,
                       int32_t *deferred, int64_t deferred_capacity, shq_sfr_result *result);
 
+/* ---- Snapshot blocks: selection, typed columns, readout (libgadget/petaio.cpp, fofpetaio.cpp; csrc/snapshot.hip) ------------------------
+ * The three per-particle loops of a snapshot on device-resident records, in the conventions of shq_exchange_*: particle_data[] and the
+ * slot arrays are opaque bytes behind device pointers, fields are byte offsets, counts come back through host int64_t.
+ *   petaio_build_selection (petaio.cpp:86-128), fof_select_func (fofpetaio.cpp:33-36)        shq_io_select
+ *   petaio_build_buffer (:550-575) with the getters (:673-894, :1012-1023)                   shq_io_gather
+ *   GTNeutralHydrogenFraction ... GTHeliumIIIFraction (:817-849)                             shq_io_ion_fractions
+ *   petaio_readout_buffer (:536-545) with the setters (:684-893)                             shq_io_scatter
+ * bigfile I/O, the header, the neutrino blocks and the FOF group blocks stay with the caller. */
+#define SHQ_IO_SELECT_ALL 0   /* the reference's NULL select function */
+#define SHQ_IO_SELECT_FOF 1   /* fof_select_func: GrNr >= 0 && !Swallowed */
+#define SHQ_IO_ORDER_INDEX 0  /* every type in index order (the serial second loop of petaio_build_selection) */
+#define SHQ_IO_ORDER_GRNR 1   /* every type in order of GrNr, ties in index order: what fof_distribute_particles' local sort
+                                 (fofpetaio.cpp:365-374) leaves for the selection that follows it; the reference's sort is unstable among equal
+                                 GrNr, this one is stable, as in shq_slots_gc_sorted */
+typedef struct shq_io_layout {
+    size_t part_elsize, off_flags, off_type, off_pi;   /* as shq_exchange_layout: bit 0 of the flag byte IsGarbage, bit 1 Swallowed */
+    size_t off_grnr;                                   /* int64 GrNr; read by SHQ_IO_SELECT_FOF and SHQ_IO_ORDER_GRNR only */
+    size_t slot_elsize[6];                             /* 0: the type has no slots */
+} shq_io_layout;
+/* petaio_build_selection: d_selection (int32[numpart], device) receives the indices of the particles that are not garbage and pass the
+ * predicate, grouped by type: type t at offset[t] = sum of count[< t].  Entries behind the last selected one are unspecified.  A selected
+ * particle with Type > 5 is SHQ_ERR_INVALID.  Synchronous (count and offset are host arrays). */
+int shq_io_select(shq_context *ctx, const shq_io_layout *layout, const void *d_parts, int64_t numpart, int predicate, int order, int32_t *d_selection,
+                  int64_t count[6], int64_t offset[6]);
+
+/* A block: where one column of a snapshot comes from (getter) or goes to (setter).  `field_type` is the type of the member in the record,
+ * `col_type` the type of the column in the file ("f8" "f4" "u8" "u4" "i4" "u1" are SHQ_IO_F64 _F32 _U64 _U32 _I32 _U8). */
+#define SHQ_IO_SRC_BASE 0   /* particle_data */
+#define SHQ_IO_SRC_SLOT 1   /* the slot of the call's ptype, through PI */
+#define SHQ_IO_F64 0
+#define SHQ_IO_F32 1
+#define SHQ_IO_I64 2
+#define SHQ_IO_U64 3
+#define SHQ_IO_I32 4
+#define SHQ_IO_U32 5
+#define SHQ_IO_I8 6
+#define SHQ_IO_U8 7
+#define SHQ_IO_BITS 8       /* bit_width bits from bit_shift of the byte at offset (HeIIIionized, Swallowed, Generation); field type only */
+#define SHQ_IO_COPY 0            /* SIMPLE_GETTER(_PI) / SIMPLE_SETTER(_PI): out[k] = (col) field[k], field[k] = (field) in[k], C conversions;
+                                    the bit-field form writes only its bits */
+#define SHQ_IO_POSITION 1        /* GTPosition / GTBlackholeMinPotPos: out = x - CurrentParticleOffset[d]; while(out > BoxSize) out -= BoxSize;
+                                    while(out <= 0) out += BoxSize; each loop at most 64 rounds.  A non-finite value or a loop that does not end
+                                    is SHQ_ERR_INVALID (the reference would spin).  As a setter a plain copy (STPosition removes no offset). */
+#define SHQ_IO_SCALE 2           /* GTVelocity: out = (col) (fac * field[d]); STVelocity: field[d] = in[d] * fac */
+#define SHQ_IO_INTERNAL_ENERGY 3 /* GTInternalEnergy: (float) (Entropy / GAMMA_MINUS1 * pow(Density * a3inv, GAMMA_MINUS1)); STInternalEnergy:
+                                    Entropy = GAMMA_MINUS1 * u / pow(Density * a3inv, GAMMA_MINUS1).  offset = Entropy, offset2 = Density */
+#define SHQ_IO_MAXBLOCKS 48      /* blocks per kernel launch; longer arrays are served in several launches */
+typedef struct shq_io_block {
+    int32_t source, kind, field_type, col_type;
+    int32_t items;                  /* consecutive members of field_type from offset */
+    int32_t bit_shift, bit_width;   /* SHQ_IO_BITS */
+    int32_t pad_;
+    uint64_t offset, offset2;
+} shq_io_block;
+typedef struct shq_io_conv {
+    double fac;                       /* SCALE: getter 1 / atime under UsePeculiarVelocity else 1; setter atime else 1 */
+    double atime;                     /* INTERNAL_ENERGY: a3inv = 1 / (atime * atime * atime) */
+    double BoxSize;                   /* POSITION */
+    double CurrentParticleOffset[3];
+} shq_io_conv;
+/* petaio_build_buffer for all blocks of one particle type in one pass: column b (d_out[b], device) is dense [n][items_b] of its col_type,
+ * row k belongs to particle d_selection[k].  A record is read from HBM once per call: a tile of selected records is staged in LDS, then
+ * one lane per record picks the fields; slot records reached through PI go through the same code.  Checked before the dependent read,
+ * each SHQ_ERR_INVALID with the outputs unspecified: a selection index outside [0, numpart); a selected particle whose Type != ptype
+ * ("Selection %d has type ...", :569-571); a PI outside [0, slot_size[ptype]) when a block reads the slot.  Records and slot arrays must be
+ * 8-byte aligned with sizes that are multiples of 8 and at most 480 bytes.  Synchronous (the status comes from the device). */
+int shq_io_gather(shq_context *ctx, const shq_io_layout *layout, const void *d_parts, int64_t numpart, const void *const d_slots[6], const int64_t slot_size[6],
+                  int ptype, const int32_t *d_selection, int64_t n, const shq_io_block *blocks, int nblocks, const shq_io_conv *conv, void *const d_out[]);
+/* petaio_readout_buffer: the k-th particle of Type == ptype in index order (garbage included: the reference has no garbage test there) takes
+ * row k of every column d_in[b] (device, dense [n][items_b] of col_type).  Blocks are applied in array order per particle: STInternalEnergy
+ * reads the Density an earlier block of the call may have written.  Each particle is written by one lane.  n != the number of particles
+ * of the type, or a PI outside the slot array when a block writes the slot, is SHQ_ERR_INVALID before anything is written. */
+int shq_io_scatter(shq_context *ctx, const shq_io_layout *layout, void *d_parts, int64_t numpart, void *const d_slots[6], const int64_t slot_size[6], int ptype,
+                   int64_t n, const shq_io_block *blocks, int nblocks, const shq_io_conv *conv, const void *const d_in[]);
+
+/* The four ion-fraction columns: get_neutral_fraction_sfreff and get_helium_neutral_fraction_sfreff(0 / 1 / 2) (sfr_eff.cpp:536-600) for the
+ * gas particles of a list, by the engine of shq_sfr_eval (SHQ_SFR_NH0 ... SHQ_SFR_HEPP) with the per-particle local UVBG of shq_cooling
+ * (step->uvbg_mode) and dloga_for_bin[TimeBinHydro].  Views, staging and shq_set_inputs_current as in shq_starformation.
+ *   list, n      : particle indices (host), e.g. the gas part of a selection; NULL: all particles
+ *   which_mask   : bit q set: out[q] (host, [n] floats) receives (float) of query q: 0 NH0, 1 HeI, 2 HeII, 3 HeIII
+ *   status [n]   : the first outcome other than SHQ_COOL_OK among the particle's queries, else SHQ_COOL_OK
+ *   listed       : the list positions whose status is not SHQ_COOL_OK, in order: their rows hold a quiet NaN and are the caller's to fill with
+ *                  the reference's own function (the contract of the deferred lists).  More than listed_capacity: SHQ_ERR_NOMEM after
+ *                  everything else has been written.
+ * SHQ_ERR_STATE without shq_cooling_set_tables. */
+typedef struct shq_io_ion_result {
+    int64_t n_status[SHQ_COOL_NSTATUS];
+    int64_t n_listed;
+    int64_t steps;
+    double kernel_ms;
+} shq_io_ion_result;
+int shq_io_ion_fractions(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_sfr_fields *fields, const shq_sfr_params *par,
+                         const shq_cooling_step *step, const int32_t *list, int64_t n, int which_mask, float *const out[4], int32_t *status, int32_t *listed,
+                         int64_t listed_capacity, shq_io_ion_result *result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1039,3 +1039,8 @@ def hydro_force(ctx, act, atime, hubble, EntVarPred, kick, tree, pman, SphP, dri
                                     atime, hubble, capi.ptr(EntVarPred), C.byref(kick), capi.ptr(d), int(UseGPU), C.byref(st))
     capi.check_host(rc, "hydro_force")
     return st
+
+# ---- snapshot blocks: selection, typed columns, readout (csrc/snapshot.hip; snapshot.py) ----------
+from .snapshot import (IOBlock, io_blocks, io_layout, io_conv, io_select, io_gather, io_scatter, io_ion_fractions, snapshot_columns,  # noqa: E402,F401
+                       snapshot_readout)
+from .capi import IO_SELECT_ALL, IO_SELECT_FOF, IO_ORDER_INDEX, IO_ORDER_GRNR  # noqa: E402,F401

@@ -1170,3 +1170,42 @@ hip.shq_pm_slab_green.argtypes = [_vp, C.POINTER(PMParams), C.c_int, C.c_int, _v
 hip.shq_pm_slab_readout.argtypes = [_vp, C.POINTER(PMParams), C.c_int, C.c_int, _vp]
 hip.shq_pm_get_deposit_log2scale.argtypes = [_vp]
 hip.shq_pm_set_deposit_log2scale.argtypes = [_vp, C.c_int]
+
+# ---- snapshot blocks (csrc/snapshot.hip) ------------------------------------------------------
+IO_SELECT_ALL, IO_SELECT_FOF = 0, 1
+IO_ORDER_INDEX, IO_ORDER_GRNR = 0, 1
+IO_SRC_BASE, IO_SRC_SLOT = 0, 1
+IO_F64, IO_F32, IO_I64, IO_U64, IO_I32, IO_U32, IO_I8, IO_U8, IO_BITS = range(9)
+IO_COPY, IO_POSITION, IO_SCALE, IO_INTERNAL_ENERGY = range(4)
+IO_TYPE_OF_DTYPE = {"f8": IO_F64, "f4": IO_F32, "i8": IO_I64, "u8": IO_U64, "i4": IO_I32, "u4": IO_U32, "i1": IO_I8, "u1": IO_U8}
+
+
+class IoLayout(C.Structure):
+    """shq_io_layout"""
+    _fields_ = [("part_elsize", C.c_size_t), ("off_flags", C.c_size_t), ("off_type", C.c_size_t), ("off_pi", C.c_size_t), ("off_grnr", C.c_size_t),
+                ("slot_elsize", C.c_size_t * 6)]
+
+
+class IoBlock(C.Structure):
+    """shq_io_block"""
+    _fields_ = [("source", C.c_int32), ("kind", C.c_int32), ("field_type", C.c_int32), ("col_type", C.c_int32), ("items", C.c_int32), ("bit_shift", C.c_int32),
+                ("bit_width", C.c_int32), ("pad_", C.c_int32), ("offset", C.c_uint64), ("offset2", C.c_uint64)]
+
+
+class IoConv(C.Structure):
+    """shq_io_conv"""
+    _fields_ = [("fac", C.c_double), ("atime", C.c_double), ("BoxSize", C.c_double), ("CurrentParticleOffset", C.c_double * 3)]
+
+
+class IoIonResult(C.Structure):
+    """shq_io_ion_result"""
+    _fields_ = [("n_status", C.c_int64 * 4), ("n_listed", C.c_int64), ("steps", C.c_int64), ("kernel_ms", C.c_double)]
+
+
+hip.shq_io_select.argtypes = [_vp, C.POINTER(IoLayout), _vp, C.c_int64, C.c_int, C.c_int, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+hip.shq_io_gather.argtypes = [_vp, C.POINTER(IoLayout), _vp, C.c_int64, _vp, C.POINTER(C.c_int64), C.c_int, _vp, C.c_int64, _vp, C.c_int, C.POINTER(IoConv), _vp]
+hip.shq_io_scatter.argtypes = [_vp, C.POINTER(IoLayout), _vp, C.c_int64, _vp, C.POINTER(C.c_int64), C.c_int, C.c_int64, _vp, C.c_int, C.POINTER(IoConv), _vp]
+hip.shq_io_ion_fractions.argtypes = [_vp, C.POINTER(PartView), C.POINTER(SphView), C.POINTER(SfrFields), C.POINTER(SfrParams), C.POINTER(CoolingStep), _vp, C.c_int64,
+                                     C.c_int, _vp, _vp, _vp, C.c_int64, C.POINTER(IoIonResult)]
+for _f in ("shq_io_select", "shq_io_gather", "shq_io_scatter", "shq_io_ion_fractions"):
+    getattr(hip, _f).restype = C.c_int

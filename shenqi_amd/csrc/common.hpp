@@ -388,6 +388,11 @@ struct shq_context {
     DevBuf<int32_t> dd_i32[3];
     DevBuf<uint8_t> dd_u8;
     DevBuf<char> dd_rec;
+    /* snapshot blocks (snapshot.hip) */
+    DevBuf<uint8_t> io_u8[2];            /* type keys, in and out of the sort */
+    DevBuf<unsigned long long> io_u64[2]; /* GrNr keys, in and out of the sort */
+    DevBuf<int32_t> io_i32;              /* indices between the two sorts; the readout's list of a type */
+    DevBuf<unsigned long long> io_cnt;   /* [0..7] counts by key, [8] the error word, [9] a selected count */
     /* friends-of-friends (fof.hip) */
     DevBuf<int32_t> fof_parent, fof_i32[6], fof_g32[5], fof_partgrnr, fof_members, fof_biglist;
     DevBuf<unsigned long long> fof_u64[4];

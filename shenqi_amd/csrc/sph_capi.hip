@@ -1895,9 +1895,10 @@ int sfr_run(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sp
     SHQ_CHECK(step->uvbg_mode >= SHQ_COOL_UVBG_GLOBAL && step->uvbg_mode <= SHQ_COOL_UVBG_J21, SHQ_ERR_INVALID, "star formation: uvbg_mode = %d", step->uvbg_mode);
     SHQ_CHECK(step->uvbg_mode != SHQ_COOL_UVBG_J21 || (step->local_J21 && step->zreion), SHQ_ERR_INVALID, "star formation: the J21 mode needs local_J21 and zreion");
     SHQ_CHECK(step->hubble > 0 && step->a3inv > 0, SHQ_ERR_INVALID, "star formation: hubble and a3inv must be > 0");
-    SHQ_CHECK(what == SHQ_SFR_ON_EEQOS || (rnd_table && rnd_size > 0 && ids), SHQ_ERR_INVALID, "star formation: needs the IDs and a random table");
+    /* only starformation() draws; sfreff_on_eeqos and the ion-fraction queries read neither the IDs, the table nor GradRho */
+    SHQ_CHECK(what != SHQ_SFR_STARFORM || (rnd_table && rnd_size > 0 && ids), SHQ_ERR_INVALID, "star formation: needs the IDs and a random table");
     /* "GradRho not allocated but has SFR_CRITERION_MOLECULAR_H2" (sfr_eff.cpp:822-823) */
-    SHQ_CHECK(what == SHQ_SFR_ON_EEQOS || GradRho || (par->StarformationCriterion & 3) != 3, SHQ_ERR_INVALID,
+    SHQ_CHECK(what != SHQ_SFR_STARFORM || GradRho || (par->StarformationCriterion & 3) != 3, SHQ_ERR_INVALID,
               "star formation: GradRho is NULL but StarformationCriterion has the H2 bits");
     SHQ_TRY(winds_list_check(parts, list, nlist, false, "star formation"));
     SHQ_CHECK(ctx->cool_have, SHQ_ERR_STATE, "star formation: shq_cooling_set_tables first");
@@ -1953,7 +1954,7 @@ int sfr_run(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sp
     int32_t *d_list = ctx->cool_i.ptr, *d_status = d_list + C, *d_steps = d_status + C;
     SHQ_HIP(hipMemcpyAsync(d_list, r->hlist.data(), sizeof(int32_t) * C, hipMemcpyHostToDevice, st));
     const double *d_rnd = nullptr;
-    if(what != SHQ_SFR_ON_EEQOS) {
+    if(what == SHQ_SFR_STARFORM) {
         SHQ_TRY(ids_upload(ctx, ids, n));
         SHQ_TRY(ctx->bhw_rnd.reserve((size_t) rnd_size));
         SHQ_HIP(hipMemcpyAsync(ctx->bhw_rnd.ptr, rnd_table, sizeof(double) * (size_t) rnd_size, hipMemcpyHostToDevice, st));
@@ -1977,7 +1978,7 @@ int sfr_run(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sp
     a.gradrho = GradRho ? d + 2 * N : nullptr;
     a.j21 = j21 ? d + 3 * N : nullptr;
     a.zre = j21 ? d + 4 * N : nullptr;
-    a.ids = what != SHQ_SFR_ON_EEQOS ? ctx->bhw_ids.ptr : nullptr;
+    a.ids = what == SHQ_SFR_STARFORM ? ctx->bhw_ids.ptr : nullptr;
     a.dloga_for_bin = d_bins;
     a.ztab = ctx->cool_zreion.ptr;
     a.znside = ctx->cool_znside;
@@ -2121,5 +2122,54 @@ extern "C" int shq_starformation(shq_context *ctx, const shq_part_view *parts, c
               (long) maybewind_capacity);
     SHQ_CHECK(result->n_deferred <= deferred_capacity, SHQ_ERR_NOMEM, "starformation: %ld deferred particles, room for %ld", (long) result->n_deferred,
               (long) deferred_capacity);
+    return SHQ_OK;
+}
+
+/* ---- the ion-fraction columns of a snapshot (petaio.cpp:817-849): the queries of the same engine over a list ---- */
+extern "C" int shq_io_ion_fractions(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_sfr_fields *fields, const shq_sfr_params *par,
+                                    const shq_cooling_step *step, const int32_t *list, int64_t n, int which_mask, float *const out[4], int32_t *status,
+                                    int32_t *listed, int64_t listed_capacity, shq_io_ion_result *result)
+{
+    SHQ_CHECK(ctx && parts && sph && fields && par && step && result && out, SHQ_ERR_INVALID, "null argument");
+    SHQ_CHECK(which_mask >= 0 && which_mask < 16, SHQ_ERR_INVALID, "io_ion_fractions: which_mask = %d", which_mask);
+    SHQ_CHECK(listed_capacity >= 0 && (listed || listed_capacity == 0), SHQ_ERR_INVALID, "io_ion_fractions: the list of refused particles is NULL");
+    memset(result, 0, sizeof(*result));
+    const int64_t cnt = list ? n : parts->numpart;
+    SHQ_CHECK(cnt == 0 || status, SHQ_ERR_INVALID, "io_ion_fractions: status is NULL");
+    for(int q = 0; q < 4; q++)
+        SHQ_CHECK(!(which_mask >> q & 1) || out[q] || cnt == 0, SHQ_ERR_INVALID, "io_ion_fractions: column %d is NULL", q);
+    for(int64_t k = 0; k < cnt; k++)
+        status[k] = SHQ_COOL_OK;
+    bool ran = false;
+    for(int q = 0; q < 4; q++) {
+        if(!(which_mask >> q & 1))
+            continue;
+        SfrRun r;
+        SHQ_TRY(sfr_run(ctx, parts, sph, fields->off_ne, fields->off_metallicity, nullptr, nullptr, par, SHQ_SFR_NH0 + q, list, n, step, nullptr, 0, &r));
+        result->kernel_ms += ctx->sfr_ms;
+        result->steps += ctx->sfr_steps;
+        const size_t C = r.hlist.size();
+        for(size_t k = 0; k < C; k++) {
+            if(status[k] == SHQ_COOL_OK && r.status[k] != SHQ_COOL_OK)
+                status[k] = r.status[k];
+            out[q][k] = (float) r.out[(size_t) SHQ_SFR_O_QUERY * C + k];
+        }
+        ran = true;
+    }
+    if(!ran) /* no column asked for: the list is still checked by nothing, and nothing is refused */
+        return SHQ_OK;
+    for(int64_t k = 0; k < cnt; k++) {
+        const int s = status[k];
+        result->n_status[s]++;
+        if(s == SHQ_COOL_OK)
+            continue;
+        for(int q = 0; q < 4; q++)
+            if(which_mask >> q & 1)
+                out[q][k] = __builtin_nanf("");
+        if(result->n_listed < listed_capacity)
+            listed[result->n_listed] = (int32_t) k;
+        result->n_listed++;
+    }
+    SHQ_CHECK(result->n_listed <= listed_capacity, SHQ_ERR_NOMEM, "io_ion_fractions: %ld refused particles, room for %ld", (long) result->n_listed, (long) listed_capacity);
     return SHQ_OK;
 }
