@@ -2198,6 +2198,69 @@ int shq_io_ion_fractions(shq_context *ctx, const shq_part_view *parts, const shq
                          const shq_cooling_step *step, const int32_t *list, int64_t n, int which_mask, float *const out[4], int32_t *status, int32_t *listed,
                          int64_t listed_capacity, shq_io_ion_result *result);
 
+/* ---- Light-cone crossings: replicas, sampling, ordered rows (libgadget/lightcone.cpp; csrc/lightcone.hip) --------------------------------
+ * lightcone_compute (run.cpp:687) on device-resident records, in the conventions of shq_io_* / shq_exchange_*.
+ *   lightcone_get_horizon (:101-115)                     shq_lightcone_horizon    host
+ *   lightcone_init, the statics' start (:95)             shq_lightcone_init       host
+ *   lightcone_set_time, update_replicas (:118-200)       shq_lightcone_set_time   host
+ *   the loop over lightcone_cross (:159-168, :203-250)   shq_lightcone_compute    device
+ * The three host functions replay the reference statement by statement (same expression order, same int truncation of the bin) and
+ * need no GPU.  The table is the caller's (the reference integrates it with boost's Gauss-Kronrod rule); the output file too.
+ *
+ * Lines :219-220 of the reference read the velocity of record i, the REPLICA index, and add no replica shift to the new position, so
+ * |pnew| stays below about the box diagonal and nothing crosses a horizon beyond it.  Two modes:
+ *   SHQ_LIGHTCONE_CONSISTENT  velocity of particle p, the replica shift on both ends (what the file's comments describe)
+ *   SHQ_LIGHTCONE_AS_WRITTEN  :219-220 literally: the same set of rows as the reference's call; needs numpart >= Nreplica */
+#define SHQ_LIGHTCONE_MAXREPLICA 1000
+#define SHQ_LIGHTCONE_CONSISTENT 0
+#define SHQ_LIGHTCONE_AS_WRITTEN 1
+typedef struct shq_lightcone_params {
+    double zmin, zmax, ReferenceRedshift;   /* reference: 0.1, 80, 2.0 */
+    int32_t BoxBoost, pad_;                 /* reference: 20 */
+} shq_lightcone_params;
+typedef struct shq_lightcone_table {
+    const double *tab_loga, *tab_Dc;        /* host, nentry each: tab_loga[i] = -dloga * (nentry - i - 1), comoving distance to a = exp(tab_loga[i]) */
+    int32_t nentry, pad_;
+    double dloga;
+} shq_lightcone_table;
+typedef struct shq_lightcone_state {        /* the reference's file statics */
+    double HorizonDistance, HorizonDistance2, HorizonDistancePrev, HorizonDistance2Prev, HorizonDistanceRef, SampleFraction;
+    int32_t Nreplica, pad_;
+    double Reps[SHQ_LIGHTCONE_MAXREPLICA][3];
+} shq_lightcone_state;
+typedef struct shq_lightcone_layout {
+    size_t part_elsize, off_type, off_pos, off_vel, off_id;   /* double Pos[3], double Vel[3] (MyFloat as shq_part_view has it), uint64 ID, the Type byte as in shq_io_layout */
+} shq_lightcone_layout;
+
+/* Linear interpolation of the table in log a; the bin truncates toward zero, the result clamps at both ends.  a <= 0, a NULL or a table
+ * of fewer than 2 entries or dloga <= 0: SHQ_ERR_INVALID. */
+int shq_lightcone_horizon(const shq_lightcone_table *t, double a, double *Dc);
+/* All of the state zero but HorizonDistanceRef = horizon(1 / (1 + ReferenceRedshift)). */
+int shq_lightcone_init(const shq_lightcone_table *t, const shq_lightcone_params *p, shq_lightcone_state *s);
+/* Inside zmin < z < zmax: the horizons move to Prev, the new horizon, the replica list (rx-major, then ry, then rz; the 1001st is
+ * SHQ_ERR_INVALID, "too many replica", the state then holding the first 1000), SampleFraction.  Outside the
+ * window only SampleFraction = 0.  BoxBoost outside 1 .. 1290 (BoxBoost^3 fits an int) is SHQ_ERR_INVALID. */
+int shq_lightcone_set_time(const shq_lightcone_table *t, const shq_lightcone_params *p, double a, double BoxSize, shq_lightcone_state *s);
+/* The crossings of every Type-1 particle (garbage or not: the reference has no garbage test) with every replica of the state.
+ *   d_parts    : device, numpart records of layout->part_elsize bytes, 8-byte aligned; numpart in [0, 2^31 - 200)
+ *   ddrift, CurrentParticleOffset : as the reference's arguments; finite
+ *   rnd_table  : RandTable::Table on the host (rnd_size > 0 entries), staged in the context's buffer of the winds and star-formation
+ *                entries; the draw of (p, i) is rnd_table[(ID + i) % rnd_size], the sum wrapping in uint64
+ *   d_rows     : device, [capacity][4] doubles: x, y, z of the interpolated crossing, SampleFraction
+ *   d_index, d_replica : device, int32[capacity], either may be NULL: the particle index and the replica index of each row
+ *   *nrows     : always the number of crossings found
+ * Rows are ordered by particle index, then by replica index: the reference's loop on one thread.  The bytes are reproducible.
+ * *nrows > capacity: nothing is written, SHQ_ERR_NOMEM; repeat the call with room.  SampleFraction <= 0 or Nreplica == 0: zero rows,
+ * no launch.  SHQ_ERR_INVALID with nothing written for a NULL argument, a part_elsize that is no multiple of 8 or outside 8 .. 480, a
+ * member outside the record or misaligned, numpart out of range, rnd_size <= 0, a non-finite ddrift, offset or horizon, Nreplica outside
+ * 0 .. SHQ_LIGHTCONE_MAXREPLICA, an unknown mode, AS_WRITTEN with numpart < Nreplica.  All f64, no contraction, IEEE sqrt and divide.
+ * Synchronous. */
+int shq_lightcone_compute(shq_context *ctx, const shq_lightcone_layout *layout, const void *d_parts, int64_t numpart, const shq_lightcone_state *s, int mode,
+                          double ddrift, const double CurrentParticleOffset[3], const double *rnd_table, int64_t rnd_size, double *d_rows, int32_t *d_index,
+                          int32_t *d_replica, int64_t capacity, int64_t *nrows);
+/* Device times of the last shq_lightcone_compute that launched, in ms: pass A (counts), the scan, pass B (rows; 0 when nothing crossed). */
+int shq_lightcone_phase_ms(shq_context *ctx, double ms[3]);
+
 #ifdef __cplusplus
 }
 #endif

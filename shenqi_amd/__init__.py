@@ -1044,3 +1044,8 @@ def hydro_force(ctx, act, atime, hubble, EntVarPred, kick, tree, pman, SphP, dri
 from .snapshot import (IOBlock, io_blocks, io_layout, io_conv, io_select, io_gather, io_scatter, io_ion_fractions, snapshot_columns,  # noqa: E402,F401
                        snapshot_readout)
 from .capi import IO_SELECT_ALL, IO_SELECT_FOF, IO_ORDER_INDEX, IO_ORDER_GRNR  # noqa: E402,F401
+
+# ---- light-cone crossings: replicas, sampling, ordered rows (csrc/lightcone.hip; lightcone.py) ----------
+from .lightcone import (Lightcone, LightconeStateView, lightcone_layout, lightcone_table, lightcone_horizon, lightcone_compute_raw,  # noqa: E402,F401
+                        lightcone_phase_ms)
+from .capi import LIGHTCONE_CONSISTENT, LIGHTCONE_AS_WRITTEN, LIGHTCONE_MAXREPLICA  # noqa: E402,F401

@@ -1209,3 +1209,41 @@ hip.shq_io_ion_fractions.argtypes = [_vp, C.POINTER(PartView), C.POINTER(SphView
                                      C.c_int, _vp, _vp, _vp, C.c_int64, C.POINTER(IoIonResult)]
 for _f in ("shq_io_select", "shq_io_gather", "shq_io_scatter", "shq_io_ion_fractions"):
     getattr(hip, _f).restype = C.c_int
+
+# ---- light-cone crossings (csrc/lightcone.hip) ------------------------------------------------
+LIGHTCONE_MAXREPLICA = 1000
+LIGHTCONE_CONSISTENT, LIGHTCONE_AS_WRITTEN = 0, 1
+ERR_INVALID, ERR_NOMEM = 1, 3                      # SHQ_ERR_INVALID, SHQ_ERR_NOMEM
+
+
+class LightconeParams(C.Structure):
+    """shq_lightcone_params"""
+    _fields_ = [("zmin", C.c_double), ("zmax", C.c_double), ("ReferenceRedshift", C.c_double), ("BoxBoost", C.c_int32), ("pad_", C.c_int32)]
+
+
+class LightconeTable(C.Structure):
+    """shq_lightcone_table"""
+    _fields_ = [("tab_loga", _vp), ("tab_Dc", _vp), ("nentry", C.c_int32), ("pad_", C.c_int32), ("dloga", C.c_double)]
+
+
+class LightconeState(C.Structure):
+    """shq_lightcone_state"""
+    _fields_ = [("HorizonDistance", C.c_double), ("HorizonDistance2", C.c_double), ("HorizonDistancePrev", C.c_double), ("HorizonDistance2Prev", C.c_double),
+                ("HorizonDistanceRef", C.c_double), ("SampleFraction", C.c_double), ("Nreplica", C.c_int32), ("pad_", C.c_int32),
+                ("Reps", (C.c_double * 3) * LIGHTCONE_MAXREPLICA)]
+
+
+class LightconeLayout(C.Structure):
+    """shq_lightcone_layout"""
+    _fields_ = [("part_elsize", C.c_size_t), ("off_type", C.c_size_t), ("off_pos", C.c_size_t), ("off_vel", C.c_size_t), ("off_id", C.c_size_t)]
+
+
+assert C.sizeof(LightconeState) == 56 + 24 * LIGHTCONE_MAXREPLICA
+hip.shq_lightcone_horizon.argtypes = [C.POINTER(LightconeTable), C.c_double, C.POINTER(C.c_double)]
+hip.shq_lightcone_init.argtypes = [C.POINTER(LightconeTable), C.POINTER(LightconeParams), C.POINTER(LightconeState)]
+hip.shq_lightcone_set_time.argtypes = [C.POINTER(LightconeTable), C.POINTER(LightconeParams), C.c_double, C.c_double, C.POINTER(LightconeState)]
+hip.shq_lightcone_compute.argtypes = [_vp, C.POINTER(LightconeLayout), _vp, C.c_int64, C.POINTER(LightconeState), C.c_int, C.c_double, C.POINTER(C.c_double), _vp,
+                                      C.c_int64, _vp, _vp, _vp, C.c_int64, C.POINTER(C.c_int64)]
+hip.shq_lightcone_phase_ms.argtypes = [_vp, C.POINTER(C.c_double)]
+for _f in ("shq_lightcone_horizon", "shq_lightcone_init", "shq_lightcone_set_time", "shq_lightcone_compute", "shq_lightcone_phase_ms"):
+    getattr(hip, _f).restype = C.c_int

@@ -260,6 +260,7 @@ extern "C" void shq_shutdown(shq_context *ctx)
     for(auto &b : ctx->dd_i64) b.release();
     for(auto &b : ctx->dd_i32) b.release();
     ctx->io_i32.release(); ctx->io_cnt.release();
+    ctx->lc_reps.release(); ctx->lc_cnt.release(); ctx->lc_off.release();
     for(auto &b : ctx->io_u8) b.release();
     for(auto &b : ctx->io_u64) b.release();
     ctx->fof_parent.release(); ctx->fof_partgrnr.release(); ctx->fof_members.release(); ctx->fof_groups.release(); ctx->fof_biglist.release(); ctx->fof_partial.release();

@@ -393,6 +393,11 @@ struct shq_context {
     DevBuf<unsigned long long> io_u64[2]; /* GrNr keys, in and out of the sort */
     DevBuf<int32_t> io_i32;              /* indices between the two sorts; the readout's list of a type */
     DevBuf<unsigned long long> io_cnt;   /* [0..7] counts by key, [8] the error word, [9] a selected count */
+    /* light-cone crossings (lightcone.hip) */
+    DevBuf<double> lc_reps;              /* the state's replica shifts, [Nreplica][3] */
+    DevBuf<int32_t> lc_cnt;              /* crossings per particle, one zero behind the last; then the first two replicas of each */
+    DevBuf<long long> lc_off;            /* their exclusive scan: [numpart] is the row count */
+    double lc_ms[3] = {0, 0, 0};         /* shq_lightcone_phase_ms */
     /* friends-of-friends (fof.hip) */
     DevBuf<int32_t> fof_parent, fof_i32[6], fof_g32[5], fof_partgrnr, fof_members, fof_biglist;
     DevBuf<unsigned long long> fof_u64[4];
