@@ -2261,6 +2261,122 @@ int shq_lightcone_compute(shq_context *ctx, const shq_lightcone_layout *layout, 
 /* Device times of the last shq_lightcone_compute that launched, in ms: pass A (counts), the scan, pass B (rows; 0 when nothing crossed). */
 int shq_lightcone_phase_ms(shq_context *ctx, double ms[3]);
 
+/* ---- Run start-up: init()'s loops, the first Hsml, the initial entropy (libgadget/init.cpp, density2.cpp:154-204; csrc/startup.hip) ----
+ * What the reference does between petaio_read_snapshot and the first step:
+ *   get_mean_separation (init.cpp:390-397)                        shq_startup_mean_separation     host
+ *   u_init of setup_smoothinglengths (:467-498)                   shq_startup_u_init              host
+ *   check_omega's verdict (:223-236)                              shq_startup_omega               host
+ *   check_omega's / check_positions' / check_smoothing_length's / init()'s particle loops (:203-214, :313-335, :342-359, :119-188)
+ *                                                                 shq_startup_particles           device records
+ *   check_density_entropy (:363-388)                              shq_startup_check_density_entropy   device slots
+ *   set_init_hsml (density2.cpp:164-203)                          shq_set_init_hsml               resident particles + current tree
+ *   Entropy from u_init (init.cpp:422-423, :518)                  shq_init_entropy                resident gas
+ *   setup_smoothinglengths + setup_density_indep_entropy (:402-521)   shq_setup_smoothinglengths  host views, one upload
+ * The reference ends the run on the conditions these loops find; here they are reported and the caller decides. */
+
+/* Host functions.  mean_separation: MeanSeparation[t] = BoxSize / pow(NTotalInit[t], 1.0 / 3) where NTotalInit[t] > 0, other entries are
+ * left as they are.  u_init: InitGasTemp < 0 becomes CMBTemperature / atime (*InitGasTemp_used, may be NULL, receives the temperature
+ * used); u = 1 / GAMMA_MINUS1 * (BOLTZMANN / PROTONMASS) * T / uu_in_cgs / molecular_weight, the weight of full ionisation above 1e4 K
+ * and of neutral gas otherwise, floored at MinEgySpec.  omega: omegas[t] = mass_type[t] / (BoxSize^3 RhoCrit), *omega = mass_total /
+ * (BoxSize^3 RhoCrit) + (MassiveNuLinRespOn ? OmegaNu : 0), *bad = |omega - Omega0| > 1.0e-3.  meanbar: check_density_entropy's mean
+ * baryon density, OmegaBaryon 3 (HUBBLE HubbleParam)^2 / (8 pi GRAVITY) in the reference's order. */
+int shq_startup_mean_separation(double MeanSeparation[6], double BoxSize, const int64_t NTotalInit[6]);
+int shq_startup_u_init(double InitGasTemp, double CMBTemperature, double atime, double uu_in_cgs, double MinEgySpec, double *u_init, double *InitGasTemp_used);
+int shq_startup_omega(const double mass_type[6], double mass_total, double BoxSize, double RhoCrit, double OmegaNu, int MassiveNuLinRespOn, double Omega0,
+                      double omegas[6], double *omega, int *bad);
+int shq_startup_meanbar(double OmegaBaryon, double HubbleParam, double *meanbar);
+
+/* Where the members the loops touch lie: byte offsets into the particle record, the gas slot and the black-hole slot (element sizes
+ * multiples of 8, at most 480; every member inside its record and aligned to its own size).  sph_off_local_j21 / sph_off_zreion may be
+ * SHQ_NOFIELD (a build without EXCUR_REION); every other member is required.  The particle record is at most 240 bytes (a tile of 256
+ * records is staged in LDS).  Members: double Pos[3], float Mass, the flag byte
+ * (Generation in its upper four bits), the Type byte, int32 PI, double Hsml, int64 Ti_drift; gas slot doubles Density, EgyWtDensity,
+ * Entropy, DtEntropy, MaxSignalVel, HydroAccel[3], DhsmlEgyDensityFactor, DivVel, CurlVel, Sfr, Ne, DelayTime, Metallicity,
+ * float Metals[sph_nmetals], double local_J21, zreion; black-hole slot doubles Mass, DFAccel[3], DragAccel[3]. */
+typedef struct shq_startup_layout {
+    size_t part_elsize, off_pos, off_mass, off_flags, off_type, off_pi, off_hsml, off_ti_drift;
+    size_t sph_elsize, sph_off_density, sph_off_egywtdensity, sph_off_entropy, sph_off_dtentropy, sph_off_maxsignalvel, sph_off_hydroaccel,
+        sph_off_dhsmlegydensityfactor, sph_off_divvel, sph_off_curlvel, sph_off_sfr, sph_off_ne, sph_off_delaytime, sph_off_metallicity, sph_off_metals,
+        sph_nmetals, sph_off_local_j21, sph_off_zreion;
+    size_t bh_elsize, bh_off_mass, bh_off_dfaccel, bh_off_dragaccel;
+} shq_startup_layout;
+
+#define SHQ_STARTUP_OMEGA 1       /* check_omega's loop: Mass == 0 recovered from MassTable and Generation, badmass, the mass sums */
+#define SHQ_STARTUP_POSITIONS 2   /* check_positions: coordinates outside [0, BoxSize] or not finite; particles at the origin */
+#define SHQ_STARTUP_HSML 4        /* check_smoothing_length: Hsml > BoxSize || Hsml <= 0 of types 0 and 5 becomes MeanSeparation[Type] */
+#define SHQ_STARTUP_INIT 8        /* init()'s field-initialisation loop */
+typedef struct shq_startup_params {
+    double BoxSize;
+    double MassTable[6];
+    double MeanSeparation[6];
+    int64_t Ti_Current;
+    int32_t generations;          /* get_generations() */
+    int32_t RestartSnapNum;       /* -1: initial conditions */
+    int32_t init_reion;           /* the condition of init.cpp:183: ExcursionSetReionOn && TimeSnapshot < 1 / (1 + ExcursionSetZStart) */
+    int32_t pad_;
+} shq_startup_params;
+typedef struct shq_startup_report {
+    double mass_type[6], mass_total;   /* OMEGA: per rank; the caller all-reduces them */
+    int64_t badmass;                   /* OMEGA: masses recovered */
+    int64_t noutside, first_outside;   /* POSITIONS: particles with a coordinate < 0, > BoxSize or not finite; the lowest such index or -1 */
+    int64_t numzero, lastzero;         /* POSITIONS: particles with every coordinate < 1e-35; the highest such index or -1 */
+    int64_t numprob, lastprob;         /* HSML: smoothing lengths replaced; the highest such index or -1 */
+    int64_t nbad_delaytime, first_bad_delaytime; /* INIT: gas with a non-finite DelayTime; the lowest such index or -1 */
+} shq_startup_report;
+/* One pass over the records for every loop in `which` (in the reference's order per record: OMEGA, POSITIONS, HSML, INIT).  d_parts:
+ * numpart records, d_sph / d_bh: the gas and black-hole slot arrays PI indexes (nsph, nbh slots); all 8-byte aligned device memory,
+ * counts below 2^31 - 64.  A workgroup stages 256 records in LDS with 16-byte loads, works on them there and streams the tile back if
+ * a loop changed it; the slots are written per particle.  With INIT, a pass before it checks the PI of every Type-0 and Type-5 particle:
+ * one outside its slot array is SHQ_ERR_INVALID with nothing written.  A Type above 5 with Mass == 0 counts in badmass and keeps its
+ * mass (the reference reads past MassTable); it enters mass_total only.  The sums are reproducible: wave and block partial sums in
+ * a fixed shape, then one fixed-order pass over the block sums.  The conditions the reference ends the run on are reported, the call
+ * returns SHQ_OK.  Synchronous (the report crosses PCIe). */
+int shq_startup_particles(shq_context *ctx, const shq_startup_layout *layout, void *d_parts, int64_t numpart, void *d_sph, int64_t nsph, void *d_bh, int64_t nbh,
+                          const shq_startup_params *params, int which, shq_startup_report *report);
+/* check_density_entropy over the slot array itself: Density <= 0 or not finite becomes meanbar (counted in *bad), EgyWtDensity <= 0 or
+ * not finite becomes Density, Entropy below GAMMA_MINUS1 MinEgySpec / pow(Density / atime^3, GAMMA_MINUS1) is raised to it. */
+int shq_startup_check_density_entropy(shq_context *ctx, const shq_startup_layout *layout, void *d_sph, int64_t nsph, double meanbar, double MinEgySpec, double atime,
+                                      int64_t *bad);
+
+/* set_init_hsml for the resident particles (shq_particles_upload with Type and flags, Hsml resident) and the current tree, which must
+ * carry the particle -> leaf array (shq_tree_build, or shq_tree_upload of a tree with father): Type 0 and 5 particles that are not
+ * garbage climb from their leaf while 10 DesNumNgb Mass > the node's mass and get len pow(3 / (4 pi) DesNumNgb Mass / mass, 1 / 3) of
+ * the node they end on when that is below 500 MeanGasSeparation, else MeanGasSeparation; a particle the tree does not hold (a swallowed
+ * black hole) keeps no = its own index and gets MeanGasSeparation.  d_node_out (device, int32 per particle, may be NULL): that node,
+ * numbered from the tree's firstnode as the caller's NODE array is (for a device-built tree: shq_tree_download with firstnode =
+ * NumPart), the particle's own index when it never entered the tree, -1 for particles the loop skips.  The reference's conditions
+ * "Bad tree moments" (len > BoxSize - which the root, 1.001 BoxSize long, meets - or node mass < Mass), "Bad hsml guess" (Hsml <= 0)
+ * and "Bad init father" (here: a father chain longer than 64) are counted; any of them is SHQ_ERR_INVALID after every Hsml has
+ * been written. */
+int shq_set_init_hsml(shq_context *ctx, double MeanGasSeparation, double DesNumNgb, int32_t *d_node_out);
+/* Entropy = GAMMA_MINUS1 u_init / pow(X / a3, GAMMA_MINUS1) for every resident gas particle, X = EgyWtDensity (from_egywt, which also
+ * keeps X for shq_setup_smoothinglengths' max-change reduction) or Density; GAMMA_MINUS1 = (5.0 / 3.0) - 1. */
+int shq_init_entropy(shq_context *ctx, double u_init, double a3, int from_egywt);
+
+typedef struct shq_startup_sml_params {
+    shq_density_params density;   /* update_hsml and DoEgyDensity are set by the call */
+    double MeanGasSeparation, u_init, atime;
+    int32_t DensityIndependentSphOn;
+    int32_t pad_;
+} shq_startup_sml_params;
+typedef struct shq_startup_sml_stats {
+    shq_sph_stats first;          /* the density pass with update_hsml */
+    int32_t nrounds;              /* entropy + density rounds of setup_density_indep_entropy (0 without DensityIndependentSph) */
+    int32_t nmaxdiff;             /* rounds that were followed by the max-change reduction: nrounds - 1 when the loop stopped, else 100 */
+    double maxdiff[100];
+    int64_t nbad_moments, nbad_hsml; /* set_init_hsml's "Bad tree moments" and "Bad hsml guess" particles: reported, the call goes on */
+} shq_startup_sml_stats;
+/* setup_smoothinglengths for RestartSnapNum == -1 on host views: one upload, then on the device the GASMASK + BHMASK tree,
+ * shq_set_init_hsml, density with update_hsml = 1 and DoEgyDensity = 0, and either the entropy from Density or
+ * setup_density_indep_entropy's loop (EgyWtDensity = Density; entropy, density with DoEgyDensity = 1, max over gas of
+ * |EgyWtDensity - old| / EgyWtDensity; one more round after the max falls below 1e-3, 100 at most); then one write-back of Hsml,
+ * DtHsml, Density, EgyWtDensity, DhsmlEgyDensityFactor, DivVel, CurlVel, Entropy and the black-hole slots for the walked targets, as
+ * shq_density_close does (Hsml also for the particles set_init_hsml wrote and no walk visits: a swallowed black hole).  No tree stays installed.  No gas and no black-hole slots: SHQ_OK, nothing done.  SHQ_ERR_NOCONV passes through.
+ * Particles that meet set_init_hsml's conditions (in a set so small or so sparse that a climb reaches the root) are counted in the
+ * stats and the call goes on with the Hsml they got, which the density loop then corrects; the reference ends the run there. */
+int shq_setup_smoothinglengths(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_bh_view *bh, const shq_startup_sml_params *params,
+                               shq_startup_sml_stats *stats);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1049,3 +1049,8 @@ from .capi import IO_SELECT_ALL, IO_SELECT_FOF, IO_ORDER_INDEX, IO_ORDER_GRNR  #
 from .lightcone import (Lightcone, LightconeStateView, lightcone_layout, lightcone_table, lightcone_horizon, lightcone_compute_raw,  # noqa: E402,F401
                         lightcone_phase_ms)
 from .capi import LIGHTCONE_CONSISTENT, LIGHTCONE_AS_WRITTEN, LIGHTCONE_MAXREPLICA  # noqa: E402,F401
+
+# ---- run start-up: init()'s loops, the first Hsml, the initial entropy (csrc/startup.hip; startup.py) ----------
+from .startup import (StartupError, StartupReport, SmlStats, startup_layout, startup_params, startup_particles, check_density_entropy,  # noqa: E402,F401
+                      set_init_hsml_device, init_entropy, setup_smoothinglengths, mean_separation, u_init, check_omega, meanbar)
+from .capi import STARTUP_OMEGA, STARTUP_POSITIONS, STARTUP_HSML, STARTUP_INIT, STARTUP_ALL  # noqa: E402,F401

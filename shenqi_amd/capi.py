@@ -1247,3 +1247,58 @@ hip.shq_lightcone_compute.argtypes = [_vp, C.POINTER(LightconeLayout), _vp, C.c_
 hip.shq_lightcone_phase_ms.argtypes = [_vp, C.POINTER(C.c_double)]
 for _f in ("shq_lightcone_horizon", "shq_lightcone_init", "shq_lightcone_set_time", "shq_lightcone_compute", "shq_lightcone_phase_ms"):
     getattr(hip, _f).restype = C.c_int
+
+# ---- run start-up (csrc/startup.hip) -------------------------------------------------------------
+STARTUP_OMEGA, STARTUP_POSITIONS, STARTUP_HSML, STARTUP_INIT = 1, 2, 4, 8
+STARTUP_ALL = 15
+
+
+class StartupLayout(C.Structure):
+    """shq_startup_layout"""
+    _fields_ = [(k, C.c_size_t) for k in (
+        "part_elsize", "off_pos", "off_mass", "off_flags", "off_type", "off_pi", "off_hsml", "off_ti_drift",
+        "sph_elsize", "sph_off_density", "sph_off_egywtdensity", "sph_off_entropy", "sph_off_dtentropy", "sph_off_maxsignalvel", "sph_off_hydroaccel",
+        "sph_off_dhsmlegydensityfactor", "sph_off_divvel", "sph_off_curlvel", "sph_off_sfr", "sph_off_ne", "sph_off_delaytime", "sph_off_metallicity",
+        "sph_off_metals", "sph_nmetals", "sph_off_local_j21", "sph_off_zreion",
+        "bh_elsize", "bh_off_mass", "bh_off_dfaccel", "bh_off_dragaccel")]
+
+
+class StartupParams(C.Structure):
+    """shq_startup_params"""
+    _fields_ = [("BoxSize", C.c_double), ("MassTable", C.c_double * 6), ("MeanSeparation", C.c_double * 6), ("Ti_Current", C.c_int64),
+                ("generations", C.c_int32), ("RestartSnapNum", C.c_int32), ("init_reion", C.c_int32), ("pad_", C.c_int32)]
+
+
+class StartupReport(C.Structure):
+    """shq_startup_report"""
+    _fields_ = [("mass_type", C.c_double * 6), ("mass_total", C.c_double), ("badmass", C.c_int64), ("noutside", C.c_int64), ("first_outside", C.c_int64),
+                ("numzero", C.c_int64), ("lastzero", C.c_int64), ("numprob", C.c_int64), ("lastprob", C.c_int64), ("nbad_delaytime", C.c_int64),
+                ("first_bad_delaytime", C.c_int64)]
+
+
+class StartupSmlParams(C.Structure):
+    """shq_startup_sml_params"""
+    _fields_ = [("density", DensityParams), ("MeanGasSeparation", C.c_double), ("u_init", C.c_double), ("atime", C.c_double),
+                ("DensityIndependentSphOn", C.c_int32), ("pad_", C.c_int32)]
+
+
+class StartupSmlStats(C.Structure):
+    """shq_startup_sml_stats"""
+    _fields_ = [("first", SphStats), ("nrounds", C.c_int32), ("nmaxdiff", C.c_int32), ("maxdiff", C.c_double * 100), ("nbad_moments", C.c_int64),
+                ("nbad_hsml", C.c_int64)]
+
+
+_dp = C.POINTER(C.c_double)
+hip.shq_startup_mean_separation.argtypes = [_dp, C.c_double, C.POINTER(C.c_int64)]
+hip.shq_startup_u_init.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, _dp]
+hip.shq_startup_omega.argtypes = [_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, C.c_double, _dp, _dp, C.POINTER(C.c_int)]
+hip.shq_startup_meanbar.argtypes = [C.c_double, C.c_double, _dp]
+hip.shq_startup_particles.argtypes = [_vp, C.POINTER(StartupLayout), _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, C.POINTER(StartupParams), C.c_int,
+                                      C.POINTER(StartupReport)]
+hip.shq_startup_check_density_entropy.argtypes = [_vp, C.POINTER(StartupLayout), _vp, C.c_int64, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_int64)]
+hip.shq_set_init_hsml.argtypes = [_vp, C.c_double, C.c_double, _vp]
+hip.shq_init_entropy.argtypes = [_vp, C.c_double, C.c_double, C.c_int]
+hip.shq_setup_smoothinglengths.argtypes = [_vp, C.POINTER(PartView), C.POINTER(SphView), C.POINTER(BhView), C.POINTER(StartupSmlParams), C.POINTER(StartupSmlStats)]
+for _f in ("shq_startup_mean_separation", "shq_startup_u_init", "shq_startup_omega", "shq_startup_meanbar", "shq_startup_particles",
+           "shq_startup_check_density_entropy", "shq_set_init_hsml", "shq_init_entropy", "shq_setup_smoothinglengths"):
+    getattr(hip, _f).restype = C.c_int

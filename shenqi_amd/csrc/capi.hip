@@ -246,7 +246,8 @@ extern "C" void shq_shutdown(shq_context *ctx)
     ctx->cool_ion.release(); ctx->cool_rates.release(); ctx->cool_metal.release(); ctx->cool_zreion.release(); ctx->cool_d.release(); ctx->cool_i.release();
     ctx->cool_b.release(); ctx->cool_cnt.release();
     ctx->gravtab.release(); ctx->stage.release();
-    ctx->node_hmax.release(); ctx->pfather.release();
+    ctx->node_hmax.release(); ctx->pfather.release(); ctx->node_father.release();
+    ctx->st_cnt.release(); ctx->st_part.release(); ctx->st_old.release(); ctx->st_i32.release();
     ctx->hsml.release(); ctx->dthsml.release(); ctx->vel.release(); ctx->bin_grav.release(); ctx->bin_hydro.release();
     ctx->g_entropy.release(); ctx->g_dtentropy.release(); ctx->g_hydroaccel.release(); ctx->g_delaytime.release();
     ctx->g_density.release(); ctx->g_egywt.release(); ctx->g_dhsmlegy.release(); ctx->g_divvel.release(); ctx->g_curlvel.release();
@@ -703,13 +704,14 @@ extern "C" int shq_tree_upload(shq_context *ctx, const shq_tree_view *tree)
     SHQ_TRY(ctx->nodeC.reserve(nn + 1));
     SHQ_TRY(ctx->nodeG.reserve(nn + 1));
     SHQ_TRY(ctx->node_hmax.reserve(nn + 1));
+    SHQ_TRY(ctx->node_father.reserve(nn + 1));
     SHQ_TRY(ctx->leaf_pidx.reserve((size_t) npad));
     SHQ_TRY(ctx->posm_leaf.reserve((size_t) npad));
     /* Pack the merged 128-byte walk records (plus hmax and the leaves' particle indices) straight into pinned staging,
      * a chunk of nodes at a time, each chunk copied while the next is packed; the split A / B / C streams of the SPH
      * walks are cut from the merged records on the device. */
     const int64_t CH = 1 << 20;
-    const size_t chunk_bytes = (size_t) CH * (sizeof(NodeG) + sizeof(double) + SHQ_NMAXCHILD * sizeof(int32_t));
+    const size_t chunk_bytes = (size_t) CH * (sizeof(NodeG) + sizeof(double) + (SHQ_NMAXCHILD + 1) * sizeof(int32_t));
     SHQ_TRY(ctx->stage.reserve(2 * chunk_bytes + 256));
     std::atomic<int> bad(0);
     hipEvent_t ev[2] = {ctx->ev_begin[SHQ_NTIMERS - 2], ctx->ev_end[SHQ_NTIMERS - 2]};
@@ -721,6 +723,7 @@ extern "C" int shq_tree_upload(shq_context *ctx, const shq_tree_view *tree)
         NodeG *hG = reinterpret_cast<NodeG *>(base);
         double *hH = reinterpret_cast<double *>(base + (size_t) CH * sizeof(NodeG));
         int32_t *hP = reinterpret_cast<int32_t *>(hH + CH);
+        int32_t *hF = hP + (size_t) CH * SHQ_NMAXCHILD; /* the fathers, for set_init_hsml's climb */
         const int64_t p0 = pstart[c0], p1 = pstart[std::min<int64_t>(c0 + m, nn)];
         if(nchunk >= 2)
             SHQ_HIP(hipEventSynchronize(ev[sl]));
@@ -734,9 +737,11 @@ extern "C" int shq_tree_upload(shq_context *ctx, const shq_tree_view *tree)
                     g.wraplim = 0.5 * tree->BoxSize;
                     hG[k] = g;
                     hH[k] = 0;
+                    hF[k] = -1;
                     continue;
                 }
                 const shq_node &sn = src[order[j]];
+                hF[k] = (sn.father >= fn && sn.father < fn + nall) ? newidx[sn.father - fn] : -1;
                 for(int d = 0; d < 3; d++) {
                     g.cofm[d] = sn.cofm[d];
                     g.center[d] = sn.center[d];
@@ -777,6 +782,7 @@ extern "C" int shq_tree_upload(shq_context *ctx, const shq_tree_view *tree)
         });
         SHQ_HIP(hipMemcpyAsync(ctx->nodeG.ptr + c0, hG, sizeof(NodeG) * m, hipMemcpyHostToDevice, ctx->stream));
         SHQ_HIP(hipMemcpyAsync(ctx->node_hmax.ptr + c0, hH, sizeof(double) * m, hipMemcpyHostToDevice, ctx->stream));
+        SHQ_HIP(hipMemcpyAsync(ctx->node_father.ptr + c0, hF, sizeof(int32_t) * m, hipMemcpyHostToDevice, ctx->stream));
         if(p1 > p0)
             SHQ_HIP(hipMemcpyAsync(ctx->leaf_pidx.ptr + p0, hP, sizeof(int32_t) * (p1 - p0), hipMemcpyHostToDevice, ctx->stream));
         SHQ_HIP(hipEventRecord(ev[sl], ctx->stream));

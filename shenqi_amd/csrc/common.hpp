@@ -327,6 +327,7 @@ struct shq_context {
     double treeBox = 0;
     DevBuf<double> node_hmax;  /* mom.hmax per packed node (SPH symmetric cull) */
     DevBuf<int32_t> pfather;   /* particle -> packed index of the leaf holding it, or -1 */
+    DevBuf<int32_t> node_father; /* packed node -> packed index of its father, -1 for the root (set_init_hsml's climb, startup.hip) */
     std::vector<int32_t> node_order; /* packed index -> index into the caller's nodes_base */
     std::vector<int32_t> node_rank;  /* caller's node index -> packed index (-1: unreachable); empty = identity */
     bool have_father = false;
@@ -393,6 +394,11 @@ struct shq_context {
     DevBuf<unsigned long long> io_u64[2]; /* GrNr keys, in and out of the sort */
     DevBuf<int32_t> io_i32;              /* indices between the two sorts; the readout's list of a type */
     DevBuf<unsigned long long> io_cnt;   /* [0..7] counts by key, [8] the error word, [9] a selected count */
+    /* run start-up (startup.hip): integer counters and indices of the record loops, block partial sums, the EgyWtDensity of the round
+     * before, the node numbers of an uploaded tree */
+    DevBuf<long long> st_cnt;
+    DevBuf<double> st_part, st_old;
+    DevBuf<int32_t> st_i32;
     /* light-cone crossings (lightcone.hip) */
     DevBuf<double> lc_reps;              /* the state's replica shifts, [Nreplica][3] */
     DevBuf<int32_t> lc_cnt;              /* crossings per particle, one zero behind the last; then the first two replicas of each */

@@ -426,7 +426,7 @@ __global__ void tb_rank_kernel(int nn, const int32_t *__restrict__ order, int32_
 /* pool records in pre-order (common.hpp); record nn is the pad the walks may touch */
 __global__ void tb_pack_kernel(int nn, const int32_t *__restrict__ order, const int32_t *__restrict__ rank, TbNodes nd,
                                const int32_t *__restrict__ idx, NodeA *A, NodeB *B, NodeC *C, NodeG *G, double *H, int32_t *pfather,
-                               double Box, TbGeo geo)
+                               int32_t *nfather, double Box, TbGeo geo)
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if(r > nn)
@@ -435,6 +435,7 @@ __global__ void tb_pack_kernel(int nn, const int32_t *__restrict__ order, const 
     NodeB b;
     NodeC c;
     double hmax = 0;
+    int32_t fa = -1;
     if(r == nn) {
         memset(&a, 0, sizeof(a));
         memset(&b, 0, sizeof(b));
@@ -467,11 +468,14 @@ __global__ void tb_pack_kernel(int nn, const int32_t *__restrict__ order, const 
             c.count = 0;
         }
         hmax = nd.hmax[no];
+        const int par = nd.parent[no];
+        fa = par >= 0 ? rank[par] : -1;
     }
     A[r] = a;
     B[r] = b;
     C[r] = c;
     H[r] = hmax;
+    nfather[r] = fa;
     NodeG g;
     memset(&g, 0, sizeof(g));
     for(int k = 0; k < 3; k++) {
@@ -892,9 +896,11 @@ static int tree_build_impl(shq_context *ctx, double BoxSize, int mask, const int
     SHQ_TRY(ctx->nodeG.reserve((size_t) nn + 1));
     SHQ_TRY(ctx->node_hmax.reserve((size_t) nn + 1));
     SHQ_TRY(ctx->pfather.reserve((size_t) (np > 0 ? np : 1)));
+    SHQ_TRY(ctx->node_father.reserve((size_t) nn + 1));
     SHQ_HIP(hipMemsetAsync(ctx->pfather.ptr, 0xff, sizeof(int32_t) * (size_t) (np > 0 ? np : 1), st));
     tb_pack_kernel<<<dim3(nblk(nn + 1)), dim3(256), 0, st>>>(nn, b.order[1].ptr, b.rank.ptr, nd, idx, ctx->nodeA.ptr, ctx->nodeB.ptr,
-                                                              ctx->nodeC.ptr, ctx->nodeG.ptr, ctx->node_hmax.ptr, ctx->pfather.ptr, BoxSize, geo);
+                                                              ctx->nodeC.ptr, ctx->nodeG.ptr, ctx->node_hmax.ptr, ctx->pfather.ptr,
+                                                              ctx->node_father.ptr, BoxSize, geo);
     const long long npad = n + SHQ_NMAXCHILD;
     SHQ_TRY(ctx->posm_leaf.reserve((size_t) npad));
     SHQ_TRY(ctx->leaf_pidx.reserve((size_t) npad));
