@@ -235,7 +235,7 @@ extern "C" void shq_shutdown(shq_context *ctx)
     ctx->posm.release(); ctx->oldacc.release(); ctx->treeacc.release(); ctx->gravpm.release();
     ctx->pmpot.release(); ctx->acc.release(); ctx->pot.release(); ctx->nint.release(); ctx->walk_tasks.release();
     ctx->sp_items.release(); ctx->sp_stack.release(); ctx->sp_count.release(); ctx->sp_flags.release(); ctx->sp_host.release(); ctx->node_lean_bad.release();
-    ctx->pflags.release(); ctx->active.release(); ctx->act_list.release(); ctx->act_sub.release(); ctx->act_counts.release(); ctx->act_temp.release(); ctx->act_flag.release();
+    ctx->pflags.release(); ctx->active.release(); ctx->act_list.release(); ctx->act_sub.release(); ctx->act_counts.release(); ctx->prim_temp.release(); ctx->act_flag.release();
     ctx->gq_res.release(); ctx->s_queue0.release(); ctx->s_nlist2.release(); ctx->topnodes.release(); ctx->topleaves.release(); ctx->top_counts.release(); ctx->top_table.release(); ctx->gstats.release(); ctx->nodeF.release(); ctx->walk_counters.release(); ctx->walk_pool_idx.release(); ctx->walk_pool_msk.release(); ctx->walk_chunk_cnt.release(); ctx->walk_chunk_next.release(); ctx->walk_group_head.release();
     ctx->nodeA.release(); ctx->nodeB.release(); ctx->nodeC.release(); ctx->nodeG.release();
     ctx->posm_leaf.release(); ctx->leaf_pidx.release();
@@ -270,7 +270,6 @@ extern "C" void shq_shutdown(shq_context *ctx)
     for(auto &b : ctx->fof_u64) b.release();
     for(auto &b : ctx->fof_gkey) b.release();
     for(auto &b : ctx->fof_goff) b.release();
-    ctx->hilb_iota.release();
     ctx->bhw_bhp.release(); ctx->bhw_queue.release(); ctx->bhw_rec.release(); ctx->bhw_ids.release(); ctx->bhw_sphsw.release(); ctx->bhw_bhsw.release();
     ctx->bhw_swid.release(); ctx->bhw_rnd.release(); ctx->bhw_out.release(); ctx->bhw_eeqos.release(); ctx->bhw_heated.release();
     ctx->wind_kicks.release(); ctx->wind_d.release(); ctx->wind_cnt.release();

@@ -189,7 +189,6 @@ struct TreeBuildBufs {
     DevBuf<double> topbuf;               /* gather / scatter of the top-level nodes' records */
     DevBuf<double4> cen, mom;
     DevBuf<double> hmax;
-    DevBuf<char> temp;
     DevBuf<shq_node> exportbuf;
     void release()
     {
@@ -197,7 +196,7 @@ struct TreeBuildBufs {
             keys[i].release(); okeys[i].release(); packed[i].release(); idx[i].release(); order[i].release(); frontier[i].release();
         }
         counters.release(); rank.release(); bounds.release(); lo.release(); hi.release(); parent.release(); sibling.release();
-        firstchild.release(); nchild.release(); level.release(); cen.release(); mom.release(); hmax.release(); temp.release();
+        firstchild.release(); nchild.release(); level.release(); cen.release(); mom.release(); hmax.release();
         exportbuf.release(); top.release(); path.release(); geo_child[0].release(); geo_child[1].release(); geo_kind.release(); topbuf.release(); state.release();
     }
 };
@@ -292,11 +291,14 @@ struct shq_context {
     DevBuf<shq_grav_result> gq_res;
     DevBuf<int32_t> act_list, act_sub;   /* resident ActiveParticle list and gravity sub-list (shq_build_active_*) */
     DevBuf<unsigned long long> act_counts;
-    DevBuf<char> act_temp;
     DevBuf<uint8_t> act_flag;
     int64_t n_act = -1, n_sub = -1;      /* -1: not built */
     bool act_all = false;                /* PM step: the list is NULL, every particle is active */
     DevBuf<GravStatsDev> gstats;
+    /* scratch of the sort / select / scan helpers (device_prims.hpp), theirs alone.  Contents undefined between calls: it never holds data
+     * a caller reads after its next helper call.  Sized SHQ_PRIM_PAD bytes beyond every request, so that a zero-size request still yields
+     * a non-null scratch pointer: rocPRIM takes a null one for a size query and does nothing */
+    DevBuf<char> prim_temp;
     bool have_parts = false;
     int stats_guard = 0;       /* SHQ_WALK_STATS_GUARD (A/B knob): 1 reads before atomicMin / atomicMax (slower), 2 drops the wave tallies */
     bool allow_padding = false; /* SHQ_WALK_PADDING=1: -1 entries of a gravity target list are idle lanes (tools/walk_cell_probe.py) */
@@ -340,7 +342,6 @@ struct shq_context {
     int tree_targets_refresh = 8;  /* SHQ_TREE_TARGETS_REFRESH: rebuilds over the same particle set that keep the list (1: a new list per build) */
     int tree_targets_age = 0, tree_targets_mask = -2;
     long long tree_targets_np = -1, tree_targets_ntree = -1;
-    DevBuf<long long> hilb_iota;  /* shq_hilbert_order: 0 .. n-1, the values of its sort */
     /* black-hole accretion / feedback walks: per-call uploads (sph_capi.hip) */
     DevBuf<int32_t> bhw_bhp, bhw_queue;
     DevBuf<char> bhw_rec;

@@ -19,14 +19,10 @@
  * shares the first d - 1 digits arrived (one binary search).  Count of any node = samples in its key range (two binary searches):
  * that is the leaf count and the sum up the tree at once.  Count == Cost and both fall monotonically down the tree, so the top-down
  * truncation keeps a node exactly when its parent's Count reaches min(countlimit, costlimit). */
-#include "common.hpp"
+#include "device_prims.hpp"
 #include "domain_host.hpp"
 #include <string.h>
 #include <vector>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 namespace {
 
@@ -343,15 +339,6 @@ int check_parts(const shq_domain_parts *p)
     return SHQ_OK;
 }
 
-int sort_keys(shq_context *ctx, const unsigned long long *in, unsigned long long *out, size_t n)
-{
-    size_t tmp = 0;
-    SHQ_HIP(rocprim::radix_sort_keys(nullptr, tmp, in, out, n, 0, 64, ctx->stream));
-    SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::radix_sort_keys((void *) ctx->act_temp.ptr, tmp, in, out, n, 0, 64, ctx->stream));
-    return SHQ_OK;
-}
-
 } // namespace
 
 extern "C" int shq_peano_tables_from_key(shq_peano_keyfn keyfn, shq_peano_tables *out)
@@ -415,7 +402,7 @@ extern "C" int shq_domain_samples(shq_context *ctx, const shq_peano_tables *tabl
                                                                    parts->BoxSize, ctx->dd_tab.ptr, ctx->dd_u64[0].ptr, ctx->dd_u64[2].ptr);
     SHQ_HIP(hipGetLastError());
     /* garbage (PEANOCELLS) sorts behind every key */
-    SHQ_TRY(sort_keys(ctx, ctx->dd_u64[0].ptr, ctx->dd_u64[1].ptr, (size_t) nkeys));
+    SHQ_TRY(prim_sort_keys(ctx, ctx->dd_u64[0].ptr, ctx->dd_u64[1].ptr, (size_t) nkeys, 0, 64));
     unsigned long long live = 0;
     SHQ_HIP(hipMemcpyAsync(&live, ctx->dd_u64[2].ptr, sizeof(live), hipMemcpyDeviceToHost, st));
     SHQ_HIP(hipStreamSynchronize(st));
@@ -457,12 +444,7 @@ extern "C" int shq_domain_local_toptree(shq_context *ctx, const uint64_t *d_sort
     long long *c = ctx->dd_i64[0].ptr, *S = ctx->dd_i64[1].ptr;
     dd_nsplit_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, k, c);
     SHQ_HIP(hipGetLastError());
-    {
-        size_t tmp = 0;
-        SHQ_HIP(rocprim::exclusive_scan(nullptr, tmp, c, S, 0ll, (size_t) n, rocprim::plus<long long>(), st));
-        SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-        SHQ_HIP(rocprim::exclusive_scan((void *) ctx->act_temp.ptr, tmp, c, S, 0ll, (size_t) n, rocprim::plus<long long>(), st));
-    }
+    SHQ_TRY(prim_exclusive_scan(ctx, c, S, 0ll, (size_t) n));
     long long tail[2] = {0, 0};
     SHQ_HIP(hipMemcpyAsync(&tail[0], S + (n - 1), sizeof(long long), hipMemcpyDeviceToHost, st));
     SHQ_HIP(hipMemcpyAsync(&tail[1], c + (n - 1), sizeof(long long), hipMemcpyDeviceToHost, st));
@@ -478,7 +460,6 @@ extern "C" int shq_domain_local_toptree(shq_context *ctx, const uint64_t *d_sort
     SHQ_TRY(ctx->dd_i32[2].reserve((size_t) nnodes + 2));
     SHQ_TRY(ctx->dd_u8.reserve((size_t) nnodes));
     SHQ_TRY(ctx->dd_rec.reserve(sizeof(shq_local_topnode) * (size_t) nnodes + sizeof(int32_t) * (size_t) nnodes));
-    SHQ_TRY(ctx->dd_u64[2].reserve(2));
     DdSkel sk{ctx->dd_u64[0].ptr, ctx->dd_i32[0].ptr, ctx->dd_i32[1].ptr, ctx->dd_i32[2].ptr};
     SHQ_HIP(hipMemsetAsync(sk.Daughter, 0xff, sizeof(int32_t) * (size_t) nnodes, st));
     dd_split_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, k, S, sk, nnodes);
@@ -492,19 +473,11 @@ extern "C" int shq_domain_local_toptree(shq_context *ctx, const uint64_t *d_sort
     dd_flag_kernel<<<dim3(nblk(nnodes)), dim3(256), 0, st>>>(nnodes, sk, count, lim, ctx->dd_u8.ptr);
     SHQ_HIP(hipGetLastError());
     int32_t *list = reinterpret_cast<int32_t *>(ctx->dd_rec.ptr + sizeof(shq_local_topnode) * (size_t) nnodes);
-    size_t *d_n = reinterpret_cast<size_t *>(ctx->dd_u64[2].ptr);
-    {
-        size_t tmp = 0;
-        SHQ_HIP(rocprim::select(nullptr, tmp, rocprim::counting_iterator<int32_t>(0), ctx->dd_u8.ptr, list, d_n, (size_t) nnodes, st));
-        SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-        SHQ_HIP(rocprim::select((void *) ctx->act_temp.ptr, tmp, rocprim::counting_iterator<int32_t>(0), ctx->dd_u8.ptr, list, d_n, (size_t) nnodes, st));
-    }
-    size_t nkeep = 0;
-    SHQ_HIP(hipMemcpyAsync(&nkeep, d_n, sizeof(nkeep), hipMemcpyDeviceToHost, st));
-    SHQ_HIP(hipStreamSynchronize(st));
-    SHQ_CHECK(nkeep >= 1 && (long long) nkeep <= nnodes && (nkeep - 1) % 8 == 0, SHQ_ERR_DEVICE, "domain_local_toptree: %zu survivors of %lld nodes", nkeep, nnodes);
+    int64_t nkeep = 0;
+    SHQ_TRY(prim_select_flagged(ctx, rocprim::counting_iterator<int32_t>(0), ctx->dd_u8.ptr, list, (size_t) nnodes, nullptr, &nkeep));
+    SHQ_CHECK(nkeep >= 1 && nkeep <= nnodes && (nkeep - 1) % 8 == 0, SHQ_ERR_DEVICE, "domain_local_toptree: %lld survivors of %lld nodes", (long long) nkeep, nnodes);
     shq_local_topnode *d_out = reinterpret_cast<shq_local_topnode *>(ctx->dd_rec.ptr);
-    dd_gather_kernel<<<dim3(nblk((long long) nkeep)), dim3(256), 0, st>>>((long long) nkeep, list, sk, count, lim, d_out);
+    dd_gather_kernel<<<dim3(nblk(nkeep)), dim3(256), 0, st>>>(nkeep, list, sk, count, lim, d_out);
     SHQ_HIP(hipGetLastError());
     std::vector<shq_local_topnode> nodes(nkeep);
     std::vector<int32_t> old(nkeep);

@@ -9,15 +9,13 @@
  * host integration.  Black-hole repositioning (drift.cpp:32-53) runs when the BH slot fields are resident
  * (shq_bh_dynamics_upload, timestep.hip) and shq_set_bh_reposition is on.  The per-particle loops of the integer time line
  * are in timestep.hip; Ti_drift / Ti_kick stay with the host. */
-#include "common.hpp"
+#include "device_prims.hpp"
 #include <string.h>
 #include <cstring>
 #include <vector>
 #include <atomic>
 #include <thread>
 #include <algorithm>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 namespace {
 
@@ -229,34 +227,6 @@ struct SubActive {
     }
 };
 
-template <typename In> int select_flagged(shq_context *ctx, In in, const uint8_t *flags, int32_t *out, size_t n, int64_t *count)
-{
-    size_t tmp = 0;
-    size_t *d_count = reinterpret_cast<size_t *>(ctx->act_counts.ptr + ACT_NB + 2);
-    SHQ_HIP(rocprim::select(nullptr, tmp, in, flags, out, d_count, n, ctx->stream));
-    SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::select((void *) ctx->act_temp.ptr, tmp, in, flags, out, d_count, n, ctx->stream));
-    size_t h = 0;
-    SHQ_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    SHQ_HIP(hipStreamSynchronize(ctx->stream));
-    *count = (int64_t) h;
-    return SHQ_OK;
-}
-
-template <typename In> int select_if(shq_context *ctx, In in, SubActive pred, int32_t *out, size_t n, int64_t *count)
-{
-    size_t tmp = 0;
-    size_t *d_count = reinterpret_cast<size_t *>(ctx->act_counts.ptr + ACT_NB + 2);
-    SHQ_HIP(rocprim::select(nullptr, tmp, in, out, d_count, n, pred, ctx->stream));
-    SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::select((void *) ctx->act_temp.ptr, tmp, in, out, d_count, n, pred, ctx->stream));
-    size_t h = 0;
-    SHQ_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    SHQ_HIP(hipStreamSynchronize(ctx->stream));
-    *count = (int64_t) h;
-    return SHQ_OK;
-}
-
 } // namespace
 
 extern "C" int shq_dynamics_upload(shq_context *ctx, const shq_part_view *parts)
@@ -409,7 +379,8 @@ extern "C" int shq_build_active_particles(shq_context *ctx, int64_t Ti_Current, 
     if(!is_pm_step) {
         nact = 0;
         if(n > 0)
-            SHQ_TRY(select_flagged(ctx, rocprim::counting_iterator<int32_t>(0), (const uint8_t *) ctx->act_flag.ptr, ctx->act_list.ptr, (size_t) n, &nact));
+            SHQ_TRY(prim_select_flagged(ctx, rocprim::counting_iterator<int32_t>(0), (const uint8_t *) ctx->act_flag.ptr, ctx->act_list.ptr, (size_t) n,
+                                        ctx->act_counts.ptr + ACT_NB + 2, &nact));
     }
     unsigned long long h[ACT_NB + 2];
     SHQ_HIP(hipMemcpyAsync(h, ctx->act_counts.ptr, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
@@ -438,9 +409,9 @@ extern "C" int shq_build_active_sublist(shq_context *ctx, int maxtimebin, int64_
     ctx->n_sub = -1;
     if(n > 0) {
         if(ctx->act_all)
-            SHQ_TRY(select_if(ctx, rocprim::counting_iterator<int32_t>(0), pred, ctx->act_sub.ptr, (size_t) n, &cnt));
+            SHQ_TRY(prim_select_if(ctx, rocprim::counting_iterator<int32_t>(0), ctx->act_sub.ptr, (size_t) n, pred, ctx->act_counts.ptr + ACT_NB + 2, &cnt));
         else
-            SHQ_TRY(select_if(ctx, (const int32_t *) ctx->act_list.ptr, pred, ctx->act_sub.ptr, (size_t) n, &cnt));
+            SHQ_TRY(prim_select_if(ctx, (const int32_t *) ctx->act_list.ptr, ctx->act_sub.ptr, (size_t) n, pred, ctx->act_counts.ptr + ACT_NB + 2, &cnt));
     }
     ctx->n_sub = cnt;
     if(nsub)

@@ -9,12 +9,9 @@
  * every target task, for the base records and for each slot type.  Here the list comes from a stable select, the per-task and
  * per-(task, type) positions from two stable radix sorts of the list (so the orders are the serial loop's), and records move as
  * 16-byte words, a few lanes per record.  The buffers come out byte-identical to the serial loop's. */
-#include "common.hpp"
+#include "device_prims.hpp"
 #include <string.h>
 #include <vector>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 namespace {
 
@@ -235,12 +232,6 @@ __global__ void gcs_gather_u32_kernel(long long n, const int32_t *order, const u
     if(i < n)
         out[i] = in[order[i]];
 }
-__global__ void gcs_iota_kernel(long long n, int32_t *v)
-{
-    const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if(i < n)
-        v[i] = (int32_t) i;
-}
 __global__ void gcs_rlkey_kernel(long long n, const char *slots, size_t elsize, size_t off_rl, unsigned int *key, int32_t *val)
 {
     const long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x;
@@ -248,20 +239,6 @@ __global__ void gcs_rlkey_kernel(long long n, const char *slots, size_t elsize, 
         return;
     key[i] = (unsigned) *reinterpret_cast<const int32_t *>(slots + (size_t) i * elsize + off_rl);
     val[i] = (int32_t) i;
-}
-
-template <typename Pred> int select_keep(shq_context *ctx, Pred pred, size_t n, int32_t *out, int64_t *nkeep)
-{
-    size_t tmp = 0;
-    size_t *d_n = reinterpret_cast<size_t *>(ctx->ex_counts.ptr);
-    SHQ_HIP(rocprim::select(nullptr, tmp, rocprim::counting_iterator<int32_t>(0), out, d_n, n, pred, ctx->stream));
-    SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::select((void *) ctx->act_temp.ptr, tmp, rocprim::counting_iterator<int32_t>(0), out, d_n, n, pred, ctx->stream));
-    size_t h = 0;
-    SHQ_HIP(hipMemcpyAsync(&h, d_n, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    SHQ_HIP(hipStreamSynchronize(ctx->stream));
-    *nkeep = (int64_t) h;
-    return SHQ_OK;
 }
 
 int check_layout(const shq_exchange_layout *l)
@@ -272,15 +249,6 @@ int check_layout(const shq_exchange_layout *l)
     for(int t = 0; t < 6; t++)
         SHQ_CHECK(l->slot_elsize[t] % 4 == 0 && (l->slot_elsize[t] == 0 || l->off_reverselink + 4 <= l->slot_elsize[t]), SHQ_ERR_INVALID,
                   "exchange: slot type %d: record size %zu must be a multiple of 4 and hold ReverseLink", t, l->slot_elsize[t]);
-    return SHQ_OK;
-}
-
-template <typename K> int sort_pairs(shq_context *ctx, const K *kin, K *kout, const int32_t *vin, int32_t *vout, size_t n, int bits)
-{
-    size_t tmp = 0;
-    SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, vin, vout, n, 0, bits, ctx->stream));
-    SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::radix_sort_pairs((void *) ctx->act_temp.ptr, tmp, kin, kout, vin, vout, n, 0, bits, ctx->stream));
     return SHQ_OK;
 }
 
@@ -311,15 +279,7 @@ extern "C" int shq_exchange_plan(shq_context *ctx, const shq_exchange_layout *la
     int64_t nex = 0;
     if(numpart > 0) {
         const Leaving pred{(const char *) d_parts, layout->part_elsize, layout->off_flags, d_target, ThisTask};
-        size_t tmp = 0;
-        size_t *d_n = reinterpret_cast<size_t *>(ctx->ex_counts.ptr + (size_t) NTask * 7);
-        SHQ_HIP(rocprim::select(nullptr, tmp, rocprim::counting_iterator<int32_t>(0), ctx->ex_list.ptr, d_n, (size_t) numpart, pred, st));
-        SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-        SHQ_HIP(rocprim::select((void *) ctx->act_temp.ptr, tmp, rocprim::counting_iterator<int32_t>(0), ctx->ex_list.ptr, d_n, (size_t) numpart, pred, st));
-        size_t h = 0;
-        SHQ_HIP(hipMemcpyAsync(&h, d_n, sizeof(h), hipMemcpyDeviceToHost, st));
-        SHQ_HIP(hipStreamSynchronize(st));
-        nex = (int64_t) h;
+        SHQ_TRY(prim_select_if(ctx, rocprim::counting_iterator<int32_t>(0), ctx->ex_list.ptr, (size_t) numpart, pred, ctx->ex_counts.ptr + (size_t) NTask * 7, &nex));
     }
     const int64_t last = (maxlast > 0 && maxlast < nex) ? maxlast : nex;
     if(nexchange)
@@ -340,10 +300,9 @@ extern "C" int shq_exchange_plan(shq_context *ctx, const shq_exchange_layout *la
                                                                ctx->ex_key[0].ptr, ctx->ex_key[1].ptr, ctx->ex_val[0].ptr, ctx->ex_counts.ptr, d_err);
         SHQ_HIP(hipGetLastError());
         /* order by task (base records) and by (task, type) (slot records); stable: list order inside every run */
-        SHQ_TRY(sort_pairs(ctx, (const unsigned int *) ctx->ex_key[0].ptr, ctx->ex_key[2].ptr, (const int32_t *) ctx->ex_val[0].ptr, ctx->ex_val[1].ptr, (size_t) last,
-                           bits_for((unsigned long long) NTask)));
-        SHQ_TRY(sort_pairs(ctx, (const unsigned int *) ctx->ex_key[1].ptr, ctx->ex_key[3].ptr, (const int32_t *) ctx->ex_val[0].ptr, ctx->ex_val[2].ptr, (size_t) last,
-                           bits_for((unsigned long long) NTask * 6)));
+        SHQ_TRY(prim_sort_pairs(ctx, ctx->ex_key[0].ptr, ctx->ex_key[2].ptr, ctx->ex_val[0].ptr, ctx->ex_val[1].ptr, (size_t) last, 0, bits_for((unsigned long long) NTask)));
+        SHQ_TRY(prim_sort_pairs(ctx, ctx->ex_key[1].ptr, ctx->ex_key[3].ptr, ctx->ex_val[0].ptr, ctx->ex_val[2].ptr, (size_t) last, 0,
+                                bits_for((unsigned long long) NTask * 6)));
         ex_count_kernel<<<dim3(nblk((long long) NTask * 6)), dim3(256), 0, st>>>(NTask * 6, last, ctx->ex_key[3].ptr, ctx->ex_counts.ptr);
         SHQ_HIP(hipGetLastError());
         std::vector<unsigned long long> h((size_t) NTask * 7 + 8);
@@ -451,7 +410,7 @@ extern "C" int shq_exchange_unpack(shq_context *ctx, const shq_exchange_layout *
         SHQ_CHECK(acc == n, SHQ_ERR_INVALID, "exchange_unpack: toGet[%d].slots do not add up to base (N_slots mismatched, exchange.hpp:505-509)", src);
         SHQ_HIP(hipMemcpyAsync(ctx->ex_i64.ptr, h, sizeof(h), hipMemcpyHostToDevice, st));
         ex_types_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, (const char *) d_parts, layout->part_elsize, layout->off_type, first, ctx->ex_key[0].ptr, ctx->ex_val[0].ptr);
-        SHQ_TRY(sort_pairs(ctx, (const unsigned int *) ctx->ex_key[0].ptr, ctx->ex_key[2].ptr, (const int32_t *) ctx->ex_val[0].ptr, ctx->ex_val[1].ptr, (size_t) n, 8));
+        SHQ_TRY(prim_sort_pairs(ctx, ctx->ex_key[0].ptr, ctx->ex_key[2].ptr, ctx->ex_val[0].ptr, ctx->ex_val[1].ptr, (size_t) n, 0, 8));
         ex_pi_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, (char *) d_parts, layout->part_elsize, layout->off_pi, first, ctx->ex_key[2].ptr, ctx->ex_val[1].ptr,
                                                           ctx->ex_i64.ptr, ctx->ex_i64.ptr + 6);
         SHQ_HIP(hipGetLastError());
@@ -475,7 +434,8 @@ extern "C" int shq_slots_gc(shq_context *ctx, const shq_exchange_layout *layout,
     if(n > 0) {
         SHQ_TRY(ctx->ex_list.reserve((size_t) n));
         int64_t nkeep = 0;
-        SHQ_TRY(select_keep(ctx, LiveParticle{(const char *) d_parts, esz, layout->off_flags}, (size_t) n, ctx->ex_list.ptr, &nkeep));
+        SHQ_TRY(prim_select_if(ctx, rocprim::counting_iterator<int32_t>(0), ctx->ex_list.ptr, (size_t) n, LiveParticle{(const char *) d_parts, esz, layout->off_flags},
+                               ctx->ex_counts.ptr, &nkeep));
         if(nkeep < n) {
             SHQ_TRY(ctx->ex_bytes.reserve((size_t) std::max<int64_t>(nkeep, 1) * esz));
             if(nkeep > 0) {
@@ -530,7 +490,8 @@ extern "C" int shq_slots_gc(shq_context *ctx, const shq_exchange_layout *layout,
         const int64_t used = slot_size[ty];
         SHQ_TRY(ctx->ex_list.reserve((size_t) used));
         int64_t nkeep = 0;
-        SHQ_TRY(select_keep(ctx, LiveSlot{tab.ptr[ty], tab.elsize[ty], layout->off_reverselink, (int) MaxPart}, (size_t) used, ctx->ex_list.ptr, &nkeep));
+        SHQ_TRY(prim_select_if(ctx, rocprim::counting_iterator<int32_t>(0), ctx->ex_list.ptr, (size_t) used,
+                               LiveSlot{tab.ptr[ty], tab.elsize[ty], layout->off_reverselink, (int) MaxPart}, ctx->ex_counts.ptr, &nkeep));
         if(nkeep < used && nkeep > 0) {
             SHQ_TRY(ctx->ex_bytes.reserve((size_t) nkeep * tab.elsize[ty]));
             gc_gather_kernel<<<dim3(nblk(nkeep * (long long) (tab.elsize[ty] / 4))), dim3(256), 0, st>>>(nkeep, ctx->ex_list.ptr, tab.ptr[ty], tab.elsize[ty], ctx->ex_bytes.ptr);
@@ -574,7 +535,6 @@ extern "C" int shq_slots_gc_sorted(shq_context *ctx, const shq_exchange_layout *
         SHQ_TRY(ctx->ex_key[0].reserve(cap));
         SHQ_TRY(ctx->ex_key[1].reserve(cap));
         SHQ_TRY(ctx->ex_key[2].reserve(cap));
-        SHQ_TRY(ctx->ex_val[0].reserve(cap));
         SHQ_TRY(ctx->ex_val[1].reserve(cap));
         SHQ_TRY(ctx->ex_val[2].reserve(cap));
         SHQ_TRY(ctx->ex_u64.reserve(cap));
@@ -582,17 +542,10 @@ extern "C" int shq_slots_gc_sorted(shq_context *ctx, const shq_exchange_layout *
         unsigned long long *d_ng = ctx->ex_counts.ptr + 16;
         SHQ_HIP(hipMemsetAsync(d_ng, 0, sizeof(unsigned long long), st));
         /* PeanoOrder::operator<: TypeKey first, then Key.  Least significant first: a stable sort by key, then by TypeKey */
-        gcs_iota_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, ctx->ex_val[0].ptr);
-        {
-            size_t tmp = 0;
-            SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, (const unsigned long long *) d_keys, ctx->ex_u64.ptr, (const int32_t *) ctx->ex_val[0].ptr, ctx->ex_val[1].ptr, cap, 0, 64, st));
-            SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-            SHQ_HIP(rocprim::radix_sort_pairs((void *) ctx->act_temp.ptr, tmp, (const unsigned long long *) d_keys, ctx->ex_u64.ptr, (const int32_t *) ctx->ex_val[0].ptr,
-                                              ctx->ex_val[1].ptr, cap, 0, 64, st));
-        }
+        SHQ_TRY(prim_sort_pairs(ctx, (const unsigned long long *) d_keys, ctx->ex_u64.ptr, rocprim::counting_iterator<int32_t>(0), ctx->ex_val[1].ptr, cap, 0, 64));
         gcs_typekey_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, (const char *) d_parts, esz, layout->off_flags, layout->off_type, ctx->ex_key[0].ptr, d_ng);
         gcs_gather_u32_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, ctx->ex_val[1].ptr, ctx->ex_key[0].ptr, ctx->ex_key[1].ptr);
-        SHQ_TRY(sort_pairs(ctx, (const unsigned int *) ctx->ex_key[1].ptr, ctx->ex_key[2].ptr, (const int32_t *) ctx->ex_val[1].ptr, ctx->ex_val[2].ptr, cap, 8));
+        SHQ_TRY(prim_sort_pairs(ctx, ctx->ex_key[1].ptr, ctx->ex_key[2].ptr, ctx->ex_val[1].ptr, ctx->ex_val[2].ptr, cap, 0, 8));
         gc_gather_kernel<<<dim3(nblk(n * (long long) (esz / 4))), dim3(256), 0, st>>>(n, ctx->ex_val[2].ptr, (const char *) d_parts, esz, ctx->ex_bytes.ptr);
         SHQ_HIP(hipMemcpyAsync(d_parts, ctx->ex_bytes.ptr, cap * esz, hipMemcpyDeviceToDevice, st));
         unsigned long long h = 0;
@@ -625,12 +578,13 @@ extern "C" int shq_slots_gc_sorted(shq_context *ctx, const shq_exchange_layout *
         SHQ_TRY(ctx->ex_val[1].reserve((size_t) used));
         SHQ_TRY(ctx->ex_bytes.reserve((size_t) used * tab.elsize[ty]));
         gcs_rlkey_kernel<<<dim3(nblk(used)), dim3(256), 0, st>>>(used, tab.ptr[ty], tab.elsize[ty], layout->off_reverselink, ctx->ex_key[0].ptr, ctx->ex_val[0].ptr);
-        SHQ_TRY(sort_pairs(ctx, (const unsigned int *) ctx->ex_key[0].ptr, ctx->ex_key[1].ptr, (const int32_t *) ctx->ex_val[0].ptr, ctx->ex_val[1].ptr, (size_t) used, 32));
+        SHQ_TRY(prim_sort_pairs(ctx, ctx->ex_key[0].ptr, ctx->ex_key[1].ptr, ctx->ex_val[0].ptr, ctx->ex_val[1].ptr, (size_t) used, 0, 32));
         gc_gather_kernel<<<dim3(nblk(used * (long long) (tab.elsize[ty] / 4))), dim3(256), 0, st>>>(used, ctx->ex_val[1].ptr, tab.ptr[ty], tab.elsize[ty], ctx->ex_bytes.ptr);
         SHQ_HIP(hipMemcpyAsync(tab.ptr[ty], ctx->ex_bytes.ptr, (size_t) used * tab.elsize[ty], hipMemcpyDeviceToDevice, st));
         SHQ_TRY(ctx->ex_list.reserve((size_t) used));
         int64_t nkeep = 0;
-        SHQ_TRY(select_keep(ctx, LiveSlot{tab.ptr[ty], tab.elsize[ty], layout->off_reverselink, (int) MaxPart}, (size_t) used, ctx->ex_list.ptr, &nkeep));
+        SHQ_TRY(prim_select_if(ctx, rocprim::counting_iterator<int32_t>(0), ctx->ex_list.ptr, (size_t) used,
+                               LiveSlot{tab.ptr[ty], tab.elsize[ty], layout->off_reverselink, (int) MaxPart}, ctx->ex_counts.ptr, &nkeep));
         slot_size[ty] = nkeep;
         if(nkeep > 0) {
             gc_collect_kernel<<<dim3(nblk(nkeep)), dim3(256), 0, st>>>(nkeep, tab.ptr[ty], tab.elsize[ty], layout->off_reverselink, (char *) d_parts, esz, layout->off_pi);

@@ -13,14 +13,10 @@
  * snapshot times only and is bound by the ~20 neighbours per particle, not by the node fetches the wave-union walks were built for.
  * The catalogue is a radix sort by label, run detection by scans, and one thread per kept group for the property sums (in particle
  * index order, so the sums are reproducible; the reference's order is whatever its unstable sort left). */
-#include "common.hpp"
+#include "device_prims.hpp"
 #include <string.h>
 #include <vector>
 #include <algorithm>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 namespace {
 
@@ -561,23 +557,6 @@ __global__ void fof_members_kernel(long long n, const int32_t *idx, const int32_
         members[off_excl[keptidx_excl[r]] + (k - runstart[r])] = idx[k];
 }
 
-template <typename T> int scan_excl(shq_context *ctx, const T *in, T *out, size_t n)
-{
-    size_t tmp = 0;
-    SHQ_HIP(rocprim::exclusive_scan(nullptr, tmp, in, out, T(0), n, rocprim::plus<T>(), ctx->stream));
-    SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::exclusive_scan((void *) ctx->act_temp.ptr, tmp, in, out, T(0), n, rocprim::plus<T>(), ctx->stream));
-    return SHQ_OK;
-}
-template <typename T> int scan_incl(shq_context *ctx, const T *in, T *out, size_t n)
-{
-    size_t tmp = 0;
-    SHQ_HIP(rocprim::inclusive_scan(nullptr, tmp, in, out, n, rocprim::plus<T>(), ctx->stream));
-    SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::inclusive_scan((void *) ctx->act_temp.ptr, tmp, in, out, n, rocprim::plus<T>(), ctx->stream));
-    return SHQ_OK;
-}
-
 } // namespace
 
 extern "C" int shq_fof(shq_context *ctx, const shq_fof_params *fp, const uint64_t *ids, uint64_t *minid_by_particle, int32_t *grnr_by_particle,
@@ -654,15 +633,10 @@ extern "C" int shq_fof(shq_context *ctx, const shq_fof_params *fp, const uint64_
             *d_keep = ctx->fof_i32[4].ptr, *d_keptidx = ctx->fof_i32[5].ptr;
     unsigned long long *d_keys = ctx->fof_u64[0].ptr; /* the ids are no longer needed */
     fof_iota_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, d_iota);
-    {
-        size_t tmp = 0;
-        SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, d_label2, d_keys, d_iota, d_idx, cap, 0, 64, st));
-        SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-        SHQ_HIP(rocprim::radix_sort_pairs((void *) ctx->act_temp.ptr, tmp, d_label2, d_keys, d_iota, d_idx, cap, 0, 64, st));
-    }
+    SHQ_TRY(prim_sort_pairs(ctx, d_label2, d_keys, d_iota, d_idx, cap, 0, 64));
     int32_t *d_flags = d_iota;
     fof_flag_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, d_keys, d_flags);
-    SHQ_TRY(scan_incl(ctx, (const int32_t *) d_flags, d_runid, cap));
+    SHQ_TRY(prim_inclusive_scan(ctx, (const int32_t *) d_flags, d_runid, cap));
     int32_t h_nruns = 0;
     SHQ_HIP(hipMemcpyAsync(&h_nruns, d_runid + (n - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
     SHQ_HIP(hipStreamSynchronize(st));
@@ -670,7 +644,7 @@ extern "C" int shq_fof(shq_context *ctx, const shq_fof_params *fp, const uint64_
     fof_runstart_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, d_flags, d_runid, d_runstart, nruns);
     fof_keep_kernel<<<dim3(nblk(nruns)), dim3(256), 0, st>>>(nruns, d_runstart, fp->HaloMinLength, d_keep);
     SHQ_HIP(hipMemsetAsync(d_keep + nruns, 0, sizeof(int32_t), st));
-    SHQ_TRY(scan_excl(ctx, (const int32_t *) d_keep, d_keptidx, (size_t) nruns + 1));
+    SHQ_TRY(prim_exclusive_scan(ctx, (const int32_t *) d_keep, d_keptidx, int32_t(0), (size_t) nruns + 1));
     int32_t h_ng = 0;
     SHQ_HIP(hipMemcpyAsync(&h_ng, d_keptidx + nruns, sizeof(int32_t), hipMemcpyDeviceToHost, st));
     SHQ_HIP(hipStreamSynchronize(st));
@@ -691,14 +665,8 @@ extern "C" int shq_fof(shq_context *ctx, const shq_fof_params *fp, const uint64_
     long long nmembers = 0;
     if(ng > 0) {
         fof_groups_kernel<<<dim3(nblk(nruns)), dim3(256), 0, st>>>(nruns, d_runstart, d_keep, d_keptidx, d_gstart, d_glen, ctx->fof_gkey[0].ptr, ctx->fof_g32[3].ptr);
-        {
-            /* groups are in MinID order; a stable sort on UINT_MAX - Length gives (length descending, MinID ascending) */
-            size_t tmp = 0;
-            SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, ctx->fof_gkey[0].ptr, ctx->fof_gkey[1].ptr, ctx->fof_g32[3].ptr, ctx->fof_g32[4].ptr, (size_t) ng, 0, 32, st));
-            SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-            SHQ_HIP(rocprim::radix_sort_pairs((void *) ctx->act_temp.ptr, tmp, ctx->fof_gkey[0].ptr, ctx->fof_gkey[1].ptr, ctx->fof_g32[3].ptr, ctx->fof_g32[4].ptr,
-                                              (size_t) ng, 0, 32, st));
-        }
+        /* groups are in MinID order; a stable sort on UINT_MAX - Length gives (length descending, MinID ascending) */
+        SHQ_TRY(prim_sort_pairs(ctx, ctx->fof_gkey[0].ptr, ctx->fof_gkey[1].ptr, ctx->fof_g32[3].ptr, ctx->fof_g32[4].ptr, (size_t) ng, 0, 32));
         fof_grnr_kernel<<<dim3(nblk(ng)), dim3(256), 0, st>>>(ng, ctx->fof_g32[4].ptr, d_grnr);
         const double *d_vel = (ctx->have_sph || ctx->have_dyn) ? ctx->vel.ptr : nullptr;
         const double *d_dens = ctx->have_sph ? ctx->g_density.ptr : nullptr;
@@ -711,7 +679,7 @@ extern "C" int shq_fof(shq_context *ctx, const shq_fof_params *fp, const uint64_
             int32_t *d_flag = ctx->fof_g32[3].ptr, *d_excl = ctx->fof_g32[4].ptr; /* the GrNr sort is done with them */
             SHQ_TRY(ctx->fof_biglist.reserve(gcap + 1));
             fof_bigflag_kernel<<<dim3(nblk(ng)), dim3(256), 0, st>>>(ng, d_glen, d_flag);
-            SHQ_TRY(scan_excl(ctx, (const int32_t *) d_flag, d_excl, (size_t) ng));
+            SHQ_TRY(prim_exclusive_scan(ctx, (const int32_t *) d_flag, d_excl, int32_t(0), (size_t) ng));
             int32_t lastf = 0, laste = 0;
             SHQ_HIP(hipMemcpyAsync(&lastf, d_flag + (ng - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
             SHQ_HIP(hipMemcpyAsync(&laste, d_excl + (ng - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
@@ -727,7 +695,7 @@ extern "C" int shq_fof(shq_context *ctx, const shq_fof_params *fp, const uint64_
         }
         fof_glen64_kernel<<<dim3(nblk(ng)), dim3(256), 0, st>>>(ng, d_glen, ctx->fof_goff[0].ptr);
         SHQ_HIP(hipMemsetAsync(ctx->fof_goff[0].ptr + ng, 0, sizeof(long long), st));
-        SHQ_TRY(scan_excl(ctx, (const long long *) ctx->fof_goff[0].ptr, ctx->fof_goff[1].ptr, (size_t) ng + 1));
+        SHQ_TRY(prim_exclusive_scan(ctx, (const long long *) ctx->fof_goff[0].ptr, ctx->fof_goff[1].ptr, 0ll, (size_t) ng + 1));
         fof_member_offsets_kernel<<<dim3(nblk(ng)), dim3(256), 0, st>>>(ng, d_glen, ctx->fof_goff[1].ptr, ctx->fof_groups.ptr);
         SHQ_HIP(hipMemcpyAsync(&nmembers, ctx->fof_goff[1].ptr + ng, sizeof(long long), hipMemcpyDeviceToHost, st));
     }
@@ -808,21 +776,14 @@ extern "C" int shq_fof_seed_select(shq_context *ctx, double MinFoFMassForNewSeed
     SHQ_HIP(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     SHQ_TRY(ctx->ex_list.reserve((size_t) ng));
-    SHQ_TRY(ctx->ex_counts.reserve(64));
-    size_t tmp = 0;
-    rocprim::counting_iterator<int32_t> it(0);
     const SeedGroup pred{ctx->fof_groups.ptr, MinFoFMassForNewSeed, MinMStarForNewSeed};
-    SHQ_HIP(rocprim::select(nullptr, tmp, it, ctx->ex_list.ptr, ctx->ex_counts.ptr, (size_t) ng, pred, st));
-    SHQ_TRY(ctx->ex_bytes.reserve(tmp + 16));
-    SHQ_HIP(rocprim::select(ctx->ex_bytes.ptr, tmp, it, ctx->ex_list.ptr, ctx->ex_counts.ptr, (size_t) ng, pred, st));
-    unsigned long long h = 0;
-    SHQ_HIP(hipMemcpyAsync(&h, ctx->ex_counts.ptr, sizeof(h), hipMemcpyDeviceToHost, st));
-    SHQ_HIP(hipStreamSynchronize(st));
-    *nseeds = (int64_t) h;
+    int64_t h = 0;
+    SHQ_TRY(prim_select_if(ctx, rocprim::counting_iterator<int32_t>(0), ctx->ex_list.ptr, (size_t) ng, pred, nullptr, &h));
+    *nseeds = h;
     if(!d_seed_index || h == 0)
         return SHQ_OK;
-    SHQ_CHECK(capacity >= (int64_t) h, SHQ_ERR_INVALID, "fof_seed_select: capacity %ld < %ld seeds", (long) capacity, (long) h);
-    fof_seed_index_kernel<<<dim3(nblk((long long) h)), dim3(256), 0, st>>>((long long) h, ctx->ex_list.ptr, ctx->fof_groups.ptr, d_seed_index);
+    SHQ_CHECK(capacity >= h, SHQ_ERR_INVALID, "fof_seed_select: capacity %ld < %ld seeds", (long) capacity, (long) h);
+    fof_seed_index_kernel<<<dim3(nblk(h)), dim3(256), 0, st>>>(h, ctx->ex_list.ptr, ctx->fof_groups.ptr, d_seed_index);
     SHQ_HIP(hipGetLastError());
     return SHQ_OK;
 }

@@ -33,9 +33,7 @@
  * run.cpp:482 / 624 does (the walk would miss one that is not in it).
  */
 #include "call_scope.hpp"
-#include <rocprim/device/device_partition.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
+#include "device_prims.hpp"
 #include <rocprim/iterator/transform_iterator.hpp>
 #include <math.h>
 #include <string.h>
@@ -245,24 +243,6 @@ struct HitBefore {    /* first hit among the bubbles the loop ran */
     __device__ bool operator()(const int32_t &h) const { return h >= 0 && h < kstop; }
 };
 
-template <typename Pred> int select_indices(shq_context *ctx, CallScope &sc, long long n, Pred pred, int32_t *out, unsigned long long *d_count, int64_t *m)
-{
-    *m = 0;
-    if(n <= 0)
-        return SHQ_OK;
-    size_t tmp = 0;
-    const rocprim::counting_iterator<int32_t> all(0);
-    SHQ_HIP(rocprim::select(nullptr, tmp, all, out, d_count, (size_t) n, pred, ctx->stream));
-    SHQ_TRY(ctx->tb.temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::select(ctx->tb.temp.ptr, tmp, all, out, d_count, (size_t) n, pred, ctx->stream));
-    unsigned long long h = 0;
-    SHQ_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-    SHQ_HIP(hipStreamSynchronize(ctx->stream));
-    *m = (int64_t) h;
-    (void) sc;
-    return SHQ_OK;
-}
-
 } // namespace
 
 extern "C" int shq_heiii_last_stats(shq_context *ctx, shq_heiii_stats *stats)
@@ -309,7 +289,8 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
         CandRow *rows;
         SHQ_TRY(sc.alloc(&gidx, (size_t) TotNgroups));
         int64_t K = 0;
-        SHQ_TRY(select_indices(ctx, sc, TotNgroups, InWindow{ctx->fof_groups.ptr, p->qso_candidate_min_mass, p->qso_candidate_max_mass}, gidx, d_cnt, &K));
+        SHQ_TRY(prim_select_if(ctx, rocprim::counting_iterator<int32_t>(0), gidx, (size_t) TotNgroups,
+                               InWindow{ctx->fof_groups.ptr, p->qso_candidate_min_mass, p->qso_candidate_max_mass}, d_cnt, &K));
         SHQ_TRY(sc.alloc(&rows, (size_t) K));
         if(K > 0) {
             heiii_cand_kernel<<<dim3(nblk(K, HT)), dim3(HT), 0, s>>>(K, gidx, ctx->fof_groups.ptr, rows);
@@ -343,7 +324,7 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
         int32_t *fidx;
         SHQ_TRY(sc.alloc(&fidx, (size_t) n));
         int64_t nf = 0;
-        SHQ_TRY(select_indices(ctx, sc, n, Flashable{d_flags}, fidx, d_cnt, &nf));
+        SHQ_TRY(prim_select_if(ctx, rocprim::counting_iterator<int32_t>(0), fidx, (size_t) n, Flashable{d_flags}, d_cnt, &nf));
         if(nf > 0) {
             heiii_apply_idx_kernel<<<dim3(nblk(nf, HT)), dim3(HT), 0, s>>>(nf, fidx, d_flags, d_entropy, d_density, a3inv, du, d_rows);
             SHQ_HIP(hipGetLastError());
@@ -381,7 +362,7 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
         unsigned long long *d_counts;
         SHQ_TRY(sc.alloc(&eidx, (size_t) n));
         int64_t m = 0;
-        SHQ_TRY(select_indices(ctx, sc, n, Eligible{d_flags}, eidx, d_cnt, &m));
+        SHQ_TRY(prim_select_if(ctx, rocprim::counting_iterator<int32_t>(0), eidx, (size_t) n, Eligible{d_flags}, d_cnt, &m));
         SHQ_TRY(sc.alloc(&E[0], (size_t) m));
         SHQ_TRY(sc.alloc(&E[1], (size_t) m));
         SHQ_TRY(sc.alloc(&S, (size_t) m));
@@ -524,21 +505,14 @@ extern "C" int shq_heiii_reionization(shq_context *ctx, const shq_heiii_params *
             /* ---- flag and heat the particles whose first hit the loop reached; the rest stay eligible */
             SHQ_TRY(sc.mark(s));
             if(kstop > 0 && m > 0) {
-                size_t tmp = 0;
-                auto flags = rocprim::make_transform_iterator(d_hit, HitBefore{kstop});
-                SHQ_HIP(rocprim::partition_two_way(nullptr, tmp, E[cur], flags, S, E[cur ^ 1], d_cnt, (size_t) m, s));
-                SHQ_TRY(ctx->tb.temp.reserve(tmp + 16));
-                SHQ_HIP(rocprim::partition_two_way(ctx->tb.temp.ptr, tmp, E[cur], flags, S, E[cur ^ 1], d_cnt, (size_t) m, s));
-                unsigned long long nsel = 0;
-                SHQ_HIP(hipMemcpyAsync(&nsel, d_cnt, sizeof(nsel), hipMemcpyDeviceToHost, s));
-                SHQ_HIP(hipStreamSynchronize(s));
+                int64_t nsel = 0;
+                SHQ_TRY(prim_partition_two_way(ctx, E[cur], rocprim::make_transform_iterator(d_hit, HitBefore{kstop}), S, E[cur ^ 1], (size_t) m, d_cnt, &nsel));
                 if(nsel > 0) {
-                    heiii_apply_rec_kernel<<<dim3(nblk((long long) nsel, HT)), dim3(HT), 0, s>>>((long long) nsel, S, d_flags, d_entropy, d_density, a3inv,
-                                                                                         du, d_rows + nrows);
+                    heiii_apply_rec_kernel<<<dim3(nblk(nsel, HT)), dim3(HT), 0, s>>>(nsel, S, d_flags, d_entropy, d_density, a3inv, du, d_rows + nrows);
                     SHQ_HIP(hipGetLastError());
                 }
-                nrows += (int64_t) nsel;
-                m -= (int64_t) nsel;
+                nrows += nsel;
+                m -= nsel;
                 cur ^= 1;
             }
             SHQ_TRY(sc.mark(s));

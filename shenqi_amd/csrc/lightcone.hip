@@ -14,11 +14,10 @@
  * scheduling, and no atomic decides a position.  In pass B a lane with one or two rows (nearly all that have any) computes just the pairs
  * pass A noted; only lanes with more run the loop again.  A workgroup of pass B whose offsets do not move leaves on two scalar loads.
  * Both passes compute a pair by the same functions, so that they cannot disagree. */
-#include "common.hpp"
+#include "device_prims.hpp"
 #include "call_scope.hpp"
 #include <math.h>
 #include <string.h>
-#include <rocprim/device/device_scan.hpp>
 
 namespace {
 
@@ -369,10 +368,7 @@ extern "C" int shq_lightcone_compute(shq_context *ctx, const shq_lightcone_layou
     lc_launch<false>(mode, st, a, ctx->lc_cnt.ptr, ctx->lc_cnt.ptr + N + 1, nullptr, nullptr, nullptr, nullptr);
     SHQ_HIP(hipGetLastError());
     SHQ_TRY(sc.mark(st));
-    size_t tmp = 0;
-    SHQ_HIP(rocprim::exclusive_scan(nullptr, tmp, ctx->lc_cnt.ptr, ctx->lc_off.ptr, 0ll, N + 1, rocprim::plus<long long>(), st));
-    SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::exclusive_scan((void *) ctx->act_temp.ptr, tmp, ctx->lc_cnt.ptr, ctx->lc_off.ptr, 0ll, N + 1, rocprim::plus<long long>(), st));
+    SHQ_TRY(prim_exclusive_scan(ctx, ctx->lc_cnt.ptr, ctx->lc_off.ptr, 0ll, N + 1));
     SHQ_TRY(sc.mark(st));
     long long total = 0;
     SHQ_HIP(hipMemcpyAsync(&total, ctx->lc_off.ptr + N, sizeof(total), hipMemcpyDeviceToHost, st));

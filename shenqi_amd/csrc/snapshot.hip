@@ -12,13 +12,10 @@
  * The LDS row pitch is the record size rounded up to an odd number of 8-byte words (160 -> 168, 176 -> 184, 72, 248): 32 lanes reading
  * the same 8-byte member of 32 consecutive rows then touch all 64 banks once (DESIGN.md has the arithmetic).
  * The descriptors are kernel arguments: wave-uniform, read through scalar loads, every switch over them is a scalar branch. */
-#include "common.hpp"
+#include "device_prims.hpp"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
 namespace {
 
@@ -427,16 +424,6 @@ int io_reset(shq_context *ctx)
     return SHQ_OK;
 }
 
-/* stable sort of (key, value) by the low three bits of the key */
-template <class ValIn> int sort_by_typekey(shq_context *ctx, const uint8_t *kin, uint8_t *kout, ValIn vin, int32_t *vout, size_t n)
-{
-    size_t tmp = 0;
-    SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, kin, kout, vin, vout, n, 0, 3, ctx->stream));
-    SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::radix_sort_pairs((void *) ctx->act_temp.ptr, tmp, kin, kout, vin, vout, n, 0, 3, ctx->stream));
-    return SHQ_OK;
-}
-
 } // namespace
 
 extern "C" int shq_io_select(shq_context *ctx, const shq_io_layout *layout, const void *d_parts, int64_t numpart, int predicate, int order, int32_t *d_selection,
@@ -467,17 +454,13 @@ extern "C" int shq_io_select(shq_context *ctx, const shq_io_layout *layout, cons
     io_keys_kernel<<<dim3(nblk(numpart)), dim3(256), 0, st>>>(pr, predicate, ctx->io_u8[0].ptr, bygr ? ctx->io_u64[0].ptr : nullptr, ctx->io_cnt.ptr);
     SHQ_HIP(hipGetLastError());
     if(!bygr)
-        SHQ_TRY(sort_by_typekey(ctx, ctx->io_u8[0].ptr, ctx->io_u8[1].ptr, rocprim::counting_iterator<int32_t>(0), d_selection, N));
+        SHQ_TRY(prim_sort_pairs(ctx, ctx->io_u8[0].ptr, ctx->io_u8[1].ptr, rocprim::counting_iterator<int32_t>(0), d_selection, N, 0, 3));
     else {
         /* by GrNr first, then stably by type: within a type the order of GrNr, ties in index order */
-        size_t tmp = 0;
-        const rocprim::counting_iterator<int32_t> iota(0);
-        SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, ctx->io_u64[0].ptr, ctx->io_u64[1].ptr, iota, ctx->io_i32.ptr, N, 0, 64, st));
-        SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-        SHQ_HIP(rocprim::radix_sort_pairs((void *) ctx->act_temp.ptr, tmp, ctx->io_u64[0].ptr, ctx->io_u64[1].ptr, iota, ctx->io_i32.ptr, N, 0, 64, st));
+        SHQ_TRY(prim_sort_pairs(ctx, ctx->io_u64[0].ptr, ctx->io_u64[1].ptr, rocprim::counting_iterator<int32_t>(0), ctx->io_i32.ptr, N, 0, 64));
         io_key_of_kernel<<<dim3(nblk(numpart)), dim3(256), 0, st>>>(numpart, ctx->io_i32.ptr, ctx->io_u8[0].ptr, ctx->io_u8[1].ptr);
         SHQ_HIP(hipGetLastError());
-        SHQ_TRY(sort_by_typekey(ctx, ctx->io_u8[1].ptr, ctx->io_u8[0].ptr, ctx->io_i32.ptr, d_selection, N));
+        SHQ_TRY(prim_sort_pairs(ctx, ctx->io_u8[1].ptr, ctx->io_u8[0].ptr, ctx->io_i32.ptr, d_selection, N, 0, 3));
     }
     unsigned long long h[8];
     SHQ_HIP(hipMemcpyAsync(h, ctx->io_cnt.ptr, sizeof(h), hipMemcpyDeviceToHost, st));
@@ -551,7 +534,7 @@ extern "C" int shq_io_scatter(shq_context *ctx, const shq_io_layout *layout, voi
     if(need_slot)
         SHQ_TRY(check_slots(layout, ptype, (const void *const *) d_slots, slot_size));
     SHQ_TRY(check_conv(conv, blocks, nblocks, false));
-    size_t cnt = 0;
+    int64_t cnt = 0;
     const IoRec pr = io_rec(layout, d_parts, numpart);
     hipStream_t st = ctx->stream;
     if(numpart > 0) {
@@ -561,20 +544,13 @@ extern "C" int shq_io_scatter(shq_context *ctx, const shq_io_layout *layout, voi
         SHQ_TRY(ctx->io_i32.reserve((size_t) numpart));
         io_typeflag_kernel<<<dim3(nblk(numpart)), dim3(256), 0, st>>>(pr, ptype, ctx->io_u8[0].ptr);
         SHQ_HIP(hipGetLastError());
-        size_t *d_n = reinterpret_cast<size_t *>(ctx->io_cnt.ptr + 9);
-        size_t tmp = 0;
-        const rocprim::counting_iterator<int32_t> iota(0);
-        SHQ_HIP(rocprim::select(nullptr, tmp, iota, ctx->io_u8[0].ptr, ctx->io_i32.ptr, d_n, (size_t) numpart, st));
-        SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-        SHQ_HIP(rocprim::select((void *) ctx->act_temp.ptr, tmp, iota, ctx->io_u8[0].ptr, ctx->io_i32.ptr, d_n, (size_t) numpart, st));
-        SHQ_HIP(hipMemcpyAsync(&cnt, d_n, sizeof(cnt), hipMemcpyDeviceToHost, st));
-        SHQ_HIP(hipStreamSynchronize(st));
+        SHQ_TRY(prim_select_flagged(ctx, rocprim::counting_iterator<int32_t>(0), ctx->io_u8[0].ptr, ctx->io_i32.ptr, (size_t) numpart, ctx->io_cnt.ptr + 9, &cnt));
     }
-    SHQ_CHECK((int64_t) cnt == n, SHQ_ERR_INVALID, "io_scatter: %ld rows for %zu particles of type %d", (long) n, cnt, ptype);
+    SHQ_CHECK(cnt == n, SHQ_ERR_INVALID, "io_scatter: %ld rows for %ld particles of type %d", (long) n, (long) cnt, ptype);
     if(cnt == 0 || nblocks == 0)
         return SHQ_OK;
     if(need_slot) {
-        io_scatter_check_kernel<<<dim3(nblk((long long) cnt)), dim3(256), 0, st>>>(pr, ctx->io_i32.ptr, (long long) cnt, (long long) slot_size[ptype], io_err(ctx));
+        io_scatter_check_kernel<<<dim3(nblk(cnt)), dim3(256), 0, st>>>(pr, ctx->io_i32.ptr, cnt, (long long) slot_size[ptype], io_err(ctx));
         SHQ_HIP(hipGetLastError());
         int e = 0;
         SHQ_HIP(hipMemcpyAsync(&e, io_err(ctx), sizeof(e), hipMemcpyDeviceToHost, st));
@@ -589,8 +565,8 @@ extern "C" int shq_io_scatter(shq_context *ctx, const shq_io_layout *layout, voi
             B.b[b] = blocks[b0 + b];
             B.col[b] = (char *) d_in[b0 + b];
         }
-        io_scatter_kernel<<<dim3(nblk((long long) cnt)), dim3(256), 0, st>>>(pr, (char *) d_parts, need_slot ? (char *) d_slots[ptype] : nullptr,
-                                                                            need_slot ? layout->slot_elsize[ptype] : 0, ctx->io_i32.ptr, (long long) cnt, B, *conv);
+        io_scatter_kernel<<<dim3(nblk(cnt)), dim3(256), 0, st>>>(pr, (char *) d_parts, need_slot ? (char *) d_slots[ptype] : nullptr,
+                                                                need_slot ? layout->slot_elsize[ptype] : 0, ctx->io_i32.ptr, cnt, B, *conv);
         SHQ_HIP(hipGetLastError());
     }
     return SHQ_OK;

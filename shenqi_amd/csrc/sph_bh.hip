@@ -1,8 +1,7 @@
 /* sph_bh.hip — black-hole accretion and feedback on the walk of sph_walk.hpp, and the marked-particle lists and row gathers
  * their callers read the changed particles back with. */
 #include "sph_walk.hpp"
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
+#include "device_prims.hpp"
 
 /* ---- black-hole accretion and feedback: libgadget/blackhole.cpp:373-1003 ------------------------------
  * The two legacy-API tree walks of blackhole(): symmetric neighbour search over gas + black holes (treewalk_visit_ngbiter,
@@ -482,19 +481,9 @@ int shq_marked_list(shq_context *ctx, const uint8_t *d_mark, int64_t n, int32_t 
     *m = 0;
     if(n <= 0)
         return SHQ_OK;
-    hipStream_t st = ctx->stream;
     SHQ_TRY(ctx->s_counters.reserve(8));
-    unsigned long long *d_count = reinterpret_cast<unsigned long long *>(ctx->s_counters.ptr);
-    size_t tmp = 0;
-    const rocprim::counting_iterator<int32_t> all(0);
-    SHQ_HIP(rocprim::select(nullptr, tmp, all, d_list, d_count, (size_t) n, Marked{d_mark}, st));
-    SHQ_TRY(ctx->tb.temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::select(ctx->tb.temp.ptr, tmp, all, d_list, d_count, (size_t) n, Marked{d_mark}, st));
-    unsigned long long h = 0;
-    SHQ_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, st));
-    SHQ_HIP(hipStreamSynchronize(st));
-    *m = (int64_t) h;
-    return SHQ_OK;
+    return prim_select_if(ctx, rocprim::counting_iterator<int32_t>(0), d_list, (size_t) n, Marked{d_mark},
+                          reinterpret_cast<unsigned long long *>(ctx->s_counters.ptr), m);
 }
 
 namespace {

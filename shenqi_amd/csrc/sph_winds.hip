@@ -1,7 +1,7 @@
 /* sph_winds.hip — stellar winds from new stars (walk, nearest-star resolution, kick), metal return around dying stars, and the
  * wind model's particle loops, on the walk of sph_walk.hpp. */
 #include "sph_walk.hpp"
-#include <rocprim/device/device_radix_sort.hpp>
+#include "device_prims.hpp"
 #include <utility>
 
 /* ---- stellar winds from new stars: libgadget/winds.cpp:227-369, 411-447, 510-565 --------------------------
@@ -178,10 +178,7 @@ int shq_wind_resolve_device(shq_context *ctx, const WindWalkArgs *w, long long n
     for(int which = 0; which < 3; which++) {
         wind_kick_keys_kernel<<<dim3(nblk(nk)), dim3(256), 0, st>>>(nk, w->kicks, which, ctx->metal_keys[0].ptr, ord[0], cur);
         SHQ_HIP(hipGetLastError());
-        size_t tmp = 0;
-        SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ord[0], ord[1], (size_t) nk, 0, 64, st));
-        SHQ_TRY(ctx->hydrec_leaf.reserve(tmp + 16));
-        SHQ_HIP(rocprim::radix_sort_pairs(ctx->hydrec_leaf.ptr, tmp, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ord[0], ord[1], (size_t) nk, 0, 64, st));
+        SHQ_TRY(prim_sort_pairs(ctx, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ord[0], ord[1], (size_t) nk, 0, 64));
         cur = ord[1];
         std::swap(ord[0], ord[1]); /* the next pass writes its identity-permuted indices over the old input */
     }
@@ -422,20 +419,13 @@ int shq_metal_return_device(shq_context *ctx, MetalWalkArgs *w, int kernel_type,
     SHQ_HIP(hipMemsetAsync(d_massreturn, 0, sizeof(double) * (size_t) nq, st));
     if(np == 0)
         return SHQ_OK;
-    size_t tmp = 0;
-    SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ctx->metal_val[0].ptr, ctx->metal_val[1].ptr, (size_t) np, 0, 64, st));
-    SHQ_TRY(ctx->wind_kicks.reserve(tmp + 16));
-    SHQ_HIP(rocprim::radix_sort_pairs(ctx->wind_kicks.ptr, tmp, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ctx->metal_val[0].ptr, ctx->metal_val[1].ptr, (size_t) np, 0, 64,
-                                      st));
+    SHQ_TRY(prim_sort_pairs(ctx, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ctx->metal_val[0].ptr, ctx->metal_val[1].ptr, (size_t) np, 0, 64));
     /* thismass per pair, in (particle, star) order, into metal_val[0] */
     metal_apply_kernel<<<dim3(nblk((long long) np)), dim3(256), 0, st>>>((long long) np, ctx->metal_keys[1].ptr, ctx->metal_val[1].ptr, *w, ctx->metal_val[0].ptr);
     SHQ_HIP(hipGetLastError());
     metal_rekey_kernel<<<dim3(nblk((long long) np)), dim3(256), 0, st>>>((long long) np, ctx->metal_keys[1].ptr, ctx->metal_keys[0].ptr);
     SHQ_HIP(hipGetLastError());
-    SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ctx->metal_val[0].ptr, ctx->metal_val[1].ptr, (size_t) np, 0, 64, st));
-    SHQ_TRY(ctx->wind_kicks.reserve(tmp + 16));
-    SHQ_HIP(rocprim::radix_sort_pairs(ctx->wind_kicks.ptr, tmp, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ctx->metal_val[0].ptr, ctx->metal_val[1].ptr, (size_t) np, 0, 64,
-                                      st));
+    SHQ_TRY(prim_sort_pairs(ctx, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ctx->metal_val[0].ptr, ctx->metal_val[1].ptr, (size_t) np, 0, 64));
     metal_sum_kernel<<<dim3(nblk((long long) np)), dim3(256), 0, st>>>((long long) np, ctx->metal_keys[1].ptr, ctx->metal_val[1].ptr, d_massreturn);
     SHQ_HIP(hipGetLastError());
     return SHQ_OK;

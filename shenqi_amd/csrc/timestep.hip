@@ -10,7 +10,7 @@
  *   get_long_range_timestep_dloga (particle loop)                 libgadget/timestep.cpp:1153-1166
  *   black-hole half of do_hydro_kick, repositioning of the drift  libgadget/timestep.cpp:973-979, drift.cpp:32-53
  * The sync-point table, cosmology and DriftKickTimes stay on the host (integration/reference_side/timestep.cpp). */
-#include "common.hpp"
+#include "device_prims.hpp"
 #include <string.h>
 #include <vector>
 #include <algorithm>
@@ -745,8 +745,9 @@ extern "C" int shq_velocity_moments(shq_context *ctx, double v2sum[6], double mi
     if(n == 0)
         return SHQ_OK;
     const unsigned nb = nblk(n);
-    SHQ_TRY(ctx->act_temp.reserve((size_t) nb * 18 * sizeof(double) + 16));
-    double *d_part = reinterpret_cast<double *>(ctx->act_temp.ptr);
+    void *scratch = nullptr; /* consumed before this function returns */
+    SHQ_TRY(prim_scratch(ctx, (size_t) nb * 18 * sizeof(double), &scratch));
+    double *d_part = static_cast<double *>(scratch);
     velmom_kernel<<<dim3(nb), dim3(256), 0, ctx->stream>>>(n, ctx->posm.ptr, ctx->vel.ptr, ctx->pflags.ptr, d_part);
     SHQ_HIP(hipGetLastError());
     std::vector<double> h((size_t) nb * 18);

@@ -14,9 +14,7 @@
  * the reference: count, inclusive scan (rocPRIM), fill at the scanned offsets. */
 #include <cstring>
 #include <vector>
-#include "common.hpp"
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_radix_sort.hpp>
+#include "device_prims.hpp"
 
 namespace {
 
@@ -191,11 +189,7 @@ int run_toptree(shq_context *ctx, const GravTopArgs &ga, const NgbTopArgs &na, c
     toptree_kernel<GRAV, false><<<dim3(nblk(nt)), dim3(256), 0, st>>>(nt, d_act, ctx->posm.ptr, ctx->topnodes.ptr, ctx->topleaves.ptr, ga, na,
                                                                      ctx->top_counts.ptr, nullptr);
     SHQ_HIP(hipGetLastError());
-    size_t tmp = 0;
-    SHQ_HIP(rocprim::inclusive_scan(nullptr, tmp, ctx->top_counts.ptr, ctx->top_counts.ptr, (size_t) nt, rocprim::plus<int32_t>(), st));
-    SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::inclusive_scan((void *) ctx->act_temp.ptr, tmp, ctx->top_counts.ptr, ctx->top_counts.ptr, (size_t) nt,
-                                    rocprim::plus<int32_t>(), st));
+    SHQ_TRY(prim_inclusive_scan(ctx, ctx->top_counts.ptr, ctx->top_counts.ptr, (size_t) nt));
     int32_t total = 0;
     SHQ_HIP(hipMemcpyAsync(&total, ctx->top_counts.ptr + (nt - 1), sizeof(int32_t), hipMemcpyDeviceToHost, st));
     if(exportcounts)
@@ -394,10 +388,7 @@ extern "C" int shq_grav_export_pack(shq_context *ctx, shq_grav_query *d_queries,
     SHQ_TRY(ctx->top_slot.reserve((size_t) n));
     int32_t *key = ctx->top_sort.ptr, *val = key + n, *key2 = val + n, *val2 = key2 + n;
     top_keys_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, ctx->top_table.ptr, key, val);
-    size_t tmp = 0;
-    SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, key, key2, val, val2, (size_t) n, 0, 32, st));
-    SHQ_TRY(ctx->act_temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::radix_sort_pairs((void *) ctx->act_temp.ptr, tmp, key, key2, val, val2, (size_t) n, 0, 32, st)); /* stable */
+    SHQ_TRY(prim_sort_pairs(ctx, key, key2, val, val2, (size_t) n, 0, 32)); /* stable */
     top_slots_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, val2, ctx->top_slot.ptr);
     top_pack_queries_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, ctx->top_table.ptr, ctx->top_slot.ptr, ctx->posm.ptr, ctx->oldacc.ptr, d_queries, d_place);
     SHQ_HIP(hipGetLastError());

@@ -27,10 +27,7 @@
 #include <cstring>
 #include <math.h>
 #include <vector>
-#include "common.hpp"
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_select.hpp>
+#include "device_prims.hpp"
 
 namespace {
 
@@ -664,15 +661,6 @@ __global__ void hilbert_key_kernel(long long n, const int32_t *__restrict__ targ
     keys[t] = key;
 }
 
-namespace {
-__global__ void iota64_kernel(long long n, long long *out)
-{
-    const long long t = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if(t < n)
-        out[t] = t;
-}
-} // namespace
-
 extern "C" int shq_hilbert_order(shq_context *ctx, const double *d_posm, int64_t n, double BoxSize, int64_t *d_order)
 {
     SHQ_CHECK(ctx && (n == 0 || (d_posm && d_order)), SHQ_ERR_INVALID, "null argument");
@@ -683,15 +671,9 @@ extern "C" int shq_hilbert_order(shq_context *ctx, const double *d_posm, int64_t
     TreeBuildBufs &b = ctx->tb;
     SHQ_TRY(b.keys[0].reserve((size_t) n));
     SHQ_TRY(b.keys[1].reserve((size_t) n));
-    SHQ_TRY(ctx->hilb_iota.reserve((size_t) n));
     hilbert_key_kernel<<<dim3(nblk(n)), dim3(256), 0, ctx->stream>>>(n, nullptr, (const double4 *) d_posm, BoxSize, b.keys[0].ptr);
     SHQ_HIP(hipGetLastError());
-    iota64_kernel<<<dim3(nblk(n)), dim3(256), 0, ctx->stream>>>(n, ctx->hilb_iota.ptr);
-    SHQ_HIP(hipGetLastError());
-    size_t tmp = 0;
-    SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, b.keys[0].ptr, b.keys[1].ptr, ctx->hilb_iota.ptr, (long long *) d_order, (size_t) n, 0, 63, ctx->stream));
-    SHQ_TRY(b.temp.reserve(tmp + 16));
-    SHQ_HIP(rocprim::radix_sort_pairs(b.temp.ptr, tmp, b.keys[0].ptr, b.keys[1].ptr, ctx->hilb_iota.ptr, (long long *) d_order, (size_t) n, 0, 63, ctx->stream));
+    SHQ_TRY(prim_sort_pairs(ctx, b.keys[0].ptr, b.keys[1].ptr, rocprim::counting_iterator<long long>(0), (long long *) d_order, (size_t) n, 0, 63));
     return SHQ_OK;
 }
 
@@ -707,28 +689,16 @@ int shq_build_tree_targets(shq_context *ctx)
     SHQ_TRY(b.counters.reserve(4));
     ctx->ntree_targets = 0;
     if(n > 0) {
-        size_t tmp = 0;
-        unsigned long long *d_count = b.counters.ptr + 2;
-        SHQ_HIP(rocprim::select(nullptr, tmp, ctx->leaf_pidx.ptr, ctx->tree_targets.ptr, d_count, (size_t) n, BelowLimit{limit}, ctx->stream));
-        SHQ_TRY(b.temp.reserve(tmp + 16));
-        SHQ_HIP(rocprim::select(b.temp.ptr, tmp, ctx->leaf_pidx.ptr, ctx->tree_targets.ptr, d_count, (size_t) n, BelowLimit{limit}, ctx->stream));
-        unsigned long long h = 0;
-        SHQ_HIP(hipMemcpyAsync(&h, d_count, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
-        SHQ_HIP(hipStreamSynchronize(ctx->stream));
-        ctx->ntree_targets = (int64_t) h;
+        SHQ_TRY(prim_select_if(ctx, ctx->leaf_pidx.ptr, ctx->tree_targets.ptr, (size_t) n, BelowLimit{limit}, b.counters.ptr + 2, &ctx->ntree_targets));
         /* leaf order is an octant order: re-sort the targets along the Peano-Hilbert curve */
-        const long long nt = (long long) h;
+        const long long nt = ctx->ntree_targets;
         if(nt > 64 && ctx->treeBox > 0) {
             SHQ_TRY(b.keys[0].reserve((size_t) nt));
             SHQ_TRY(b.keys[1].reserve((size_t) nt));
             SHQ_TRY(b.idx[0].reserve((size_t) nt));
             hilbert_key_kernel<<<dim3(nblk(nt)), dim3(256), 0, ctx->stream>>>(nt, ctx->tree_targets.ptr, ctx->posm.ptr, ctx->treeBox, b.keys[0].ptr);
             SHQ_HIP(hipGetLastError());
-            SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, b.keys[0].ptr, b.keys[1].ptr, ctx->tree_targets.ptr, b.idx[0].ptr, (size_t) nt, 0, 63,
-                                              ctx->stream));
-            SHQ_TRY(b.temp.reserve(tmp + 16));
-            SHQ_HIP(rocprim::radix_sort_pairs(b.temp.ptr, tmp, b.keys[0].ptr, b.keys[1].ptr, ctx->tree_targets.ptr, b.idx[0].ptr, (size_t) nt, 0, 63,
-                                              ctx->stream));
+            SHQ_TRY(prim_sort_pairs(ctx, b.keys[0].ptr, b.keys[1].ptr, ctx->tree_targets.ptr, b.idx[0].ptr, (size_t) nt, 0, 63));
             SHQ_HIP(hipMemcpyAsync(ctx->tree_targets.ptr, b.idx[0].ptr, sizeof(int32_t) * (size_t) nt, hipMemcpyDeviceToDevice, ctx->stream));
         }
     }
@@ -783,10 +753,7 @@ static int tree_build_impl(shq_context *ctx, double BoxSize, int mask, const int
 
     /* 2. stable sort by key: depth-first leaf order, ties in candidate order */
     if(ncand > 0) {
-        size_t tmp = 0;
-        SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, b.keys[0].ptr, b.keys[1].ptr, b.idx[0].ptr, b.idx[1].ptr, (size_t) ncand, 0, 64, st));
-        SHQ_TRY(b.temp.reserve(tmp + 16));
-        SHQ_HIP(rocprim::radix_sort_pairs(b.temp.ptr, tmp, b.keys[0].ptr, b.keys[1].ptr, b.idx[0].ptr, b.idx[1].ptr, (size_t) ncand, 0, 64, st));
+        SHQ_TRY(prim_sort_pairs(ctx, b.keys[0].ptr, b.keys[1].ptr, b.idx[0].ptr, b.idx[1].ptr, (size_t) ncand, 0, 64));
         tb_count_kernel<<<1, 1, 0, st>>>(b.keys[1].ptr, ncand, b.counters.ptr);
         SHQ_HIP(hipMemcpyAsync(&h_nvalid, b.counters.ptr, sizeof(h_nvalid), hipMemcpyDeviceToHost, st));
     }
@@ -872,20 +839,13 @@ static int tree_build_impl(shq_context *ctx, double BoxSize, int mask, const int
     /* 5. pre-order ranks and the walk pool */
     if(!dom) {
         tb_orderkey_kernel<<<dim3(nblk(nn)), dim3(256), 0, st>>>(nn, nd, b.okeys[0].ptr, b.order[0].ptr);
-        size_t tmp = 0;
-        SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, b.okeys[0].ptr, b.okeys[1].ptr, b.order[0].ptr, b.order[1].ptr, (size_t) nn, 0, 40, st));
-        SHQ_TRY(b.temp.reserve(tmp + 16));
-        SHQ_HIP(rocprim::radix_sort_pairs(b.temp.ptr, tmp, b.okeys[0].ptr, b.okeys[1].ptr, b.order[0].ptr, b.order[1].ptr, (size_t) nn, 0, 40, st));
+        SHQ_TRY(prim_sort_pairs(ctx, b.okeys[0].ptr, b.okeys[1].ptr, b.order[0].ptr, b.order[1].ptr, (size_t) nn, 0, 40));
         tb_rank_kernel<<<dim3(nblk(nn)), dim3(256), 0, st>>>(nn, b.order[1].ptr, b.rank.ptr);
     } else {
-        size_t tmp = 0, tmp2 = 0;
-        SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp, b.okeys[0].ptr, b.okeys[1].ptr, b.order[0].ptr, b.order[1].ptr, (size_t) nn, 0, 8, st));
-        SHQ_HIP(rocprim::radix_sort_pairs(nullptr, tmp2, b.okeys[0].ptr, b.okeys[1].ptr, b.order[0].ptr, b.order[1].ptr, (size_t) nn, 0, 64, st));
-        SHQ_TRY(b.temp.reserve(std::max(tmp, tmp2) + 16));
         tb_levelkey_kernel<<<dim3(nblk(nn)), dim3(256), 0, st>>>(nn, nd, b.okeys[0].ptr, b.order[0].ptr);
-        SHQ_HIP(rocprim::radix_sort_pairs(b.temp.ptr, tmp, b.okeys[0].ptr, b.okeys[1].ptr, b.order[0].ptr, b.order[1].ptr, (size_t) nn, 0, 8, st));
+        SHQ_TRY(prim_sort_pairs(ctx, b.okeys[0].ptr, b.okeys[1].ptr, b.order[0].ptr, b.order[1].ptr, (size_t) nn, 0, 8));
         tb_pathkey_kernel<<<dim3(nblk(nn)), dim3(256), 0, st>>>(nn, nd, b.order[1].ptr, b.okeys[0].ptr);
-        SHQ_HIP(rocprim::radix_sort_pairs(b.temp.ptr, tmp2, b.okeys[0].ptr, b.okeys[1].ptr, b.order[1].ptr, b.order[0].ptr, (size_t) nn, 0, 64, st));
+        SHQ_TRY(prim_sort_pairs(ctx, b.okeys[0].ptr, b.okeys[1].ptr, b.order[1].ptr, b.order[0].ptr, (size_t) nn, 0, 64));
         /* the pre-order is in order[0]; the rest of the file reads order[1] */
         SHQ_HIP(hipMemcpyAsync(b.order[1].ptr, b.order[0].ptr, sizeof(int32_t) * (size_t) nn, hipMemcpyDeviceToDevice, st));
         tb_rank_kernel<<<dim3(nblk(nn)), dim3(256), 0, st>>>(nn, b.order[1].ptr, b.rank.ptr);

@@ -228,6 +228,30 @@ def test_active_lists_equal_reference(ctx, Ti):
             assert np.array_equal(sq.active_download(ctx, sublist=True), rsub)
 
 
+def test_active_lists_across_sizes_one_context(ctx):
+    """The selections share one grow-only scratch buffer per context: small, large, small (and empty) particle sets in
+    one context make it grow in the middle and leave it oversized at the end.  Every list equals the reference's."""
+    Ti, maxbin = 1 << 22, 22
+    for n in (300, 70000, 300, 0):
+        pman, rng = _setup(n=n, seed=11 + n)
+        P = pman.Base
+        P["TimeBinGravity"] = rng.integers(18, 28, size=n).astype(np.uint8)
+        P["TimeBinHydro"] = rng.integers(16, 26, size=n).astype(np.uint8)
+        pv = pman.view()
+        capi.check(capi.hip.shq_particles_upload(ctx.h, C.byref(pv)))
+        sq.dynamics_upload(ctx, pman)
+        ract, rgrav, rhydro, rcounts = ref_active(P, Ti, False)
+        info = sq.build_active_particles(ctx, Ti, False)
+        assert info.NumActiveParticle == len(ract) and np.array_equal(sq.active_download(ctx), ract)
+        assert info.NumActiveGravity == rgrav and info.NumActiveHydro == rhydro
+        assert np.array_equal(np.array(info.TimeBinCountType[:]), rcounts)
+        bg = P["TimeBinGravity"][ract]
+        rsub = ract[(bg <= maxbin) & ref_timebin_active(bg, Ti)]
+        assert n == 0 or 0 < len(rsub) < len(ract) < n   # both selections drop something and keep something
+        assert sq.build_active_sublist(ctx, maxbin, Ti) == len(rsub)
+        assert np.array_equal(sq.active_download(ctx, sublist=True), rsub)
+
+
 def test_resident_active_list_drives_tree_walk_and_kick(ctx):
     """SHQ_ACTIVE_RESIDENT / SHQ_SUBLIST_RESIDENT as the `active` argument give the same tree, forces and
     velocities as the same list passed from the host."""
