@@ -2377,6 +2377,98 @@ typedef struct shq_startup_sml_stats {
 int shq_setup_smoothinglengths(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_bh_view *bh, const shq_startup_sml_params *params,
                                shq_startup_sml_stats *stats);
 
+/* ---- Run logs: energy statistics, black-hole totals and details (libgadget/stats.cpp:217-396, bhinfo.cpp:66-204; csrc/stats.hip) ---------
+ * The particle loops behind the run's log files, on device-resident records in the conventions of shq_io_* / shq_startup_*: records are
+ * opaque device bytes, fields are byte offsets, results arrive in host structs, the calls are synchronous.  Records and slots are read only.
+ *   compute_global_quantities_of_system's loop (stats.cpp:235-272)      shq_energy_statistics   device records
+ *   its rank-0 block (:289-361)                                         shq_stats_finish        host
+ *   write_blackhole_txt's loop (bhinfo.cpp:176-184)                     shq_bh_totals           device slots
+ *   collect_BH_info's loop (:76-151)                                    shq_bh_details          device records, slots and BHPriv arrays
+ * The all-reduce between the loops and the lines, and the files, stay with the caller. */
+typedef struct shq_stats_layout {
+    /* double Pos[3], float Mass, the Type byte, int32 PI, double Vel[3], double Potential: the rules of shq_startup_layout (8-byte aligned
+     * records of a multiple of 8 and at most 240 bytes, every member inside and aligned to its own size) */
+    size_t part_elsize, off_pos, off_mass, off_type, off_pi, off_vel, off_potential;
+    /* gas slot (a multiple of 8, at most 480 bytes): doubles Density, Entropy, Ne; local_J21 and zreion may be SHQ_NOFIELD */
+    size_t sph_elsize, sph_off_density, sph_off_entropy, sph_off_ne, sph_off_local_j21, sph_off_zreion;
+} shq_stats_layout;
+typedef struct shq_stats_params {
+    double Time;
+    int32_t want_temperature;          /* 0: no get_temp solves, TemperatureComp stays 0, no cooling tables needed */
+    int32_t uvbg_mode;                 /* SHQ_COOL_UVBG_*; the members below as in shq_cooling_step; redshift = 1 / Time - 1 */
+    shq_cooling_uvbg GlobalUVBG;
+    double CurrentParticleOffset[3];
+    double J21_coeffs[6];
+    double ss_greyopac_factor, ss_fbar_factor;
+} shq_stats_params;
+typedef struct shq_stats_sums {        /* the rank's raw sums, struct state_of_system's Comp members before MPI_Reduce */
+    double MassComp[6], EnergyPotComp[6], EnergyKinComp[6], EnergyIntComp[6];
+    double TemperatureComp[6];         /* sum of Mass * T, not yet divided */
+    double MomentumComp[6][4], AngMomentumComp[6][4], CenterOfMassComp[6][4];   /* column 3 is 0 */
+    int64_t count[6];                  /* particles by type */
+    int64_t n_bad_type;                /* Type > 5: the reference indexes past its arrays; here counted, adding nothing */
+    int64_t n_status[SHQ_COOL_NSTATUS]; /* temperature solves by outcome */
+    int64_t n_deferred;                /* entries the deferred list would hold: the solves that did not end SHQ_COOL_OK */
+    double kernel_ms;                  /* HIP-event time from the first kernel to the last */
+} shq_stats_sums;
+typedef struct shq_stats_state {       /* struct state_of_system, stats.h */
+    double Mass, EnergyKin, EnergyPot, EnergyInt, EnergyTot;
+    double Momentum[4], AngMomentum[4], CenterOfMass[4];
+    double MassComp[6], EnergyKinComp[6], EnergyPotComp[6], EnergyIntComp[6], EnergyTotComp[6], TemperatureComp[6];
+    double MomentumComp[6][4], AngMomentumComp[6][4], CenterOfMassComp[6][4];
+} shq_stats_state;
+/* stats.cpp:235-272 statement by statement, f64 without contraction: a1, a2, a3 = Time, Time * Time, Time * Time * Time; Mass widened from
+ * float; no garbage or swallowed test, as the reference has none.  For gas egyspec = Entropy / GAMMA_MINUS1 * pow(Density / a3,
+ * GAMMA_MINUS1) and T = get_temp(Density, egyspec, 1 - HYDROGEN_MASSFRAC, &uvbg, &ne): density and energy enter the rate network in
+ * internal units, as the reference passes them (the units of shq_cooling_set_tables are not applied); ne starts from the slot's Ne and
+ * is not written back; uvbg is get_local_UVBG as in shq_cooling (the Zreion table is that of shq_cooling_set_tables).  A solve that does
+ * not end SHQ_COOL_OK adds nothing to TemperatureComp[0], is counted in n_status, and its particle index goes to `deferred` (host,
+ * index order): the contract of the deferred lists; more than deferred_capacity of them is SHQ_ERR_NOMEM after everything else has been
+ * written.  The sums are reproducible: a wave adds each type its ballot holds in one butterfly, the wave sums are added in wave order,
+ * and a second kernel adds the block sums in a fixed order; no floating-point atomics.  One pass over the records (256-record tiles staged
+ * in LDS, as in shq_startup_particles); the temperature solves run in a second kernel over the list of gas particles.
+ * SHQ_ERR_STATE when temperatures are wanted without shq_cooling_set_tables, or in the Zreion mode without a Zreion table;
+ * SHQ_ERR_INVALID for a broken layout, the J21 mode with local_J21 or zreion SHQ_NOFIELD, or a gas PI outside [0, nsph) (tested on the
+ * device before the slot is read); in each case no output is touched. */
+int shq_energy_statistics(shq_context *ctx, const shq_stats_layout *layout, const void *d_parts, int64_t numpart, const void *d_sph, int64_t nsph,
+                          const shq_stats_params *params, shq_stats_sums *out, int32_t *deferred, int64_t deferred_capacity);
+/* Rank 0's block on sums the caller has added over the ranks, in the reference's expression order: EnergyTotComp, TemperatureComp /
+ * MassComp where MassComp > 0, the totals, the centres of mass divided by their mass, the [3] norms.  No GPU. */
+int shq_stats_finish(const shq_stats_sums *summed, shq_stats_state *out);
+
+/* write_blackhole_txt's loop over the nbh black-hole slots at d_bh (bh_elsize bytes each, a multiple of 8, at most 480; uint64 SwallowID,
+ * doubles Mass and Mdot): the slots with SwallowID == (uint64) -1 add to *num and to sums[] = { Mass, Mdot, Mdot / Mass }.  Reproducible
+ * as above. */
+int shq_bh_totals(shq_context *ctx, const void *d_bh, int64_t nbh, size_t bh_elsize, size_t off_swallowid, size_t off_mass, size_t off_mdot, int64_t *num,
+                  double sums[3]);
+
+#define SHQ_BHINFO_SIZE 436   /* sizeof(struct BHinfo), packed, MyFloat a double; size1 = size2 = 428 */
+typedef struct shq_bh_detail_layout {
+    /* particle record: double Pos[3], float Mass, the flag byte (bit 1 Swallowed), the Type byte, int32 PI, double Vel[3],
+     * double FullTreeGravAccel[3], uint64 ID */
+    size_t part_elsize, off_pos, off_mass, off_flags, off_type, off_pi, off_vel, off_fulltreegravaccel, off_id;
+    /* black-hole slot: doubles Mass, Mdot, Density, Mtrack, KineticFdbkEnergy, VDisp, DFAccel[3], DF_SurroundingVel[3], DF_SurroundingRmsVel,
+     * DF_SurroundingDensity, DragAccel[3], MinPot, MinPotPos[3]; unsigned char minTimeBin, char encounter, uint64 SwallowID, int32 CountProgs */
+    size_t bh_elsize, bh_off_mintimebin, bh_off_encounter, bh_off_mass, bh_off_mdot, bh_off_density, bh_off_mtrack, bh_off_kineticfdbkenergy, bh_off_vdisp,
+        bh_off_dfaccel, bh_off_df_surroundingvel, bh_off_df_surroundingrmsvel, bh_off_df_surroundingdensity, bh_off_dragaccel, bh_off_swallowid, bh_off_minpot,
+        bh_off_minpotpos, bh_off_countprogs;
+} shq_bh_detail_layout;
+typedef struct shq_bh_detail_arrays {   /* struct BHPriv's arrays, device memory, by black-hole slot; a NULL array leaves its members zero */
+    const double *BH_Entropy, *BH_SurroundingGasVel /* [][3] */, *BH_accreted_momentum /* [][3] */, *BH_accreted_Mass, *BH_accreted_BHMass,
+        *BH_FeedbackWeightSum, *NumDM, *MgasEnc;
+    const int32_t *KEflag;
+    const uint64_t *SPH_SwallowID;      /* indexed by the black hole's own PI, as the reference does */
+    int64_t n_sph_swallowid;            /* its length (the reference sizes it by the gas slots); the other arrays hold nbh entries */
+    double CurrentParticleOffset[3];    /* subtracted from Pos and MinPotPos */
+} shq_bh_detail_arrays;
+/* collect_BH_info's loop: d_out (device) receives nactive records of SHQ_BHINFO_SIZE bytes in the reference's packed format, record k for
+ * particle d_active[k] (device; NULL: particle k).  BH_SurroundingParticles and V1sumDM stay zero.  A record is composed as 109 32-bit
+ * words and stored word by word.  SHQ_ERR_INVALID, tested on the device before the dependent read, the output then unspecified: an
+ * active index outside [0, numpart) (the reference's test lets numpart through), a Type other than 5, a PI outside [0, nbh) or, with
+ * SPH_SwallowID given, outside [0, n_sph_swallowid). */
+int shq_bh_details(shq_context *ctx, const shq_bh_detail_layout *layout, const void *d_parts, int64_t numpart, const void *d_bh, int64_t nbh,
+                   const shq_bh_detail_arrays *arrays, const int32_t *d_active, int64_t nactive, double atime, void *d_out);
+
 #ifdef __cplusplus
 }
 #endif

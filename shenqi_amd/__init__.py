@@ -1054,3 +1054,7 @@ from .capi import LIGHTCONE_CONSISTENT, LIGHTCONE_AS_WRITTEN, LIGHTCONE_MAXREPLI
 from .startup import (StartupError, StartupReport, SmlStats, startup_layout, startup_params, startup_particles, check_density_entropy,  # noqa: E402,F401
                       set_init_hsml_device, init_entropy, setup_smoothinglengths, mean_separation, u_init, check_omega, meanbar)
 from .capi import STARTUP_OMEGA, STARTUP_POSITIONS, STARTUP_HSML, STARTUP_INIT, STARTUP_ALL  # noqa: E402,F401
+
+# ---- run logs: energy statistics, black-hole totals and details, the log lines (csrc/stats.hip; stats.py) ----------
+from .stats import (BHINFO_DTYPE, stats_layout, stats_params, energy_statistics, stats_finish, bh_totals, bh_detail_layout, bh_detail_arrays,  # noqa: E402,F401
+                    bh_details, energy_line, blackholes_line, sfr_line)

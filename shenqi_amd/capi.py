@@ -1302,3 +1302,62 @@ hip.shq_setup_smoothinglengths.argtypes = [_vp, C.POINTER(PartView), C.POINTER(S
 for _f in ("shq_startup_mean_separation", "shq_startup_u_init", "shq_startup_omega", "shq_startup_meanbar", "shq_startup_particles",
            "shq_startup_check_density_entropy", "shq_set_init_hsml", "shq_init_entropy", "shq_setup_smoothinglengths"):
     getattr(hip, _f).restype = C.c_int
+
+# ---- run logs (csrc/stats.hip) -------------------------------------------------------------------
+BHINFO_SIZE = 436
+
+
+class StatsLayout(C.Structure):
+    """shq_stats_layout"""
+    _fields_ = [(k, C.c_size_t) for k in (
+        "part_elsize", "off_pos", "off_mass", "off_type", "off_pi", "off_vel", "off_potential",
+        "sph_elsize", "sph_off_density", "sph_off_entropy", "sph_off_ne", "sph_off_local_j21", "sph_off_zreion")]
+
+
+class StatsParams(C.Structure):
+    """shq_stats_params"""
+    _fields_ = [("Time", C.c_double), ("want_temperature", C.c_int32), ("uvbg_mode", C.c_int32), ("GlobalUVBG", CoolingUVBG),
+                ("CurrentParticleOffset", C.c_double * 3), ("J21_coeffs", C.c_double * 6), ("ss_greyopac_factor", C.c_double), ("ss_fbar_factor", C.c_double)]
+
+
+class StatsSums(C.Structure):
+    """shq_stats_sums"""
+    _fields_ = [("MassComp", C.c_double * 6), ("EnergyPotComp", C.c_double * 6), ("EnergyKinComp", C.c_double * 6), ("EnergyIntComp", C.c_double * 6),
+                ("TemperatureComp", C.c_double * 6), ("MomentumComp", C.c_double * 4 * 6), ("AngMomentumComp", C.c_double * 4 * 6),
+                ("CenterOfMassComp", C.c_double * 4 * 6), ("count", C.c_int64 * 6), ("n_bad_type", C.c_int64), ("n_status", C.c_int64 * 4),
+                ("n_deferred", C.c_int64), ("kernel_ms", C.c_double)]
+
+
+class StatsState(C.Structure):
+    """shq_stats_state (struct state_of_system)"""
+    _fields_ = [("Mass", C.c_double), ("EnergyKin", C.c_double), ("EnergyPot", C.c_double), ("EnergyInt", C.c_double), ("EnergyTot", C.c_double),
+                ("Momentum", C.c_double * 4), ("AngMomentum", C.c_double * 4), ("CenterOfMass", C.c_double * 4),
+                ("MassComp", C.c_double * 6), ("EnergyKinComp", C.c_double * 6), ("EnergyPotComp", C.c_double * 6), ("EnergyIntComp", C.c_double * 6),
+                ("EnergyTotComp", C.c_double * 6), ("TemperatureComp", C.c_double * 6), ("MomentumComp", C.c_double * 4 * 6),
+                ("AngMomentumComp", C.c_double * 4 * 6), ("CenterOfMassComp", C.c_double * 4 * 6)]
+
+
+class BhDetailLayout(C.Structure):
+    """shq_bh_detail_layout"""
+    _fields_ = [(k, C.c_size_t) for k in (
+        "part_elsize", "off_pos", "off_mass", "off_flags", "off_type", "off_pi", "off_vel", "off_fulltreegravaccel", "off_id",
+        "bh_elsize", "bh_off_mintimebin", "bh_off_encounter", "bh_off_mass", "bh_off_mdot", "bh_off_density", "bh_off_mtrack", "bh_off_kineticfdbkenergy",
+        "bh_off_vdisp", "bh_off_dfaccel", "bh_off_df_surroundingvel", "bh_off_df_surroundingrmsvel", "bh_off_df_surroundingdensity", "bh_off_dragaccel",
+        "bh_off_swallowid", "bh_off_minpot", "bh_off_minpotpos", "bh_off_countprogs")]
+
+
+BH_DETAIL_ARRAYS = ("BH_Entropy", "BH_SurroundingGasVel", "BH_accreted_momentum", "BH_accreted_Mass", "BH_accreted_BHMass", "BH_FeedbackWeightSum", "NumDM",
+                    "MgasEnc", "KEflag", "SPH_SwallowID")
+
+
+class BhDetailArrays(C.Structure):
+    """shq_bh_detail_arrays"""
+    _fields_ = [(k, _vp) for k in BH_DETAIL_ARRAYS] + [("n_sph_swallowid", C.c_int64), ("CurrentParticleOffset", C.c_double * 3)]
+
+
+hip.shq_energy_statistics.argtypes = [_vp, C.POINTER(StatsLayout), _vp, C.c_int64, _vp, C.c_int64, C.POINTER(StatsParams), C.POINTER(StatsSums), _vp, C.c_int64]
+hip.shq_stats_finish.argtypes = [C.POINTER(StatsSums), C.POINTER(StatsState)]
+hip.shq_bh_totals.argtypes = [_vp, _vp, C.c_int64, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_int64), _dp]
+hip.shq_bh_details.argtypes = [_vp, C.POINTER(BhDetailLayout), _vp, C.c_int64, _vp, C.c_int64, C.POINTER(BhDetailArrays), _vp, C.c_int64, C.c_double, _vp]
+for _f in ("shq_energy_statistics", "shq_stats_finish", "shq_bh_totals", "shq_bh_details"):
+    getattr(hip, _f).restype = C.c_int

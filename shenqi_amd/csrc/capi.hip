@@ -248,6 +248,7 @@ extern "C" void shq_shutdown(shq_context *ctx)
     ctx->gravtab.release(); ctx->stage.release();
     ctx->node_hmax.release(); ctx->pfather.release(); ctx->node_father.release();
     ctx->st_cnt.release(); ctx->st_part.release(); ctx->st_old.release(); ctx->st_i32.release();
+    ctx->stat_cnt.release(); ctx->stat_part.release(); ctx->stat_mark.release(); ctx->stat_list.release(); ctx->stat_pos.release();
     ctx->hsml.release(); ctx->dthsml.release(); ctx->vel.release(); ctx->bin_grav.release(); ctx->bin_hydro.release();
     ctx->g_entropy.release(); ctx->g_dtentropy.release(); ctx->g_hydroaccel.release(); ctx->g_delaytime.release();
     ctx->g_density.release(); ctx->g_egywt.release(); ctx->g_dhsmlegy.release(); ctx->g_divvel.release(); ctx->g_curlvel.release();

@@ -400,6 +400,12 @@ struct shq_context {
     DevBuf<long long> st_cnt;
     DevBuf<double> st_part, st_old;
     DevBuf<int32_t> st_i32;
+    /* run logs (stats.hip): integer counters, block partial sums, and for the temperature solves the gas marks, the gas list and the
+     * list positions of the solves that did not end OK */
+    DevBuf<unsigned long long> stat_cnt;
+    DevBuf<double> stat_part;
+    DevBuf<uint8_t> stat_mark;
+    DevBuf<int32_t> stat_list, stat_pos;
     /* light-cone crossings (lightcone.hip) */
     DevBuf<double> lc_reps;              /* the state's replica shifts, [Nreplica][3] */
     DevBuf<int32_t> lc_cnt;              /* crossings per particle, one zero behind the last; then the first two replicas of each */

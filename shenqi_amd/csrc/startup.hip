@@ -6,7 +6,7 @@
  *   the entropy of setup_smoothinglengths / setup_density_indep_entropy      init.cpp:422-423, 518                         shq_init_entropy
  *   setup_smoothinglengths                                                   init.cpp:402-521                              shq_setup_smoothinglengths
  *
- * The record pass.  A workgroup of ST_TILE threads owns ST_TILE consecutive particle records.  It copies them into LDS with 16-byte
+ * The record pass (the tile copies are in record_tile.hpp).  A workgroup of ST_TILE threads owns ST_TILE consecutive particle records.  It copies them into LDS with 16-byte
  * loads, consecutive lanes on consecutive pieces (the records are contiguous, so this is a stream), ST_BATCH loads in flight per lane
  * as in snapshot.hip's gather; lane k then runs every selected loop on record k in LDS, and if a loop changed a member the tile is
  * streamed back the same way.  The LDS row pitch is the record size rounded up to an odd number of 8-byte words (160 -> 168), as in
@@ -14,16 +14,13 @@
  * The mass sums: a butterfly over the wave (the same shape for every wave), the four wave sums added in wave order, one partial per
  * workgroup; a second kernel adds the partials in a fixed order.  No floating-point atomics, so equal inputs give equal bytes. */
 #include "common.hpp"
+#include "record_tile.hpp"
 #include <math.h>
 #include <string.h>
 #include <algorithm>
 
 namespace {
 
-constexpr int ST_TILE = 256;
-constexpr int ST_BATCH = 5;
-constexpr size_t ST_MAXREC = 480;  /* slot records */
-constexpr size_t ST_MAXPART = 240; /* particle records: ST_TILE * (240 + 8) bytes of LDS stay below the 64 KiB a launch gets without asking */
 constexpr int ST_MAXCLIMB = 64; /* a father chain longer than this is no tree (the deepest cell is Box / 2^21 wide) */
 /* GAMMA_MINUS1 as the reference forms it (physconst.h:35-36) */
 #define ST_GAMMA_MINUS1 ((5.0 / 3.0) - 1)
@@ -33,59 +30,11 @@ enum { C_BADMASS = 0, C_NOUTSIDE, C_NUMZERO, C_NUMPROB, C_NBADDELAY, C_FIRST_OUT
        C_BADCHAIN, C_BADDENS, C_MAXDIFF, C_N };
 constexpr unsigned long long ST_NONE = ~0ull;
 
-inline size_t st_pitch(size_t elsize) { return ((elsize / 8) & 1) ? elsize : elsize + 8; }
-
 __global__ void st_reset_kernel(unsigned long long *cnt)
 {
     const int k = threadIdx.x;
     if(k < C_N)
         cnt[k] = (k == C_FIRST_OUTSIDE || k == C_FIRST_BADDELAY) ? ST_NONE : 0ull; /* the two "highest index" cells hold index + 1 */
-}
-
-/* rows [0, nrow) of the tile at g (contiguous records of R bytes) into LDS rows of `pitch` bytes, CH bytes per lane and step */
-template <int CH> __device__ __forceinline__ void st_stage_in(char *lds, unsigned pitch, const char *__restrict__ g, unsigned R, int nrow)
-{
-    const unsigned P = R / CH, total = (unsigned) nrow * P;
-    for(unsigned t0 = threadIdx.x; t0 < total; t0 += ST_TILE * ST_BATCH) {
-        uint4 v[ST_BATCH];
-        unsigned dst[ST_BATCH];
-#pragma unroll
-        for(int u = 0; u < ST_BATCH; u++) {
-            const unsigned t = t0 + (unsigned) u * ST_TILE;
-            const bool in = t < total;
-            const char *src = g + (size_t) (in ? t : 0u) * CH; /* piece 0 of the tile is always there */
-            const unsigned rec = t / P;
-            dst[u] = in ? rec * pitch + (t - rec * P) * CH : ~0u;
-            if(CH == 16)
-                v[u] = *reinterpret_cast<const uint4 *>(src);
-            else {
-                const uint2 w = *reinterpret_cast<const uint2 *>(src);
-                v[u] = make_uint4(w.x, w.y, 0u, 0u);
-            }
-        }
-#pragma unroll
-        for(int u = 0; u < ST_BATCH; u++)
-            if(dst[u] != ~0u) {
-                uint2 *l = reinterpret_cast<uint2 *>(lds + dst[u]); /* the pitch keeps 8-byte alignment only */
-                l[0] = make_uint2(v[u].x, v[u].y);
-                if(CH == 16)
-                    l[1] = make_uint2(v[u].z, v[u].w);
-            }
-    }
-}
-
-template <int CH> __device__ __forceinline__ void st_stage_out(const char *lds, unsigned pitch, char *__restrict__ g, unsigned R, int nrow)
-{
-    const unsigned P = R / CH, total = (unsigned) nrow * P;
-    for(unsigned t = threadIdx.x; t < total; t += ST_TILE) {
-        const unsigned rec = t / P;
-        const uint2 *l = reinterpret_cast<const uint2 *>(lds + rec * pitch + (t - rec * P) * CH);
-        if(CH == 16) {
-            const uint2 a = l[0], b = l[1];
-            *reinterpret_cast<uint4 *>(g + (size_t) t * CH) = make_uint4(a.x, a.y, b.x, b.y);
-        } else
-            *reinterpret_cast<uint2 *>(g + (size_t) t * CH) = l[0];
-    }
 }
 
 __device__ __forceinline__ double st_pick6(const double a[6], int t)
