@@ -6,7 +6,7 @@ LIBDIR := shenqi_amd/lib
 HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wall -Wno-unused-result -Iinclude
 # longest compile first: make -j starts the jobs in this order, and the build is as long as its last job (fft3d.hip alone takes about as
 # long as a quarter of all the others together)
-HIPSRC := $(addprefix $(CSRC)/,$(addsuffix .hip,fft3d exchange fof tree_build sph_winds sph grav_walk heiii toptree dynamics sph_bh sph_ngbsums sph_capi capi uvbg grav_group lens zeldovich glass thermal timestep pm sph_resident yields cooling cooling_host sfr sfr_host domain snapshot lightcone startup stats))
+HIPSRC := $(addprefix $(CSRC)/,$(addsuffix .hip,fft3d exchange fof tree_build sph_winds sph grav_walk heiii toptree dynamics sph_bh sph_ngbsums sph_capi capi uvbg grav_group lens zeldovich glass thermal timestep pm sph_resident yields cooling cooling_host sfr sfr_host domain snapshot lightcone startup stats nulra nulra_host))
 HIPOBJ := $(patsubst $(CSRC)/%.hip,$(LIBDIR)/%.o,$(HIPSRC))
 
 all: $(LIBDIR)/libshenqi_hip.so host oracle

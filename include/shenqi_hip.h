@@ -1407,6 +1407,99 @@ int shq_pm_set_mesh_scrub(shq_context *ctx, int enable);
 int shq_pm_mesh_prezeroed(shq_context *ctx, int *zeroed);
 int shq_pm_download_mesh(shq_context *ctx, int which /*0 density,1 potential*/, double *mesh);
 
+/* ---- linear-response massive neutrinos (libgadget/neutrinos_lra.cpp) ----------------------------
+ * compute_neutrino_power (gravpm.cpp:308-321: powerspectrum_sum, the square root, delta_nu_from_power) and potential_transfer's nufac
+ * table on the device, between shq_pm_forward and the finish.  The state of init_neutrinos_lra is resident: delta_tot[nk][namax],
+ * delta_nu_last, delta_nu_init and wavenum live on the device; the host keeps ia, nk and scalefact, which decide every branch.
+ * The cosmology stays with the caller: three host callbacks f(a, mi, user) - hubble_function(a), get_omega_nu_nopart(a) and
+ * omega_nu_single(a, mi) (mi is 0 for the first two) - called at arguments that do not depend on k, about 10^4 times per step.
+ * particle_nu_fraction is closed form from the hybrid parameters below.
+ *
+ * The time integral of get_delta_nu (:717-725) is not the reference's adaptive rule but a k-independent graded one (csrc/nulra_math.hpp):
+ * 8 Gauss-Legendre points per panel, the panels the merged knots of the fs spline and of the history, split so that log(a) - l halves
+ * at most per panel, 30 levels into the last interval.  It agrees with a converged sum to a few 1e-11 relative; the reference's rule is
+ * run at sqrt(epsilon) = 1.49e-8, so two faithful implementations may differ by that.  While hybrid particle neutrinos gravitate,
+ * specialJ is the truncated series, which oscillates as cos(vcrit k fs): the panels are then cut until none spans more than two radians
+ * of the largest k's phase, and a step that would need more than 2^20 nodes for that returns SHQ_ERR_INVALID (k and light must be in the
+ * same length unit; the reference's rule, at most 2^15 x 61 points, cannot resolve such a phase either).  Three readings of boost are taken without a boost
+ * build to check them against:
+ *  - makima as stated for the thermal velocities below; Na < 4 history knots use barycentric_rational of order Na - 1, which is the
+ *    interpolating polynomial through them;
+ *  - gauss_kronrod<double, 61>::integrate defaults to max depth 15 and tolerance sqrt(epsilon);
+ *  - boost's splines throw outside their knots.  Here a log k outside the knots of the final spline (and of the rebinning back) takes
+ *    the end knot's value - the rule of plane_neutrino_correction_transfer - and a history knot range that does not reach
+ *    log(TimeTransfer) continues its end cubic.
+ * The sums of a step are reduced in a fixed order without floating-point atomics: two runs from the same sums give the same bits. */
+#define SHQ_NULRA_NUSPECIES 3
+typedef double (*shq_nulra_cosmo_fn)(double a, int mi, void *user);
+typedef struct shq_nulra_params {
+    int32_t nk_allocated;       /* init_neutrinos_lra's nk_in: at least the number of non-empty P(k) bins */
+    int32_t hybrid_enabled;     /* hybnu.enabled */
+    double TimeTransfer, TimeMax; /* namax = ceil((TimeMax - TimeTransfer) / 0.008) + 4 */
+    double light, delta_nu_prefac, Omeganonu, OmegaNu1, kBtnu; /* d_tot's fields; OmegaNu1 = get_omega_nu(omnu, 1) */
+    double mnu[SHQ_NULRA_NUSPECIES];        /* RhoNuTab[mi].mnu, eV */
+    double degeneracy[SHQ_NULRA_NUSPECIES]; /* nu_degeneracies[mi]; a species with 0 is left out */
+    double vcrit_by_light, nu_crit_time, nufrac_low[SHQ_NULRA_NUSPECIES]; /* hybnu.vcrit (already divided by light), .nu_crit_time, .nufrac_low */
+    double BoxSize_in_MPC;      /* ps->BoxSize_in_MPC */
+    int32_t NPowerTable, pad_;  /* the IC transfer table (petaio_read_icnutransfer): logk is log10 k, T_nu = DELTA_NU / DELTA_CB; >= 4 rows, copied */
+    const double *logk, *T_nu;
+    shq_nulra_cosmo_fn hubble, omega_nu_nopart, omega_nu_single;
+    void *user;
+} shq_nulra_params;
+/* the block petaio_save_neutrinos writes (:267-314): scalefact[ia], delta_tot flat [nk][ia], delta_nu_init[nk], kvalue[nk].
+ * delta_nu_last[nk] is this library's addition: with it a restored state continues bit for bit; without it (NULL in set_state, a
+ * snapshot of the reference) the first step recomputes it from the history, as the reference does after petaio_read_neutrinos. */
+typedef struct shq_nulra_state {
+    int32_t ia, nk;
+    double *scalefact, *delta_tot, *delta_nu_init, *kvalue, *delta_nu_last;
+} shq_nulra_state;
+typedef struct shq_nulra_info {
+    int32_t ia, nk, nonzero, namax;
+    int32_t kept;             /* the last step: 1 its spectrum was saved, 0 discarded (the 0.009 rule), -1 no update */
+    int32_t nnodes;           /* quadrature nodes of the last get_delta_nu */
+    double nu_prefac;
+    double ms[3];             /* device time of the last step: node table upload, delta_nu kernels, mode table */
+    double callback_s;        /* host time of the last step's node tables, the callbacks in it */
+} shq_nulra_info;
+/*   shq_nulra_init       : allocates the state (replacing an earlier one).  The callbacks and `user` must stay valid until shq_nulra_free.
+ *   shq_nulra_step       : one delta_nu_from_power at `Time`.  sums == NULL reads the context's own raw P(k) sums, which shq_pm_forward
+ *                          just took (nbins is ignored; needs a pending spectrum, SHQ_ERR_STATE otherwise).  Otherwise sums is a DEVICE
+ *                          pointer to reduced sums in the layout [nbins] power, [nbins] kk, [nbins] modes (uint64), norm - the caller's
+ *                          all-reduce of what shq_pm_download_power returns per rank (a host pointer is taken too: uploaded, and the
+ *                          step waits for that copy).  The set of non-empty bins is found once per nbins
+ *                          (one download); the first call and the first step after shq_nulra_set_state also wait for the device; every
+ *                          other step queues its work behind the forward and returns.  With a spectrum pending the step then fills
+ *                          the context's mode-factor table, T[k2] = 1 + nu_prefac spline(log(sqrt(k2) 2 pi / BoxSize_in_MPC)), under the
+ *                          rules of shq_pm_set_mode_factor (the finish consumes it; a pending spectrum of an Nmesh other than nbins is
+ *                          SHQ_ERR_INVALID).  A second step at the same Time changes no history but refreshes nu_prefac and the table.
+ *                          Before shq_nulra_init: SHQ_ERR_STATE.
+ *   shq_nulra_mode_table : the table of the last step for any even Nmesh, 3 (Nmesh/2)^2 + 1 doubles to the host; add_one = 0 gives
+ *                          nu_prefac * spline alone (the lensing planes', plane.cpp:326-341).  Entry 0 is add_one.
+ *   shq_nulra_download   : delta_nu_last[nk], kk[nonzero] (either may be NULL) and the info of the last step.
+ *   shq_nulra_delta_nu   : get_delta_nu_combined at scale factor a over the stored history, to the host; changes nothing.
+ *   shq_nulra_get_state  : with every pointer NULL fills ia and nk only; otherwise copies the block.  shq_nulra_set_state replaces the
+ *                          state; nk > nk_allocated or ia > namax (petaio_read_neutrinos' endrun(5), :404) is SHQ_ERR_INVALID.
+ * A NaN in delta_nu_last (endrun(2004), :215) sets a sticky device status: the nulra entry points that follow return SHQ_ERR_DEVICE
+ * until shq_nulra_init; the step that produced it may itself still return SHQ_OK, as it does not wait for the device.
+ * shq_nulra_host_* is the same engine on the host (csrc/nulra_host.hip: no device, no context); there sums is a host pointer. */
+int shq_nulra_init(shq_context *ctx, const shq_nulra_params *params);
+int shq_nulra_free(shq_context *ctx);
+int shq_nulra_step(shq_context *ctx, double Time, double TimeIC, const void *d_sums, int nbins);
+int shq_nulra_mode_table(shq_context *ctx, int Nmesh, int add_one, double *table);
+int shq_nulra_download(shq_context *ctx, double *delta_nu_last, double *kk, shq_nulra_info *info);
+int shq_nulra_delta_nu(shq_context *ctx, double a, double *delta_nu);
+int shq_nulra_get_state(shq_context *ctx, shq_nulra_state *state);
+int shq_nulra_set_state(shq_context *ctx, const shq_nulra_state *state);
+typedef struct shq_nulra_host shq_nulra_host;
+int shq_nulra_host_create(const shq_nulra_params *params, shq_nulra_host **out);
+void shq_nulra_host_destroy(shq_nulra_host *h);
+int shq_nulra_host_step(shq_nulra_host *h, double Time, double TimeIC, const void *sums, int nbins);
+int shq_nulra_host_mode_table(shq_nulra_host *h, int Nmesh, int add_one, double *table);
+int shq_nulra_host_download(shq_nulra_host *h, double *delta_nu_last, double *kk, shq_nulra_info *info);
+int shq_nulra_host_delta_nu(shq_nulra_host *h, double a, double *delta_nu);
+int shq_nulra_host_get_state(shq_nulra_host *h, shq_nulra_state *state);
+int shq_nulra_host_set_state(shq_nulra_host *h, const shq_nulra_state *state);
+
 /* ---- slab-sharded PM for multi-GPU runs (one rank per GPU, x-slabs of the mesh) ------------------
  * The mesh is split into slabs of x-planes exactly as petapm splits its real-space pencils over
  * np0 (petapm.cpp:243-257, here np1 = 1).  These are the LOCAL phases on device buffers the

@@ -337,6 +337,7 @@ def grav_short_tree(ctx, act, pm, tree, AccelStore, rho0, Ti_Current=0, UseGPU=T
 def gravpm_force(ctx, pm, pman, UseGPU=True, analysis=None, deposit_types=capi.ALL_TYPES):
     """analysis(kk, power, nmodes, Norm) -> T: the hook between the PM's forward and inverse halves (petapm's global_analysis,
     compute_neutrino_power for MassiveNuLinRespOn); it gets the raw P(k) sums of the density and returns T[k2] for k2 = 0 .. 3 (Nmesh/2)^2.
+    A NuLRA with its times set (nu.at(Time, TimeIC)) is such a hook: the resident linear-response state steps on the sums.
     deposit_types: the deposit's type mask (bit t = Type t)."""
     if analysis is None and deposit_types == capi.ALL_TYPES:
         capi.check_host(capi.host.shqh_gravpm_force(ctx.h, pman._h, pm["Asmth"], pm["Nmesh"], pm["G"], int(UseGPU)), "gravpm_force")
@@ -1058,3 +1059,6 @@ from .capi import STARTUP_OMEGA, STARTUP_POSITIONS, STARTUP_HSML, STARTUP_INIT, 
 # ---- run logs: energy statistics, black-hole totals and details, the log lines (csrc/stats.hip; stats.py) ----------
 from .stats import (BHINFO_DTYPE, stats_layout, stats_params, energy_statistics, stats_finish, bh_totals, bh_detail_layout, bh_detail_arrays,  # noqa: E402,F401
                     bh_details, energy_line, blackholes_line, sfr_line)
+
+# ---- linear-response massive neutrinos: resident state, delta_nu from the PM's P(k), the mode table (csrc/nulra.hip; nulra.py) ----------
+from .nulra import NuLRA, pack_sums  # noqa: E402,F401

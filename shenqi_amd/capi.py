@@ -1361,3 +1361,45 @@ hip.shq_bh_totals.argtypes = [_vp, _vp, C.c_int64, C.c_size_t, C.c_size_t, C.c_s
 hip.shq_bh_details.argtypes = [_vp, C.POINTER(BhDetailLayout), _vp, C.c_int64, _vp, C.c_int64, C.POINTER(BhDetailArrays), _vp, C.c_int64, C.c_double, _vp]
 for _f in ("shq_energy_statistics", "shq_stats_finish", "shq_bh_totals", "shq_bh_details"):
     getattr(hip, _f).restype = C.c_int
+
+# ---- linear-response massive neutrinos (csrc/nulra.hip, csrc/nulra_host.hip) ---------------------
+NULRA_COSMO_FN = C.CFUNCTYPE(C.c_double, C.c_double, C.c_int, C.c_void_p)
+
+
+class NulraParams(C.Structure):
+    """shq_nulra_params"""
+    _fields_ = [("nk_allocated", C.c_int32), ("hybrid_enabled", C.c_int32), ("TimeTransfer", C.c_double), ("TimeMax", C.c_double),
+                ("light", C.c_double), ("delta_nu_prefac", C.c_double), ("Omeganonu", C.c_double), ("OmegaNu1", C.c_double), ("kBtnu", C.c_double),
+                ("mnu", C.c_double * 3), ("degeneracy", C.c_double * 3), ("vcrit_by_light", C.c_double), ("nu_crit_time", C.c_double),
+                ("nufrac_low", C.c_double * 3), ("BoxSize_in_MPC", C.c_double), ("NPowerTable", C.c_int32), ("pad_", C.c_int32),
+                ("logk", _vp), ("T_nu", _vp), ("hubble", NULRA_COSMO_FN), ("omega_nu_nopart", NULRA_COSMO_FN), ("omega_nu_single", NULRA_COSMO_FN),
+                ("user", C.c_void_p)]
+
+
+class NulraState(C.Structure):
+    """shq_nulra_state"""
+    _fields_ = [("ia", C.c_int32), ("nk", C.c_int32), ("scalefact", _vp), ("delta_tot", _vp), ("delta_nu_init", _vp), ("kvalue", _vp), ("delta_nu_last", _vp)]
+
+
+class NulraInfo(C.Structure):
+    """shq_nulra_info"""
+    _fields_ = [("ia", C.c_int32), ("nk", C.c_int32), ("nonzero", C.c_int32), ("namax", C.c_int32), ("kept", C.c_int32), ("nnodes", C.c_int32),
+                ("nu_prefac", C.c_double), ("ms", C.c_double * 3), ("callback_s", C.c_double)]
+
+
+hip.shq_nulra_init.argtypes = [_vp, C.POINTER(NulraParams)]
+hip.shq_nulra_free.argtypes = [_vp]
+hip.shq_nulra_host_create.argtypes = [C.POINTER(NulraParams), C.POINTER(C.c_void_p)]
+hip.shq_nulra_host_destroy.argtypes = [_vp]
+hip.shq_nulra_host_destroy.restype = None
+for _p in ("shq_nulra_", "shq_nulra_host_"):
+    getattr(hip, _p + "step").argtypes = [_vp, C.c_double, C.c_double, _vp, C.c_int]
+    getattr(hip, _p + "mode_table").argtypes = [_vp, C.c_int, C.c_int, _vp]
+    getattr(hip, _p + "download").argtypes = [_vp, _vp, _vp, C.POINTER(NulraInfo)]
+    getattr(hip, _p + "delta_nu").argtypes = [_vp, C.c_double, _vp]
+    getattr(hip, _p + "get_state").argtypes = [_vp, C.POINTER(NulraState)]
+    getattr(hip, _p + "set_state").argtypes = [_vp, C.POINTER(NulraState)]
+    for _f in ("step", "mode_table", "download", "delta_nu", "get_state", "set_state"):
+        getattr(hip, _p + _f).restype = C.c_int
+for _f in ("shq_nulra_init", "shq_nulra_free", "shq_nulra_host_create"):
+    getattr(hip, _f).restype = C.c_int

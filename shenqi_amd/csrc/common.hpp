@@ -564,6 +564,8 @@ struct shq_context {
     double cool_ms = 0;                   /* shq_cooling_last_kernel */
     int64_t cool_steps = 0;
     /* ---- star formation (sfr.hip): works on the cooling tables and per-call arrays above */
+    /* ---- linear-response massive neutrinos (nulra.hip): the resident state of shq_nulra_init, owned by that file */
+    struct NuLraDev *nulra = nullptr;
     int sfr_refill = 1;                   /* shq_sfr_set_refill */
     double sfr_ms = 0;                    /* shq_sfr_last_kernel */
     int64_t sfr_steps = 0;

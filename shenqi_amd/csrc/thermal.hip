@@ -20,6 +20,7 @@
  * The call owns every buffer it uses and changes nothing of the context but its phase times.
  */
 #include "call_scope.hpp"
+#include "makima.hpp" /* makima_slopes */
 #include <math.h>
 #include <string.h>
 #include <random>
@@ -195,26 +196,6 @@ __global__ __launch_bounds__(TW) void thermal_speeds_kernel(int N, int ncol, dou
             vel[((size_t) (cbase + col) * N + z0) * 3 + e] = tile[col][e];
         }
         __syncthreads();
-    }
-}
-
-/* the modified Akima slopes at the n knots (x, y): secants m, two ghost secants on each side */
-void makima_slopes(int n, const double *x, const double *y, double *s)
-{
-#pragma clang fp contract(off)
-    std::vector<double> mm((size_t) n + 3); /* mm[i + 2] = m[i], i = -2 .. n */
-    double *m = mm.data() + 2;
-    for(int i = 0; i < n - 1; i++)
-        m[i] = (y[i + 1] - y[i]) / (x[i + 1] - x[i]);
-    m[-1] = 2 * m[0] - m[1];
-    m[-2] = 2 * m[-1] - m[0];
-    m[n - 1] = 2 * m[n - 2] - m[n - 3];
-    m[n] = 2 * m[n - 1] - m[n - 2];
-    for(int i = 0; i < n; i++) {
-        const double w1 = fabs(m[i + 1] - m[i]) + fabs(m[i + 1] + m[i]) / 2;
-        const double w2 = fabs(m[i - 1] - m[i - 2]) + fabs(m[i - 1] + m[i - 2]) / 2;
-        const double w = w1 + w2;
-        s[i] = w > 0 ? (w1 * m[i - 1] + w2 * m[i]) / w : 0.0;
     }
 }
 
