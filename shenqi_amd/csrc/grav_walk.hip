@@ -181,7 +181,7 @@ __device__ __forceinline__ void leaf_particle(const double4 *__restrict__ tab, c
         ey = wrapd(ey, a.Box, a.invBox);
         ez = wrapd(ez, a.Box, a.invBox);
     }
-    const double rr2 = ex * ex + ey * ey + ez * ez;
+    const double rr2 = fma(ez, ez, fma(ey, ey, ex * ex)); /* the contraction it has always compiled to, pinned (see the node's r2) */
     apply_accn<POT>(tab, ex, ey, ez, rr2, q.w, a, ax, ay, az, pot);
 }
 
@@ -387,6 +387,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
     unsigned int node_int_wave = 0; /* STATS: monopole interactions of the whole wave (wave-uniform: no VGPR) */
     int mynext = valid ? a.root : -2;
     int cur = a.root;
+    int wrapnode = -1;                 /* the last node whose visit wrapped some lane's displacements (wave-uniform) */
     /* GHOSTS (GravLocalTreeWalk::visit<TREEWALK_GHOSTS>, gravshort2.hpp:243-261): an imported query walks only
      * the branches under the top-level nodes of its NodeList, i.e. the pre-order index ranges
      * [start, sibling(start)).  The lane waits at the start of its next branch; the wave cursor still begins
@@ -409,7 +410,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
     do { /* cur >= 0: the root on entry, then every node the union walk reaches */
         /* the compiler fetches the record with four scalar loads (x16, x4, x8, x4).  Two s_load_dwordx16 of the two 64-byte halves
          * were measured instead: 39.6 against 33.9 ms in a same-box A/B — not worth the two issue slots */
-        const NodeG nd = nodeG[cur];
+        /* (A 32-bit byte offset in the scalar loads' register-offset form would make the record's address one shift instead of four
+         * instructions, and measured well, but a pool beyond 2^25 records of 128 bytes - 512^3 particles - does not fit it; the
+         * zero-extended 64-bit form saves one instruction and costs a register pair, which spills under the 96-SGPR cap.) */
+        NodeG nd = nodeG[cur];
+        /* the interior flag is tested on the word the load delivered: a 32-bit scalar compare on the loaded register.  The high word
+         * passes through an empty asm and the double is put together from it again: left alone the compiler widens the test to a
+         * 64-bit VECTOR compare, and laundering a copy beside the double costs a scalar move per visit */
+        int wl_hi = __double2hiint(nd.wraplim);
+        asm volatile("" : "+s"(wl_hi));
+        nd.wraplim = __hiloint2double(wl_hi, __double2loint(nd.wraplim));
         if(STATS)
             visited++;
         const bool act = (mynext == cur);
@@ -429,15 +439,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
          * (inverse ballot: no instruction).  A vote on a compound boolean would cost two VALU instructions, and lane booleans
          * computed beside the masks would repeat the whole scalar algebra: every scalar instruction holds the SIMD's scalar pipe
          * for four cycles, as long as an f64 instruction holds the vector pipe, and the walk issues nearly as many of the one as
-         * of the other (SQ_INSTS_SALU 61 k, SQ_INSTS_VALU 66 k per task). */
+         * of the other (round 4, six waves beside the pair kernel: SQ_INSTS_SALU 37.8 k, SQ_INSTS_VALU 49.8 k per task; the vector
+         * pipe 78 % busy, the scalar pipe 65 %). */
         const unsigned long long actm = shq_ballot(mynext == cur);
-        unsigned long long wrapm = 0ull;
-        int wl_hi = __double2hiint(nd.wraplim);
-        asm volatile("" : "+s"(wl_hi)); /* a 32-bit scalar compare (left alone the compiler widens it to a 64-bit VECTOR compare) */
         if(wl_hi >= 0) { /* not an interior node (fill_rcuthl_kernel): the wrap may matter */
             asm volatile("" ::: "memory");
-            wrapm = shq_ballot(cmax >= nd.wraplim) & actm; /* >=: a zero limit (the root) means always; wrapping at equality is the identity */
+            const unsigned long long wrapm = shq_ballot(cmax >= nd.wraplim) & actm; /* >=: a zero limit (the root) means always; wrapping at equality is the identity */
             if(wrapm != 0ull) {
+                wrapnode = cur; /* what a leaf's particles need to know (below): no mask is kept, an interior visit sets nothing */
                 dx = wrapd(dx, a.Box, a.invBox);
                 dy = wrapd(dy, a.Box, a.invBox);
                 dz = wrapd(dz, a.Box, a.invBox);
@@ -447,7 +456,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
                 cmax = fmax(fmax(fabs(ux), fabs(uy)), fabs(uz));
             }
         }
-        const double r2 = dx * dx + dy * dy + dz * dz;
+        /* written as the contraction it has always compiled to: left as a sum of products, which product the compiler fuses last is
+         * its own choice and changed with an unrelated edit of this loop (the last bit of r2, and of the sums behind it) */
+        const double r2 = fma(dz, dz, fma(dy, dy, dx * dx));
         /* shall_we_discard_node, gravshort2.hpp:152-167 (rcuthl = Rcut + len / 2, per node).  (Making the second compare conditional
          * on some lane being beyond Rcut at all — a scalar branch for a vector compare — measured 34.1 against 33.6 ms.) */
         const unsigned long long keepm = actm & ~(shq_ballot(r2 > nd.rcut2) & shq_ballot(cmax > nd.rcuthl));
@@ -477,7 +488,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
                 nint++;
             }
         }
-        int next;
         if(nd.type == SHQ_PARTICLE_NODE_TYPE) {
             /* gravshort2.hpp:290-304: every particle of an opened leaf is evaluated */
             asm volatile("" ::: "memory"); /* two scalar compare-and-branch pairs, not a merged boolean (five more scalar instructions) */
@@ -497,9 +507,11 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
                     nint += cnt;
                 }
                 ringfill += cnt;
-                ringwrap |= wrapm;
+                if(wrapnode == cur)
+                    ringwrap = 1ull;
             }
             if(!RING && doopenm != 0ull) {
+                const unsigned long long wrapm = wrapnode == cur ? 1ull : 0ull;
                 const Double4K lp = posm_leaf + nd.child;
                 const int cnt = nd.count;
                 if(STATS)
@@ -531,51 +543,56 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
                 if(doopen)
                     nint += cnt;
             }
-        }
+            }
         /* Links.  A leaf or a pseudo node (gravshort2.hpp:305-315: skipped by the local walk) is left through its sibling whatever
-         * the lane decided; an internal node is entered by the lanes that open it.  Written as one select on a wave-uniform
-         * "is internal" flag rather than three branches on the node type: the compiler lowered those to a dozen scalar flag
-         * moves and branches per visit. */
-        {
-            /* the lanes that descend: those that open an internal node (a wave-uniform select on the node type, not a branch) */
-            unsigned long long descendm = nd.type == SHQ_NODE_NODE_TYPE ? doopenm : 0ull;
-            if(SPARSE && descendm != 0ull) {
+         * the lane decided; an internal node is entered by the lanes that open it.  Only `if`s without `else`, each on one scalar
+         * compare: the visit holds lane-divergent branches, so the compiler serialises every two-sided or merged condition through mask
+         * registers it sets, copies and tests again (the type tested twice, two selects of flags, a zeroed mask, a select of the next
+         * node and a 64-bit compare for it: eleven scalar instructions where five do). */
+        unsigned long long downm = 0ull; /* the lanes that descend: those that open an internal node */
+        int next = nd.sibling;
+        if(nd.type == SHQ_NODE_NODE_TYPE) {
+            asm volatile("" ::: "memory"); /* scalar compare-and-branch pairs, not merged booleans */
+            if(doopenm != 0ull) {
                 asm volatile("" ::: "memory");
-                if(__popcll(descendm) <= SHQ_SPARSE_LANES && sp_n < SHQ_SPARSE_CAP) {
-                    /* few lanes want this subtree: note it and pass on, as if they had accepted the node (its own monopole was
-                     * evaluated above for the lanes that accept it; the lanes in the mask OPEN it: the pair kernel starts at its
-                     * first child) */
-                    if(lane == 0) {
-                        unsigned long long *const it = reinterpret_cast<unsigned long long *>(walk_cold_args()->sp_items + (wave * SHQ_SPARSE_CAP + sp_n));
-                        agent_store(it, ((unsigned long long) (unsigned) nd.sibling << 32) | (unsigned) nd.child);
-                        agent_store(it + 1, descendm);
+                downm = doopenm;
+                next = nd.child;
+                if(SPARSE) {
+                    int pc; /* written out: the compiler compares the 64-bit count on the VECTOR pipe */
+                    asm("s_bcnt1_i32_b64 %[pc], %[m]" : [pc] "=s"(pc) : [m] "s"(doopenm) : "scc");
+                    /* few lanes want this subtree and the task has a free slot: both differences negative.  One test */
+                    if(((pc - (SHQ_SPARSE_LANES + 1)) & (sp_n - SHQ_SPARSE_CAP)) < 0) {
+                        /* note it and pass on, as if they had accepted the node (its own monopole was evaluated above for the lanes that
+                         * accept it; the lanes in the mask OPEN it: the pair kernel starts at its first child) */
+                        if(lane == 0) {
+                            unsigned long long *const it = reinterpret_cast<unsigned long long *>(walk_cold_args()->sp_items + (wave * SHQ_SPARSE_CAP + sp_n));
+                            agent_store(it, ((unsigned long long) (unsigned) nd.sibling << 32) | (unsigned) nd.child);
+                            agent_store(it + 1, doopenm);
+                        }
+                        sp_n++;
+                        downm = 0ull;
+                        next = nd.sibling;
                     }
-                    sp_n++;
-                    descendm = 0ull;
                 }
-                descendm = ((unsigned long long) (unsigned) __builtin_amdgcn_readfirstlane((int) (descendm >> 32)) << 32) |
-                           (unsigned) __builtin_amdgcn_readfirstlane((int) descendm);
             }
-            const unsigned long long descendm_lanes = descendm;
-            if(GHOSTS && nd.type == SHQ_NODE_NODE_TYPE) /* a lane waits at a branch below this node: go down even if nobody opens it */
-                descendm |= shq_ballot(mynext > cur && (nd.sibling < 0 || mynext < nd.sibling));
-            /* Two moves of a scalar operand under the two lane masks, written out: as a select the compiler moves both values into
-             * vector registers first (2 v_mov + 2 v_cndmask, 12 vector-pipe cycles per visit against 4 here), and the vector pipe
-             * is the busier one (SQ_ACTIVE_INST_VALU 0.90, SQ_ACTIVE_INST_SCA 0.52 of the cycles).  exec is the whole wave here
-             * (top level of the visit loop) and is restored. */
-            {
-                const unsigned long long staym = actm & ~descendm_lanes;
-                unsigned long long saved;
-                asm volatile("s_mov_b64 %[sv], exec\n\t"
-                             "s_mov_b64 exec, %[m1]\n\t"
-                             "v_mov_b32 %[dst], %[sib]\n\t"
-                             "s_mov_b64 exec, %[m2]\n\t"
-                             "v_mov_b32 %[dst], %[chd]\n\t"
-                             "s_mov_b64 exec, %[sv]"
-                             : [dst] "+v"(mynext), [sv] "=&s"(saved)
-                             : [m1] "s"(staym), [m2] "s"(descendm_lanes), [sib] "s"(nd.sibling), [chd] "s"(nd.child));
+            if(GHOSTS) { /* a lane waits at a branch below this node: go down even if nobody opens it */
+                if(shq_ballot(mynext > cur && (nd.sibling < 0 || mynext < nd.sibling)) != 0ull)
+                    next = nd.child;
             }
-            next = descendm != 0ull ? nd.child : nd.sibling;
+        }
+        /* Two moves of a scalar operand under the two lane masks, written out: as a select the compiler moves both values into
+         * vector registers first (2 v_mov + 2 v_cndmask, 12 vector-pipe cycles per visit against 4 here), and the vector pipe is the
+         * busier one (SQ_ACTIVE_INST_VALU 0.78, SQ_ACTIVE_INST_SCA 0.65 of the cycles).  exec is the whole wave here (top level of
+         * the visit loop, workgroups of whole waves), so it is set back to all ones rather than saved and restored. */
+        {
+            const unsigned long long staym = actm & ~downm;
+            asm volatile("s_mov_b64 exec, %[m1]\n\t"
+                         "v_mov_b32 %[dst], %[sib]\n\t"
+                         "s_mov_b64 exec, %[m2]\n\t"
+                         "v_mov_b32 %[dst], %[chd]\n\t"
+                         "s_mov_b64 exec, -1"
+                         : [dst] "+v"(mynext)
+                         : [m1] "s"(staym), [m2] "s"(downm), [sib] "s"(nd.sibling), [chd] "s"(nd.child));
         }
         if(GHOSTS && act && mynext == myend) { /* branch done: wait at the next one of the NodeList */
             mynext = seg1 >= 0 ? seg1 : -2;
