@@ -770,6 +770,15 @@ int shq_walk_pair_lean(shq_context *ctx);
  * the main walk has raised its flag (results, noted subtrees and OldAcc cross at the device's coherence point); 0 behind it on the
  * same stream; 2 beside it whatever the size of the launch (tests).  Same interaction sets and the same sums in every mode. */
 int shq_set_walk_overlap(shq_context *ctx, int mode);
+/* How the production launch (persistent waves + leaf ring + sparse hand-over, relative criterion, no fused readout) addresses the node
+ * pool: 1 (default; SHQ_WALK_ADDR) a record's byte offset in one 32-bit register wherever the pool allows it, 0 always the 64-bit
+ * address.  Every other launch form uses the 64-bit address.  The same loads of the same records: results are equal bit for bit.  A
+ * test / tuning knob like shq_set_walk_launch.
+ * shq_walk_addr32_fits: the rule, on numbers alone: 1 if a pool of numnodes + 1 records of 128 bytes lies within reach of the 32-bit
+ * offset (numnodes + 1 <= 2^25), else 0.  shq_walk_last_addr: 1 if the last exact walk launched fetched its records by 32-bit offset. */
+int shq_set_walk_addr(shq_context *ctx, int mode);
+int shq_walk_last_addr(shq_context *ctx, int *mode);
+int shq_walk_addr32_fits(int64_t numnodes);
 /* The pair kernel's failures are STICKY and loud (the reference checks every launch and ends the run, treewalk2.cuh:351-353).
  *  - A pair stack that ran full dropped pairs: the accelerations of that launch are incomplete.  The error word stays up on the device
  *    whatever is launched afterwards; a copy follows every launch to pinned host memory, and shq_synchronize, every *_download,

@@ -190,6 +190,8 @@ extern "C" int shq_init(int device, void *stream, shq_context **out)
         ctx->walk_sparse = atoi(v);
     if(const char *v = getenv("SHQ_WALK_OVERLAP"))
         ctx->walk_overlap = atoi(v);
+    if(const char *v = getenv("SHQ_WALK_ADDR"))
+        ctx->walk_addr = atoi(v) != 0;
     if(const char *v = getenv("SHQ_TREE_TARGETS_REFRESH"))
         ctx->tree_targets_refresh = atoi(v) > 0 ? atoi(v) : 1;
     if(const char *v = getenv("SHQ_FFT_TRANSPOSED"))
@@ -321,6 +323,21 @@ extern "C" int shq_set_walk_overlap(shq_context *ctx, int mode)
     SHQ_CHECK(ctx, SHQ_ERR_INVALID, "null context");
     SHQ_CHECK(mode >= 0 && mode <= 2, SHQ_ERR_INVALID, "walk overlap mode %d", mode);
     ctx->walk_overlap = mode;
+    return SHQ_OK;
+}
+
+extern "C" int shq_set_walk_addr(shq_context *ctx, int mode)
+{
+    SHQ_CHECK(ctx, SHQ_ERR_INVALID, "null context");
+    SHQ_CHECK(mode == 0 || mode == 1, SHQ_ERR_INVALID, "walk addr mode %d", mode);
+    ctx->walk_addr = mode;
+    return SHQ_OK;
+}
+
+extern "C" int shq_walk_last_addr(shq_context *ctx, int *mode)
+{
+    SHQ_CHECK(ctx && mode, SHQ_ERR_INVALID, "null argument");
+    *mode = ctx->last_walk_addr32 ? 1 : 0;
     return SHQ_OK;
 }
 

@@ -284,8 +284,12 @@ __device__ __forceinline__ void leaf_ring_drain(const double4 *__restrict__ tab,
                                                 const unsigned long long wrapm)
 {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* the LDS-DMA copies into the ring have landed */
-    while(shq_ballot(mymask != 0u) != 0ull) {
-        if(mymask != 0u) {
+    /* The lanes that pop are the vote read back as a lane condition, not `mymask != 0u` tested again: from that test the compiler knows
+     * the mask of a lane without a slot to be zero, and carries the popped mask through a temporary that it zeroes ahead of the masked
+     * region and copies back behind it (two vector moves per round).  Read back, the lowest bit is cleared in place. */
+    unsigned long long popm;
+    while((popm = shq_ballot(mymask != 0u)) != 0ull) {
+        if(__builtin_amdgcn_inverse_ballot_w64(popm)) {
             const int b = __builtin_ctz(mymask);
             mymask &= mymask - 1u;
             const double4 q = ring[b];
@@ -294,8 +298,16 @@ __device__ __forceinline__ void leaf_ring_drain(const double4 *__restrict__ tab,
     }
 }
 
+/* ADDR32: the node record is fetched at a 32-bit byte offset from the pool (see the fetch).  The production form only, and only for
+ * a pool the offset reaches: shq_walk_addr32_fits decides at launch. */
+typedef unsigned int walk_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int walk_u32x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int walk_u32x16 __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ double walk_f64(unsigned lo, unsigned hi) { return __hiloint2double((int) hi, (int) lo); }
+static_assert(offsetof(NodeG, sibling) == 0x40 && offsetof(NodeG, bhlim) == 0x50 && offsetof(NodeG, wraplim) == 0x70, "the ADDR32 fetch names the record's pieces by offset");
+
 template <bool POT, bool PREFETCH, int LEAFB, int STATS, bool BH, bool GHOSTS = false, bool PERSIST = false, bool RING = false, bool READOUT = false,
-          bool SPARSE = false>
+          bool SPARSE = false, bool ADDR32 = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num_vgpr(64))) void grav_walk_exact_kernel(const WalkArgs a)
 {
     extern __shared__ double4 ring_all[]; /* RING: SHQ_LEAF_RING slots per wave */
@@ -410,10 +422,45 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
     do { /* cur >= 0: the root on entry, then every node the union walk reaches */
         /* the compiler fetches the record with four scalar loads (x16, x4, x8, x4).  Two s_load_dwordx16 of the two 64-byte halves
          * were measured instead: 39.6 against 33.9 ms in a same-box A/B — not worth the two issue slots */
-        /* (A 32-bit byte offset in the scalar loads' register-offset form would make the record's address one shift instead of four
-         * instructions, and measured well, but a pool beyond 2^25 records of 128 bytes - 512^3 particles - does not fit it; the
-         * zero-extended 64-bit form saves one instruction and costs a register pair, which spills under the 96-SGPR cap.) */
-        NodeG nd = nodeG[cur];
+        /* ADDR32: the same four loads in their register-offset form (gfx950 takes an immediate beside the offset register), the record's
+         * byte offset `cur << 7` in one 32-bit register: one shift where &nodeG[cur] takes four instructions (sign extension, 64-bit
+         * shift, add, add with carry).  The pieces are loaded by name, the compiler neither emits nor merges loads of that form.  A pool
+         * beyond 2^25 records of 128 bytes (512^3 particles) does not fit the offset: shq_walk_addr32_fits, at launch.  (The split form,
+         * high bits added to the base, compiles back to four instructions; the zero-extended 64-bit form saves one and costs a register
+         * pair, which spills in the fused-readout instantiations under the 96-SGPR cap.) */
+        NodeG nd;
+        if constexpr(ADDR32) {
+            walk_u32x16 q0;
+            walk_u32x4 q1, q3;
+            walk_u32x8 q2;
+            const unsigned recoff = (unsigned) cur << 7;
+            asm volatile("s_load_dwordx4 %[q3], %[pool], %[off] offset:0x70\n\t"
+                         "s_load_dwordx16 %[q0], %[pool], %[off] offset:0x0\n\t"
+                         "s_load_dwordx4 %[q1], %[pool], %[off] offset:0x40\n\t"
+                         "s_load_dwordx8 %[q2], %[pool], %[off] offset:0x50\n\t"
+                         "s_waitcnt lgkmcnt(0)"
+                         : [q0] "=&s"(q0), [q1] "=&s"(q1), [q2] "=&s"(q2), [q3] "=&s"(q3)
+                         : [pool] "s"((unsigned long long) (size_t) a.nodeG), [off] "s"(recoff));
+            nd.cofm[0] = walk_f64(q0[0], q0[1]);
+            nd.cofm[1] = walk_f64(q0[2], q0[3]);
+            nd.cofm[2] = walk_f64(q0[4], q0[5]);
+            nd.mass = walk_f64(q0[6], q0[7]);
+            nd.center[0] = walk_f64(q0[8], q0[9]);
+            nd.center[1] = walk_f64(q0[10], q0[11]);
+            nd.center[2] = walk_f64(q0[12], q0[13]);
+            nd.len = walk_f64(q0[14], q0[15]);
+            nd.sibling = (int) q1[0];
+            nd.child = (int) q1[1];
+            nd.type = (int) q1[2];
+            nd.count = (int) q1[3];
+            nd.bhlim = walk_f64(q2[0], q2[1]);
+            nd.mlen2 = walk_f64(q2[2], q2[3]);
+            nd.inside = walk_f64(q2[4], q2[5]);
+            nd.rcut2 = walk_f64(q2[6], q2[7]);
+            nd.wraplim = walk_f64(q3[0], q3[1]);
+            nd.rcuthl = walk_f64(q3[2], q3[3]);
+        } else
+            nd = nodeG[cur];
         /* the interior flag is tested on the word the load delivered: a 32-bit scalar compare on the loaded register.  The high word
          * passes through an empty asm and the double is put together from it again: left alone the compiler widens the test to a
          * 64-bit VECTOR compare, and laundering a copy beside the double costs a scalar move per visit */
@@ -502,9 +549,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
                 if(lane < 2 * cnt)
                     __builtin_amdgcn_global_load_lds(reinterpret_cast<const double2 *>(a.posm_leaf + nd.child) + lane,
                                                      (__attribute__((address_space(3))) void *) (ring + ringfill), 16, 0, 0);
-                if(doopen) {
-                    ringmask |= ((1u << cnt) - 1u) << ringfill;
-                    nint += cnt;
+                /* the lanes that open the leaf note its slots and count its particles: two operations with a scalar operand under their
+                 * lane mask, written out like the link moves below (as `if(doopen)` the compiler moves both scalars into vector
+                 * registers and selects them against zero: six vector instructions).  exec is the whole wave here as it is there. */
+                {
+                    const unsigned slots = ((1u << cnt) - 1u) << ringfill;
+                    asm volatile("s_mov_b64 exec, %[m]\n\t"
+                                 "v_or_b32 %[rm], %[slots], %[rm]\n\t"
+                                 "v_add_u32 %[ni], %[cnt], %[ni]\n\t"
+                                 "s_mov_b64 exec, -1"
+                                 : [rm] "+v"(ringmask), [ni] "+v"(nint)
+                                 : [m] "s"(doopenm), [slots] "s"(slots), [cnt] "s"(cnt));
                 }
                 ringfill += cnt;
                 if(wrapnode == cur)
@@ -540,8 +595,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
                         }
                     }
                 }
-                if(doopen)
-                    nint += cnt;
+                /* the count under the lane mask, as in the ring form above (as `if(doopen)`: a move, a select and the add) */
+                asm volatile("s_mov_b64 exec, %[m]\n\t"
+                             "v_add_u32 %[ni], %[cnt], %[ni]\n\t"
+                             "s_mov_b64 exec, -1"
+                             : [ni] "+v"(nint)
+                             : [m] "s"(doopenm), [cnt] "s"(cnt));
             }
             }
         /* Links.  A leaf or a pseudo node (gravshort2.hpp:305-315: skipped by the local walk) is left through its sibling whatever
@@ -549,13 +608,24 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
          * compare: the visit holds lane-divergent branches, so the compiler serialises every two-sided or merged condition through mask
          * registers it sets, copies and tests again (the type tested twice, two selects of flags, a zeroed mask, a select of the next
          * node and a 64-bit compare for it: eleven scalar instructions where five do). */
-        unsigned long long downm = 0ull; /* the lanes that descend: those that open an internal node */
+        /* The moves are a scalar operand under a lane mask, written out: as a select the compiler moves both values into vector
+         * registers first (2 v_mov + 2 v_cndmask, 12 vector-pipe cycles per visit against 4), and the vector pipe is the busier one
+         * (SQ_ACTIVE_INST_VALU 0.78, SQ_ACTIVE_INST_SCA 0.65 of the cycles).  exec is the whole wave here (top level of the visit
+         * loop, workgroups of whole waves), so it is set back to all ones rather than saved and restored.
+         * Every awake lane takes the sibling first; the lanes that descend take the child on top of it, inside the branch only a visit
+         * that opens an internal node reaches: the common visit, which nobody opens, carries one move and no mask of the descending
+         * lanes (zeroed, subtracted from the awake lanes and moved under: three scalar and one vector instruction per visit). */
         int next = nd.sibling;
+        asm volatile("s_mov_b64 exec, %[m]\n\t"
+                     "v_mov_b32 %[dst], %[sib]\n\t"
+                     "s_mov_b64 exec, -1"
+                     : [dst] "+v"(mynext)
+                     : [m] "s"(actm), [sib] "s"(nd.sibling));
         if(nd.type == SHQ_NODE_NODE_TYPE) {
             asm volatile("" ::: "memory"); /* scalar compare-and-branch pairs, not merged booleans */
             if(doopenm != 0ull) {
                 asm volatile("" ::: "memory");
-                downm = doopenm;
+                unsigned long long downm = doopenm; /* the lanes that descend: those that open an internal node */
                 next = nd.child;
                 if(SPARSE) {
                     int pc; /* written out: the compiler compares the 64-bit count on the VECTOR pipe */
@@ -574,25 +644,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
                         next = nd.sibling;
                     }
                 }
+                asm volatile("s_mov_b64 exec, %[m]\n\t"
+                             "v_mov_b32 %[dst], %[chd]\n\t"
+                             "s_mov_b64 exec, -1"
+                             : [dst] "+v"(mynext)
+                             : [m] "s"(downm), [chd] "s"(nd.child));
             }
-            if(GHOSTS) { /* a lane waits at a branch below this node: go down even if nobody opens it */
-                if(shq_ballot(mynext > cur && (nd.sibling < 0 || mynext < nd.sibling)) != 0ull)
+            if(GHOSTS) { /* a lane waits at a branch below this node: go down even if nobody opens it (the awake lanes have their link already) */
+                if(shq_ballot(!act && mynext > cur && (nd.sibling < 0 || mynext < nd.sibling)) != 0ull)
                     next = nd.child;
             }
-        }
-        /* Two moves of a scalar operand under the two lane masks, written out: as a select the compiler moves both values into
-         * vector registers first (2 v_mov + 2 v_cndmask, 12 vector-pipe cycles per visit against 4 here), and the vector pipe is the
-         * busier one (SQ_ACTIVE_INST_VALU 0.78, SQ_ACTIVE_INST_SCA 0.65 of the cycles).  exec is the whole wave here (top level of
-         * the visit loop, workgroups of whole waves), so it is set back to all ones rather than saved and restored. */
-        {
-            const unsigned long long staym = actm & ~downm;
-            asm volatile("s_mov_b64 exec, %[m1]\n\t"
-                         "v_mov_b32 %[dst], %[sib]\n\t"
-                         "s_mov_b64 exec, %[m2]\n\t"
-                         "v_mov_b32 %[dst], %[chd]\n\t"
-                         "s_mov_b64 exec, -1"
-                         : [dst] "+v"(mynext)
-                         : [m1] "s"(staym), [m2] "s"(downm), [sib] "s"(nd.sibling), [chd] "s"(nd.child));
         }
         if(GHOSTS && act && mynext == myend) { /* branch done: wait at the next one of the NodeList */
             mynext = seg1 >= 0 ? seg1 : -2;
@@ -604,8 +665,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
         cur = __builtin_amdgcn_readfirstlane(next);
     } while(cur >= 0);
 
-    if(RING)
+    if(RING) {
         leaf_ring_drain<POT>(tab, ring, ringmask, px, py, pz, a, ax, ay, az, pot, ringwrap);
+    }
     {
     const WalkArgs c = PERSIST ? *walk_cold_args() : a;
     if(valid) {
@@ -1135,13 +1197,17 @@ __global__ void stats_init_kernel(GravStatsDev *s)
 /* BH: pure Barnes-Hut opening angle (TreeUseBH, the seeding walk before any acceleration exists) as its
  * own instantiation: the relative criterion drops out at compile time, and a profile lists the seeding
  * walk and the production walk as two kernels. */
+/* addr32: the caller wants the 32-bit record offsets where the launch takes the production form; returns whether it did */
 template <bool POT, bool PREFETCH, int LEAFB, bool BH>
-void launch_variant_bh(int stats, bool persist, dim3 grid, dim3 block, hipStream_t stream, const WalkArgs &a, size_t dyn_lds = 0)
+bool launch_variant_bh(int stats, bool persist, dim3 grid, dim3 block, hipStream_t stream, const WalkArgs &a, size_t dyn_lds = 0, bool addr32 = false)
 {
     constexpr bool RO = !PREFETCH && LEAFB == 2 && !BH; /* the fused readout and the sparse-subtree hand-over exist for the production variant only */
     if(a.pm_mesh && a.sp_items && RO && !stats && persist && block.x == 512)
         grav_walk_exact_kernel<POT, PREFETCH, LEAFB, 0, BH, false, RO, RO, RO, RO><<<grid, block, dyn_lds, stream>>>(a);
-    else if(a.sp_items && RO && !stats && persist && block.x == 512)
+    else if(a.sp_items && RO && !stats && persist && block.x == 512 && addr32) {
+        grav_walk_exact_kernel<POT, PREFETCH, LEAFB, 0, BH, false, RO, RO, false, RO, RO><<<grid, block, dyn_lds, stream>>>(a);
+        return true;
+    } else if(a.sp_items && RO && !stats && persist && block.x == 512)
         grav_walk_exact_kernel<POT, PREFETCH, LEAFB, 0, BH, false, RO, RO, false, RO><<<grid, block, dyn_lds, stream>>>(a);
     else if(a.pm_mesh && RO && !stats && persist && block.x == 512)
         grav_walk_exact_kernel<POT, PREFETCH, LEAFB, 0, BH, false, RO, RO, RO><<<grid, block, dyn_lds, stream>>>(a);
@@ -1157,18 +1223,22 @@ void launch_variant_bh(int stats, bool persist, dim3 grid, dim3 block, hipStream
         grav_walk_exact_kernel<POT, PREFETCH, LEAFB, 0, BH, false, (!PREFETCH && LEAFB == 2)><<<grid, block, dyn_lds, stream>>>(a);
     else
         grav_walk_exact_kernel<POT, PREFETCH, LEAFB, 0, BH><<<grid, block, 0, stream>>>(a);
+    return false;
 }
 
 template <bool POT, bool PREFETCH, int LEAFB>
-void launch_variant(int stats, bool persist, dim3 grid, dim3 block, hipStream_t stream, const WalkArgs &a, size_t dyn_lds = 0)
+bool launch_variant(int stats, bool persist, dim3 grid, dim3 block, hipStream_t stream, const WalkArgs &a, size_t dyn_lds = 0, bool addr32 = false)
 {
     if(a.useBH)
-        launch_variant_bh<POT, PREFETCH, LEAFB, true>(stats, persist, grid, block, stream, a, dyn_lds);
-    else
-        launch_variant_bh<POT, PREFETCH, LEAFB, false>(stats, persist, grid, block, stream, a, dyn_lds);
+        return launch_variant_bh<POT, PREFETCH, LEAFB, true>(stats, persist, grid, block, stream, a, dyn_lds, addr32);
+    return launch_variant_bh<POT, PREFETCH, LEAFB, false>(stats, persist, grid, block, stream, a, dyn_lds, addr32);
 }
 
 } // namespace
+
+/* The 32-bit form of the walk's record fetch reaches byte (cur << 7) + 0x70 + 15 of the pool through an unsigned 32-bit offset register
+ * and an immediate: every record of a pool of numnodes + 1 records (cur <= numnodes) must start below 2^32, i.e. numnodes + 1 <= 2^25. */
+extern "C" int shq_walk_addr32_fits(int64_t numnodes) { return (numnodes >= 0 && numnodes + 1 <= ((int64_t) 1 << 25)) ? 1 : 0; }
 
 void shq_launch_stats_init(shq_context *ctx) { stats_init_kernel<<<1, 1, 0, ctx->stream>>>(ctx->gstats.ptr); }
 
@@ -1542,22 +1612,26 @@ int shq_launch_grav_walk(shq_context *ctx, const shq_grav_params *p, const int32
     SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_WALK], ctx->stream));
     if(live) /* what precedes the walk on this stream (the PM, the flags' reset) also precedes the pair kernel on the other */
         SHQ_HIP(hipEventRecord(ctx->ev_pair_fork, ctx->stream));
+    /* the record's address as a 32-bit byte offset (shq_set_walk_addr), where the launch takes the production form and the pool fits */
+    const bool addr32 = ctx->walk_addr != 0 && shq_walk_addr32_fits(ctx->numnodes) != 0;
+    bool used32 = false;
     if(update_potential) {
         switch(variant) {
         case 0: launch_variant<true, false, 4>(stats, persist, grid, block, ctx->stream, a); break;
         case 1: launch_variant<true, false, 2>(stats, persist, grid, block, ctx->stream, a); break;
         case 2: launch_variant<true, false, 4>(stats, persist, grid, block, ctx->stream, a); break;
-        default: launch_variant<true, false, 2>(stats, persist, grid, block, ctx->stream, a, dyn_lds); break;
+        default: used32 = launch_variant<true, false, 2>(stats, persist, grid, block, ctx->stream, a, dyn_lds, addr32); break;
         }
     } else {
         switch(variant) {
         case 0: launch_variant<false, false, 4>(stats, persist, grid, block, ctx->stream, a); break;
         case 1: launch_variant<false, false, 2>(stats, persist, grid, block, ctx->stream, a); break;
         case 2: launch_variant<false, false, 4>(stats, persist, grid, block, ctx->stream, a); break;
-        default: launch_variant<false, false, 2>(stats, persist, grid, block, ctx->stream, a, dyn_lds); break;
+        default: used32 = launch_variant<false, false, 2>(stats, persist, grid, block, ctx->stream, a, dyn_lds, addr32); break;
         }
     }
     SHQ_HIP(hipGetLastError());
+    ctx->last_walk_addr32 = used32;
     if(sparse) { /* the noted subtrees, one lane per (target, node) pair; inside the walk's timer */
         /* live: submitted AFTER the main walk, which never waits for it — if the two are run one after the other after all (a
          * profiler collecting counters serialises dispatches) the pair kernel finds every flag up */
