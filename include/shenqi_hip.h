@@ -964,7 +964,9 @@ int shq_density(shq_context *ctx, const shq_tree_view *tree, shq_node *nodes_rw,
 /* One-shot replacement of hydro_force_cuda(): symmetric neighbour walk (cull radius
  * max(hmax_node, Hsml_i)), HydroResult::reduce and HydroOutput::postprocess
  * (hydratree2.hpp:127-149,201-379).  Writes SphP[].HydroAccel / DtEntropy / MaxSignalVel for
- * the active Type-0 targets.  EntVarPred may be NULL (then computed per particle). */
+ * the active Type-0 targets.  EntVarPred may be NULL (then computed per particle).
+ * A target's time bin must have params->drifts[bin] == 0, as the HydroPriv ctor leaves it for active bins
+ * (hydratree2.hpp:94-100): the query takes the target un-drifted; otherwise SHQ_ERR_INVALID (shq_hydro_open too). */
 int shq_hydro_force(shq_context *ctx, const shq_tree_view *tree, const shq_part_view *parts,
                     const shq_sph_view *sph, const int32_t *active, int64_t nactive,
                     const shq_hydro_params *params, const double *EntVarPred, shq_sph_stats *stats);

@@ -368,6 +368,15 @@ extern "C" int shq_hydro_open(shq_context *ctx, const shq_tree_view *tree, const
     std::vector<int32_t> &queue = run_queue(ctx);
     queue = build_queue(parts, active, nactive, false);
     const int64_t nq = (int64_t) queue.size();
+    /* HydroQuery takes the target's Density and EgyWtDensity un-drifted (hydratree2.hpp:165-191); the walk reads the drifted record
+     * of the predict kernel for the target too, which is the same only where the target's drift factor is zero.  The reference
+     * leaves drifts[] zero for every active bin (HydroPriv ctor, hydratree2.hpp:94-100), so anything else is a caller's mistake. */
+    if(parts->off_timebin_hydro != SHQ_NOFIELD)
+        for(int32_t i : queue) {
+            const uint8_t b = *pfield<uint8_t>(parts, i, parts->off_timebin_hydro);
+            SHQ_CHECK(b > SHQ_TIMEBINS || params->drifts[b] == 0, SHQ_ERR_INVALID,
+                      "hydro target %d is in time bin %d with drift factor %g: targets must be in bins with drifts[] = 0", i, (int) b, params->drifts[b]);
+        }
     SHQ_TRY(ctx->s_queue0.reserve((size_t) std::max<int64_t>(nq, 1)));
     if(nq > 0)
         SHQ_HIP(hipMemcpyAsync(ctx->s_queue0.ptr, queue.data(), sizeof(int32_t) * nq, hipMemcpyHostToDevice, ctx->stream));

@@ -40,8 +40,15 @@ def records(pos, garbage=None, types=None):
     return P
 
 
+def settled(t):
+    """torch fills and copies run on torch's stream, the library's kernels on its own non-blocking one: finish the former before
+    the tensor is handed to the library"""
+    torch.cuda.synchronize()
+    return t
+
+
 def dev(a):
-    return torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(DEV)
+    return settled(torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).to(DEV))
 
 
 def parts_view(d_parts, n, box):
@@ -50,7 +57,7 @@ def parts_view(d_parts, n, box):
 
 def device_keys(ctx, t, pos, box):
     d_pos = torch.from_numpy(np.ascontiguousarray(pos, dtype=np.float64)).to(DEV)
-    d_keys = torch.zeros(len(pos), dtype=torch.int64, device=DEV)
+    d_keys = settled(torch.zeros(len(pos), dtype=torch.int64, device=DEV))
     capi.check(capi.hip.shq_peano_keys(ctx.h, C.byref(t), d_pos.data_ptr(), 24, len(pos), box, d_keys.data_ptr()))
     ctx.synchronize()
     return d_keys.cpu().numpy().view(np.uint64)
@@ -65,7 +72,7 @@ def test_keys_equal_the_reference(ctx, tab, box):
     want = dr.reference_PEANO(pos, box)
     assert np.array_equal(device_keys(ctx, t, pos, box), want)
     d_parts = dev(records(pos))
-    d_keys = torch.zeros(len(pos), dtype=torch.int64, device=DEV)
+    d_keys = settled(torch.zeros(len(pos), dtype=torch.int64, device=DEV))
     capi.check(capi.hip.shq_peano_keys(ctx.h, C.byref(t), d_parts.data_ptr() + OFF_POS, ESZ, len(pos), box, d_keys.data_ptr()))
     ctx.synchronize()
     assert np.array_equal(d_keys.cpu().numpy().view(np.uint64), want)
@@ -73,7 +80,7 @@ def test_keys_equal_the_reference(ctx, tab, box):
 
 
 def device_samples(ctx, t, d_parts, n, box, dist_, presort):
-    out = torch.full((n // dist_ + 1,), -1, dtype=torch.int64, device=DEV)
+    out = settled(torch.full((n // dist_ + 1,), -1, dtype=torch.int64, device=DEV))
     ns = C.c_int64(-1)
     capi.check(capi.hip.shq_domain_samples(ctx.h, C.byref(t), C.byref(parts_view(d_parts, n, box)), dist_, presort, out.data_ptr(), C.byref(ns)))
     ctx.synchronize()
@@ -102,7 +109,7 @@ def test_samples_equal_the_restatement(ctx, tab):
 
 
 def device_local_toptree(ctx, lp, countlimit, costlimit, maxtop):
-    d = torch.from_numpy(np.ascontiguousarray(lp, dtype=np.uint64).view(np.int64).copy()).to(DEV)
+    d = settled(torch.from_numpy(np.ascontiguousarray(lp, dtype=np.uint64).view(np.int64).copy()).to(DEV))
     tree = np.zeros(maxtop, dtype=capi.LOCAL_TOPNODE_DTYPE)
     tree["Shift"] = -99                                                     # a mark: what the call does not write stays
     size = C.c_int(-1)
@@ -204,7 +211,7 @@ def test_leaf_counts_topleaves_and_targets(ctx, tab, ntopleaves):
     Tasks, status = dr.balance(N, L, count, ntask, n)
     install(ctx, t, N, L)                                                    # the final leaf numbers and tasks
     d_leaf = torch.full((n,), -7, dtype=torch.int32, device=DEV)
-    d_tgt = torch.full((n,), -5, dtype=torch.int32, device=DEV)
+    d_tgt = settled(torch.full((n,), -5, dtype=torch.int32, device=DEV))
     capi.check(capi.hip.shq_domain_particle_topleaves(ctx.h, C.byref(pv), d_leaf.data_ptr(), d_tgt.data_ptr()))
     ctx.synchronize()
     leaf, tgt = d_leaf.cpu().numpy(), d_tgt.cpu().numpy()
@@ -245,7 +252,7 @@ def test_closure_with_tree_build_and_topleaf_maintenance(ctx, tab):
     tl = np.ascontiguousarray(L[:-1])
     sq.tree_build_domain(ctx, cm.BOX, geo, tl, 0, n + 5)
     d_parts = dev(pman.Base)
-    d_leaf = torch.full((n,), -1, dtype=torch.int32, device=DEV)
+    d_leaf = settled(torch.full((n,), -1, dtype=torch.int32, device=DEV))
     capi.check(capi.hip.shq_domain_particle_topleaves(ctx.h, C.byref(parts_view(d_parts, n, cm.BOX)), d_leaf.data_ptr(), None))
     ctx.synchronize()
     before = d_leaf.cpu().numpy().copy()
