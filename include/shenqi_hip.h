@@ -940,8 +940,9 @@ typedef struct shq_sph_stats {
     int32_t niterations;     /* Hsml iterations (do_hsml_loop, treewalk2.h:480-557) */
     int32_t pad_;
     double kernel_ms;        /* HIP-event time of the walk kernels */
-    double hsml_max_tried;   /* density calls: the largest Hsml any walk of the loop searched with or any target ends with (a collapsed
-                                bracket ends on Right, a floor on MinGasHsml: radii no walk ran with); 0 for other operators.  A sharded
+    double hsml_max_tried;   /* density and stellar-density calls: the largest Hsml any walk of the loop searched with or any target ends
+                                with (a collapsed bracket ends on Right, a floor on MinGasHsml: radii no walk ran with; stellar density: the
+                                largest of its trial radii); 0 for other operators.  A sharded
                                 caller sizes its ghost halo by this, not by the Hsml the loop ends with: an intermediate guess beyond the
                                 halo undercounts NumNgb and steers the iteration (treewalk2.h:480-557 runs every guess against all ranks) */
 } shq_sph_stats;
@@ -1073,7 +1074,8 @@ int shq_sph_fill_queries(shq_context *ctx, const shq_data_index *table, int64_t 
  * queue shq_metal_yields returns), with its own Hsml iteration over ten trial radii per walk (stellareffhsml, ngbiter, postprocess,
  * ngb_narrow_down).  `tree` is the gas tree (GASMASK); gas densities come from the SPH view.  Writes Part[].Hsml of the
  * stars and StarVolumeSPH[PI of the star].  A star with Hsml == 0 is refused (the reference re-seeds it from its father
- * node).  SHQ_ERR_NOCONV beyond MAXITER iterations. */
+ * node).  SHQ_ERR_NOCONV beyond MAXITER iterations.  stats->hsml_max_tried is the largest trial radius of any walk of the loop, or
+ * any final Hsml: what a sharded caller compares with its ghost halo (shenqi_amd/dist.py:DistMetalReturn.stellar_density). */
 typedef struct shq_stellar_params {
     double BoxSize;
     double DesNumNgb;           /* GetNumNgb(GetDensityKernelType()) */
@@ -1247,6 +1249,40 @@ typedef struct shq_gas_metal_view {
 int shq_metal_return(shq_context *ctx, const shq_tree_view *tree, const shq_part_view *parts, const shq_gas_metal_view *gas, const int32_t *queue, int64_t nqueue,
                      const double *StarVolumeSPH, const double *MassGenerated, const double *MetalGenerated, const double *MetalSpeciesGenerated /* [nqueue][nmetals] */,
                      double MaxGasMass, int SPHWeighting, int DensityKernelType, double *MassReturn, int64_t *npairs);
+
+/* The parts of the call above for a multi-rank driver (shenqi_amd/dist.py:DistMetalReturn).  Every rank walks its own stars over its own
+ * gas plus the gas it imported, sends the triples that fell on imports to the gas's owner, the owner applies all triples of a particle
+ * in the order of the GLOBAL queue (the ranks' queues one after the other, in rank order), and the mass each triple moved travels back to the
+ * star's rank: the gas ends with the bits of shq_metal_return on the undivided set with that global queue, whatever the decomposition.
+ *
+ * shq_metal_return_triples  the two emit walks, nothing changed.  Rows [0, nlocal) of `parts` are this rank's own, rows >= nlocal
+ *     imports: ghost_owner[row - nlocal] in [0, nranks) and ghost_index[row - nlocal] >= 0 are the owner's rank and the row there.
+ *     Every triple becomes (owner, row at the owner, queue_offset + queue position, wk) - own rows: (rank, row) - and the list is sorted by
+ *     (owner, row, star): counts[nranks] triples per owner, contiguous, in rank order; *ntriples their total.  With triples == NULL only
+ *     counts and *ntriples are returned; a list with capacity < *ntriples is SHQ_ERR_INVALID (counts and *ntriples still set).
+ *     queue_offset + nqueue must stay below 2^31 (the star position is 32 bits of a sort key).
+ * shq_metal_return_apply    n triples of this rank's own gas, gathered from all ranks in any order (it sorts them by (row, star); owner
+ *     is not read): metal_return_ngbiter's body per triple, one thread per gas particle, stars in ascending position.  star_table holds
+ *     SHQ_METAL_STAR_NCOL doubles per global queue position: StarVolumeSPH, MassGenerated, MetalGenerated, MetalSpeciesGenerated[9].
+ *     Metals, Metallicity, Mass and Density of the touched particles go back into the caller's records; thismass[k] is the mass triple k
+ *     moved, 0 where the MaxGasMass rule refused it.  A row outside [0, numpart) or that is not live gas, a star position outside
+ *     [0, nstars), or StarVolumeSPH == 0 of a star some triple names: SHQ_ERR_INVALID, nothing written.
+ * shq_metal_return_sums     MassReturn[q] for q in [0, nqueue): the thismass of the triples with local queue position qpos == q, added
+ *     in ascending (owner, row) order - the same bits on every run. */
+#define SHQ_METAL_STAR_NCOL 12
+typedef struct shq_metal_triple {
+    int32_t owner, part_index;      /* rank that owns the gas particle, its row there */
+    uint32_t star;                  /* position in the global queue */
+    int32_t pad_;
+    double wk;
+} shq_metal_triple;
+int shq_metal_return_triples(shq_context *ctx, const shq_tree_view *tree, const shq_part_view *parts, const int32_t *queue, int64_t nqueue, int SPHWeighting,
+                             int DensityKernelType, int64_t nlocal, const int32_t *ghost_owner, const int32_t *ghost_index, int nranks, int rank,
+                             int64_t queue_offset, shq_metal_triple *triples, int64_t capacity, int64_t *counts, int64_t *ntriples);
+int shq_metal_return_apply(shq_context *ctx, const shq_part_view *parts, const shq_gas_metal_view *gas, const shq_metal_triple *triples, int64_t n,
+                           const double *star_table, int64_t nstars, double MaxGasMass, double *thismass);
+int shq_metal_return_sums(shq_context *ctx, const int32_t *qpos, const int32_t *owner, const int32_t *part_index, const double *thismass, int64_t n,
+                          int64_t nqueue, double *MassReturn);
 
 /* ---- stellar yields: metal_return_init and the yields of metal_return_copy (libgadget/metal_return.cpp:157-462, 539-569) ------------
  * What metal_return() does per active star before its two tree walks: the star's age, the masses of the stars that die during the

@@ -493,6 +493,14 @@ hip.shq_winds_candidates.restype = hip.shq_winds_apply.restype = C.c_int
 hip.shq_metal_return.argtypes = [_vp, C.POINTER(TreeView), C.POINTER(PartView), C.POINTER(GasMetalView), _vp, C.c_int64, _vp, _vp, _vp, _vp, C.c_double, C.c_int, C.c_int, _vp,
                                  C.POINTER(C.c_int64)]
 hip.shq_metal_return.restype = C.c_int
+# struct shq_metal_triple: a (gas particle, star, kernel weight) triple routed to the particle's owner
+METAL_TRIPLE_DTYPE = np.dtype([("owner", "<i4"), ("part_index", "<i4"), ("star", "<u4"), ("pad_", "<i4"), ("wk", "<f8")])
+METAL_STAR_NCOL = 12     # SHQ_METAL_STAR_NCOL: StarVolumeSPH, MassGenerated, MetalGenerated, MetalSpeciesGenerated[9]
+hip.shq_metal_return_triples.argtypes = [_vp, C.POINTER(TreeView), C.POINTER(PartView), _vp, C.c_int64, C.c_int, C.c_int, C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_int64,
+                                         _vp, C.c_int64, _vp, C.POINTER(C.c_int64)]
+hip.shq_metal_return_apply.argtypes = [_vp, C.POINTER(PartView), C.POINTER(GasMetalView), _vp, C.c_int64, _vp, C.c_int64, C.c_double, _vp]
+hip.shq_metal_return_sums.argtypes = [_vp, _vp, _vp, _vp, _vp, C.c_int64, C.c_int64, _vp]
+hip.shq_metal_return_triples.restype = hip.shq_metal_return_apply.restype = hip.shq_metal_return_sums.restype = C.c_int
 hip.shq_domain_maintain_topleaf.argtypes = [_vp, C.c_int, C.c_int64, _vp, _vp, C.POINTER(C.c_int64)]
 hip.shq_domain_maintain_topleaf.restype = C.c_int
 

@@ -278,7 +278,8 @@ extern "C" void shq_shutdown(shq_context *ctx)
     ctx->wind_kicks.release(); ctx->wind_d.release(); ctx->wind_cnt.release();
     for(auto &b : ctx->metal_keys) b.release();
     for(auto &b : ctx->metal_val) b.release();
-    ctx->metal_star.release(); ctx->metal_gd.release(); ctx->metal_gf.release();
+    ctx->metal_star.release(); ctx->metal_gd.release(); ctx->metal_gf.release(); ctx->metal_trip.release();
+    for(auto &b : ctx->metal_u32) b.release();
     ctx->velp.release(); ctx->hydC.release(); ctx->hydD.release(); ctx->velp_leaf.release(); ctx->hydrec_leaf.release();
     ctx->hsml_leaf.release(); ctx->flag_leaf.release(); ctx->posf_leaf.release(); ctx->ngarb_leaf.release();
     ctx->s_numngb.release(); ctx->s_dhsmldens.release(); ctx->s_left.release(); ctx->s_right.release(); ctx->s_rot.release();

@@ -353,6 +353,8 @@ struct shq_context {
     DevBuf<unsigned long long> metal_keys[2];
     DevBuf<double> metal_val[2], metal_star, metal_gd;
     DevBuf<float> metal_gf;
+    DevBuf<uint32_t> metal_u32[4];  /* owners, sort orders and original indices of the routed metal-return calls */
+    DevBuf<char> metal_trip;        /* the routed triple list */
     DevBuf<char> wind_kicks;
     DevBuf<double> wind_d;
     DevBuf<unsigned long long> wind_cnt;
@@ -765,6 +767,7 @@ struct MetalWalkArgs {
     double MaxGasMass;
     /* by queue position */
     const double *starvolume, *massgenerated, *metalgenerated, *speciesgenerated;
+    size_t star_stride, species_stride; /* doubles between two stars: 1 and SHQ_NMETALS for separate arrays, SHQ_METAL_STAR_NCOL for the star table */
     /* gas state by particle index */
     float *gmass, *gmetals;
     double *gdensity, *gmetallicity;
@@ -774,6 +777,19 @@ struct MetalWalkArgs {
 int shq_metal_rows_gather(shq_context *ctx, const MetalWalkArgs *w, const int32_t *d_list, int64_t m, double *d_rows);
 int shq_metal_return_device(shq_context *ctx, MetalWalkArgs *w, int kernel_type, double BoxSize, const int32_t *d_queue, int64_t nq, double *d_massreturn,
                             int64_t *npairs_out);
+/* The parts of the call above for a multi-rank driver.
+ * triples: the two emit passes, then every triple rewritten to (owner, index at the owner, global queue position, wk) and sorted by
+ *   these three; the list is left in ctx->metal_trip, the per-owner counts in d_counts[nranks].  Rows >= nlocal are imports: their owner
+ *   and their index there come from d_ghost_owner / d_ghost_index (by row - nlocal).
+ * apply: n triples (any order) of this rank's own gas, applied per particle in ascending star position; d_thismass[k] belongs to d_trip[k].
+ *   w->starvolume ... speciesgenerated point into the star table.
+ * sums: massreturn[q] = the thismass of the triples of local queue position q, added in ascending (owner, particle) order. */
+int shq_metal_triples_device(shq_context *ctx, MetalWalkArgs *w, int kernel_type, double BoxSize, const int32_t *d_queue, int64_t nq, int64_t nlocal,
+                             const int32_t *d_ghost_owner, const int32_t *d_ghost_index, int nranks, int rank, int64_t queue_offset,
+                             unsigned long long *d_counts, int64_t *ntriples);
+int shq_metal_apply_device(shq_context *ctx, const MetalWalkArgs *w, const shq_metal_triple *d_trip, int64_t n, double *d_thismass);
+int shq_metal_sums_device(shq_context *ctx, const int32_t *d_qpos, const int32_t *d_owner, const int32_t *d_pidx, const double *d_thismass, int64_t n, int64_t nq,
+                          double *d_massreturn);
 int shq_bh_accretion_device(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, const int32_t *d_queue, int64_t nq, double *d_post);
 int shq_bh_feedback_device(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, const int32_t *d_queue, int64_t nq);
 /* the particles marked in `mark` (one byte each), ascending, into d_list (room for n entries); *m = their number (one host round trip) */

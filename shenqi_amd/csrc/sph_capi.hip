@@ -1520,6 +1520,83 @@ extern "C" int shq_winds_apply(shq_context *ctx, const shq_part_view *parts, con
 }
 
 /* ---- metal_return's treewalk (metal_return.cpp:513-530, 573-667) ---------------------------------------------------------------- */
+namespace {
+/* Mass (float) of every particle and Density, Metallicity, Metals of the live gas, by particle index, into metal_gf / metal_gd; the
+ * touched marks cleared.  Fills the gas half of *w. */
+int metal_gas_upload(shq_context *ctx, const shq_part_view *parts, const shq_gas_metal_view *gas, MetalWalkArgs *w, const char *who)
+{
+    hipStream_t st = ctx->stream;
+    const int64_t n = parts->numpart;
+    const size_t cap = (size_t) std::max<int64_t>(n, 1);
+    std::vector<float> gf(cap * (1 + SHQ_NMETALS), 0.f);
+    std::vector<double> gd(cap * 2, 1.0);
+    float *hm = gf.data(), *hz = gf.data() + cap;
+    double *hd = gd.data(), *hy = gd.data() + cap;
+    for(int64_t i = 0; i < n; i++) {
+        hm[i] = *pfield<float>(parts, i, parts->off_mass);
+        if(*pfield<uint8_t>(parts, i, parts->off_type) != 0 || (*pfield<uint8_t>(parts, i, parts->off_flags) & 1u))
+            continue;
+        const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+        SHQ_CHECK(pi >= 0 && pi < gas->numslots, SHQ_ERR_INVALID, "%s: gas particle %ld has PI %d outside the slot array", who, (long) i, pi);
+        const char *s = static_cast<const char *>(gas->base) + (size_t) pi * gas->elsize;
+        hd[i] = *reinterpret_cast<const double *>(s + gas->off_density);
+        hy[i] = *reinterpret_cast<const double *>(s + gas->off_metallicity);
+        for(int m = 0; m < SHQ_NMETALS; m++)
+            hz[(size_t) i * SHQ_NMETALS + m] = reinterpret_cast<const float *>(s + gas->off_metals)[m];
+    }
+    SHQ_TRY(ctx->metal_gf.reserve(gf.size()));
+    SHQ_TRY(ctx->metal_gd.reserve(gd.size()));
+    SHQ_HIP(hipMemcpyAsync(ctx->metal_gf.ptr, gf.data(), sizeof(float) * gf.size(), hipMemcpyHostToDevice, st));
+    SHQ_HIP(hipMemcpyAsync(ctx->metal_gd.ptr, gd.data(), sizeof(double) * gd.size(), hipMemcpyHostToDevice, st));
+    SHQ_HIP(hipStreamSynchronize(st)); /* gf and gd leave scope */
+    w->gmass = ctx->metal_gf.ptr;
+    w->gmetals = ctx->metal_gf.ptr + cap;
+    w->gdensity = ctx->metal_gd.ptr;
+    w->gmetallicity = ctx->metal_gd.ptr + cap;
+    /* the gas the return changes comes back as rows of the particles it touched */
+    SHQ_TRY(ctx->bhw_touched.reserve(cap));
+    SHQ_TRY(ctx->bhw_tlist.reserve(cap));
+    SHQ_HIP(hipMemsetAsync(ctx->bhw_touched.ptr, 0, cap, st));
+    w->touched = ctx->bhw_touched.ptr;
+    return SHQ_OK;
+}
+
+/* the rows of the particles the return touched back into the caller's records */
+int metal_gas_writeback(shq_context *ctx, const shq_part_view *parts, const shq_gas_metal_view *gas, const MetalWalkArgs *w, const char *who)
+{
+    hipStream_t st = ctx->stream;
+    const int64_t n = parts->numpart;
+    int64_t nt = 0;
+    SHQ_TRY(ctx->bhw_tlist.reserve((size_t) std::max<int64_t>(n, 1)));
+    SHQ_TRY(shq_marked_list(ctx, ctx->bhw_touched.ptr, n, ctx->bhw_tlist.ptr, &nt));
+    const size_t W = 3 + SHQ_NMETALS;
+    SHQ_TRY(ctx->bhw_trows.reserve(W * (size_t) std::max<int64_t>(nt, 1)));
+    std::vector<double> rows(W * (size_t) std::max<int64_t>(nt, 1));
+    std::vector<int32_t> tl((size_t) std::max<int64_t>(nt, 1));
+    if(nt) {
+        SHQ_TRY(shq_metal_rows_gather(ctx, w, ctx->bhw_tlist.ptr, nt, ctx->bhw_trows.ptr));
+        SHQ_HIP(hipMemcpyAsync(rows.data(), ctx->bhw_trows.ptr, sizeof(double) * W * (size_t) nt, hipMemcpyDeviceToHost, st));
+        SHQ_HIP(hipMemcpyAsync(tl.data(), ctx->bhw_tlist.ptr, sizeof(int32_t) * (size_t) nt, hipMemcpyDeviceToHost, st));
+    }
+    SHQ_HIP(hipStreamSynchronize(st));
+    for(int64_t t = 0; t < nt; t++) {
+        const int64_t i = tl[(size_t) t];
+        const double *r = &rows[W * (size_t) t];
+        SHQ_CHECK(*pfield<uint8_t>(parts, i, parts->off_type) == 0 && !(*pfield<uint8_t>(parts, i, parts->off_flags) & 1u), SHQ_ERR_STATE,
+                  "%s: the walk touched a particle that is not live gas", who);
+        char *s = static_cast<char *>(gas->base) + (size_t) *pfield<int32_t>(parts, i, parts->off_pi) * gas->elsize;
+        *pfield_w<float>(parts, i, parts->off_mass) = (float) r[0];
+        *reinterpret_cast<double *>(s + gas->off_density) = r[1];
+        *reinterpret_cast<double *>(s + gas->off_metallicity) = r[2];
+        for(int m = 0; m < SHQ_NMETALS; m++)
+            reinterpret_cast<float *>(s + gas->off_metals)[m] = (float) r[3 + m];
+    }
+    /* the gas masses (and densities) changed in the caller's records only: the context's particle and SPH copies are no longer the views */
+    ctx->inputs_current &= ~(SHQ_CURRENT_PARTICLES | SHQ_CURRENT_SPH);
+    return SHQ_OK;
+}
+} // namespace
+
 extern "C" int shq_metal_return(shq_context *ctx, const shq_tree_view *tree, const shq_part_view *parts, const shq_gas_metal_view *gas, const int32_t *queue,
                                 int64_t nqueue, const double *StarVolumeSPH, const double *MassGenerated, const double *MetalGenerated,
                                 const double *MetalSpeciesGenerated, double MaxGasMass, int SPHWeighting, int DensityKernelType, double *MassReturn, int64_t *npairs)
@@ -1548,81 +1625,161 @@ extern "C" int shq_metal_return(shq_context *ctx, const shq_tree_view *tree, con
     if(nq == 0)
         return SHQ_OK;
     hipStream_t st = ctx->stream;
-    const size_t cap = (size_t) std::max<int64_t>(n, 1);
-    std::vector<float> gf(cap * (1 + SHQ_NMETALS), 0.f);
-    std::vector<double> gd(cap * 2, 1.0);
-    float *hm = gf.data(), *hz = gf.data() + cap;
-    double *hd = gd.data(), *hy = gd.data() + cap;
-    auto slot = [&](int64_t i) { return static_cast<char *>(gas->base) + (size_t) *pfield<int32_t>(parts, i, parts->off_pi) * gas->elsize; };
-    for(int64_t i = 0; i < n; i++) {
-        hm[i] = *pfield<float>(parts, i, parts->off_mass);
-        if(*pfield<uint8_t>(parts, i, parts->off_type) != 0 || (*pfield<uint8_t>(parts, i, parts->off_flags) & 1u))
-            continue;
-        const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
-        SHQ_CHECK(pi >= 0 && pi < gas->numslots, SHQ_ERR_INVALID, "metal_return: gas particle %ld has PI %d outside the slot array", (long) i, pi);
-        const char *s = slot(i);
-        hd[i] = *reinterpret_cast<const double *>(s + gas->off_density);
-        hy[i] = *reinterpret_cast<const double *>(s + gas->off_metallicity);
-        for(int m = 0; m < SHQ_NMETALS; m++)
-            hz[(size_t) i * SHQ_NMETALS + m] = reinterpret_cast<const float *>(s + gas->off_metals)[m];
-    }
-    SHQ_TRY(ctx->metal_gf.reserve(gf.size()));
-    SHQ_TRY(ctx->metal_gd.reserve(gd.size()));
+    MetalWalkArgs w;
+    memset(&w, 0, sizeof(w));
+    SHQ_TRY(metal_gas_upload(ctx, parts, gas, &w, "metal_return"));
     SHQ_TRY(ctx->metal_star.reserve((size_t) nq * (4 + SHQ_NMETALS)));
     SHQ_TRY(ctx->bhw_queue.reserve((size_t) nq));
-    SHQ_HIP(hipMemcpyAsync(ctx->metal_gf.ptr, gf.data(), sizeof(float) * gf.size(), hipMemcpyHostToDevice, st));
-    SHQ_HIP(hipMemcpyAsync(ctx->metal_gd.ptr, gd.data(), sizeof(double) * gd.size(), hipMemcpyHostToDevice, st));
     double *ds = ctx->metal_star.ptr;
     SHQ_HIP(hipMemcpyAsync(ds, StarVolumeSPH, sizeof(double) * (size_t) nq, hipMemcpyHostToDevice, st));
     SHQ_HIP(hipMemcpyAsync(ds + nq, MassGenerated, sizeof(double) * (size_t) nq, hipMemcpyHostToDevice, st));
     SHQ_HIP(hipMemcpyAsync(ds + 2 * nq, MetalGenerated, sizeof(double) * (size_t) nq, hipMemcpyHostToDevice, st));
     SHQ_HIP(hipMemcpyAsync(ds + 4 * nq, MetalSpeciesGenerated, sizeof(double) * (size_t) nq * SHQ_NMETALS, hipMemcpyHostToDevice, st));
     SHQ_HIP(hipMemcpyAsync(ctx->bhw_queue.ptr, queue, sizeof(int32_t) * (size_t) nq, hipMemcpyHostToDevice, st));
-    MetalWalkArgs w;
-    memset(&w, 0, sizeof(w));
     w.SPHWeighting = SPHWeighting;
     w.MaxGasMass = MaxGasMass;
     w.starvolume = ds;
     w.massgenerated = ds + nq;
     w.metalgenerated = ds + 2 * nq;
     w.speciesgenerated = ds + 4 * nq;
-    w.gmass = ctx->metal_gf.ptr;
-    w.gmetals = ctx->metal_gf.ptr + cap;
-    w.gdensity = ctx->metal_gd.ptr;
-    w.gmetallicity = ctx->metal_gd.ptr + cap;
-    /* the gas the return changes comes back as rows of the particles it touched */
-    SHQ_TRY(ctx->bhw_touched.reserve(cap));
-    SHQ_TRY(ctx->bhw_tlist.reserve(cap));
-    SHQ_HIP(hipMemsetAsync(ctx->bhw_touched.ptr, 0, cap, st));
-    w.touched = ctx->bhw_touched.ptr;
+    w.star_stride = 1;
+    w.species_stride = SHQ_NMETALS;
     SHQ_TRY(shq_metal_return_device(ctx, &w, DensityKernelType, tree->BoxSize, ctx->bhw_queue.ptr, nq, ds + 3 * nq, npairs));
-    int64_t nt = 0;
-    SHQ_TRY(shq_marked_list(ctx, ctx->bhw_touched.ptr, n, ctx->bhw_tlist.ptr, &nt));
-    const size_t W = 3 + SHQ_NMETALS;
-    SHQ_TRY(ctx->bhw_trows.reserve(W * (size_t) std::max<int64_t>(nt, 1)));
-    std::vector<double> rows(W * (size_t) std::max<int64_t>(nt, 1));
-    std::vector<int32_t> tl((size_t) std::max<int64_t>(nt, 1));
     SHQ_HIP(hipMemcpyAsync(MassReturn, ds + 3 * nq, sizeof(double) * (size_t) nq, hipMemcpyDeviceToHost, st));
-    if(nt) {
-        SHQ_TRY(shq_metal_rows_gather(ctx, &w, ctx->bhw_tlist.ptr, nt, ctx->bhw_trows.ptr));
-        SHQ_HIP(hipMemcpyAsync(rows.data(), ctx->bhw_trows.ptr, sizeof(double) * W * (size_t) nt, hipMemcpyDeviceToHost, st));
-        SHQ_HIP(hipMemcpyAsync(tl.data(), ctx->bhw_tlist.ptr, sizeof(int32_t) * (size_t) nt, hipMemcpyDeviceToHost, st));
+    return metal_gas_writeback(ctx, parts, gas, &w, "metal_return");
+}
+
+/* ---- the parts of shq_metal_return for a multi-rank driver ---------------------------------------------------------------------------- */
+extern "C" int shq_metal_return_triples(shq_context *ctx, const shq_tree_view *tree, const shq_part_view *parts, const int32_t *queue, int64_t nqueue, int SPHWeighting,
+                                        int DensityKernelType, int64_t nlocal, const int32_t *ghost_owner, const int32_t *ghost_index, int nranks, int rank,
+                                        int64_t queue_offset, shq_metal_triple *triples, int64_t capacity, int64_t *counts, int64_t *ntriples)
+{
+    SHQ_CHECK(ctx && tree && parts && counts && ntriples && (nqueue == 0 || queue), SHQ_ERR_INVALID, "null argument");
+    SHQ_CHECK(ctx->sphrun.phase == 0, SHQ_ERR_STATE, "metal_return_triples: an SPH walk is open");
+    SHQ_CHECK(parts->off_hsml != SHQ_NOFIELD && parts->off_pi != SHQ_NOFIELD && parts->off_type != SHQ_NOFIELD && parts->off_flags != SHQ_NOFIELD, SHQ_ERR_INVALID,
+              "metal_return_triples: the particle view needs Hsml, PI, Type and the flag byte");
+    const int64_t n = parts->numpart, nq = nqueue, ng = n - nlocal;
+    SHQ_CHECK(nq >= 0 && nranks >= 1 && rank >= 0 && rank < nranks && nlocal >= 0 && nlocal <= n && (ng == 0 || (ghost_owner && ghost_index)) && capacity >= 0,
+              SHQ_ERR_INVALID, "metal_return_triples: bad counts (nqueue %ld, nlocal %ld of %ld, rank %d of %d)", (long) nq, (long) nlocal, (long) n, rank, nranks);
+    SHQ_CHECK(queue_offset >= 0 && queue_offset + nq < (1ll << 31), SHQ_ERR_INVALID,
+              "metal_return_triples: a global queue of 2^31 or more stars (offset %ld + %ld): the star position is 32 bits of a sort key", (long) queue_offset, (long) nq);
+    *ntriples = 0;
+    for(int r = 0; r < nranks; r++)
+        counts[r] = 0;
+    for(int64_t k = 0; k < nq; k++) {
+        const int32_t i = queue[k];
+        SHQ_CHECK(i >= 0 && i < nlocal, SHQ_ERR_INVALID, "metal_return_triples: queue[%ld] = %d is not one of this rank's own particles", (long) k, i);
+        SHQ_CHECK(*pfield<uint8_t>(parts, i, parts->off_type) == 4 && !(*pfield<uint8_t>(parts, i, parts->off_flags) & 1u), SHQ_ERR_INVALID,
+                  "metal_return_triples: particle %d in the queue is not a live star", i);
     }
+    for(int64_t g = 0; g < ng; g++)
+        SHQ_CHECK(ghost_owner[g] >= 0 && ghost_owner[g] < nranks && ghost_index[g] >= 0, SHQ_ERR_INVALID, "metal_return_triples: import %ld has owner %d, index %d",
+                  (long) g, ghost_owner[g], ghost_index[g]);
+    SHQ_HIP(hipSetDevice(ctx->device));
+    SHQ_TRY(shq_particles_upload(ctx, parts));
+    SHQ_TRY(shq_dynamics_upload(ctx, parts));
+    SHQ_TRY(shq_tree_upload(ctx, tree));
+    if(nq == 0)
+        return SHQ_OK;
+    hipStream_t st = ctx->stream;
+    SHQ_TRY(ctx->bhw_queue.reserve((size_t) nq));
+    SHQ_TRY(ctx->bhw_tlist.reserve(2 * (size_t) std::max<int64_t>(ng, 1)));
+    SHQ_TRY(ctx->bhw_ids.reserve((size_t) nranks));
+    SHQ_HIP(hipMemcpyAsync(ctx->bhw_queue.ptr, queue, sizeof(int32_t) * (size_t) nq, hipMemcpyHostToDevice, st));
+    int32_t *d_go = ctx->bhw_tlist.ptr, *d_gi = ctx->bhw_tlist.ptr + std::max<int64_t>(ng, 1);
+    if(ng > 0) {
+        SHQ_HIP(hipMemcpyAsync(d_go, ghost_owner, sizeof(int32_t) * (size_t) ng, hipMemcpyHostToDevice, st));
+        SHQ_HIP(hipMemcpyAsync(d_gi, ghost_index, sizeof(int32_t) * (size_t) ng, hipMemcpyHostToDevice, st));
+    }
+    MetalWalkArgs w;
+    memset(&w, 0, sizeof(w));
+    w.SPHWeighting = SPHWeighting;
+    int64_t nt = 0;
+    SHQ_TRY(shq_metal_triples_device(ctx, &w, DensityKernelType, tree->BoxSize, ctx->bhw_queue.ptr, nq, nlocal, d_go, d_gi, nranks, rank, queue_offset, ctx->bhw_ids.ptr, &nt));
+    std::vector<unsigned long long> hc((size_t) nranks);
+    SHQ_HIP(hipMemcpyAsync(hc.data(), ctx->bhw_ids.ptr, sizeof(unsigned long long) * (size_t) nranks, hipMemcpyDeviceToHost, st));
     SHQ_HIP(hipStreamSynchronize(st));
-    for(int64_t t = 0; t < nt; t++) {
-        const int64_t i = tl[(size_t) t];
-        const double *r = &rows[W * (size_t) t];
-        SHQ_CHECK(*pfield<uint8_t>(parts, i, parts->off_type) == 0 && !(*pfield<uint8_t>(parts, i, parts->off_flags) & 1u), SHQ_ERR_STATE,
-                  "metal_return: the walk touched a particle that is not live gas");
-        char *s = slot(i);
-        *pfield_w<float>(parts, i, parts->off_mass) = (float) r[0];
-        *reinterpret_cast<double *>(s + gas->off_density) = r[1];
-        *reinterpret_cast<double *>(s + gas->off_metallicity) = r[2];
-        for(int m = 0; m < SHQ_NMETALS; m++)
-            reinterpret_cast<float *>(s + gas->off_metals)[m] = (float) r[3 + m];
+    int64_t sum = 0;
+    for(int r = 0; r < nranks; r++)
+        sum += counts[r] = (int64_t) hc[(size_t) r];
+    SHQ_CHECK(sum == nt, SHQ_ERR_STATE, "metal_return_triples: the per-owner counts add up to %ld of %ld triples", (long) sum, (long) nt);
+    *ntriples = nt;
+    if(!triples)
+        return SHQ_OK;
+    SHQ_CHECK(capacity >= nt, SHQ_ERR_INVALID, "metal_return_triples: room for %ld triples, %ld found", (long) capacity, (long) nt);
+    if(nt > 0) {
+        SHQ_HIP(hipMemcpyAsync(triples, ctx->metal_trip.ptr, sizeof(shq_metal_triple) * (size_t) nt, hipMemcpyDeviceToHost, st));
+        SHQ_HIP(hipStreamSynchronize(st));
     }
-    /* the gas masses (and densities) changed in the caller's records only: the context's particle and SPH copies are no longer the views */
-    ctx->inputs_current &= ~(SHQ_CURRENT_PARTICLES | SHQ_CURRENT_SPH);
+    return SHQ_OK;
+}
+
+extern "C" int shq_metal_return_apply(shq_context *ctx, const shq_part_view *parts, const shq_gas_metal_view *gas, const shq_metal_triple *triples, int64_t n,
+                                      const double *star_table, int64_t nstars, double MaxGasMass, double *thismass)
+{
+    SHQ_CHECK(ctx && parts && gas && n >= 0 && nstars >= 0 && (n == 0 || (triples && star_table && thismass)), SHQ_ERR_INVALID, "null argument");
+    SHQ_CHECK(gas->nmetals == SHQ_NMETALS, SHQ_ERR_INVALID, "metal_return_apply: NMETALS = %d, the library was built for %d", gas->nmetals, SHQ_NMETALS);
+    SHQ_CHECK(parts->off_pi != SHQ_NOFIELD && parts->off_type != SHQ_NOFIELD && parts->off_flags != SHQ_NOFIELD, SHQ_ERR_INVALID,
+              "metal_return_apply: the particle view needs PI, Type and the flag byte");
+    SHQ_CHECK(nstars < (1ll << 31), SHQ_ERR_INVALID, "metal_return_apply: a global queue of 2^31 or more stars (%ld)", (long) nstars);
+    const int64_t np = parts->numpart;
+    for(int64_t k = 0; k < n; k++) {
+        const int32_t i = triples[k].part_index;
+        SHQ_CHECK(i >= 0 && i < np && *pfield<uint8_t>(parts, i, parts->off_type) == 0 && !(*pfield<uint8_t>(parts, i, parts->off_flags) & 1u), SHQ_ERR_INVALID,
+                  "metal_return_apply: triple %ld names particle %d, which is not a live gas particle of this set", (long) k, i);
+        SHQ_CHECK((int64_t) triples[k].star < nstars, SHQ_ERR_INVALID, "metal_return_apply: triple %ld names star %u of %ld", (long) k, triples[k].star, (long) nstars);
+        /* "StarVolumeSPH %g hsml %g" (metal_return.cpp:619) */
+        SHQ_CHECK(star_table[(size_t) triples[k].star * SHQ_METAL_STAR_NCOL] != 0, SHQ_ERR_INVALID, "metal_return_apply: StarVolumeSPH = 0 for star %u", triples[k].star);
+    }
+    if(n == 0)
+        return SHQ_OK;
+    SHQ_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    MetalWalkArgs w;
+    memset(&w, 0, sizeof(w));
+    SHQ_TRY(metal_gas_upload(ctx, parts, gas, &w, "metal_return_apply"));
+    SHQ_TRY(ctx->metal_star.reserve((size_t) nstars * SHQ_METAL_STAR_NCOL));
+    SHQ_TRY(ctx->metal_trip.reserve((size_t) n * sizeof(shq_metal_triple)));
+    SHQ_TRY(ctx->metal_val[1].reserve((size_t) n));
+    double *ds = ctx->metal_star.ptr;
+    SHQ_HIP(hipMemcpyAsync(ds, star_table, sizeof(double) * (size_t) nstars * SHQ_METAL_STAR_NCOL, hipMemcpyHostToDevice, st));
+    SHQ_HIP(hipMemcpyAsync(ctx->metal_trip.ptr, triples, sizeof(shq_metal_triple) * (size_t) n, hipMemcpyHostToDevice, st));
+    w.MaxGasMass = MaxGasMass;
+    w.starvolume = ds;
+    w.massgenerated = ds + 1;
+    w.metalgenerated = ds + 2;
+    w.speciesgenerated = ds + 3;
+    w.star_stride = w.species_stride = SHQ_METAL_STAR_NCOL;
+    SHQ_TRY(shq_metal_apply_device(ctx, &w, reinterpret_cast<const shq_metal_triple *>(ctx->metal_trip.ptr), n, ctx->metal_val[1].ptr));
+    SHQ_HIP(hipMemcpyAsync(thismass, ctx->metal_val[1].ptr, sizeof(double) * (size_t) n, hipMemcpyDeviceToHost, st));
+    return metal_gas_writeback(ctx, parts, gas, &w, "metal_return_apply");
+}
+
+extern "C" int shq_metal_return_sums(shq_context *ctx, const int32_t *qpos, const int32_t *owner, const int32_t *part_index, const double *thismass, int64_t n,
+                                     int64_t nqueue, double *MassReturn)
+{
+    SHQ_CHECK(ctx && n >= 0 && nqueue >= 0 && (n == 0 || (qpos && owner && part_index && thismass)) && (nqueue == 0 || MassReturn), SHQ_ERR_INVALID, "null argument");
+    for(int64_t k = 0; k < n; k++)
+        SHQ_CHECK(qpos[k] >= 0 && qpos[k] < nqueue && owner[k] >= 0 && part_index[k] >= 0, SHQ_ERR_INVALID,
+                  "metal_return_sums: triple %ld has queue position %d of %ld, owner %d, particle %d", (long) k, qpos[k], (long) nqueue, owner[k], part_index[k]);
+    if(nqueue == 0)
+        return SHQ_OK;
+    SHQ_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const size_t m = (size_t) std::max<int64_t>(n, 1);
+    SHQ_TRY(ctx->bhw_tlist.reserve(3 * m));
+    SHQ_TRY(ctx->bhw_trows.reserve(m));
+    SHQ_TRY(ctx->metal_star.reserve((size_t) nqueue));
+    int32_t *d_q = ctx->bhw_tlist.ptr, *d_o = d_q + m, *d_p = d_o + m;
+    if(n > 0) {
+        SHQ_HIP(hipMemcpyAsync(d_q, qpos, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, st));
+        SHQ_HIP(hipMemcpyAsync(d_o, owner, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, st));
+        SHQ_HIP(hipMemcpyAsync(d_p, part_index, sizeof(int32_t) * (size_t) n, hipMemcpyHostToDevice, st));
+        SHQ_HIP(hipMemcpyAsync(ctx->bhw_trows.ptr, thismass, sizeof(double) * (size_t) n, hipMemcpyHostToDevice, st));
+    }
+    SHQ_TRY(shq_metal_sums_device(ctx, d_q, d_o, d_p, ctx->bhw_trows.ptr, n, nqueue, ctx->metal_star.ptr));
+    SHQ_HIP(hipMemcpyAsync(MassReturn, ctx->metal_star.ptr, sizeof(double) * (size_t) nqueue, hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipStreamSynchronize(st));
     return SHQ_OK;
 }
 

@@ -28,6 +28,7 @@ struct StellarArgs {
     const double *rho_leaf;   /* gas density by leaf slot */
     double *starvol;          /* by particle index */
     int32_t *todo;
+    unsigned long long *hmax_tried; /* the largest trial radius any walk ran with or any star ends with, as the bits of a non-negative double */
 };
 
 template <int KT>
@@ -174,6 +175,14 @@ __global__ __launch_bounds__(256) void sph_stellar_kernel(const SphDev a, const 
             redo = ((R - L) < 1.0e-4 * L) ? 0 : 1;
         sa.todo[t] = redo ? (int32_t) pi : -1;
     }
+    /* what a sharded caller sizes its halo by: the walk searched with he[ST_NHSML - 1], and hs is the next start */
+    unsigned long long tried = valid ? (unsigned long long) __double_as_longlong(fmax(he[ST_NHSML - 1], a.hsml[pi])) : 0ull;
+    for(int off = 32; off > 0; off >>= 1) {
+        const unsigned long long o = __shfl_xor(tried, off);
+        tried = o > tried ? o : tried;
+    }
+    if(lane == 0 && tried > *(volatile unsigned long long *) sa.hmax_tried)
+        atomicMax(sa.hmax_tried, tried);
     unsigned int sn = nint;
     for(int off = 32; off > 0; off >>= 1)
         sn += __shfl_xor(sn, off);
@@ -221,6 +230,7 @@ int shq_sph_stellar_density_device(shq_context *ctx, const shq_stellar_params *p
     sa.starvol = d_starvol;
     sa.todo = ctx->s_todo.ptr;
     unsigned long long *nint = reinterpret_cast<unsigned long long *>(ctx->s_counters.ptr + 1);
+    sa.hmax_tried = nint + 2;
     int niter = 0;
     SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_SPH], st));
     SHQ_TRY(sph_redo_loop(ctx, d_queue, nq, "failed to converge the stellar density for %lld stars",
@@ -234,7 +244,7 @@ int shq_sph_stellar_density_device(shq_context *ctx, const shq_stellar_params *p
                           &niter));
     SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_T_SPH], st));
     if(stats)
-        SHQ_TRY(sph_fill_stats(ctx, stats, nq, niter, nint));
+        SHQ_TRY(sph_fill_stats(ctx, stats, nq, niter, nint, true));
     return SHQ_OK;
 }
 

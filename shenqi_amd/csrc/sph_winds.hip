@@ -272,7 +272,9 @@ __global__ __launch_bounds__(256) void metal_emit_kernel(const SphDev a, const i
 }
 
 /* one thread per run of equal gas particles in the (particle, star)-sorted list: metal_return_ngbiter's body, :622-660 */
-__global__ void metal_apply_kernel(long long npairs, const unsigned long long *__restrict__ keys, const double *__restrict__ wk, const MetalWalkArgs w, double *thismass_out)
+/* ord (may be NULL: the list itself is sorted): wk and thismass_out are indexed by ord[k], the place of sorted pair k in the caller's list */
+__global__ void metal_apply_kernel(long long npairs, const unsigned long long *__restrict__ keys, const uint32_t *__restrict__ ord, const double *__restrict__ wk,
+                                   const MetalWalkArgs w, double *thismass_out)
 {
 #pragma clang fp contract(off)
     const long long k0 = (long long) blockIdx.x * blockDim.x + threadIdx.x;
@@ -288,23 +290,24 @@ __global__ void metal_apply_kernel(long long npairs, const unsigned long long *_
         metals[i] = w.gmetals[(size_t) p * SHQ_NMETALS + i];
     for(long long k = k0; k < npairs && (unsigned) (keys[k] >> 32) == p; k++) {
         const unsigned t = (unsigned) (keys[k] & 0xffffffffull);
+        const size_t j = ord ? (size_t) ord[k] : (size_t) k, ts = (size_t) t * w.star_stride;
         const double volume = mass / density;
-        const double returnfraction = wk[k] * volume / w.starvolume[t];
-        const double thismass = returnfraction * w.massgenerated[t];
+        const double returnfraction = wk[j] * volume / w.starvolume[ts];
+        const double thismass = returnfraction * w.massgenerated[ts];
         if(mass + thismass > w.MaxGasMass) {
-            thismass_out[k] = 0;
+            thismass_out[j] = 0;
             continue;
         }
         for(int i = 0; i < SHQ_NMETALS; i++) {
-            const double tm = returnfraction * w.speciesgenerated[(size_t) t * SHQ_NMETALS + i];
+            const double tm = returnfraction * w.speciesgenerated[(size_t) t * w.species_stride + i];
             metals[i] = (float) ((metals[i] * mass + tm) / (mass + thismass));
         }
-        const double thismetal = returnfraction * w.metalgenerated[t];
+        const double thismetal = returnfraction * w.metalgenerated[ts];
         metallicity = (metallicity * mass + thismetal) / (mass + thismass);
         const double massfrac = (mass + thismass) / mass;
         mass = (float) (mass * massfrac);
         density *= massfrac;
-        thismass_out[k] = thismass;
+        thismass_out[j] = thismass;
     }
     w.gmass[p] = mass;
     w.gdensity[p] = density;
@@ -361,12 +364,10 @@ int shq_metal_rows_gather(shq_context *ctx, const MetalWalkArgs *w, const int32_
     return SHQ_OK;
 }
 
-int shq_metal_return_device(shq_context *ctx, MetalWalkArgs *w, int kernel_type, double BoxSize, const int32_t *d_queue, int64_t nq, double *d_massreturn, int64_t *npairs_out)
+/* the two emit passes: *np triples, (particle << 32 | queue position) in metal_keys[0] and wk in metal_val[0], in no particular order;
+ * both pairs of buffers hold *np entries on return */
+static int metal_emit_device(shq_context *ctx, MetalWalkArgs *w, int kernel_type, double BoxSize, const int32_t *d_queue, int64_t nq, unsigned long long *np_out)
 {
-    if(npairs_out)
-        *npairs_out = 0;
-    if(nq == 0)
-        return SHQ_OK;
     SHQ_CHECK(kernel_type == 1 || kernel_type == 2 || kernel_type == 4, SHQ_ERR_INVALID, "unknown DensityKernelType %d", kernel_type);
     hipStream_t st = ctx->stream;
     const long long nl = ctx->ntreeparts + SHQ_NMAXCHILD;
@@ -414,6 +415,19 @@ int shq_metal_return_device(shq_context *ctx, MetalWalkArgs *w, int kernel_type,
         } else
             SHQ_CHECK(h == np, SHQ_ERR_STATE, "metal_return: the two walks disagree on the number of pairs (%llu, %llu)", np, h);
     }
+    *np_out = np;
+    return SHQ_OK;
+}
+
+int shq_metal_return_device(shq_context *ctx, MetalWalkArgs *w, int kernel_type, double BoxSize, const int32_t *d_queue, int64_t nq, double *d_massreturn, int64_t *npairs_out)
+{
+    if(npairs_out)
+        *npairs_out = 0;
+    if(nq == 0)
+        return SHQ_OK;
+    hipStream_t st = ctx->stream;
+    unsigned long long np = 0;
+    SHQ_TRY(metal_emit_device(ctx, w, kernel_type, BoxSize, d_queue, nq, &np));
     if(npairs_out)
         *npairs_out = (int64_t) np;
     SHQ_HIP(hipMemsetAsync(d_massreturn, 0, sizeof(double) * (size_t) nq, st));
@@ -421,12 +435,184 @@ int shq_metal_return_device(shq_context *ctx, MetalWalkArgs *w, int kernel_type,
         return SHQ_OK;
     SHQ_TRY(prim_sort_pairs(ctx, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ctx->metal_val[0].ptr, ctx->metal_val[1].ptr, (size_t) np, 0, 64));
     /* thismass per pair, in (particle, star) order, into metal_val[0] */
-    metal_apply_kernel<<<dim3(nblk((long long) np)), dim3(256), 0, st>>>((long long) np, ctx->metal_keys[1].ptr, ctx->metal_val[1].ptr, *w, ctx->metal_val[0].ptr);
+    metal_apply_kernel<<<dim3(nblk((long long) np)), dim3(256), 0, st>>>((long long) np, ctx->metal_keys[1].ptr, nullptr, ctx->metal_val[1].ptr, *w, ctx->metal_val[0].ptr);
     SHQ_HIP(hipGetLastError());
     metal_rekey_kernel<<<dim3(nblk((long long) np)), dim3(256), 0, st>>>((long long) np, ctx->metal_keys[1].ptr, ctx->metal_keys[0].ptr);
     SHQ_HIP(hipGetLastError());
     SHQ_TRY(prim_sort_pairs(ctx, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ctx->metal_val[0].ptr, ctx->metal_val[1].ptr, (size_t) np, 0, 64));
     metal_sum_kernel<<<dim3(nblk((long long) np)), dim3(256), 0, st>>>((long long) np, ctx->metal_keys[1].ptr, ctx->metal_val[1].ptr, d_massreturn);
+    SHQ_HIP(hipGetLastError());
+    return SHQ_OK;
+}
+
+/* ---- the same return in the parts a multi-rank driver needs (shenqi_amd/dist.py:DistMetalReturn) -------------------------------------
+ * A triple that fell on an imported gas particle belongs to that particle's owner.  The route kernel rewrites every emitted triple to
+ * (owner, row at the owner, position in the global queue); two stable sorts, by (row, star) and then by owner, leave one list in
+ * owner order that the driver cuts by the per-owner counts.  The owner sorts what it gathered by (row, star) once more and applies it
+ * with metal_apply_kernel: the global queue order, whatever rank a star lives on. */
+#define METAL_ROUTE_LDS 1024 /* owners a workgroup counts in LDS before it adds to the global counts; more ranks count in global memory */
+__global__ __launch_bounds__(256) void metal_route_kernel(long long np, const unsigned long long *__restrict__ keys, long long nlocal, const int32_t *__restrict__ ghost_owner,
+                                                          const int32_t *__restrict__ ghost_index, int nranks, int rank, unsigned long long queue_offset,
+                                                          unsigned long long *__restrict__ routed, uint32_t *__restrict__ owner_out, unsigned long long *counts)
+{
+    __shared__ unsigned int hist[METAL_ROUTE_LDS];
+    const bool lds = nranks <= METAL_ROUTE_LDS;
+    if(lds)
+        for(int i = threadIdx.x; i < nranks; i += blockDim.x)
+            hist[i] = 0;
+    __syncthreads();
+    const long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if(k < np) {
+        const long long p = (long long) (keys[k] >> 32);
+        const unsigned long long t = keys[k] & 0xffffffffull;
+        const bool own = p < nlocal;
+        const unsigned o = (unsigned) (own ? rank : ghost_owner[p - nlocal]);
+        const unsigned idx = (unsigned) (own ? (int32_t) p : ghost_index[p - nlocal]);
+        routed[k] = ((unsigned long long) idx << 32) | (queue_offset + t);
+        owner_out[k] = o;
+        if(lds)
+            atomicAdd(&hist[o], 1u);
+        else
+            atomicAdd(&counts[o], 1ull);
+    }
+    __syncthreads();
+    if(lds)
+        for(int i = threadIdx.x; i < nranks; i += blockDim.x)
+            if(hist[i])
+                atomicAdd(&counts[i], (unsigned long long) hist[i]);
+}
+
+__global__ void metal_gather_u32_kernel(long long n, const uint32_t *__restrict__ src, const uint32_t *__restrict__ ord, uint32_t *out)
+{
+    const long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if(k < n)
+        out[k] = src[ord[k]];
+}
+
+__global__ void metal_trip_write_kernel(long long n, const uint32_t *__restrict__ owner_sorted, const uint32_t *__restrict__ ord, const unsigned long long *__restrict__ routed,
+                                        const double *__restrict__ wk, shq_metal_triple *out)
+{
+    const long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if(k >= n)
+        return;
+    const size_t j = ord[k];
+    shq_metal_triple T;
+    T.owner = (int32_t) owner_sorted[k];
+    T.part_index = (int32_t) (routed[j] >> 32);
+    T.star = (uint32_t) (routed[j] & 0xffffffffull);
+    T.pad_ = 0;
+    T.wk = wk[j];
+    out[k] = T;
+}
+
+int shq_metal_triples_device(shq_context *ctx, MetalWalkArgs *w, int kernel_type, double BoxSize, const int32_t *d_queue, int64_t nq, int64_t nlocal,
+                             const int32_t *d_ghost_owner, const int32_t *d_ghost_index, int nranks, int rank, int64_t queue_offset,
+                             unsigned long long *d_counts, int64_t *ntriples)
+{
+    hipStream_t st = ctx->stream;
+    *ntriples = 0;
+    SHQ_HIP(hipMemsetAsync(d_counts, 0, sizeof(unsigned long long) * (size_t) nranks, st));
+    if(nq == 0)
+        return SHQ_OK;
+    unsigned long long np = 0;
+    SHQ_TRY(metal_emit_device(ctx, w, kernel_type, BoxSize, d_queue, nq, &np));
+    if(np == 0)
+        return SHQ_OK;
+    SHQ_CHECK(np < (1ull << 32), SHQ_ERR_INVALID, "metal_return_triples: %llu triples, the sort orders are 32 bits", np);
+    for(auto &b : ctx->metal_u32)
+        SHQ_TRY(b.reserve((size_t) np));
+    SHQ_TRY(ctx->metal_trip.reserve((size_t) np * sizeof(shq_metal_triple)));
+    const long long n = (long long) np;
+    uint32_t *owner = ctx->metal_u32[0].ptr, *ord1 = ctx->metal_u32[1].ptr, *okey = ctx->metal_u32[2].ptr, *ord2 = ctx->metal_u32[3].ptr;
+    unsigned long long *routed = ctx->metal_keys[1].ptr;
+    metal_route_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, ctx->metal_keys[0].ptr, nlocal, d_ghost_owner, d_ghost_index, nranks, rank,
+                                                            (unsigned long long) queue_offset, routed, owner, d_counts);
+    SHQ_HIP(hipGetLastError());
+    /* by (row at the owner, star); the sorted keys themselves are not needed (they land on the emitted keys, which are done with) */
+    SHQ_TRY(prim_sort_pairs(ctx, routed, ctx->metal_keys[0].ptr, rocprim::counting_iterator<uint32_t>(0), ord1, (size_t) np, 0, 64));
+    /* then, stable, by owner */
+    metal_gather_u32_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, owner, ord1, okey);
+    SHQ_HIP(hipGetLastError());
+    unsigned bits = 1;
+    while(bits < 32 && (1ull << bits) < (unsigned long long) nranks)
+        bits++;
+    SHQ_TRY(prim_sort_pairs(ctx, okey, owner, ord1, ord2, (size_t) np, 0, bits)); /* `owner` is free again: every entry went into okey */
+    metal_trip_write_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, owner, ord2, routed, ctx->metal_val[0].ptr, reinterpret_cast<shq_metal_triple *>(ctx->metal_trip.ptr));
+    SHQ_HIP(hipGetLastError());
+    *ntriples = (int64_t) np;
+    return SHQ_OK;
+}
+
+__global__ void metal_trip_keys_kernel(long long n, const shq_metal_triple *__restrict__ trip, unsigned long long *keys, double *wk)
+{
+    const long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if(k >= n)
+        return;
+    keys[k] = ((unsigned long long) (uint32_t) trip[k].part_index << 32) | (unsigned long long) trip[k].star;
+    wk[k] = trip[k].wk;
+}
+
+int shq_metal_apply_device(shq_context *ctx, const MetalWalkArgs *w, const shq_metal_triple *d_trip, int64_t n, double *d_thismass)
+{
+    if(n == 0)
+        return SHQ_OK;
+    hipStream_t st = ctx->stream;
+    SHQ_CHECK(n < (1ll << 32), SHQ_ERR_INVALID, "metal_return_apply: %lld triples, the sort orders are 32 bits", (long long) n);
+    SHQ_TRY(ctx->metal_keys[0].reserve((size_t) n));
+    SHQ_TRY(ctx->metal_keys[1].reserve((size_t) n));
+    SHQ_TRY(ctx->metal_val[0].reserve((size_t) n));
+    SHQ_TRY(ctx->metal_u32[0].reserve((size_t) n));
+    metal_trip_keys_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, d_trip, ctx->metal_keys[0].ptr, ctx->metal_val[0].ptr);
+    SHQ_HIP(hipGetLastError());
+    /* the carried original index is the sort's value column */
+    SHQ_TRY(prim_sort_pairs(ctx, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, rocprim::counting_iterator<uint32_t>(0), ctx->metal_u32[0].ptr, (size_t) n, 0, 64));
+    metal_apply_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, ctx->metal_keys[1].ptr, ctx->metal_u32[0].ptr, ctx->metal_val[0].ptr, *w, d_thismass);
+    SHQ_HIP(hipGetLastError());
+    return SHQ_OK;
+}
+
+__global__ void metal_sums_key1_kernel(long long n, const int32_t *__restrict__ owner, const int32_t *__restrict__ pidx, unsigned long long *keys)
+{
+    const long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if(k < n)
+        keys[k] = ((unsigned long long) (uint32_t) owner[k] << 32) | (unsigned long long) (uint32_t) pidx[k];
+}
+
+/* the star's key in the upper half, as metal_sum_kernel reads it; the lower half is zero */
+__global__ void metal_sums_key2_kernel(long long n, const int32_t *__restrict__ qpos, const double *__restrict__ thismass, const uint32_t *__restrict__ ord,
+                                       unsigned long long *keys, double *val)
+{
+    const long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x;
+    if(k >= n)
+        return;
+    const size_t j = ord[k];
+    keys[k] = (unsigned long long) (uint32_t) qpos[j] << 32;
+    val[k] = thismass[j];
+}
+
+int shq_metal_sums_device(shq_context *ctx, const int32_t *d_qpos, const int32_t *d_owner, const int32_t *d_pidx, const double *d_thismass, int64_t n, int64_t nq,
+                          double *d_massreturn)
+{
+    hipStream_t st = ctx->stream;
+    if(nq > 0)
+        SHQ_HIP(hipMemsetAsync(d_massreturn, 0, sizeof(double) * (size_t) nq, st));
+    if(n == 0 || nq == 0)
+        return SHQ_OK;
+    SHQ_CHECK(n < (1ll << 32), SHQ_ERR_INVALID, "metal_return_sums: %lld triples, the sort orders are 32 bits", (long long) n);
+    for(int i = 0; i < 2; i++) {
+        SHQ_TRY(ctx->metal_keys[i].reserve((size_t) n));
+        SHQ_TRY(ctx->metal_val[i].reserve((size_t) n));
+    }
+    SHQ_TRY(ctx->metal_u32[0].reserve((size_t) n));
+    /* by (owner, particle) first, then, stable, by the star: the existing rekey, sort and sum with a wider key */
+    metal_sums_key1_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, d_owner, d_pidx, ctx->metal_keys[0].ptr);
+    SHQ_HIP(hipGetLastError());
+    SHQ_TRY(prim_sort_pairs(ctx, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, rocprim::counting_iterator<uint32_t>(0), ctx->metal_u32[0].ptr, (size_t) n, 0, 64));
+    metal_sums_key2_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, d_qpos, d_thismass, ctx->metal_u32[0].ptr, ctx->metal_keys[0].ptr, ctx->metal_val[0].ptr);
+    SHQ_HIP(hipGetLastError());
+    /* all 64 bits, the lower half being zero: a bit range that ends at bit 64 and does not start at 0 is beyond what the sort's small-size path compares */
+    SHQ_TRY(prim_sort_pairs(ctx, ctx->metal_keys[0].ptr, ctx->metal_keys[1].ptr, ctx->metal_val[0].ptr, ctx->metal_val[1].ptr, (size_t) n, 0, 64));
+    metal_sum_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, ctx->metal_keys[1].ptr, ctx->metal_val[1].ptr, d_massreturn);
     SHQ_HIP(hipGetLastError());
     return SHQ_OK;
 }

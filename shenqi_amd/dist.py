@@ -1546,6 +1546,189 @@ class GpuWindOps:
         return na.value
 
 
+# Metal return across ranks (libgadget/metal_return.cpp:464-530, stellar_density2.cpp:306-341).  The reference exports every dying
+# star's query to the ranks its kernel touches and updates the gas there under a spin lock, in thread-arrival order.  Here every rank
+# imports the gas records within reach of its slab (as DistWinds does), walks its own stars over local + ghost gas, and the walk only
+# emits (gas particle, star, kernel weight) triples: those that fell on ghosts travel to the ghosts' owners, every owner applies the
+# triples of a particle in the order of the GLOBAL queue (the ranks' queues one after the other), and the mass each triple moved
+# travels back to the star's rank.  The gas ends as in the undivided run with that queue, whatever the decomposition.
+class DistMetalReturn:
+    """P: numpy PARTICLE_DTYPE array of everything this rank owns (gas PI -> SphP, star PI -> the star slots), queue: rows of P, the
+    dying stars of the step in the order shq_metal_yields returned them.
+
+    A step's metal return is, per rank: shq_metal_yields (per star, local: ages, yields, the queue) -> stellar_density() below ->
+    run() below -> shq_metal_return_postprocess (per star, local: Mass -= MassReturn, TotalMassReturned, LastEnrichmentMyr).  The two
+    per-star calls need nothing from other ranks and stay outside this class.
+
+    ops.stellar_density(Pall, Sall, queue, params) -> (StarVolumeSPH by queue position, largest radius tried or None), Hsml of the
+        queue's stars updated in Pall;
+    ops.triples(Pall, nlocal, queue, ghost_owner, ghost_index, nranks, rank, queue_offset, SPHWeighting, kt) -> (triples: numpy array
+        of capi.METAL_TRIPLE_DTYPE sorted by (owner, part_index, star), counts per owner);
+    ops.apply(P, SphP, triples, star_table, MaxGasMass) -> thismass per triple, the gas of P / SphP updated;
+    ops.sums(qpos, owner, part_index, thismass, nqueue) -> MassReturn by queue position
+    (GpuMetalOps below; the CPU tests use restatements).  Nothing here has run on more than one GPU."""
+
+    def __init__(self, comm, decomp, ops, hfac=1.3):
+        self.comm, self.d, self.ops, self.hfac = comm, decomp, ops, hfac
+        self.nghost = self.ntriples_sent = self.nrounds = 0
+
+    def _allmax(self, v):
+        """v of every rank, as a list by rank"""
+        return self.comm.allreduce_sum_vec(np.eye(max(1, self.comm.size))[self.comm.rank] * float(v)).tolist()
+
+    def _import(self, P, SphP, reach_of_rank, with_sph):
+        """local rows + the other ranks' live gas within reach_of_rank[this rank] of the slab.  A ghost's record carries its owner and
+        its row there in fields the walks do not read (TopLeaf, GrNr); with_sph: its gas slot travels too, into slots after SphP's."""
+        comm, nloc = self.comm, len(P)
+        gas = np.flatnonzero((P["Type"] == 0) & ((P["Flags"] & 1) == 0))
+        G = P[gas].copy()
+        G["TopLeaf"] = comm.rank
+        G["GrNr"] = gas
+        rec = G.view(np.uint8).reshape(len(G), -1)
+        if with_sph:
+            rec = np.concatenate([rec, SphP[P["PI"][gas]].view(np.uint8).reshape(len(G), -1)], axis=1)
+        got = ghost_records(comm, self.d, torch.from_numpy(np.ascontiguousarray(G["Pos"][:, 0])), torch.zeros(len(G), dtype=torch.float64),
+                            torch.from_numpy(np.ascontiguousarray(rec)), reach_of_rank).numpy()
+        ng = self.nghost = len(got)
+        psz = P.dtype.itemsize
+        Pall = np.empty(nloc + ng, dtype=P.dtype)
+        Pall[:nloc] = P
+        Pall[nloc:] = np.ascontiguousarray(got[:, :psz]).view(P.dtype).reshape(ng)
+        if not with_sph:
+            return Pall, None
+        Sall = np.empty(len(SphP) + ng, dtype=SphP.dtype)
+        Sall[:len(SphP)] = SphP
+        Sall[len(SphP):] = np.ascontiguousarray(got[:, psz:]).view(SphP.dtype).reshape(ng)
+        Pall["PI"][nloc:] = len(SphP) + np.arange(ng)
+        return Pall, Sall
+
+    def stellar_density(self, P, SphP, queue, params):
+        """stellar_density() for the stars of `queue`: DistSPH.density's loop for star targets.  The halo starts at hfac x the largest
+        Hsml of the rank's queue; the loop repeats on a wider one whenever the largest radius tried, on any rank, left the halo (a
+        trial radius beyond it undercounts the neighbours and steers the iteration), every repeat from the saved Hsml.  Writes
+        P["Hsml"] of the stars; returns (StarVolumeSPH by queue position, number of import rounds)."""
+        queue = np.ascontiguousarray(queue, dtype=np.int32)
+        nq = len(queue)
+        h0 = P["Hsml"][queue].copy()
+        halo = self.hfac * (float(h0.max()) if nq else 0.0)
+        rounds = 0
+        while True:
+            rounds += 1
+            halos = self._allmax(halo)
+            Pall, Sall = self._import(P, SphP, halos, True)
+            Pall["Hsml"][queue] = h0
+            vol, tried = self.ops.stellar_density(Pall, Sall, queue, params)
+            # the largest radius the loop TRIED where the operator reports it (the device library does), else the Hsml it ended with
+            hmax = max(float(Pall["Hsml"][queue].max()), float(tried or 0.0)) if nq else 0.0
+            # every rank must agree on repeating
+            worst = max(h / max(hl, 1e-300) for h, hl in zip(self._allmax(hmax), halos)) if self.comm.multi else 0.0
+            if worst <= 1.0:
+                break
+            halo = self.hfac * max(hmax, halo)
+        P["Hsml"][queue] = Pall["Hsml"][queue]
+        self.nrounds = rounds
+        return np.asarray(vol, dtype=np.float64), rounds
+
+    def run(self, P, SphP, queue, StarVolumeSPH, MassGenerated, MetalGenerated, MetalSpeciesGenerated, MaxGasMass, SPHWeighting, kt):
+        """metal_return()'s treewalk for the stars of `queue` (per-star arrays by queue position).  Updates Mass of P and Density,
+        Metallicity, Metals of SphP for the gas this rank owns; returns MassReturn by local queue position."""
+        comm = self.comm
+        nloc, size = len(P), max(1, comm.size)
+        queue = np.ascontiguousarray(queue, dtype=np.int32)
+        nq = len(queue)
+        nqs = [int(x) for x in comm.allreduce_sum_vec(np.eye(size, dtype=np.int64)[comm.rank] * nq)]
+        off, total = sum(nqs[:comm.rank]), sum(nqs)
+        self.nghost = self.ntriples_sent = 0
+        if total == 0:          # "if(nqueue_total == 0) return", metal_return.cpp:500-503
+            return np.zeros(0)
+        # The star table of the global queue on every rank: dying stars per step are few next to the gas.  Should that ever not hold,
+        # this is the place to send a star's row only to the ranks its triples go to.
+        rows = np.zeros((nq, capi.METAL_STAR_NCOL))
+        if nq:
+            rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3:] = StarVolumeSPH, MassGenerated, MetalGenerated, np.reshape(MetalSpeciesGenerated, (nq, -1))
+        table, _ = comm.all_to_all_rows(torch.from_numpy(np.tile(rows, (size, 1))), [nq] * size)
+        table = np.ascontiguousarray(table.numpy())
+        reach = max(self._allmax(float(P["Hsml"][queue].max()) if nq else 0.0))
+        Pall, _ = self._import(P, SphP, [reach] * size, False)
+        trip, counts = self.ops.triples(Pall, nloc, queue, np.ascontiguousarray(Pall["TopLeaf"][nloc:], dtype=np.int32),
+                                        np.ascontiguousarray(Pall["GrNr"][nloc:], dtype=np.int32), size, comm.rank, off, SPHWeighting, kt)
+        self.ntriples_sent = len(trip) - int(counts[comm.rank])
+        # 24-byte records as three int64 words, to the owners; thismass comes back along the same counts: the order within a
+        # (source, destination) pair is kept, so no key travels back
+        words = torch.from_numpy(np.ascontiguousarray(trip).view(np.int64).reshape(len(trip), 3))
+        recv, rcounts = comm.all_to_all_rows(words, [int(c) for c in counts])
+        mine = np.ascontiguousarray(recv.numpy()).view(capi.METAL_TRIPLE_DTYPE).reshape(-1)
+        tm = np.ascontiguousarray(self.ops.apply(P, SphP, mine, table, MaxGasMass), dtype=np.float64)
+        back, _ = comm.all_to_all_rows(torch.from_numpy(tm.reshape(-1, 1)), rcounts)
+        back = np.ascontiguousarray(back.numpy()).reshape(-1)
+        return self.ops.sums((trip["star"].astype(np.int64) - off).astype(np.int32), trip["owner"], trip["part_index"], back, nq)
+
+
+class GpuMetalOps:
+    """DistMetalReturn's steps on the device library (shq_stellar_density, shq_metal_return_triples / _apply / _sums) through the host
+    mirror's tree builder."""
+
+    def __init__(self, ctx, BoxSize):
+        import shenqi_amd as sq
+        self.sq, self.ctx, self.L = sq, ctx, BoxSize
+
+    def _pman(self, Pall):
+        pman = self.sq.PartManager(len(Pall), self.L)
+        pman.Base[:] = Pall
+        return pman
+
+    def stellar_density(self, Pall, Sall, queue, params):
+        sq = self.sq
+        pman = self._pman(Pall)
+        tree = sq.force_tree_rebuild_mask(pman, sq.GASMASK)
+        queue = np.ascontiguousarray(queue, dtype=np.int32)
+        sp = capi.StellarParams(self.L, params.DesNumNgb, params.MaxNgbDeviation, params.SPHWeighting, params.DensityKernelType)
+        slots = Pall["PI"][queue]
+        vol = np.zeros(int(slots.max()) + 1 if len(queue) else 1)
+        st = capi.SphStats()
+        pv, tv, sv = pman.view(), tree.view(), capi.sph_view(Sall)
+        capi.check(capi.hip.shq_stellar_density(self.ctx.h, C.byref(tv), C.byref(pv), C.byref(sv), capi.ptr(queue), len(queue), C.byref(sp), capi.ptr(vol), C.byref(st)))
+        Pall["Hsml"] = pman.Base["Hsml"]
+        return vol[slots], float(st.hsml_max_tried)
+
+    def triples(self, Pall, nlocal, queue, ghost_owner, ghost_index, nranks, rank, queue_offset, SPHWeighting, kt):
+        sq = self.sq
+        pman = self._pman(Pall)
+        tree = sq.force_tree_rebuild_mask(pman, sq.GASMASK)
+        queue = np.ascontiguousarray(queue, dtype=np.int32)
+        pv, tv = pman.view(), tree.view()
+        counts = np.zeros(nranks, dtype=np.int64)
+        nt = C.c_int64()
+
+        def call(trip, cap):
+            return capi.hip.shq_metal_return_triples(self.ctx.h, C.byref(tv), C.byref(pv), capi.ptr(queue), len(queue), SPHWeighting, kt, nlocal, capi.ptr(ghost_owner),
+                                                     capi.ptr(ghost_index), nranks, rank, queue_offset, trip, cap, capi.ptr(counts), C.byref(nt))
+        capi.check(call(None, 0))
+        trip = np.zeros(max(nt.value, 1), dtype=capi.METAL_TRIPLE_DTYPE)
+        capi.check(call(capi.ptr(trip), len(trip)))
+        return trip[:nt.value], counts
+
+    def apply(self, P, SphP, triples, star_table, MaxGasMass):
+        pman = self._pman(P)
+        triples = np.ascontiguousarray(triples, dtype=capi.METAL_TRIPLE_DTYPE)
+        star_table = np.ascontiguousarray(star_table, dtype=np.float64)
+        f = SphP.dtype.fields
+        gv = capi.GasMetalView(SphP.ctypes.data, SphP.dtype.itemsize, len(SphP), f["Density"][1], f["Metallicity"][1], f["Metals"][1], 9, 0)
+        pv = pman.view()
+        tm = np.zeros(max(len(triples), 1))
+        capi.check(capi.hip.shq_metal_return_apply(self.ctx.h, C.byref(pv), C.byref(gv), capi.ptr(triples), len(triples), capi.ptr(star_table), len(star_table),
+                                                   MaxGasMass, capi.ptr(tm)))
+        P["Mass"] = pman.Base["Mass"]
+        return tm[:len(triples)]
+
+    def sums(self, qpos, owner, part_index, thismass, nqueue):
+        a = [np.ascontiguousarray(x, dtype=np.int32) for x in (qpos, owner, part_index)]
+        thismass = np.ascontiguousarray(thismass, dtype=np.float64)
+        out = np.zeros(max(nqueue, 1))
+        capi.check(capi.hip.shq_metal_return_sums(self.ctx.h, capi.ptr(a[0]), capi.ptr(a[1]), capi.ptr(a[2]), capi.ptr(thismass), len(thismass), nqueue, capi.ptr(out)))
+        return out[:nqueue]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The domain decomposition itself: domain_decompose_full (libgadget/domain.cpp:174-277).  The particle loops run in `ops` (GpuDomainOps:
 # shq_domain_* on the device; the tests' CPU stand-in: the restated procedures), the small serial stages are host functions, and this
