@@ -152,25 +152,75 @@ class Comm:
         recv, _ = self.all_to_all_rows(t, counts)
         return recv
 
+    # ---- collectives on small host values: RCCL moves device memory only, so they are staged on the device for it
+    def _cdev(self):
+        return torch.device("cuda") if self.backend == "nccl" else torch.device("cpu")
+
     def allreduce_sum(self, x):
         if not self.multi:
             return x
-        t = torch.tensor([x], dtype=torch.float64)
-        if self.backend == "nccl":
-            t = t.cuda()
+        t = torch.tensor([x], dtype=torch.float64).to(self._cdev())
         dist.all_reduce(t, group=self.group)
         return float(t.item())
 
     def allreduce_sum_vec(self, a):
-        """Element-wise sum over the ranks of a 1-D numpy array, in its own dtype (float64 or int64); every rank gets the same array."""
-        a = np.ascontiguousarray(a)
-        if not self.multi:
-            return a.copy()
-        t = torch.from_numpy(a.copy())
-        if self.backend == "nccl":
-            t = t.cuda()
+        """Element-wise sum over the ranks of a numpy array (or a CPU torch tensor) of any shape, in its own dtype (float64 or
+        int64); every rank gets the same new array, of the kind it gave."""
+        if torch.is_tensor(a):
+            return torch.from_numpy(self.allreduce_sum_vec(a.numpy()))
+        a = np.array(a, order="C")             # a copy: the reduction runs in place
+        if not self.multi or a.size == 0:      # the shape is the same on every rank
+            return a
+        t = torch.from_numpy(a).to(self._cdev())
         dist.all_reduce(t, group=self.group)
         return t.cpu().numpy()
+
+    def gather_scalar(self, v, dtype=np.float64):
+        """every rank's v as an array indexed by rank: float64, or int64 for counts (exact beyond 2^53)"""
+        a = np.zeros(self.size, dtype=dtype)
+        a[self.rank] = v
+        return self.allreduce_sum_vec(a)
+
+    def allgather_u64(self, a):
+        """every rank's uint64 array, concatenated in rank order"""
+        if not self.multi:
+            return np.asarray(a, dtype=np.uint64).copy()
+        n = self.gather_scalar(len(a), np.int64)
+        m = int(n.max())
+        mine = torch.zeros(max(m, 1), dtype=torch.int64)
+        mine[:len(a)] = torch.from_numpy(np.asarray(a, dtype=np.uint64).view(np.int64).copy())
+        mine = mine.to(self._cdev())
+        outs = [torch.empty_like(mine) for _ in range(self.size)]
+        dist.all_gather(outs, mine, group=self.group)
+        return np.concatenate([o.cpu().numpy()[:int(c)] for o, c in zip(outs, n)]).view(np.uint64)
+
+    def send_array(self, arr, dst):
+        """a (structured) numpy array to rank dst, as its length and its bytes; recv_array(src, dtype) takes it there"""
+        b = torch.from_numpy(np.frombuffer(arr.tobytes(), dtype=np.uint8).copy())
+        dist.send(torch.tensor([len(arr)], dtype=torch.int64).to(self._cdev()), dst, group=self.group)
+        if len(arr):
+            dist.send(b.to(self._cdev()), dst, group=self.group)
+
+    def recv_array(self, src, dtype):
+        n = torch.zeros(1, dtype=torch.int64).to(self._cdev())
+        dist.recv(n, src, group=self.group)
+        b = torch.zeros(int(n.item()) * dtype.itemsize, dtype=torch.uint8).to(self._cdev())
+        if int(n.item()):
+            dist.recv(b, src, group=self.group)
+        return np.frombuffer(b.cpu().numpy().tobytes(), dtype=dtype).copy()
+
+    def bcast_array(self, arr, dtype):
+        """rank 0's structured array on every rank"""
+        if not self.multi:
+            return arr
+        n = torch.tensor([len(arr) if self.rank == 0 else 0], dtype=torch.int64).to(self._cdev())
+        dist.broadcast(n, 0, group=self.group)
+        b = torch.zeros(int(n.item()) * dtype.itemsize, dtype=torch.uint8)
+        if self.rank == 0:
+            b = torch.from_numpy(np.frombuffer(arr.tobytes(), dtype=np.uint8).copy())
+        b = b.to(self._cdev())
+        dist.broadcast(b, 0, group=self.group)
+        return np.frombuffer(b.cpu().numpy().tobytes(), dtype=dtype).copy()
 
     def allreduce_power(self, sums):
         """powerspectrum_sum (powerspectrum.cpp:53-88): the raw P(k) sums (kk, power, nmodes, Norm) of every rank added up - kk, power
@@ -242,6 +292,17 @@ class SlabDecomp:
         """x extent of what rank r owns: its planes, and the boundary plane behind them when part of that is its own too"""
         return self.bounds[r] * self.cell, (self.bounds[r + 1] + (1 if self.ycuts[r + 1] > 0.0 else 0)) * self.cell
 
+    def reach_mask(self, d, x, halo):
+        """which of the positions x lie within `halo` (one length, or one per position) of what rank d owns, periodically:
+        a - halo <= x < b + halo for its x extent [a, b), or everything once that span covers the box.  x and a per-position
+        halo are both torch tensors or both numpy arrays; the mask is of the same kind."""
+        xp = torch if torch.is_tensor(x) else np
+        a, b = self.slab_range(d)
+        span = (b - a) + 2 * halo
+        near = xp.remainder(x - (a - halo), self.L) < span
+        wide = span >= self.L          # one answer for a plain length (the common one, False, costs no operation on x), else one per position
+        return near if wide is False else near | wide
+
 
 def balanced_bounds(comm, Nmesh, BoxSize, x, weights=None, plane_cost=0.0, y=None):
     """Plane boundaries giving every rank about the same share of the work (x: positions held by this rank, any
@@ -256,15 +317,7 @@ def balanced_bounds(comm, Nmesh, BoxSize, x, weights=None, plane_cost=0.0, y=Non
     cell = BoxSize / Nmesh
     plane = (torch.floor(x / cell).to(torch.int64) % Nmesh).cpu()
     w = None if weights is None else torch.as_tensor(weights).to(torch.float64).cpu()
-
-    def allsum(h):
-        if P > 1:
-            g = h.cuda() if comm.backend == "nccl" else h
-            dist.all_reduce(g, group=comm.group)
-            h = g.cpu()
-        return h
-
-    hist = allsum(torch.bincount(plane, weights=w, minlength=Nmesh).to(torch.float64))
+    hist = comm.allreduce_sum_vec(torch.bincount(plane, weights=w, minlength=Nmesh).to(torch.float64))
     cum = torch.cumsum(hist + float(plane_cost), 0).numpy()
     total = cum[-1]
     minp = SlabDecomp.MIN_PLANES + (0 if y is None else 1)
@@ -290,7 +343,7 @@ def balanced_bounds(comm, Nmesh, BoxSize, x, weights=None, plane_cost=0.0, y=Non
     for r in range(1, P):
         sel = plane == bounds[r]
         yh[r - 1] = torch.bincount(row[sel], weights=None if w is None else w[sel], minlength=Nmesh).to(torch.float64)
-    yh = allsum(yh).numpy() if P > 1 else yh.numpy()
+    yh = comm.allreduce_sum_vec(yh).numpy()
     ycuts = [0.0]
     for r in range(1, P):
         cy = np.cumsum(yh[r - 1])
@@ -346,28 +399,83 @@ def _split_types(rows, dtype):
     return rows[:, :4].contiguous(), rows[:, 4].to(dtype)
 
 
-def ghost_exchange(comm, decomp, posm, halo):
-    """Import every other rank's particles within `halo` (periodic) of this rank's slab.  Returns
-    the ghost rows (x, y, z, m) in source-rank order; a particle goes at most once to a rank."""
+def ghost_records(comm, decomp, x, reach, recs, reach_of_rank=None):
+    """Import the records (rows of a tensor) of other ranks' particles: a particle at x with own reach `reach` (a tensor) goes to
+    rank d if it lies within max(reach, reach_of_rank[d]) of d's slab (SlabDecomp.reach_mask); without reach_of_rank `reach` is one
+    length for all.  Returns the received rows in source-rank order; a particle goes at most once to a rank."""
     if not comm.multi:
-        return posm[:0]
-    L = decomp.L
-    x = posm[:, 0]
+        return recs[:0]
     parts, counts = [], [0] * comm.size
     for d in range(comm.size):
         if d == comm.rank:
             continue
-        a, b = decomp.slab_range(d)
-        span = (b - a) + 2 * halo
-        if span >= L:
-            sel = posm
-        else:
-            sel = posm[torch.remainder(x - (a - halo), L) < span]
-        parts.append(sel)
-        counts[d] = int(sel.shape[0])
-    send = torch.cat(parts, dim=0) if parts else posm[:0]
+        halo = reach if reach_of_rank is None else torch.clamp(reach, min=float(reach_of_rank[d]))
+        parts.append(recs[decomp.reach_mask(d, x, halo)])
+        counts[d] = int(parts[-1].shape[0])
+    send = torch.cat(parts, dim=0) if parts else recs[:0]
     recv, _ = comm.all_to_all_rows(send, counts)
     return recv
+
+
+def ghost_exchange(comm, decomp, posm, halo):
+    """Import every other rank's particles (rows x, y, z, m) within `halo` (periodic) of this rank's slab"""
+    return ghost_records(comm, decomp, posm[:, 0], halo, posm)
+
+
+def append_records(local, got):
+    """the records `local` followed by those in the rows of `got` (uint8, one record each), e.g. what ghost_records returned.  Not
+    np.concatenate: it repacks structured dtypes (sph_particle_data's padding would go, 176 -> 168 bytes)."""
+    n, ng = len(local), len(got)
+    out = np.empty(n + ng, dtype=local.dtype)
+    out[:n] = local
+    out[n:] = np.ascontiguousarray(got).view(local.dtype).reshape(ng)
+    return out
+
+
+def import_ghost_gas(comm, decomp, P, SphP, reach, reach_of_rank):
+    """P (everything this rank owns) followed by the other ranks' live gas within reach of this rank's slab, by ghost_records' rule
+    (reach: one length per live gas particle of P, or None for 0).  A ghost's record carries its owner and its row there in fields
+    the walks do not read (TopLeaf, GrNr).  With SphP the ghosts' gas slots travel too, into slots after SphP's (PI rewritten).
+    Returns (Pall, Sall or None, number of ghosts)."""
+    nloc = len(P)
+    gas = np.flatnonzero((P["Type"] == 0) & ((P["Flags"] & 1) == 0))
+    G = P[gas].copy()
+    G["TopLeaf"] = comm.rank
+    G["GrNr"] = gas
+    rec = G.view(np.uint8).reshape(len(G), -1)
+    if SphP is not None:
+        rec = np.concatenate([rec, SphP[P["PI"][gas]].view(np.uint8).reshape(len(G), -1)], axis=1)
+    reach = torch.zeros(len(G), dtype=torch.float64) if reach is None else torch.from_numpy(reach)
+    got = ghost_records(comm, decomp, torch.from_numpy(np.ascontiguousarray(G["Pos"][:, 0])), reach,
+                        torch.from_numpy(np.ascontiguousarray(rec)), reach_of_rank).numpy()
+    ng, psz = len(got), P.dtype.itemsize
+    Pall = append_records(P, got[:, :psz])
+    if SphP is None:
+        return Pall, None, ng
+    Sall = append_records(SphP, got[:, psz:])
+    Pall["PI"][nloc:] = len(SphP) + np.arange(ng)
+    return Pall, Sall, ng
+
+
+def widen_until_covered(comm, hfac, start_radius, attempt):
+    """The repeat-on-a-wider-halo protocol of the operators that iterate a search radius (the Hsml loops of density and
+    stellar_density).  Every rank starts with the halo hfac x start_radius (the largest radius of its targets) and calls
+    attempt(halos), halos being every rank's halo by rank: it restores the targets' saved radii, imports the ghosts within the
+    halos, runs the operator and returns the largest radius the loop TRIED on this rank (0.0 with no targets) - not the one it ended
+    with: a guess that reaches past the imported ghosts undercounts the neighbours, which steers the guesses after it, so a loop
+    whose guesses left the halo is run again even if it came back inside (the reference runs every guess against all ranks,
+    treewalk2.h:480-557).  An operator that does not report the radii tried (the CPU stand-ins of the tests) gives the final one:
+    with hfac = 1.3 the first guess, at most 1.26 x the start value (densitytree2.hpp:233-246), cannot leave the halo.
+    The exit rule, the same on every rank: no rank tried a radius beyond its own halo.  Otherwise every rank repeats with
+    hfac x max(tried, halo).  One rank alone has nothing to import and ends after the first round.  Returns the rounds it took."""
+    halo, rounds = hfac * start_radius, 0
+    while True:
+        rounds += 1
+        halos = comm.gather_scalar(halo)
+        tried = attempt(halos)
+        if not comm.multi or max(t / max(h, 1e-300) for t, h in zip(comm.gather_scalar(tried), halos)) <= 1.0:
+            return rounds
+        halo = hfac * max(tried, halo)
 
 
 class SlabPM:
@@ -529,6 +637,47 @@ class SlabPM:
         self.ops.readout(ext, self.d.plane0, nxl, pr)
 
 
+class _StreamHandover:
+    """The hand-over between torch's current stream and the library context's, around a library call on tensors: before() once
+    torch has produced the call's inputs, after() once the library has written its outputs."""
+
+    def __init__(self, ctx, device):
+        self.ctx, self.device = ctx, device
+
+    def _shared(self):
+        """The context was created on torch's current stream: library kernels and torch operators are ordered by the stream
+        itself (and the RCCL rounds join it through their work handles), so no host synchronisation is needed anywhere in a
+        step.  With a stream of its own (the tests) every hand-over is a full synchronisation of the producing stream."""
+        if os.environ.get("SHQ_DIST_SYNC", "0") == "1":      # diagnostic: synchronise around every phase anyway
+            return False
+        s = getattr(self.ctx, "stream", None)      # 0 is the null stream: shq_init then made a stream of its own
+        return bool(s) and int(s) == int(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def before(self):
+        if not self._shared():
+            torch.cuda.current_stream(self.device).synchronize()
+
+    def after(self):
+        if not self._shared():
+            self.ctx.synchronize()
+
+
+def records_pman(sq, L, Pall):
+    """the host mirror's particle manager holding a copy of the records Pall (what its tree builder and views take)"""
+    pman = sq.PartManager(len(Pall), L)
+    pman.Base[:] = Pall
+    return pman
+
+
+def sized_call(call, count, dtype):
+    """The library's "how many, then fill" convention: call(buffer, capacity) runs once without a buffer, which leaves the number of
+    records in `count` (the c_int64 the call writes), and again with room for them.  Returns the records."""
+    capi.check(call(None, 0))
+    out = np.zeros(max(count.value, 1), dtype=dtype)
+    capi.check(call(capi.ptr(out), len(out)))
+    return out[:count.value]
+
+
 class GpuOps:
     """Local compute phases on the device through the C-ABI (libshenqi_hip.so)."""
 
@@ -536,26 +685,10 @@ class GpuOps:
         self.ctx, self.device = ctx, device
         self.pm = capi.PMParams(Nmesh, 0, BoxSize, Asmth, G)
         self.N = Nmesh
+        self._hand = _StreamHandover(ctx, device)
 
     def empty(self, shape, dtype):
         return torch.zeros(shape, dtype=dtype, device=self.device)
-
-    def _shared(self):
-        """The context was created on torch's current stream: library kernels and torch operators are ordered by the stream
-        itself (and the RCCL rounds join it through their work handles), so no host synchronisation is needed anywhere in a
-        step.  With a stream of its own (the tests) every hand-over is a full synchronisation of both streams."""
-        if os.environ.get("SHQ_DIST_SYNC", "0") == "1":      # diagnostic: synchronise around every phase anyway
-            return False
-        s = getattr(self.ctx, "stream", None)      # 0 is the null stream: shq_init then made a stream of its own
-        return bool(s) and int(s) == int(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _before(self):
-        if not self._shared():
-            torch.cuda.current_stream(self.device).synchronize()
-
-    def _after(self):
-        if not self._shared():
-            self.ctx.synchronize()
 
     def set_particles(self, posm_all, nlocal, keep_tree=False, types=None, carry=False):
         """posm_all: device tensor [n, 4] (x, y, z, m), the first nlocal rows are this rank's own.  keep_tree: these are the
@@ -566,11 +699,11 @@ class GpuOps:
         t = posm_all.contiguous()
         ty = None if types is None else types.to(device=t.device, dtype=torch.uint8).contiguous()
         flags = (capi.SET_KEEP_TREE if keep_tree else 0) | (capi.SET_CARRY_LOCAL if carry else 0)
-        self._before()                  # torch produced t on its stream; the library copies on its own
+        self._hand.before()                  # torch produced t on its stream; the library copies on its own
         capi.check(capi.hip.shq_particles_set_device(self.ctx.h, C.c_void_p(t.data_ptr()), t.shape[0], nlocal, flags))
         if ty is not None:
             capi.check(capi.hip.shq_particles_set_device_types(self.ctx.h, C.c_void_p(ty.data_ptr()), ty.shape[0]))
-        self._after()
+        self._hand.after()
         self._keep, self._keep_types = t, ty
 
     def set_deposit_types(self, mask):
@@ -589,9 +722,9 @@ class GpuOps:
         return self._mesh
 
     def _call(self, fn, *args):
-        self._before()
+        self._hand.before()
         capi.check(fn(self.ctx.h, *args))
-        self._after()
+        self._hand.after()
 
     def deposit2(self, buf, plane0, nxl, xoff, nalloc, ghosts=1):
         self._call(capi.hip.shq_pm_slab2_deposit_ghosts, C.byref(self.pm), plane0, nxl, xoff, nalloc, ghosts, C.c_void_p(buf.data_ptr()))
@@ -841,35 +974,14 @@ class DistTreePM:
 # densitytree2.hpp:260-344, hydratree2.hpp:151-228), once per Hsml iteration.  Here every rank imports, once per operator,
 # the records of the other ranks' gas within reach of its slab and runs the whole operator locally for its own targets:
 #   density: a neighbour j matters to target i if r_ij < Hsml_i           -> import within halo = hfac * max local Hsml;
-#            the Hsml loop may grow a target's Hsml past the halo: then the import is repeated with a larger one;
+#            the Hsml loop may grow a target's Hsml past the halo: then the import is repeated with a larger one
+#            (widen_until_covered above);
 #   hydro:   symmetric, r_ij < max(Hsml_i, Hsml_j) (hydratree2.hpp:258-259; the reference propagates hmax for this,
 #            run.cpp:493)                                                 -> a particle goes to rank d if it lies within
 #            max(its own Hsml, max Hsml of d's targets) of d's slab; its record carries the density results of its owner.
 # Records travel whole (particle_data 160 B + sph_particle_data 176 B), so predicted velocities and entropies of ghosts are
-# evaluated from the same fields as on their owner.
-
-
-def ghost_records(comm, decomp, x, reach, recs, reach_of_rank):
-    """Import the records (uint8 rows) of other ranks' particles: a particle at x with own reach `reach` goes to rank d if it
-    lies within max(reach, reach_of_rank[d]) of d's slab (periodic).  Returns the received rows in source-rank order."""
-    if not comm.multi:
-        return recs[:0]
-    L = decomp.L
-    parts, counts = [], [0] * comm.size
-    for d in range(comm.size):
-        if d == comm.rank:
-            continue
-        a, b = decomp.slab_range(d)
-        halo = torch.clamp(reach, min=float(reach_of_rank[d]))
-        span = (b - a) + 2 * halo
-        sel = (span >= L) | (torch.remainder(x - (a - halo), L) < span)
-        parts.append(recs[sel])
-        counts[d] = int(sel.sum())
-    send = torch.cat(parts, dim=0) if parts else recs[:0]
-    recv, _ = comm.all_to_all_rows(send, counts)
-    return recv
-
-
+# evaluated from the same fields as on their owner.  The operators on sets that hold more than gas (winds, metal return) import
+# through import_ghost_gas above, which stamps the ghosts with their owner and row.
 class DistSPH:
     """One rank of the sharded SPH operators.  `P` / `SphP`: numpy arrays (capi.PARTICLE_DTYPE / capi.SPH_DTYPE) of the gas this
     rank owns (PI = slot index).  `ops` runs an operator on local + ghost particles for the first `nloc` of them:
@@ -880,59 +992,32 @@ class DistSPH:
         self.comm, self.d, self.ops, self.hfac = comm, decomp, ops, hfac
         self.nghost = 0
 
-    def _allmax(self, v):
-        if not self.comm.multi:
-            return [float(v)] * max(1, self.comm.size)
-        t = torch.zeros(self.comm.size, dtype=torch.float64)
-        t[self.comm.rank] = float(v)
-        if self.comm.backend == "nccl":
-            t = t.cuda()
-        dist.all_reduce(t, group=self.comm.group)
-        return [float(x) for x in t.cpu()]
-
     def _import(self, P, SphP, reach, reach_of_rank):
-        """local + ghost records: ghosts get consecutive slots after the local ones"""
-        nloc = len(P)
-        rec = np.concatenate([P.view(np.uint8).reshape(nloc, -1), SphP[P["PI"]].view(np.uint8).reshape(nloc, -1)], axis=1)
+        """local + ghost records, everything gas: the slots in the order of the particles, PI = 0 .. n"""
+        nloc, S = len(P), SphP[P["PI"]]
+        rec = np.concatenate([P.view(np.uint8).reshape(nloc, -1), S.view(np.uint8).reshape(nloc, -1)], axis=1)
         got = ghost_records(self.comm, self.d, torch.from_numpy(np.ascontiguousarray(P["Pos"][:, 0])), torch.from_numpy(reach),
                             torch.from_numpy(rec), reach_of_rank).numpy()
-        ng = len(got)
-        self.nghost = ng
+        self.nghost = len(got)
         psz = P.dtype.itemsize
-        # not np.concatenate: it repacks structured dtypes (sph_particle_data's padding would go, 176 -> 168 bytes)
-        Pall = np.empty(nloc + ng, dtype=P.dtype)
-        Sall = np.empty(nloc + ng, dtype=SphP.dtype)
-        Pall[:nloc] = P
-        Sall[:nloc] = SphP[P["PI"]]
-        Pall[nloc:] = np.ascontiguousarray(got[:, :psz]).view(P.dtype).reshape(ng)
-        Sall[nloc:] = np.ascontiguousarray(got[:, psz:]).view(SphP.dtype).reshape(ng)
-        Pall["PI"] = np.arange(nloc + ng)
+        Pall, Sall = append_records(P, got[:, :psz]), append_records(S, got[:, psz:])
+        Pall["PI"] = np.arange(len(Pall))
         return Pall, Sall
 
     def density(self, P, SphP, **kw):
-        """density() for the local gas (Hsml loop included).  Returns the number of import rounds it took.
-        The repeat decision looks at the largest Hsml the loop TRIED (shq_sph_stats.hsml_max_tried; round 4): an intermediate guess
-        that reaches past the halo undercounts NumNgb, which changes the next guess, so a loop whose guesses left the halo is run
-        again on a wider one even if it came back inside.  (An operator that does not report it - the CPU stand-in of the tests -
-        falls back to the final Hsml: with hfac = 1.3 the first guess, at most 1.26 x the start value, densitytree2.hpp:233-246,
-        cannot leave the halo.)  The sharded tests assert Hsml against the undivided result to 1e-9."""
+        """density() for the local gas (Hsml loop included), by widen_until_covered.  Returns the number of import rounds it took.
+        ops.density returns the largest Hsml the loop tried where it can (shq_sph_stats.hsml_max_tried), else None."""
         nloc = len(P)
-        rounds = 0
-        halo = self.hfac * (float(P["Hsml"].max()) if nloc else 0.0)
         h0 = P["Hsml"].copy()
-        while True:
-            rounds += 1
-            halos = self._allmax(halo)
+        Pall = Sall = None
+
+        def attempt(halos):
+            nonlocal Pall, Sall
             Pall, Sall = self._import(P, SphP, np.zeros(nloc), halos)
             Pall["Hsml"][:nloc] = h0
             tried = self.ops.density(Pall, Sall, nloc, **kw)
-            # the largest Hsml the loop TRIED where the operator reports it (the device library does), else the one it ended with
-            hmax = max(float(Pall["Hsml"][:nloc].max()), float(tried or 0.0)) if nloc else 0.0
-            # every rank must agree on repeating: a target whose sphere outgrew the halo may have missed neighbours
-            worst = max(h / max(hl, 1e-300) for h, hl in zip(self._allmax(hmax), halos)) if self.comm.multi else 0.0
-            if worst <= 1.0 or not self.comm.multi:
-                break
-            halo = self.hfac * max(hmax, halo)
+            return max(float(Pall["Hsml"][:nloc].max()), float(tried or 0.0)) if nloc else 0.0
+        rounds = widen_until_covered(self.comm, self.hfac, float(h0.max()) if nloc else 0.0, attempt)
         for k in ("Hsml", "DtHsml"):
             P[k] = Pall[k][:nloc]
         for k in ("Density", "EgyWtDensity", "DhsmlEgyDensityFactor", "DivVel", "CurlVel"):
@@ -942,7 +1027,7 @@ class DistSPH:
     def hydro(self, P, SphP, **kw):
         """hydro_force() for the local gas; needs the density fields of density() above on every rank"""
         nloc = len(P)
-        hmax = self._allmax(float(P["Hsml"].max()) if nloc else 0.0)
+        hmax = self.comm.gather_scalar(float(P["Hsml"].max()) if nloc else 0.0)
         Pall, Sall = self._import(P, SphP, P["Hsml"].astype(np.float64), hmax)
         self.ops.hydro(Pall, Sall, nloc, **kw)
         for k in ("HydroAccel", "DtEntropy", "MaxSignalVel"):
@@ -988,66 +1073,37 @@ class DistSPHDevice:
         self.nghost = 0
         self.stats = {}
 
-    def _allmax(self, v):
-        if not self.comm.multi:
-            return [float(v)] * max(1, self.comm.size)
-        t = torch.zeros(self.comm.size, dtype=torch.float64)
-        t[self.comm.rank] = float(v)
-        if self.comm.backend == "nccl":
-            t = t.cuda()
-        dist.all_reduce(t, group=self.comm.group)
-        return [float(x) for x in t.cpu()]
-
-    def _shared(self, device):
-        """the context runs on torch's current stream (then the stream orders library kernels and torch operators); with a stream of
-        its own (the tests) every hand-over between torch and the library is a synchronisation of the producing stream"""
-        s = getattr(self.ctx, "stream", None)
-        return bool(s) and int(s) == int(torch.cuda.current_stream(device).cuda_stream)
-
-    def _before(self, device):
-        if not self._shared(device):
-            torch.cuda.current_stream(device).synchronize()
-
-    def _after(self, device):
-        if not self._shared(device):
-            self.ctx.synchronize()
-
     def _load(self, rows, reach, reach_of_rank):
         """import the ghosts, make local + ghost rows the resident set, build their tree"""
         ghosts = ghost_records(self.comm, self.d, rows[:, 0], reach, rows, reach_of_rank)
         allrows = torch.cat([rows, ghosts.to(rows.device)], dim=0).contiguous()
         self.nghost = int(ghosts.shape[0])
-        self._before(rows.device)        # torch produced allrows on its stream
+        self._hand = _StreamHandover(self.ctx, rows.device)
+        self._hand.before()        # torch produced allrows on its stream
         capi.check(capi.hip.shq_gas_set_device(self.ctx.h, allrows.data_ptr(), int(allrows.shape[0]), int(rows.shape[0])), "shq_gas_set_device")
         self.sq.tree_build_device(self.ctx, self.L, mask=self.sq.GASMASK)
         return allrows
 
     def _results(self, allrows, nloc, which):
         capi.check(capi.hip.shq_gas_get_device(self.ctx.h, allrows.data_ptr(), nloc, which), "shq_gas_get_device")
-        self._after(allrows.device)      # the library wrote allrows on its stream
+        self._hand.after()         # the library wrote allrows on its stream
 
     def density(self, rows, dp):
-        """density() for the local gas (Hsml loop included); rows are updated in place.  Returns the number of import rounds."""
+        """density() for the local gas (Hsml loop included), by widen_until_covered; rows are updated in place.  Returns the number
+        of import rounds."""
         nloc = int(rows.shape[0])
         h0 = rows[:, 7].clone()
-        halo = self.hfac * (float(h0.max().item()) if nloc else 0.0)
-        rounds = 0
         st = capi.SphStats()
-        while True:
-            rounds += 1
-            halos = self._allmax(halo)
+        allrows = None
+
+        def attempt(halos):
+            nonlocal allrows
             rows[:, 7] = h0
             allrows = self._load(rows, torch.zeros(nloc, dtype=torch.float64, device=rows.device), halos)
             capi.check(capi.hip.shq_density_resident(self.ctx.h, C.byref(dp), C.byref(st)), "shq_density_resident")
             self._results(allrows, nloc, 1)
-            # the halo must cover the largest Hsml the loop TRIED, not the one it ended with: a guess that reached past the imported
-            # ghosts undercounted NumNgb and steered the guesses after it (the reference runs every guess against all ranks,
-            # treewalk2.h:480-557)
-            hmax = max(float(st.hsml_max_tried), float(allrows[:nloc, 7].max().item())) if nloc else 0.0
-            worst = max(h / max(hl, 1e-300) for h, hl in zip(self._allmax(hmax), halos)) if self.comm.multi else 0.0
-            if worst <= 1.0 or not self.comm.multi:
-                break
-            halo = self.hfac * max(hmax, halo)
+            return max(float(st.hsml_max_tried), float(allrows[:nloc, 7].max().item())) if nloc else 0.0
+        rounds = widen_until_covered(self.comm, self.hfac, float(h0.max().item()) if nloc else 0.0, attempt)
         rows.copy_(allrows[:nloc])
         self.stats["density"] = dict(kernel_ms=float(st.kernel_ms), iterations=int(st.niterations), ninteractions=int(st.ninteractions), nghost=self.nghost)
         return rounds
@@ -1055,7 +1111,7 @@ class DistSPHDevice:
     def hydro(self, rows, hp):
         """hydro_force() for the local gas; needs the density fields of density() above on every rank"""
         nloc = int(rows.shape[0])
-        hmax = self._allmax(float(rows[:, 7].max().item()) if nloc else 0.0)
+        hmax = self.comm.gather_scalar(float(rows[:, 7].max().item()) if nloc else 0.0)
         allrows = self._load(rows, rows[:, 7].contiguous(), hmax)
         st = capi.SphStats()
         capi.check(capi.hip.shq_hydro_resident(self.ctx.h, C.byref(hp), C.byref(st)), "shq_hydro_resident")
@@ -1072,14 +1128,9 @@ class GpuSphOps:
         import shenqi_amd as sq
         self.sq, self.ctx, self.L = sq, ctx, BoxSize
 
-    def _pman(self, Pall):
-        pman = self.sq.PartManager(len(Pall), self.L)
-        pman.Base[:] = Pall
-        return pman
-
     def density(self, Pall, Sall, nloc, DoEgyDensity=1, kick=None, **_):
         sq = self.sq
-        pman = self._pman(Pall)
+        pman = records_pman(sq, self.L, Pall)
         tree = sq.force_tree_rebuild_mask(pman, sq.GASMASK)
         BhP = np.zeros(2, dtype=sq.BH_SLOT_DTYPE)
         _, st = sq.density(self.ctx, np.arange(nloc, dtype=np.int32), 1, DoEgyDensity, 0, kick, tree, pman, Sall, BhP)
@@ -1088,7 +1139,7 @@ class GpuSphOps:
 
     def hydro(self, Pall, Sall, nloc, atime=0.1, hubble=0.1, kick=None, **_):
         sq = self.sq
-        pman = self._pman(Pall)
+        pman = records_pman(sq, self.L, Pall)
         tree = sq.force_tree_rebuild_mask(pman, sq.GASMASK)
         sq.force_tree_update_hmax(tree, pman)
         sq.hydro_force(self.ctx, np.arange(nloc, dtype=np.int32), atime, hubble, None, kick, tree, pman, Sall)
@@ -1115,22 +1166,10 @@ class DistFOF:
         self.rounds = 0
         self.nghost = 0
 
-    def _allsum(self, v):
-        return int(round(self.comm.allreduce_sum(float(v)))) if self.comm.multi else int(v)
-
     def _selections(self, x, halo):
         """per destination rank: which of my particles it holds as ghosts (the same masks give the order of every later label
         message, so labels travel as bare uint64 rows)"""
-        L = self.d.L
-        sels = []
-        for dd in range(self.comm.size):
-            if dd == self.comm.rank or not self.comm.multi:
-                sels.append(None)
-                continue
-            a, b = self.d.slab_range(dd)
-            span = (b - a) + 2 * halo
-            sels.append(np.ones(len(x), dtype=bool) if span >= L else (np.remainder(x - (a - halo), L) < span))
-        return sels
+        return [None if dd == self.comm.rank or not self.comm.multi else self.d.reach_mask(dd, x, halo) for dd in range(self.comm.size)]
 
     def _send(self, rows, sels):
         parts, counts = [], [0] * self.comm.size
@@ -1151,20 +1190,11 @@ class DistFOF:
         ids = P["ID"].astype(np.uint64)
         # the largest radius the secondary search can reach: the first of 0.4 L 2^k (or 0.5 Hsml 2^k) that is >= 4 linking lengths
         hs = float(P["Hsml"].max()) if nloc else 0.0
-        halo = max(8.0 * linkl, hs if self.comm.multi else 0.0)
-        if comm.multi:
-            t = torch.tensor([halo], dtype=torch.float64)
-            t = t.cuda() if comm.backend == "nccl" else t
-            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=comm.group)
-            halo = float(t.item())
-        x = np.ascontiguousarray(P["Pos"][:, 0])
-        sels = self._selections(x, halo)
-        got = self._send(P.view(np.uint8).reshape(nloc, -1), sels) if comm.multi else P.view(np.uint8).reshape(nloc, -1)[:0]
-        ng = len(got)
-        self.nghost = ng
-        Pall = np.empty(nloc + ng, dtype=P.dtype)
-        Pall[:nloc] = P
-        Pall[nloc:] = np.ascontiguousarray(got).view(P.dtype).reshape(ng)
+        halo = float(comm.gather_scalar(max(8.0 * linkl, hs if comm.multi else 0.0)).max())
+        sels = self._selections(np.ascontiguousarray(P["Pos"][:, 0]), halo)
+        got = self._send(P.view(np.uint8).reshape(nloc, -1), sels)      # nothing on one rank
+        self.nghost = len(got)
+        Pall = append_records(P, got)
         idall = Pall["ID"].astype(np.uint64)
         prim = (((1 << Pall["Type"].astype(np.int64)) & primary_mask) != 0) & ((Pall["Flags"] & 3) == 0)
         # 1. local components of the primaries (label = smallest ID inside local + ghost)
@@ -1183,7 +1213,7 @@ class DistFOF:
             new = np.where(prim, low[comp], new)
             changed = int((new != lab).sum())
             lab = new
-            if self._allsum(changed) == 0:
+            if comm.allreduce_sum(float(changed)) == 0.0:      # a count, exact as a float
                 break
         # 3. secondary types: nearest primary; the primaries carry their final labels as IDs, everybody else its own ID
         ids2 = np.where(prim, lab, idall)
@@ -1228,7 +1258,7 @@ class DistFOF:
         mine = np.flatnonzero(ingroup & (ids == minid))
         fp[gidx[mine], :3] = P["Pos"][mine].astype(np.float32).astype(np.float64)
         fp[gidx[mine], 3] = 1.0
-        fp = self._sum_rows(fp)
+        fp = comm.allreduce_sum_vec(fp)
         host = fp[:, 3] > 0                    # exactly one owner per kept group holds the MinID particle
         first = fp[:, :3]
         hosted = np.zeros(ngk, dtype=bool)
@@ -1255,7 +1285,7 @@ class DistFOF:
                 np.add.at(S[:, 28 + k], g, mass * jm[:, k])
                 for k2 in range(3):
                     np.add.at(S[:, 19 + 3 * k + k2], g, mass * rel[:, k] * rel[:, k2])
-        S = self._sum_rows(S)
+        S = comm.allreduce_sum_vec(S)
         groups = []
         for gi in np.flatnonzero(hosted):
             s = S[gi]
@@ -1275,15 +1305,6 @@ class DistFOF:
         groups.sort(key=lambda G: G["MinID"])
         return groups
 
-    def _sum_rows(self, a):
-        if not self.comm.multi:
-            return a
-        t = torch.from_numpy(np.ascontiguousarray(a))
-        t = t.cuda() if self.comm.backend == "nccl" else t
-        dist.all_reduce(t, group=self.comm.group)
-        return t.cpu().numpy()
-
-
 class GpuFofOps:
     """DistFOF's labelling on the device library (shq_fof: tree of the primary types, linking, secondary attachment)."""
 
@@ -1294,8 +1315,7 @@ class GpuFofOps:
     def labels(self, Pall, ids, linkl, primary_mask, secondary_mask):
         sq = self.sq
         n = len(Pall)
-        pman = sq.PartManager(n, self.L)
-        pman.Base[:] = Pall
+        pman = records_pman(sq, self.L, Pall)
         pv = pman.view()
         capi.check(capi.hip.shq_particles_upload(self.ctx.h, C.byref(pv)))
         sq.dynamics_upload(self.ctx, pman)
@@ -1339,13 +1359,7 @@ class DistExchange:
 
     def _allsum(self, v):
         """element-wise sum of a small int64 vector over the ranks"""
-        if not self.comm.multi:
-            return np.asarray(v, dtype=np.int64)
-        t = torch.tensor(np.asarray(v, dtype=np.int64))
-        if self.comm.backend == "nccl":
-            t = t.cuda()
-        dist.all_reduce(t, group=self.comm.group)
-        return t.cpu().numpy()
+        return self.comm.allreduce_sum_vec(np.asarray(v, dtype=np.int64))
 
     def exchange(self, parts, numpart, slots, slot_size, layoutfn, maxlast=0, maxrounds=10000):
         comm, L, h = self.comm, self.L, self.ctx.h
@@ -1451,30 +1465,8 @@ class DistWinds:
         comm = self.comm
         nloc = len(P)
         newstars = np.asarray(newstars, dtype=np.int32)
-        reach = float(P["Hsml"][newstars].max()) if len(newstars) else 0.0
-        if comm.multi:
-            t = torch.tensor([reach], dtype=torch.float64)
-            if comm.backend == "nccl":
-                t = t.cuda()
-            dist.all_reduce(t, op=dist.ReduceOp.MAX, group=comm.group)
-            reach = float(t.item())
-        gas = np.flatnonzero((P["Type"] == 0) & ((P["Flags"] & 1) == 0))
-        # ghost gas: the record carries its owner and its index there in fields the walks do not read
-        G = P[gas].copy()
-        G["TopLeaf"] = comm.rank
-        G["GrNr"] = gas
-        rec = np.concatenate([G.view(np.uint8).reshape(len(G), -1), SphP[P["PI"][gas]].view(np.uint8).reshape(len(G), -1)], axis=1)
-        got = ghost_records(comm, self.d, torch.from_numpy(np.ascontiguousarray(G["Pos"][:, 0])), torch.zeros(len(G), dtype=torch.float64),
-                            torch.from_numpy(rec), [reach] * max(1, comm.size)).numpy()
-        ng = self.nghost = len(got)
-        psz = P.dtype.itemsize
-        Pall = np.empty(nloc + ng, dtype=P.dtype)
-        Pall[:nloc] = P
-        Pall[nloc:] = np.ascontiguousarray(got[:, :psz]).view(P.dtype).reshape(ng)
-        Sall = np.empty(len(SphP) + ng, dtype=SphP.dtype)
-        Sall[:len(SphP)] = SphP
-        Sall[len(SphP):] = np.ascontiguousarray(got[:, psz:]).view(SphP.dtype).reshape(ng)
-        Pall["PI"][nloc:] = len(SphP) + np.arange(ng)
+        reach = float(comm.gather_scalar(float(P["Hsml"][newstars].max()) if len(newstars) else 0.0).max())
+        Pall, Sall, self.nghost = import_ghost_gas(comm, self.d, P, SphP, None, [reach] * comm.size)
         tw, kicks = self.ops.candidates(Pall, Sall, StarP, newstars, prm, rnd)
         # a candidate goes to the owner of its particle, with the particle's index there
         part = kicks["part_index"].astype(np.int64)
@@ -1501,11 +1493,6 @@ class GpuWindOps:
         import shenqi_amd as sq
         self.sq, self.ctx, self.L = sq, ctx, BoxSize
 
-    def _pman(self, Pall):
-        pman = self.sq.PartManager(len(Pall), self.L)
-        pman.Base[:] = Pall
-        return pman
-
     def _params(self, prm):
         p = capi.WindParams()
         for k, _ in capi.WindParams._fields_:
@@ -1515,7 +1502,7 @@ class GpuWindOps:
 
     def candidates(self, Pall, Sall, StarP, newstars, prm, rnd):
         sq = self.sq
-        pman = self._pman(Pall)
+        pman = records_pman(sq, self.L, Pall)
         tree = sq.force_tree_rebuild_mask(pman, sq.GASMASK)
         ids = np.ascontiguousarray(Pall["ID"])
         new = np.ascontiguousarray(newstars, dtype=np.int32)
@@ -1525,15 +1512,14 @@ class GpuWindOps:
         stv = capi.StarView(StarP.ctypes.data, StarP.dtype.itemsize, len(StarP), StarP.dtype.fields["VDisp"][1])
         cp = self._params(prm)
         nk = C.c_int64()
-        capi.check(capi.hip.shq_winds_candidates(self.ctx.h, C.byref(tv), C.byref(pv), C.byref(sv), C.byref(stv), capi.ptr(ids), capi.ptr(new), len(new), C.byref(cp),
-                                                 capi.ptr(rnd), len(rnd), capi.ptr(tw), None, 0, C.byref(nk)))
-        kicks = np.zeros(max(nk.value, 1), dtype=capi.WIND_KICK_DTYPE)
-        capi.check(capi.hip.shq_winds_candidates(self.ctx.h, C.byref(tv), C.byref(pv), C.byref(sv), C.byref(stv), capi.ptr(ids), capi.ptr(new), len(new), C.byref(cp),
-                                                 capi.ptr(rnd), len(rnd), capi.ptr(tw), capi.ptr(kicks), len(kicks), C.byref(nk)))
-        return tw, kicks[:nk.value]
+
+        def call(kicks, cap):
+            return capi.hip.shq_winds_candidates(self.ctx.h, C.byref(tv), C.byref(pv), C.byref(sv), C.byref(stv), capi.ptr(ids), capi.ptr(new), len(new), C.byref(cp),
+                                                 capi.ptr(rnd), len(rnd), capi.ptr(tw), kicks, cap, C.byref(nk))
+        return tw, sized_call(call, nk, capi.WIND_KICK_DTYPE)
 
     def apply(self, P, SphP, kicks, prm, rnd):
-        pman = self._pman(P)
+        pman = records_pman(self.sq, self.L, P)
         ids = np.ascontiguousarray(P["ID"])
         rnd = np.ascontiguousarray(rnd, dtype=np.float64)
         kicks = np.ascontiguousarray(kicks, dtype=capi.WIND_KICK_DTYPE)
@@ -1572,71 +1558,33 @@ class DistMetalReturn:
         self.comm, self.d, self.ops, self.hfac = comm, decomp, ops, hfac
         self.nghost = self.ntriples_sent = self.nrounds = 0
 
-    def _allmax(self, v):
-        """v of every rank, as a list by rank"""
-        return self.comm.allreduce_sum_vec(np.eye(max(1, self.comm.size))[self.comm.rank] * float(v)).tolist()
-
-    def _import(self, P, SphP, reach_of_rank, with_sph):
-        """local rows + the other ranks' live gas within reach_of_rank[this rank] of the slab.  A ghost's record carries its owner and
-        its row there in fields the walks do not read (TopLeaf, GrNr); with_sph: its gas slot travels too, into slots after SphP's."""
-        comm, nloc = self.comm, len(P)
-        gas = np.flatnonzero((P["Type"] == 0) & ((P["Flags"] & 1) == 0))
-        G = P[gas].copy()
-        G["TopLeaf"] = comm.rank
-        G["GrNr"] = gas
-        rec = G.view(np.uint8).reshape(len(G), -1)
-        if with_sph:
-            rec = np.concatenate([rec, SphP[P["PI"][gas]].view(np.uint8).reshape(len(G), -1)], axis=1)
-        got = ghost_records(comm, self.d, torch.from_numpy(np.ascontiguousarray(G["Pos"][:, 0])), torch.zeros(len(G), dtype=torch.float64),
-                            torch.from_numpy(np.ascontiguousarray(rec)), reach_of_rank).numpy()
-        ng = self.nghost = len(got)
-        psz = P.dtype.itemsize
-        Pall = np.empty(nloc + ng, dtype=P.dtype)
-        Pall[:nloc] = P
-        Pall[nloc:] = np.ascontiguousarray(got[:, :psz]).view(P.dtype).reshape(ng)
-        if not with_sph:
-            return Pall, None
-        Sall = np.empty(len(SphP) + ng, dtype=SphP.dtype)
-        Sall[:len(SphP)] = SphP
-        Sall[len(SphP):] = np.ascontiguousarray(got[:, psz:]).view(SphP.dtype).reshape(ng)
-        Pall["PI"][nloc:] = len(SphP) + np.arange(ng)
-        return Pall, Sall
-
     def stellar_density(self, P, SphP, queue, params):
-        """stellar_density() for the stars of `queue`: DistSPH.density's loop for star targets.  The halo starts at hfac x the largest
-        Hsml of the rank's queue; the loop repeats on a wider one whenever the largest radius tried, on any rank, left the halo (a
-        trial radius beyond it undercounts the neighbours and steers the iteration), every repeat from the saved Hsml.  Writes
-        P["Hsml"] of the stars; returns (StarVolumeSPH by queue position, number of import rounds)."""
+        """stellar_density() for the stars of `queue`: the Hsml loop for star targets over local + ghost gas, by widen_until_covered
+        from the largest Hsml of the rank's queue.  Writes P["Hsml"] of the stars; returns (StarVolumeSPH by queue position, number of
+        import rounds)."""
         queue = np.ascontiguousarray(queue, dtype=np.int32)
         nq = len(queue)
         h0 = P["Hsml"][queue].copy()
-        halo = self.hfac * (float(h0.max()) if nq else 0.0)
-        rounds = 0
-        while True:
-            rounds += 1
-            halos = self._allmax(halo)
-            Pall, Sall = self._import(P, SphP, halos, True)
+        Pall = vol = None
+
+        def attempt(halos):
+            nonlocal Pall, vol
+            Pall, Sall, self.nghost = import_ghost_gas(self.comm, self.d, P, SphP, None, halos)
             Pall["Hsml"][queue] = h0
             vol, tried = self.ops.stellar_density(Pall, Sall, queue, params)
-            # the largest radius the loop TRIED where the operator reports it (the device library does), else the Hsml it ended with
-            hmax = max(float(Pall["Hsml"][queue].max()), float(tried or 0.0)) if nq else 0.0
-            # every rank must agree on repeating
-            worst = max(h / max(hl, 1e-300) for h, hl in zip(self._allmax(hmax), halos)) if self.comm.multi else 0.0
-            if worst <= 1.0:
-                break
-            halo = self.hfac * max(hmax, halo)
+            return max(float(Pall["Hsml"][queue].max()), float(tried or 0.0)) if nq else 0.0
+        self.nrounds = widen_until_covered(self.comm, self.hfac, float(h0.max()) if nq else 0.0, attempt)
         P["Hsml"][queue] = Pall["Hsml"][queue]
-        self.nrounds = rounds
-        return np.asarray(vol, dtype=np.float64), rounds
+        return np.asarray(vol, dtype=np.float64), self.nrounds
 
     def run(self, P, SphP, queue, StarVolumeSPH, MassGenerated, MetalGenerated, MetalSpeciesGenerated, MaxGasMass, SPHWeighting, kt):
         """metal_return()'s treewalk for the stars of `queue` (per-star arrays by queue position).  Updates Mass of P and Density,
         Metallicity, Metals of SphP for the gas this rank owns; returns MassReturn by local queue position."""
         comm = self.comm
-        nloc, size = len(P), max(1, comm.size)
+        nloc, size = len(P), comm.size
         queue = np.ascontiguousarray(queue, dtype=np.int32)
         nq = len(queue)
-        nqs = [int(x) for x in comm.allreduce_sum_vec(np.eye(size, dtype=np.int64)[comm.rank] * nq)]
+        nqs = [int(x) for x in comm.gather_scalar(nq, np.int64)]
         off, total = sum(nqs[:comm.rank]), sum(nqs)
         self.nghost = self.ntriples_sent = 0
         if total == 0:          # "if(nqueue_total == 0) return", metal_return.cpp:500-503
@@ -1648,8 +1596,8 @@ class DistMetalReturn:
             rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3:] = StarVolumeSPH, MassGenerated, MetalGenerated, np.reshape(MetalSpeciesGenerated, (nq, -1))
         table, _ = comm.all_to_all_rows(torch.from_numpy(np.tile(rows, (size, 1))), [nq] * size)
         table = np.ascontiguousarray(table.numpy())
-        reach = max(self._allmax(float(P["Hsml"][queue].max()) if nq else 0.0))
-        Pall, _ = self._import(P, SphP, [reach] * size, False)
+        reach = float(comm.gather_scalar(float(P["Hsml"][queue].max()) if nq else 0.0).max())
+        Pall, _, self.nghost = import_ghost_gas(comm, self.d, P, None, None, [reach] * size)
         trip, counts = self.ops.triples(Pall, nloc, queue, np.ascontiguousarray(Pall["TopLeaf"][nloc:], dtype=np.int32),
                                         np.ascontiguousarray(Pall["GrNr"][nloc:], dtype=np.int32), size, comm.rank, off, SPHWeighting, kt)
         self.ntriples_sent = len(trip) - int(counts[comm.rank])
@@ -1672,14 +1620,9 @@ class GpuMetalOps:
         import shenqi_amd as sq
         self.sq, self.ctx, self.L = sq, ctx, BoxSize
 
-    def _pman(self, Pall):
-        pman = self.sq.PartManager(len(Pall), self.L)
-        pman.Base[:] = Pall
-        return pman
-
     def stellar_density(self, Pall, Sall, queue, params):
         sq = self.sq
-        pman = self._pman(Pall)
+        pman = records_pman(sq, self.L, Pall)
         tree = sq.force_tree_rebuild_mask(pman, sq.GASMASK)
         queue = np.ascontiguousarray(queue, dtype=np.int32)
         sp = capi.StellarParams(self.L, params.DesNumNgb, params.MaxNgbDeviation, params.SPHWeighting, params.DensityKernelType)
@@ -1693,7 +1636,7 @@ class GpuMetalOps:
 
     def triples(self, Pall, nlocal, queue, ghost_owner, ghost_index, nranks, rank, queue_offset, SPHWeighting, kt):
         sq = self.sq
-        pman = self._pman(Pall)
+        pman = records_pman(sq, self.L, Pall)
         tree = sq.force_tree_rebuild_mask(pman, sq.GASMASK)
         queue = np.ascontiguousarray(queue, dtype=np.int32)
         pv, tv = pman.view(), tree.view()
@@ -1703,13 +1646,10 @@ class GpuMetalOps:
         def call(trip, cap):
             return capi.hip.shq_metal_return_triples(self.ctx.h, C.byref(tv), C.byref(pv), capi.ptr(queue), len(queue), SPHWeighting, kt, nlocal, capi.ptr(ghost_owner),
                                                      capi.ptr(ghost_index), nranks, rank, queue_offset, trip, cap, capi.ptr(counts), C.byref(nt))
-        capi.check(call(None, 0))
-        trip = np.zeros(max(nt.value, 1), dtype=capi.METAL_TRIPLE_DTYPE)
-        capi.check(call(capi.ptr(trip), len(trip)))
-        return trip[:nt.value], counts
+        return sized_call(call, nt, capi.METAL_TRIPLE_DTYPE), counts
 
     def apply(self, P, SphP, triples, star_table, MaxGasMass):
-        pman = self._pman(P)
+        pman = records_pman(self.sq, self.L, P)
         triples = np.ascontiguousarray(triples, dtype=capi.METAL_TRIPLE_DTYPE)
         star_table = np.ascontiguousarray(star_table, dtype=np.float64)
         f = SphP.dtype.fields
@@ -1755,52 +1695,8 @@ class DistDomain:
                 d = self.policies[i - 1]["SubSampleDistance"] // 2
             self.policies.append(dict(PreSort=int(i >= 2), SubSampleDistance=d, NTopLeaves=self.dodf * comm.size * (i + 1)))
 
-    # -- collectives on small host arrays
-    def _cdev(self):
-        return torch.device("cuda") if self.comm.backend == "nccl" else torch.device("cpu")
-
     def _any(self, flag):
         return int(self.comm.allreduce_sum_vec(np.array([int(bool(flag))], dtype=np.int64))[0]) > 0
-
-    def _allgather_u64(self, a):
-        """every rank's uint64 array, concatenated in rank order"""
-        if not self.comm.multi:
-            return np.asarray(a, dtype=np.uint64).copy()
-        n = self.comm.allreduce_sum_vec(np.eye(self.comm.size, dtype=np.int64)[self.comm.rank] * len(a))
-        m = int(n.max())
-        mine = torch.zeros(max(m, 1), dtype=torch.int64)
-        mine[:len(a)] = torch.from_numpy(np.asarray(a, dtype=np.uint64).view(np.int64).copy())
-        mine = mine.to(self._cdev())
-        outs = [torch.empty_like(mine) for _ in range(self.comm.size)]
-        dist.all_gather(outs, mine, group=self.comm.group)
-        return np.concatenate([o.cpu().numpy()[:int(c)] for o, c in zip(outs, n)]).view(np.uint64)
-
-    def _send(self, arr, dst):
-        b = torch.from_numpy(np.frombuffer(arr.tobytes(), dtype=np.uint8).copy())
-        dist.send(torch.tensor([len(arr)], dtype=torch.int64).to(self._cdev()), dst, group=self.comm.group)
-        if len(arr):
-            dist.send(b.to(self._cdev()), dst, group=self.comm.group)
-
-    def _recv(self, src, dtype):
-        n = torch.zeros(1, dtype=torch.int64).to(self._cdev())
-        dist.recv(n, src, group=self.comm.group)
-        b = torch.zeros(int(n.item()) * dtype.itemsize, dtype=torch.uint8).to(self._cdev())
-        if int(n.item()):
-            dist.recv(b, src, group=self.comm.group)
-        return np.frombuffer(b.cpu().numpy().tobytes(), dtype=dtype).copy()
-
-    def _bcast(self, arr, dtype):
-        """rank 0's structured array on every rank"""
-        if not self.comm.multi:
-            return arr
-        n = torch.tensor([len(arr) if self.comm.rank == 0 else 0], dtype=torch.int64).to(self._cdev())
-        dist.broadcast(n, 0, group=self.comm.group)
-        b = torch.zeros(int(n.item()) * dtype.itemsize, dtype=torch.uint8)
-        if self.comm.rank == 0:
-            b = torch.from_numpy(np.frombuffer(arr.tobytes(), dtype=np.uint8).copy())
-        b = b.to(self._cdev())
-        dist.broadcast(b, 0, group=self.comm.group)
-        return np.frombuffer(b.cpu().numpy().tobytes(), dtype=dtype).copy()
 
     # -- domain_nonrecursively_combine_topTree, :1178-1261
     def _combine(self, tree, MaxTopNodes):
@@ -1813,7 +1709,7 @@ class DistDomain:
                 if (comm.rank // sep) % 2 == 0:
                     src = comm.rank + sep
                     if src < comm.size:
-                        imp = self._recv(src, capi.LOCAL_TOPNODE_DTYPE)
+                        imp = comm.recv_array(src, capi.LOCAL_TOPNODE_DTYPE)
                         if size + len(imp) > MaxTopNodes:
                             errorflag = 1
                         elif len(imp) > 0 and not errorflag:
@@ -1825,10 +1721,10 @@ class DistDomain:
                 else:
                     dst = comm.rank - sep
                     if dst >= 0:
-                        self._send(tree, dst)
+                        comm.send_array(tree, dst)
                     size = -1
             sep *= 2
-        tree = self._bcast(tree, capi.LOCAL_TOPNODE_DTYPE)
+        tree = comm.bcast_array(tree, capi.LOCAL_TOPNODE_DTYPE)
         if len(tree) >= MaxTopNodes:
             errorflag = 1
         return (None if self._any(errorflag) else tree)
@@ -1838,9 +1734,9 @@ class DistDomain:
         ops, comm = self.ops, self.comm
         mine = np.asarray(ops.samples(pol["SubSampleDistance"], pol["PreSort"]), dtype=np.uint64)
         # mpsort_mpi: sorted across the ranks, every rank keeps as many as it gave
-        allk = np.sort(self._allgather_u64(mine), kind="stable")
+        allk = np.sort(comm.allgather_u64(mine), kind="stable")
         if comm.multi:
-            n = comm.allreduce_sum_vec(np.eye(comm.size, dtype=np.int64)[comm.rank] * len(mine))
+            n = comm.gather_scalar(len(mine), np.int64)
             off = int(n[:comm.rank].sum())
             mine = allk[off:off + len(mine)]
         else:
