@@ -1689,8 +1689,8 @@ typedef struct shq_uvbg_result {
 } shq_uvbg_result;
 /* calculate_uvbg for ONE rank (NTask == 1, as shq_fft_r2c): init_particle_uvbg, the deposit of mass, stellar mass x f_esc (Type 4) and,
  * with ReionUseParticleSFR, Sfr x f_esc (Type 0), one forward transform per field, then for every radius from min(ReionRBubbleMax, BoxSize)
- * down to the cell size the filter, the inverse transforms and reion_loop_pm, and readout_J21.  Several ranks (the x-slab route:
- * shq_pm_slab2_* with the caller's transposes once per radius) are not supported yet.
+ * down to the cell size the filter, the inverse transforms and reion_loop_pm, and readout_J21.  Several ranks run the same phases on
+ * x-slabs of the UVBGdim mesh with the caller's transposes between them: shq_uvbg_slab_* below.
  *   parts     : Pos, Mass and Type (off_type is required); with shq_set_inputs_current(SHQ_CURRENT_PARTICLES) and this very view resident
  *               (uploaded with its Type), the resident positions are read instead.  Every particle in [0, numpart) deposits its mass
  *               (petapm_reion has no regions and no active mask); swallowed particles included.
@@ -1705,6 +1705,56 @@ typedef struct shq_uvbg_result {
  * mask all survive the call.  Synchronous. */
 int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *params, const shq_uvbg_cosmo *cosmo, const shq_part_view *parts,
                        double *fesc, const double *sfr, double *local_J21, double *zreion, shq_uvbg_result *result);
+/* The phases of shq_uvbg_calculate on a rank's x-slab, for several ranks (shenqi_amd/dist.py, DistUVBG; INTEGRATION.md "reionisation on
+ * several ranks").  Every d_ pointer is device memory of the caller: d_posm = double[n][4] rows (x, y, z, m) and d_types = uint8[n]
+ * Types of the particles whose CIC base cell lies in this rank's planes, d_fesc / d_sfr / d_local_J21 / d_zreion = double[n].
+ * A mesh field is one buffer [nalloc][UVBGdim][zp] doubles (zp = shq_uvbg_slab_pitch, 0 for a mesh size without a bespoke transform)
+ * that is in turn the int64 deposit, the (y, z) half spectrum and the real mesh of a radius; the window (plane0, nplanes, xoff, nalloc,
+ * nghost) is shq_pm_slab2_deposit_ghosts': the slab's first own plane, global plane plane0, is buffer plane xoff, and one plane behind
+ * the own ones takes the deposit for the right-hand neighbour (nghost = 1).  One rank is plane0 = 0, xoff = 0, nalloc = UVBGdim.
+ * None of the calls reads or writes the PM's state (mesh, deposit scale, type mask, twiddles, pending spectrum).
+ *   slab_fesc     : init_particle_uvbg on d_fesc (in / out); sums = this rank's |Mass|, |Mass f_esc| (Type 4), |Sfr f_esc| (Type 0);
+ *                   *negative = 1 when a transformed escape fraction is negative (NOT an error here: the ranks must agree first, so
+ *                   the caller reduces the flag with the sums and refuses on every rank).  Writes nothing else.  Synchronous.
+ *   slab_deposit  : zeroes the two (three with ReionUseParticleSFR) buffers and deposits the fields in ONE particle pass in 64-bit
+ *                   fixed point, field f with the scale 2^(61 - exps[f]): exps[f] is the frexp exponent of the field's sum over ALL
+ *                   ranks (of 1.0 for a sum of 0), so every rank count deposits the same integers and ghost planes add exactly.
+ *                   A particle outside the window is SHQ_ERR_INVALID.  Synchronous.  Without a bespoke transform the pitch of
+ *                   the buffers is UVBGdim + 2.
+ *   slab_fft_yz   : shq_pm_slab2_fft_yz(_packed) with the scale as an argument: direction 0 takes `nplanes` int64 planes deposited
+ *                   with exponent `exp` to their (y, z) half spectrum, direction 1 goes back to real space (exp unused).  d_packed
+ *                   (NULL: in place) is shq_pm_slab2_fft_yz_packed's all-to-all buffer.
+ *   slab_xforward : X forward of the y-slab [UVBGdim][nyl][zp / 2] complex the all-to-all delivers, in place.  The spectrum stays
+ *                   there for the whole radius loop: a radius costs one all-to-all per field.
+ *   slab_tables   : the filter tables (shq_uvbg_filter_table, host) of radii[0 .. nradii - 2], kept on the device until the next call;
+ *                   the last radius is the unfiltered step.  Every rank makes the same tables.
+ *   slab_xfilter  : radius r of those tables on the kept spectrum d_spec: every mode (v / ncell) T[k2] - divide_by_ncell, then
+ *                   filter_pm, k2 from the signed (kx, ky = y0 + row, kz) - then the X inverse, stored OUT OF PLACE into d_out (same
+ *                   shape: what the return all-to-all sends).  d_spec is only read.
+ *   slab_filter   : the same factor for a mesh size without a bespoke transform, between the caller's own X transforms: d_spec =
+ *                   [UVBGdim][nyl][UVBGdim / 2 + 1] complex, dense, x slowest, into d_out of that shape (may be d_spec).
+ *   slab_cells    : reion_loop_pm of radius R over the nplanes own planes of the real meshes (pitch zp, from buffer plane xoff) and of
+ *                   the rank's dense float planes d_J21 / d_xHI [nplanes][UVBGdim][UVBGdim] (J21 = 0, xHI = 1 before the first
+ *                   radius).  last != 0: the unfiltered step; sums then takes this rank's sums of xHI, xHI density_over_mean and
+ *                   density_over_mean, from a fixed grid: two runs agree bit for bit (synchronous then).
+ *   slab_readout  : readout_J21 for this rank's gas: d_J21 = float [nalloc][UVBGdim][UVBGdim], the own planes and behind them the
+ *                   right-hand neighbour's first plane (nalloc = nplanes + 1; nplanes = UVBGdim: the periodic grid, nalloc = UVBGdim).
+ *                   Writes d_local_J21 / d_zreion of gas.  Synchronous. */
+int shq_uvbg_slab_pitch(int UVBGdim);
+int shq_uvbg_slab_fesc(shq_context *ctx, const shq_uvbg_params *params, const shq_uvbg_cosmo *cosmo, const void *d_posm, const void *d_types,
+                       int64_t n, void *d_fesc, const void *d_sfr, double sums[3], int *negative);
+int shq_uvbg_slab_deposit(shq_context *ctx, const shq_uvbg_params *params, const void *d_posm, const void *d_types, int64_t n,
+                          const void *d_fesc, const void *d_sfr, const int exps[3], int plane0, int nplanes, int xoff, int nalloc, int nghost,
+                          void *d_m0, void *d_m1, void *d_m2);
+int shq_uvbg_slab_fft_yz(shq_context *ctx, int UVBGdim, void *d_planes, int nplanes, int direction, int exp, void *d_packed, int nranks);
+int shq_uvbg_slab_xforward(shq_context *ctx, int UVBGdim, void *d_spec, int y0, int nyl);
+int shq_uvbg_slab_tables(shq_context *ctx, int filter_type, int UVBGdim, double BoxSize, const double *radii, int nradii);
+int shq_uvbg_slab_xfilter(shq_context *ctx, int UVBGdim, const void *d_spec, void *d_out, int y0, int nyl, int r);
+int shq_uvbg_slab_filter(shq_context *ctx, int UVBGdim, const void *d_spec, void *d_out, int y0, int nyl, int r);
+int shq_uvbg_slab_cells(shq_context *ctx, const shq_uvbg_params *params, const shq_uvbg_cosmo *cosmo, double R, int last, const void *d_mass,
+                        const void *d_star, const void *d_sfr, int zp, int xoff, int nplanes, void *d_J21, void *d_xHI, double sums[3]);
+int shq_uvbg_slab_readout(shq_context *ctx, const shq_uvbg_params *params, const shq_uvbg_cosmo *cosmo, const void *d_posm, const void *d_types,
+                          int64_t n, const void *d_J21, int plane0, int nplanes, int nalloc, void *d_local_J21, void *d_zreion);
 /* save_uvbg_grids' data: with shq_uvbg_keep_grids(ctx, 1) every later call copies its J21 and xHI grids to host memory of the context
  * (2 x 4 Nmesh^3 bytes); shq_uvbg_download_grids returns the last call's as dense [x][y][z] float (SHQ_ERR_STATE without one, SHQ_ERR_INVALID
  * for another Nmesh).  keep_grids(ctx, 0) frees them. */

@@ -724,6 +724,21 @@ hip.shq_uvbg_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 4)]
 hip.shq_uvbg_phase_ms.restype = C.c_int
 hip.shq_uvbg_filter_table.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, _vp]
 hip.shq_uvbg_filter_table.restype = C.c_int
+# the phases on a rank's x-slab (dist.DistUVBG): device pointers of torch tensors
+_UP, _UC = C.POINTER(UvbgParams), C.POINTER(UvbgCosmo)
+hip.shq_uvbg_slab_pitch.argtypes = [C.c_int]
+hip.shq_uvbg_slab_fesc.argtypes = [_vp, _UP, _UC, _vp, _vp, C.c_int64, _vp, _vp, C.POINTER(C.c_double * 3), C.POINTER(C.c_int)]
+hip.shq_uvbg_slab_deposit.argtypes = [_vp, _UP, _vp, _vp, C.c_int64, _vp, _vp, C.POINTER(C.c_int * 3)] + [C.c_int] * 5 + [_vp] * 3
+hip.shq_uvbg_slab_fft_yz.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int]
+hip.shq_uvbg_slab_xforward.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int]
+hip.shq_uvbg_slab_tables.argtypes = [_vp, C.c_int, C.c_int, C.c_double, _vp, C.c_int]
+hip.shq_uvbg_slab_xfilter.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int]
+hip.shq_uvbg_slab_filter.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int]
+hip.shq_uvbg_slab_cells.argtypes = [_vp, _UP, _UC, C.c_double, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp,
+                                    C.POINTER(C.c_double * 3)]
+hip.shq_uvbg_slab_readout.argtypes = [_vp, _UP, _UC, _vp, _vp, C.c_int64, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]
+for _f in ("pitch", "fesc", "deposit", "fft_yz", "xforward", "tables", "xfilter", "filter", "cells", "readout"):
+    getattr(hip, "shq_uvbg_slab_" + _f).restype = C.c_int
 
 
 FLAG_HEIII = 4                                     # SHQ_FLAG_HEIII: HeIIIionized, bit 2 of the flag byte

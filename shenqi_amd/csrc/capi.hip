@@ -286,6 +286,7 @@ extern "C" void shq_shutdown(shq_context *ctx)
     ctx->s_gradrho.release(); ctx->s_evp_in.release(); ctx->s_todo.release(); ctx->s_queue2.release(); ctx->s_queue3.release();
     (void) shq_nulra_free(ctx); /* the resident linear-response neutrino state (nulra.hip) */
     ctx->tb.release(); ctx->tree_targets.release(); ctx->ps_sums.release(); ctx->ps_bintab.release(); ctx->s_blockcount.release(); ctx->s_nlist.release(); ctx->s_ncount.release(); ctx->s_redo.release(); ctx->s_redo2.release(); ctx->s_counters.release(); ctx->pm_oob.release(); ctx->fft_tw.release();
+    ctx->uvbg_tw.release(); ctx->uvbg_tabs.release(); ctx->uvbg_part.release(); ctx->uvbg_flag.release();
     for(int i = 0; i < SHQ_NTIMERS; i++) {
         (void) hipEventDestroy(ctx->ev_begin[i]);
         (void) hipEventDestroy(ctx->ev_end[i]);

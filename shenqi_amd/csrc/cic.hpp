@@ -33,21 +33,33 @@ __device__ __forceinline__ void cic_cell3(double px, double py, double pz, doubl
 }
 
 /* f(c, lin, w) for the connections c = 0..7 in order: bit k of c is the offset along axis k, lin the index of the periodic cell in a
- * mesh [N][N][zp], w the product of the three weights taken from 1.0 along k = 0, 1, 2 */
-template <typename F> __device__ __forceinline__ void cic_corners(const int ic[3], const double res[3], int N, int zp, F f)
+ * mesh [N][N][zp], w the product of the three weights taken from 1.0 along k = 0, 1, 2.
+ * SLAB: the mesh is a rank's window [nxalloc][N][zp] of x planes whose plane 0 is the global plane xshift (xloc above).  A corner whose
+ * plane lies outside the window is not visited and raises *oob: the caller routed the particle to the wrong rank. */
+template <bool SLAB = false, typename F>
+__device__ __forceinline__ void cic_corners(const int ic[3], const double res[3], int N, int zp, F f, int xshift = 0, int nxalloc = 0,
+                                            int *oob = nullptr)
 {
 #pragma clang fp contract(off)
 #pragma unroll
     for(int c = 0; c < 8; c++) {
         double w = 1.0;
         size_t lin = 0;
+        bool inside = true;
 #pragma unroll
         for(int k = 0; k < 3; k++) {
             const int off = (c >> k) & 1;
-            const int t = wrapi(ic[k] + off, N);
+            int t = wrapi(ic[k] + off, N);
+            if(SLAB && k == 0) {
+                t = xloc(t, xshift, N);
+                inside = t < nxalloc;
+            }
             lin = lin * (size_t) (k == 2 ? zp : N) + (size_t) t;
             w *= off ? res[k] : (1 - res[k]);
         }
-        f(c, lin, w);
+        if(!SLAB || inside)
+            f(c, lin, w);
+        else
+            *oob = 1;
     }
 }

@@ -209,7 +209,7 @@ struct shq_fft_plan {
         unsigned res_z = 0, res_s = 0, res_x = 0, res_x3 = 0, res_x4 = 0, res_x5 = 0;
     } t; /* transposing pipeline */
     struct {
-        unsigned res_zf = 0, res_zi = 0, res_s = 0, res_x3 = 0, res_x4 = 0;
+        unsigned res_zf = 0, res_zi = 0, res_s = 0, res_x3 = 0, res_x4 = 0, res_x5 = 0;
     } n; /* in-place pipeline */
 };
 
@@ -528,6 +528,11 @@ struct shq_context {
     int uvbg_n = 0;                       /* Nmesh of the kept grids (0: none) */
     std::vector<float> uvbg_j21, uvbg_xhi;
     double uvbg_ms[4] = {0, 0, 0, 0};     /* shq_uvbg_phase_ms */
+    /* the slab phases (shq_uvbg_slab_*): twiddles of their own (the PM's stay as they are), the radius loop's filter tables
+     * [nr][3 (N/2)^2 + 1] (shq_uvbg_slab_tables), the kernels' partial sums and the outside-the-window flag */
+    DevBuf<double> uvbg_tw, uvbg_tabs, uvbg_part;
+    DevBuf<int> uvbg_flag;
+    int uvbg_tw_n = 0, uvbg_tabs_n = 0, uvbg_tabs_nr = 0;
     /* ---- helium reionisation (heiii.hip): a call allocates and frees its own device buffers; only its statistics stay behind */
     shq_heiii_stats heiii_stats = {};
     /* ---- lensing potential planes (lens.hip): a call allocates and frees its own device buffers; only its times stay behind */
@@ -647,6 +652,8 @@ enum shq_fft_stage {
     SHQ_FFT_X_SOLVE,           /* X forward + potential_transfer + X inverse on the y-slab (lines along the slowest axis) */
     SHQ_FFT_X_FORWARD_SUMS,    /* X_SOLVE split in two: the X forward, the spectrum left in place, with the P(k) sums */
     SHQ_FFT_X_FINISH,          /* ... then the mode factor, potential_transfer and the X inverse; needs modefac */
+    SHQ_FFT_X_FILTER,          /* from X_FORWARD_SUMS' kept spectrum the excursion-set filter: every mode times (v / ncell)
+                                  modefac[k2 & fac_mask], then the X inverse into the y-slab `out`; d_mesh is only read */
 };
 /* what the transposing pipeline runs between d_mesh and a scratch mesh of the same size */
 enum shq_fft_part {
@@ -665,10 +672,9 @@ struct shq_fft_opts {
     int fac_mask = 0;
     const int32_t *bintab = nullptr;  /* the bin of k2 (pm.hip, pm_power_prepare) */
     double *ps = nullptr;             /* the P(k) sums of powerspectrum_add_mode; null: none taken */
-    /* transposing pipeline only */
     const double *tw = nullptr;       /* the caller's own twiddles of N (shq_fft3d_fill_twiddles): the context's are left alone */
-    double *out = nullptr;            /* T_FILTER: where the Z inverse writes */
-    int ncell = 1;                    /* T_FILTER: the int N^3 every mode is divided by */
+    double *out = nullptr;            /* T_FILTER: where the Z inverse writes; X_FILTER: the y-slab the X inverse writes */
+    int ncell = 1;                    /* T_FILTER, X_FILTER: the int N^3 every mode is divided by */
 };
 /* from_i64: the mesh holds the int64 fixed-point deposit, worth inv_scale per unit.  d_sinctab, asmth2, pot_factor: the Green's function. */
 int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, shq_fft_stage stage, bool from_i64, double inv_scale, const double *d_sinctab,

@@ -463,7 +463,8 @@ struct GreenArgs {
     int fac_mask = 0;
     const int32_t *bintab = nullptr;
     double *ps = nullptr;
-    int ncell = 1; /* fft_t_tile MODE 5: the int N^3 every mode is divided by (uvbg.cpp:211-215 divide_by_ncell) */
+    int ncell = 1; /* MODE 5: the int N^3 every mode is divided by (uvbg.cpp:211-215 divide_by_ncell) */
+    double2 *out = nullptr; /* fft_pass_strided MODE 5: the y-slab the result is stored into, laid out as the one it reads */
 };
 
 /* powerspectrum_add_mode (gravpm.cpp:323-356) of one mode into a workgroup's LDS histogram [3][N]: the operations of pm_power_kernel
@@ -495,6 +496,9 @@ __device__ __forceinline__ void pk_add(double *hist, const GreenArgs &ga, double
  *   MODE 4: every mode times T[k2], then MODE 2's Green's factor with MODE 2's arithmetic - (v T) green, potential_transfer's order
  *           (gravpm.cpp:412-443) - as the tile lands in LDS; with ga.ps the P(k) sums of v T; then X inverse.  T = 1 gives MODE 2's
  *           bits: v * 1.0 is exact.  T[k2] of the next tile is gathered after the current tile's stages, as fft_t_tile does.
+ *   MODE 5: the excursion-set filter on a y-slab (uvbg.hip, the sibling of fft_t_tile's MODE 5): reads a tile of the kept spectrum,
+ *           every mode becomes (v / ncell) T[k2] - divide_by_ncell, then filter_pm (uvbg.cpp:211-250) - with no Green's function,
+ *           then X inverse, stored OUT OF PLACE into the same place of ga.out: the kept spectrum is only read.
  * MODES 3, 4 with ga.ps keep a P(k) histogram [3][N] in LDS behind the tables (3 N doubles more), flushed once per workgroup. */
 template <int N, int MODE, int PK = 0>
 __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const long long es, const long long outer_stride,
@@ -523,7 +527,7 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
      * bytes), so they should run on the same XCD at about the same time and find the other half in its L2. */
     const unsigned vb = xcd_block(blockIdx.x, gridDim.x, xcdk);
     double prx[E], pry[E];
-    double tfac[MODE == 4 ? E : 1]; /* MODE 4: T[k2] of the prefetched tile's modes */
+    double tfac[MODE == 4 || MODE == 5 ? E : 1]; /* MODES 4, 5: T[k2] of the prefetched tile's modes */
 #define FFT_FETCH(BASE, ABASE)                                                                   \
     _Pragma("unroll") for(int i = 0; i < E; i++)                                                 \
     {                                                                                            \
@@ -536,9 +540,9 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
             pry[i] = t_.y;                                                                       \
         }                                                                                        \
     }
-    /* MODE 4: T[k2] of the modes of tile (O_, TL_); a pad column (z > N / 2) reads entry 0, so k2 stays inside the table */
+    /* MODES 4, 5: T[k2] of the modes of tile (O_, TL_); a pad column (z > N / 2) reads entry 0, so k2 stays inside the table */
 #define FFT_TFETCH(O_, TL_)                                                                      \
-    if(MODE == 4) {                                                                              \
+    if(MODE == 4 || MODE == 5) {                                                                            \
         const int y_ = ga.y0 + (O_), ky_ = y_ <= N / 2 ? y_ : y_ - N;                            \
         _Pragma("unroll") for(int i = 0; i < E; i++)                                             \
         {                                                                                        \
@@ -587,6 +591,16 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
                 const double fac = (k2 == 0.0 || z > N / 2) ? 0.0 : gax[x] * gy * gax[z] / k2;
                 *p = make_double2(v.x * fac, v.y * fac);
             }
+        } else if(MODE == 5) {
+            /* value /= total_n_cells, then value *= filter: a division and a multiplication, never contracted */
+#pragma clang fp contract(off)
+            const double nc = (double) ga.ncell;
+#pragma unroll
+            for(int i = 0; i < E; i++) {
+                const int e = threadIdx.x + i * FFT_T;
+                if(EXACT || e < FFT_C * N)
+                    buf[(e % FFT_C) * LS + lx<N>(e / FFT_C)] = make_double2((prx[i] / nc) * tfac[i], (pry[i] / nc) * tfac[i]);
+            }
         } else {
 #pragma unroll
             for(int i = 0; i < E; i++) {
@@ -621,7 +635,7 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
             fft_lines<N, -1>(buf, Wl, green);
             fft_lines<N, +1>(buf, Wl);
         }
-        if(MODE == 1 || MODE == 4)
+        if(MODE == 1 || MODE == 4 || MODE == 5)
             fft_lines<N, +1>(buf, Wl);
         FFT_TFETCH(outer_n, tile_n)
         if(MODE == 3) { /* the spectrum back in place; the density's P(k) on the way */
@@ -636,14 +650,16 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
                     pk_add<N>(hist, ga, v, row, y, z0 + col, kx * kx + ky * ky + (z0 + col) * (z0 + col));
                 }
             }
-        } else
+        } else {
+            double2 *ob = MODE == 5 ? ga.out + (base - cm) : base; /* MODE 5: the same tile of the other y-slab */
             for(int e = threadIdx.x; e < FFT_C * N; e += FFT_T) {
                 const int row = e / FFT_C, col = e - row * FFT_C;
                 if(PK == 1)
                     abase[(long long) (row / ga.nyl) * ga.qstride + (long long) (row % ga.nyl) * es + col] = buf[col * LS + lx<N>(row)];
                 else
-                    base[(long long) row * es + col] = buf[col * LS + lx<N>(row)];
+                    ob[(long long) row * es + col] = buf[col * LS + lx<N>(row)];
             }
+        }
         if(!more)
             break;
         __syncthreads(); /* everyone has read its results out of LDS before the next tile lands there */
@@ -1152,9 +1168,9 @@ int run_t(shq_context *ctx, const double2 *W, double *d_mesh, double *d_scratch,
 
 /* nslab: N for the stages of a full cube */
 template <int N>
-int run_n(shq_context *ctx, double *d_mesh, int zp, shq_fft_stage stage, bool from_i64, double inv_scale, const GreenArgs &ga, int nslab)
+int run_n(shq_context *ctx, const double2 *W, double *d_mesh, int zp, shq_fft_stage stage, bool from_i64, double inv_scale, const GreenArgs &ga,
+          int nslab)
 {
-    const double2 *W = reinterpret_cast<const double2 *>(ctx->fft_tw.ptr);
     /* FFT_C padded lines + the twiddle table + (X pass) the sinc table */
     constexpr size_t lds = sizeof(double2) * (FFT_C * fft_ls(N) + fft_twn(N)) + sizeof(double) * N;
     constexpr size_t lds_hist = lds + sizeof(double) * 3 * N; /* the split X pass with the P(k) histogram */
@@ -1177,6 +1193,7 @@ int run_n(shq_context *ctx, double *d_mesh, int zp, shq_fft_stage stage, bool fr
         SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_z_inv<N>, lds}}, &p.res_zi));
         SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 3>, lds_hist}}, &p.res_x3));
         SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 4>, lds_hist}}, &p.res_x4));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 5>, lds}}, &p.res_x5));
         SHQ_TRY(fft_resident(ncu, FFT_T,
                              {{fft_pass_strided<N, 0>, lds}, {fft_pass_strided<N, 1>, lds}, {fft_pass_strided<N, 2>, lds}, {fft_pass_strided<N, 0, 1>, lds},
                               {fft_pass_strided<N, 1, 2>, lds}},
@@ -1203,6 +1220,9 @@ int run_n(shq_context *ctx, double *d_mesh, int zp, shq_fft_stage stage, bool fr
         break;
     case SHQ_FFT_X_FINISH:
         fft_pass_strided<N, 4><<<k.grid(stot, pl.res_x4), dim3(FFT_T), lds_split, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        break;
+    case SHQ_FFT_X_FILTER:
+        fft_pass_strided<N, 5><<<k.grid(stot, pl.res_x5), dim3(FFT_T), lds, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
         break;
     case SHQ_FFT_YZ_FORWARD:
     case SHQ_FFT_YZ_FORWARD_PACKED:
@@ -1348,14 +1368,17 @@ int shq_fft3d_run_transposed(shq_context *ctx, double *d_mesh, double *d_scratch
 int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, shq_fft_stage stage, bool from_i64, double inv_scale, const double *d_sinctab,
                   double asmth2, double pot_factor, const shq_fft_opts &o)
 {
-    const bool yslab = stage == SHQ_FFT_X_SOLVE || stage == SHQ_FFT_X_FORWARD_SUMS || stage == SHQ_FFT_X_FINISH;
+    const bool yslab = stage == SHQ_FFT_X_SOLVE || stage == SHQ_FFT_X_FORWARD_SUMS || stage == SHQ_FFT_X_FINISH || stage == SHQ_FFT_X_FILTER;
     const bool packed = stage == SHQ_FFT_YZ_FORWARD_PACKED || stage == SHQ_FFT_YZ_INVERSE_PACKED;
     const int nslab = stage <= SHQ_FFT_SOLVE ? N : o.nslab;
     SHQ_CHECK(shq_fft3d_supported(N), SHQ_ERR_INVALID, "fft3d: unsupported mesh size %d", N);
     SHQ_CHECK(nslab > 0 && nslab <= N && o.y0 >= 0 && o.y0 + (yslab ? nslab : 0) <= N, SHQ_ERR_INVALID, "fft3d: bad slab geometry");
     SHQ_CHECK(zp >= N + 2 && zp % 8 == 0, SHQ_ERR_INVALID, "fft3d: pitch %d must be a multiple of 8 doubles and >= N+2", zp);
     SHQ_CHECK((stage != SHQ_FFT_X_FINISH || o.modefac) && (!o.ps || o.bintab), SHQ_ERR_INVALID, "fft3d: bad split X pass arguments");
-    SHQ_TRY(ensure_twiddles(ctx, N));
+    SHQ_CHECK(stage != SHQ_FFT_X_FILTER || (o.modefac && o.out && o.out != d_mesh && o.ncell > 0), SHQ_ERR_INVALID,
+              "fft3d: bad filter pass arguments");
+    if(!o.tw)
+        SHQ_TRY(ensure_twiddles(ctx, N));
     GreenArgs ga;
     ga.sinctab = d_sinctab;
     ga.asmth2 = asmth2;
@@ -1366,6 +1389,8 @@ int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, shq_fft_stage
     ga.fac_mask = o.fac_mask;
     ga.bintab = o.bintab;
     ga.ps = o.ps;
+    ga.ncell = o.ncell;
+    ga.out = reinterpret_cast<double2 *>(o.out);
     if(packed) {
         SHQ_CHECK(o.packed && o.nranks >= 1 && N % o.nranks == 0, SHQ_ERR_INVALID,
                   "fft3d: packed stages need a buffer and a rank count that divides the mesh");
@@ -1373,5 +1398,6 @@ int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, shq_fft_stage
         ga.alt_outer = (long long) ga.nyl * (zp / 2);
         ga.qstride = (long long) nslab * ga.alt_outer;
     }
-    return fft_dispatch(N, [&](auto n) { return run_n<decltype(n)::N>(ctx, d_mesh, zp, stage, from_i64, inv_scale, ga, nslab); });
+    const double2 *W = reinterpret_cast<const double2 *>(o.tw ? o.tw : ctx->fft_tw.ptr);
+    return fft_dispatch(N, [&](auto n) { return run_n<decltype(n)::N>(ctx, W, d_mesh, zp, stage, from_i64, inv_scale, ga, nslab); });
 }

@@ -1669,6 +1669,270 @@ class GpuMetalOps:
         return out[:nqueue]
 
 
+def uvbg_radii(p):
+    """petapm_reion_c2r's radius schedule (petapm.cpp:536-606) from the parameters alone: the same list on every rank, the last
+    entry the unfiltered cell-size step"""
+    cell = p.BoxSize / p.UVBGdim
+    R = min(p.ReionRBubbleMax, p.BoxSize)
+    radii, last, count = [], False, 0
+    while not last:
+        count += 1
+        if R / p.ReionDeltaRFactor < p.ReionRBubbleMin or R / p.ReionDeltaRFactor < cell or count > 10000:
+            last, R = True, cell
+        radii.append(R)
+        R = R / p.ReionDeltaRFactor
+    return radii
+
+
+class DistUVBG:
+    """calculate_uvbg + petapm_reion (uvbg.cpp:474-597, petapm.cpp:495-685) on x-slabs of the UVBGdim mesh, one per rank: whole
+    planes, equal widths unless `bounds` says otherwise (the PM's slabs live on another mesh and may be cut below a plane: they are
+    not reused).  UVBGdim must be divisible by the rank count (equal y-slabs of the spectrum): otherwise the constructor raises
+    ValueError on every rank, before any collective.
+
+    The grids come from a fixed-point deposit whose three scales every rank derives from the global sums, the filter tables are made
+    on every host alike and the cell loop is local, so the J21 / xHI grids and the particles' results do not depend on the rank
+    count or on who held which particle.  ops (GpuUvbgOps below; the CPU tests use a numpy stand-in) works on torch tensors:
+      ops.fesc(p, cosmo, posm, types, fesc, sfr) -> ([|Mass|, |Mass f_esc|, |Sfr f_esc|] of the rows, negative flag), fesc in place;
+      ops.deposit(p, posm, types, fesc, sfr, exps, plane0, nxl, nalloc) -> the 2 (3) int64 meshes [nalloc, N, pitch];
+      ops.tables(p, radii); ops.cells(p, cosmo, R, last, meshes, zp, nxl, J21, xHI) -> the three partial sums on the last radius;
+      ops.readout(p, cosmo, posm, types, J21ext, plane0, nxl, local_J21, zreion);
+      bespoke route (ops.pitch() > 0): ops.fft_yz(planes, nxl, direction, exp, packed, P), ops.xforward(spec, y0, nyl),
+      ops.xfilter(spec, out, y0, nyl, r);   torch.fft route: ops.to_real(mesh_i, exp), ops.filter(spec, y0, nyl, r) in place.
+    Counters of the last call: rows_sent (particle rows that left this rank), nradii, nalltoall (all-to-alls and shifts started).
+    J21 / xHI hold the rank's planes of the grids afterwards (save_uvbg_grids' data).  Nothing here has run on more than one GPU."""
+
+    COLS = 9     # x, y, z, Mass, Type, f_esc, Sfr, local_J21, zreion: one float64 row per particle (Type and float Mass are exact)
+
+    def __init__(self, comm, UVBGdim, BoxSize, ops, bounds=None):
+        self.comm, self.ops, self.N, self.L = comm, ops, int(UVBGdim), float(BoxSize)
+        self.d = SlabDecomp(comm, self.N, self.L, bounds)
+        self.rows_sent = self.nradii = self.nalltoall = 0
+        self.J21 = self.xHI = None
+
+    def _a2a(self, send, send_counts, recv_counts=None):
+        self.nalltoall += 1
+        if recv_counts is None:
+            return self.comm.all_to_all_rows(send, send_counts)
+        return self.comm.all_to_all_rows_start(send, send_counts, recv_counts)
+
+    def _shift(self, t, direction):
+        self.nalltoall += 1
+        return self.comm.shift(t, direction)
+
+    def calculate(self, p, cosmo, pos, mass, types, fesc, sfr, local_J21, zreion):
+        """p: capi.UvbgParams, cosmo: capi.UvbgCosmo; pos [n, 3], mass, types, fesc (in / out), sfr (may be None without
+        ReionUseParticleSFR), local_J21 (out, gas) and zreion (in / out, gas): numpy arrays of the particles this rank holds, in any
+        distribution over the ranks.  They are written only at the very end, in the caller's order.  Returns (volume-weighted xHI,
+        mass-weighted xHI, number of radii), the same on every rank.  A negative escape fraction on any rank raises ValueError on
+        every rank, the arrays untouched."""
+        c, d, ops, N = self.comm, self.d, self.ops, self.N
+        if p.UVBGdim != N or p.BoxSize != self.L:
+            raise ValueError("the parameters' UVBGdim / BoxSize are not this decomposition's")
+        use_sfr = bool(p.ReionUseParticleSFR)
+        self.rows_sent = self.nalltoall = 0
+        n = len(pos)
+        rows = np.empty((n, self.COLS))
+        rows[:, 0:3], rows[:, 3], rows[:, 4], rows[:, 5] = pos, mass, types, fesc
+        rows[:, 6] = sfr if sfr is not None else 0.0
+        rows[:, 7], rows[:, 8] = local_J21, zreion
+        rows = torch.from_numpy(rows).to(ops.device)
+        # ---- to the owner of the particle's UVBG plane; rows already at home stay in the self block
+        owner = d.owner_of(rows[:, 0])
+        order = torch.argsort(owner, stable=True)
+        counts = torch.bincount(owner, minlength=c.size).tolist()
+        self.rows_sent = n - counts[c.rank]
+        mine, rcounts = self._a2a(rows[order].contiguous(), counts)
+        posm = mine[:, 0:4].contiguous()
+        ty = mine[:, 4].to(torch.uint8).contiguous()
+        col = [mine[:, k].contiguous() for k in range(5, 9)]
+        f_esc, s_fr, lj, zr = col
+        # ---- init_particle_uvbg; the three sums and the negative flag agreed on in ONE vector before anything else: a rank that
+        # raised alone would leave the others inside an all-to-all
+        sums, neg = ops.fesc(p, cosmo, posm, ty, f_esc, s_fr)
+        tot = c.allreduce_sum_vec(np.array([sums[0], sums[1], sums[2], 1.0 if neg else 0.0]))
+        if tot[3] > 0:
+            raise ValueError("negative escape fraction?")
+        if not np.isfinite(tot[:3]).all():
+            raise ValueError("uvbg: non-finite mass, f_esc or Sfr")
+        exps = [math.frexp(s if s > 0 else 1.0)[1] for s in tot[:3]]
+        radii = uvbg_radii(p)
+        self.nradii = len(radii)
+        ops.tables(p, radii)
+        P, nxl = c.size, d.nxl
+        nalloc = N if P == 1 else nxl + 1
+        bufs = ops.deposit(p, posm, ty, f_esc, s_fr, exps, d.plane0, nxl, nalloc)     # int64 [nalloc, N, pitch] per field
+        nf = 3 if use_sfr else 2
+        assert len(bufs) == nf
+        if P > 1:      # the ghost planes of all fields in one message to the right neighbour; integer add: exact
+            ghost = self._shift(torch.stack([b[nxl] for b in bufs]), +1)
+            for f in range(nf):
+                bufs[f][0] += ghost[f]
+        self._J21ext = ops.full((nalloc, N, N), 0.0, torch.float32)     # the own planes, then room for the right neighbour's first
+        self.J21 = self._J21ext[:nxl]
+        self.xHI = ops.full((nxl, N, N), 1.0, torch.float32)
+        bespoke = getattr(ops, "pitch", None) is not None and ops.pitch() > 0 and os.environ.get("SHQ_SLAB_TORCH_FFT", "0") != "1"
+        part = (self._loop_bespoke if bespoke else self._loop_torch)(p, cosmo, bufs, exps, radii)
+        # ---- UVBGgrids' globals (uvbg.cpp:446-451) and readout_J21 with the right neighbour's first plane behind the own ones
+        tot = c.allreduce_sum_vec(np.asarray(part, dtype=np.float64))
+        vol, mw = tot[0] / float(N ** 3), tot[1] / tot[2]
+        if P > 1:
+            self._J21ext[nxl] = self._shift(self.J21[0:1].contiguous(), -1)[0]
+        ops.readout(p, cosmo, posm, ty, self._J21ext, d.plane0, nxl, lj, zr)
+        # ---- the three results return along the same counts: the order within a (source, destination) pair is kept, so no key travels
+        back, _ = self._a2a(torch.stack([f_esc, lj, zr], dim=1), rcounts)
+        res = np.empty((n, 3))
+        res[order.cpu().numpy()] = back.cpu().numpy()
+        fesc[:], local_J21[:], zreion[:] = res[:, 0], res[:, 1], res[:, 2]
+        return float(vol), float(mw), len(radii)
+
+    def _loop_bespoke(self, p, cosmo, bufs, exps, radii):
+        """The library's own FFT passes (csrc/fft3d.hip): a field's buffer [nalloc][N][zp] is in turn its int64 deposit, its (y, z)
+        half spectrum and its real mesh of a radius.  Per field: Y/Z forward packed, all-to-all, X forward - the spectrum stays on
+        the y-slab.  Per radius and field: the filter pass out of place, ONE all-to-all back, Y/Z inverse; then the cell loop."""
+        c, ops, N, P, nxl = self.comm, self.ops, self.N, self.comm.size, self.d.nxl
+        zp = ops.pitch()
+        zpc, nyl, y0 = zp // 2, N // P, c.rank * (N // P)
+        widths, multi = self.d.widths, c.multi
+        own = [b[:nxl] for b in bufs]
+        pend = []
+        for f, o in enumerate(own):
+            if multi:
+                send = torch.empty((P * nxl, nyl, zpc), dtype=torch.complex128, device=o.device)      # rows [dest q][x_l]
+                ops.fft_yz(o, nxl, 0, exps[f], send, P)
+                pend.append(self._a2a(send, [nxl] * P, widths))                                       # [x (all)][y_l][z']
+            else:
+                ops.fft_yz(o, nxl, 0, exps[f], None, 1)
+                pend.append(_Done(o.view(torch.float64).view(torch.complex128).clone()))
+        kept = []
+        for pe in pend:
+            spec_t = pe.wait().contiguous()
+            ops.xforward(spec_t, y0, nyl)
+            kept.append(spec_t)
+        real = [b.view(torch.float64) for b in bufs]
+        part = None
+        for r, R in enumerate(radii):
+            pend = []
+            for f, spec_t in enumerate(kept):
+                if multi:
+                    out = torch.empty_like(spec_t)
+                    ops.xfilter(spec_t, out, y0, nyl, r)
+                    pend.append(self._a2a(out, widths, [nxl] * P))                                    # rows [src q][x_l]
+                else:       # the filtered planes land where the Y/Z inverse takes them
+                    ops.xfilter(spec_t, own[f].view(torch.float64).view(torch.complex128), y0, nyl, r)
+            for f, o in enumerate(own):
+                if multi:
+                    ops.fft_yz(o, nxl, 1, 0, pend[f].wait().contiguous(), P)
+                else:
+                    ops.fft_yz(o, nxl, 1, 0, None, 1)
+            part = ops.cells(p, cosmo, R, r == len(radii) - 1, real, zp, nxl, self.J21, self.xHI)
+        return part
+
+    def _loop_torch(self, p, cosmo, bufs, exps, radii):
+        """The same loop with torch.fft for mesh sizes without a bespoke transform, and on the CPU stand-ins: the spectrum is kept as
+        [x][y_l][z'], x slowest, as the all-to-all delivers it."""
+        c, ops, N, P, nxl = self.comm, self.ops, self.N, self.comm.size, self.d.nxl
+        Nc, nyl, y0 = N // 2 + 1, N // P, c.rank * (N // P)
+        widths = self.d.widths
+        kept = []
+        for f, b in enumerate(bufs):
+            real = ops.to_real(b[:nxl, :, :N], exps[f])                                          # f64 [nxl, N, N]
+            spec = torch.fft.rfft2(real, dim=(1, 2))                                             # [nxl, N, Nc], unscaled
+            send = spec.reshape(nxl, P, nyl, Nc).permute(1, 0, 2, 3).reshape(P * nxl, nyl, Nc)   # rows [dest q][x_l]
+            recv, _ = self._a2a(send.contiguous(), [nxl] * P)                                    # rows [src p][x_l] = all x
+            kept.append(torch.fft.fft(recv.reshape(N, nyl, Nc), dim=0).contiguous())
+        part = None
+        for r, R in enumerate(radii):
+            real = []
+            for spec_t in kept:
+                out = ops.filter(spec_t.clone(), y0, nyl, r)
+                out = torch.fft.ifft(out, dim=0, norm="forward").contiguous()                    # rows = x planes, in order
+                recv, _ = self._a2a(out, widths)                                                 # rows [src q][x_l]
+                spec = recv.reshape(P, nxl, nyl, Nc).permute(1, 0, 2, 3).reshape(nxl, N, Nc)
+                real.append(torch.fft.irfft2(spec, s=(N, N), dim=(1, 2), norm="forward").contiguous())   # [nxl, N, N], unscaled
+            part = ops.cells(p, cosmo, R, r == len(radii) - 1, real, N, nxl, self.J21, self.xHI)
+        return part
+
+
+class GpuUvbgOps:
+    """DistUVBG's phases on the device library (shq_uvbg_slab_*), on torch tensors of the context's device."""
+
+    def __init__(self, ctx, device=None):
+        self.ctx = ctx
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self._hand = _StreamHandover(ctx, self.device)
+        self.N = None
+
+    def _call(self, fn, *args):
+        self._hand.before()
+        capi.check(fn(self.ctx.h, *args), fn.__name__)
+        self._hand.after()
+
+    @staticmethod
+    def _p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
+    def full(self, shape, value, dtype):
+        return torch.full(shape, value, dtype=dtype, device=self.device)
+
+    def pitch(self):
+        return int(capi.hip.shq_uvbg_slab_pitch(self.N))
+
+    def fesc(self, p, cosmo, posm, types, fesc, sfr):
+        self.N = int(p.UVBGdim)
+        sums, neg = (C.c_double * 3)(), C.c_int(0)
+        self._call(capi.hip.shq_uvbg_slab_fesc, C.byref(p), C.byref(cosmo), self._p(posm), self._p(types), posm.shape[0], self._p(fesc), self._p(sfr),
+                   C.byref(sums), C.byref(neg))
+        return list(sums), bool(neg.value)
+
+    def tables(self, p, radii):
+        r = np.ascontiguousarray(radii, dtype=np.float64)
+        self.N = int(p.UVBGdim)
+        self._call(capi.hip.shq_uvbg_slab_tables, int(p.ReionFilterType), int(p.UVBGdim), float(p.BoxSize), capi.ptr(r), len(r))
+
+    def deposit(self, p, posm, types, fesc, sfr, exps, plane0, nxl, nalloc):
+        N = int(p.UVBGdim)
+        zp = self.pitch() or N + 2
+        nf = 3 if p.ReionUseParticleSFR else 2
+        bufs = [torch.empty((nalloc, N, zp), dtype=torch.int64, device=self.device) for _ in range(nf)]
+        self._call(capi.hip.shq_uvbg_slab_deposit, C.byref(p), self._p(posm), self._p(types), posm.shape[0], self._p(fesc), self._p(sfr),
+                   C.byref((C.c_int * 3)(*exps)), plane0, nxl, 0, nalloc, 1, *[self._p(b) for b in bufs], *([None] * (3 - nf)))
+        return bufs
+
+    def fft_yz(self, planes, nplanes, direction, exp, packed, nranks):
+        assert planes.is_contiguous() and (packed is None or (packed.is_contiguous() and packed.dtype == torch.complex128))
+        self._call(capi.hip.shq_uvbg_slab_fft_yz, self.N, self._p(planes), nplanes, direction, exp, self._p(packed), nranks)
+
+    def xforward(self, spec_t, y0, nyl):
+        assert spec_t.is_contiguous() and spec_t.dtype == torch.complex128
+        self._call(capi.hip.shq_uvbg_slab_xforward, self.N, self._p(spec_t), y0, nyl)
+
+    def xfilter(self, spec_t, out, y0, nyl, r):
+        assert spec_t.is_contiguous() and out.is_contiguous() and out.dtype == torch.complex128 and out.shape == spec_t.shape
+        self._call(capi.hip.shq_uvbg_slab_xfilter, self.N, self._p(spec_t), self._p(out), y0, nyl, r)
+
+    def to_real(self, mesh_i, exp):
+        return mesh_i.to(torch.float64) * math.ldexp(1.0, exp - 61)
+
+    def filter(self, spec_t, y0, nyl, r):
+        assert spec_t.is_contiguous() and spec_t.dtype == torch.complex128
+        self._call(capi.hip.shq_uvbg_slab_filter, self.N, self._p(spec_t), self._p(spec_t), y0, nyl, r)
+        return spec_t
+
+    def cells(self, p, cosmo, R, last, meshes, zp, nxl, J21, xHI):
+        assert all(m.is_contiguous() and m.dtype == torch.float64 for m in meshes) and J21.is_contiguous() and xHI.is_contiguous()
+        sums = (C.c_double * 3)()
+        m = [self._p(x) for x in meshes] + [None] * (3 - len(meshes))
+        self._call(capi.hip.shq_uvbg_slab_cells, C.byref(p), C.byref(cosmo), float(R), int(last), m[0], m[1], m[2], zp, 0, nxl, self._p(J21), self._p(xHI),
+                   C.byref(sums))
+        return list(sums) if last else None
+
+    def readout(self, p, cosmo, posm, types, J21ext, plane0, nxl, local_J21, zreion):
+        assert J21ext.is_contiguous() and J21ext.dtype == torch.float32
+        self._call(capi.hip.shq_uvbg_slab_readout, C.byref(p), C.byref(cosmo), self._p(posm), self._p(types), posm.shape[0], self._p(J21ext), plane0, nxl,
+                   J21ext.shape[0], self._p(local_J21), self._p(zreion))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # The domain decomposition itself: domain_decompose_full (libgadget/domain.cpp:174-277).  The particle loops run in `ops` (GpuDomainOps:
 # shq_domain_* on the device; the tests' CPU stand-in: the restated procedures), the small serial stages are host functions, and this
