@@ -66,7 +66,10 @@ int shq_timer_end(shq_context *ctx, int slot);
 int shq_timer_elapsed_ms(shq_context *ctx, int slot, double *ms);
 /* elapsed time between two recorded timer events (which: 0 begin, 1 end), e.g. the caller's slot 1 begin -> the library's walk (slot 19)
  * begin: where the phases of a resident step lie on one time line although they run on different streams.  Library slots: 8 PM begin,
- * 9 / 10 FFT pipeline begin / end, 13 PM end (all as begin events), 16 tree build, 19 tree walk. */
+ * 9 / 10 FFT pipeline begin / end, 13 PM end (all as begin events), 16 tree build, 19 tree walk.  The black-hole walks bracket their
+ * device work as slots of their own (shq_timer_elapsed_ms): 15 walk + postprocess of shq_bh_accretion / shq_bh_feedback and of the emit pass
+ * of shq_bh_accretion_marks / shq_bh_feedback_effects, or sort + kernel of shq_bh_marks_resolve / shq_bh_effects_apply; 17 the count pass;
+ * 18 routing and sorting the emitted records. */
 int shq_timer_between_ms(shq_context *ctx, int slot_a, int which_a, int slot_b, int which_b, double *ms);
 /* Library version string. */
 const char *shq_version(void);
@@ -1179,7 +1182,58 @@ int shq_bh_feedback(shq_context *ctx, const shq_tree_view *tree, const shq_part_
                     const double *rnd_table, int64_t rnd_size, const uint8_t *eeqos, const shq_bh_work *work, int64_t *n_sph_swallowed,
                     int64_t *n_bh_swallowed);
 
-/* winds_and_feedback() (libgadget/winds.cpp:295-369): the two asymmetric walks over the gas tree for the new
+/* The two walks above in the parts a multi-rank driver needs (shenqi_amd/dist.py:DistBlackHole); shq_bh_accretion / shq_bh_feedback
+ * stay as they are.  Both walks write on the neighbours' side, and a neighbour may be an import of another rank's particle, so here a
+ * walk keeps its hole-side sums and postprocess and only EMITS what it would have written; the records travel to the particle's owner,
+ * who applies them per particle in the order of the GLOBAL accretion queue (the ranks' queues one after the other): the serial loop
+ * over that queue, deterministic where the one-rank kernels' arrival-order updates of entropy and velocity are not.
+ *
+ * Rows [0, nlocal) of `parts` are this rank's own, rows >= nlocal imports: ghost_owner[row - nlocal] in [0, nranks) and
+ * ghost_index[row - nlocal] >= 0 are the owner's rank and the row there; the queue holds own rows only.  A record is
+ * (owner, row at the owner, hole = queue_offset + queue position < 2^31, kind, 8 bytes); an emitted list is sorted by (owner, row, hole),
+ * counts[nranks] records per owner, *nrecords their total.  With records == NULL a call only counts (*nrecords set, counts zero, nothing
+ * else written); a capacity < *nrecords is SHQ_ERR_INVALID with *nrecords set and nothing else written.
+ *
+ * shq_bh_accretion_marks   shq_bh_accretion without the two mark arrays: encounter, Mdot, Mass, DragAccel, KineticFdbkEnergy into the
+ *     slots and BH_FeedbackWeightSum, BH_Entropy, BH_SurroundingGasVel, MgasEnc, KEflag into `work` for the holes of `queue`.  Emits
+ *     kind 0 on a hole (a merger candidate: r < 2 ForceSoftening / 2.8 and the reposition / check_grav_bound flag) and kind 1 on a gas
+ *     particle (the draw succeeded), both with bits = the marking hole's ID.
+ * shq_bh_marks_resolve     on the owner, the marks gathered from all ranks in any order (it sorts them): zeroes work->SPH_SwallowID
+ *     [n_sph_slots] and work->BH_SwallowID[n_bh_slots]; a gas particle gets the largest ID + 1 of its kind-1 marks, a hole the
+ *     reference's compare-and-swap rule (blackhole.cpp:570-590) applied to its kind-0 marks in ascending hole order.
+ * shq_bh_feedback_effects  shq_bh_feedback for the holes of `queue` whose own mark is 0, the marks in `work` covering the imports'
+ *     slots too: accreted mass, BH mass and momentum, CountProgs, minTimeBin, then BHP.Mass, Part.Vel, Mtrack / Part.Mass and the
+ *     KineticFdbkEnergy reset of those holes.  Nothing on the neighbours' side; emits kind 0 (the hole is swallowed by this one), kind 1
+ *     (the gas particle is), kind 2 (heat: bits = the double injected / mass_j), kind 3 (kick: the double dvel).
+ * shq_bh_effects_apply     on the owner, the effects gathered from all ranks in any order: kind 0 SwallowID = BH_SwallowID - 1,
+ *     SwallowTime = atime, Swallowed, encounter = 0; kind 1 slots_mark_garbage (ReverseLink = MaxPart + 100); kind 2 BHHeated where
+ *     eeqos, add_injected_BH_energy with the MaxThermalU cap; kind 3 Vel += value x get_random_dir(ID).  Before anything is written,
+ *     SHQ_ERR_INVALID (shq_bh_marks_resolve too) for a row outside the particles, a kind that does not fit the particle's type, a hole
+ *     >= 2^31.
+ * Nothing here has run on more than one GPU. */
+typedef struct shq_bh_record {
+    int32_t owner, part_index;      /* rank that owns the particle, its row there */
+    uint32_t hole;                  /* position of the emitting hole in the global queue */
+    int32_t kind;
+    uint64_t bits;                  /* marks: the hole's ID; effects: a double */
+} shq_bh_record;
+int shq_bh_accretion_marks(shq_context *ctx, const shq_tree_view *tree, const shq_part_view *parts, const shq_sph_view *sph, const shq_bh_slot_view *bh,
+                           const uint64_t *ids, const int32_t *queue, int64_t nqueue, const shq_kick_factors *kf, const shq_bh_params *params, int64_t Ti_Current,
+                           const double *rnd_table, int64_t rnd_size, const shq_bh_work *work, int64_t nlocal, const int32_t *ghost_owner,
+                           const int32_t *ghost_index, int nranks, int rank, int64_t queue_offset, shq_bh_record *records, int64_t capacity, int64_t *counts,
+                           int64_t *nrecords);
+int shq_bh_marks_resolve(shq_context *ctx, const shq_part_view *parts, const uint64_t *ids, const shq_bh_record *marks, int64_t n, int64_t Ti_Current,
+                         int64_t n_sph_slots, int64_t n_bh_slots, const shq_bh_work *work);
+int shq_bh_feedback_effects(shq_context *ctx, const shq_tree_view *tree, const shq_part_view *parts, const shq_sph_view *sph, const shq_bh_slot_view *bh,
+                            const uint64_t *ids, const int32_t *queue, int64_t nqueue, const shq_kick_factors *kf, const shq_bh_params *params,
+                            const double *rnd_table, int64_t rnd_size, const shq_bh_work *work, int64_t nlocal, const int32_t *ghost_owner,
+                            const int32_t *ghost_index, int nranks, int rank, int64_t queue_offset, shq_bh_record *records, int64_t capacity, int64_t *counts,
+                            int64_t *nrecords);
+int shq_bh_effects_apply(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_bh_slot_view *bh, const uint64_t *ids,
+                         const shq_bh_record *effects, int64_t n, const shq_bh_params *params, int64_t MaxPart, const double *rnd_table, int64_t rnd_size,
+                         const uint8_t *eeqos, const shq_bh_work *work, int64_t *n_sph_swallowed, int64_t *n_bh_swallowed);
+
+/* winds_and_feedback()(libgadget/winds.cpp:295-369): the two asymmetric walks over the gas tree for the new
  * stars of the step — sfr_wind_weight_ngbiter (:411-447: mass of the gas inside the star's Hsml that is not already a wind particle,
  * into TotalWeight[star slot]) and sfr_wind_feedback_ngbiter (:510-565: a gas particle becomes a kick candidate when
  * Table[(star ID + gas ID) % size] < windeff Mass / TotalWeight, with get_wind_params, :489-507) — then the reference's resolution:

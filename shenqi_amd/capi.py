@@ -483,6 +483,20 @@ hip.shq_bh_accretion.argtypes = [_vp, C.POINTER(TreeView), C.POINTER(PartView), 
 hip.shq_bh_feedback.argtypes = [_vp, C.POINTER(TreeView), C.POINTER(PartView), C.POINTER(SphView), C.POINTER(BhSlotView), _vp, _vp, C.c_int64, C.POINTER(KickFactors),
                                 C.POINTER(BhParams), C.c_int64, _vp, C.c_int64, _vp, C.POINTER(BhWork), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
 hip.shq_bh_accretion.restype = hip.shq_bh_feedback.restype = C.c_int
+# struct shq_bh_record: what a black-hole walk would have written on a neighbour, routed to the neighbour's owner.  One layout, read as
+# a mark (the 8 bytes are the marking hole's ID) or as an effect (they are a double)
+BH_MARK_DTYPE = np.dtype([("owner", "<i4"), ("part_index", "<i4"), ("hole", "<u4"), ("kind", "<i4"), ("id", "<u8")])
+BH_EFFECT_DTYPE = np.dtype([("owner", "<i4"), ("part_index", "<i4"), ("hole", "<u4"), ("kind", "<i4"), ("value", "<f8")])
+assert BH_MARK_DTYPE.itemsize == BH_EFFECT_DTYPE.itemsize == 24
+_bh_dist = [C.c_int64, _vp, _vp, C.c_int, C.c_int, C.c_int64, _vp, C.c_int64, _vp, C.POINTER(C.c_int64)]   # nlocal ... nrecords
+hip.shq_bh_accretion_marks.argtypes = hip.shq_bh_accretion.argtypes + _bh_dist
+hip.shq_bh_marks_resolve.argtypes = [_vp, C.POINTER(PartView), _vp, _vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(BhWork)]
+hip.shq_bh_feedback_effects.argtypes = [_vp, C.POINTER(TreeView), C.POINTER(PartView), C.POINTER(SphView), C.POINTER(BhSlotView), _vp, _vp, C.c_int64,
+                                        C.POINTER(KickFactors), C.POINTER(BhParams), _vp, C.c_int64, C.POINTER(BhWork)] + _bh_dist
+hip.shq_bh_effects_apply.argtypes = [_vp, C.POINTER(PartView), C.POINTER(SphView), C.POINTER(BhSlotView), _vp, _vp, C.c_int64, C.POINTER(BhParams), C.c_int64, _vp,
+                                     C.c_int64, _vp, C.POINTER(BhWork), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+for _f in ("shq_bh_accretion_marks", "shq_bh_marks_resolve", "shq_bh_feedback_effects", "shq_bh_effects_apply"):
+    getattr(hip, _f).restype = C.c_int
 hip.shq_winds_and_feedback.argtypes = [_vp, C.POINTER(TreeView), C.POINTER(PartView), C.POINTER(SphView), C.POINTER(StarView), _vp, _vp, C.c_int64, C.POINTER(WindParams),
                                        _vp, C.c_int64, _vp, _vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
 hip.shq_winds_and_feedback.restype = C.c_int

@@ -174,7 +174,10 @@ __device__ __forceinline__ unsigned xcd_block(unsigned b, unsigned nb, unsigned 
 }
 
 #define SHQ_NTIMERS 20 /* slots of ev_begin / ev_end: 0-7 are the caller's */
-enum { SHQ_T_PM0 = 8 /* PM phases: SHQ_T_PM0 .. SHQ_T_PM0 + 5 */, SHQ_T_SPH = 14, SHQ_T_TREE = 16, SHQ_T_WALK = SHQ_NTIMERS - 1 };
+enum { SHQ_T_PM0 = 8 /* PM phases: SHQ_T_PM0 .. SHQ_T_PM0 + 5 */, SHQ_T_SPH = 14, SHQ_T_TREE = 16, SHQ_T_WALK = SHQ_NTIMERS - 1,
+       /* the black-hole walks (sph_bh.hip): walk + postprocess of either route, or sort + per-particle kernel of resolve / apply; the count pass
+        * of the routed walks; their route kernel, two sorts and record write */
+       SHQ_T_BH = 15, SHQ_T_BH_COUNT = 17, SHQ_T_BH_ROUTE = 18 };
 
 /* scratch of the device tree build (tree_build.hip) */
 struct TreeBuildBufs {
@@ -354,7 +357,8 @@ struct shq_context {
     DevBuf<double> metal_val[2], metal_star, metal_gd;
     DevBuf<float> metal_gf;
     DevBuf<uint32_t> metal_u32[4];  /* owners, sort orders and original indices of the routed metal-return calls */
-    DevBuf<char> metal_trip;        /* the routed triple list */
+    DevBuf<char> metal_trip;        /* the routed triple list (and the routed black-hole record list) */
+    DevBuf<uint32_t> bhd_kind;      /* kinds of the emitted black-hole records; the run heads of the resolved ones */
     DevBuf<char> wind_kicks;
     DevBuf<double> wind_d;
     DevBuf<unsigned long long> wind_cnt;
@@ -798,6 +802,20 @@ int shq_metal_sums_device(shq_context *ctx, const int32_t *d_qpos, const int32_t
                           double *d_massreturn);
 int shq_bh_accretion_device(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, const int32_t *d_queue, int64_t nq, double *d_post);
 int shq_bh_feedback_device(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, const int32_t *d_queue, int64_t nq);
+/* The parts of the two walks above for a multi-rank driver (effects: the feedback walk, else the accretion walk).
+ * count: the count pass alone, nothing written.  emit: the emit pass for those nrec records, the hole-side postprocess (d_post as in
+ *   shq_bh_accretion_device; not read for the feedback walk) and the list rewritten to (owner, row at the owner, queue_offset + queue
+ *   position, or d_qpos[queue position] where the walk ran over a part of the rank's queue), sorted by these three, in ctx->metal_trip;
+ *   per-owner counts in d_counts[nranks].
+ * resolve / apply: n records (any order) of this rank's own particles, one lane per particle in ascending hole order.  resolve leaves
+ *   (row, mark) per run head in d_out_part / d_out_mark (row -1 elsewhere); apply writes pflags, entropy, heated and velw of w. */
+int shq_bh_records_count_device(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, bool effects, const int32_t *d_queue, int64_t nq, int64_t *nrec);
+int shq_bh_records_emit_device(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, bool effects, const int32_t *d_queue, int64_t nq, int64_t nrec,
+                               int64_t nlocal, const int32_t *d_ghost_owner, const int32_t *d_ghost_index, int nranks, int rank, int64_t queue_offset,
+                               const int32_t *d_qpos, unsigned long long *d_counts, double *d_post);
+int shq_bh_resolve_device(shq_context *ctx, const shq_bh_record *d_rec, int64_t n, const unsigned long long *d_ids, const uint8_t *d_bin_hydro, int64_t Ti_Current,
+                          int32_t *d_out_part, unsigned long long *d_out_mark);
+int shq_bh_apply_device(shq_context *ctx, const BhWalkArgs *w, const shq_bh_record *d_rec, int64_t n);
 /* the particles marked in `mark` (one byte each), ascending, into d_list (room for n entries); *m = their number (one host round trip) */
 int shq_marked_list(shq_context *ctx, const uint8_t *d_mark, int64_t n, int32_t *d_list, int64_t *m);
 

@@ -1313,6 +1313,369 @@ extern "C" int shq_bh_feedback(shq_context *ctx, const shq_tree_view *tree, cons
     return SHQ_OK;
 }
 
+/* ---- the parts of the two calls above for a multi-rank driver ------------------------------------------------------------------- */
+namespace {
+struct BhDist {
+    int64_t nlocal;
+    const int32_t *ghost_owner, *ghost_index;
+    int nranks, rank;
+    int64_t queue_offset;
+    shq_bh_record *records;
+    int64_t capacity, *counts, *nrecords;
+};
+
+int bh_dist_check(const shq_part_view *parts, const int32_t *queue, int64_t nqueue, const BhDist &d, const char *who)
+{
+    const int64_t n = parts->numpart, ng = n - d.nlocal;
+    SHQ_CHECK(d.counts && d.nrecords, SHQ_ERR_INVALID, "%s: null argument", who);
+    SHQ_CHECK(nqueue >= 0 && d.nranks >= 1 && d.rank >= 0 && d.rank < d.nranks && d.nlocal >= 0 && d.nlocal <= n && (ng == 0 || (d.ghost_owner && d.ghost_index)) &&
+                  d.capacity >= 0,
+              SHQ_ERR_INVALID, "%s: bad counts (nqueue %ld, nlocal %ld of %ld, rank %d of %d)", who, (long) nqueue, (long) d.nlocal, (long) n, d.rank, d.nranks);
+    SHQ_CHECK(d.queue_offset >= 0 && d.queue_offset + nqueue < (1ll << 31), SHQ_ERR_INVALID,
+              "%s: a global queue of 2^31 or more holes (offset %ld + %ld): the hole position is 32 bits of a sort key", who, (long) d.queue_offset, (long) nqueue);
+    *d.nrecords = 0;
+    for(int r = 0; r < d.nranks; r++)
+        d.counts[r] = 0;
+    for(int64_t k = 0; k < nqueue; k++)
+        SHQ_CHECK(queue[k] < d.nlocal, SHQ_ERR_INVALID, "%s: queue[%ld] = %d is not one of this rank's own particles", who, (long) k, queue[k]);
+    for(int64_t g = 0; g < ng; g++)
+        SHQ_CHECK(d.ghost_owner[g] >= 0 && d.ghost_owner[g] < d.nranks && d.ghost_index[g] >= 0, SHQ_ERR_INVALID, "%s: import %ld has owner %d, index %d", who, (long) g,
+                  d.ghost_owner[g], d.ghost_index[g]);
+    return SHQ_OK;
+}
+
+/* owners and rows of the imports, then qpos (may be empty), into bhw_tlist; the per-owner counts live behind the emit cursor */
+int bh_dist_upload(shq_context *ctx, int64_t n, const BhDist &d, const std::vector<int32_t> &qpos, int32_t **d_go, int32_t **d_gi, int32_t **d_qpos,
+                   unsigned long long **d_counts)
+{
+    hipStream_t st = ctx->stream;
+    const int64_t ng = n - d.nlocal;
+    const size_t g1 = (size_t) std::max<int64_t>(ng, 1);
+    SHQ_TRY(ctx->bhw_tlist.reserve(2 * g1 + std::max<size_t>(qpos.size(), 1)));
+    SHQ_TRY(ctx->wind_cnt.reserve(4 + (size_t) d.nranks));
+    *d_go = ctx->bhw_tlist.ptr;
+    *d_gi = *d_go + g1;
+    *d_qpos = qpos.empty() ? nullptr : *d_gi + g1;
+    *d_counts = ctx->wind_cnt.ptr + 4;
+    if(ng > 0) {
+        SHQ_HIP(hipMemcpyAsync(*d_go, d.ghost_owner, sizeof(int32_t) * (size_t) ng, hipMemcpyHostToDevice, st));
+        SHQ_HIP(hipMemcpyAsync(*d_gi, d.ghost_index, sizeof(int32_t) * (size_t) ng, hipMemcpyHostToDevice, st));
+    }
+    if(!qpos.empty())
+        SHQ_HIP(hipMemcpyAsync(*d_qpos, qpos.data(), sizeof(int32_t) * qpos.size(), hipMemcpyHostToDevice, st));
+    return SHQ_OK;
+}
+
+/* the routed list and its per-owner counts into the caller's arrays (enqueued; the caller synchronises) */
+int bh_dist_download(shq_context *ctx, const BhDist &d, int64_t nrec, const unsigned long long *d_counts, std::vector<unsigned long long> &hc)
+{
+    hipStream_t st = ctx->stream;
+    hc.assign((size_t) d.nranks, 0);
+    SHQ_HIP(hipMemcpyAsync(hc.data(), d_counts, sizeof(unsigned long long) * (size_t) d.nranks, hipMemcpyDeviceToHost, st));
+    if(nrec > 0)
+        SHQ_HIP(hipMemcpyAsync(d.records, ctx->metal_trip.ptr, sizeof(shq_bh_record) * (size_t) nrec, hipMemcpyDeviceToHost, st));
+    return SHQ_OK;
+}
+
+int bh_dist_counts(const BhDist &d, int64_t nrec, const std::vector<unsigned long long> &hc, const char *who)
+{
+    int64_t sum = 0;
+    for(int r = 0; r < d.nranks; r++)
+        sum += d.counts[r] = (int64_t) hc[(size_t) r];
+    SHQ_CHECK(sum == nrec, SHQ_ERR_STATE, "%s: the per-owner counts add up to %ld of %ld records", who, (long) sum, (long) nrec);
+    return SHQ_OK;
+}
+
+/* what a list of records gathered from other ranks must satisfy before anything reads a particle through it */
+int bh_records_check(const shq_part_view *parts, const shq_bh_record *rec, int64_t n, int maxkind, int64_t n_sph_slots, int64_t n_bh_slots, const char *who)
+{
+    SHQ_CHECK(parts->off_pi != SHQ_NOFIELD && parts->off_type != SHQ_NOFIELD && parts->off_flags != SHQ_NOFIELD, SHQ_ERR_INVALID,
+              "%s: the particle view needs PI, Type and the flag byte", who);
+    const int64_t np = parts->numpart;
+    for(int64_t k = 0; k < n; k++) {
+        const int32_t i = rec[k].part_index, kind = rec[k].kind;
+        SHQ_CHECK(i >= 0 && i < np, SHQ_ERR_INVALID, "%s: record %ld names particle %d of %ld", who, (long) k, i, (long) np);
+        SHQ_CHECK(kind >= 0 && kind <= maxkind, SHQ_ERR_INVALID, "%s: record %ld has kind %d", who, (long) k, kind);
+        const int type = *pfield<uint8_t>(parts, i, parts->off_type);
+        SHQ_CHECK(type == (kind == 0 ? 5 : 0), SHQ_ERR_INVALID, "%s: record %ld of kind %d names particle %d of type %d", who, (long) k, kind, i, type);
+        SHQ_CHECK(rec[k].hole < (1u << 31), SHQ_ERR_INVALID, "%s: record %ld names hole %u: a queue position has 31 bits", who, (long) k, rec[k].hole);
+        const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+        SHQ_CHECK(pi >= 0 && pi < (kind == 0 ? n_bh_slots : n_sph_slots), SHQ_ERR_INVALID, "%s: particle %d has PI %d outside its slot array", who, i, pi);
+    }
+    return SHQ_OK;
+}
+} // namespace
+
+extern "C" int shq_bh_accretion_marks(shq_context *ctx, const shq_tree_view *tree, const shq_part_view *parts, const shq_sph_view *sph, const shq_bh_slot_view *bh,
+                                      const uint64_t *ids, const int32_t *queue, int64_t nqueue, const shq_kick_factors *kf, const shq_bh_params *params,
+                                      int64_t Ti_Current, const double *rnd_table, int64_t rnd_size, const shq_bh_work *work, int64_t nlocal,
+                                      const int32_t *ghost_owner, const int32_t *ghost_index, int nranks, int rank, int64_t queue_offset, shq_bh_record *records,
+                                      int64_t capacity, int64_t *counts, int64_t *nrecords)
+{
+    const char *who = "bh_accretion_marks";
+    SHQ_TRY(bh_check_common(ctx, tree, parts, sph, bh, ids, queue, nqueue, kf, params, rnd_table, rnd_size, work, who));
+    const BhDist d = {nlocal, ghost_owner, ghost_index, nranks, rank, queue_offset, records, capacity, counts, nrecords};
+    SHQ_TRY(bh_dist_check(parts, queue, nqueue, d, who));
+    if(nqueue == 0)
+        return SHQ_OK;
+    SHQ_HIP(hipSetDevice(ctx->device));
+    const int64_t n = parts->numpart;
+    BhSet S;
+    SHQ_TRY(bh_collect(parts, bh, work, false, S));
+    const size_t nbh = S.bhp.size();
+    std::vector<int32_t> q(queue, queue + nqueue);
+    SHQ_TRY(bh_upload_common(ctx, tree, parts, sph, ids, rnd_table, rnd_size, S, q));
+    int32_t *d_go, *d_gi, *d_qpos;
+    unsigned long long *d_counts;
+    SHQ_TRY(bh_dist_upload(ctx, n, d, std::vector<int32_t>(), &d_go, &d_gi, &d_qpos, &d_counts));
+    hipStream_t st = ctx->stream;
+    BhWalkArgs w;
+    bh_fill_args(ctx, params, rnd_size, nbh, w);
+    w.Ti_Current = Ti_Current;
+    int64_t nrec = 0;
+    SHQ_TRY(shq_bh_records_count_device(ctx, kf, &w, false, ctx->bhw_queue.ptr, nqueue, &nrec));
+    *nrecords = nrec;
+    if(!records)
+        return SHQ_OK;
+    SHQ_CHECK(capacity >= nrec, SHQ_ERR_INVALID, "%s: room for %ld records, %ld found", who, (long) capacity, (long) nrec);
+    double *d_post = ctx->bhw_out.ptr + 8 * (size_t) nqueue;
+    SHQ_TRY(shq_bh_records_emit_device(ctx, kf, &w, false, ctx->bhw_queue.ptr, nqueue, nrec, nlocal, d_go, d_gi, nranks, rank, queue_offset, nullptr, d_counts, d_post));
+    std::vector<double> out(16 * (size_t) nqueue);
+    std::vector<unsigned long long> hc;
+    SHQ_HIP(hipMemcpyAsync(out.data(), ctx->bhw_out.ptr, sizeof(double) * out.size(), hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipMemcpyAsync(S.rec.data(), ctx->bhw_rec.ptr, sizeof(BhRec) * nbh, hipMemcpyDeviceToHost, st));
+    SHQ_TRY(bh_dist_download(ctx, d, nrec, d_counts, hc));
+    SHQ_HIP(hipStreamSynchronize(st));
+    SHQ_TRY(bh_dist_counts(d, nrec, hc, who));
+    for(int64_t t = 0; t < nqueue; t++) { /* blackhole_accretion_reduce (PRIMARY) and what the postprocess left, as in shq_bh_accretion */
+        const size_t b = (size_t) (std::lower_bound(S.bhp.begin(), S.bhp.end(), queue[t]) - S.bhp.begin());
+        const int32_t pi = S.pi[b];
+        const double *o = &out[8 * (size_t) t], *p = &out[8 * (size_t) nqueue + 8 * (size_t) t];
+        const BhRec &R = S.rec[b];
+        *bhfield<int8_t>(bh, pi, bh->off_encounter) = (int8_t) o[0];
+        work->BH_FeedbackWeightSum[pi] = o[1];
+        work->MgasEnc[pi] = o[6];
+        work->BH_Entropy[pi] = p[0];
+        for(int k = 0; k < 3; k++) {
+            work->BH_SurroundingGasVel[pi][k] = p[1 + k];
+            bhfield<double>(bh, pi, bh->off_dragaccel)[k] = p[4 + k];
+        }
+        *bhfield<double>(bh, pi, bh->off_mdot) = R.Mdot;
+        *bhfield<double>(bh, pi, bh->off_mass) = R.Mass;
+        *bhfield<double>(bh, pi, bh->off_kineticfdbkenergy) = R.KineticFdbkEnergy;
+        if(work->KEflag)
+            work->KEflag[pi] = R.KEflag;
+    }
+    return SHQ_OK;
+}
+
+extern "C" int shq_bh_marks_resolve(shq_context *ctx, const shq_part_view *parts, const uint64_t *ids, const shq_bh_record *marks, int64_t n, int64_t Ti_Current,
+                                    int64_t n_sph_slots, int64_t n_bh_slots, const shq_bh_work *work)
+{
+    const char *who = "bh_marks_resolve";
+    SHQ_CHECK(ctx && parts && ids && work && work->SPH_SwallowID && work->BH_SwallowID && n >= 0 && (n == 0 || marks) && n_sph_slots >= 0 && n_bh_slots >= 0,
+              SHQ_ERR_INVALID, "%s: null argument", who);
+    SHQ_CHECK(parts->off_timebin_hydro != SHQ_NOFIELD, SHQ_ERR_INVALID, "%s: the particle view needs TimeBinHydro", who);
+    SHQ_TRY(bh_records_check(parts, marks, n, 1, n_sph_slots, n_bh_slots, who));
+    memset(work->SPH_SwallowID, 0, sizeof(uint64_t) * (size_t) n_sph_slots);
+    memset(work->BH_SwallowID, 0, sizeof(uint64_t) * (size_t) n_bh_slots);
+    if(n == 0)
+        return SHQ_OK;
+    SHQ_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t np = parts->numpart;
+    std::vector<uint8_t> bin((size_t) np);
+    for(int64_t i = 0; i < np; i++)
+        bin[(size_t) i] = *pfield<uint8_t>(parts, i, parts->off_timebin_hydro);
+    SHQ_TRY(up(ctx, ctx->bhw_eeqos, bin));
+    SHQ_TRY(ids_upload(ctx, ids, np));
+    SHQ_TRY(ctx->metal_trip.reserve((size_t) n * sizeof(shq_bh_record)));
+    SHQ_TRY(ctx->bhw_tlist.reserve((size_t) n));
+    SHQ_TRY(ctx->bhw_sphsw.reserve((size_t) n));
+    SHQ_HIP(hipMemcpyAsync(ctx->metal_trip.ptr, marks, sizeof(shq_bh_record) * (size_t) n, hipMemcpyHostToDevice, st));
+    SHQ_TRY(shq_bh_resolve_device(ctx, reinterpret_cast<const shq_bh_record *>(ctx->metal_trip.ptr), n, ctx->bhw_ids.ptr, ctx->bhw_eeqos.ptr, Ti_Current,
+                                  ctx->bhw_tlist.ptr, ctx->bhw_sphsw.ptr));
+    std::vector<int32_t> part((size_t) n);
+    std::vector<unsigned long long> mark((size_t) n);
+    SHQ_HIP(hipMemcpyAsync(part.data(), ctx->bhw_tlist.ptr, sizeof(int32_t) * (size_t) n, hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipMemcpyAsync(mark.data(), ctx->bhw_sphsw.ptr, sizeof(unsigned long long) * (size_t) n, hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipStreamSynchronize(st));
+    for(int64_t k = 0; k < n; k++) {
+        const int32_t i = part[(size_t) k];
+        if(i < 0)
+            continue;
+        const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+        (*pfield<uint8_t>(parts, i, parts->off_type) == 0 ? work->SPH_SwallowID : work->BH_SwallowID)[pi] = mark[(size_t) k];
+    }
+    return SHQ_OK;
+}
+
+extern "C" int shq_bh_feedback_effects(shq_context *ctx, const shq_tree_view *tree, const shq_part_view *parts, const shq_sph_view *sph, const shq_bh_slot_view *bh,
+                                       const uint64_t *ids, const int32_t *queue, int64_t nqueue, const shq_kick_factors *kf, const shq_bh_params *params,
+                                       const double *rnd_table, int64_t rnd_size, const shq_bh_work *work, int64_t nlocal, const int32_t *ghost_owner,
+                                       const int32_t *ghost_index, int nranks, int rank, int64_t queue_offset, shq_bh_record *records, int64_t capacity,
+                                       int64_t *counts, int64_t *nrecords)
+{
+    const char *who = "bh_feedback_effects";
+    SHQ_TRY(bh_check_common(ctx, tree, parts, sph, bh, ids, queue, nqueue, kf, params, rnd_table, rnd_size, work, who));
+    SHQ_CHECK(work->BH_accreted_Mass && work->BH_accreted_BHMass && work->BH_accreted_momentum, SHQ_ERR_INVALID, "%s: the accreted-mass arrays are needed", who);
+    const BhDist d = {nlocal, ghost_owner, ghost_index, nranks, rank, queue_offset, records, capacity, counts, nrecords};
+    SHQ_TRY(bh_dist_check(parts, queue, nqueue, d, who));
+    SHQ_HIP(hipSetDevice(ctx->device));
+    const int64_t n = parts->numpart;
+    BhSet S;
+    SHQ_TRY(bh_collect(parts, bh, work, true, S));
+    const size_t nbh = S.bhp.size();
+    /* blackhole_feedback_haswork (:878-883); a hole's record still carries its position in the whole queue */
+    std::vector<int32_t> q, qpos;
+    for(int64_t k = 0; k < nqueue; k++)
+        if(work->BH_SwallowID[*pfield<int32_t>(parts, queue[k], parts->off_pi)] == 0) {
+            q.push_back(queue[k]);
+            qpos.push_back((int32_t) k);
+        }
+    const int64_t nq = (int64_t) q.size();
+    if(nq == 0)
+        return SHQ_OK;
+    SHQ_TRY(bh_upload_common(ctx, tree, parts, sph, ids, rnd_table, rnd_size, S, q));
+    int32_t *d_go, *d_gi, *d_qpos;
+    unsigned long long *d_counts;
+    SHQ_TRY(bh_dist_upload(ctx, n, d, qpos, &d_go, &d_gi, &d_qpos, &d_counts));
+    hipStream_t st = ctx->stream;
+    std::vector<uint64_t> sphsw((size_t) std::max<int64_t>(n, 1), 0), bhsw(std::max<size_t>(nbh, 1), 0);
+    for(int64_t i = 0; i < n; i++)
+        if(*pfield<uint8_t>(parts, i, parts->off_type) == 0 && !(*pfield<uint8_t>(parts, i, parts->off_flags) & 1u)) {
+            const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+            SHQ_CHECK(pi >= 0 && pi < sph->numslots, SHQ_ERR_INVALID, "%s: gas particle %ld has PI %d outside the slot array", who, (long) i, pi);
+            sphsw[(size_t) i] = work->SPH_SwallowID[pi];
+        }
+    for(size_t b = 0; b < nbh; b++)
+        bhsw[b] = work->BH_SwallowID[S.pi[b]];
+    SHQ_HIP(hipMemcpyAsync(ctx->bhw_sphsw.ptr, sphsw.data(), sizeof(uint64_t) * (size_t) n, hipMemcpyHostToDevice, st));
+    SHQ_HIP(hipMemcpyAsync(ctx->bhw_bhsw.ptr, bhsw.data(), sizeof(uint64_t) * nbh, hipMemcpyHostToDevice, st));
+    BhWalkArgs w;
+    bh_fill_args(ctx, params, rnd_size, nbh, w);
+    int64_t nrec = 0;
+    SHQ_TRY(shq_bh_records_count_device(ctx, kf, &w, true, ctx->bhw_queue.ptr, nq, &nrec));
+    *nrecords = nrec;
+    if(!records)
+        return SHQ_OK;
+    SHQ_CHECK(capacity >= nrec, SHQ_ERR_INVALID, "%s: room for %ld records, %ld found", who, (long) capacity, (long) nrec);
+    SHQ_TRY(shq_bh_records_emit_device(ctx, kf, &w, true, ctx->bhw_queue.ptr, nq, nrec, nlocal, d_go, d_gi, nranks, rank, queue_offset, d_qpos, d_counts, nullptr));
+    /* the holes of the queue after the postprocess: their records, and Vel and Mass as rows */
+    SHQ_TRY(ctx->bhw_trows.reserve(8 * (size_t) nq));
+    SHQ_TRY(shq_rows_gather(ctx, ctx->bhw_queue.ptr, nq, nullptr, ctx->bhw_trows.ptr));
+    std::vector<double> out(8 * (size_t) nq), rows(8 * (size_t) nq);
+    std::vector<unsigned long long> hc;
+    SHQ_HIP(hipMemcpyAsync(out.data(), ctx->bhw_out.ptr, sizeof(double) * out.size(), hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipMemcpyAsync(rows.data(), ctx->bhw_trows.ptr, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipMemcpyAsync(S.rec.data(), ctx->bhw_rec.ptr, sizeof(BhRec) * nbh, hipMemcpyDeviceToHost, st));
+    SHQ_TRY(bh_dist_download(ctx, d, nrec, d_counts, hc));
+    SHQ_HIP(hipStreamSynchronize(st));
+    SHQ_TRY(bh_dist_counts(d, nrec, hc, who));
+    for(int64_t t = 0; t < nq; t++) { /* blackhole_feedback_reduce (PRIMARY) and the postprocess, as in shq_bh_feedback */
+        const int32_t i = q[(size_t) t];
+        const size_t b = (size_t) (std::lower_bound(S.bhp.begin(), S.bhp.end(), i) - S.bhp.begin());
+        const int32_t pi = S.pi[b];
+        const double *o = &out[8 * (size_t) t], *r = &rows[8 * (size_t) t];
+        const BhRec &R = S.rec[b];
+        work->BH_accreted_Mass[pi] = o[0];
+        work->BH_accreted_BHMass[pi] = o[1];
+        for(int k = 0; k < 3; k++)
+            work->BH_accreted_momentum[pi][k] = o[2 + k];
+        *bhfield<uint8_t>(bh, pi, bh->off_mintimebin) = (uint8_t) o[6];
+        *bhfield<int32_t>(bh, pi, bh->off_countprogs) = R.CountProgs;
+        *bhfield<double>(bh, pi, bh->off_mass) = R.Mass;
+        *bhfield<double>(bh, pi, bh->off_mtrack) = R.Mtrack;
+        *bhfield<double>(bh, pi, bh->off_kineticfdbkenergy) = R.KineticFdbkEnergy;
+        double *v = pfield_w<double>(parts, i, parts->off_vel);
+        for(int k = 0; k < 3; k++)
+            v[k] = r[k];
+        *pfield_w<float>(parts, i, parts->off_mass) = (float) r[5];
+    }
+    return SHQ_OK;
+}
+
+extern "C" int shq_bh_effects_apply(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_bh_slot_view *bh, const uint64_t *ids,
+                                    const shq_bh_record *effects, int64_t n, const shq_bh_params *params, int64_t MaxPart, const double *rnd_table, int64_t rnd_size,
+                                    const uint8_t *eeqos, const shq_bh_work *work, int64_t *n_sph_swallowed, int64_t *n_bh_swallowed)
+{
+    const char *who = "bh_effects_apply";
+    SHQ_CHECK(ctx && parts && sph && bh && ids && params && rnd_table && work && work->BH_SwallowID && n >= 0 && (n == 0 || effects), SHQ_ERR_INVALID,
+              "%s: null argument", who);
+    SHQ_CHECK(rnd_size > 0, SHQ_ERR_INVALID, "%s: empty random table", who);
+    SHQ_CHECK(parts->off_vel != SHQ_NOFIELD, SHQ_ERR_INVALID, "%s: the particle view needs Vel", who);
+    SHQ_TRY(bh_records_check(parts, effects, n, 3, sph->numslots, bh->numslots, who));
+    if(n_sph_swallowed)
+        *n_sph_swallowed = 0;
+    if(n_bh_swallowed)
+        *n_bh_swallowed = 0;
+    if(n == 0)
+        return SHQ_OK;
+    SHQ_HIP(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const int64_t np = parts->numpart;
+    SHQ_TRY(shq_particles_upload(ctx, parts));
+    SHQ_TRY(sph_upload(ctx, parts, sph));
+    SHQ_TRY(ids_upload(ctx, ids, np));
+    std::vector<int32_t> list((size_t) n);
+    for(int64_t k = 0; k < n; k++)
+        list[(size_t) k] = effects[k].part_index;
+    std::sort(list.begin(), list.end());
+    list.erase(std::unique(list.begin(), list.end()), list.end());
+    const int64_t m = (int64_t) list.size();
+    SHQ_TRY(ctx->bhw_rnd.reserve((size_t) rnd_size));
+    SHQ_TRY(ctx->bhw_eeqos.reserve((size_t) np));
+    SHQ_TRY(ctx->bhw_heated.reserve((size_t) np));
+    SHQ_TRY(ctx->metal_trip.reserve((size_t) n * sizeof(shq_bh_record)));
+    SHQ_TRY(ctx->bhw_trows.reserve(8 * (size_t) m));
+    SHQ_TRY(up(ctx, ctx->bhw_tlist, list));
+    SHQ_HIP(hipMemcpyAsync(ctx->bhw_rnd.ptr, rnd_table, sizeof(double) * (size_t) rnd_size, hipMemcpyHostToDevice, st));
+    if(eeqos)
+        SHQ_HIP(hipMemcpyAsync(ctx->bhw_eeqos.ptr, eeqos, (size_t) np, hipMemcpyHostToDevice, st));
+    SHQ_HIP(hipMemsetAsync(ctx->bhw_heated.ptr, 0, (size_t) np, st));
+    SHQ_HIP(hipMemcpyAsync(ctx->metal_trip.ptr, effects, sizeof(shq_bh_record) * (size_t) n, hipMemcpyHostToDevice, st));
+    BhWalkArgs w;
+    bh_fill_args(ctx, params, rnd_size, 0, w);
+    w.eeqos = eeqos ? ctx->bhw_eeqos.ptr : nullptr;
+    w.heated = ctx->bhw_heated.ptr;
+    SHQ_TRY(shq_bh_apply_device(ctx, &w, reinterpret_cast<const shq_bh_record *>(ctx->metal_trip.ptr), n));
+    SHQ_TRY(shq_rows_gather(ctx, ctx->bhw_tlist.ptr, m, ctx->bhw_heated.ptr, ctx->bhw_trows.ptr));
+    std::vector<double> rows(8 * (size_t) m);
+    SHQ_HIP(hipMemcpyAsync(rows.data(), ctx->bhw_trows.ptr, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipStreamSynchronize(st));
+    int64_t nsph = 0, nbhs = 0;
+    for(int64_t t = 0; t < m; t++) {
+        const int64_t i = list[(size_t) t];
+        const double *r = &rows[8 * (size_t) t];
+        const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+        uint8_t *flags = pfield_w<uint8_t>(parts, i, parts->off_flags);
+        if(*pfield<uint8_t>(parts, i, parts->off_type) == 0) {
+            *sfield(sph, pi, sph->off_entropy) = r[3];
+            double *v = pfield_w<double>(parts, i, parts->off_vel);
+            for(int k = 0; k < 3; k++)
+                v[k] = r[k];
+            if(r[7] != 0)
+                *flags |= 8u; /* BHHeated */
+            if(((unsigned) r[6] & 1u) && !(*flags & 1u)) { /* slots_mark_garbage, slotsmanager.cpp:590-599 */
+                *flags |= 1u;
+                *reinterpret_cast<int32_t *>(static_cast<char *>(sph->base) + (size_t) pi * sph->elsize) = (int32_t) (MaxPart + 100);
+                nsph++;
+            }
+        } else if(((unsigned) r[6] & 2u) && !(*flags & 2u)) {
+            *flags |= 2u; /* Swallowed */
+            *bhfield<uint64_t>(bh, pi, bh->off_swallowid) = work->BH_SwallowID[pi] - 1;
+            *bhfield<double>(bh, pi, bh->off_swallowtime) = params->atime;
+            *bhfield<int8_t>(bh, pi, bh->off_encounter) = 0;
+            nbhs++;
+        }
+    }
+    if(n_sph_swallowed)
+        *n_sph_swallowed = nsph;
+    if(n_bh_swallowed)
+        *n_bh_swallowed = nbhs;
+    return SHQ_OK;
+}
+
 /* ---- winds_and_feedback (winds.cpp:295-369) ------------------------------------------------------------------------------------ */
 namespace {
 /* Vel, Entropy, DelayTime of the kicked particles (the first of every run of the sorted list) back into the caller's arrays */

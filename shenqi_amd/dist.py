@@ -457,6 +457,49 @@ def import_ghost_gas(comm, decomp, P, SphP, reach, reach_of_rank):
     return Pall, Sall, ng
 
 
+def import_ghost_gas_bh(comm, decomp, P, SphP, BhP, reach_of_rank):
+    """import_ghost_gas for the black-hole walks, whose neighbour search is symmetric (r2 <= max(Hsml_i, Hsml_j)^2) over gas and holes:
+    P followed by the other ranks' live gas and their live, unswallowed holes within max(own Hsml, reach_of_rank[d]) of this rank's
+    slab (reach_of_rank[d]: the largest Hsml of rank d's queued holes).  The ghosts' gas and black-hole slot rows come after SphP's and
+    BhP's (PI rewritten); owner in TopLeaf, row at the owner in GrNr.  Returns (Pall, Sall, Ball, number of ghosts)."""
+    nloc, psz, ssz, bsz = len(P), P.dtype.itemsize, SphP.dtype.itemsize, BhP.dtype.itemsize
+    gas, hole = P["Type"] == 0, (P["Type"] == 5) & ((P["Flags"] & 2) == 0)
+    sel = np.flatnonzero(((P["Flags"] & 1) == 0) & (gas | hole))
+    G = P[sel].copy()
+    G["TopLeaf"] = comm.rank
+    G["GrNr"] = sel
+    g = G["Type"] == 0
+    rec = np.zeros((len(G), psz + max(ssz, bsz)), dtype=np.uint8)                 # a particle's record, then its slot's
+    rec[:, :psz] = G.view(np.uint8).reshape(len(G), psz)
+    rec[g, psz:psz + ssz] = SphP[G["PI"][g]].view(np.uint8).reshape(-1, ssz)
+    rec[~g, psz:psz + bsz] = BhP[G["PI"][~g]].view(np.uint8).reshape(-1, bsz)
+    got = ghost_records(comm, decomp, torch.from_numpy(np.ascontiguousarray(G["Pos"][:, 0])), torch.from_numpy(np.ascontiguousarray(G["Hsml"])),
+                        torch.from_numpy(rec), reach_of_rank).numpy()
+    Pall = append_records(P, got[:, :psz])
+    gg = Pall["Type"][nloc:] == 0
+    Sall = append_records(SphP, got[gg, psz:psz + ssz])
+    Ball = append_records(BhP, got[~gg, psz:psz + bsz])
+    Pall["PI"][nloc:][gg] = len(SphP) + np.arange(int(gg.sum()))
+    Pall["PI"][nloc:][~gg] = len(BhP) + np.arange(int((~gg).sum()))
+    return Pall, Sall, Ball, len(got)
+
+
+def fetch_from_owners(comm, owner, index, rows):
+    """For each (owner[k], index[k]) asked for, row index[k] of the owner's `rows` as it is now: a 2-D numpy array (uint8, or any type
+    all_to_all_rows moves), or a function of the asked indices that returns their rows.  Two all_to_all_rows: the indices out, the rows
+    back along the same counts - the order within a pair of ranks is kept, so no key travels back."""
+    owner, index = np.asarray(owner, dtype=np.int64), np.asarray(index, dtype=np.int64)
+    take = rows if callable(rows) else (lambda ask: rows[ask])
+    order = np.argsort(owner, kind="stable")
+    counts = np.bincount(owner, minlength=comm.size).tolist()
+    ask, acounts = comm.all_to_all_rows(torch.from_numpy(index[order].reshape(-1, 1)), counts)
+    ans = np.ascontiguousarray(take(np.ascontiguousarray(ask.numpy()).reshape(-1)))
+    back, _ = comm.all_to_all_rows(torch.from_numpy(ans), acounts)
+    out = np.empty_like(ans, shape=(len(owner),) + ans.shape[1:])
+    out[order] = back.numpy()
+    return out
+
+
 def widen_until_covered(comm, hfac, start_radius, attempt):
     """The repeat-on-a-wider-halo protocol of the operators that iterate a search radius (the Hsml loops of density and
     stellar_density).  Every rank starts with the halo hfac x start_radius (the largest radius of its targets) and calls
@@ -1667,6 +1710,192 @@ class GpuMetalOps:
         out = np.zeros(max(nqueue, 1))
         capi.check(capi.hip.shq_metal_return_sums(self.ctx.h, capi.ptr(a[0]), capi.ptr(a[1]), capi.ptr(a[2]), capi.ptr(thismass), len(thismass), nqueue, capi.ptr(out)))
         return out[:nqueue]
+
+
+# Black-hole accretion and feedback across ranks (libgadget/blackhole.cpp:217-370).  Both walks write on the neighbours' side: merger
+# and swallow marks, flags, the entropy with its cap, kicks.  The reference exports a hole's query to the ranks its kernel touches
+# and does those writes there with atomics, in thread-arrival order.  Here, as for the metal return, every rank imports the gas and the
+# holes within reach of its slab, walks its own queued holes over local + ghost particles, and a walk only emits records of what it
+# would have written: they travel to the particle's owner, who applies a particle's records in the order of the GLOBAL queue (the ranks'
+# queues one after the other).  Between the two walks the ghosts are refreshed from their owners: the resolved marks, and the holes'
+# slots, whose Mass grew in the owner's accretion postprocess.
+BH_WORK = (("SPH_SwallowID", np.uint64, 0, ()), ("BH_SwallowID", np.uint64, 1, ()), ("BH_FeedbackWeightSum", np.float64, 1, ()), ("BH_Entropy", np.float64, 1, ()),
+           ("BH_SurroundingGasVel", np.float64, 1, (3,)), ("MgasEnc", np.float64, 1, ()), ("KEflag", np.int32, 1, ()), ("BH_accreted_Mass", np.float64, 1, ()),
+           ("BH_accreted_BHMass", np.float64, 1, ()), ("BH_accreted_momentum", np.float64, 1, (3,)))
+
+
+def bh_work_arrays(nsph, nbh):
+    """struct BHPriv's arrays (shq_bh_work) by slot index, zeroed: SPH_SwallowID over the gas slots, the rest over the hole slots"""
+    return {k: np.zeros((max(nbh if by_bh else nsph, 1),) + shape, dtype=t) for k, t, by_bh, shape in BH_WORK}
+
+
+class DistBlackHole:
+    """P: numpy PARTICLE_DTYPE array of everything this rank owns (gas PI -> SphP, hole PI -> BhP), IDs in P["ID"]; queue: rows of P, the
+    active live holes.  kf: the kick factors, prm: the shq_bh_params fields as attributes, eeqos: one byte per row of P or None.
+
+    ops.accretion_marks(Pall, Sall, Ball, nlocal, queue, ghost_owner, ghost_index, nranks, rank, queue_offset, kf, prm, Ti_Current, rnd,
+        work) -> (marks: capi.BH_MARK_DTYPE sorted by (owner, part_index, hole), counts per owner); the slots of Ball and the hole-side
+        arrays of work updated for the queue's holes;
+    ops.marks_resolve(P, marks, Ti_Current, nsph, nbh, work): SPH_SwallowID[:nsph] and BH_SwallowID[:nbh] of work zeroed and set;
+    ops.feedback_effects(Pall, Sall, Ball, nlocal, queue, ghost_owner, ghost_index, nranks, rank, queue_offset, kf, prm, rnd, work)
+        -> (effects: capi.BH_EFFECT_DTYPE, counts per owner); Vel and Mass of Pall, Ball and work updated for the queue's holes;
+    ops.effects_apply(P, SphP, BhP, effects, prm, MaxPart, rnd, eeqos, work) -> (gas swallowed, holes swallowed)
+    (GpuBhOps below; the CPU tests use the restatement).  After run(): nghost, marks_sent[kind], effects_sent[kind] (records that left
+    this rank), n_sph_swallowed, n_bh_swallowed, and work: the BHPriv arrays of the rank's own slots.
+    Nothing here has run on more than one GPU."""
+
+    def __init__(self, comm, decomp, ops):
+        self.comm, self.d, self.ops = comm, decomp, ops
+        self._reset(0, 0)
+
+    def _reset(self, nsph, nbh):
+        self.nghost = self.n_sph_swallowed = self.n_bh_swallowed = 0
+        self.marks_sent, self.effects_sent = [0, 0], [0, 0, 0, 0]
+        self.work = bh_work_arrays(nsph, nbh)
+
+    def _to_owners(self, rec, counts, sent):
+        """24-byte records as three int64 words to their owners; counts those that leave, by kind, into `sent`"""
+        away = rec["kind"][rec["owner"] != self.comm.rank]
+        sent[:] = np.bincount(away, minlength=len(sent)).tolist()
+        words = torch.from_numpy(np.ascontiguousarray(rec).view(np.int64).reshape(len(rec), 3))
+        recv, _ = self.comm.all_to_all_rows(words, [int(c) for c in counts])
+        return np.ascontiguousarray(recv.numpy()).view(rec.dtype).reshape(-1)
+
+    def run(self, P, SphP, BhP, queue, kf, prm, Ti_Current, MaxPart, rnd, eeqos):
+        """blackhole()'s two treewalks for the holes of `queue`.  Updates P, SphP and BhP for what this rank owns; returns
+        (gas swallowed, holes swallowed) among its own particles."""
+        comm, ops = self.comm, self.ops
+        nloc, ns, nb, size = len(P), len(SphP), len(BhP), comm.size
+        queue = np.ascontiguousarray(queue, dtype=np.int32)
+        nq = len(queue)
+        nqs = [int(x) for x in comm.gather_scalar(nq, np.int64)]
+        off, total = sum(nqs[:comm.rank]), sum(nqs)
+        self._reset(ns, nb)
+        if total == 0:
+            return 0, 0
+        reach = comm.gather_scalar(float(P["Hsml"][queue].max()) if nq else 0.0)
+        Pall, Sall, Ball, self.nghost = import_ghost_gas_bh(comm, self.d, P, SphP, BhP, reach)
+        work = bh_work_arrays(len(Sall), len(Ball))
+        own = {k: v[:(nb if by_bh else ns)] for (k, _, by_bh, _), v in zip(BH_WORK, work.values())}     # views of the rank's own slots
+        gown = np.ascontiguousarray(Pall["TopLeaf"][nloc:], dtype=np.int32)
+        gidx = np.ascontiguousarray(Pall["GrNr"][nloc:], dtype=np.int32)
+        marks, counts = ops.accretion_marks(Pall, Sall, Ball, nloc, queue, gown, gidx, size, comm.rank, off, kf, prm, Ti_Current, rnd, work)
+        BhP[:] = Ball[:nb]
+        ops.marks_resolve(P, self._to_owners(marks, counts, self.marks_sent), Ti_Current, ns, nb, work)
+        # The ghosts as their owners have them now: the resolved marks, and the holes' slots - an active hole's Mass grew by Mdot dtime
+        # in its owner's postprocess, and the feedback walk adds that Mass to its swallower
+        ggas = Pall["Type"][nloc:] == 0
+        pi = P["PI"].astype(np.int64)
+        u8 = lambda a: np.ascontiguousarray(a).view(np.uint8).reshape(len(a), a.dtype.itemsize)      # noqa: E731
+        work["SPH_SwallowID"][ns:ns + int(ggas.sum())] = fetch_from_owners(
+            comm, gown[ggas], gidx[ggas], lambda ask: u8(own["SPH_SwallowID"][pi[ask]])).view(np.uint64).reshape(-1)
+        got = fetch_from_owners(comm, gown[~ggas], gidx[~ggas], lambda ask: np.concatenate([u8(BhP[pi[ask]]), u8(own["BH_SwallowID"][pi[ask]])], axis=1))
+        nbg, bsz = int((~ggas).sum()), BhP.dtype.itemsize
+        Ball[nb:] = np.ascontiguousarray(got[:, :bsz]).view(BhP.dtype).reshape(nbg)
+        work["BH_SwallowID"][nb:nb + nbg] = np.ascontiguousarray(got[:, bsz:]).view(np.uint64).reshape(-1)
+        effects, counts = ops.feedback_effects(Pall, Sall, Ball, nloc, queue, gown, gidx, size, comm.rank, off, kf, prm, rnd, work)
+        BhP[:] = Ball[:nb]
+        P["Vel"][queue], P["Mass"][queue] = Pall["Vel"][queue], Pall["Mass"][queue]
+        res = ops.effects_apply(P, SphP, BhP, self._to_owners(effects, counts, self.effects_sent), prm, MaxPart, rnd, eeqos, own)
+        self.n_sph_swallowed, self.n_bh_swallowed = int(res[0]), int(res[1])
+        self.work = {k: v.copy() for k, v in own.items()}
+        return self.n_sph_swallowed, self.n_bh_swallowed
+
+
+class GpuBhOps:
+    """DistBlackHole's four steps on the device library (shq_bh_accretion_marks / _marks_resolve / _feedback_effects / _effects_apply)
+    through the host mirror's tree builder (gas + holes, moments with hmax)."""
+
+    def __init__(self, ctx, BoxSize):
+        import shenqi_amd as sq
+        self.sq, self.ctx, self.L = sq, ctx, BoxSize
+        self._walkset, self._room = None, {}
+
+    @staticmethod
+    def _params(prm):
+        p = capi.BhParams()
+        for k, _ in capi.BhParams._fields_:
+            setattr(p, k, getattr(prm, k))
+        return p
+
+    @staticmethod
+    def _work(work):
+        return capi.BhWork(*[work[k].ctypes.data for k, _ in capi.BhWork._fields_])
+
+    def _tree(self, Pall):
+        """the particle manager and tree of the walks; the feedback walk takes the accretion walk's (same records, nothing moved)"""
+        sq = self.sq
+        if self._walkset is not None and self._walkset[0] is Pall:
+            pman, tree = self._walkset[1:]
+            pman.Base[:] = Pall
+            return pman, tree
+        pman = records_pman(sq, self.L, Pall)
+        tree = sq.force_tree_rebuild_mask(pman, sq.GASMASK + sq.BHMASK)
+        sq.force_tree_update_hmax(tree, pman)
+        self._walkset = (Pall, pman, tree)
+        return pman, tree
+
+    def _walk(self, fn, Pall, Sall, Ball, nlocal, queue, gown, gidx, nranks, rank, off, kf, prm, rnd, work, dtype, Ti=None):
+        pman, tree = self._tree(Pall)
+        ids = np.ascontiguousarray(Pall["ID"])
+        queue = np.ascontiguousarray(queue, dtype=np.int32)
+        rnd = np.ascontiguousarray(rnd, dtype=np.float64)
+        pv, tv, sv, bv = pman.view(), tree.view(), capi.sph_view(Sall), capi.bh_slot_view(Ball)
+        cp, cw = self._params(prm), self._work(work)
+        counts = np.zeros(nranks, dtype=np.int64)
+        nr = C.c_int64()
+        mid = (C.byref(cp),) + (() if Ti is None else (Ti,))
+
+        def call(rec, cap):
+            return fn(self.ctx.h, C.byref(tv), C.byref(pv), C.byref(sv), C.byref(bv), capi.ptr(ids), capi.ptr(queue), len(queue), C.byref(kf), *mid,
+                      capi.ptr(rnd), len(rnd), C.byref(cw), nlocal, capi.ptr(gown), capi.ptr(gidx), nranks, rank, off, rec, cap, capi.ptr(counts), C.byref(nr))
+        # The count pass walks as long as the emit pass, and a sized call runs it twice (without a buffer, then before it emits).  From
+        # the second step on the last step's count, with a margin, is offered as the capacity: one count pass where it suffices.
+        room, rec = self._room.get(dtype, 0), None
+        if room:
+            buf = np.zeros(room, dtype=dtype)
+            rc = call(capi.ptr(buf), room)
+            if rc == 0:
+                rec = buf[:nr.value]
+            elif not (rc == capi.ERR_INVALID and nr.value > room):      # anything but "room for fewer records than found"
+                capi.check(rc)
+        if rec is None:
+            rec = sized_call(call, nr, dtype)
+        self._room[dtype] = len(rec) + len(rec) // 4 + 64
+        return pman, rec, counts
+
+    def accretion_marks(self, Pall, Sall, Ball, nlocal, queue, gown, gidx, nranks, rank, off, kf, prm, Ti_Current, rnd, work):
+        self._walkset = None
+        _, marks, counts = self._walk(capi.hip.shq_bh_accretion_marks, Pall, Sall, Ball, nlocal, queue, gown, gidx, nranks, rank, off, kf, prm, rnd, work,
+                                      capi.BH_MARK_DTYPE, Ti_Current)
+        return marks, counts
+
+    def marks_resolve(self, P, marks, Ti_Current, nsph, nbh, work):
+        pman = records_pman(self.sq, self.L, P)
+        ids = np.ascontiguousarray(P["ID"])
+        marks = np.ascontiguousarray(marks, dtype=capi.BH_MARK_DTYPE)
+        pv, cw = pman.view(), self._work(work)
+        capi.check(capi.hip.shq_bh_marks_resolve(self.ctx.h, C.byref(pv), capi.ptr(ids), capi.ptr(marks), len(marks), Ti_Current, nsph, nbh, C.byref(cw)))
+
+    def feedback_effects(self, Pall, Sall, Ball, nlocal, queue, gown, gidx, nranks, rank, off, kf, prm, rnd, work):
+        pman, effects, counts = self._walk(capi.hip.shq_bh_feedback_effects, Pall, Sall, Ball, nlocal, queue, gown, gidx, nranks, rank, off, kf, prm, rnd, work,
+                                           capi.BH_EFFECT_DTYPE)
+        Pall["Vel"], Pall["Mass"] = pman.Base["Vel"], pman.Base["Mass"]
+        self._walkset = None
+        return effects, counts
+
+    def effects_apply(self, P, SphP, BhP, effects, prm, MaxPart, rnd, eeqos, work):
+        pman = records_pman(self.sq, self.L, P)
+        ids = np.ascontiguousarray(P["ID"])
+        rnd = np.ascontiguousarray(rnd, dtype=np.float64)
+        effects = np.ascontiguousarray(effects, dtype=capi.BH_EFFECT_DTYPE)
+        eeqos = None if eeqos is None else np.ascontiguousarray(eeqos, dtype=np.uint8)
+        pv, sv, bv, cp, cw = pman.view(), capi.sph_view(SphP), capi.bh_slot_view(BhP), self._params(prm), self._work(work)
+        ns, nb = C.c_int64(), C.c_int64()
+        capi.check(capi.hip.shq_bh_effects_apply(self.ctx.h, C.byref(pv), C.byref(sv), C.byref(bv), capi.ptr(ids), capi.ptr(effects), len(effects), C.byref(cp), MaxPart,
+                                                 capi.ptr(rnd), len(rnd), None if eeqos is None else capi.ptr(eeqos), C.byref(cw), C.byref(ns), C.byref(nb)))
+        P["Vel"], P["Flags"] = pman.Base["Vel"], pman.Base["Flags"]
+        return ns.value, nb.value
 
 
 def uvbg_radii(p):
