@@ -1875,6 +1875,52 @@ typedef struct shq_heiii_stats {
 } shq_heiii_stats;
 int shq_heiii_last_stats(shq_context *ctx, shq_heiii_stats *stats);
 
+/* ---- the same operator in phases, for a driver that runs turn_on_quasars over several ranks (shenqi_amd/dist.py:DistHeIII) ----
+ * On several ranks every rank holds some of the gas and some of the groups; the bubble of a lit quasar reaches gas on every rank, and the
+ * loop's control needs the per-bubble counts summed over the ranks.  So the one call above is cut where those sums are taken:
+ *   open   : upload (or reuse), flash, count, build the list of eligible gas (Type 0, not garbage, not ionised) as records (x, y, z, index)
+ *   sweep  : every eligible record gets the seq of the FIRST bubble of the list that holds it; hits are counted per seq
+ *   commit : the records whose first hit has seq < seq_stop are flagged and heated and leave the eligible list
+ *   close  : flag bit and Entropy of everything ionised since open go into the caller's records; the run is freed
+ * sweep and commit alternate any number of times between open and close (a sweep may be repeated; a commit needs a sweep since the last
+ * commit).  The run lives in the context; one run at a time, and not while an SPH walk is open.  A call out of order returns SHQ_ERR_STATE.
+ * Between open and close the context's particles and gas state belong to the run: the eligible records hold particle indices, and the
+ * heating lives in the context's copies.  What is checked: shq_density_open and shq_hydro_open refuse while a run is open, and every
+ * phase returns SHQ_ERR_STATE when the context's particle count is no longer the one at open.  What is not: an upload of another set of
+ * the same length, or a one-shot operator on the context, between open and close; the caller must not make one.  Positions are finite
+ * (shq_particles_upload refuses others), so the extents are those of every eligible record.
+ * Nothing is written to the caller's records before close, so a failed
+ * call leaves them untouched, and after a failed sweep or commit the run can still be closed.  Membership is the particle test of the
+ * legacy walk, !(r2 > R*R) with r2 summed in x, y, z order of NEAREST(c - Pos): that decides alone for R >= 0, +inf and NaN on any number
+ * of ranks.  For R < 0 (-inf included) the walk's node test decides too, and with it each rank's tree: the sweep refuses such a radius
+ * (SHQ_ERR_INVALID); negative radii stay with shq_heiii_reionization and its gas tree. */
+typedef struct shq_heiii_bubble {
+    double c[3];                  /* the quasar's CM */
+    double R;                     /* bubble radius: >= 0, +inf or NaN */
+    int32_t seq, pad_;            /* the bubble's number: strictly increasing along the list, 0 <= seq < nseq */
+} shq_heiii_bubble;
+#define SHQ_HEIII_MAX_SEQ 1024
+/* params as for the one call (the mass window, var_bubble and the offset are not read).  n_flash: particles flash-ionised by this call;
+ * n_ionized_now: Type-0 particles with the flag after the flash, garbage included (gas_ionization_fraction's local count); n_eligible:
+ * length of the eligible list; lo / hi: per axis the smallest and largest coordinate of the eligible records (a two-pass min / max
+ * reduction: the same bits on every run), lo = +inf > hi = -inf when there is none. */
+int shq_heiii_open(shq_context *ctx, const shq_heiii_params *params, const shq_part_view *parts, const shq_sph_view *sph, int64_t *n_flash,
+                   int64_t *n_ionized_now, int64_t *n_eligible, double lo[3], double hi[3]);
+/* counts[nseq] (host, u64): hits per seq, 0 for every seq not in the list.  nbubbles == 0 is valid (all zeros; bubbles may be NULL).
+ * SHQ_ERR_INVALID for nseq outside 1 .. SHQ_HEIII_MAX_SEQ, a seq that does not increase or is not below nseq, or a radius < 0. */
+int shq_heiii_sweep(shq_context *ctx, const shq_heiii_bubble *bubbles, int nbubbles, int nseq, uint64_t *counts);
+/* seq_stop == 0 commits nothing; n_committed may be NULL */
+int shq_heiii_commit(shq_context *ctx, int seq_stop, int64_t *n_committed);
+/* parts / sph: the records given to open (the same numpart; SHQ_ERR_INVALID and the run stays open otherwise).  n_rows (may be NULL):
+ * particles written = flashed + committed.  The run is freed whether or not the download succeeds.  shq_heiii_last_stats then holds the
+ * run's numbers: ms = open, sweeps, commits, and those three plus close; nsweeps, nbubbles, neligible, ntests as above; ndraws = 0. */
+int shq_heiii_close(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, int64_t *n_rows);
+/* Host only: the numbers of the loop that must be glibc's, from the functions shq_heiii_reionization itself uses.  radii_out[i] =
+ * gaussian_rng(mean_bubble, sqrt(var_bubble), minids[i]) (:249-255); *non_overlapping_bubble_number as :514-518 forms it from
+ * n_gas_tot, mean_bubble, OmegaBaryon, HubbleParam and atime.  minids / radii_out may be NULL with n == 0. */
+int shq_heiii_host_numbers(const shq_heiii_params *params, const uint64_t *minids, int64_t n, const double *rnd_table, int64_t rnd_size,
+                           double *radii_out, int64_t *non_overlapping_bubble_number);
+
 /* ---- lensing potential planes (write_plane's compute, libgadget/plane.cpp:511-600; cutPlaneGaussianGrid and
  * calculate_lensing_potential, lenstools.cpp:168-319; the PM neutrino correction, plane.cpp:355-475) ----
  * For ONE rank: the caller sums the planes over ranks (MPI_Reduce) as write_plane does. */

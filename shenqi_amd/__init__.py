@@ -409,6 +409,19 @@ def heiii_reionization(ctx, pman, SphP, params, rnd_table, gas_tree=None, log_ca
     return res, log[:nlog.value].copy()
 
 
+def heiii_host_numbers(params, minids, rnd_table):
+    """The numbers of the quasar loop that must be glibc's (host only): gaussian_rng's bubble radius per MinID (cooling_qso_lightup.cpp:
+    249-255) and non_overlapping_bubble_number (:514-518), from the functions shq_heiii_reionization itself uses.  The phases of the
+    same operator (shq_heiii_open / _sweep / _commit / _close) are driven by dist.DistHeIII with dist.GpuHeiiiOps."""
+    rnd = np.ascontiguousarray(rnd_table, dtype=np.float64)
+    minids = np.ascontiguousarray(minids, dtype=np.uint64)
+    radii = np.zeros(len(minids))
+    nn = C.c_int64()
+    capi.check(capi.hip.shq_heiii_host_numbers(C.byref(params), capi.ptr(minids), len(minids), capi.ptr(rnd), len(rnd), capi.ptr(radii), C.byref(nn)),
+               "heiii_host_numbers")
+    return radii, nn.value
+
+
 def lens_count_active(ctx, pman, exclude_type2=False):
     """plane_count_active_particles' local count (plane.cpp:72-83) on the device: not Swallowed, not Type 2 under exclude_type2"""
     pv = pman.view()

@@ -788,6 +788,18 @@ hip.shq_heiii_reionization.restype = C.c_int
 hip.shq_heiii_last_stats.argtypes = [_vp, C.POINTER(HeiiiStats)]
 hip.shq_heiii_last_stats.restype = C.c_int
 
+# the operator in phases (open / sweep / commit / close), for DistHeIII
+HEIII_BUBBLE_DTYPE = np.dtype([("c", "<f8", 3), ("R", "<f8"), ("seq", "<i4"), ("pad_", "<i4")])   # shq_heiii_bubble
+HEIII_MAX_SEQ = 1024
+hip.shq_heiii_open.argtypes = [_vp, C.POINTER(HeiiiParams), C.POINTER(PartView), C.POINTER(SphView), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                               C.POINTER(C.c_int64), _vp, _vp]
+hip.shq_heiii_sweep.argtypes = [_vp, _vp, C.c_int, C.c_int, _vp]
+hip.shq_heiii_commit.argtypes = [_vp, C.c_int, C.POINTER(C.c_int64)]
+hip.shq_heiii_close.argtypes = [_vp, C.POINTER(PartView), C.POINTER(SphView), C.POINTER(C.c_int64)]
+hip.shq_heiii_host_numbers.argtypes = [C.POINTER(HeiiiParams), _vp, C.c_int64, _vp, C.c_int64, _vp, C.POINTER(C.c_int64)]
+for _f in ("open", "sweep", "commit", "close", "host_numbers"):
+    getattr(hip, "shq_heiii_" + _f).restype = C.c_int
+
 
 class LensParams(C.Structure):
     """shq_lens_params: PlaneParams (plane.cpp:25-33) for one call, the box and the particle offset"""

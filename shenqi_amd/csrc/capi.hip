@@ -234,6 +234,7 @@ extern "C" void shq_shutdown(shq_context *ctx)
         (void) hipStreamSynchronize(ctx->stream_pair);
     (void) hipStreamSynchronize(ctx->stream);
     shq_pm_destroy_plans(ctx);
+    shq_heiii_run_free(ctx);
     ctx->posm.release(); ctx->oldacc.release(); ctx->treeacc.release(); ctx->gravpm.release();
     ctx->pmpot.release(); ctx->acc.release(); ctx->pot.release(); ctx->nint.release(); ctx->walk_tasks.release();
     ctx->sp_items.release(); ctx->sp_stack.release(); ctx->sp_count.release(); ctx->sp_flags.release(); ctx->sp_host.release(); ctx->node_lean_bad.release();

@@ -13,6 +13,7 @@
 #include "cooling_math.hpp"
 
 void shq_set_error(const char *fmt, ...);
+void shq_heiii_run_free(shq_context *ctx); /* heiii.hip: gives back an open HeIII run, if any */
 
 #define SHQ_HIP(call)                                                                          \
     do {                                                                                       \
@@ -537,8 +538,24 @@ struct shq_context {
     DevBuf<double> uvbg_tw, uvbg_tabs, uvbg_part;
     DevBuf<int> uvbg_flag;
     int uvbg_tw_n = 0, uvbg_tabs_n = 0, uvbg_tabs_nr = 0;
-    /* ---- helium reionisation (heiii.hip): a call allocates and frees its own device buffers; only its statistics stay behind */
+    /* ---- helium reionisation (heiii.hip): a run's device buffers live from open to close (within one call of shq_heiii_reionization);
+     * only its statistics stay behind */
     shq_heiii_stats heiii_stats = {};
+    struct HeiiiRun {              /* shq_heiii_open ... shq_heiii_close */
+        int phase = 0;             /* 0 none, 1 open (eligible list built, nothing swept since the last commit), 2 swept */
+        struct CallScope *sc = nullptr; /* owns every buffer and event of the run */
+        int64_t n = 0;             /* numpart at open */
+        double box = 0, a3inv = 0, du = 0;
+        int64_t m = 0, nrows = 0, n_flash = 0; /* eligible records left; rows (index, new Entropy) so far; of those, flashed */
+        int cur = 0;               /* which of E[2] holds the eligible records */
+        double4 *E[2] = {nullptr, nullptr}, *S = nullptr;
+        int32_t *hit = nullptr;
+        void *bub = nullptr;
+        unsigned long long *counts = nullptr, *cnt = nullptr;
+        double2 *rows = nullptr;
+        double *ext = nullptr;     /* per-block partial extents, then the six results */
+        shq_heiii_stats st = {};
+    } heiiirun;
     /* ---- lensing potential planes (lens.hip): a call allocates and frees its own device buffers; only its times stay behind */
     double lens_ms[4] = {0, 0, 0, 0};     /* shq_lens_phase_ms */
     /* ---- Zel'dovich displacements (zeldovich.hip): a call allocates and frees its work buffers; the Gaussian field stays resident */

@@ -194,6 +194,7 @@ extern "C" int shq_density_open(shq_context *ctx, const shq_tree_view *tree, con
 {
     SHQ_CHECK(ctx && tree && parts && sph && params, SHQ_ERR_INVALID, "null argument");
     SHQ_CHECK(ctx->sphrun.phase == 0, SHQ_ERR_STATE, "density_open: another SPH walk is open");
+    SHQ_CHECK(ctx->heiiirun.sc == nullptr, SHQ_ERR_STATE, "density_open: a HeIII run is open (its heating lives in the context's copies)");
     SHQ_HIP(hipSetDevice(ctx->device));
     const int64_t n = parts->numpart;
     if(active)
@@ -357,6 +358,7 @@ extern "C" int shq_hydro_open(shq_context *ctx, const shq_tree_view *tree, const
 {
     SHQ_CHECK(ctx && tree && parts && sph && params, SHQ_ERR_INVALID, "null argument");
     SHQ_CHECK(ctx->sphrun.phase == 0, SHQ_ERR_STATE, "hydro_open: another SPH walk is open");
+    SHQ_CHECK(ctx->heiiirun.sc == nullptr, SHQ_ERR_STATE, "hydro_open: a HeIII run is open (its heating lives in the context's copies)");
     SHQ_HIP(hipSetDevice(ctx->device));
     const int64_t n = parts->numpart;
     if(active)

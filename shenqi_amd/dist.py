@@ -2163,6 +2163,258 @@ class GpuUvbgOps:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# Helium reionisation by quasar bubbles across ranks: turn_on_quasars (libgadget/cooling_qso_lightup.cpp:489-596) as its loop runs
+# on several tasks.  Every rank holds some of the gas (any particle may sit on any rank: no decomposition, no ghosts) and hosts some
+# of the groups.  The reference draws one global position per iteration on every task with the same random number; each task keeps
+# its own ncand_before, and choose_QSO_halo (:314-328) decrements it BEFORE the range test.  So when the drawn position is the last
+# candidate of all earlier tasks together, a task with a non-empty list returns local index 0 as well: it does not walk (only
+# qso_ind > 0 walks) but erases its candidate 0 (:588-589), its list is from then on shorter than the global count assumes, and
+# later draws can fall on a position no task hosts.  The outcome therefore depends on how the candidates are split over the tasks;
+# what is reproduced here is the reference's loop for the split that is given, not a rank-independent result.
+#
+# Which quasars are drawn depends only on the random table and the candidate counts, so every rank replays every rank's counters
+# (HeiiiDraws) without communication.  The lit bubbles of a batch of draws are swept on every rank against its own eligible gas (the
+# walk of the hosting task reaches gas on every task; for R >= 0, +inf or NaN the particle test !(r2 > R*R) alone decides membership),
+# the per-draw counts are all-reduced as one vector, and every rank replays the loop's control (:551-590) on the global counts.
+#
+# Culling.  A rank may leave a bubble (c, R) out of its sweep only if every eligible particle is proven outside by one axis alone.
+# The sweep forms dx = NEAREST(fl(c - x)) and r2 = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)); rounding is monotone and the added
+# terms are >= 0, so r2 >= fl(dx dx).  For the rank's eligible coordinates x in [lo, hi] (extents taken at open; the list only
+# shrinks afterwards) t = fl(c - x) is non-increasing in x, so t lies in [a, b] with a = fl(c - hi), b = fl(c - lo).  f(t) =
+# |NEAREST(t)| is, in the sweep's own floating-point operations, non-decreasing on -L <= t < -L/2 (fl(t + L) >= 0), non-increasing
+# on [-L/2, 0], non-decreasing on [0, L/2] and non-increasing on L/2 < t <= L (|fl(t - L)| = fl(L - t)): on an interval inside
+# [-L, L] that does not contain 0 its minimum is taken at an end, d = min(f(a), f(b)), computed with the same operations.  Then
+# |dx| >= d >= 0 gives fl(dx dx) >= fl(d d), and fl(d d) > fl(R R) proves r2 > R*R for every eligible particle.  NEAREST wraps
+# once only, so beyond |t| = L the outer pieces turn (|fl(t - L)| rises again) and the minimum can lie inside [a, b]: the proof
+# needs |a| <= L and |b| <= L.  The reference keeps Pos in (0, L] and CM in [0, L), so that holds in a run, but it is checked, not
+# assumed.  Kept without a proof: an interval that contains t = 0, an interval that leaves [-L, L], an interval at least L/2 wide,
+# a non-finite centre or extent, and every bubble whose R is NaN or infinite.
+def heiii_nearest(x, L):
+    """NEAREST (partmanager.h:99) on Python floats: the operations of the sweep kernel"""
+    return x - L if x > 0.5 * L else (x + L if x < -0.5 * L else x)
+
+
+def heiii_bubble_reaches(c, R, lo, hi, L):
+    """False only with a proof (above) that no coordinate box [lo, hi] particle passes the sweep's test for bubble (c, R)"""
+    if not math.isfinite(R):
+        return True
+    R2 = R * R
+    for d in range(3):
+        if not (hi[d] - lo[d] < 0.5 * L):       # also extents that are not numbers
+            continue
+        a, b = c[d] - hi[d], c[d] - lo[d]
+        if not (a > 0 or b < 0):      # 0 inside [a, b], or a centre that is not a number
+            continue
+        if not (abs(a) <= L and abs(b) <= L):   # NEAREST wraps once: beyond |t| = L the pieces of f are no longer monotone
+            continue
+        g = min(abs(heiii_nearest(a, L)), abs(heiii_nearest(b, L)))
+        if g * g > R2:
+            return False
+    return True
+
+
+class HeiiiDraws:
+    """choose_QSO_halo's counters of every rank, replayed as written.  ncands: candidates per rank, in rank order; the candidates
+    are numbered globally in that order.  batch(nd) makes up to nd draws and returns per draw the global number of the lit
+    candidate, or -1 when no rank walked; `ended` is set by the draw that leaves ncand_tot <= 0, which lights nothing.  events counts
+    two_host (two ranks with new_qso >= 0: the spurious erase), unhosted (no rank has the position), index0 (position 0 of some
+    rank and nobody walks)."""
+
+    def __init__(self, ncands, TotNgroups, rnd):
+        off = np.concatenate([[0], np.cumsum(ncands)]).astype(np.int64)
+        self.cand = [list(range(int(off[r]), int(off[r + 1]))) for r in range(len(ncands))]
+        self.before = [int(x) for x in off[:-1]]          # count_QSO_halos (:283-304)
+        self.ncand_tot = int(off[-1])
+        self.seed, self.rnd = int(TotNgroups), rnd
+        self.ndrawn, self.ended = 0, False
+        self.events = dict(two_host=0, unhosted=0, index0=0)
+
+    def batch(self, nd):
+        out = []
+        for _ in range(nd):
+            drand = float(self.rnd[(self.seed + self.ndrawn) % len(self.rnd)])
+            qso = int(drand * self.ncand_tot)
+            self.ncand_tot -= 1
+            new = []
+            for r, cand in enumerate(self.cand):
+                if qso < self.before[r]:
+                    self.before[r] -= 1
+                new.append(-1 if (qso < self.before[r] or qso >= self.before[r] + len(cand)) else qso - self.before[r])
+            if self.ncand_tot <= 0:     # "not enough quasars": the loop ends before this one
+                self.ended = True
+                break
+            walkers = [r for r, q in enumerate(new) if q > 0]
+            assert len(walkers) <= 1, "two ranks walk in one iteration"
+            out.append(self.cand[walkers[0]][new[walkers[0]]] if walkers else -1)
+            hosts = sum(q >= 0 for q in new)
+            self.events["two_host"] += hosts >= 2
+            self.events["unhosted"] += hosts == 0
+            self.events["index0"] += not walkers and hosts > 0
+            for r, q in enumerate(new):
+                if q >= 0:
+                    del self.cand[r][q]
+            self.ndrawn += 1
+        return out
+
+
+class DistHeIII:
+    """run(P, SphP, groups, TotNgroups, params, rnd) -> (log, result), the same on every rank.
+    P: numpy PARTICLE_DTYPE array of everything this rank owns (gas PI -> SphP), flag bit and Entropy of the ionised gas are written
+    at the end; groups: the catalogue this rank hosts, in the order given (DistFOF.fof's list of dicts, or a FOF_GROUP_DTYPE array);
+    TotNgroups: the global group count (the seed of the draws); params: capi.HeiiiParams (n_gas_tot is replaced by the all-reduced
+    len(SphP)); rnd: RandTable::Table.  log: the FdHelium lines as (host rank, local group index, pos, ionfrac, n_ionized), with
+    (-1, -1, zeros) when nothing was walked; result: shq_heiii_result's fields with global values.
+    ops.open(P, SphP, params) -> (n_flash, n_ionized_now, n_eligible, lo[3], hi[3]); ops.sweep(bubbles, nseq) -> counts[nseq];
+    ops.commit(seq_stop) -> particles committed; ops.close(P, SphP) -> rows written (GpuHeiiiOps below; the CPU tests use the
+    restatement); ops.cull: leave out the bubbles that provably cannot reach this rank's eligible gas.
+    The whole run is refused (ValueError on every rank) when ANY candidate of the gathered list has a radius below 0, -inf included,
+    even one that would never be drawn: for such a radius the walk's node test decides too (at -inf cull_node rejects the root and
+    the walk takes nothing, while the particle test alone would take everything), so membership would depend on each rank's tree.
+    The radii are all known before the first draw, and refusing up front keeps every rank on the same path.  The run is closed on
+    every way out, and after a refusal only the flash, if the target called for one, has been applied.
+    Counters of the last run: nsweeps (batches), kept (bubbles this rank swept, per batch), ntests (eligible x kept, summed),
+    events (HeiiiDraws').  Nothing here has run on more than one GPU."""
+
+    FIRST_BATCH, MAX_BATCH = 32, capi.HEIII_MAX_SEQ      # the one call's schedule: 32, 64, ... 1024 draws per sweep
+
+    def __init__(self, comm, ops):
+        self.comm, self.ops = comm, ops
+        self.nsweeps = self.ntests = self.nrows = 0
+        self.kept, self.events = [], {}
+
+    def _candidates(self, groups, p):
+        """this rank's rows of build_qso_candidate_list (:260-276): (rank, local index, MinID, CM) as six 64-bit words each"""
+        if isinstance(groups, np.ndarray):
+            mass, minid, cm = groups["Mass"], groups["MinID"], groups["CM"]
+        else:
+            mass = np.array([g["Mass"] for g in groups], dtype=np.float64)
+            minid = np.array([g["MinID"] for g in groups], dtype=np.uint64)
+            cm = np.array([g["CM"] for g in groups], dtype=np.float64).reshape(len(groups), 3)
+        sel = np.flatnonzero(~(mass < p.qso_candidate_min_mass) & ~(mass > p.qso_candidate_max_mass))
+        rows = np.zeros((len(sel), 6), dtype=np.uint64)
+        rows[:, 0], rows[:, 1], rows[:, 2] = self.comm.rank, sel, np.asarray(minid, dtype=np.uint64)[sel]
+        rows[:, 3:] = np.ascontiguousarray(np.asarray(cm, dtype=np.float64)[sel]).view(np.uint64)
+        return rows
+
+    def run(self, P, SphP, groups, TotNgroups, params, rnd):
+        rnd = np.ascontiguousarray(rnd, dtype=np.float64)
+        p = capi.HeiiiParams.from_buffer_copy(params)
+        p.n_gas_tot = int(self.comm.allreduce_sum_vec(np.array([len(SphP)], dtype=np.int64))[0])       # :492
+        self.nsweeps = self.ntests = self.nrows = 0
+        self.kept, self.events = [], {}
+        opened = self.ops.open(P, SphP, p)
+        try:
+            return self._loop(p, groups, TotNgroups, rnd, *opened)
+        finally:
+            self.nrows = self.ops.close(P, SphP)
+
+    def _loop(self, p, groups, TotNgroups, rnd, n_flash, n_ionized_now, m, lo, hi):
+        comm, ops, L = self.comm, self.ops, p.BoxSize
+        tot = comm.allreduce_sum_vec(np.array([n_ionized_now, n_flash], dtype=np.int64))                # :344-345, :510
+        ngas = float(p.n_gas_tot)
+        cur = int(tot[0]) / ngas
+        res = dict(init_ionfrac=cur, final_ionfrac=cur, n_candidates=0, n_iterations=0, n_flash=int(tot[1]), n_ionized=0)
+        log = []
+        if not (cur < p.desired_ion_frac):
+            return log, res
+        cand = comm.allgather_u64(self._candidates(groups, p).reshape(-1)).reshape(-1, 6)
+        res["n_candidates"] = len(cand)
+        if len(cand) == 0:                                                                                 # :534-536
+            return log, res
+        crank, cindex = cand[:, 0].astype(np.int64), cand[:, 1].astype(np.int64)
+        minid, cm = np.ascontiguousarray(cand[:, 2]), np.ascontiguousarray(cand[:, 3:]).view(np.float64)
+        from . import heiii_host_numbers
+        radii, threshold = heiii_host_numbers(p, minid, rnd)
+        if np.any(radii < 0):
+            raise ValueError("DistHeIII: candidate %d has the negative radius %g: membership would depend on each rank's tree"
+                             % (int(np.flatnonzero(radii < 0)[0]), float(radii[radii < 0][0])))
+        draws = HeiiiDraws(np.bincount(crank, minlength=comm.size), TotNgroups, rnd)
+        self.events = draws.events
+        cull = getattr(ops, "cull", True)
+        batch, iteration, stopped = self.FIRST_BATCH, 0, False
+        while not stopped and not draws.ended:
+            drawn = draws.batch(batch)
+            lit = [(k, g) for k, g in enumerate(drawn) if g >= 0]
+            kept = [(k, g) for k, g in lit if m > 0 and (not cull or heiii_bubble_reaches(cm[g], float(radii[g]), lo, hi, L))]
+            counts = np.zeros(len(drawn))
+            if kept:
+                bub = np.zeros(len(kept), dtype=capi.HEIII_BUBBLE_DTYPE)
+                bub["seq"], gk = [k for k, _ in kept], [g for _, g in kept]
+                bub["c"], bub["R"] = cm[gk], radii[gk]
+                counts = ops.sweep(bub, len(drawn)).astype(np.float64)
+            if lit:
+                counts = comm.allreduce_sum_vec(counts)          # exact: counts are integers far below 2^53 (:554)
+            self.nsweeps += 1
+            self.kept.append(len(kept))
+            self.ntests += m * len(kept)
+            seq_stop = 0
+            for k, g in enumerate(drawn):                         # the loop's control (:551-590), the same on every rank
+                n_ionized = int(counts[k]) if g >= 0 else 0
+                seq_stop = k + 1
+                cur += n_ionized / ngas
+                res["n_ionized"] += n_ionized
+                if g >= 0:
+                    pos = []
+                    for d in range(3):                           # the MPI_MAX of :574 returns the host's wrapped CM: in (0, BoxSize]
+                        x = float(cm[g, d]) - p.CurrentParticleOffset[d]
+                        if math.isfinite(x):
+                            while x > L:
+                                x -= L
+                            while x <= 0:
+                                x += L
+                        pos.append(x)
+                    log.append((int(crank[g]), int(cindex[g]), tuple(pos), cur, n_ionized))
+                else:
+                    log.append((-1, -1, (0.0, 0.0, 0.0), cur, n_ionized))
+                insufficient = n_ionized < 0.01 * threshold and iteration > 10
+                iteration += 1
+                if insufficient or not (cur < p.desired_ion_frac):
+                    stopped = True
+                    break
+            if kept:
+                m -= ops.commit(seq_stop)
+            batch = min(2 * batch, self.MAX_BATCH)
+        res.update(final_ionfrac=cur, n_iterations=iteration)
+        return log, res
+
+
+class GpuHeiiiOps:
+    """DistHeIII's four steps on the device library (shq_heiii_open / _sweep / _commit / _close)"""
+
+    def __init__(self, ctx, BoxSize, cull=True):
+        import shenqi_amd as sq
+        self.sq, self.ctx, self.L, self.cull = sq, ctx, BoxSize, cull
+        self._pman = None
+
+    def open(self, P, SphP, p):
+        self._pman = records_pman(self.sq, self.L, P)
+        pv, sv = self._pman.view(), capi.sph_view(SphP)
+        nf, ni, ne = C.c_int64(), C.c_int64(), C.c_int64()
+        lo, hi = np.zeros(3), np.zeros(3)
+        capi.check(capi.hip.shq_heiii_open(self.ctx.h, C.byref(p), C.byref(pv), C.byref(sv), C.byref(nf), C.byref(ni), C.byref(ne), capi.ptr(lo), capi.ptr(hi)))
+        return nf.value, ni.value, ne.value, lo, hi
+
+    def sweep(self, bubbles, nseq):
+        bubbles = np.ascontiguousarray(bubbles, dtype=capi.HEIII_BUBBLE_DTYPE)
+        counts = np.zeros(nseq, dtype=np.uint64)
+        capi.check(capi.hip.shq_heiii_sweep(self.ctx.h, capi.ptr(bubbles), len(bubbles), nseq, capi.ptr(counts)))
+        return counts
+
+    def commit(self, seq_stop):
+        n = C.c_int64()
+        capi.check(capi.hip.shq_heiii_commit(self.ctx.h, seq_stop, C.byref(n)))
+        return n.value
+
+    def close(self, P, SphP):
+        pman, self._pman = self._pman, None
+        pv, sv = pman.view(), capi.sph_view(SphP)
+        n = C.c_int64()
+        capi.check(capi.hip.shq_heiii_close(self.ctx.h, C.byref(pv), C.byref(sv), C.byref(n)))
+        P["Flags"] = pman.Base["Flags"]
+        return n.value
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # The domain decomposition itself: domain_decompose_full (libgadget/domain.cpp:174-277).  The particle loops run in `ops` (GpuDomainOps:
 # shq_domain_* on the device; the tests' CPU stand-in: the restated procedures), the small serial stages are host functions, and this
 # class holds what the reference does between them: the policy table, the retry with more top nodes, the global sample sort, the
