@@ -2025,6 +2025,51 @@ int shq_zeldovich_phase_ms(shq_context *ctx, double ms[4]);
  * SAMPLEs (pmesh.h:55-62) of the same start as (phase, ampl before the log), the ampl == 0 redraw included.  m even, n <= 65536. */
 int shq_zeldovich_column_draws(shq_context *ctx, int n, const uint32_t *seeds, const uint32_t *states, int m, uint32_t *raw, double *pairs);
 
+/* ---- Zel'dovich displacements on several ranks (shenqi_amd/dist.py, DistZeldovich): the phases of shq_zeldovich_displacements as
+ * entry points of their own, with the caller's exchanges between them.  The reference gives every task its sub-block of the lattice
+ * (zeldovich.cpp:46-65), fills only its own Fourier region (pmesh.h:93-172) and all-reduces the two maxima (zeldovich.cpp:150-264).
+ *
+ * Every pointer named d_ is DEVICE memory of the caller; nothing is uploaded or downloaded but the tables and the two maxima.  The
+ * Gaussian field lives on the rank's y-slab, the mesh rows y0 <= y < y0 + nyl: d_spec = [Nmesh][nyl][zpc] complex, x slowest, zpc =
+ * shq_zeldovich_slab_pitch(Nmesh) / 2 - or, for a mesh size without a bespoke transform (pitch 0), dense with Nmesh / 2 + 1.  One mt19937
+ * per mesh column means a rank makes exactly its own columns: the slab's modes are the SAME BITS as the matching rows of
+ * shq_zeldovich_download_field, whatever the slab.  A field's real mesh lives on the rank's x planes, [nalloc][Nmesh][zp] doubles.
+ * None of these calls reads or writes the PM's state (mesh, deposit scale, type mask, twiddles, pending spectrum, prestarted PM) or
+ * the one-rank resident field: twiddles, tables and flags are the family's own.  They run on the context's stream; fill, tables,
+ * gather and finalize return synchronised, xtransfer, transfer and fft_yz only launch.
+ *
+ * The order of a call, per rank:
+ *   shq_zeldovich_slab_fill       once per (Nmesh, Seed, flags): d_spec is only read afterwards, so it serves every field and species;
+ *                                 pad columns z' > Nmesh / 2 are written as 0; chunked by shq_zeldovich_set_fill_chunk
+ *   shq_zeldovich_slab_tables     dens[k2] made on the host as the one-rank call makes it, delta[k2], growth[k2] (NULL: no velocity
+ *                                 fields) uploaded; they stay on the device until the next call.  SHQ_ERR_INVALID for a bad mesh size,
+ *                                 a BoxSize that is not finite and > 0, or a non-finite entry
+ *   per field 0 .. 6 (Density, DispX/Y/Z, VelX/Y/Z):
+ *     shq_zeldovich_slab_xtransfer  the transfer function per mode (the one-rank kernel's arithmetic, signed kx, ky = y0 + row, kz;
+ *                                 k2 = 0 left as it is) fused into the X inverse, stored OUT OF PLACE into d_out of d_spec's shape:
+ *                                 the buffer of the return all-to-all.  SHQ_ERR_STATE without tables of this Nmesh and BoxSize
+ *     (shq_zeldovich_slab_transfer  the factor alone on the dense slab, between the caller's own X transforms, for a mesh size without
+ *                                 a bespoke transform; d_out may be d_spec)
+ *     shq_zeldovich_slab_fft_yz   the Y/Z inverse of the x planes, the Y pass reading the all-to-all buffer d_packed =
+ *                                 [nranks][nplanes][Nmesh / nranks][zpc] (NULL: the planes hold the spectrum already)
+ *     shq_zeldovich_slab_gather   pm_iterate_one's gather at d_pos = double[n][3] into d_out[n] from the window [nalloc][Nmesh][zp]
+ *                                 (zp: the slab pitch, or Nmesh + 2): the own planes from plane0 on and behind them the right-hand
+ *                                 neighbour's first plane (nalloc = nplanes + 1; one rank: plane0 = 0, nalloc = nplanes = Nmesh).  A
+ *                                 position whose Pos / CellSize rounds up to Nmesh is cell 0 with residual 0: rank 0's plane 0.  A
+ *                                 particle with a corner outside the window is SHQ_ERR_INVALID and is not written
+ *   shq_zeldovich_slab_finalize   the particle loop on d_fld = double[7][n] (rows 4 .. 6 read only with ScaleDepVelocity) into
+ *                                 d_pos_out, d_vel, d_disp = double[n][3]; mx = this rank's maxdisp and max |Vel|^2 */
+int shq_zeldovich_slab_pitch(int Nmesh);
+int shq_zeldovich_slab_fill(shq_context *ctx, int Nmesh, int Seed, int UnitaryAmplitude, int InvertPhase, int y0, int nyl, void *d_spec);
+int shq_zeldovich_slab_tables(shq_context *ctx, int Nmesh, double BoxSize, const double *delta, const double *growth);
+int shq_zeldovich_slab_xtransfer(shq_context *ctx, int Nmesh, double BoxSize, const void *d_spec, void *d_out, int y0, int nyl, int field);
+int shq_zeldovich_slab_transfer(shq_context *ctx, int Nmesh, double BoxSize, const void *d_spec, void *d_out, int y0, int nyl, int field);
+int shq_zeldovich_slab_fft_yz(shq_context *ctx, int Nmesh, void *d_planes, int nplanes, const void *d_packed, int nranks);
+int shq_zeldovich_slab_gather(shq_context *ctx, int Nmesh, double BoxSize, const void *d_pos, int64_t n, const void *d_mesh, int plane0,
+                              int nplanes, int nalloc, void *d_out);
+int shq_zeldovich_slab_finalize(shq_context *ctx, int64_t n, const void *d_pos, const void *d_fld, int ScaleDepVelocity, double vel_prefac,
+                                double BoxSize, void *d_pos_out, void *d_vel, void *d_disp, double mx[2]);
+
 /* ---- Glass making (glass_evolve, libgenic/glass.cpp:76-360, with petapm_force's deposit and readout, petapm.cpp:1132-1183, and
  * powerspectrum_add_mode, gravpm.cpp:323-376) ----  one rank.  The reversed-gravity PM relaxation loop, resident on the device from
  * the first deposit to the last kick.  Storage types and rounding points are ic_part_data's (allvars.h:8-16): double Pos, float Vel,

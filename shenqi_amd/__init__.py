@@ -761,12 +761,21 @@ def sfr_last_kernel(ctx):
 
 
 class IDGenerator:
-    """idgen_init on one rank (libgenic/zeldovich.cpp:46-65): the whole Ngrid^3 lattice"""
+    """idgen_init (libgenic/zeldovich.cpp:46-65) for task ThisTask2d of an NTask2d task grid: the sub-block x in [offset[0],
+    offset[0] + size[0]), y likewise, every z, with offset[k] = ThisTask2d[k] * Ngrid / NTask2d[k] and size[k] reaching to the next
+    task's offset.  The defaults are one rank: the whole Ngrid^3 lattice."""
 
-    def __init__(self, Ngrid, BoxSize):
+    def __init__(self, Ngrid, BoxSize, ThisTask2d=(0, 0), NTask2d=(1, 1)):
         self.Ngrid, self.BoxSize = int(Ngrid), float(BoxSize)
-        self.offset, self.size = (0, 0, 0), (self.Ngrid,) * 3
-        self.NumPart = self.Ngrid**3
+        offset, size = [0, 0, 0], [self.Ngrid] * 3
+        for k in range(2):
+            t, nt = int(ThisTask2d[k]), int(NTask2d[k])
+            if nt < 1 or not 0 <= t < nt:
+                raise ValueError("IDGenerator: task %d of %d along axis %d" % (t, nt, k))
+            offset[k] = t * self.Ngrid // nt
+            size[k] = (t + 1) * self.Ngrid // nt - offset[k]
+        self.offset, self.size = tuple(offset), tuple(size)
+        self.NumPart = size[0] * size[1] * size[2]
 
 
 def idgen_create_id_from_index(idgen, index):

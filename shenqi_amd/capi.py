@@ -854,6 +854,16 @@ hip.shq_zeldovich_phase_ms.argtypes = [_vp, C.POINTER(C.c_double * 4)]
 hip.shq_zeldovich_phase_ms.restype = C.c_int
 hip.shq_zeldovich_column_draws.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, _vp, _vp]
 hip.shq_zeldovich_column_draws.restype = C.c_int
+hip.shq_zeldovich_slab_pitch.argtypes = [C.c_int]
+hip.shq_zeldovich_slab_fill.argtypes = [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _vp]
+hip.shq_zeldovich_slab_tables.argtypes = [_vp, C.c_int, C.c_double, _vp, _vp]
+hip.shq_zeldovich_slab_xtransfer.argtypes = [_vp, C.c_int, C.c_double, _vp, _vp, C.c_int, C.c_int, C.c_int]
+hip.shq_zeldovich_slab_transfer.argtypes = [_vp, C.c_int, C.c_double, _vp, _vp, C.c_int, C.c_int, C.c_int]
+hip.shq_zeldovich_slab_fft_yz.argtypes = [_vp, C.c_int, _vp, C.c_int, _vp, C.c_int]
+hip.shq_zeldovich_slab_gather.argtypes = [_vp, C.c_int, C.c_double, _vp, C.c_int64, _vp, C.c_int, C.c_int, C.c_int, _vp]
+hip.shq_zeldovich_slab_finalize.argtypes = [_vp, C.c_int64, _vp, _vp, C.c_int, C.c_double, C.c_double, _vp, _vp, _vp, C.POINTER(C.c_double * 2)]
+for _f in ("pitch", "fill", "tables", "xtransfer", "transfer", "fft_yz", "gather", "finalize"):
+    getattr(hip, "shq_zeldovich_slab_" + _f).restype = C.c_int
 
 
 class GlassParams(C.Structure):

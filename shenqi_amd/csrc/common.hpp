@@ -213,7 +213,7 @@ struct shq_fft_plan {
         unsigned res_z = 0, res_s = 0, res_x = 0, res_x3 = 0, res_x4 = 0, res_x5 = 0;
     } t; /* transposing pipeline */
     struct {
-        unsigned res_zf = 0, res_zi = 0, res_s = 0, res_x3 = 0, res_x4 = 0, res_x5 = 0;
+        unsigned res_zf = 0, res_zi = 0, res_s = 0, res_x3 = 0, res_x4 = 0, res_x5 = 0, res_x6 = 0;
     } n; /* in-place pipeline */
 };
 
@@ -564,6 +564,14 @@ struct shq_context {
     int zel_n = 0, zel_seed = 0, zel_unitary = 0, zel_invert = 0; /* its key */
     int64_t zel_chunk = 0;                /* shq_zeldovich_set_fill_chunk: columns per fill launch (0: the default) */
     double zel_ms[4] = {0, 0, 0, 0};      /* shq_zeldovich_phase_ms */
+    /* the slab phases (shq_zeldovich_slab_*): twiddles of their own (the PM's stay as they are), the three tables by k2 -
+     * [3][3 (N/2)^2 + 1]: dens, delta, growth (shq_zeldovich_slab_tables) - the outside-the-window flag and the two maxima */
+    DevBuf<double> zels_tw, zels_tabs;
+    DevBuf<int> zels_flag;
+    DevBuf<unsigned long long> zels_mx;
+    int zels_tw_n = 0, zels_tabs_n = 0;
+    bool zels_growth = false;             /* the tables hold a growth table */
+    double zels_box = 0;                  /* the BoxSize the density table was made for */
     /* ---- glass making (glass.hip): a call allocates and frees its own device buffers; only its times stay behind */
     double glass_ms[4] = {0, 0, 0, 0};    /* shq_glass_phase_ms */
     /* ---- thermal velocities (thermal.hip): a call allocates and frees its own device buffers; only its times stay behind */
@@ -675,6 +683,8 @@ enum shq_fft_stage {
     SHQ_FFT_X_FINISH,          /* ... then the mode factor, potential_transfer and the X inverse; needs modefac */
     SHQ_FFT_X_FILTER,          /* from X_FORWARD_SUMS' kept spectrum the excursion-set filter: every mode times (v / ncell)
                                   modefac[k2 & fac_mask], then the X inverse into the y-slab `out`; d_mesh is only read */
+    SHQ_FFT_X_ZEL,             /* from a kept Gaussian field the Zel'dovich transfer of one field (zel_transfer_mode with
+                                  modefac[k2], zel_axis, zel_c0), then the X inverse into the y-slab `out`; d_mesh is only read */
 };
 /* what the transposing pipeline runs between d_mesh and a scratch mesh of the same size */
 enum shq_fft_part {
@@ -696,7 +706,31 @@ struct shq_fft_opts {
     const double *tw = nullptr;       /* the caller's own twiddles of N (shq_fft3d_fill_twiddles): the context's are left alone */
     double *out = nullptr;            /* T_FILTER: where the Z inverse writes; X_FILTER: the y-slab the X inverse writes */
     int ncell = 1;                    /* T_FILTER, X_FILTER: the int N^3 every mode is divided by */
+    int zel_axis = -1;                /* X_ZEL: -1 the density transfer, 0 / 1 / 2 the gradient along x / y / z */
+    double zel_c0 = 0;                /* X_ZEL: 1 / (2 pi) / sqrt(BoxSize) */
 };
+
+/* density_transfer / disp_transfer (libgenic/zeldovich.cpp:277-314) of one mode, for the one-rank kernel (zeldovich.hip) and the
+ * X pass of a y-slab (fft3d.hip, fft_pass_strided MODE 6) alike.  axis < 0: value *= tab, the whole density factor of k2;
+ * otherwise fac = c0 * kaxis / k2, fac *= tab, value = i fac value, with kaxis the signed wave number along the axis and tab the
+ * table's entry of k2.  The zero mode is left as it is.  k2 < 2^53, so it may arrive as any integer type. */
+__device__ __forceinline__ double2 zel_transfer_mode(double2 v, long long k2, int kaxis, int axis, double tab, double c0)
+{
+#pragma clang fp contract(off)
+    if(k2) {
+        if(axis < 0) {
+            v.x *= tab;
+            v.y *= tab;
+        } else {
+            double fac = c0 * kaxis / k2;
+            fac *= tab;
+            const double tmp = v.x;
+            v.x = -v.y * fac;
+            v.y = tmp * fac;
+        }
+    }
+    return v;
+}
 /* from_i64: the mesh holds the int64 fixed-point deposit, worth inv_scale per unit.  d_sinctab, asmth2, pot_factor: the Green's function. */
 int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, shq_fft_stage stage, bool from_i64, double inv_scale, const double *d_sinctab,
                   double asmth2, double pot_factor, const shq_fft_opts &o = {});

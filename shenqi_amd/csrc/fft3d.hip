@@ -464,7 +464,9 @@ struct GreenArgs {
     const int32_t *bintab = nullptr;
     double *ps = nullptr;
     int ncell = 1; /* MODE 5: the int N^3 every mode is divided by (uvbg.cpp:211-215 divide_by_ncell) */
-    double2 *out = nullptr; /* fft_pass_strided MODE 5: the y-slab the result is stored into, laid out as the one it reads */
+    double2 *out = nullptr; /* fft_pass_strided MODES 5, 6: the y-slab the result is stored into, laid out as the one it reads */
+    int zel_axis = -1;      /* fft_pass_strided MODE 6: zel_transfer_mode's axis and c0 */
+    double zel_c0 = 0;
 };
 
 /* powerspectrum_add_mode (gravpm.cpp:323-356) of one mode into a workgroup's LDS histogram [3][N]: the operations of pm_power_kernel
@@ -499,6 +501,9 @@ __device__ __forceinline__ void pk_add(double *hist, const GreenArgs &ga, double
  *   MODE 5: the excursion-set filter on a y-slab (uvbg.hip, the sibling of fft_t_tile's MODE 5): reads a tile of the kept spectrum,
  *           every mode becomes (v / ncell) T[k2] - divide_by_ncell, then filter_pm (uvbg.cpp:211-250) - with no Green's function,
  *           then X inverse, stored OUT OF PLACE into the same place of ga.out: the kept spectrum is only read.
+ *   MODE 6: the Zel'dovich transfer of one field on a y-slab (zeldovich.hip), MODE 5 with another factor: reads a tile of the kept
+ *           Gaussian field, every mode becomes zel_transfer_mode(v, k2, k_axis, axis, T[k2], c0) - the one-rank kernel's function -
+ *           then X inverse, stored out of place into ga.out.  A pad column (z > N / 2) passes as it is.
  * MODES 3, 4 with ga.ps keep a P(k) histogram [3][N] in LDS behind the tables (3 N doubles more), flushed once per workgroup. */
 template <int N, int MODE, int PK = 0>
 __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const long long es, const long long outer_stride,
@@ -527,7 +532,7 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
      * bytes), so they should run on the same XCD at about the same time and find the other half in its L2. */
     const unsigned vb = xcd_block(blockIdx.x, gridDim.x, xcdk);
     double prx[E], pry[E];
-    double tfac[MODE == 4 || MODE == 5 ? E : 1]; /* MODES 4, 5: T[k2] of the prefetched tile's modes */
+    double tfac[MODE == 4 || MODE == 5 || MODE == 6 ? E : 1]; /* MODES 4, 5, 6: T[k2] of the prefetched tile's modes */
 #define FFT_FETCH(BASE, ABASE)                                                                   \
     _Pragma("unroll") for(int i = 0; i < E; i++)                                                 \
     {                                                                                            \
@@ -540,9 +545,9 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
             pry[i] = t_.y;                                                                       \
         }                                                                                        \
     }
-    /* MODES 4, 5: T[k2] of the modes of tile (O_, TL_); a pad column (z > N / 2) reads entry 0, so k2 stays inside the table */
+    /* MODES 4, 5, 6: T[k2] of the modes of tile (O_, TL_); a pad column (z > N / 2) reads entry 0, so k2 stays inside the table */
 #define FFT_TFETCH(O_, TL_)                                                                      \
-    if(MODE == 4 || MODE == 5) {                                                                            \
+    if(MODE == 4 || MODE == 5 || MODE == 6) {                                                  \
         const int y_ = ga.y0 + (O_), ky_ = y_ <= N / 2 ? y_ : y_ - N;                            \
         _Pragma("unroll") for(int i = 0; i < E; i++)                                             \
         {                                                                                        \
@@ -601,6 +606,20 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
                 if(EXACT || e < FFT_C * N)
                     buf[(e % FFT_C) * LS + lx<N>(e / FFT_C)] = make_double2((prx[i] / nc) * tfac[i], (pry[i] / nc) * tfac[i]);
             }
+        } else if(MODE == 6) {
+            const int y = ga.y0 + outer, z0 = tile * FFT_C;
+            const int ky = y <= N / 2 ? y : y - N;
+#pragma unroll
+            for(int i = 0; i < E; i++) {
+                const int e = threadIdx.x + i * FFT_T;
+                if(EXACT || e < FFT_C * N) {
+                    const int x = e / FFT_C, z = z0 + e % FFT_C;
+                    const int kx = x <= N / 2 ? x : x - N;
+                    const int k2 = z <= N / 2 ? kx * kx + ky * ky + z * z : 0;
+                    const int ka = ga.zel_axis == 0 ? kx : (ga.zel_axis == 1 ? ky : z);
+                    buf[(e % FFT_C) * LS + lx<N>(x)] = zel_transfer_mode(make_double2(prx[i], pry[i]), k2, ka, ga.zel_axis, tfac[i], ga.zel_c0);
+                }
+            }
         } else {
 #pragma unroll
             for(int i = 0; i < E; i++) {
@@ -635,7 +654,7 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
             fft_lines<N, -1>(buf, Wl, green);
             fft_lines<N, +1>(buf, Wl);
         }
-        if(MODE == 1 || MODE == 4 || MODE == 5)
+        if(MODE == 1 || MODE == 4 || MODE == 5 || MODE == 6)
             fft_lines<N, +1>(buf, Wl);
         FFT_TFETCH(outer_n, tile_n)
         if(MODE == 3) { /* the spectrum back in place; the density's P(k) on the way */
@@ -651,7 +670,7 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
                 }
             }
         } else {
-            double2 *ob = MODE == 5 ? ga.out + (base - cm) : base; /* MODE 5: the same tile of the other y-slab */
+            double2 *ob = MODE == 5 || MODE == 6 ? ga.out + (base - cm) : base; /* MODES 5, 6: the same tile of the other y-slab */
             for(int e = threadIdx.x; e < FFT_C * N; e += FFT_T) {
                 const int row = e / FFT_C, col = e - row * FFT_C;
                 if(PK == 1)
@@ -1194,6 +1213,7 @@ int run_n(shq_context *ctx, const double2 *W, double *d_mesh, int zp, shq_fft_st
         SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 3>, lds_hist}}, &p.res_x3));
         SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 4>, lds_hist}}, &p.res_x4));
         SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 5>, lds}}, &p.res_x5));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 6>, lds}}, &p.res_x6));
         SHQ_TRY(fft_resident(ncu, FFT_T,
                              {{fft_pass_strided<N, 0>, lds}, {fft_pass_strided<N, 1>, lds}, {fft_pass_strided<N, 2>, lds}, {fft_pass_strided<N, 0, 1>, lds},
                               {fft_pass_strided<N, 1, 2>, lds}},
@@ -1223,6 +1243,9 @@ int run_n(shq_context *ctx, const double2 *W, double *d_mesh, int zp, shq_fft_st
         break;
     case SHQ_FFT_X_FILTER:
         fft_pass_strided<N, 5><<<k.grid(stot, pl.res_x5), dim3(FFT_T), lds, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        break;
+    case SHQ_FFT_X_ZEL:
+        fft_pass_strided<N, 6><<<k.grid(stot, pl.res_x6), dim3(FFT_T), lds, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
         break;
     case SHQ_FFT_YZ_FORWARD:
     case SHQ_FFT_YZ_FORWARD_PACKED:
@@ -1368,7 +1391,8 @@ int shq_fft3d_run_transposed(shq_context *ctx, double *d_mesh, double *d_scratch
 int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, shq_fft_stage stage, bool from_i64, double inv_scale, const double *d_sinctab,
                   double asmth2, double pot_factor, const shq_fft_opts &o)
 {
-    const bool yslab = stage == SHQ_FFT_X_SOLVE || stage == SHQ_FFT_X_FORWARD_SUMS || stage == SHQ_FFT_X_FINISH || stage == SHQ_FFT_X_FILTER;
+    const bool yslab = stage == SHQ_FFT_X_SOLVE || stage == SHQ_FFT_X_FORWARD_SUMS || stage == SHQ_FFT_X_FINISH || stage == SHQ_FFT_X_FILTER ||
+                       stage == SHQ_FFT_X_ZEL;
     const bool packed = stage == SHQ_FFT_YZ_FORWARD_PACKED || stage == SHQ_FFT_YZ_INVERSE_PACKED;
     const int nslab = stage <= SHQ_FFT_SOLVE ? N : o.nslab;
     SHQ_CHECK(shq_fft3d_supported(N), SHQ_ERR_INVALID, "fft3d: unsupported mesh size %d", N);
@@ -1377,12 +1401,16 @@ int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, shq_fft_stage
     SHQ_CHECK((stage != SHQ_FFT_X_FINISH || o.modefac) && (!o.ps || o.bintab), SHQ_ERR_INVALID, "fft3d: bad split X pass arguments");
     SHQ_CHECK(stage != SHQ_FFT_X_FILTER || (o.modefac && o.out && o.out != d_mesh && o.ncell > 0), SHQ_ERR_INVALID,
               "fft3d: bad filter pass arguments");
+    SHQ_CHECK(stage != SHQ_FFT_X_ZEL || (o.modefac && o.fac_mask == -1 && o.out && o.out != d_mesh && o.zel_axis >= -1 && o.zel_axis <= 2),
+              SHQ_ERR_INVALID, "fft3d: bad transfer pass arguments");
     if(!o.tw)
         SHQ_TRY(ensure_twiddles(ctx, N));
     GreenArgs ga;
     ga.sinctab = d_sinctab;
     ga.asmth2 = asmth2;
     ga.pot_factor = pot_factor;
+    ga.zel_axis = o.zel_axis;
+    ga.zel_c0 = o.zel_c0;
     ga.y0 = o.y0;
     ga.alt = reinterpret_cast<double2 *>(o.packed);
     ga.modefac = o.modefac;

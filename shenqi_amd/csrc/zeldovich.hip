@@ -21,6 +21,11 @@
  * (the bespoke pipeline of fft3d.hip where it has the mesh size, hipFFT otherwise), one kernel gathers the mesh at the particles with
  * pm_iterate_one's weights.  A last kernel does the particle loop and the two max reductions.
  * The call owns every buffer it uses; of the context it touches only the resident field and the FFT twiddle table.
+ *
+ * Several ranks: the same phases as entry points of their own (shq_zeldovich_slab_*, at the end of the file) on the caller's device
+ * memory, with the caller's exchanges between them (shenqi_amd/dist.py, DistZeldovich).  The fill takes the columns (i, j) of a rank's
+ * y-slab, so no Gaussian field travels; the transfer is fused into the X inverse of that slab (fft3d.hip, fft_pass_strided MODE 6) with
+ * zel_transfer_mode, the function zel_transfer_kernel applies; the gather reads a window of x planes.
  */
 #include "mesh_common.hpp"
 #include <math.h>
@@ -100,12 +105,14 @@ __device__ __forceinline__ void mt_sample(MtLane &g, double *ampl, double *phase
     *ampl = a;
 }
 
-/* pmic_fill_gaussian_gadget's column loop (pmesh.h:93-172) for the columns [c0, c1), c = i * N + j.
+/* pmic_fill_gaussian_gadget's column loop (pmesh.h:93-172) for the columns [c0, c1) of a y-slab: c = i * njl + jl is the column (i, j)
+ * with j = j0 + jl, and its modes are stored as row c of `spec`, `pitch` complex apart (the whole mesh: j0 = 0, njl = N, pitch =
+ * N / 2 + 1).  The seed tables are the whole mesh's, [N][N].  Pad columns k > N / 2 of a wider pitch are written as 0.
  * !PATCH: tab = table[0][0]; every mode of the column from its own generator, the self-conjugate modes real, the zero mode 0.
  *  PATCH: tab = table[1][1]; the d1 = d2 = 1 columns only, their k = 0 and k = N / 2 modes conjugated (launched after the other). */
 template <bool PATCH>
-__global__ __launch_bounds__(ZW) void zel_fill_kernel(int N, long long c0, long long c1, const uint32_t *__restrict__ tab, uint32_t *ws,
-                                                      int unitary, int invert, double2 *__restrict__ spec)
+__global__ __launch_bounds__(ZW) void zel_fill_kernel(int N, long long c0, long long c1, int j0, int njl, int pitch, const uint32_t *__restrict__ tab,
+                                                      uint32_t *ws, int unitary, int invert, double2 *__restrict__ spec)
 {
 #pragma clang fp contract(off)
     __shared__ double2 tile[ZW][ZK + 1];
@@ -114,7 +121,7 @@ __global__ __launch_bounds__(ZW) void zel_fill_kernel(int N, long long c0, long 
     const long long c = cbase + lane;
     const int Nc = N / 2 + 1;
     bool act = c < c1;
-    const int i = act ? (int) (c / N) : 0, j = act ? (int) (c - (long long) i * N) : 0;
+    const int i = act ? (int) (c / njl) : 0, j = j0 + (act ? (int) (c - (long long) i * njl) : 0);
     const int ci = (N - i) % N, cj = (N - j) % N;
     const bool d = (ci == i && cj < j) || ci < i; /* pmesh.h:109-114 */
     if(PATCH)
@@ -123,7 +130,7 @@ __global__ __launch_bounds__(ZW) void zel_fill_kernel(int N, long long c0, long 
     g.stride = (size_t) gridDim.x * ZW;
     g.st = ws + (size_t) blockIdx.x * ZW + lane;
     if(act)
-        mt_seed(g, tab[c]);
+        mt_seed(g, tab[(size_t) i * N + j]);
     if(PATCH) {
         if(!act)
             return;
@@ -137,34 +144,37 @@ __global__ __launch_bounds__(ZW) void zel_fill_kernel(int N, long long c0, long 
                 ampl = 1.0;
             if(invert)
                 phase += M_PI;
-            spec[(size_t) c * Nc + k] = make_double2(ampl * cos(phase), -(ampl * sin(phase)));
+            spec[(size_t) c * pitch + k] = make_double2(ampl * cos(phase), -(ampl * sin(phase)));
         }
         return;
     }
     const bool selfij = ci == i && cj == j;
-    for(int k0 = 0; k0 < Nc; k0 += ZK) {
+    for(int k0 = 0; k0 < pitch; k0 += ZK) {
         if(act)
-            for(int kk = 0; kk < ZK && k0 + kk < Nc; kk++) {
+            for(int kk = 0; kk < ZK && k0 + kk < pitch; kk++) {
                 const int k = k0 + kk;
-                double ampl, phase;
-                mt_sample(g, &ampl, &phase);
-                ampl = sqrt(-log(ampl));
-                if(unitary)
-                    ampl = 1.0;
-                if(invert)
-                    phase += M_PI;
-                double2 v = make_double2(ampl * cos(phase), ampl * sin(phase));
-                if(selfij && (N - k) % N == k)
-                    v.y = 0;
-                if(c == 0 && k == 0)
-                    v = make_double2(0.0, 0.0);
+                double2 v = make_double2(0.0, 0.0);
+                if(k < Nc) {
+                    double ampl, phase;
+                    mt_sample(g, &ampl, &phase);
+                    ampl = sqrt(-log(ampl));
+                    if(unitary)
+                        ampl = 1.0;
+                    if(invert)
+                        phase += M_PI;
+                    v = make_double2(ampl * cos(phase), ampl * sin(phase));
+                    if(selfij && (N - k) % N == k)
+                        v.y = 0;
+                    if(i == 0 && j == 0 && k == 0)
+                        v = make_double2(0.0, 0.0);
+                }
                 tile[lane][kk] = v;
             }
         __syncthreads();
         for(int r = 0; r < ZW / 8; r++) {
             const int col = r * 8 + (lane >> 3), kk = lane & 7;
-            if(cbase + col < c1 && k0 + kk < Nc)
-                spec[(size_t) (cbase + col) * Nc + k0 + kk] = tile[col][kk];
+            if(cbase + col < c1 && k0 + kk < pitch)
+                spec[(size_t) (cbase + col) * pitch + k0 + kk] = tile[col][kk];
         }
         __syncthreads();
     }
@@ -222,22 +232,25 @@ __global__ __launch_bounds__(ZT) void zel_transfer_kernel(const double2 *__restr
         return;
     const HalfMode md = half_mode(ip, N);
     const int kpos[3] = {md.kx, md.ky, md.z};
-    const long long k2 = md.k2;
-    double2 v = spec[ip];
-    if(k2) {
-        if(axis < 0) {
-            const double fac = tab[k2];
-            v.x *= fac;
-            v.y *= fac;
-        } else {
-            double fac = c0 * kpos[axis] / k2;
-            fac *= tab[k2];
-            const double tmp = v.x;
-            v.x = -v.y * fac;
-            v.y = tmp * fac;
-        }
-    }
-    out[md.row * zpc + md.z] = v;
+    out[md.row * zpc + md.z] = zel_transfer_mode(spec[ip], md.k2, axis < 0 ? 0 : kpos[axis], axis, md.k2 ? tab[md.k2] : 0.0, c0);
+}
+
+/* the same factor on a rank's dense y-slab [x][row][N / 2 + 1], row = mesh row y0 + row (shq_zeldovich_slab_transfer) */
+__global__ __launch_bounds__(ZT) void zel_slab_transfer_kernel(const double2 *spec, double2 *out, int N, int y0, int nyl,
+                                                               const double *__restrict__ tab, int axis, double c0)
+{
+#pragma clang fp contract(off)
+    const int Nc = N / 2 + 1;
+    const size_t total = (size_t) N * nyl * Nc;
+    const size_t ip = (size_t) blockIdx.x * ZT + threadIdx.x;
+    if(ip >= total)
+        return;
+    const int z = (int) (ip % Nc), row = (int) ((ip / Nc) % nyl), x = (int) (ip / ((size_t) Nc * nyl));
+    const int y = y0 + row;
+    const int kx = x <= N / 2 ? x : x - N, ky = y <= N / 2 ? y : y - N;
+    const long long k2 = (long long) kx * kx + (long long) ky * ky + (long long) z * z;
+    const int kpos[3] = {kx, ky, z};
+    out[ip] = zel_transfer_mode(spec[ip], k2, axis < 0 ? 0 : kpos[axis], axis, k2 ? tab[k2] : 0.0, c0);
 }
 
 /* pm_iterate_one (petapm.cpp:1153-1177) with the readout functions: out[p] = sum over the 8 connections, in their order, of weight * mesh */
@@ -259,6 +272,33 @@ __global__ __launch_bounds__(ZT) void zel_readout_kernel(long long n, const doub
         acc += weight * mesh[lin];
     });
     out[p] = acc;
+}
+
+/* zel_readout_kernel on a rank's window [nalloc][N][zp] of x planes whose plane 0 is the mesh plane plane0: the same eight
+ * connections in the same order with the same weights.  A particle with a corner outside the window raises *oob and writes nothing. */
+__global__ __launch_bounds__(ZT) void zel_gather_kernel(long long n, const double *__restrict__ pos, const double *__restrict__ mesh, int N, int zp,
+                                                        double cellsize, int plane0, int nalloc, double *__restrict__ out, int *oob)
+{
+#pragma clang fp contract(off)
+    const long long p = (long long) blockIdx.x * ZT + threadIdx.x;
+    if(p >= n)
+        return;
+    int ic[3];
+    double res[3];
+    cic_cell3(pos[3 * p], pos[3 * p + 1], pos[3 * p + 2], cellsize, N, ic, res);
+    double acc = 0;
+    int outside = 0;
+    cic_corners<true>(
+        ic, res, N, zp,
+        [&](int, size_t lin, double weight) {
+#pragma clang fp contract(off)
+            acc += weight * mesh[lin];
+        },
+        plane0, nalloc, &outside);
+    if(outside)
+        *oob = 1;
+    else
+        out[p] = acc;
 }
 
 __device__ __forceinline__ double zel_wrap(double x, double L)
@@ -335,20 +375,15 @@ void zel_seed_table(int N, int Seed, uint32_t *t00, uint32_t *t11)
     }
 }
 
-/* the resident field of (N, Seed, unitary, invert): reused, or filled; *filled says which */
-int zel_ensure_field(shq_context *ctx, int N, int Seed, int unitary, int invert, bool *filled)
+/* The two fill launches over the columns (i, j), j0 <= j < j0 + njl, into spec = [N][njl][pitch] complex, in chunks of the context's
+ * fill chunk.  The seed tables are made here, for the whole mesh: every rank makes the same ones. */
+int zel_fill_columns(shq_context *ctx, int N, int Seed, int unitary, int invert, int j0, int njl, int pitch, double2 *spec)
 {
-    *filled = false;
-    if(ctx->zel_have && ctx->zel_n == N && ctx->zel_seed == Seed && ctx->zel_unitary == unitary && ctx->zel_invert == invert)
-        return SHQ_OK;
-    ctx->zel_have = false;
     const size_t NN = (size_t) N * N;
-    const int Nc = N / 2 + 1;
-    SHQ_TRY(ctx->zel_spec.reserve(NN * Nc * 2));
     std::vector<uint32_t> t00(NN), t11(NN);
     zel_seed_table(N, Seed, t00.data(), t11.data());
     CallScope sc(ctx, "zeldovich");
-    const long long ncol = (long long) NN;
+    const long long ncol = (long long) N * njl;
     long long chunk = ctx->zel_chunk > 0 ? ctx->zel_chunk : ZEL_CHUNK;
     chunk = std::min(ncol, (chunk + ZW - 1) / ZW * ZW);
     uint32_t *d_t00, *d_t11, *d_ws;
@@ -358,18 +393,30 @@ int zel_ensure_field(shq_context *ctx, int N, int Seed, int unitary, int invert,
     hipStream_t s = ctx->stream;
     SHQ_HIP(hipMemcpyAsync(d_t00, t00.data(), sizeof(uint32_t) * NN, hipMemcpyHostToDevice, s));
     SHQ_HIP(hipMemcpyAsync(d_t11, t11.data(), sizeof(uint32_t) * NN, hipMemcpyHostToDevice, s));
-    double2 *spec = reinterpret_cast<double2 *>(ctx->zel_spec.ptr);
     for(int pass = 0; pass < 2; pass++)
         for(long long c0 = 0; c0 < ncol; c0 += chunk) {
             const long long c1 = std::min(ncol, c0 + chunk);
             const dim3 grid(nblk(c1 - c0, ZW));
             if(pass == 0)
-                zel_fill_kernel<false><<<grid, dim3(ZW), 0, s>>>(N, c0, c1, d_t00, d_ws, unitary, invert, spec);
+                zel_fill_kernel<false><<<grid, dim3(ZW), 0, s>>>(N, c0, c1, j0, njl, pitch, d_t00, d_ws, unitary, invert, spec);
             else
-                zel_fill_kernel<true><<<grid, dim3(ZW), 0, s>>>(N, c0, c1, d_t11, d_ws, unitary, invert, spec);
+                zel_fill_kernel<true><<<grid, dim3(ZW), 0, s>>>(N, c0, c1, j0, njl, pitch, d_t11, d_ws, unitary, invert, spec);
             SHQ_HIP(hipGetLastError());
         }
     SHQ_HIP(hipStreamSynchronize(s)); /* the host tables go out of scope */
+    return SHQ_OK;
+}
+
+/* the resident field of (N, Seed, unitary, invert): reused, or filled; *filled says which */
+int zel_ensure_field(shq_context *ctx, int N, int Seed, int unitary, int invert, bool *filled)
+{
+    *filled = false;
+    if(ctx->zel_have && ctx->zel_n == N && ctx->zel_seed == Seed && ctx->zel_unitary == unitary && ctx->zel_invert == invert)
+        return SHQ_OK;
+    ctx->zel_have = false;
+    const int Nc = N / 2 + 1;
+    SHQ_TRY(ctx->zel_spec.reserve((size_t) N * N * Nc * 2));
+    SHQ_TRY(zel_fill_columns(ctx, N, Seed, unitary, invert, 0, N, Nc, reinterpret_cast<double2 *>(ctx->zel_spec.ptr)));
     ctx->zel_have = true;
     ctx->zel_n = N;
     ctx->zel_seed = Seed;
@@ -603,5 +650,189 @@ extern "C" int shq_zeldovich_displacements(shq_context *ctx, const shq_zeldovich
     ctx->zel_ms[1] = sc.ms(1, 2);
     ctx->zel_ms[2] = sc.ms(2, 3);
     ctx->zel_ms[3] = sc.ms(0, 4);
+    return SHQ_OK;
+}
+
+/* ---- the same phases on a rank's slab (several ranks: shenqi_amd/dist.py, DistZeldovich) ---------------------------------------
+ * Every pointer named d_ is device memory of the caller (torch tensors).  The Gaussian field lives on a y-slab [N][nyl][zpc] complex
+ * (zpc = shq_zeldovich_slab_pitch / 2, or N / 2 + 1 without a bespoke transform), a field's real mesh on the rank's x planes
+ * [nalloc][N][zp] doubles.  None of these calls reads or writes the PM's state or the one-rank resident field: the twiddles, the tables
+ * and the flags are the context's zels_ ones. */
+namespace {
+
+int zel_slab_twiddles(shq_context *ctx, int N, const double **tw)
+{
+    if(ctx->zels_tw_n != N) {
+        SHQ_HIP(hipStreamSynchronize(ctx->stream)); /* a pass of another size may still read the table */
+        SHQ_TRY(ctx->zels_tw.reserve(2 * (size_t) N));
+        SHQ_TRY(shq_fft3d_fill_twiddles(N, ctx->zels_tw.ptr));
+        ctx->zels_tw_n = N;
+    }
+    *tw = ctx->zels_tw.ptr;
+    return SHQ_OK;
+}
+
+/* the table and the axis of field 0 .. 6 (Density, DispX/Y/Z, VelX/Y/Z) from the uploaded tables */
+int zel_slab_field(shq_context *ctx, int N, double BoxSize, int field, const char *who, const double **tab, int *axis)
+{
+    SHQ_CHECK(field >= 0 && field < 7, SHQ_ERR_INVALID, "%s: field %d outside [0, 7)", who, field);
+    SHQ_CHECK(ctx->zels_tabs_n == N && ctx->zels_box == BoxSize, SHQ_ERR_STATE,
+              "%s: no tables of mesh size %d and this BoxSize (shq_zeldovich_slab_tables first)", who, N);
+    SHQ_CHECK(field < 4 || ctx->zels_growth, SHQ_ERR_STATE, "%s: a velocity field without a dlogGrowth table", who);
+    const size_t nk2 = 3 * (size_t) (N / 2) * (N / 2) + 1;
+    *tab = ctx->zels_tabs.ptr + (field == 0 ? 0 : (field < 4 ? 1 : 2)) * nk2;
+    *axis = field == 0 ? -1 : (field - 1) % 3;
+    return SHQ_OK;
+}
+
+} // namespace
+
+extern "C" int shq_zeldovich_slab_pitch(int Nmesh) { return fft3d_route(Nmesh).bespoke ? shq_fft3d_pitch(Nmesh) : 0; }
+
+extern "C" int shq_zeldovich_slab_fill(shq_context *ctx, int Nmesh, int Seed, int UnitaryAmplitude, int InvertPhase, int y0, int nyl, void *d_spec)
+{
+    SHQ_CHECK(ctx && d_spec, SHQ_ERR_INVALID, "zeldovich_slab_fill: null argument");
+    SHQ_TRY(mesh_check_size(Nmesh, "zeldovich_slab_fill"));
+    SHQ_CHECK(nyl > 0 && y0 >= 0 && y0 + nyl <= Nmesh, SHQ_ERR_INVALID, "zeldovich_slab_fill: bad slab geometry");
+    SHQ_HIP(hipSetDevice(ctx->device));
+    const int zp = shq_zeldovich_slab_pitch(Nmesh);
+    return zel_fill_columns(ctx, Nmesh, Seed, UnitaryAmplitude != 0, InvertPhase != 0, y0, nyl, zp ? zp / 2 : Nmesh / 2 + 1, (double2 *) d_spec);
+}
+
+extern "C" int shq_zeldovich_slab_tables(shq_context *ctx, int Nmesh, double BoxSize, const double *delta, const double *growth)
+{
+    SHQ_CHECK(ctx && delta, SHQ_ERR_INVALID, "zeldovich_slab_tables: null argument");
+    const int N = Nmesh;
+    SHQ_TRY(mesh_check_size(N, "zeldovich_slab_tables"));
+    SHQ_CHECK(isfinite(BoxSize) && BoxSize > 0, SHQ_ERR_INVALID, "zeldovich_slab_tables: BoxSize must be finite and > 0");
+    const size_t nk2 = 3 * (size_t) (N / 2) * (N / 2) + 1;
+    for(size_t k2 = 1; k2 < nk2; k2++)
+        SHQ_CHECK(isfinite(delta[k2]) && (!growth || isfinite(growth[k2])), SHQ_ERR_INVALID, "zeldovich_slab_tables: non-finite table entry at k2 = %zu", k2);
+    SHQ_HIP(hipSetDevice(ctx->device));
+    std::vector<double> tabs(3 * nk2, 0.0);
+    zel_density_table(N, BoxSize, delta, tabs.data());
+    memcpy(tabs.data() + nk2, delta, sizeof(double) * nk2);
+    if(growth)
+        memcpy(tabs.data() + 2 * nk2, growth, sizeof(double) * nk2);
+    tabs[nk2] = tabs[2 * nk2] = 0; /* entry 0 is what a pad column fetches: never used, but finite */
+    ctx->zels_tabs_n = 0;
+    SHQ_HIP(hipStreamSynchronize(ctx->stream)); /* a transfer pass may still read the previous tables */
+    SHQ_TRY(ctx->zels_tabs.reserve(tabs.size()));
+    SHQ_HIP(hipMemcpy(ctx->zels_tabs.ptr, tabs.data(), sizeof(double) * tabs.size(), hipMemcpyHostToDevice));
+    ctx->zels_tabs_n = N;
+    ctx->zels_growth = growth != nullptr;
+    ctx->zels_box = BoxSize;
+    return SHQ_OK;
+}
+
+/* The transfer pass of one field on the kept Gaussian field d_spec = [N][nyl][zp / 2] complex: zel_transfer_mode per mode, then the X
+ * inverse, stored into d_out of the same shape.  d_spec is only read. */
+extern "C" int shq_zeldovich_slab_xtransfer(shq_context *ctx, int Nmesh, double BoxSize, const void *d_spec, void *d_out, int y0, int nyl, int field)
+{
+#pragma clang fp contract(off)
+    SHQ_CHECK(ctx && d_spec && d_out && d_spec != d_out, SHQ_ERR_INVALID, "zeldovich_slab_xtransfer: null argument, or the pass asked to run in place");
+    const int N = Nmesh, zp = shq_zeldovich_slab_pitch(N);
+    SHQ_CHECK(zp > 0, SHQ_ERR_INVALID, "zeldovich_slab_xtransfer: mesh size %d has no bespoke FFT", N);
+    SHQ_CHECK(nyl > 0 && y0 >= 0 && y0 + nyl <= N, SHQ_ERR_INVALID, "zeldovich_slab_xtransfer: bad slab geometry");
+    shq_fft_opts o;
+    SHQ_TRY(zel_slab_field(ctx, N, BoxSize, field, "zeldovich_slab_xtransfer", &o.modefac, &o.zel_axis));
+    SHQ_HIP(hipSetDevice(ctx->device));
+    SHQ_TRY(zel_slab_twiddles(ctx, N, &o.tw));
+    o.nslab = nyl;
+    o.y0 = y0;
+    o.fac_mask = -1;
+    o.out = (double *) d_out;
+    o.zel_c0 = 1. / (2 * M_PI) / libm_sqrt(BoxSize);
+    return shq_fft3d_run(ctx, (double *) const_cast<void *>(d_spec), N, zp, SHQ_FFT_X_ZEL, false, 1.0, nullptr, 0, 0, o);
+}
+
+/* the same factor for a mesh size without a bespoke transform, between the caller's own X transforms: d_spec = [N][nyl][N / 2 + 1]
+ * complex, dense, x slowest, into d_out of the same shape (d_out may be d_spec) */
+extern "C" int shq_zeldovich_slab_transfer(shq_context *ctx, int Nmesh, double BoxSize, const void *d_spec, void *d_out, int y0, int nyl, int field)
+{
+#pragma clang fp contract(off)
+    SHQ_CHECK(ctx && d_spec && d_out, SHQ_ERR_INVALID, "zeldovich_slab_transfer: null argument");
+    const int N = Nmesh;
+    SHQ_TRY(mesh_check_size(N, "zeldovich_slab_transfer"));
+    SHQ_CHECK(nyl > 0 && y0 >= 0 && y0 + nyl <= N, SHQ_ERR_INVALID, "zeldovich_slab_transfer: bad slab geometry");
+    const double *tab;
+    int axis;
+    SHQ_TRY(zel_slab_field(ctx, N, BoxSize, field, "zeldovich_slab_transfer", &tab, &axis));
+    SHQ_HIP(hipSetDevice(ctx->device));
+    const long long modes = (long long) N * nyl * (N / 2 + 1);
+    zel_slab_transfer_kernel<<<dim3(nblk(modes, ZT)), dim3(ZT), 0, ctx->stream>>>((const double2 *) d_spec, (double2 *) d_out, N, y0, nyl, tab, axis,
+                                                                                 1. / (2 * M_PI) / libm_sqrt(BoxSize));
+    SHQ_HIP(hipGetLastError());
+    return SHQ_OK;
+}
+
+/* the Y/Z inverse of `nplanes` x planes [nplanes][N][zp] doubles, in place; d_packed (NULL: the planes hold the spectrum already) is the
+ * all-to-all buffer [nranks][nplanes][N / nranks][zp / 2] complex the Y pass reads instead */
+extern "C" int shq_zeldovich_slab_fft_yz(shq_context *ctx, int Nmesh, void *d_planes, int nplanes, const void *d_packed, int nranks)
+{
+    SHQ_CHECK(ctx && d_planes, SHQ_ERR_INVALID, "zeldovich_slab_fft_yz: null argument");
+    const int N = Nmesh, zp = shq_zeldovich_slab_pitch(N);
+    SHQ_CHECK(zp > 0, SHQ_ERR_INVALID, "zeldovich_slab_fft_yz: mesh size %d has no bespoke FFT", N);
+    SHQ_CHECK(nplanes > 0 && nplanes <= N, SHQ_ERR_INVALID, "zeldovich_slab_fft_yz: bad arguments");
+    SHQ_CHECK(!d_packed || (nranks >= 1 && N % nranks == 0), SHQ_ERR_INVALID, "zeldovich_slab_fft_yz: %d ranks do not divide the mesh", nranks);
+    SHQ_HIP(hipSetDevice(ctx->device));
+    shq_fft_opts o;
+    SHQ_TRY(zel_slab_twiddles(ctx, N, &o.tw));
+    o.nslab = nplanes;
+    o.packed = (double *) const_cast<void *>(d_packed);
+    o.nranks = d_packed ? nranks : 1;
+    return shq_fft3d_run(ctx, (double *) d_planes, N, zp, d_packed ? SHQ_FFT_YZ_INVERSE_PACKED : SHQ_FFT_YZ_INVERSE, false, 1.0, nullptr, 0, 0, o);
+}
+
+/* pm_iterate_one's gather of d_mesh = [nalloc][N][zp] doubles (zp: the slab pitch, or N + 2 without a bespoke transform) at d_pos =
+ * double[n][3] into d_out[n]: the rank's own planes from plane0 on and, for a slab with a neighbour, the neighbour's first plane
+ * behind them (nalloc = nplanes + 1; nplanes = N: the whole periodic mesh, nalloc = N) */
+extern "C" int shq_zeldovich_slab_gather(shq_context *ctx, int Nmesh, double BoxSize, const void *d_pos, int64_t n, const void *d_mesh, int plane0,
+                                         int nplanes, int nalloc, void *d_out)
+{
+    SHQ_CHECK(ctx && d_mesh, SHQ_ERR_INVALID, "zeldovich_slab_gather: null argument");
+    SHQ_CHECK(n >= 0 && n < (1ll << 31) && (n == 0 || (d_pos && d_out)), SHQ_ERR_INVALID, "zeldovich_slab_gather: bad particle arrays");
+    const int N = Nmesh;
+    SHQ_TRY(mesh_check_size(N, "zeldovich_slab_gather"));
+    SHQ_CHECK(isfinite(BoxSize) && BoxSize > 0, SHQ_ERR_INVALID, "zeldovich_slab_gather: BoxSize must be finite and > 0");
+    SHQ_CHECK(nplanes > 0 && nplanes <= N && plane0 >= 0 && plane0 < N && nalloc == (nplanes == N ? N : nplanes + 1), SHQ_ERR_INVALID,
+              "zeldovich_slab_gather: bad slab geometry");
+    SHQ_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    SHQ_TRY(ctx->zels_flag.reserve(1));
+    SHQ_HIP(hipMemsetAsync(ctx->zels_flag.ptr, 0, sizeof(int), s));
+    if(n > 0)
+        zel_gather_kernel<<<dim3(nblk(n, ZT)), dim3(ZT), 0, s>>>(n, (const double *) d_pos, (const double *) d_mesh, N, fft3d_route(N).zp,
+                                                                  BoxSize / N, plane0, nalloc, (double *) d_out, ctx->zels_flag.ptr);
+    SHQ_HIP(hipGetLastError());
+    int oob = 0;
+    SHQ_HIP(hipMemcpyAsync(&oob, ctx->zels_flag.ptr, sizeof(int), hipMemcpyDeviceToHost, s));
+    SHQ_HIP(hipStreamSynchronize(s));
+    SHQ_CHECK(!oob, SHQ_ERR_INVALID, "zeldovich_slab_gather: a particle lies outside this rank's slab (planes %d .. %d)", plane0, plane0 + nplanes - 1);
+    return SHQ_OK;
+}
+
+/* the particle loop on device pointers: d_pos = double[n][3], d_fld = double[7][n] (rows 4 .. 6 read only with ScaleDepVelocity),
+ * d_pos_out, d_vel, d_disp = double[n][3]; mx = this rank's maxdisp and max |Vel|^2 */
+extern "C" int shq_zeldovich_slab_finalize(shq_context *ctx, int64_t n, const void *d_pos, const void *d_fld, int ScaleDepVelocity, double vel_prefac,
+                                           double BoxSize, void *d_pos_out, void *d_vel, void *d_disp, double mx[2])
+{
+    SHQ_CHECK(ctx && mx, SHQ_ERR_INVALID, "zeldovich_slab_finalize: null argument");
+    SHQ_CHECK(n >= 0 && n < (1ll << 31) && (n == 0 || (d_pos && d_fld && d_pos_out && d_vel && d_disp)), SHQ_ERR_INVALID,
+              "zeldovich_slab_finalize: bad particle arrays");
+    SHQ_CHECK(isfinite(BoxSize) && BoxSize > 0 && isfinite(vel_prefac), SHQ_ERR_INVALID,
+              "zeldovich_slab_finalize: BoxSize must be finite and > 0, vel_prefac finite");
+    SHQ_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    SHQ_TRY(ctx->zels_mx.reserve(2));
+    SHQ_HIP(hipMemsetAsync(ctx->zels_mx.ptr, 0, sizeof(unsigned long long) * 2, s));
+    if(n > 0)
+        zel_finalize_kernel<<<dim3(nblk(n, ZT)), dim3(ZT), 0, s>>>(n, (const double *) d_pos, (const double *) d_fld, ScaleDepVelocity != 0, vel_prefac,
+                                                                    BoxSize, (double *) d_pos_out, (double *) d_vel, (double *) d_disp, ctx->zels_mx.ptr);
+    SHQ_HIP(hipGetLastError());
+    unsigned long long h[2] = {0, 0};
+    SHQ_HIP(hipMemcpyAsync(h, ctx->zels_mx.ptr, sizeof(h), hipMemcpyDeviceToHost, s));
+    SHQ_HIP(hipStreamSynchronize(s));
+    memcpy(mx, h, sizeof(h));
     return SHQ_OK;
 }

@@ -175,6 +175,16 @@ class Comm:
         dist.all_reduce(t, group=self.group)
         return t.cpu().numpy()
 
+    def allreduce_max_vec(self, a):
+        """Element-wise maximum over the ranks of a numpy array of any shape, in its own dtype (float64 or int64); every rank gets
+        the same new array."""
+        a = np.array(a, order="C")             # a copy: the reduction runs in place
+        if not self.multi or a.size == 0:
+            return a
+        t = torch.from_numpy(a).to(self._cdev())
+        dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+        return t.cpu().numpy()
+
     def gather_scalar(self, v, dtype=np.float64):
         """every rank's v as an array indexed by rank: float64, or int64 for counts (exact beyond 2^53)"""
         a = np.zeros(self.size, dtype=dtype)
@@ -2160,6 +2170,225 @@ class GpuUvbgOps:
         assert J21ext.is_contiguous() and J21ext.dtype == torch.float32
         self._call(capi.hip.shq_uvbg_slab_readout, C.byref(p), C.byref(cosmo), self._p(posm), self._p(types), posm.shape[0], self._p(J21ext), plane0, nxl,
                    J21ext.shape[0], self._p(local_J21), self._p(zreion))
+
+
+class DistZeldovich:
+    """displacement_fields (libgenic/zeldovich.cpp:150-264) on x-slabs of the Nmesh mesh, one per rank: whole planes of equal width.
+    Nmesh must be divisible by the rank count (equal y-slabs of the spectrum): otherwise the constructor raises ValueError on every
+    rank, before any collective.
+
+    Every rank fills the Gaussian field of its own y-slab (one mt19937 per mesh column: no communication, the bits of the one-rank
+    field) and keeps it on this object across calls, keyed on (Nmesh, Seed, UnitaryAmplitude, InvertPhase): a second species does
+    not refill.  Per field the transfer function is fused into the X inverse on the y-slab, ONE all-to-all takes the result to the
+    x-slabs, the Y/Z inverse runs there, one shift brings the right-hand neighbour's first plane, and the particles routed to the
+    owner of their CIC base cell gather with pm_iterate_one's weights.  A mesh line sees the same kernel arithmetic on any rank, so
+    on the bespoke route the results do not depend on the rank count or on who held which particle.  ops (GpuZeldovichOps below; the
+    CPU tests use a numpy stand-in) works on torch tensors:
+      ops.pitch(N) -> doubles per z row of the bespoke passes, 0 without them;
+      ops.fill(N, Seed, unitary, invert, y0, nyl) -> complex [N, nyl, pitch / 2 or N / 2 + 1];  ops.tables(N, L, delta, growth);
+      ops.gather(N, L, pos, window, plane0, nxl, out);  ops.finalize(pos, fld, scaledep, vel_prefac, L) -> (Pos, Vel, Disp, [mx, mv]);
+      bespoke route: ops.xtransfer(N, L, spec, out, y0, nyl, field), ops.fft_yz(N, planes, nxl, packed, P);
+      torch.fft route: ops.transfer(N, L, spec, y0, nyl, field) -> a new tensor.
+    Counters of the last call: rows_sent (particle rows that left this rank), nalltoall (all-to-alls and shifts started), filled
+    (whether the field was filled rather than reused).  Nothing here has run on more than one GPU."""
+
+    def __init__(self, comm, Nmesh, BoxSize, ops, bounds=None):
+        self.comm, self.ops, self.N, self.L = comm, ops, int(Nmesh), float(BoxSize)
+        self.d = SlabDecomp(comm, self.N, self.L, bounds)
+        if len(set(self.d.widths)) != 1:
+            raise ValueError("DistZeldovich needs slabs of equal width (got %s)" % (self.d.widths,))
+        self.rows_sent = self.nalltoall = 0
+        self.filled = False
+        self._key = self._spec = None
+
+    def _a2a(self, send, send_counts, recv_counts=None):
+        self.nalltoall += 1
+        if recv_counts is None:
+            return self.comm.all_to_all_rows(send, send_counts)
+        return self.comm.all_to_all_rows_start(send, send_counts, recv_counts)
+
+    def _shift(self, t, direction):
+        self.nalltoall += 1
+        return self.comm.shift(t, direction)
+
+    def _refusal(self, params, delta, growth, pos):
+        """what is wrong with this rank's input, or None"""
+        nk2 = 3 * (self.N // 2) ** 2 + 1
+        if params.Nmesh != self.N or params.BoxSize != self.L:
+            return "the parameters' Nmesh / BoxSize are not this decomposition's"
+        if not (math.isfinite(self.L) and self.L > 0 and math.isfinite(params.vel_prefac)):
+            return "zeldovich: BoxSize must be finite and > 0, vel_prefac finite"
+        if params.ScaleDepVelocity and growth is None:
+            return "zeldovich: ScaleDepVelocity without a dlogGrowth table"
+        if len(delta) != nk2 or (growth is not None and len(growth) != nk2):
+            return "the tables by k2 need %d entries" % nk2
+        if not np.isfinite(delta[1:]).all() or (params.ScaleDepVelocity and not np.isfinite(growth[1:]).all()):
+            return "zeldovich: non-finite table entry"
+        if pos.ndim != 2 or pos.shape[1] != 3:
+            return "zeldovich: positions must be [n, 3]"
+        if not ((pos >= 0) & (pos < self.L)).all():           # a NaN fails both
+            return "zeldovich: a particle is outside [0, BoxSize)"
+        return None
+
+    def displacements(self, params, delta, growth, pos):
+        """params: capi.ZeldovichParams; delta, growth: the tables by k2 (growth may be None without ScaleDepVelocity), the same on
+        every rank; pos [n, 3]: the undisplaced positions this rank holds, in any distribution over the ranks.  Returns dict(Pos, Vel,
+        Density, Disp, maxdisp, maxvel) in the caller's order, the two maxima the same on every rank.  Bad input on any rank raises
+        ValueError on every rank: the ranks agree on it in one reduced flag, the first collective of the call."""
+        c, d, ops, N, L = self.comm, self.d, self.ops, self.N, self.L
+        pos = np.require(pos, dtype=np.float64, requirements=["C", "W"])      # torch takes no read-only array
+        delta = np.ascontiguousarray(delta, dtype=np.float64)
+        growth = None if growth is None else np.ascontiguousarray(growth, dtype=np.float64)
+        why = self._refusal(params, delta, growth, pos)
+        if c.allreduce_max_vec(np.array([0.0 if why is None else 1.0]))[0] > 0:
+            raise ValueError(why or "zeldovich: another rank refused its input")
+        scaledep = bool(params.ScaleDepVelocity)
+        self.rows_sent = self.nalltoall = 0
+        n = len(pos)
+        # ---- to the owner of the particle's CIC base plane; rows already at home stay in the self block
+        # SlabDecomp.owner_of's floor(x / cell) % N, taken on the host: numpy divides as cic_setup does, while torch on the device
+        # multiplies by the reciprocal of a scalar divisor - at nextafter(BoxSize, 0) that is plane N - 1 where the kernel sees cell
+        # N = 0, and the particle would sit on the last rank with its corners on the first
+        rows = torch.from_numpy(pos).to(ops.device)
+        plane = np.floor(pos[:, 0] / d.cell).astype(np.int64) % N
+        owner = torch.from_numpy(np.searchsorted(np.asarray(d.bounds[1:-1], dtype=np.int64), plane, side="right")).to(ops.device)
+        order = torch.argsort(owner, stable=True)
+        counts = torch.bincount(owner, minlength=c.size).tolist()
+        self.rows_sent = n - counts[c.rank]
+        mine, rcounts = self._a2a(rows[order].contiguous(), counts)
+        mine = mine.contiguous()
+        # ---- the Gaussian field of this rank's y-slab, kept across calls
+        P, nxl = c.size, d.nxl
+        nyl, y0 = N // P, c.rank * (N // P)
+        key = (N, int(params.Seed), int(bool(params.UnitaryAmplitude)), int(bool(params.InvertPhase)))
+        self.filled = self._key != key
+        if self.filled:
+            self._key = self._spec = None
+            self._spec = ops.fill(*key, y0, nyl)
+            self._key = key
+        ops.tables(N, L, delta, growth if scaledep else None)
+        nf = 7 if scaledep else 4
+        fld = ops.full((7, mine.shape[0]), 0.0, torch.float64)
+        bespoke = ops.pitch(N) > 0 and os.environ.get("SHQ_SLAB_TORCH_FFT", "0") != "1"
+        (self._loop_bespoke if bespoke else self._loop_torch)(mine, fld, nf)
+        # ---- the particle loop, the two maxima, and the way back along the same counts: no key travels
+        pos_out, vel, disp, mx = ops.finalize(mine, fld, scaledep, float(params.vel_prefac), L)
+        mx = c.allreduce_max_vec(np.asarray(mx, dtype=np.float64))
+        back, _ = self._a2a(torch.cat([pos_out, vel, disp, fld[0][:, None]], dim=1).contiguous(), rcounts)
+        res = np.empty((n, 10))
+        res[order.cpu().numpy()] = back.cpu().numpy()
+        return dict(Pos=res[:, 0:3].copy(), Vel=res[:, 3:6].copy(), Disp=res[:, 6:9].copy(), Density=res[:, 9].copy(), maxdisp=float(mx[0]),
+                    maxvel=float(mx[1]))
+
+    def _neighbour_plane(self, ext, nxl):
+        """the right-hand neighbour's first plane behind the own ones: one shift to the left"""
+        if self.comm.size > 1:
+            ext[nxl] = self._shift(ext[0:1].contiguous(), -1)[0]
+
+    def _loop_bespoke(self, pos, fld, nf):
+        """The library's own FFT passes (csrc/fft3d.hip).  Per field: the transfer pass out of place on the kept y-slab, ONE
+        all-to-all, the Y/Z inverse from the packed buffer, the neighbour's plane, the gather.  Field f + 1's pass is queued before
+        field f's exchange is waited for."""
+        c, ops, N, L, P, nxl, plane0 = self.comm, self.ops, self.N, self.L, self.comm.size, self.d.nxl, self.d.plane0
+        zp = ops.pitch(N)
+        nyl, y0 = N // P, c.rank * (N // P)
+        widths, multi, spec = self.d.widths, c.multi, self._spec
+        nalloc = N if P == 1 else nxl + 1
+        ext = ops.full((nalloc, N, zp), 0.0, torch.float64)
+        own = ext[:nxl]
+
+        def start(f):
+            out = torch.empty_like(spec)
+            ops.xtransfer(N, L, spec, out, y0, nyl, f)
+            return self._a2a(out, widths, [nxl] * P)                                             # rows [src q][x_l]
+
+        pend = start(0) if multi else None
+        for f in range(nf):
+            if multi:
+                packed = pend.wait().contiguous()
+                pend = start(f + 1) if f + 1 < nf else None
+                ops.fft_yz(N, own, nxl, packed, P)
+            else:       # the planes land where the Y/Z inverse takes them
+                ops.xtransfer(N, L, spec, own.view(torch.complex128), y0, nyl, f)
+                ops.fft_yz(N, own, nxl, None, 1)
+            self._neighbour_plane(ext, nxl)
+            ops.gather(N, L, pos, ext, plane0, nxl, fld[f])
+
+    def _loop_torch(self, pos, fld, nf):
+        """The same loop with torch.fft for mesh sizes without a bespoke transform, and on the CPU stand-in: the field is kept as
+        [x][y_l][z'], x slowest, dense."""
+        c, ops, N, L, P, nxl, plane0 = self.comm, self.ops, self.N, self.L, self.comm.size, self.d.nxl, self.d.plane0
+        Nc, nyl, y0 = N // 2 + 1, N // P, c.rank * (N // P)
+        spec = self._spec if self._spec.shape[2] == Nc else self._spec[:, :, :Nc].contiguous()
+        nalloc = N if P == 1 else nxl + 1
+        ext = ops.full((nalloc, N, N + 2), 0.0, torch.float64)
+        for f in range(nf):
+            out = torch.fft.ifft(ops.transfer(N, L, spec, y0, nyl, f), dim=0, norm="forward").contiguous()   # rows = x planes, in order
+            recv, _ = self._a2a(out, self.d.widths)                                                          # rows [src q][x_l]
+            sp = recv.reshape(P, nxl, nyl, Nc).permute(1, 0, 2, 3).reshape(nxl, N, Nc)
+            ext[:nxl, :, :N] = torch.fft.irfft2(sp, s=(N, N), dim=(1, 2), norm="forward")                    # unscaled
+            self._neighbour_plane(ext, nxl)
+            ops.gather(N, L, pos, ext, plane0, nxl, fld[f])
+
+
+class GpuZeldovichOps:
+    """DistZeldovich's phases on the device library (shq_zeldovich_slab_*), on torch tensors of the context's device."""
+
+    def __init__(self, ctx, device=None):
+        self.ctx = ctx
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self._hand = _StreamHandover(ctx, self.device)
+
+    def _call(self, fn, *args):
+        self._hand.before()
+        capi.check(fn(self.ctx.h, *args), fn.__name__)
+        self._hand.after()
+
+    @staticmethod
+    def _p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
+    def full(self, shape, value, dtype):
+        return torch.full(shape, value, dtype=dtype, device=self.device)
+
+    def pitch(self, N):
+        return int(capi.hip.shq_zeldovich_slab_pitch(int(N)))
+
+    def fill(self, N, Seed, unitary, invert, y0, nyl):
+        spec = torch.empty((N, nyl, self.pitch(N) // 2 or N // 2 + 1), dtype=torch.complex128, device=self.device)
+        self._call(capi.hip.shq_zeldovich_slab_fill, N, Seed, unitary, invert, y0, nyl, self._p(spec))
+        return spec
+
+    def tables(self, N, L, delta, growth):
+        self._call(capi.hip.shq_zeldovich_slab_tables, N, L, capi.ptr(delta), capi.ptr(growth))
+
+    def xtransfer(self, N, L, spec, out, y0, nyl, field):
+        assert spec.is_contiguous() and out.is_contiguous() and out.dtype == spec.dtype == torch.complex128 and out.shape == spec.shape
+        self._call(capi.hip.shq_zeldovich_slab_xtransfer, N, L, self._p(spec), self._p(out), y0, nyl, field)
+
+    def transfer(self, N, L, spec, y0, nyl, field):
+        assert spec.is_contiguous() and spec.dtype == torch.complex128 and spec.shape == (N, nyl, N // 2 + 1)
+        out = torch.empty_like(spec)
+        self._call(capi.hip.shq_zeldovich_slab_transfer, N, L, self._p(spec), self._p(out), y0, nyl, field)
+        return out
+
+    def fft_yz(self, N, planes, nplanes, packed, nranks):
+        assert planes.is_contiguous() and (packed is None or (packed.is_contiguous() and packed.dtype == torch.complex128))
+        self._call(capi.hip.shq_zeldovich_slab_fft_yz, N, self._p(planes), nplanes, self._p(packed), nranks)
+
+    def gather(self, N, L, pos, window, plane0, nxl, out):
+        assert pos.is_contiguous() and window.is_contiguous() and out.is_contiguous() and window.dtype == out.dtype == torch.float64
+        assert window.shape[1:] == (N, self.pitch(N) or N + 2)
+        self._call(capi.hip.shq_zeldovich_slab_gather, N, L, self._p(pos), pos.shape[0], self._p(window), plane0, nxl, window.shape[0], self._p(out))
+
+    def finalize(self, pos, fld, scaledep, vel_prefac, L):
+        n = pos.shape[0]
+        assert pos.is_contiguous() and fld.is_contiguous() and fld.shape == (7, n)
+        out = [torch.empty((n, 3), dtype=torch.float64, device=self.device) for _ in range(3)]
+        mx = (C.c_double * 2)()
+        self._call(capi.hip.shq_zeldovich_slab_finalize, n, self._p(pos), self._p(fld), int(scaledep), vel_prefac, L, *[self._p(o) for o in out],
+                   C.byref(mx))
+        return out[0], out[1], out[2], list(mx)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
