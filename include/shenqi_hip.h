@@ -758,7 +758,7 @@ int shq_set_walk_stats(shq_context *ctx, int level);
  * what the chip holds at once; 2 persistent waves for every launch.  leaf_ring: 1 (default) leaf particles go through the
  * wave-private LDS ring of the persistent walk, 0 they are evaluated as the leaf is opened (the reference's summation order). */
 int shq_set_walk_launch(shq_context *ctx, int persist, int leaf_ring);
-/* The production launch (persistent waves + leaf ring, relative criterion) does not enter a subtree that at most eight of a wave's 64
+/* The production launch (persistent waves + leaf ring, relative criterion) does not enter a subtree that at most twelve (SHQ_SPARSE_LANES; eight before DESIGN 3.1 round 7) of a wave's 64
  * lanes open: it notes it, and a second kernel walks the noted subtrees with one lane per (target, node) pair: the
  * same interaction sets, a different order of the sum (forces to 1e-13 of the largest).  On by default; 0 (or SHQ_WALK_SPARSE=0)
  * makes the main walk enter every subtree itself.  A test / tuning knob like shq_set_walk_launch.
@@ -782,6 +782,12 @@ int shq_set_walk_overlap(shq_context *ctx, int mode);
 int shq_set_walk_addr(shq_context *ctx, int mode);
 int shq_walk_last_addr(shq_context *ctx, int *mode);
 int shq_walk_addr32_fits(int64_t numnodes);
+/* The pair kernel has a 32-bit form of its own (scalar base + 32-bit lane offset for node records, the leaf-ordered particle copy and the
+ * wave's pair stack), taken under the same knob where all three fit.  shq_pair_addr32_fits: the rule on numbers alone: 1 if
+ * shq_walk_addr32_fits(numnodes), leaf_slots slots of 32 bytes and stack_cap stack entries of 16 bytes all end at or below 2^32.
+ * shq_walk_last_pair_addr: 1 if the last pair kernel launched took that form.  Same pairs, same order: results equal bit for bit. */
+int shq_pair_addr32_fits(int64_t numnodes, int64_t leaf_slots, int64_t stack_cap);
+int shq_walk_last_pair_addr(shq_context *ctx, int *mode);
 /* The pair kernel's failures are STICKY and loud (the reference checks every launch and ends the run, treewalk2.cuh:351-353).
  *  - A pair stack that ran full dropped pairs: the accelerations of that launch are incomplete.  The error word stays up on the device
  *    whatever is launched afterwards; a copy follows every launch to pinned host memory, and shq_synchronize, every *_download,

@@ -456,6 +456,10 @@ hip.shq_walk_last_addr.argtypes = [_vp, C.POINTER(C.c_int)]
 hip.shq_walk_last_addr.restype = C.c_int
 hip.shq_walk_addr32_fits.argtypes = [C.c_int64]
 hip.shq_walk_addr32_fits.restype = C.c_int
+hip.shq_pair_addr32_fits.argtypes = [C.c_int64, C.c_int64, C.c_int64]
+hip.shq_pair_addr32_fits.restype = C.c_int
+hip.shq_walk_last_pair_addr.argtypes = [_vp, C.POINTER(C.c_int)]
+hip.shq_walk_last_pair_addr.restype = C.c_int
 hip.shq_pm_set_fft_transposed.argtypes = [_vp, C.c_int]
 hip.shq_pm_set_fft_transposed.restype = C.c_int
 hip.shq_walk_pair_status.argtypes = [_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]

@@ -345,6 +345,13 @@ extern "C" int shq_walk_last_addr(shq_context *ctx, int *mode)
     return SHQ_OK;
 }
 
+extern "C" int shq_walk_last_pair_addr(shq_context *ctx, int *mode)
+{
+    SHQ_CHECK(ctx && mode, SHQ_ERR_INVALID, "null argument");
+    *mode = ctx->last_pair_addr32 ? 1 : 0;
+    return SHQ_OK;
+}
+
 extern "C" int shq_walk_pair_lean(shq_context *ctx)
 {
     SHQ_CHECK(ctx, SHQ_ERR_INVALID, "null context");

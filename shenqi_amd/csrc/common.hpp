@@ -520,6 +520,7 @@ struct shq_context {
     int walk_overlap = 1;             /* SHQ_WALK_OVERLAP: the pair kernel beside the main walk (second stream) instead of behind it */
     int walk_addr = 1;                /* SHQ_WALK_ADDR / shq_set_walk_addr: node records at 32-bit byte offsets where shq_walk_addr32_fits (0: never) */
     bool last_walk_addr32 = false;    /* the last exact launch fetched its records that way */
+    bool last_pair_addr32 = false;    /* the last pair kernel launched took its 32-bit form (shq_pair_addr32_fits) */
     bool sp_check_pending = false;
     int xcd_k = 32;            /* SHQ_XCD_K: blocks per XCD chunk in the remap (0 = off); 32 measured best (2 %) */
     float last_walk_ms = 0;

@@ -202,8 +202,10 @@ __device__ __forceinline__ void leaf_particle(const double4 *__restrict__ tab, c
 /* constant address space on the device pass; the host pass only parses the kernels */
 #if defined(__HIP_DEVICE_COMPILE__)
 #define SHQ_CONSTANT_AS __attribute__((address_space(4)))
+#define SHQ_GLOBAL_AS __attribute__((address_space(1)))
 #else
 #define SHQ_CONSTANT_AS
+#define SHQ_GLOBAL_AS
 #endif
 typedef const SHQ_CONSTANT_AS WalkArgs *WalkArgsK;
 __device__ __forceinline__ WalkArgsK walk_cold_args()
@@ -247,7 +249,8 @@ __device__ __forceinline__ int walk_next_task(WalkArgsK c, int &region, int &tri
  * last bits of the sums).  tools/walk_defer_sim.py: leaf rounds 340 -> 219 per wave (64^3 S-cluster) at 32 slots. */
 #define SHQ_LEAF_RING 32
 #ifndef SHQ_SPARSE_LANES
-#define SHQ_SPARSE_LANES 8     /* a subtree entered by at most this many lanes goes to the pair kernel */
+#define SHQ_SPARSE_LANES 12    /* a subtree entered by at most this many lanes goes to the pair kernel (8 until the pair kernel's
+                                  instruction diet of round 7 made a pair cheap enough for 12: DESIGN 3.1) */
 #endif
 #ifndef SHQ_SPARSE_CAP
 #define SHQ_SPARSE_CAP 96      /* ... while the task has a free slot (31.7 per task on average at 256^3) */
@@ -743,7 +746,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_num_sgpr(96), amdgpu_num
 
 /* ---- the sparse subtrees: one lane per (target, node) pair ---------------------------------------------------------------
  * A wave of the main walk spends a node visit's ~45 vector instructions whether 64 or 3 of its lanes are awake, and the subtrees
- * that at most eight lanes enter are 21 % of its visits and 27 % of its monopole rounds for 2.4 % of the interactions.  Here a wave
+ * that at most eight lanes enter are 21 % of its visits and 27 % of its monopole rounds for 2.4 % of the interactions (the hand-over
+ * threshold is SHQ_SPARSE_LANES, twelve since round 7).  Here a wave
  * takes ONE task's noted subtrees (same 64 targets, target slot = lane of the main walk) and keeps a stack of pairs {node, end,
  * slot}: it pops 64, every lane loads ITS node's record, tests it against ITS target with the reference's expressions
  * (gravshort2.hpp:152-193, the same code path as the main walk: identical decisions), evaluates it on accept into the target's LDS
@@ -770,7 +774,10 @@ __device__ __forceinline__ int lean_level(double rootlen, double len) { return (
 
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wpass-failed"
-template <bool POT, int WAVES>
+/* A32: stack entries, node records and leaf particles are addressed as a scalar base and an unsigned 32-bit byte offset per lane (the
+ * form of the global loads and stores that takes the base from scalar registers), instead of a 64-bit address formed per lane and access.
+ * Selected at launch where every offset fits: shq_pair_addr32_fits. */
+template <bool POT, int WAVES, bool A32>
 __device__ __forceinline__ void grav_pair_body(const WalkArgs &a)
 {
     /* the workgroup's waves share one window table: 52 KB per workgroup of eight waves, two of them per CU (behind the walk); 34 KB per
@@ -801,13 +808,38 @@ __device__ __forceinline__ void grav_pair_body(const WalkArgs &a)
     double4 *const tgt = tgt_all[wv];
     double(*const acc)[64] = acc_all[wv];
     int *const cntl = cnt_all[wv];
-    int4 *const stack = a.sp_stack + ((size_t) blockIdx.x * WAVES + wv) * (size_t) a.sp_stack_cap;
+    /* the wave's slot is wave-uniform: said so, its stack's base stays in scalar registers */
+    const int wslot = __builtin_amdgcn_readfirstlane((int) (blockIdx.x * WAVES + wv));
+    int4 *const stack = a.sp_stack + (size_t) wslot * (size_t) a.sp_stack_cap;
+    auto stk = [&](int i) -> int4 & {
+        if constexpr(A32)
+            return *reinterpret_cast<int4 *>(reinterpret_cast<char *>(stack) + ((unsigned) i << 4));
+        else
+            return stack[i];
+    };
+    /* A32: the two bases a source is fetched from, once in vector registers (the select between them takes vector operands: left in
+     * scalar registers, each select is preceded by a move) */
+    unsigned nb_lo = 0, nb_hi = 0, lb_lo = 0, lb_hi = 0;
+    if constexpr(A32) {
+        asm volatile("v_mov_b32 %0, %1" : "=v"(nb_lo) : "s"((unsigned) (size_t) a.nodeG));
+        asm volatile("v_mov_b32 %0, %1" : "=v"(nb_hi) : "s"((unsigned) ((size_t) a.nodeG >> 32)));
+        asm volatile("v_mov_b32 %0, %1" : "=v"(lb_lo) : "s"((unsigned) (size_t) a.posm_leaf));
+        asm volatile("v_mov_b32 %0, %1" : "=v"(lb_hi) : "s"((unsigned) ((size_t) a.posm_leaf >> 32)));
+    }
+    auto rec = [&](int i) -> const NodeG * {
+        if constexpr(A32)
+            return reinterpret_cast<const NodeG *>(reinterpret_cast<const char *>(a.nodeG) + ((unsigned) i << 7));
+        else
+            return a.nodeG + i;
+    };
     int sp_high = 0;
     int mopped = 0;
-    const unsigned long long below = (1ull << lane) - 1ull;
+    /* set bits of a vote below this lane: v_mbcnt_lo / _hi on the scalar mask, two instructions and no lane-mask register pair */
+    auto below = [](unsigned long long m) { return (int) __builtin_amdgcn_mbcnt_hi((unsigned) (m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) m, 0u)); };
     /* tasks in a fixed stride over the resident waves, and ONE set of tallies per wave at the end: a returning atomic on one word
      * completes ~88 times per microsecond chip-wide and three no-return ones on one line take ~12 ns each (MI355X_MICROARCH.md) —
-     * per task that was 10 ms for this kernel, whatever it did in between */
+     * per task that was 10 ms for this kernel, whatever it did in between.  The tallies stay lane-local over the wave's tasks (lane l: the
+     * targets of slot l) and are reduced across the lanes once, behind the task loop */
     long long w_sum = 0, w_min = 0x7fffffffffffll, w_max = 0;
     /* live (beside the main walk): the next task in order from one counter — the main walk finishes its tasks roughly in order, 9 per
      * microsecond, and only one of this kernel's workgroups fits a CU beside it: the others start when it ends and share what is left */
@@ -818,16 +850,19 @@ __device__ __forceinline__ void grav_pair_body(const WalkArgs &a)
                 k = atomicAdd(a.sp_task, 1u);
             return (long long) (unsigned) __builtin_amdgcn_readfirstlane((int) k);
         }
-        return prev < 0 ? (long long) blockIdx.x * WAVES + wv : prev + (long long) gridDim.x * WAVES;
+        return prev < 0 ? (long long) wslot : prev + (long long) gridDim.x * WAVES;
     };
     for(long long task = next_task(-1); task < a.nwaves; task = next_task(task)) {
         const long long t = task * 64 + lane;
         const bool valid = t < a.ntargets;
         const long long pi = valid ? (a.targets ? (long long) a.targets[t] : t) : -1;
         const bool have = pi >= 0;
-        int cnt = agent_load(&a.sp_count[task]);
+        /* one word for the whole wave: read back as a scalar at every load, so that the stack pointer that follows from it, the batch
+         * sizes and every vote below stay in scalar registers (left per lane, the compiler takes `cnt > 0` for a lane condition and
+         * keeps everything that depends on it in vector registers, the masks included) */
+        int cnt = __builtin_amdgcn_readfirstlane(agent_load(&a.sp_count[task]));
         if(a.sp_mop) {
-            if(__builtin_amdgcn_readfirstlane(cnt) == SP_TASK_DONE)
+            if(cnt == SP_TASK_DONE)
                 continue;
             mopped++;
         }
@@ -836,9 +871,8 @@ __device__ __forceinline__ void grav_pair_body(const WalkArgs &a)
              * flag; the bound only keeps a broken launch from hanging the card: ~4 s, then the error flag) */
             for(unsigned spin = 0; cnt < 0 && spin < a.sp_spin_max; spin++) {
                 __builtin_amdgcn_s_sleep(32);
-                cnt = agent_load(&a.sp_count[task]);
+                cnt = __builtin_amdgcn_readfirstlane(agent_load(&a.sp_count[task]));
             }
-            cnt = __builtin_amdgcn_readfirstlane(cnt);
             if(cnt < 0) {
                 if(lane == 0)
                     agent_store(a.sp_flags + SP_GAVEUP, 1);
@@ -871,7 +905,7 @@ __device__ __forceinline__ void grav_pair_body(const WalkArgs &a)
                     const unsigned long long m = ((unsigned long long) (unsigned) __builtin_amdgcn_readlane(mine.w, k) << 32) |
                                                  (unsigned) __builtin_amdgcn_readlane(mine.z, k);
                     if((m >> lane) & 1ull)
-                        stack[sp + __popcll(m & below)] = make_int4(ix, iy, lane, 0);
+                        stk(sp + below(m)) = make_int4(ix, iy, lane, 0);
                     sp += __popcll(m);
                 }
             }
@@ -882,45 +916,55 @@ __device__ __forceinline__ void grav_pair_body(const WalkArgs &a)
          * batches' records the next, where a batch at a time made them two trips per 64 pairs - the kernel waits for memory, not for
          * arithmetic, and beside the main walk it has one wave per SIMD and registers to spare (128 fit behind the main walk's 6 x 64).
          * Batch A's records are requested first, so its evaluation starts while B's are still on their way. */
+        /* Which lanes hold a pair, which of these a node, and what each lane pushes are carried as the votes themselves (scalar masks),
+         * not as per-lane defaults: a lane without a pair re-reads the batch's last pair and a lane without a node reads record 0 (same
+         * lines, valid indices), every lane runs the test on whatever it holds, and only the stores, the LDS atomics and the pushes are
+         * under a lane condition - the vote read back.  No field is set for a lane that does not use it, and no load sits in a masked
+         * region that its join would have to wait for. */
         struct PairLd {
             int node, end, slot, kind;
+            unsigned long long livem, nodem; /* lanes with a pair; those whose pair is a node */
+            int nidx;                        /* the node's record, record 0 for every other lane */
             double4 src;
             double cx, cy, cz, len;
             int nsib, nchild, ntype, ncount;
         };
         struct PairOut {
-            int push_sib, push_child, child_end, leaf0, leafn;
+            unsigned long long sibm, childm, leafm; /* lanes that push nsib / nchild (end: nsib) / the leaf's particles nchild .. + ncount */
         };
         auto pair_pop = [&](int base, int np, PairLd &p) {
-            p.node = -1, p.end = -1, p.slot = 0, p.kind = 0;
-            if(lane < np) {
-                const int4 pr = stack[base + lane];
-                p.node = pr.x, p.end = pr.y, p.slot = pr.z, p.kind = pr.w;
-            }
+            const int4 pr = stk(base + (lane < np ? lane : np - 1));
+            p.node = pr.x, p.end = pr.y, p.slot = pr.z, p.kind = pr.w;
+            p.livem = shq_ballot(lane < np);
         };
         /* ONE body for both kinds of pair: a node record begins with {cofm, mass}, which is what a leaf particle's record is, so the
          * source is one load from either array and the rest of a node's record is requested right behind it */
         auto pair_fetch = [&](PairLd &p) {
-            p.src = make_double4(0, 0, 0, 0);
-            p.cx = p.cy = p.cz = p.len = 0;
-            p.nsib = -1, p.nchild = -1, p.ntype = 0, p.ncount = 0;
-            if(p.node >= 0) {
-                const double4 *const sp4 = p.kind == 1 ? a.posm_leaf + p.node : reinterpret_cast<const double4 *>(a.nodeG + p.node);
+            const bool isn = p.kind == 0;
+            p.nodem = shq_ballot(isn) & p.livem;
+            p.nidx = isn ? p.node : 0;
+            if constexpr(A32) { /* one select of the base (from the copies in vector registers), one of the record's size */
+                const unsigned long long b = ((unsigned long long) (isn ? nb_hi : lb_hi) << 32) | (isn ? nb_lo : lb_lo);
+                p.src = *reinterpret_cast<const SHQ_GLOBAL_AS double4 *>(b + ((unsigned) p.node << (isn ? 7 : 5)));
+            } else {
+                const double4 *const sp4 = isn ? reinterpret_cast<const double4 *>(a.nodeG + p.node) : a.posm_leaf + p.node;
                 p.src = *sp4;
-                if(p.kind == 0) {
-                    const NodeG *const nd = a.nodeG + p.node;
-                    p.len = nd->len;
-                    p.cx = nd->center[0], p.cy = nd->center[1], p.cz = nd->center[2];
-                    p.nsib = nd->sibling, p.nchild = nd->child, p.ntype = nd->type, p.ncount = nd->count;
-                }
+            }
+            if(p.nodem != 0ull) { /* wave-uniform: a batch of leaf particles alone requests nothing more */
+                const NodeG *const nd = rec(p.nidx);
+                p.len = nd->len;
+                p.cx = nd->center[0], p.cy = nd->center[1], p.cz = nd->center[2];
+                p.nsib = nd->sibling, p.nchild = nd->child, p.ntype = nd->type, p.ncount = nd->count;
             }
         };
         auto pair_eval = [&](const PairLd &p, PairOut &o) {
-            o.push_sib = -1, o.push_child = -1, o.child_end = -1, o.leaf0 = 0, o.leafn = 0;
-            double ax = 0, ay = 0, az = 0, pot = 0;
-            const bool live = p.node >= 0, isnode = live && p.kind == 0;
-            double wraplim = 0, rcut2 = 0, rcuthl = 0, mlen2 = 0, bhlim = 0, inside = 0;
-            if(isnode) {
+            o.sibm = o.childm = o.leafm = 0ull;
+            const unsigned long long partm = p.livem & ~p.nodem; /* leaf particles */
+            const double4 tg = tgt[p.slot];
+            double dx = p.src.x - tg.x, dy = p.src.y - tg.y, dz = p.src.z - tg.z;
+            double ux, uy, uz, cmax, wraplim, rcut2, rcuthl, mlen2, bhlim, inside;
+            unsigned long long nwrapm = 0ull;
+            if(p.nodem != 0ull) {
                 if(lean) {
                     /* this kernel is bound by the 16-byte pieces its lanes fetch from 64 different lines (a second record's worth of
                      * loads per pair: 3.5 -> 5.8 ms), not by arithmetic: the second half of the record - products of {mass, len} and
@@ -930,86 +974,132 @@ __device__ __forceinline__ void grav_pair_body(const WalkArgs &a)
                     const LeanProducts lp = lean_products(p.src.w, p.len, a.rcut, a.Box);
                     rcuthl = lp.rcuthl, mlen2 = lp.mlen2, inside = lp.inside, wraplim = lp.wraplim, rcut2 = a.rcut2;
                     bhlim = bh_lvl[lean_level(rootlen, p.len) & 31];
+                    /* pinned here: merged with the whole-record form's load below into one load through a generic pointer, it counts as
+                     * a memory load, and waiting for it waits for batch B's records behind it as well */
+                    asm volatile("" : "+v"(bhlim));
                 } else {
-                    const NodeG *const nd = a.nodeG + p.node;
+                    const NodeG *const nd = rec(p.nidx);
                     bhlim = nd->bhlim, mlen2 = nd->mlen2, inside = nd->inside, rcut2 = nd->rcut2, wraplim = nd->wraplim, rcuthl = nd->rcuthl;
                 }
-            }
-            const double4 tg = tgt[p.slot];
-            double dx = p.src.x - tg.x, dy = p.src.y - tg.y, dz = p.src.z - tg.z;
-            double ux = p.cx - tg.x, uy = p.cy - tg.y, uz = p.cz - tg.z;
-            double cmax = fmax(fmax(fabs(ux), fabs(uy)), fabs(uz));
-            /* the wrap is the identity on every component it is not needed for: applying it per lane gives the main walk's bits.  A
-             * leaf particle is always wrapped (gravshort2.hpp:290-304), a node unless it is interior (sign bit of wraplim) */
-            const bool nwrap = isnode && __double2hiint(wraplim) >= 0 && cmax >= wraplim;
-            if(nwrap || (live && !isnode)) {
-                dx = wrapd(dx, a.Box, a.invBox);
-                dy = wrapd(dy, a.Box, a.invBox);
-                dz = wrapd(dz, a.Box, a.invBox);
-            }
-            if(nwrap) {
-                ux = wrapd(ux, a.Box, a.invBox);
-                uy = wrapd(uy, a.Box, a.invBox);
-                uz = wrapd(uz, a.Box, a.invBox);
+                ux = p.cx - tg.x, uy = p.cy - tg.y, uz = p.cz - tg.z;
                 cmax = fmax(fmax(fabs(ux), fabs(uy)), fabs(uz));
+                /* the wrap is the identity on every component it is not needed for: applying it per lane gives the main walk's bits.  A
+                 * leaf particle is always wrapped (gravshort2.hpp:290-304), a node unless it is interior (sign bit of wraplim) */
+                nwrapm = shq_ballot(__double2hiint(wraplim) >= 0) & shq_ballot(cmax >= wraplim) & p.nodem;
             }
-            const double r2 = dx * dx + dy * dy + dz * dz;
-            bool ev = live && !isnode;
-            if(isnode) {
-                const bool keep = !(r2 > rcut2 && cmax > rcuthl);
-                const bool open = (!a.useBH && mlen2 > r2 * r2 * tg.w) || r2 < bhlim || cmax < inside;
-                ev = keep && !open;
-                if(keep && open) {
-                    if(p.ntype == SHQ_NODE_NODE_TYPE) {
-                        o.push_child = p.nchild;
-                        o.child_end = p.nsib;
-                    } else if(p.ntype == SHQ_PARTICLE_NODE_TYPE) { /* its particles become pairs of their own: one per lane and batch */
-                        o.leaf0 = p.nchild;
-                        o.leafn = p.ncount;
+            const unsigned long long dwrapm = nwrapm | partm;
+            if(dwrapm != 0ull) {
+                if(__builtin_amdgcn_inverse_ballot_w64(dwrapm)) {
+                    dx = wrapd(dx, a.Box, a.invBox);
+                    dy = wrapd(dy, a.Box, a.invBox);
+                    dz = wrapd(dz, a.Box, a.invBox);
+                }
+            }
+            /* the contraction `dx * dx + dy * dy + dz * dz` had compiled to in every instantiation of this kernel, pinned: the order is the
+             * compiler's choice and changed with the code around it (the trap of round 5, here with y first) */
+            const double r2 = fma(dz, dz, fma(dx, dx, dy * dy));
+            unsigned long long evm = partm;
+            if(p.nodem != 0ull) {
+                if(nwrapm != 0ull) {
+                    if(__builtin_amdgcn_inverse_ballot_w64(nwrapm)) {
+                        ux = wrapd(ux, a.Box, a.invBox);
+                        uy = wrapd(uy, a.Box, a.invBox);
+                        uz = wrapd(uz, a.Box, a.invBox);
+                        cmax = fmax(fmax(fabs(ux), fabs(uy)), fabs(uz));
                     }
                 }
-                if(p.nsib != p.end && p.nsib >= 0)
-                    o.push_sib = p.nsib;
+                /* every vote is one compare and the votes are joined on the scalar side: a vote on `a && b` is compiled as both compares, a
+                 * lane flag made of their conjunction and a third compare on the flag */
+                const unsigned long long keepm = p.nodem & ~(shq_ballot(r2 > rcut2) & shq_ballot(cmax > rcuthl));
+                unsigned long long openm = shq_ballot(r2 < bhlim) | shq_ballot(cmax < inside);
+                if(!a.useBH)
+                    openm |= shq_ballot(mlen2 > r2 * r2 * tg.w);
+                const unsigned long long kopenm = keepm & openm;
+                evm |= keepm & ~openm;
+                if(kopenm != 0ull) {
+                    o.childm = kopenm & shq_ballot(p.ntype == SHQ_NODE_NODE_TYPE);
+                    o.leafm = kopenm & shq_ballot(p.ntype == SHQ_PARTICLE_NODE_TYPE); /* its particles become pairs of their own: one per lane and batch */
+                }
+                o.sibm = p.nodem & shq_ballot(p.nsib != p.end) & shq_ballot(p.nsib >= 0);
             }
-            if(ev) { /* CLAMP for the particle that is the target itself; a no-op on an accepted node's r^2 */
-                apply_accn<POT, true>(tab, dx, dy, dz, r2, p.src.w, a, ax, ay, az, pot);
-                atomicAdd(&acc[0][p.slot], ax);
-                atomicAdd(&acc[1][p.slot], ay);
-                atomicAdd(&acc[2][p.slot], az);
-                if(POT)
-                    atomicAdd(&acc[3][p.slot], pot);
-                atomicAdd(&cntl[p.slot], 1);
+            if(evm != 0ull) {
+                if(__builtin_amdgcn_inverse_ballot_w64(evm)) { /* CLAMP for the particle that is the target itself; a no-op on an accepted node's r^2 */
+                    double ax = 0, ay = 0, az = 0, pot = 0;
+                    apply_accn<POT, true>(tab, dx, dy, dz, r2, p.src.w, a, ax, ay, az, pot);
+                    atomicAdd(&acc[0][p.slot], ax);
+                    atomicAdd(&acc[1][p.slot], ay);
+                    atomicAdd(&acc[2][p.slot], az);
+                    if(POT)
+                        atomicAdd(&acc[3][p.slot], pot);
+                    atomicAdd(&cntl[p.slot], 1);
+                }
             }
         };
-        auto push_nodes = [&](int what, int what_end, int slot) {
-            const unsigned long long m = shq_ballot(what >= 0);
-            if(what >= 0)
-                stack[sp + __popcll(m & below)] = make_int4(what, what_end, slot, 0);
-            sp += __popcll(m);
+        auto push_nodes = [&](unsigned long long m, int what, int what_end, int slot) {
+            if(m != 0ull) {
+                if(__builtin_amdgcn_inverse_ballot_w64(m))
+                    stk(sp + below(m)) = make_int4(what, what_end, slot, 0);
+                sp += __popcll(m);
+            }
         };
         /* a leaf's particles: the lane's first slot is the prefix sum of the counts below it, formed from the votes on the four
-         * bits of the count (count <= 8) instead of one vote per particle */
-        auto push_leaves = [&](int leaf0, int leafn, int slot) {
-            if(shq_ballot(leafn > 0) != 0ull) {
-                const unsigned long long b0 = shq_ballot((leafn & 1) != 0), b1 = shq_ballot((leafn & 2) != 0),
-                                         b2 = shq_ballot((leafn & 4) != 0), b3 = shq_ballot((leafn & 8) != 0);
-                const int off = __popcll(b0 & below) + 2 * __popcll(b1 & below) + 4 * __popcll(b2 & below) + 8 * __popcll(b3 & below);
-                for(int k = 0; k < SHQ_NMAXCHILD; k++) {
-                    if(shq_ballot(k < leafn) == 0ull)
-                        break;
-                    if(k < leafn)
-                        stack[sp + off + k] = make_int4(leaf0 + k, -1, slot, 1);
+         * bits of the count (count <= 8) instead of one vote per particle.  The same votes say which lanes have a k-th particle
+         * (gk: count > k), so the stores need no vote of their own: straight-line masked stores that end at the largest count present */
+        auto push_leaves = [&](unsigned long long m, int leaf0, int leafn, int slot) {
+            if(m != 0ull) {
+                const unsigned long long b0 = m & shq_ballot((leafn & 1) != 0), b1 = m & shq_ballot((leafn & 2) != 0),
+                                         b2 = m & shq_ballot((leafn & 4) != 0), b3 = m & shq_ballot((leafn & 8) != 0);
+                const int at = sp + below(b0) + 2 * below(b1) + 4 * below(b2) + 8 * below(b3);
+                /* A32: the lane's first slot as one byte offset, the k-th particle's 16 bytes further on in the store's immediate */
+                const unsigned atb = (unsigned) at << 4;
+                auto put = [&](unsigned long long g, int k) {
+                    if(__builtin_amdgcn_inverse_ballot_w64(g)) {
+                        if constexpr(A32)
+                            *reinterpret_cast<int4 *>(reinterpret_cast<char *>(stack) + ((size_t) atb + 16u * (unsigned) k)) = make_int4(leaf0 + k, -1, slot, 1);
+                        else
+                            stk(at + k) = make_int4(leaf0 + k, -1, slot, 1);
+                    }
+                };
+                const unsigned long long g1 = b3 | b2 | b1, g0 = g1 | b0, g2 = b3 | b2 | (b1 & b0), g3 = b3 | b2, g4 = b3 | (b2 & (b1 | b0)), g5 = b3 | (b2 & b1),
+                                         g6 = b3 | (b2 & b1 & b0), g7 = b3;
+                if(g0 != 0ull) {
+                    put(g0, 0);
+                    if(g1 != 0ull) {
+                        put(g1, 1);
+                        if(g2 != 0ull) {
+                            put(g2, 2);
+                            if(g3 != 0ull) {
+                                put(g3, 3);
+                                if(g4 != 0ull) {
+                                    put(g4, 4);
+                                    if(g5 != 0ull) {
+                                        put(g5, 5);
+                                        if(g6 != 0ull) {
+                                            put(g6, 6);
+                                            if(g7 != 0ull)
+                                                put(g7, 7);
+                                        }
+                                    }
+                                }
+                            }
+                        }
+                    }
                 }
                 sp += __popcll(b0) + 2 * __popcll(b1) + 4 * __popcll(b2) + 8 * __popcll(b3);
             }
         };
         while(sp > 0) {
+            sp = __builtin_amdgcn_readfirstlane(sp); /* wave-uniform by construction; said here, the batch sizes and the votes stay scalar */
             const int npa = sp < 64 ? sp : 64;
             sp -= npa;
             const int npb = SHQ_PAIR_DEPTH2 ? (sp < 64 ? sp : 64) : 0;
             sp -= npb;
             PairLd pa, pb;
             PairOut oa, ob;
+            /* scalar zeros for the masks of an absent batch B: left undefined, they meet the votes in vector registers at the join and
+             * take the stack pointer and every prefix count with them */
+            pb.livem = pb.nodem = 0ull;
+            ob.sibm = ob.childm = ob.leafm = 0ull;
             pair_pop(sp + npb, npa, pa);
             if(npb > 0)
                 pair_pop(sp, npb, pb);
@@ -1020,15 +1110,15 @@ __device__ __forceinline__ void grav_pair_body(const WalkArgs &a)
             if(npb > 0)
                 pair_eval(pb, ob);
             /* siblings first, then children, leaf particles on top: the stack stays depth-bounded */
-            push_nodes(oa.push_sib, pa.end, pa.slot);
+            push_nodes(oa.sibm, pa.nsib, pa.end, pa.slot);
             if(npb > 0)
-                push_nodes(ob.push_sib, pb.end, pb.slot);
-            push_nodes(oa.push_child, oa.child_end, pa.slot);
+                push_nodes(ob.sibm, pb.nsib, pb.end, pb.slot);
+            push_nodes(oa.childm, pa.nchild, pa.nsib, pa.slot);
             if(npb > 0)
-                push_nodes(ob.push_child, ob.child_end, pb.slot);
-            push_leaves(oa.leaf0, oa.leafn, pa.slot);
+                push_nodes(ob.childm, pb.nchild, pb.nsib, pb.slot);
+            push_leaves(oa.leafm, pa.nchild, pa.ncount, pa.slot);
             if(npb > 0)
-                push_leaves(ob.leaf0, ob.leafn, pb.slot);
+                push_leaves(ob.leafm, pb.nchild, pb.ncount, pb.slot);
             sp_high = sp > sp_high ? sp : sp_high;
             if(sp > a.sp_stack_cap - 1280) { /* never seen (SP_HIGHWATER is reported); loud and sticky if it happens: the pairs are dropped */
                 if(lane == 0) {
@@ -1054,21 +1144,20 @@ __device__ __forceinline__ void grav_pair_body(const WalkArgs &a)
                 nint += (long long) cntl[lane];
                 a.nint[pi] = (int32_t) nint;
             }
+            w_sum += nint;
+            w_min = nint < w_min ? nint : w_min;
+            w_max = nint > w_max ? nint : w_max;
         }
-        long long mn = have ? nint : 0x7fffffffffffll, mx = have ? nint : 0, sm = have ? nint : 0;
-        for(int off = 32; off > 0; off >>= 1) {
-            const long long o1 = __shfl_xor(mn, off), o2 = __shfl_xor(mx, off), o3 = __shfl_xor(sm, off);
-            mn = o1 < mn ? o1 : mn;
-            mx = o2 > mx ? o2 : mx;
-            sm += o3;
-        }
-        w_sum += sm;
-        w_min = mn < w_min ? mn : w_min;
-        w_max = mx > w_max ? mx : w_max;
         /* the task is through: a second pass (the mop-up behind a live kernel that gave up somewhere) must not add its sums again */
         if(lane == 0)
             agent_store(&a.sp_count[task], (int32_t) SP_TASK_DONE);
         __builtin_amdgcn_wave_barrier();
+    }
+    for(int off = 32; off > 0; off >>= 1) {
+        const long long o1 = __shfl_xor(w_min, off), o2 = __shfl_xor(w_max, off), o3 = __shfl_xor(w_sum, off);
+        w_min = o1 < w_min ? o1 : w_min;
+        w_max = o2 > w_max ? o2 : w_max;
+        w_sum += o3;
     }
     if(lane == 0 && a.stats) {
         atomicAdd(&a.stats->ninteractions, (unsigned long long) w_sum);
@@ -1088,10 +1177,31 @@ __device__ __forceinline__ void grav_pair_body(const WalkArgs &a)
 /* One register budget for both launch forms, 128 (waves_per_eu(4, 4) is there for the budget it implies): beside the main walk (workgroups
  * of four waves, one per SIMD) that is what is left of a SIMD's 512 registers behind the main walk's six waves of 64; behind it (workgroups
  * of eight waves, two per CU) the two batches per round need it as well.  The same code in both: the same sums in the same order. */
-template <bool POT> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void grav_pair_kernel_live(const WalkArgs a) { grav_pair_body<POT, 4>(a); }
-template <bool POT> __global__ __launch_bounds__(64 * SHQ_PAIR_WAVES) __attribute__((amdgpu_waves_per_eu(SHQ_PAIR_EU, SHQ_PAIR_EU))) void grav_pair_kernel(const WalkArgs a)
+template <bool POT, bool A32> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void grav_pair_kernel_live(const WalkArgs a)
 {
-    grav_pair_body<POT, SHQ_PAIR_WAVES>(a);
+    grav_pair_body<POT, 4, A32>(a);
+}
+template <bool POT, bool A32>
+__global__ __launch_bounds__(64 * SHQ_PAIR_WAVES) __attribute__((amdgpu_waves_per_eu(SHQ_PAIR_EU, SHQ_PAIR_EU))) void grav_pair_kernel(const WalkArgs a)
+{
+    grav_pair_body<POT, SHQ_PAIR_WAVES, A32>(a);
+}
+/* both launch forms of the pair kernel, by potential and address form */
+void launch_pair(bool live_form, bool pot, bool a32, dim3 grid, hipStream_t st, const WalkArgs &a)
+{
+    if(live_form) { /* workgroups of four waves, one per SIMD: 6 x 64 registers of the main walk + 128 */
+        const dim3 b(256);
+        if(pot)
+            a32 ? grav_pair_kernel_live<true, true><<<grid, b, 0, st>>>(a) : grav_pair_kernel_live<true, false><<<grid, b, 0, st>>>(a);
+        else
+            a32 ? grav_pair_kernel_live<false, true><<<grid, b, 0, st>>>(a) : grav_pair_kernel_live<false, false><<<grid, b, 0, st>>>(a);
+    } else {
+        const dim3 b(64 * SHQ_PAIR_WAVES);
+        if(pot)
+            a32 ? grav_pair_kernel<true, true><<<grid, b, 0, st>>>(a) : grav_pair_kernel<true, false><<<grid, b, 0, st>>>(a);
+        else
+            a32 ? grav_pair_kernel<false, true><<<grid, b, 0, st>>>(a) : grav_pair_kernel<false, false><<<grid, b, 0, st>>>(a);
+    }
 }
 
 #pragma clang diagnostic pop
@@ -1239,6 +1349,14 @@ bool launch_variant(int stats, bool persist, dim3 grid, dim3 block, hipStream_t 
 /* The 32-bit form of the walk's record fetch reaches byte (cur << 7) + 0x70 + 15 of the pool through an unsigned 32-bit offset register
  * and an immediate: every record of a pool of numnodes + 1 records (cur <= numnodes) must start below 2^32, i.e. numnodes + 1 <= 2^25. */
 extern "C" int shq_walk_addr32_fits(int64_t numnodes) { return (numnodes >= 0 && numnodes + 1 <= ((int64_t) 1 << 25)) ? 1 : 0; }
+/* The pair kernel's 32-bit form shifts an index into an unsigned 32-bit byte offset from three scalar bases: a node record (128 bytes; the
+ * rule above), a slot of the leaf-ordered particle copy (32 bytes: leaf_slots slots end at leaf_slots << 5) and an entry of the wave's own
+ * pair stack (16 bytes: stack_cap entries end at stack_cap << 4; the wave's base is added on the scalar side).  Every end must be <= 2^32. */
+extern "C" int shq_pair_addr32_fits(int64_t numnodes, int64_t leaf_slots, int64_t stack_cap)
+{
+    const int64_t reach = (int64_t) 1 << 32;
+    return (shq_walk_addr32_fits(numnodes) != 0 && leaf_slots >= 0 && leaf_slots <= (reach >> 5) && stack_cap >= 0 && stack_cap <= (reach >> 4)) ? 1 : 0;
+}
 
 void shq_launch_stats_init(shq_context *ctx) { stats_init_kernel<<<1, 1, 0, ctx->stream>>>(ctx->gstats.ptr); }
 
@@ -1639,15 +1757,11 @@ int shq_launch_grav_walk(shq_context *ctx, const shq_grav_params *p, const int32
         if(live)
             SHQ_HIP(hipStreamWaitEvent(ps, ctx->ev_pair_fork, 0));
         const dim3 pg((unsigned) pair_blocks);
-        if(live) { /* workgroups of four waves, one per SIMD: 6 x 64 registers of the main walk + 80 */
-            if(update_potential)
-                grav_pair_kernel_live<true><<<pg, dim3(256), 0, ps>>>(a);
-            else
-                grav_pair_kernel_live<false><<<pg, dim3(256), 0, ps>>>(a);
-        } else if(update_potential)
-            grav_pair_kernel<true><<<pg, dim3(64 * SHQ_PAIR_WAVES), 0, ps>>>(a);
-        else
-            grav_pair_kernel<false><<<pg, dim3(64 * SHQ_PAIR_WAVES), 0, ps>>>(a);
+        /* the pair kernel's own 32-bit form: its records, the leaf copy and a wave's stack must all lie within reach of the offset */
+        /* (the leaf copy of THIS tree, ntreeparts slots and its padding: the buffer's capacity is that of the largest tree the context has held) */
+        const bool pair32 = ctx->walk_addr != 0 && shq_pair_addr32_fits(ctx->numnodes, ctx->ntreeparts + SHQ_NMAXCHILD, a.sp_stack_cap) != 0;
+        ctx->last_pair_addr32 = pair32;
+        launch_pair(live, update_potential != 0, pair32, pg, ps, a);
         SHQ_HIP(hipGetLastError());
         if(live) {
             SHQ_HIP(hipEventRecord(ctx->ev_pair_join, ps));
@@ -1659,10 +1773,7 @@ int shq_launch_grav_walk(shq_context *ctx, const shq_grav_params *p, const int32
             m.sp_live = 0;
             m.sp_mop = 1;
             const dim3 mg((unsigned) mop_blocks);
-            if(update_potential)
-                grav_pair_kernel<true><<<mg, dim3(64 * SHQ_PAIR_WAVES), 0, ctx->stream>>>(m);
-            else
-                grav_pair_kernel<false><<<mg, dim3(64 * SHQ_PAIR_WAVES), 0, ctx->stream>>>(m);
+            launch_pair(false, update_potential != 0, pair32, mg, ctx->stream, m);
             SHQ_HIP(hipGetLastError());
         }
         /* the sticky words follow every launch to pinned host memory: the entry points read them there without a round trip */
