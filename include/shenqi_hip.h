@@ -2126,6 +2126,69 @@ int shq_glass_setup_positions(int Ngrid, double BoxSize, double shift, int seed,
 /* Host only: powerspectrum_sum's tail (powerspectrum.cpp:71-87) on one step's raw sums, in place: bins without modes removed, the others
  * Power / Nmodes / Norm * BoxSize_in_MPC^3 and kk / Nmodes * 2 pi / BoxSize_in_MPC, moved to the front.  *nonzero: how many remain. */
 int shq_glass_finish_power(int size, double BoxSize_in_MPC, double *kk, double *power, int64_t *nmodes, double norm, int *nonzero);
+/* Host only: setup_glass's loop for ONE task's sub-block of the lattice (idgen_init, zeldovich.cpp:46-87): x in [offset[0], offset[0] +
+ * size[0]), y in [offset[1], offset[1] + size[1]), every z, in the index order of idgen_create_pos_from_index (x slowest, z fastest),
+ * three draws per particle from one serial mt19937(seed).  The reference seeds every task with seed + ThisTask: the caller passes that
+ * sum.  offset = {0, 0} and size = {Ngrid, Ngrid} give the bits of shq_glass_setup_positions.  pos: out [size[0] size[1] Ngrid][3]. */
+int shq_glass_setup_positions_block(int Ngrid, double BoxSize, double shift, int seed, const int offset[2], const int size[2], double *pos);
+
+/* ---- Glass making on several ranks (shenqi_amd/dist.py, DistGlass): the phases of shq_glass_evolve as entry points of their own, with
+ * the caller's exchanges between them.  The reference runs glass_evolve on every task through petapm_force and all-reduces
+ * glass_stats' and _prepare's sums (glass.cpp:150-172, 219-258).
+ *
+ * Every pointer named d_ is DEVICE memory of the caller; nothing is uploaded or downloaded but the tables, the outside-the-window flag
+ * and the two statistics sums.  The density's int64 deposit, its (y, z) half spectrum and a force's real mesh live on the rank's x planes,
+ * [nalloc][Nmesh][zp] of 8 bytes, zp = shq_glass_slab_pitch(Nmesh) or, for a mesh size without a bespoke transform (pitch 0), Nmesh + 2.
+ * The spectrum lives on the rank's y-slab, the mesh rows y0 <= y < y0 + nyl: d_spec = [Nmesh][nyl][zp / 2] complex, x slowest (dense with
+ * Nmesh / 2 + 1 without a bespoke transform).  The window of a rank is its own planes from plane0 on and one more plane behind them,
+ * nalloc = nplanes + 1: the deposit's ghost plane, or the right-hand neighbour's first plane for the gather; one rank alone has plane0 =
+ * 0 and nalloc = nplanes = Nmesh, the periodic mesh.  A particle belongs to the window that holds its CIC base plane
+ * (shq_glass_slab_planes): floor(Pos / CellSize) modulo Nmesh with cic.hpp's own arithmetic, so that a position whose quotient rounds up
+ * to Nmesh is plane 0 and a negative one folds as the kernels fold it.
+ * None of these calls reads or writes the PM's state (mesh, deposit scale, type mask, twiddles, pending spectrum, prestarted PM), the
+ * one-rank resident Zel'dovich field or the Zel'dovich slab family's tables: twiddles, tables, flag and sums are the family's own.  They
+ * run on the context's stream; tables, deposit, gather and particles return synchronised, the others only launch.
+ *
+ *   shq_glass_slab_tables    fac[i] = -diff_kernel(k_i 2 pi / Nmesh) * (Nmesh / BoxSize), 1 / sinc^2 per mesh index, the bin of every
+ *                            k2 and pot_factor = pow(2 pi / BoxSize, -2) / totmass, in shq_glass_evolve's expressions, kept on the
+ *                            device until the next call.  totmass is the sum over ALL ranks
+ *   shq_glass_slab_planes    d_planes[p] = the int32 base plane of particle p
+ *   shq_glass_slab_deposit   zeroes the window, then the CIC deposit of d_pos = double[n][3] (unwrapped) times double(d_mass[p]) as
+ *                            int64 with the scale 2^(61 - exp): exp is frexp's exponent of the total mass of ALL ranks, so that every
+ *                            rank count deposits the same integers.  A particle whose base plane is not one of the rank's own is
+ *                            SHQ_ERR_INVALID; it deposits nothing, and nothing is ever written outside the window
+ *   shq_glass_slab_fft_yz    direction 0: the int64 planes (worth 2^(exp - 61) per unit) to the (y, z) half spectrum; 1: back to real
+ *                            space.  d_packed (NULL: in place) is the all-to-all buffer [nranks][nplanes][Nmesh / nranks][zp / 2]
+ *                            complex the Y pass writes (0) or reads (1)
+ *   shq_glass_slab_xforward  the X forward of the y-slab in place.  With d_sums = double[3 Nmesh + 1] - power[Nmesh], kk[Nmesh],
+ *                            nmodes[Nmesh] (uint64), norm - both of the reference's additions are ADDED to it as the tile is stored
+ *                            (the caller zeroes it): measure_power_spectrum's with the deconvolution weight and potential_transfer's
+ *                            with weight 1 (glass.cpp:304), per mode the operations of the one-rank call.  Only the slab with y = 0
+ *                            writes norm.  The spectrum has the same bits with and without sums
+ *   shq_glass_slab_xtransfer per mode value *= pot_factor * (1.0 / k2) * f * f (f = 1), the zero mode 0, then (-v.y fa, v.x fa) with
+ *                            fa = fac[index along axis], fused into the X inverse and stored OUT OF PLACE into d_out of d_spec's
+ *                            shape; d_spec is only read and serves all three axes.  Pad columns z' > Nmesh / 2 are stored as 0
+ *   shq_glass_slab_power, shq_glass_slab_transfer   the same sums and the same factor on a dense slab [Nmesh][nyl][Nmesh / 2 + 1],
+ *                            between the caller's own X transforms (d_out may be d_spec)
+ *   shq_glass_slab_gather    d_disp[3 p + axis] = the float gather of d_mesh (doubles) with the eight roundings in connection order.
+ *                            A particle with a corner outside the window is SHQ_ERR_INVALID and is not written
+ *   shq_glass_slab_particles one step boundary per particle (the second kick of the step that ends with glass_stats' two terms if
+ *                            `ending`, the first kick and the drift of the step that begins if `beginning`); sums = this rank's
+ *                            {sum Disp^2, sum Vel^2} (0, 0 without `ending`)
+ * SHQ_ERR_STATE from xforward with sums, xtransfer, power and transfer without tables of this Nmesh. */
+int shq_glass_slab_pitch(int Nmesh);
+int shq_glass_slab_tables(shq_context *ctx, int Nmesh, double BoxSize, double totmass);
+int shq_glass_slab_planes(shq_context *ctx, int Nmesh, double BoxSize, const void *d_pos, int64_t n, void *d_planes);
+int shq_glass_slab_deposit(shq_context *ctx, int Nmesh, double BoxSize, const void *d_pos, const void *d_mass, int64_t n, int exp, int plane0,
+                           int nplanes, int nalloc, void *d_mesh);
+int shq_glass_slab_fft_yz(shq_context *ctx, int Nmesh, void *d_planes, int nplanes, int direction, int exp, void *d_packed, int nranks);
+int shq_glass_slab_xforward(shq_context *ctx, int Nmesh, void *d_spec, int y0, int nyl, void *d_sums);
+int shq_glass_slab_xtransfer(shq_context *ctx, int Nmesh, const void *d_spec, void *d_out, int y0, int nyl, int axis);
+int shq_glass_slab_power(shq_context *ctx, int Nmesh, const void *d_spec, int y0, int nyl, void *d_sums);
+int shq_glass_slab_transfer(shq_context *ctx, int Nmesh, const void *d_spec, void *d_out, int y0, int nyl, int axis);
+int shq_glass_slab_gather(shq_context *ctx, int Nmesh, double BoxSize, const void *d_pos, int64_t n, const void *d_mesh, int plane0, int nplanes,
+                          int nalloc, void *d_disp, int axis);
+int shq_glass_slab_particles(shq_context *ctx, int64_t n, void *d_pos, void *d_vel, const void *d_disp, int ending, int beginning, double sums[2]);
 
 /* ---- Thermal velocities (add_thermal_speeds with init_rng and init_thermalvel, libgenic/thermal.cpp:44-110, as genic/main.cpp:162-187
  * calls them for warm dark matter and main.cpp:215-228 for neutrino particles) ----  one rank's sub-block of the Ngrid^3 lattice.

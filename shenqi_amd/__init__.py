@@ -863,6 +863,17 @@ def glass_setup_positions(Ngrid, BoxSize, shift=0.0, seed=0):
     return pos
 
 
+def glass_setup_positions_block(Ngrid, BoxSize, shift, seed, offset, size):
+    """setup_glass's loop for one task's sub-block of the lattice (host only): x in [offset[0], offset[0] + size[0]), y likewise, every z,
+    in idgen_create_pos_from_index's order - an IDGenerator's offset and size.  The reference seeds task ThisTask with seed + ThisTask:
+    pass that sum.  [size[0] * size[1] * Ngrid][3]"""
+    off, sz = (C.c_int * 2)(int(offset[0]), int(offset[1])), (C.c_int * 2)(int(size[0]), int(size[1]))
+    pos = np.zeros((max(sz[0], 0) * max(sz[1], 0) * int(Ngrid), 3))
+    capi.check(capi.hip.shq_glass_setup_positions_block(int(Ngrid), float(BoxSize), float(shift), int(seed), C.byref(off), C.byref(sz), capi.ptr(pos)),
+               "glass_setup_positions_block")
+    return pos
+
+
 def glass_finish_power(BoxSize_in_MPC, kk, power, nmodes, norm):
     """powerspectrum_sum's tail (powerspectrum.cpp:71-87) on one step's raw sums: (kk, power, nmodes) of the non-empty bins"""
     kk, power = np.array(kk, dtype=np.float64), np.array(power, dtype=np.float64)

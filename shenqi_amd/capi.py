@@ -888,6 +888,21 @@ hip.shq_glass_setup_positions.argtypes = [C.c_int, C.c_double, C.c_double, C.c_i
 hip.shq_glass_setup_positions.restype = C.c_int
 hip.shq_glass_finish_power.argtypes = [C.c_int, C.c_double, _vp, _vp, _vp, C.c_double, C.POINTER(C.c_int)]
 hip.shq_glass_finish_power.restype = C.c_int
+hip.shq_glass_setup_positions_block.argtypes = [C.c_int, C.c_double, C.c_double, C.c_int, C.POINTER(C.c_int * 2), C.POINTER(C.c_int * 2), _vp]
+hip.shq_glass_setup_positions_block.restype = C.c_int
+hip.shq_glass_slab_pitch.argtypes = [C.c_int]
+hip.shq_glass_slab_tables.argtypes = [_vp, C.c_int, C.c_double, C.c_double]
+hip.shq_glass_slab_planes.argtypes = [_vp, C.c_int, C.c_double, _vp, C.c_int64, _vp]
+hip.shq_glass_slab_deposit.argtypes = [_vp, C.c_int, C.c_double, _vp, _vp, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, _vp]
+hip.shq_glass_slab_fft_yz.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int]
+hip.shq_glass_slab_xforward.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp]
+hip.shq_glass_slab_xtransfer.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int]
+hip.shq_glass_slab_power.argtypes = [_vp, C.c_int, _vp, C.c_int, C.c_int, _vp]
+hip.shq_glass_slab_transfer.argtypes = [_vp, C.c_int, _vp, _vp, C.c_int, C.c_int, C.c_int]
+hip.shq_glass_slab_gather.argtypes = [_vp, C.c_int, C.c_double, _vp, C.c_int64, _vp, C.c_int, C.c_int, C.c_int, _vp, C.c_int]
+hip.shq_glass_slab_particles.argtypes = [_vp, C.c_int64, _vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(C.c_double * 2)]
+for _f in ("pitch", "tables", "planes", "deposit", "fft_yz", "xforward", "xtransfer", "power", "transfer", "gather", "particles"):
+    getattr(hip, "shq_glass_slab_" + _f).restype = C.c_int
 
 THERMAL_NKNOTS = 2000
 

@@ -246,6 +246,7 @@ extern "C" void shq_shutdown(shq_context *ctx)
     ctx->mesh_words = 0; ctx->mesh_zeroed = false; ctx->mesh_alt.release();
     ctx->zel_spec.release(); ctx->zel_have = false;
     ctx->zels_tw.release(); ctx->zels_tabs.release(); ctx->zels_flag.release(); ctx->zels_mx.release();
+    ctx->gls_tw.release(); ctx->gls_tabs.release(); ctx->gls_stats.release(); ctx->gls_bin.release(); ctx->gls_flag.release();
     ctx->yld_tab.release(); ctx->yld_time.release(); ctx->yld_in.release(); ctx->yld_out.release(); ctx->yld_i32.release(); ctx->yld_mark.release();
     ctx->cool_ion.release(); ctx->cool_rates.release(); ctx->cool_metal.release(); ctx->cool_zreion.release(); ctx->cool_d.release(); ctx->cool_i.release();
     ctx->cool_b.release(); ctx->cool_cnt.release();

@@ -213,7 +213,7 @@ struct shq_fft_plan {
         unsigned res_z = 0, res_s = 0, res_x = 0, res_x3 = 0, res_x4 = 0, res_x5 = 0;
     } t; /* transposing pipeline */
     struct {
-        unsigned res_zf = 0, res_zi = 0, res_s = 0, res_x3 = 0, res_x4 = 0, res_x5 = 0, res_x6 = 0;
+        unsigned res_zf = 0, res_zi = 0, res_s = 0, res_x3 = 0, res_x4 = 0, res_x5 = 0, res_x6 = 0, res_x7 = 0, res_x8 = 0;
     } n; /* in-place pipeline */
 };
 
@@ -575,6 +575,14 @@ struct shq_context {
     double zels_box = 0;                  /* the BoxSize the density table was made for */
     /* ---- glass making (glass.hip): a call allocates and frees its own device buffers; only its times stay behind */
     double glass_ms[4] = {0, 0, 0, 0};    /* shq_glass_phase_ms */
+    /* the slab phases (shq_glass_slab_*): twiddles of their own, the tables of shq_glass_slab_tables - fac[N], then 1 / sinc^2 [N] in
+     * gls_tabs, the bin of every k2 in gls_bin - the outside-the-window flag and the two statistics sums */
+    DevBuf<double> gls_tw, gls_tabs, gls_stats;
+    DevBuf<int32_t> gls_bin;
+    DevBuf<int> gls_flag;
+    int gls_tw_n = 0, gls_tabs_n = 0;
+    double gls_box = 0, gls_totmass = 0;  /* what the tables were made for */
+    double gls_pot_factor = 0;            /* pow(2 pi / BoxSize, -2) / totmass */
     /* ---- thermal velocities (thermal.hip): a call allocates and frees its own device buffers; only its times stay behind */
     double thermal_ms[3] = {0, 0, 0};     /* shq_thermal_phase_ms */
     /* ---- stellar yields (yields.hip): the caller's tables of shq_yields_init and the per-call work arrays */
@@ -686,6 +694,10 @@ enum shq_fft_stage {
                                   modefac[k2 & fac_mask], then the X inverse into the y-slab `out`; d_mesh is only read */
     SHQ_FFT_X_ZEL,             /* from a kept Gaussian field the Zel'dovich transfer of one field (zel_transfer_mode with
                                   modefac[k2], zel_axis, zel_c0), then the X inverse into the y-slab `out`; d_mesh is only read */
+    SHQ_FFT_X_GLASS_FORWARD,   /* the X forward of the glass's density, the spectrum left in place; with ps both of the reference's
+                                  power additions (deconvolved and with weight 1) as the tile is stored: needs sinctab and bintab */
+    SHQ_FFT_X_GLASS,           /* from that kept spectrum the glass's potential and force transfer of one axis (pot_factor, the
+                                  per-index factors modefac[N], zel_axis = the axis), then the X inverse into the y-slab `out` */
 };
 /* what the transposing pipeline runs between d_mesh and a scratch mesh of the same size */
 enum shq_fft_part {
@@ -707,7 +719,7 @@ struct shq_fft_opts {
     const double *tw = nullptr;       /* the caller's own twiddles of N (shq_fft3d_fill_twiddles): the context's are left alone */
     double *out = nullptr;            /* T_FILTER: where the Z inverse writes; X_FILTER: the y-slab the X inverse writes */
     int ncell = 1;                    /* T_FILTER, X_FILTER: the int N^3 every mode is divided by */
-    int zel_axis = -1;                /* X_ZEL: -1 the density transfer, 0 / 1 / 2 the gradient along x / y / z */
+    int zel_axis = -1;                /* X_ZEL: -1 the density transfer, 0 / 1 / 2 the gradient along x / y / z; X_GLASS: 0 / 1 / 2 */
     double zel_c0 = 0;                /* X_ZEL: 1 / (2 pi) / sqrt(BoxSize) */
 };
 

@@ -464,8 +464,8 @@ struct GreenArgs {
     const int32_t *bintab = nullptr;
     double *ps = nullptr;
     int ncell = 1; /* MODE 5: the int N^3 every mode is divided by (uvbg.cpp:211-215 divide_by_ncell) */
-    double2 *out = nullptr; /* fft_pass_strided MODES 5, 6: the y-slab the result is stored into, laid out as the one it reads */
-    int zel_axis = -1;      /* fft_pass_strided MODE 6: zel_transfer_mode's axis and c0 */
+    double2 *out = nullptr; /* fft_pass_strided MODES 5, 6, 8: the y-slab the result is stored into, laid out as the one it reads */
+    int zel_axis = -1;      /* fft_pass_strided MODE 6: zel_transfer_mode's axis and c0; MODE 8: the axis of the glass's force */
     double zel_c0 = 0;
 };
 
@@ -491,6 +491,28 @@ __device__ __forceinline__ void pk_add(double *hist, const GreenArgs &ga, double
     atomicAdd(&hist[2 * N + kint], w);
 }
 
+/* Both power additions of a glass force (glass.hip, glass_power_kernel: the same operations per mode) into a workgroup's LDS histogram
+ * [3][N]: measure_power_spectrum's with the deconvolution weight and potential_transfer's with weight 1 (glass.cpp:304), same bins. */
+template <int N>
+__device__ __forceinline__ void glass_pk_add(double *hist, const GreenArgs &ga, double2 v, int x, int y, int z, int k2)
+{
+    if(z > N / 2)
+        return;
+    const double m = v.x * v.x + v.y * v.y;
+    if(k2 == 0) {
+        ga.ps[3 * N] = m; /* Norm: both callers write the same value */
+        return;
+    }
+    const int kint = ga.bintab[k2];
+    if(kint >= N)
+        return;
+    const double f = ga.sinctab[x] * ga.sinctab[y] * ga.sinctab[z];
+    const double w = (z == 0 || z == N / 2) ? 1.0 : 2.0;
+    atomicAdd(&hist[kint], w * m * f * f + w * m);
+    atomicAdd(&hist[N + kint], 2 * (w * sqrt((double) k2)));
+    atomicAdd(&hist[2 * N + kint], 2 * w);
+}
+
 /* PK 0: in place.  PK 1: results stored into ga.alt in the packed (send) layout.  PK 2: input loaded from ga.alt in that layout.
  * The X pass of a y-slab split for a caller that needs the density spectrum between its halves (shq_pm_slab2_xforward / _xfinish):
  *   MODE 3: X forward, the spectrum written back in place; with ga.ps the P(k) sums of the density as the tile is stored.  y = ga.y0 +
@@ -504,7 +526,13 @@ __device__ __forceinline__ void pk_add(double *hist, const GreenArgs &ga, double
  *   MODE 6: the Zel'dovich transfer of one field on a y-slab (zeldovich.hip), MODE 5 with another factor: reads a tile of the kept
  *           Gaussian field, every mode becomes zel_transfer_mode(v, k2, k_axis, axis, T[k2], c0) - the one-rank kernel's function -
  *           then X inverse, stored out of place into ga.out.  A pad column (z > N / 2) passes as it is.
- * MODES 3, 4 with ga.ps keep a P(k) histogram [3][N] in LDS behind the tables (3 N doubles more), flushed once per workgroup. */
+ *   MODE 7: the X forward of a glass force's density on a y-slab (glass.hip), MODE 3 with the glass's sums: with ga.ps both power
+ *           additions of the reference per mode (glass_pk_add) as the tile is stored.  The spectrum's bits do not depend on ga.ps.
+ *   MODE 8: the glass's potential and force transfer of one axis on a y-slab, the sibling of MODE 6: reads a tile of the kept density
+ *           spectrum, every mode becomes v * (pot_factor * (1.0 / k2) * f * f) with f = 1, the zero mode 0, then (-v.y fa, v.x fa)
+ *           with fa = ga.modefac[index along ga.zel_axis] (N entries, held in LDS where MODE 2 keeps its factors) - the operations of
+ *           glass_transfer_kernel - then X inverse, stored out of place into ga.out.  A pad column (z > N / 2) is stored as 0.
+ * MODES 3, 4, 7 with ga.ps keep a P(k) histogram [3][N] in LDS behind the tables (3 N doubles more), flushed once per workgroup. */
 template <int N, int MODE, int PK = 0>
 __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const long long es, const long long outer_stride,
                                                           const int ntiles, const int ntot, const double2 *__restrict__ W,
@@ -524,10 +552,15 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
         }
     /* MODES 3, 4 with ga.ps: the histogram behind the tables; the barrier after the first tile lands orders the zeroing */
     double *hist = MODE == 4 ? gax + N : gax;
-    const bool pk = (MODE == 3 || MODE == 4) && ga.ps;
+    const bool pk = (MODE == 3 || MODE == 4 || MODE == 7) && ga.ps;
     if(pk)
         for(int i = threadIdx.x; i < 3 * N; i += FFT_T)
             hist[i] = 0;
+    if(MODE == 8) { /* the tile lands through this table, before the first barrier of the loop */
+        for(int i = threadIdx.x; i < N; i += FFT_T)
+            gax[i] = ga.modefac[i];
+        __syncthreads();
+    }
     /* XCD-chunked workgroup order: neighbouring column tiles share 128-byte lines (a tile row is 64
      * bytes), so they should run on the same XCD at about the same time and find the other half in its L2. */
     const unsigned vb = xcd_block(blockIdx.x, gridDim.x, xcdk);
@@ -620,6 +653,34 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
                     buf[(e % FFT_C) * LS + lx<N>(x)] = zel_transfer_mode(make_double2(prx[i], pry[i]), k2, ka, ga.zel_axis, tfac[i], ga.zel_c0);
                 }
             }
+        } else if(MODE == 8) {
+            /* potential_transfer and force_transfer (glass.cpp:285-342): products and a division, never contracted */
+#pragma clang fp contract(off)
+            const int y = ga.y0 + outer, z0 = tile * FFT_C;
+            const int ky = y <= N / 2 ? y : y - N;
+#pragma unroll
+            for(int i = 0; i < E; i++) {
+                const int e = threadIdx.x + i * FFT_T;
+                if(EXACT || e < FFT_C * N) {
+                    const int x = e / FFT_C, z = z0 + e % FFT_C;
+                    const int kx = x <= N / 2 ? x : x - N;
+                    const long long k2 = (long long) kx * kx + (long long) ky * ky + (long long) z * z;
+                    double2 v = make_double2(prx[i], pry[i]);
+                    if(k2 == 0 || z > N / 2)
+                        v = make_double2(0.0, 0.0);
+                    else {
+                        const double f = 1.0;
+                        const double smth = 1.0 / k2;
+                        const double pf = ga.pot_factor * smth * f * f;
+                        v.x *= pf;
+                        v.y *= pf;
+                    }
+                    const double fa = gax[ga.zel_axis == 0 ? x : (ga.zel_axis == 1 ? y : (z <= N / 2 ? z : 0))];
+                    const double tmp0 = -v.y * fa;
+                    const double tmp1 = v.x * fa;
+                    buf[(e % FFT_C) * LS + lx<N>(x)] = make_double2(tmp0, tmp1);
+                }
+            }
         } else {
 #pragma unroll
             for(int i = 0; i < E; i++) {
@@ -635,7 +696,7 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
         double2 *base_n = cm + (long long) outer_n * outer_stride + (long long) tile_n * FFT_C;
         double2 *abase_n = PK ? ga.alt + (long long) outer_n * ga.alt_outer + (long long) tile_n * FFT_C : nullptr;
         FFT_FETCH(base_n, abase_n)
-        if(MODE == 0 || MODE == 3)
+        if(MODE == 0 || MODE == 3 || MODE == 7)
             fft_lines<N, -1>(buf, Wl);
         if(MODE == 2) {
             /* potential_transfer, gravpm.cpp:378-444, applied as the forward transform stores its last
@@ -654,10 +715,10 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
             fft_lines<N, -1>(buf, Wl, green);
             fft_lines<N, +1>(buf, Wl);
         }
-        if(MODE == 1 || MODE == 4 || MODE == 5 || MODE == 6)
+        if(MODE == 1 || MODE == 4 || MODE == 5 || MODE == 6 || MODE == 8)
             fft_lines<N, +1>(buf, Wl);
         FFT_TFETCH(outer_n, tile_n)
-        if(MODE == 3) { /* the spectrum back in place; the density's P(k) on the way */
+        if(MODE == 3 || MODE == 7) { /* the spectrum back in place; the density's P(k) on the way (MODE 7: the glass's two additions) */
             const int y = ga.y0 + outer, z0 = tile * FFT_C;
             const int ky = y <= N / 2 ? y : y - N;
             for(int e = threadIdx.x; e < FFT_C * N; e += FFT_T) {
@@ -666,11 +727,14 @@ __global__ __launch_bounds__(FFT_T) void fft_pass_strided(double2 *cm, const lon
                 base[(long long) row * es + col] = v;
                 if(pk) {
                     const int kx = row <= N / 2 ? row : row - N;
-                    pk_add<N>(hist, ga, v, row, y, z0 + col, kx * kx + ky * ky + (z0 + col) * (z0 + col));
+                    if(MODE == 7)
+                        glass_pk_add<N>(hist, ga, v, row, y, z0 + col, kx * kx + ky * ky + (z0 + col) * (z0 + col));
+                    else
+                        pk_add<N>(hist, ga, v, row, y, z0 + col, kx * kx + ky * ky + (z0 + col) * (z0 + col));
                 }
             }
         } else {
-            double2 *ob = MODE == 5 || MODE == 6 ? ga.out + (base - cm) : base; /* MODES 5, 6: the same tile of the other y-slab */
+            double2 *ob = MODE == 5 || MODE == 6 || MODE == 8 ? ga.out + (base - cm) : base; /* MODES 5, 6, 8: the same tile of the other y-slab */
             for(int e = threadIdx.x; e < FFT_C * N; e += FFT_T) {
                 const int row = e / FFT_C, col = e - row * FFT_C;
                 if(PK == 1)
@@ -1214,6 +1278,8 @@ int run_n(shq_context *ctx, const double2 *W, double *d_mesh, int zp, shq_fft_st
         SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 4>, lds_hist}}, &p.res_x4));
         SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 5>, lds}}, &p.res_x5));
         SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 6>, lds}}, &p.res_x6));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 7>, lds_hist}}, &p.res_x7));
+        SHQ_TRY(fft_resident(ncu, FFT_T, {{fft_pass_strided<N, 8>, lds}}, &p.res_x8));
         SHQ_TRY(fft_resident(ncu, FFT_T,
                              {{fft_pass_strided<N, 0>, lds}, {fft_pass_strided<N, 1>, lds}, {fft_pass_strided<N, 2>, lds}, {fft_pass_strided<N, 0, 1>, lds},
                               {fft_pass_strided<N, 1, 2>, lds}},
@@ -1246,6 +1312,12 @@ int run_n(shq_context *ctx, const double2 *W, double *d_mesh, int zp, shq_fft_st
         break;
     case SHQ_FFT_X_ZEL:
         fft_pass_strided<N, 6><<<k.grid(stot, pl.res_x6), dim3(FFT_T), lds, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        break;
+    case SHQ_FFT_X_GLASS_FORWARD:
+        fft_pass_strided<N, 7><<<k.grid(stot, pl.res_x7), dim3(FFT_T), lds_split, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
+        break;
+    case SHQ_FFT_X_GLASS:
+        fft_pass_strided<N, 8><<<k.grid(stot, pl.res_x8), dim3(FFT_T), lds, s>>>(cm, (long long) nslab * zpc, zpc, ntiles, stot, W, ga, xcdk);
         break;
     case SHQ_FFT_YZ_FORWARD:
     case SHQ_FFT_YZ_FORWARD_PACKED:
@@ -1392,7 +1464,7 @@ int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, shq_fft_stage
                   double asmth2, double pot_factor, const shq_fft_opts &o)
 {
     const bool yslab = stage == SHQ_FFT_X_SOLVE || stage == SHQ_FFT_X_FORWARD_SUMS || stage == SHQ_FFT_X_FINISH || stage == SHQ_FFT_X_FILTER ||
-                       stage == SHQ_FFT_X_ZEL;
+                       stage == SHQ_FFT_X_ZEL || stage == SHQ_FFT_X_GLASS_FORWARD || stage == SHQ_FFT_X_GLASS;
     const bool packed = stage == SHQ_FFT_YZ_FORWARD_PACKED || stage == SHQ_FFT_YZ_INVERSE_PACKED;
     const int nslab = stage <= SHQ_FFT_SOLVE ? N : o.nslab;
     SHQ_CHECK(shq_fft3d_supported(N), SHQ_ERR_INVALID, "fft3d: unsupported mesh size %d", N);
@@ -1403,6 +1475,9 @@ int shq_fft3d_run(shq_context *ctx, double *d_mesh, int N, int zp, shq_fft_stage
               "fft3d: bad filter pass arguments");
     SHQ_CHECK(stage != SHQ_FFT_X_ZEL || (o.modefac && o.fac_mask == -1 && o.out && o.out != d_mesh && o.zel_axis >= -1 && o.zel_axis <= 2),
               SHQ_ERR_INVALID, "fft3d: bad transfer pass arguments");
+    SHQ_CHECK(stage != SHQ_FFT_X_GLASS_FORWARD || !o.ps || d_sinctab, SHQ_ERR_INVALID, "fft3d: the glass's sums need the sinc table");
+    SHQ_CHECK(stage != SHQ_FFT_X_GLASS || (o.modefac && o.out && o.out != d_mesh && o.zel_axis >= 0 && o.zel_axis <= 2), SHQ_ERR_INVALID,
+              "fft3d: bad glass transfer pass arguments");
     if(!o.tw)
         SHQ_TRY(ensure_twiddles(ctx, N));
     GreenArgs ga;

@@ -2391,6 +2391,363 @@ class GpuZeldovichOps:
         return out[0], out[1], out[2], list(mx)
 
 
+class _GlassState:
+    """the particles a rank owns during a resident glass loop: Pos f64 [m, 3], Vel f32 [m, 3], Mass f32 [m], the origin tag (rank,
+    index) as f64 [m, 2] (exact), and Disp f32 [m, 3], which every force writes here and which never travels"""
+
+    def __init__(self, rows, ops):
+        self.pos = rows[:, 0:3].contiguous()
+        self.vel = rows[:, 3:6].to(torch.float32).contiguous()
+        self.mass = rows[:, 6].to(torch.float32).contiguous()
+        self.tag = rows[:, 7:9].contiguous()
+        self.disp = ops.full((rows.shape[0], 3), 0.0, torch.float32)
+
+    def rows(self, sel):
+        """the travelling rows of the particles sel: one float64 row each; float Vel and Mass are exact in it"""
+        return torch.cat([self.pos[sel], self.vel[sel].to(torch.float64), self.mass[sel].to(torch.float64)[:, None], self.tag[sel]], dim=1)
+
+
+class DistGlass:
+    """glass_evolve (libgenic/glass.cpp:76-360) on x-slabs of the Nmesh mesh, one per rank: whole planes of equal width.  Nmesh must
+    be divisible by the rank count (equal y-slabs of the spectrum): otherwise the constructor raises ValueError on every rank, before
+    any collective.
+
+    The particles move between the nsteps + 1 forces of a call, so their state lives on the slab owners for the whole loop: a row -
+    Pos (3 f64), Vel (3 f32), Mass (f32) and an origin tag (rank, index) - sits with the owner of its CIC base plane, which the device
+    takes with the kernels' own cell arithmetic (ops.planes).  After every drift ONE all-to-all re-homes the rows whose base plane
+    changed owner, and only those; Disp is written on the owner by every force and read there by the next particle kernel, so it
+    does not travel.  At the end every row goes back to its origin by its tag.
+
+    One force: the zeroed window deposit (own planes and one behind) in fixed point with the exponent of the GLOBAL total mass, one
+    shift that adds the ghost plane into the right-hand neighbour's plane 0 as int64, Y/Z forward packed, one all-to-all, X forward
+    on the y-slab (both of the reference's power additions on the way when the step's spectrum is saved); then per axis the
+    potential and force transfer fused into the out-of-place X inverse, one all-to-all, Y/Z inverse from the packed buffer, the
+    neighbour's first plane by one shift, and the window gather into float Disp.  Axis a + 1's transfer pass is queued before axis
+    a's exchange is waited for.  Mesh sizes without a bespoke transform take the same steps with torch.fft.
+
+    The deposit adds integers and a mesh line sees the same kernel arithmetic on any rank, so on the bespoke route Pos, Vel and Disp
+    do not depend on the rank count or on who held which particle - provided totmass is the same double: it is the all-reduced sum
+    of the ranks' double sums of their float masses, which is independent of the rank count only when that sum is exact (it is for
+    setup_glass's equal masses up to 2^29 particles).  The statistics and spectrum sums are added in any order.
+
+    ops (GpuGlassOps below; the CPU tests use a numpy stand-in) works on torch tensors:
+      ops.pitch(N) -> doubles per z row of the bespoke passes, 0 without them;  ops.tables(N, L, totmass);
+      ops.planes(N, L, pos) -> int32 [m];  ops.deposit(N, L, pos, mass, exp, plane0, nxl, buf) into int64 [nalloc, N, pitch or N + 2];
+      ops.gather(N, L, pos, window, plane0, nxl, disp, axis);  ops.particles(pos, vel, disp, ending, beginning) -> [sum Disp^2, sum Vel^2];
+      bespoke route: ops.fft_yz(N, planes, nxl, direction, exp, packed, P), ops.xforward(N, spec, y0, nyl, sums or None),
+      ops.xtransfer(N, spec, out, y0, nyl, axis);
+      torch.fft route: ops.to_real(mesh_i, exp), ops.power(N, spec, y0, nyl, sums), ops.transfer(N, spec, y0, nyl, axis) -> a new tensor.
+      sums is float64 [3 N + 1]: power, kk, nmodes (int64 bits), norm; the ops add to it.
+    Counters of the last call: rows_sent (rows that left this rank in the opening routing), rehomed (per step the rows this rank sent
+    away after the drift: over the ranks they add up to the owner changes of that step) and nalltoall, the all-to-alls and shifts
+    started: 2 + nsteps + (nsteps + 1) * F with F = 4 on a one-rank group and 8 on several ranks - the opening routing and the
+    return, one re-homing per step, and per force the spectrum's exchange and three force exchanges, on several ranks also the ghost
+    shift and three neighbour-plane shifts.  (A lone process without a group has F = 0 on the bespoke route: its planes are the
+    y-slab already.)  The all-reduces - the opening vector, the statistics and the spectra at the end - are not counted.
+    Nothing here has run on more than one GPU."""
+
+    def __init__(self, comm, Nmesh, BoxSize, ops, bounds=None):
+        self.comm, self.ops, self.N, self.L = comm, ops, int(Nmesh), float(BoxSize)
+        self.d = SlabDecomp(comm, self.N, self.L, bounds)
+        if len(set(self.d.widths)) != 1:
+            raise ValueError("DistGlass needs slabs of equal width (got %s)" % (self.d.widths,))
+        self.rows_sent = self.nalltoall = 0
+        self.rehomed = []
+
+    def _a2a(self, send, send_counts, recv_counts=None):
+        self.nalltoall += 1
+        if recv_counts is None:
+            return self.comm.all_to_all_rows(send, send_counts)
+        return self.comm.all_to_all_rows_start(send, send_counts, recv_counts)
+
+    def _shift(self, t, direction):
+        self.nalltoall += 1
+        return self.comm.shift(t, direction)
+
+    def _refusal(self, pos, vel, mass, nsteps):
+        """what is wrong with this rank's input, or None: the checks of shq_glass_evolve"""
+        N, L, n = self.N, self.L, len(pos)
+        if not (4 <= N <= 2048 and N % 2 == 0):
+            return "glass: Nmesh must be even and in [4, 2048] (got %d)" % N
+        if nsteps < 0:
+            return "glass: nsteps %d < 0" % nsteps
+        if not (math.isfinite(L) and L > 0):
+            return "glass: BoxSize must be finite and > 0"
+        if pos.shape != (n, 3) or vel.shape != (n, 3) or mass.shape != (n,):
+            return "glass: pos and vel are [n][3], mass is [n]"
+        if n >= 2 ** 31:
+            return "glass: %d particles on one rank (< 2^31)" % n
+        if not np.isfinite(mass).all():
+            return "glass: non-finite mass"
+        if not np.isfinite(vel).all():
+            return "glass: non-finite velocity"
+        with np.errstate(invalid="ignore", over="ignore"):
+            if not (np.isfinite(pos).all() and (np.abs(pos / (L / N)) < 1073741824.0).all()):
+                return "glass: a position is not finite or beyond 2^30 cells"
+        return None
+
+    def _home(self, rows):
+        """rows (positions in columns 0 .. 2) to the owners of their CIC base planes; the block that stays is not copied through
+        the network.  Returns (the rows this rank owns now, how many left it)."""
+        c, ops = self.comm, self.ops
+        planes = ops.planes(self.N, self.L, rows[:, 0:3].contiguous())
+        owner = torch.div(planes, self.d.nxl, rounding_mode="floor").to(torch.int64)
+        order = torch.argsort(owner, stable=True)
+        counts = torch.bincount(owner, minlength=c.size).tolist()
+        got, _ = self._a2a(rows[order].contiguous(), counts)
+        return got.contiguous(), rows.shape[0] - counts[c.rank]
+
+    def _rehome(self, S):
+        """after a drift: the rows whose base plane changed owner travel in one all-to-all; the others stay where they are"""
+        c = self.comm
+        planes = self.ops.planes(self.N, self.L, S.pos)
+        owner = torch.div(planes, self.d.nxl, rounding_mode="floor").to(torch.int64)
+        away = owner != c.rank
+        idx = torch.nonzero(away).flatten()
+        dest = owner[idx]
+        order = torch.argsort(dest, stable=True)
+        counts = torch.bincount(dest, minlength=c.size).tolist()
+        got, _ = self._a2a(S.rows(idx[order]).contiguous(), counts)
+        self.rehomed.append(int(idx.numel()))
+        if idx.numel() or got.shape[0]:
+            keep = torch.nonzero(~away).flatten()
+            S.__init__(torch.cat([S.rows(keep), got], dim=0), self.ops)
+
+    def evolve(self, pos, vel, mass, nsteps, spectra=False, wrap=False):
+        """pos f64 [n, 3] (unwrapped, any finite value), vel f32 [n, 3] or None, mass f32 [n] or a scalar: the particles this rank
+        holds, in any distribution over the ranks; nsteps, spectra and wrap are the same on every rank.  Returns dict(Pos, Vel,
+        Disp) in the caller's order, steps (dicts of t_f, t_v, t_x, force_std, vel_std, the same on every rank) and, with spectra,
+        kk / power / nmodes [nsteps][Nmesh] and norm [nsteps]: the all-reduced raw sums of every step (glass_finish_power finishes
+        one).  wrap=True applies the periodic wrap to the returned Pos.  Bad input on any rank raises ValueError on every rank, with
+        nothing changed: the ranks agree on it in one reduced vector, the first collective of the call, which also carries the
+        total mass and the particle count."""
+        c, d, ops, N, L = self.comm, self.d, self.ops, self.N, self.L
+        pos = np.array(pos, dtype=np.float64, order="C")
+        n = len(pos)
+        vel = np.zeros((n, 3), dtype=np.float32) if vel is None else np.array(vel, dtype=np.float32, order="C")
+        mass = np.full(n, mass, dtype=np.float32) if np.isscalar(mass) else np.array(mass, dtype=np.float32, order="C")
+        nsteps = int(nsteps)
+        why = self._refusal(pos, vel, mass, nsteps)
+        msum = 0.0 if why is not None else float(mass.astype(np.float64).sum())
+        tot = c.allreduce_sum_vec(np.array([0.0 if why is None else 1.0, msum, float(n)]))
+        if tot[0] > 0:
+            raise ValueError(why or "glass: another rank refused its input")
+        totmass, ntot = float(tot[1]), int(tot[2])
+        if not (math.isfinite(totmass) and totmass > 0):
+            raise ValueError("glass: the total mass must be > 0 (got %g)" % totmass)
+        self.rows_sent = self.nalltoall = 0
+        self.rehomed = []
+        self._exp = math.frexp(totmass)[1]       # the deposit's scale is 2^(61 - exp): the whole mass in one cell stays below 2^61
+        ops.tables(N, L, totmass)
+        # ---- to the owners of the base planes, with the origin tag
+        rows = np.empty((n, 9))
+        rows[:, 0:3], rows[:, 3:6], rows[:, 6], rows[:, 7], rows[:, 8] = pos, vel, mass, c.rank, np.arange(n)
+        mine, self.rows_sent = self._home(torch.from_numpy(rows).to(ops.device))
+        S = _GlassState(mine, ops)
+        P, nxl = c.size, d.nxl
+        nalloc = N if P == 1 else nxl + 1
+        bespoke = ops.pitch(N) > 0 and os.environ.get("SHQ_SLAB_TORCH_FFT", "0") != "1"
+        zp = ops.pitch(N) if bespoke else N + 2
+        self._buf = ops.full((nalloc, N, zp), 0, torch.int64)          # the deposit, then (bespoke) its (y, z) half spectrum
+        self._ext = ops.full((nalloc, N, zp), 0.0, torch.float64)      # a force's real mesh and the neighbour's first plane
+        force = self._force_bespoke if bespoke else self._force_torch
+        save = spectra and nsteps > 0
+        sums = ops.full((nsteps, 3 * N + 1), 0.0, torch.float64) if save else None
+        # ---- glass_evolve (glass.cpp:76-147): one particle kernel between two forces
+        force(S, None)
+        stats = []
+        for step in range(nsteps):
+            part = ops.particles(S.pos, S.vel, S.disp, step > 0, True)
+            if step > 0:
+                stats.append(part)
+            self._rehome(S)
+            force(S, sums[step] if save else None)
+        if nsteps > 0:
+            stats.append(ops.particles(S.pos, S.vel, S.disp, True, False))
+        self._buf = self._ext = None
+        # ---- the way back by the tag, and the reductions
+        orig = S.tag[:, 0].to(torch.int64)
+        order = torch.argsort(orig, stable=True)
+        back, _ = self._a2a(torch.cat([S.pos, S.vel.to(torch.float64), S.disp.to(torch.float64), S.tag[:, 1:2]], dim=1)[order].contiguous(),
+                            torch.bincount(orig, minlength=P).tolist())
+        back = back.cpu().numpy()
+        assert len(back) == n
+        at = back[:, 9].astype(np.int64)
+        out = dict(Pos=np.empty((n, 3)), Vel=np.empty((n, 3), dtype=np.float32), Disp=np.empty((n, 3), dtype=np.float32))
+        out["Pos"][at], out["Vel"][at], out["Disp"][at] = back[:, 0:3], back[:, 3:6], back[:, 6:9]
+        st = c.allreduce_sum_vec(np.asarray(stats, dtype=np.float64).reshape(nsteps, 2))
+        out["steps"] = []
+        hdt = 0.5 * (math.pi / 2)
+        t_x = t_v = 0.0
+        for step in range(nsteps):
+            t_x += hdt
+            t_v += math.pi / 2
+            t_f = t_x
+            t_x += hdt
+            out["steps"].append(dict(t_f=t_f, t_v=t_v, t_x=t_x, force_std=math.sqrt(st[step, 0] / float(ntot)),
+                                     vel_std=math.sqrt(st[step, 1] / float(ntot))))
+        if spectra:
+            h = sums.cpu().numpy() if save else np.zeros((0, 3 * N + 1))
+            nm = np.ascontiguousarray(h[:, 2 * N:3 * N]).view(np.int64)
+            kk, power, nmodes, norm = [], [], [], []
+            if save:
+                f = c.allreduce_sum_vec(np.concatenate([h[:, :2 * N], h[:, 3 * N:]], axis=1))
+                nm = c.allreduce_sum_vec(nm)
+                power, kk, norm = f[:, :N], f[:, N:2 * N], f[:, 2 * N]
+            out.update(kk=np.array(kk).reshape(max(nsteps, 0), N), power=np.array(power).reshape(max(nsteps, 0), N),
+                       nmodes=nm.reshape(max(nsteps, 0), N), norm=np.array(norm).reshape(max(nsteps, 0)))
+        if wrap:
+            p = out["Pos"]
+            while (p >= L).any():
+                p[p >= L] -= L
+            while (p < 0).any():
+                p[p < 0] += L
+        return out
+
+    def _deposit(self, S):
+        """the window deposit; on several ranks one shift adds the ghost plane into the right-hand neighbour's plane 0: integers, exact"""
+        nxl, buf = self.d.nxl, self._buf
+        self.ops.deposit(self.N, self.L, S.pos, S.mass, self._exp, self.d.plane0, nxl, buf)
+        if self.comm.size > 1:
+            buf[0] += self._shift(buf[nxl:nxl + 1].contiguous(), +1)[0]
+
+    def _gather(self, S, axis):
+        """the right-hand neighbour's first plane behind the own ones by one shift to the left, then the window gather"""
+        nxl, ext = self.d.nxl, self._ext
+        if self.comm.size > 1:
+            ext[nxl] = self._shift(ext[0:1].contiguous(), -1)[0]
+        self.ops.gather(self.N, self.L, S.pos, ext, self.d.plane0, nxl, S.disp, axis)
+
+    def _force_bespoke(self, S, sums):
+        """glass_force with the library's own FFT passes (csrc/fft3d.hip): the deposit's buffer becomes its (y, z) half spectrum,
+        the spectrum is kept on the y-slab for the three axes, a force's planes land in the gather's window"""
+        c, ops, N, P, nxl = self.comm, self.ops, self.N, self.comm.size, self.d.nxl
+        zpc = ops.pitch(N) // 2
+        nyl, y0 = N // P, c.rank * (N // P)
+        widths, multi = self.d.widths, c.multi
+        self._deposit(S)
+        own = self._buf[:nxl]
+        if multi:
+            send = torch.empty((P * nxl, nyl, zpc), dtype=torch.complex128, device=own.device)       # rows [dest q][x_l]
+            ops.fft_yz(N, own, nxl, 0, self._exp, send, P)
+            spec = self._a2a(send, [nxl] * P, widths).wait().contiguous()                          # [x (all)][y_l][z']
+        else:
+            ops.fft_yz(N, own, nxl, 0, self._exp, None, 1)
+            spec = own.view(torch.float64).view(torch.complex128)
+        ops.xforward(N, spec, y0, nyl, sums)
+        real = self._ext[:nxl]
+
+        def start(axis):
+            out = torch.empty_like(spec)
+            ops.xtransfer(N, spec, out, y0, nyl, axis)
+            return self._a2a(out, widths, [nxl] * P)                                               # rows [src q][x_l]
+
+        pend = start(0) if multi else None
+        for axis in range(3):
+            if multi:
+                packed = pend.wait().contiguous()
+                pend = start(axis + 1) if axis + 1 < 3 else None
+                ops.fft_yz(N, real, nxl, 1, 0, packed, P)
+            else:       # the planes land where the Y/Z inverse takes them
+                ops.xtransfer(N, spec, real.view(torch.complex128), y0, nyl, axis)
+                ops.fft_yz(N, real, nxl, 1, 0, None, 1)
+            self._gather(S, axis)
+
+    def _force_torch(self, S, sums):
+        """the same force with torch.fft, for mesh sizes without a bespoke transform and on the CPU stand-in: the spectrum is kept
+        as [x][y_l][z'], x slowest, dense"""
+        c, ops, N, P, nxl = self.comm, self.ops, self.N, self.comm.size, self.d.nxl
+        Nc, nyl, y0 = N // 2 + 1, N // P, c.rank * (N // P)
+        self._deposit(S)
+        real = ops.to_real(self._buf[:nxl, :, :N], self._exp)                                      # f64 [nxl, N, N]
+        sp = torch.fft.rfft2(real, dim=(1, 2))                                                     # [nxl, N, Nc], unscaled
+        send = sp.reshape(nxl, P, nyl, Nc).permute(1, 0, 2, 3).reshape(P * nxl, nyl, Nc)           # rows [dest q][x_l]
+        recv, _ = self._a2a(send.contiguous(), [nxl] * P)                                          # rows [src p][x_l] = all x
+        spec = torch.fft.fft(recv.reshape(N, nyl, Nc), dim=0).contiguous()
+        if sums is not None:
+            ops.power(N, spec, y0, nyl, sums)
+        for axis in range(3):
+            out = torch.fft.ifft(ops.transfer(N, spec, y0, nyl, axis), dim=0, norm="forward").contiguous()   # rows = x planes, in order
+            recv, _ = self._a2a(out, self.d.widths)                                                          # rows [src q][x_l]
+            sp = recv.reshape(P, nxl, nyl, Nc).permute(1, 0, 2, 3).reshape(nxl, N, Nc)
+            self._ext[:nxl, :, :N] = torch.fft.irfft2(sp, s=(N, N), dim=(1, 2), norm="forward")              # unscaled
+            self._gather(S, axis)
+
+
+class GpuGlassOps:
+    """DistGlass's phases on the device library (shq_glass_slab_*), on torch tensors of the context's device."""
+
+    def __init__(self, ctx, device=None):
+        self.ctx = ctx
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self._hand = _StreamHandover(ctx, self.device)
+
+    def _call(self, fn, *args):
+        self._hand.before()
+        capi.check(fn(self.ctx.h, *args), fn.__name__)
+        self._hand.after()
+
+    @staticmethod
+    def _p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
+    def full(self, shape, value, dtype):
+        return torch.full(shape, value, dtype=dtype, device=self.device)
+
+    def pitch(self, N):
+        return int(capi.hip.shq_glass_slab_pitch(int(N)))
+
+    def tables(self, N, L, totmass):
+        self._call(capi.hip.shq_glass_slab_tables, N, L, totmass)
+
+    def planes(self, N, L, pos):
+        assert pos.is_contiguous() and pos.dtype == torch.float64
+        out = torch.empty((pos.shape[0],), dtype=torch.int32, device=self.device)
+        self._call(capi.hip.shq_glass_slab_planes, N, L, self._p(pos), pos.shape[0], self._p(out))
+        return out
+
+    def deposit(self, N, L, pos, mass, exp, plane0, nxl, buf):
+        assert pos.is_contiguous() and mass.is_contiguous() and mass.dtype == torch.float32 and buf.is_contiguous() and buf.dtype == torch.int64
+        assert buf.shape[1:] == (N, self.pitch(N) or N + 2)
+        self._call(capi.hip.shq_glass_slab_deposit, N, L, self._p(pos), self._p(mass), pos.shape[0], exp, plane0, nxl, buf.shape[0], self._p(buf))
+
+    def fft_yz(self, N, planes, nplanes, direction, exp, packed, nranks):
+        assert planes.is_contiguous() and (packed is None or (packed.is_contiguous() and packed.dtype == torch.complex128))
+        self._call(capi.hip.shq_glass_slab_fft_yz, N, self._p(planes), nplanes, direction, exp, self._p(packed), nranks)
+
+    def xforward(self, N, spec, y0, nyl, sums):
+        assert spec.is_contiguous() and spec.dtype == torch.complex128 and (sums is None or (sums.is_contiguous() and sums.shape == (3 * N + 1,)))
+        self._call(capi.hip.shq_glass_slab_xforward, N, self._p(spec), y0, nyl, self._p(sums))
+
+    def xtransfer(self, N, spec, out, y0, nyl, axis):
+        assert spec.is_contiguous() and out.is_contiguous() and out.dtype == spec.dtype == torch.complex128 and out.shape == spec.shape
+        self._call(capi.hip.shq_glass_slab_xtransfer, N, self._p(spec), self._p(out), y0, nyl, axis)
+
+    def to_real(self, mesh_i, exp):
+        return mesh_i.to(torch.float64) * math.ldexp(1.0, exp - 61)
+
+    def power(self, N, spec, y0, nyl, sums):
+        assert spec.is_contiguous() and spec.dtype == torch.complex128 and spec.shape == (N, nyl, N // 2 + 1) and sums.is_contiguous()
+        self._call(capi.hip.shq_glass_slab_power, N, self._p(spec), y0, nyl, self._p(sums))
+
+    def transfer(self, N, spec, y0, nyl, axis):
+        assert spec.is_contiguous() and spec.dtype == torch.complex128 and spec.shape == (N, nyl, N // 2 + 1)
+        out = torch.empty_like(spec)
+        self._call(capi.hip.shq_glass_slab_transfer, N, self._p(spec), self._p(out), y0, nyl, axis)
+        return out
+
+    def gather(self, N, L, pos, window, plane0, nxl, disp, axis):
+        assert pos.is_contiguous() and window.is_contiguous() and disp.is_contiguous() and window.dtype == torch.float64 and disp.dtype == torch.float32
+        assert window.shape[1:] == (N, self.pitch(N) or N + 2)
+        self._call(capi.hip.shq_glass_slab_gather, N, L, self._p(pos), pos.shape[0], self._p(window), plane0, nxl, window.shape[0], self._p(disp), axis)
+
+    def particles(self, pos, vel, disp, ending, beginning):
+        assert pos.is_contiguous() and vel.is_contiguous() and disp.is_contiguous() and vel.dtype == disp.dtype == torch.float32
+        sums = (C.c_double * 2)()
+        self._call(capi.hip.shq_glass_slab_particles, pos.shape[0], self._p(pos), self._p(vel), self._p(disp), int(ending), int(beginning), C.byref(sums))
+        return list(sums)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # Helium reionisation by quasar bubbles across ranks: turn_on_quasars (libgadget/cooling_qso_lightup.cpp:489-596) as its loop runs
 # on several tasks.  Every rank holds some of the gas (any particle may sit on any rank: no decomposition, no ghosts) and hosts some
