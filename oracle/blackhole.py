@@ -66,10 +66,16 @@ def dm_velpred(P, i, kf):
     return P["Vel"][i] + kf.gravkicks[bg] * P["FullTreeGravAccel"][i] + P["GravPM"][i] * kf.FgravkickB
 
 
-def neighbours(P, i, box):
-    """indices in particle order that treewalk_visit_ngbiter hands to the ngbiter of black hole i, with r2 and r"""
-    n = len(P)
-    live = ((P["Flags"] & 1) == 0) & np.isin(P["Type"], (0, 5)) & ~((P["Type"] == 5) & ((P["Flags"] & 2) != 0))
+def neighbours(P, i, box, in_tree=None):
+    """indices in particle order that treewalk_visit_ngbiter hands to the ngbiter of black hole i, with r2 and r.  in_tree: which
+    particles the tree held when it was built (forcetree.cpp:805 leaves garbage and swallowed holes out); the walk itself tests only
+    IsGarbage and the type (treewalk.c:943-949), so a hole swallowed after the build is still a neighbour.  Without in_tree the
+    tree is taken to have been built from the flags as they are now."""
+    live = ((P["Flags"] & 1) == 0) & np.isin(P["Type"], (0, 5))
+    if in_tree is None:
+        live &= ~((P["Type"] == 5) & ((P["Flags"] & 2) != 0))
+    else:
+        live &= np.asarray(in_tree, dtype=bool)
     d = nearest(P["Pos"][i][None, :] - P["Pos"], box)
     r2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
     dist = np.maximum(P["Hsml"], P["Hsml"][i])
@@ -78,7 +84,7 @@ def neighbours(P, i, box):
     return idx, r2[idx], d[idx]
 
 
-def accretion(P, S, B, ids, queue, kf, prm, Ti_Current, rnd, work):
+def accretion(P, S, B, ids, queue, kf, prm, Ti_Current, rnd, work, in_tree=None):
     """treewalk_run(tw_accretion): fills work (dict of arrays by slot) and the slots; prm is the shq_bh_params-like namespace"""
     work["SPH_SwallowID"][:] = 0
     work["BH_SwallowID"][:] = 0
@@ -91,7 +97,7 @@ def accretion(P, S, B, ids, queue, kf, prm, Ti_Current, rnd, work):
         Iacc = P["FullTreeGravAccel"][i] + P["GravPM"][i] + B["DFAccel"][pi]
         Imass, Ibh, Idens, Imtrack = float(P["Mass"][i]), float(B["Mass"][pi]), float(B["Density"][pi]), float(B["Mtrack"][pi])
         enc, fws, sment, gv, mgas = 0, 0.0, 0.0, np.zeros(3), 0.0
-        idx, r2s, ds = neighbours(P, i, prm.BoxSize)
+        idx, r2s, ds = neighbours(P, i, prm.BoxSize, in_tree)
         for other, r2, dx in zip(idx, r2s, ds):
             other = int(other)
             r = np.sqrt(r2)
@@ -211,7 +217,7 @@ def accretion_postprocess(P, B, i, kf, prm, work):
             work["KEflag"][pi] = 2
 
 
-def feedback(P, S, B, ids, queue, kf, prm, maxpart, rnd, eeqos, work):
+def feedback(P, S, B, ids, queue, kf, prm, maxpart, rnd, eeqos, work, in_tree=None):
     """treewalk_run(tw_feedback) with haswork, then postprocess.  Returns (gas swallowed, holes swallowed)."""
     kt = prm.DensityKernelType
     todo = [int(i) for i in queue if work["BH_SwallowID"][P["PI"][i]] == 0]
@@ -232,7 +238,7 @@ def feedback(P, S, B, ids, queue, kf, prm, maxpart, rnd, eeqos, work):
             if work["KEflag"][pi] == 2:
                 kefb = float(B["KineticFdbkEnergy"][pi])
         accm, accbh, mom, cprog, mintb = 0.0, 0.0, np.zeros(3), 0, TIMEBINS
-        idx, r2s, _ = neighbours(P, i, prm.BoxSize)
+        idx, r2s, _ = neighbours(P, i, prm.BoxSize, in_tree)
         for other, r2 in zip(idx, r2s):
             other = int(other)
             t = int(P["Type"][other])

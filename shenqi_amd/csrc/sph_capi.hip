@@ -1219,17 +1219,11 @@ extern "C" int shq_bh_feedback(shq_context *ctx, const shq_tree_view *tree, cons
     SHQ_TRY(ctx->bhw_tlist.reserve((size_t) std::max<int64_t>(n, 1)));
     /* what the walk changes on the neighbours' side comes back as rows of the particles it touched (and of the holes), not as whole
      * arrays: at 2 x 10^6 particles the five array downloads and the loop over every gas particle were most of this call */
-    std::vector<double> bh0(8 * std::max<size_t>(nbh, 1));
     if(n) {
         if(eeqos)
             SHQ_HIP(hipMemcpyAsync(ctx->bhw_eeqos.ptr, eeqos, (size_t) n, hipMemcpyHostToDevice, st));
         SHQ_HIP(hipMemsetAsync(ctx->bhw_heated.ptr, 0, (size_t) n, st));
         SHQ_HIP(hipMemsetAsync(ctx->bhw_touched.ptr, 0, (size_t) n, st));
-    }
-    SHQ_TRY(ctx->bhw_trows.reserve(8 * std::max<size_t>(nbh, 1)));
-    if(nbh) { /* the holes' flags before the walk */
-        SHQ_TRY(shq_rows_gather(ctx, ctx->bhw_bhp.ptr, (int64_t) nbh, nullptr, ctx->bhw_trows.ptr));
-        SHQ_HIP(hipMemcpyAsync(bh0.data(), ctx->bhw_trows.ptr, sizeof(double) * 8 * nbh, hipMemcpyDeviceToHost, st));
     }
     const int64_t nq = (int64_t) q.size();
     BhWalkArgs w;
@@ -1278,7 +1272,9 @@ extern "C" int shq_bh_feedback(shq_context *ctx, const shq_tree_view *tree, cons
     }
     for(size_t b = 0; b < nbh; b++) {
         const int64_t i = S.bhp[b];
-        if(((unsigned) bh1[8 * b + 6] & 2u) && !((unsigned) bh0[8 * b + 6] & 2u)) {
+        /* the walk wrote a SwallowID for the holes it swallowed.  One that carried the flag already (swallowed after the tree was
+         * built) is swallowed again like any other neighbour: the reference's walk does not look at the flag (:758-797) */
+        if(swid[b] != ~0ull && ((unsigned) bh1[8 * b + 6] & 2u)) {
             const int32_t pi = S.pi[b];
             *pfield_w<uint8_t>(parts, i, parts->off_flags) |= 2u; /* Swallowed */
             *bhfield<uint64_t>(bh, pi, bh->off_swallowid) = swid[b];
@@ -1663,7 +1659,7 @@ extern "C" int shq_bh_effects_apply(shq_context *ctx, const shq_part_view *parts
                 *reinterpret_cast<int32_t *>(static_cast<char *>(sph->base) + (size_t) pi * sph->elsize) = (int32_t) (MaxPart + 100);
                 nsph++;
             }
-        } else if(((unsigned) r[6] & 2u) && !(*flags & 2u)) {
+        } else if((unsigned) r[6] & 2u) { /* a hole is in the list through a swallow record: with or without the flag before (:758-797) */
             *flags |= 2u; /* Swallowed */
             *bhfield<uint64_t>(bh, pi, bh->off_swallowid) = work->BH_SwallowID[pi] - 1;
             *bhfield<double>(bh, pi, bh->off_swallowtime) = params->atime;
