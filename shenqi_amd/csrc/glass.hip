@@ -634,44 +634,9 @@ __global__ __launch_bounds__(GT) void glass_slab_transfer_kernel(const double2 *
     out[ip] = make_double2(tmp0, tmp1);
 }
 
-int glass_slab_twiddles(shq_context *ctx, int N, const double **tw)
-{
-    if(ctx->gls_tw_n != N) {
-        SHQ_HIP(hipStreamSynchronize(ctx->stream)); /* a pass of another size may still read the table */
-        ctx->gls_tw_n = 0;
-        SHQ_TRY(ctx->gls_tw.reserve(2 * (size_t) N));
-        SHQ_TRY(shq_fft3d_fill_twiddles(N, ctx->gls_tw.ptr));
-        ctx->gls_tw_n = N;
-    }
-    *tw = ctx->gls_tw.ptr;
-    return SHQ_OK;
-}
-
-/* the own planes [plane0, plane0 + nplanes) and one more behind them, or the whole periodic mesh */
-bool glass_window_ok(int N, int plane0, int nplanes, int nalloc)
-{
-    return nplanes > 0 && nplanes <= N && plane0 >= 0 && plane0 < N && nalloc == (nplanes == N ? N : nplanes + 1);
-}
-
-int glass_slab_flag(shq_context *ctx)
-{
-    SHQ_TRY(ctx->gls_flag.reserve(1));
-    SHQ_HIP(hipMemsetAsync(ctx->gls_flag.ptr, 0, sizeof(int), ctx->stream));
-    return SHQ_OK;
-}
-
-/* the flag after the kernel: synchronises */
-int glass_slab_flag_read(shq_context *ctx, int *oob)
-{
-    *oob = 0;
-    SHQ_HIP(hipMemcpyAsync(oob, ctx->gls_flag.ptr, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    SHQ_HIP(hipStreamSynchronize(ctx->stream));
-    return SHQ_OK;
-}
-
 } // namespace
 
-extern "C" int shq_glass_slab_pitch(int Nmesh) { return fft3d_route(Nmesh).bespoke ? shq_fft3d_pitch(Nmesh) : 0; }
+extern "C" int shq_glass_slab_pitch(int Nmesh) { return slab_pitch(Nmesh); }
 
 extern "C" int shq_glass_slab_tables(shq_context *ctx, int Nmesh, double BoxSize, double totmass)
 {
@@ -724,12 +689,12 @@ extern "C" int shq_glass_slab_deposit(shq_context *ctx, int Nmesh, double BoxSiz
     const int N = Nmesh;
     SHQ_TRY(mesh_check_size(N, "glass_slab_deposit"));
     SHQ_CHECK(isfinite(BoxSize) && BoxSize > 0, SHQ_ERR_INVALID, "glass_slab_deposit: BoxSize must be finite and > 0");
-    SHQ_CHECK(glass_window_ok(N, plane0, nplanes, nalloc), SHQ_ERR_INVALID, "glass_slab_deposit: bad slab geometry");
+    SHQ_CHECK(slab_window_ok(N, plane0, nplanes, nalloc), SHQ_ERR_INVALID, "glass_slab_deposit: bad slab geometry");
     SHQ_CHECK(exp > -900 && exp < 900, SHQ_ERR_INVALID, "glass_slab_deposit: bad scale exponent %d", exp);
     SHQ_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     const int zp = fft3d_route(N).zp;
-    SHQ_TRY(glass_slab_flag(ctx));
+    SHQ_TRY(slab_flag_reset(ctx, ctx->gls_flag));
     SHQ_HIP(hipMemsetAsync(d_mesh, 0, sizeof(double) * (size_t) nalloc * N * zp, s));
     if(n > 0)
         glass_slab_deposit_kernel<<<dim3(nblk(n, GT)), dim3(GT), 0, s>>>(n, (const double *) d_pos, (const float *) d_mass,
@@ -737,28 +702,14 @@ extern "C" int shq_glass_slab_deposit(shq_context *ctx, int Nmesh, double BoxSiz
                                                                           plane0, nplanes, nalloc, ctx->gls_flag.ptr);
     SHQ_HIP(hipGetLastError());
     int oob;
-    SHQ_TRY(glass_slab_flag_read(ctx, &oob));
+    SHQ_TRY(slab_flag_read(ctx, ctx->gls_flag.ptr, &oob));
     SHQ_CHECK(!oob, SHQ_ERR_INVALID, "glass_slab_deposit: a particle lies outside this rank's slab (planes %d .. %d)", plane0, plane0 + nplanes - 1);
     return SHQ_OK;
 }
 
 extern "C" int shq_glass_slab_fft_yz(shq_context *ctx, int Nmesh, void *d_planes, int nplanes, int direction, int exp, void *d_packed, int nranks)
 {
-    SHQ_CHECK(ctx && d_planes, SHQ_ERR_INVALID, "glass_slab_fft_yz: null argument");
-    const int N = Nmesh, zp = shq_glass_slab_pitch(N);
-    SHQ_CHECK(zp > 0, SHQ_ERR_INVALID, "glass_slab_fft_yz: mesh size %d has no bespoke FFT", N);
-    SHQ_CHECK(nplanes > 0 && nplanes <= N && (direction == 0 || direction == 1) && exp > -900 && exp < 900, SHQ_ERR_INVALID,
-              "glass_slab_fft_yz: bad arguments");
-    SHQ_CHECK(!d_packed || (nranks >= 1 && N % nranks == 0), SHQ_ERR_INVALID, "glass_slab_fft_yz: %d ranks do not divide the mesh", nranks);
-    SHQ_HIP(hipSetDevice(ctx->device));
-    shq_fft_opts o;
-    SHQ_TRY(glass_slab_twiddles(ctx, N, &o.tw));
-    o.nslab = nplanes;
-    o.packed = (double *) d_packed;
-    o.nranks = d_packed ? nranks : 1;
-    const shq_fft_stage st =
-        direction == 0 ? (d_packed ? SHQ_FFT_YZ_FORWARD_PACKED : SHQ_FFT_YZ_FORWARD) : (d_packed ? SHQ_FFT_YZ_INVERSE_PACKED : SHQ_FFT_YZ_INVERSE);
-    return shq_fft3d_run(ctx, (double *) d_planes, N, zp, st, direction == 0, ldexp(1.0, exp - 61), nullptr, 0, 0, o);
+    return slab_fft_yz(ctx, "glass_slab_fft_yz", &shq_context::gls_tw, &shq_context::gls_tw_n, Nmesh, d_planes, nplanes, direction, exp, d_packed, nranks);
 }
 
 extern "C" int shq_glass_slab_xforward(shq_context *ctx, int Nmesh, void *d_spec, int y0, int nyl, void *d_sums)
@@ -770,7 +721,7 @@ extern "C" int shq_glass_slab_xforward(shq_context *ctx, int Nmesh, void *d_spec
     SHQ_CHECK(!d_sums || ctx->gls_tabs_n == N, SHQ_ERR_STATE, "glass_slab_xforward: no tables of mesh size %d (shq_glass_slab_tables first)", N);
     SHQ_HIP(hipSetDevice(ctx->device));
     shq_fft_opts o;
-    SHQ_TRY(glass_slab_twiddles(ctx, N, &o.tw));
+    SHQ_TRY(slab_twiddles(ctx, ctx->gls_tw, ctx->gls_tw_n, N, &o.tw));
     o.nslab = nyl;
     o.y0 = y0;
     if(d_sums) {
@@ -789,7 +740,7 @@ extern "C" int shq_glass_slab_xtransfer(shq_context *ctx, int Nmesh, const void 
     SHQ_CHECK(ctx->gls_tabs_n == N, SHQ_ERR_STATE, "glass_slab_xtransfer: no tables of mesh size %d (shq_glass_slab_tables first)", N);
     SHQ_HIP(hipSetDevice(ctx->device));
     shq_fft_opts o;
-    SHQ_TRY(glass_slab_twiddles(ctx, N, &o.tw));
+    SHQ_TRY(slab_twiddles(ctx, ctx->gls_tw, ctx->gls_tw_n, N, &o.tw));
     o.nslab = nyl;
     o.y0 = y0;
     o.modefac = ctx->gls_tabs.ptr; /* fac[N] */
@@ -836,16 +787,16 @@ extern "C" int shq_glass_slab_gather(shq_context *ctx, int Nmesh, double BoxSize
     const int N = Nmesh;
     SHQ_TRY(mesh_check_size(N, "glass_slab_gather"));
     SHQ_CHECK(isfinite(BoxSize) && BoxSize > 0 && axis >= 0 && axis <= 2, SHQ_ERR_INVALID, "glass_slab_gather: BoxSize must be finite and > 0, axis 0 .. 2");
-    SHQ_CHECK(glass_window_ok(N, plane0, nplanes, nalloc), SHQ_ERR_INVALID, "glass_slab_gather: bad slab geometry");
+    SHQ_CHECK(slab_window_ok(N, plane0, nplanes, nalloc), SHQ_ERR_INVALID, "glass_slab_gather: bad slab geometry");
     SHQ_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    SHQ_TRY(glass_slab_flag(ctx));
+    SHQ_TRY(slab_flag_reset(ctx, ctx->gls_flag));
     if(n > 0)
         glass_slab_gather_kernel<<<dim3(nblk(n, GT)), dim3(GT), 0, s>>>(n, (const double *) d_pos, (const double *) d_mesh, N, fft3d_route(N).zp,
                                                                          BoxSize / N, plane0, nplanes, nalloc, (float *) d_disp, axis, ctx->gls_flag.ptr);
     SHQ_HIP(hipGetLastError());
     int oob;
-    SHQ_TRY(glass_slab_flag_read(ctx, &oob));
+    SHQ_TRY(slab_flag_read(ctx, ctx->gls_flag.ptr, &oob));
     SHQ_CHECK(!oob, SHQ_ERR_INVALID, "glass_slab_gather: a particle lies outside this rank's slab (planes %d .. %d)", plane0, plane0 + nplanes - 1);
     return SHQ_OK;
 }

@@ -86,6 +86,75 @@ inline int route_inverse(shq_context *ctx, CallScope &sc, const Fft3dRoute &r, d
     return route_hipfft_inverse(sc, r, d_mesh);
 }
 
+/* ---- the slab operators (glass, zeldovich, uvbg: one x-slab of the mesh per rank, driven by shenqi_amd/dist.py) */
+
+/* doubles per z row of the bespoke passes on a slab, 0 for a mesh size without them */
+inline int slab_pitch(int N) { return fft3d_route(N).bespoke ? shq_fft3d_pitch(N) : 0; }
+
+/* The twiddles of mesh size N in an operator's own buffer of the context (buf, and n: the size it holds): a PM at one mesh size and
+ * an operator's mesh at another do not evict each other. */
+inline int slab_twiddles(shq_context *ctx, DevBuf<double> &buf, int &n, int N, const double **tw)
+{
+    if(n != N) {
+        SHQ_HIP(hipStreamSynchronize(ctx->stream)); /* a pass of another size may still read the table */
+        n = 0;
+        SHQ_TRY(buf.reserve(2 * (size_t) N));
+        SHQ_TRY(shq_fft3d_fill_twiddles(N, buf.ptr));
+        n = N;
+    }
+    *tw = buf.ptr;
+    return SHQ_OK;
+}
+
+/* The Y/Z passes of `nplanes` x planes [nplanes][N][zp] doubles, in place: direction 0 takes the int64 planes of a field deposited
+ * with exponent `exp` (worth 2^(exp - 61) per unit) to the (y, z) half spectrum, direction 1 goes back to real space with that
+ * factor (SLAB_EXP_ONE: 1).  d_packed (NULL: in place) is the all-to-all buffer [nranks][nplanes][N / nranks][zp / 2] complex that
+ * the Y pass stores into on the way out and loads from on the way back. */
+constexpr int SLAB_EXP_ONE = 61;
+
+/* tw, twn: the operator's twiddle buffer and its size in the context, as members: ctx is checked here, not by the caller */
+inline int slab_fft_yz(shq_context *ctx, const char *who, DevBuf<double> shq_context::*tw, int shq_context::*twn, int N, void *d_planes,
+                       int nplanes, int direction, int exp, const void *d_packed, int nranks)
+{
+    SHQ_CHECK(ctx && d_planes, SHQ_ERR_INVALID, "%s: null argument", who);
+    const int zp = slab_pitch(N);
+    SHQ_CHECK(zp > 0, SHQ_ERR_INVALID, "%s: mesh size %d has no bespoke FFT", who, N);
+    SHQ_CHECK(nplanes > 0 && nplanes <= N && (direction == 0 || direction == 1) && exp > -900 && exp < 900, SHQ_ERR_INVALID, "%s: bad arguments", who);
+    SHQ_CHECK(!d_packed || (nranks >= 1 && N % nranks == 0), SHQ_ERR_INVALID, "%s: %d ranks do not divide the mesh", who, nranks);
+    SHQ_HIP(hipSetDevice(ctx->device));
+    shq_fft_opts o;
+    SHQ_TRY(slab_twiddles(ctx, ctx->*tw, ctx->*twn, N, &o.tw));
+    o.nslab = nplanes;
+    o.packed = (double *) const_cast<void *>(d_packed);
+    o.nranks = d_packed ? nranks : 1;
+    const shq_fft_stage st =
+        direction == 0 ? (d_packed ? SHQ_FFT_YZ_FORWARD_PACKED : SHQ_FFT_YZ_FORWARD) : (d_packed ? SHQ_FFT_YZ_INVERSE_PACKED : SHQ_FFT_YZ_INVERSE);
+    return shq_fft3d_run(ctx, (double *) d_planes, N, zp, st, direction == 0, ldexp(1.0, exp - 61), nullptr, 0, 0, o);
+}
+
+/* a particle window [nalloc][N][..]: the own planes [plane0, plane0 + nplanes) and one more behind them, or the whole periodic mesh */
+inline bool slab_window_ok(int N, int plane0, int nplanes, int nalloc)
+{
+    return nplanes > 0 && nplanes <= N && plane0 >= 0 && plane0 < N && nalloc == (nplanes == N ? N : nplanes + 1);
+}
+
+/* The out-of-slab flag of a window kernel: `nflags` ints of an operator's own buffer zeroed on the stream before the launch, one of
+ * them read after it - which synchronises. */
+inline int slab_flag_reset(shq_context *ctx, DevBuf<int> &flag, size_t nflags = 1)
+{
+    SHQ_TRY(flag.reserve(nflags));
+    SHQ_HIP(hipMemsetAsync(flag.ptr, 0, nflags * sizeof(int), ctx->stream));
+    return SHQ_OK;
+}
+
+inline int slab_flag_read(shq_context *ctx, const int *d_flag, int *oob)
+{
+    *oob = 0;
+    SHQ_HIP(hipMemcpyAsync(oob, d_flag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    SHQ_HIP(hipStreamSynchronize(ctx->stream));
+    return SHQ_OK;
+}
+
 /* ---- mode ip of a half spectrum [x][y][z'], z' < N / 2 + 1: the signed wave numbers, k2, and the row x N + y */
 struct HalfMode {
     int x, y, z, kx, ky;

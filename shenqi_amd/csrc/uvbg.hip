@@ -585,24 +585,10 @@ extern "C" int shq_uvbg_calculate(shq_context *ctx, const shq_uvbg_params *p, co
  * the PM's state: the deposit scales are arguments, the twiddles and tables are the context's uvbg ones. */
 namespace {
 
-int uvbg_slab_twiddles(shq_context *ctx, int N, const double **tw)
-{
-    if(ctx->uvbg_tw_n != N) {
-        SHQ_HIP(hipStreamSynchronize(ctx->stream)); /* a pass of another size may still read the table */
-        SHQ_TRY(ctx->uvbg_tw.reserve(2 * (size_t) N));
-        SHQ_TRY(shq_fft3d_fill_twiddles(N, ctx->uvbg_tw.ptr));
-        ctx->uvbg_tw_n = N;
-    }
-    *tw = ctx->uvbg_tw.ptr;
-    return SHQ_OK;
-}
-
 int uvbg_slab_scratch(shq_context *ctx, size_t nblocks)
 {
     SHQ_TRY(ctx->uvbg_part.reserve(3 * nblocks + 3)); /* the blocks' partial sums, then the three totals */
-    SHQ_TRY(ctx->uvbg_flag.reserve(2));
-    SHQ_HIP(hipMemsetAsync(ctx->uvbg_flag.ptr, 0, 2 * sizeof(int), ctx->stream));
-    return SHQ_OK;
+    return slab_flag_reset(ctx, ctx->uvbg_flag, 2); /* [0] a negative escape fraction, [1] a particle outside the slab's window */
 }
 
 bool uvbg_window_ok(int N, int plane0, int nplanes, int xoff, int nalloc)
@@ -612,7 +598,7 @@ bool uvbg_window_ok(int N, int plane0, int nplanes, int xoff, int nalloc)
 
 } // namespace
 
-extern "C" int shq_uvbg_slab_pitch(int UVBGdim) { return fft3d_route(UVBGdim).bespoke ? shq_fft3d_pitch(UVBGdim) : 0; }
+extern "C" int shq_uvbg_slab_pitch(int UVBGdim) { return slab_pitch(UVBGdim); }
 
 extern "C" int shq_uvbg_slab_fesc(shq_context *ctx, const shq_uvbg_params *p, const shq_uvbg_cosmo *cp, const void *d_posm, const void *d_types,
                                   int64_t n, void *d_fesc, const void *d_sfr, double sums[3], int *negative)
@@ -672,9 +658,8 @@ extern "C" int shq_uvbg_slab_deposit(shq_context *ctx, const shq_uvbg_params *p,
             p->BoxSize / N, ldexp(1.0, 61 - exps[0]), ldexp(1.0, 61 - exps[1]), ldexp(1.0, 61 - exps[2]), (unsigned long long *) d_m0,
             (unsigned long long *) d_m1, use_sfr ? (unsigned long long *) d_m2 : nullptr, plane0 - xoff, nfit, ctx->uvbg_flag.ptr + 1);
     SHQ_HIP(hipGetLastError());
-    int oob = 0;
-    SHQ_HIP(hipMemcpyAsync(&oob, ctx->uvbg_flag.ptr + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    SHQ_HIP(hipStreamSynchronize(s));
+    int oob;
+    SHQ_TRY(slab_flag_read(ctx, ctx->uvbg_flag.ptr + 1, &oob));
     SHQ_CHECK(!oob, SHQ_ERR_INVALID, "uvbg_slab_deposit: a particle lies outside this rank's slab (planes %d .. %d)", plane0, plane0 + nplanes - 1);
     return SHQ_OK;
 }
@@ -684,19 +669,7 @@ extern "C" int shq_uvbg_slab_deposit(shq_context *ctx, const shq_uvbg_params *p,
  * the all-to-all buffer [nranks][nplanes][N / nranks][zp / 2] complex of shq_pm_slab2_fft_yz_packed. */
 extern "C" int shq_uvbg_slab_fft_yz(shq_context *ctx, int UVBGdim, void *d_planes, int nplanes, int direction, int exp, void *d_packed, int nranks)
 {
-    SHQ_CHECK(ctx && d_planes, SHQ_ERR_INVALID, "uvbg_slab_fft_yz: null argument");
-    const int N = UVBGdim, zp = shq_uvbg_slab_pitch(N);
-    SHQ_CHECK(zp > 0, SHQ_ERR_INVALID, "uvbg_slab_fft_yz: mesh size %d has no bespoke FFT", N);
-    SHQ_CHECK(nplanes > 0 && nplanes <= N && (direction == 0 || direction == 1) && exp > -900 && exp < 900, SHQ_ERR_INVALID, "uvbg_slab_fft_yz: bad arguments");
-    SHQ_CHECK(!d_packed || (nranks >= 1 && N % nranks == 0), SHQ_ERR_INVALID, "uvbg_slab_fft_yz: %d ranks do not divide the mesh", nranks);
-    SHQ_HIP(hipSetDevice(ctx->device));
-    shq_fft_opts o;
-    SHQ_TRY(uvbg_slab_twiddles(ctx, N, &o.tw));
-    o.nslab = nplanes;
-    o.packed = (double *) d_packed;
-    o.nranks = d_packed ? nranks : 1;
-    const shq_fft_stage st = direction == 0 ? (d_packed ? SHQ_FFT_YZ_FORWARD_PACKED : SHQ_FFT_YZ_FORWARD) : (d_packed ? SHQ_FFT_YZ_INVERSE_PACKED : SHQ_FFT_YZ_INVERSE);
-    return shq_fft3d_run(ctx, (double *) d_planes, N, zp, st, direction == 0, ldexp(1.0, exp - 61), nullptr, 0, 0, o);
+    return slab_fft_yz(ctx, "uvbg_slab_fft_yz", &shq_context::uvbg_tw, &shq_context::uvbg_tw_n, UVBGdim, d_planes, nplanes, direction, exp, d_packed, nranks);
 }
 
 /* the X forward of the y-slab [N][nyl][zp / 2] complex the all-to-all delivers, in place: the spectrum kept for the radius loop */
@@ -708,7 +681,7 @@ extern "C" int shq_uvbg_slab_xforward(shq_context *ctx, int UVBGdim, void *d_spe
     SHQ_CHECK(nyl > 0 && y0 >= 0 && y0 + nyl <= N, SHQ_ERR_INVALID, "uvbg_slab_xforward: bad slab geometry");
     SHQ_HIP(hipSetDevice(ctx->device));
     shq_fft_opts o;
-    SHQ_TRY(uvbg_slab_twiddles(ctx, N, &o.tw));
+    SHQ_TRY(slab_twiddles(ctx, ctx->uvbg_tw, ctx->uvbg_tw_n, N, &o.tw));
     o.nslab = nyl;
     o.y0 = y0;
     return shq_fft3d_run(ctx, (double *) d_spec, N, zp, SHQ_FFT_X_FORWARD_SUMS, false, 1.0, nullptr, 0, 0, o);
@@ -761,7 +734,7 @@ extern "C" int shq_uvbg_slab_xfilter(shq_context *ctx, int UVBGdim, const void *
               "uvbg_slab_xfilter: no table of radius %d at mesh size %d (shq_uvbg_slab_tables first)", r, N);
     SHQ_HIP(hipSetDevice(ctx->device));
     shq_fft_opts o;
-    SHQ_TRY(uvbg_slab_twiddles(ctx, N, &o.tw));
+    SHQ_TRY(slab_twiddles(ctx, ctx->uvbg_tw, ctx->uvbg_tw_n, N, &o.tw));
     o.nslab = nyl;
     o.y0 = y0;
     o.modefac = ctx->uvbg_tabs.ptr + (size_t) r * (3 * (size_t) (N / 2) * (N / 2) + 1);
@@ -832,8 +805,7 @@ extern "C" int shq_uvbg_slab_readout(shq_context *ctx, const shq_uvbg_params *p,
               "uvbg_slab_readout: bad particle arrays");
     SHQ_TRY(uvbg_check_params(p, cp));
     const int N = p->UVBGdim;
-    SHQ_CHECK(uvbg_window_ok(N, plane0, nplanes, 0, nalloc) && nalloc == (nplanes == N ? N : nplanes + 1), SHQ_ERR_INVALID,
-              "uvbg_slab_readout: bad slab geometry");
+    SHQ_CHECK(slab_window_ok(N, plane0, nplanes, nalloc), SHQ_ERR_INVALID, "uvbg_slab_readout: bad slab geometry");
     SHQ_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
     SHQ_TRY(uvbg_slab_scratch(ctx, 1));
@@ -843,9 +815,8 @@ extern "C" int shq_uvbg_slab_readout(shq_context *ctx, const shq_uvbg_params *p,
                                                                        (double *) d_local_J21, (double *) d_zreion, plane0, nalloc,
                                                                        ctx->uvbg_flag.ptr + 1);
     SHQ_HIP(hipGetLastError());
-    int oob = 0;
-    SHQ_HIP(hipMemcpyAsync(&oob, ctx->uvbg_flag.ptr + 1, sizeof(int), hipMemcpyDeviceToHost, s));
-    SHQ_HIP(hipStreamSynchronize(s));
+    int oob;
+    SHQ_TRY(slab_flag_read(ctx, ctx->uvbg_flag.ptr + 1, &oob));
     SHQ_CHECK(!oob, SHQ_ERR_INVALID, "uvbg_slab_readout: a gas particle lies outside this rank's slab (planes %d .. %d)", plane0, plane0 + nplanes - 1);
     return SHQ_OK;
 }

@@ -660,18 +660,6 @@ extern "C" int shq_zeldovich_displacements(shq_context *ctx, const shq_zeldovich
  * and the flags are the context's zels_ ones. */
 namespace {
 
-int zel_slab_twiddles(shq_context *ctx, int N, const double **tw)
-{
-    if(ctx->zels_tw_n != N) {
-        SHQ_HIP(hipStreamSynchronize(ctx->stream)); /* a pass of another size may still read the table */
-        SHQ_TRY(ctx->zels_tw.reserve(2 * (size_t) N));
-        SHQ_TRY(shq_fft3d_fill_twiddles(N, ctx->zels_tw.ptr));
-        ctx->zels_tw_n = N;
-    }
-    *tw = ctx->zels_tw.ptr;
-    return SHQ_OK;
-}
-
 /* the table and the axis of field 0 .. 6 (Density, DispX/Y/Z, VelX/Y/Z) from the uploaded tables */
 int zel_slab_field(shq_context *ctx, int N, double BoxSize, int field, const char *who, const double **tab, int *axis)
 {
@@ -687,7 +675,7 @@ int zel_slab_field(shq_context *ctx, int N, double BoxSize, int field, const cha
 
 } // namespace
 
-extern "C" int shq_zeldovich_slab_pitch(int Nmesh) { return fft3d_route(Nmesh).bespoke ? shq_fft3d_pitch(Nmesh) : 0; }
+extern "C" int shq_zeldovich_slab_pitch(int Nmesh) { return slab_pitch(Nmesh); }
 
 extern "C" int shq_zeldovich_slab_fill(shq_context *ctx, int Nmesh, int Seed, int UnitaryAmplitude, int InvertPhase, int y0, int nyl, void *d_spec)
 {
@@ -737,7 +725,7 @@ extern "C" int shq_zeldovich_slab_xtransfer(shq_context *ctx, int Nmesh, double 
     shq_fft_opts o;
     SHQ_TRY(zel_slab_field(ctx, N, BoxSize, field, "zeldovich_slab_xtransfer", &o.modefac, &o.zel_axis));
     SHQ_HIP(hipSetDevice(ctx->device));
-    SHQ_TRY(zel_slab_twiddles(ctx, N, &o.tw));
+    SHQ_TRY(slab_twiddles(ctx, ctx->zels_tw, ctx->zels_tw_n, N, &o.tw));
     o.nslab = nyl;
     o.y0 = y0;
     o.fac_mask = -1;
@@ -770,18 +758,8 @@ extern "C" int shq_zeldovich_slab_transfer(shq_context *ctx, int Nmesh, double B
  * all-to-all buffer [nranks][nplanes][N / nranks][zp / 2] complex the Y pass reads instead */
 extern "C" int shq_zeldovich_slab_fft_yz(shq_context *ctx, int Nmesh, void *d_planes, int nplanes, const void *d_packed, int nranks)
 {
-    SHQ_CHECK(ctx && d_planes, SHQ_ERR_INVALID, "zeldovich_slab_fft_yz: null argument");
-    const int N = Nmesh, zp = shq_zeldovich_slab_pitch(N);
-    SHQ_CHECK(zp > 0, SHQ_ERR_INVALID, "zeldovich_slab_fft_yz: mesh size %d has no bespoke FFT", N);
-    SHQ_CHECK(nplanes > 0 && nplanes <= N, SHQ_ERR_INVALID, "zeldovich_slab_fft_yz: bad arguments");
-    SHQ_CHECK(!d_packed || (nranks >= 1 && N % nranks == 0), SHQ_ERR_INVALID, "zeldovich_slab_fft_yz: %d ranks do not divide the mesh", nranks);
-    SHQ_HIP(hipSetDevice(ctx->device));
-    shq_fft_opts o;
-    SHQ_TRY(zel_slab_twiddles(ctx, N, &o.tw));
-    o.nslab = nplanes;
-    o.packed = (double *) const_cast<void *>(d_packed);
-    o.nranks = d_packed ? nranks : 1;
-    return shq_fft3d_run(ctx, (double *) d_planes, N, zp, d_packed ? SHQ_FFT_YZ_INVERSE_PACKED : SHQ_FFT_YZ_INVERSE, false, 1.0, nullptr, 0, 0, o);
+    return slab_fft_yz(ctx, "zeldovich_slab_fft_yz", &shq_context::zels_tw, &shq_context::zels_tw_n, Nmesh, d_planes, nplanes, 1, SLAB_EXP_ONE, d_packed,
+                       nranks);
 }
 
 /* pm_iterate_one's gather of d_mesh = [nalloc][N][zp] doubles (zp: the slab pitch, or N + 2 without a bespoke transform) at d_pos =
@@ -795,19 +773,16 @@ extern "C" int shq_zeldovich_slab_gather(shq_context *ctx, int Nmesh, double Box
     const int N = Nmesh;
     SHQ_TRY(mesh_check_size(N, "zeldovich_slab_gather"));
     SHQ_CHECK(isfinite(BoxSize) && BoxSize > 0, SHQ_ERR_INVALID, "zeldovich_slab_gather: BoxSize must be finite and > 0");
-    SHQ_CHECK(nplanes > 0 && nplanes <= N && plane0 >= 0 && plane0 < N && nalloc == (nplanes == N ? N : nplanes + 1), SHQ_ERR_INVALID,
-              "zeldovich_slab_gather: bad slab geometry");
+    SHQ_CHECK(slab_window_ok(N, plane0, nplanes, nalloc), SHQ_ERR_INVALID, "zeldovich_slab_gather: bad slab geometry");
     SHQ_HIP(hipSetDevice(ctx->device));
     hipStream_t s = ctx->stream;
-    SHQ_TRY(ctx->zels_flag.reserve(1));
-    SHQ_HIP(hipMemsetAsync(ctx->zels_flag.ptr, 0, sizeof(int), s));
+    SHQ_TRY(slab_flag_reset(ctx, ctx->zels_flag));
     if(n > 0)
         zel_gather_kernel<<<dim3(nblk(n, ZT)), dim3(ZT), 0, s>>>(n, (const double *) d_pos, (const double *) d_mesh, N, fft3d_route(N).zp,
                                                                   BoxSize / N, plane0, nalloc, (double *) d_out, ctx->zels_flag.ptr);
     SHQ_HIP(hipGetLastError());
-    int oob = 0;
-    SHQ_HIP(hipMemcpyAsync(&oob, ctx->zels_flag.ptr, sizeof(int), hipMemcpyDeviceToHost, s));
-    SHQ_HIP(hipStreamSynchronize(s));
+    int oob;
+    SHQ_TRY(slab_flag_read(ctx, ctx->zels_flag.ptr, &oob));
     SHQ_CHECK(!oob, SHQ_ERR_INVALID, "zeldovich_slab_gather: a particle lies outside this rank's slab (planes %d .. %d)", plane0, plane0 + nplanes - 1);
     return SHQ_OK;
 }

@@ -314,6 +314,140 @@ class SlabDecomp:
         return near if wide is False else near | wide
 
 
+class SlabMesh:
+    """What the drivers of a slab-decomposed mesh share (SlabPM, DistUVBG, DistZeldovich, DistGlass derive from it): the communicator,
+    the SlabDecomp `d`, the counted exchanges, the particles' route to their owners and back, the ghost planes, and the two routes
+    of the mesh transposes between the x-slabs [nxl, N, z] and the y-slab of the spectrum [N, nyl, z'] (x slowest) - torch.fft,
+    or the library's own FFT passes (csrc/fft3d.hip) through the callables of the driver's ops.
+    Counters: nalltoall (all-to-alls and shifts started through a2a / shift) and rows_sent (the rows that left this rank in the last
+    to_owners); a driver zeroes them when a call begins."""
+
+    def __init__(self, comm, Nmesh, BoxSize, ops, bounds=None, ycuts=None):
+        self.comm, self.ops, self.N, self.L = comm, ops, Nmesh, BoxSize
+        self.d = SlabDecomp(comm, Nmesh, BoxSize, bounds, ycuts)
+        self.rows_sent = self.nalltoall = 0
+
+    def _equal_widths(self):
+        if len(set(self.d.widths)) != 1:
+            raise ValueError("%s needs slabs of equal width (got %s)" % (type(self).__name__, self.d.widths))
+
+    def a2a(self, send, send_counts, recv_counts=None):
+        """Comm.all_to_all_rows, or with recv_counts all_to_all_rows_start (a handle to wait() for), counted"""
+        self.nalltoall += 1
+        if recv_counts is None:
+            return self.comm.all_to_all_rows(send, send_counts)
+        return self.comm.all_to_all_rows_start(send, send_counts, recv_counts)
+
+    def shift(self, t, direction):
+        self.nalltoall += 1
+        return self.comm.shift(t, direction)
+
+    def bespoke(self, pitch):
+        """the route of the transposes: the library's own FFT passes where it has the mesh size (pitch: doubles per z row, 0
+        without them), unless SHQ_SLAB_TORCH_FFT=1 asks for torch.fft"""
+        return pitch > 0 and os.environ.get("SHQ_SLAB_TORCH_FFT", "0") != "1"
+
+    # ---- particles: to the owner of their plane and back
+    def _send_sorted(self, rows, owner):
+        """the rows (a device tensor) to the ranks `owner` names, in one all-to-all; rows already at home stay in the self block.
+        Returns (the rows received, the stable sort by owner they left in, the counts sent, the counts received)."""
+        order = torch.argsort(owner, stable=True)
+        counts = torch.bincount(owner, minlength=self.comm.size).tolist()
+        got, rcounts = self.a2a(rows[order].contiguous(), counts)
+        return got, order, counts, rcounts
+
+    def to_owners(self, rows, owner):
+        """Returns (the rows this rank owns now, the route for back()) and records rows_sent."""
+        mine, order, counts, rcounts = self._send_sorted(rows, owner)
+        self.rows_sent = rows.shape[0] - counts[self.comm.rank]
+        return mine, (order, rcounts)
+
+    def back(self, route, cols):
+        """cols [rows owned, k]: results of the rows to_owners delivered, in that order.  They return along the same counts - the
+        order within a (source, destination) pair is kept, so no key travels - as a numpy array [n, k] in the caller's order."""
+        order, rcounts = route
+        got, _ = self.a2a(cols, rcounts)
+        out = np.empty((order.shape[0], cols.shape[1]))
+        out[order.cpu().numpy()] = got.cpu().numpy()
+        return out
+
+    # ---- ghost planes (nothing to do on one rank: the mesh is periodic in place)
+    def add_ghosts(self, bufs, nxl):
+        """the deposit ghost plane bufs[f][nxl] of every int64 field into the right-hand neighbour's plane 0: all fields in ONE
+        message; an integer add, exact"""
+        if self.comm.size > 1:
+            ghost = self.shift(torch.stack([b[nxl] for b in bufs]), +1)
+            for b, g in zip(bufs, ghost):
+                b[0] += g
+
+    def neighbour_plane(self, ext, nxl):
+        """the right-hand neighbour's first plane behind the own ones: one shift to the left"""
+        if self.comm.size > 1:
+            ext[nxl] = self.shift(ext[0:1].contiguous(), -1)[0]
+
+    # ---- the transposes' row order: x planes [nxl, N, z] <-> rows [rank q][x_l] of [nyl, z] blocks
+    def pack_rows(self, planes):
+        P, nxl, nyl = self.comm.size, self.d.nxl, self.N // self.comm.size
+        return planes.reshape(nxl, P, nyl, -1).permute(1, 0, 2, 3).reshape(P * nxl, nyl, -1)          # rows [dest q][x_l]
+
+    def unpack_rows(self, rows):
+        P, nxl, nyl = self.comm.size, self.d.nxl, self.N // self.comm.size
+        return rows.reshape(P, nxl, nyl, -1).permute(1, 0, 2, 3).reshape(nxl, self.N, -1)             # from rows [src q][x_l]
+
+    # ---- the torch.fft route: mesh sizes without a bespoke transform, and the CPU stand-ins
+    def forward_torch(self, real):
+        """real f64 [nxl, N, N] -> its unscaled spectrum on this rank's y-slab, complex [N, nyl, N / 2 + 1]"""
+        N, P, nxl = self.N, self.comm.size, self.d.nxl
+        spec = torch.fft.rfft2(real, dim=(1, 2))                                                     # [nxl, N, Nc], unscaled
+        recv, _ = self.a2a(self.pack_rows(spec).contiguous(), [nxl] * P)                             # rows [src p][x_l] = all x
+        return torch.fft.fft(recv.reshape(N, N // P, N // 2 + 1), dim=0).contiguous()
+
+    def back_torch(self, spec):
+        """the y-slab spectrum [N, nyl, N / 2 + 1] -> the real mesh of this rank's planes f64 [nxl, N, N], unscaled"""
+        N = self.N
+        out = torch.fft.ifft(spec, dim=0, norm="forward").contiguous()                               # rows = x planes, in order
+        recv, _ = self.a2a(out, self.d.widths)                                                       # rows [src q][x_l]
+        return torch.fft.irfft2(self.unpack_rows(recv), s=(N, N), dim=(1, 2), norm="forward")
+
+    # ---- the bespoke route: planes [nxl, N, zp] doubles, the y-slab [N, nyl, zp / 2] complex
+    def forward_bespoke(self, own, yz_forward):
+        """The Y/Z forward of the planes `own` and the exchange, started: yz_forward(packed) runs the passes, storing into the
+        all-to-all buffer `packed`, rows [dest q][x_l] - or in place for None, on a lone process, whose planes are the y-slab
+        already.  Returns the pending spectrum: wait() for it."""
+        P, nxl = self.comm.size, self.d.nxl
+        if not self.comm.multi:
+            yz_forward(None)
+            return _Done(own.view(torch.float64).view(torch.complex128))
+        send = torch.empty((P * nxl, self.N // P, own.shape[2] // 2), dtype=torch.complex128, device=own.device)
+        yz_forward(send)
+        return self.a2a(send, [nxl] * P, self.d.widths)                                              # [x (all)][y_l][z']
+
+    def back_bespoke(self, planes, like, xpass, yz_inverse, inflight=1):
+        """The way back of len(planes) fields, one after another; yields f once field f's real mesh stands in planes[f] (the same
+        buffer for all, or one each).  xpass(f, out) queues the field's out-of-place X pass (inverse) from the kept y-slab into
+        `out`, shaped as `like`; yz_inverse(f, packed) the Y/Z inverse into planes[f] from the received rows.  `inflight`
+        exchanges are kept started ahead of the one waited for: field f + inflight's pass is queued before field f's exchange is
+        waited for.  On a lone process the X pass lands where the Y/Z inverse (packed None) takes it."""
+        nf, P, nxl = len(planes), self.comm.size, self.d.nxl
+
+        def start(f):
+            out = torch.empty_like(like)
+            xpass(f, out)
+            return self.a2a(out, self.d.widths, [nxl] * P)                                           # rows [src q][x_l]
+
+        pend = [start(f) for f in range(min(inflight, nf))] if self.comm.multi else None
+        for f in range(nf):
+            if pend is None:
+                xpass(f, planes[f].view(torch.float64).view(torch.complex128))
+                yz_inverse(f, None)
+            else:
+                packed = pend.pop(0).wait().contiguous()
+                if f + inflight < nf:
+                    pend.append(start(f + inflight))
+                yz_inverse(f, packed)
+            yield f
+
+
 def balanced_bounds(comm, Nmesh, BoxSize, x, weights=None, plane_cost=0.0, y=None):
     """Plane boundaries giving every rank about the same share of the work (x: positions held by this rank, any
     distribution).  Work of a plane = the sum of `weights` over its particles (1 each when None: equal counts) +
@@ -531,13 +665,15 @@ def widen_until_covered(comm, hfac, start_radius, attempt):
         halo = hfac * max(tried, halo)
 
 
-class SlabPM:
-    """Distributed PM force for the particles this rank owns."""
+class SlabPM(SlabMesh):
+    """Distributed PM force for the particles this rank owns.  Of SlabMesh it takes the route decision and the transposes' row
+    order; its two pipelines are its own: the torch.fft one keeps the spectrum as [y_l][z'][x] for shq_pm_slab_green, the bespoke
+    one has the walk hooks and the split X step, and with slabs cut below the plane two deposit ghost planes travel and potential
+    planes come from both neighbours."""
 
     def __init__(self, comm, Nmesh, BoxSize, Asmth, G, ops, bounds=None, ycuts=None):
-        self.comm, self.ops = comm, ops
-        self.N, self.L, self.Asmth, self.G = Nmesh, BoxSize, Asmth, G
-        self.d = SlabDecomp(comm, Nmesh, BoxSize, bounds, ycuts)
+        super().__init__(comm, Nmesh, BoxSize, ops, bounds, ycuts)
+        self.Asmth, self.G = Asmth, G
         self.power = self.power_finish = None
 
     def force(self, hooks=(), analysis=None, measure_power=False):
@@ -556,7 +692,7 @@ class SlabPM:
         split = analysis is not None or measure_power
         self.power = self.power_finish = None
         xstep = (lambda spec_t, y0, nyl, xfwd, xfin: self._xsplit(spec_t, y0, nyl, xfwd, xfin, analysis, measure_power)) if split else None
-        if getattr(self.ops, "pitch", None) is not None and self.ops.pitch() > 0 and os.environ.get("SHQ_SLAB_TORCH_FFT", "0") != "1":
+        if getattr(self.ops, "pitch", None) is not None and self.bespoke(self.ops.pitch()):
             return self._force_bespoke(list(hooks), xstep)
         self._force_torch(xstep)
         for h in hooks:
@@ -593,12 +729,10 @@ class SlabPM:
             buf[xoff:xoff + dg] += ghost
         own = buf[xoff:xoff + nxl]
         nyl = N // P
-        # the pack / unpack around the transposes: fused into the Y pass of the FFT (SHQ_DIST_FUSED_PACK=0: torch permute copies)
-        fused = multi and hasattr(ops, "fft_yz_packed") and os.environ.get("SHQ_DIST_FUSED_PACK", "1") != "0"
-        if fused:
+        if multi:      # the pack / unpack around the transposes is fused into the Y pass of the FFT
             send = torch.empty((P * nxl, nyl, zpc), dtype=torch.complex128, device=buf.device)      # rows [dest q][x_l]
             ops.fft_yz_packed(own, nxl, 0, send, P)
-        else:
+        else:          # a lone process: nothing to pack, the planes are the y-slab
             ops.fft_yz(own, nxl, 0)
         spec = own.view(torch.float64).view(torch.complex128)               # [nxl, N, zpc]
         hooks = list(hooks) + [None, None]
@@ -606,8 +740,6 @@ class SlabPM:
         if xstep is not None:
             hooks[0] = None          # queued beside hooks[1] instead, behind the return transpose (force())
         if multi:
-            if not fused:
-                send = spec.reshape(nxl, P, nyl, zpc).permute(1, 0, 2, 3).reshape(P * nxl, nyl, zpc)   # rows [dest q][x_l]
             pend = c.all_to_all_rows_start(send, [nxl] * P, self.d.widths)                         # [x (all)][y_l][z']
             del send
             if hooks[0]:
@@ -629,17 +761,13 @@ class SlabPM:
             if hooks[1]:
                 hooks[1]()
             recv = pend.wait()                                                                     # rows [src q][x_l]
-            if fused:
-                ops.fft_yz_packed(own, nxl, 1, recv.contiguous(), P)
-            else:
-                spec.copy_(recv.reshape(P, nxl, nyl, zpc).permute(1, 0, 2, 3).reshape(nxl, N, zpc))
+            ops.fft_yz_packed(own, nxl, 1, recv.contiguous(), P)
             del recv, pend
         else:
             if deferred:
                 deferred()
             if hooks[1]:
                 hooks[1]()
-        if not fused:
             ops.fft_yz(own, nxl, 1)
         phi = buf.view(torch.float64)
         if P > 1:
@@ -663,8 +791,7 @@ class SlabPM:
         # 2. forward: 2-D r2c over (y, z), transpose (x-slabs -> equal y-slabs), 1-D along x
         spec = torch.fft.rfft2(real[..., :N], dim=(1, 2))              # [nxl, N, Nc], unscaled
         nyl = N // P
-        send = spec.reshape(nxl, P, nyl, Nc).permute(1, 0, 2, 3).reshape(P * nxl, nyl, Nc)   # rows [dest q][x_l]
-        recv, _ = c.all_to_all_rows(send, [nxl] * P)                                         # rows [src p][x_l] = all x
+        recv, _ = c.all_to_all_rows(self.pack_rows(spec), [nxl] * P)                         # rows [src p][x_l] = all x
         spec_t = recv.reshape(N, nyl, Nc).permute(1, 2, 0).contiguous()                      # [y_l][z][x]
         spec_t = torch.fft.fft(spec_t, dim=2)
         # 3. Green's function / CIC deconvolution on the transposed spectrum (split around the P(k) all-reduce for an analysis hook)
@@ -676,8 +803,7 @@ class SlabPM:
         spec_t = torch.fft.ifft(spec_t, dim=2, norm="forward")
         send = spec_t.permute(2, 0, 1).contiguous()                                          # rows = x planes, in order
         recv, _ = c.all_to_all_rows(send, widths)                                            # rows [src q][x_l]
-        spec = recv.reshape(P, nxl, nyl, Nc).permute(1, 0, 2, 3).reshape(nxl, N, Nc)
-        phi = torch.fft.irfft2(spec, s=(N, N), dim=(1, 2), norm="forward")                   # [nxl, N, N], unscaled
+        phi = torch.fft.irfft2(self.unpack_rows(recv), s=(N, N), dim=(1, 2), norm="forward")  # [nxl, N, N], unscaled
         # 5. potential ghost planes (2 from the left neighbour, 3 from the right) and readout
         if P > 1:
             ext = self.ops.empty((nxl + 2 + pr, N, N + 2), torch.float64)
@@ -1908,6 +2034,32 @@ class GpuBhOps:
         return ns.value, nb.value
 
 
+class _DeviceOps:
+    """What the device ops of the slab mesh drivers share (GpuUvbgOps, GpuZeldovichOps, GpuGlassOps): the library context, torch's
+    device, and a library call on torch tensors between the two stream hand-overs."""
+
+    def __init__(self, ctx, device=None):
+        self.ctx = ctx
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+        self._hand = _StreamHandover(ctx, self.device)
+
+    def _call(self, fn, *args):
+        self._hand.before()
+        capi.check(fn(self.ctx.h, *args), fn.__name__)
+        self._hand.after()
+
+    @staticmethod
+    def _p(t):
+        return None if t is None else C.c_void_p(t.data_ptr())
+
+    def full(self, shape, value, dtype):
+        return torch.full(shape, value, dtype=dtype, device=self.device)
+
+    def to_real(self, mesh_i, exp):
+        """the fixed-point deposit of scale 2^(61 - exp) as doubles (the torch.fft route; the bespoke Y/Z forward converts itself)"""
+        return mesh_i.to(torch.float64) * math.ldexp(1.0, exp - 61)
+
+
 def uvbg_radii(p):
     """petapm_reion_c2r's radius schedule (petapm.cpp:536-606) from the parameters alone: the same list on every rank, the last
     entry the unfiltered cell-size step"""
@@ -1923,7 +2075,7 @@ def uvbg_radii(p):
     return radii
 
 
-class DistUVBG:
+class DistUVBG(SlabMesh):
     """calculate_uvbg + petapm_reion (uvbg.cpp:474-597, petapm.cpp:495-685) on x-slabs of the UVBGdim mesh, one per rank: whole
     planes, equal widths unless `bounds` says otherwise (the PM's slabs live on another mesh and may be cut below a plane: they are
     not reused).  UVBGdim must be divisible by the rank count (equal y-slabs of the spectrum): otherwise the constructor raises
@@ -1944,20 +2096,9 @@ class DistUVBG:
     COLS = 9     # x, y, z, Mass, Type, f_esc, Sfr, local_J21, zreion: one float64 row per particle (Type and float Mass are exact)
 
     def __init__(self, comm, UVBGdim, BoxSize, ops, bounds=None):
-        self.comm, self.ops, self.N, self.L = comm, ops, int(UVBGdim), float(BoxSize)
-        self.d = SlabDecomp(comm, self.N, self.L, bounds)
-        self.rows_sent = self.nradii = self.nalltoall = 0
+        super().__init__(comm, int(UVBGdim), float(BoxSize), ops, bounds)
+        self.nradii = 0
         self.J21 = self.xHI = None
-
-    def _a2a(self, send, send_counts, recv_counts=None):
-        self.nalltoall += 1
-        if recv_counts is None:
-            return self.comm.all_to_all_rows(send, send_counts)
-        return self.comm.all_to_all_rows_start(send, send_counts, recv_counts)
-
-    def _shift(self, t, direction):
-        self.nalltoall += 1
-        return self.comm.shift(t, direction)
 
     def calculate(self, p, cosmo, pos, mass, types, fesc, sfr, local_J21, zreion):
         """p: capi.UvbgParams, cosmo: capi.UvbgCosmo; pos [n, 3], mass, types, fesc (in / out), sfr (may be None without
@@ -1977,11 +2118,7 @@ class DistUVBG:
         rows[:, 7], rows[:, 8] = local_J21, zreion
         rows = torch.from_numpy(rows).to(ops.device)
         # ---- to the owner of the particle's UVBG plane; rows already at home stay in the self block
-        owner = d.owner_of(rows[:, 0])
-        order = torch.argsort(owner, stable=True)
-        counts = torch.bincount(owner, minlength=c.size).tolist()
-        self.rows_sent = n - counts[c.rank]
-        mine, rcounts = self._a2a(rows[order].contiguous(), counts)
+        mine, route = self.to_owners(rows, d.owner_of(rows[:, 0]))
         posm = mine[:, 0:4].contiguous()
         ty = mine[:, 4].to(torch.uint8).contiguous()
         col = [mine[:, k].contiguous() for k in range(5, 9)]
@@ -2003,25 +2140,17 @@ class DistUVBG:
         bufs = ops.deposit(p, posm, ty, f_esc, s_fr, exps, d.plane0, nxl, nalloc)     # int64 [nalloc, N, pitch] per field
         nf = 3 if use_sfr else 2
         assert len(bufs) == nf
-        if P > 1:      # the ghost planes of all fields in one message to the right neighbour; integer add: exact
-            ghost = self._shift(torch.stack([b[nxl] for b in bufs]), +1)
-            for f in range(nf):
-                bufs[f][0] += ghost[f]
+        self.add_ghosts(bufs, nxl)
         self._J21ext = ops.full((nalloc, N, N), 0.0, torch.float32)     # the own planes, then room for the right neighbour's first
         self.J21 = self._J21ext[:nxl]
         self.xHI = ops.full((nxl, N, N), 1.0, torch.float32)
-        bespoke = getattr(ops, "pitch", None) is not None and ops.pitch() > 0 and os.environ.get("SHQ_SLAB_TORCH_FFT", "0") != "1"
-        part = (self._loop_bespoke if bespoke else self._loop_torch)(p, cosmo, bufs, exps, radii)
+        part = (self._loop_bespoke if self.bespoke(ops.pitch()) else self._loop_torch)(p, cosmo, bufs, exps, radii)
         # ---- UVBGgrids' globals (uvbg.cpp:446-451) and readout_J21 with the right neighbour's first plane behind the own ones
         tot = c.allreduce_sum_vec(np.asarray(part, dtype=np.float64))
         vol, mw = tot[0] / float(N ** 3), tot[1] / tot[2]
-        if P > 1:
-            self._J21ext[nxl] = self._shift(self.J21[0:1].contiguous(), -1)[0]
+        self.neighbour_plane(self._J21ext, nxl)
         ops.readout(p, cosmo, posm, ty, self._J21ext, d.plane0, nxl, lj, zr)
-        # ---- the three results return along the same counts: the order within a (source, destination) pair is kept, so no key travels
-        back, _ = self._a2a(torch.stack([f_esc, lj, zr], dim=1), rcounts)
-        res = np.empty((n, 3))
-        res[order.cpu().numpy()] = back.cpu().numpy()
+        res = self.back(route, torch.stack([f_esc, lj, zr], dim=1))
         fesc[:], local_J21[:], zreion[:] = res[:, 0], res[:, 1], res[:, 2]
         return float(vol), float(mw), len(radii)
 
@@ -2031,39 +2160,23 @@ class DistUVBG:
         the y-slab.  Per radius and field: the filter pass out of place, ONE all-to-all back, Y/Z inverse; then the cell loop."""
         c, ops, N, P, nxl = self.comm, self.ops, self.N, self.comm.size, self.d.nxl
         zp = ops.pitch()
-        zpc, nyl, y0 = zp // 2, N // P, c.rank * (N // P)
-        widths, multi = self.d.widths, c.multi
+        nyl, y0 = N // P, c.rank * (N // P)
         own = [b[:nxl] for b in bufs]
-        pend = []
-        for f, o in enumerate(own):
-            if multi:
-                send = torch.empty((P * nxl, nyl, zpc), dtype=torch.complex128, device=o.device)      # rows [dest q][x_l]
-                ops.fft_yz(o, nxl, 0, exps[f], send, P)
-                pend.append(self._a2a(send, [nxl] * P, widths))                                       # [x (all)][y_l][z']
-            else:
-                ops.fft_yz(o, nxl, 0, exps[f], None, 1)
-                pend.append(_Done(o.view(torch.float64).view(torch.complex128).clone()))
+        pend = [self.forward_bespoke(o, lambda packed, f=f, o=o: ops.fft_yz(o, nxl, 0, exps[f], packed, P)) for f, o in enumerate(own)]
         kept = []
         for pe in pend:
             spec_t = pe.wait().contiguous()
+            if not c.multi:       # a lone process: the planes are the y-slab, and every radius writes them again
+                spec_t = spec_t.clone()
             ops.xforward(spec_t, y0, nyl)
             kept.append(spec_t)
         real = [b.view(torch.float64) for b in bufs]
         part = None
         for r, R in enumerate(radii):
-            pend = []
-            for f, spec_t in enumerate(kept):
-                if multi:
-                    out = torch.empty_like(spec_t)
-                    ops.xfilter(spec_t, out, y0, nyl, r)
-                    pend.append(self._a2a(out, widths, [nxl] * P))                                    # rows [src q][x_l]
-                else:       # the filtered planes land where the Y/Z inverse takes them
-                    ops.xfilter(spec_t, own[f].view(torch.float64).view(torch.complex128), y0, nyl, r)
-            for f, o in enumerate(own):
-                if multi:
-                    ops.fft_yz(o, nxl, 1, 0, pend[f].wait().contiguous(), P)
-                else:
-                    ops.fft_yz(o, nxl, 1, 0, None, 1)
+            # every field's exchange in flight at once, each from a buffer of its own: the cell loop needs them all
+            for _ in self.back_bespoke(own, kept[0], lambda f, out: ops.xfilter(kept[f], out, y0, nyl, r),
+                                       lambda f, packed: ops.fft_yz(own[f], nxl, 1, 0, packed, P), inflight=len(own)):
+                pass
             part = ops.cells(p, cosmo, R, r == len(radii) - 1, real, zp, nxl, self.J21, self.xHI)
         return part
 
@@ -2071,48 +2184,21 @@ class DistUVBG:
         """The same loop with torch.fft for mesh sizes without a bespoke transform, and on the CPU stand-ins: the spectrum is kept as
         [x][y_l][z'], x slowest, as the all-to-all delivers it."""
         c, ops, N, P, nxl = self.comm, self.ops, self.N, self.comm.size, self.d.nxl
-        Nc, nyl, y0 = N // 2 + 1, N // P, c.rank * (N // P)
-        widths = self.d.widths
-        kept = []
-        for f, b in enumerate(bufs):
-            real = ops.to_real(b[:nxl, :, :N], exps[f])                                          # f64 [nxl, N, N]
-            spec = torch.fft.rfft2(real, dim=(1, 2))                                             # [nxl, N, Nc], unscaled
-            send = spec.reshape(nxl, P, nyl, Nc).permute(1, 0, 2, 3).reshape(P * nxl, nyl, Nc)   # rows [dest q][x_l]
-            recv, _ = self._a2a(send.contiguous(), [nxl] * P)                                    # rows [src p][x_l] = all x
-            kept.append(torch.fft.fft(recv.reshape(N, nyl, Nc), dim=0).contiguous())
+        nyl, y0 = N // P, c.rank * (N // P)
+        kept = [self.forward_torch(ops.to_real(b[:nxl, :, :N], exps[f])) for f, b in enumerate(bufs)]
         part = None
         for r, R in enumerate(radii):
-            real = []
-            for spec_t in kept:
-                out = ops.filter(spec_t.clone(), y0, nyl, r)
-                out = torch.fft.ifft(out, dim=0, norm="forward").contiguous()                    # rows = x planes, in order
-                recv, _ = self._a2a(out, widths)                                                 # rows [src q][x_l]
-                spec = recv.reshape(P, nxl, nyl, Nc).permute(1, 0, 2, 3).reshape(nxl, N, Nc)
-                real.append(torch.fft.irfft2(spec, s=(N, N), dim=(1, 2), norm="forward").contiguous())   # [nxl, N, N], unscaled
+            real = [self.back_torch(ops.filter(spec_t.clone(), y0, nyl, r)).contiguous() for spec_t in kept]     # [nxl, N, N] each
             part = ops.cells(p, cosmo, R, r == len(radii) - 1, real, N, nxl, self.J21, self.xHI)
         return part
 
 
-class GpuUvbgOps:
+class GpuUvbgOps(_DeviceOps):
     """DistUVBG's phases on the device library (shq_uvbg_slab_*), on torch tensors of the context's device."""
 
     def __init__(self, ctx, device=None):
-        self.ctx = ctx
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        self._hand = _StreamHandover(ctx, self.device)
+        super().__init__(ctx, device)
         self.N = None
-
-    def _call(self, fn, *args):
-        self._hand.before()
-        capi.check(fn(self.ctx.h, *args), fn.__name__)
-        self._hand.after()
-
-    @staticmethod
-    def _p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-
-    def full(self, shape, value, dtype):
-        return torch.full(shape, value, dtype=dtype, device=self.device)
 
     def pitch(self):
         return int(capi.hip.shq_uvbg_slab_pitch(self.N))
@@ -2150,9 +2236,6 @@ class GpuUvbgOps:
         assert spec_t.is_contiguous() and out.is_contiguous() and out.dtype == torch.complex128 and out.shape == spec_t.shape
         self._call(capi.hip.shq_uvbg_slab_xfilter, self.N, self._p(spec_t), self._p(out), y0, nyl, r)
 
-    def to_real(self, mesh_i, exp):
-        return mesh_i.to(torch.float64) * math.ldexp(1.0, exp - 61)
-
     def filter(self, spec_t, y0, nyl, r):
         assert spec_t.is_contiguous() and spec_t.dtype == torch.complex128
         self._call(capi.hip.shq_uvbg_slab_filter, self.N, self._p(spec_t), self._p(spec_t), y0, nyl, r)
@@ -2172,7 +2255,7 @@ class GpuUvbgOps:
                    J21ext.shape[0], self._p(local_J21), self._p(zreion))
 
 
-class DistZeldovich:
+class DistZeldovich(SlabMesh):
     """displacement_fields (libgenic/zeldovich.cpp:150-264) on x-slabs of the Nmesh mesh, one per rank: whole planes of equal width.
     Nmesh must be divisible by the rank count (equal y-slabs of the spectrum): otherwise the constructor raises ValueError on every
     rank, before any collective.
@@ -2193,23 +2276,10 @@ class DistZeldovich:
     (whether the field was filled rather than reused).  Nothing here has run on more than one GPU."""
 
     def __init__(self, comm, Nmesh, BoxSize, ops, bounds=None):
-        self.comm, self.ops, self.N, self.L = comm, ops, int(Nmesh), float(BoxSize)
-        self.d = SlabDecomp(comm, self.N, self.L, bounds)
-        if len(set(self.d.widths)) != 1:
-            raise ValueError("DistZeldovich needs slabs of equal width (got %s)" % (self.d.widths,))
-        self.rows_sent = self.nalltoall = 0
+        super().__init__(comm, int(Nmesh), float(BoxSize), ops, bounds)
+        self._equal_widths()
         self.filled = False
         self._key = self._spec = None
-
-    def _a2a(self, send, send_counts, recv_counts=None):
-        self.nalltoall += 1
-        if recv_counts is None:
-            return self.comm.all_to_all_rows(send, send_counts)
-        return self.comm.all_to_all_rows_start(send, send_counts, recv_counts)
-
-    def _shift(self, t, direction):
-        self.nalltoall += 1
-        return self.comm.shift(t, direction)
 
     def _refusal(self, params, delta, growth, pos):
         """what is wrong with this rank's input, or None"""
@@ -2244,7 +2314,6 @@ class DistZeldovich:
             raise ValueError(why or "zeldovich: another rank refused its input")
         scaledep = bool(params.ScaleDepVelocity)
         self.rows_sent = self.nalltoall = 0
-        n = len(pos)
         # ---- to the owner of the particle's CIC base plane; rows already at home stay in the self block
         # SlabDecomp.owner_of's floor(x / cell) % N, taken on the host: numpy divides as cic_setup does, while torch on the device
         # multiplies by the reciprocal of a scalar divisor - at nextafter(BoxSize, 0) that is plane N - 1 where the kernel sees cell
@@ -2252,10 +2321,7 @@ class DistZeldovich:
         rows = torch.from_numpy(pos).to(ops.device)
         plane = np.floor(pos[:, 0] / d.cell).astype(np.int64) % N
         owner = torch.from_numpy(np.searchsorted(np.asarray(d.bounds[1:-1], dtype=np.int64), plane, side="right")).to(ops.device)
-        order = torch.argsort(owner, stable=True)
-        counts = torch.bincount(owner, minlength=c.size).tolist()
-        self.rows_sent = n - counts[c.rank]
-        mine, rcounts = self._a2a(rows[order].contiguous(), counts)
+        mine, route = self.to_owners(rows, owner)
         mine = mine.contiguous()
         # ---- the Gaussian field of this rank's y-slab, kept across calls
         P, nxl = c.size, d.nxl
@@ -2269,21 +2335,13 @@ class DistZeldovich:
         ops.tables(N, L, delta, growth if scaledep else None)
         nf = 7 if scaledep else 4
         fld = ops.full((7, mine.shape[0]), 0.0, torch.float64)
-        bespoke = ops.pitch(N) > 0 and os.environ.get("SHQ_SLAB_TORCH_FFT", "0") != "1"
-        (self._loop_bespoke if bespoke else self._loop_torch)(mine, fld, nf)
+        (self._loop_bespoke if self.bespoke(ops.pitch(N)) else self._loop_torch)(mine, fld, nf)
         # ---- the particle loop, the two maxima, and the way back along the same counts: no key travels
         pos_out, vel, disp, mx = ops.finalize(mine, fld, scaledep, float(params.vel_prefac), L)
         mx = c.allreduce_max_vec(np.asarray(mx, dtype=np.float64))
-        back, _ = self._a2a(torch.cat([pos_out, vel, disp, fld[0][:, None]], dim=1).contiguous(), rcounts)
-        res = np.empty((n, 10))
-        res[order.cpu().numpy()] = back.cpu().numpy()
+        res = self.back(route, torch.cat([pos_out, vel, disp, fld[0][:, None]], dim=1).contiguous())
         return dict(Pos=res[:, 0:3].copy(), Vel=res[:, 3:6].copy(), Disp=res[:, 6:9].copy(), Density=res[:, 9].copy(), maxdisp=float(mx[0]),
                     maxvel=float(mx[1]))
-
-    def _neighbour_plane(self, ext, nxl):
-        """the right-hand neighbour's first plane behind the own ones: one shift to the left"""
-        if self.comm.size > 1:
-            ext[nxl] = self._shift(ext[0:1].contiguous(), -1)[0]
 
     def _loop_bespoke(self, pos, fld, nf):
         """The library's own FFT passes (csrc/fft3d.hip).  Per field: the transfer pass out of place on the kept y-slab, ONE
@@ -2292,26 +2350,13 @@ class DistZeldovich:
         c, ops, N, L, P, nxl, plane0 = self.comm, self.ops, self.N, self.L, self.comm.size, self.d.nxl, self.d.plane0
         zp = ops.pitch(N)
         nyl, y0 = N // P, c.rank * (N // P)
-        widths, multi, spec = self.d.widths, c.multi, self._spec
+        spec = self._spec
         nalloc = N if P == 1 else nxl + 1
         ext = ops.full((nalloc, N, zp), 0.0, torch.float64)
         own = ext[:nxl]
-
-        def start(f):
-            out = torch.empty_like(spec)
-            ops.xtransfer(N, L, spec, out, y0, nyl, f)
-            return self._a2a(out, widths, [nxl] * P)                                             # rows [src q][x_l]
-
-        pend = start(0) if multi else None
-        for f in range(nf):
-            if multi:
-                packed = pend.wait().contiguous()
-                pend = start(f + 1) if f + 1 < nf else None
-                ops.fft_yz(N, own, nxl, packed, P)
-            else:       # the planes land where the Y/Z inverse takes them
-                ops.xtransfer(N, L, spec, own.view(torch.complex128), y0, nyl, f)
-                ops.fft_yz(N, own, nxl, None, 1)
-            self._neighbour_plane(ext, nxl)
+        for f in self.back_bespoke([own] * nf, spec, lambda f, out: ops.xtransfer(N, L, spec, out, y0, nyl, f),
+                                   lambda f, packed: ops.fft_yz(N, own, nxl, packed, P)):
+            self.neighbour_plane(ext, nxl)
             ops.gather(N, L, pos, ext, plane0, nxl, fld[f])
 
     def _loop_torch(self, pos, fld, nf):
@@ -2323,33 +2368,13 @@ class DistZeldovich:
         nalloc = N if P == 1 else nxl + 1
         ext = ops.full((nalloc, N, N + 2), 0.0, torch.float64)
         for f in range(nf):
-            out = torch.fft.ifft(ops.transfer(N, L, spec, y0, nyl, f), dim=0, norm="forward").contiguous()   # rows = x planes, in order
-            recv, _ = self._a2a(out, self.d.widths)                                                          # rows [src q][x_l]
-            sp = recv.reshape(P, nxl, nyl, Nc).permute(1, 0, 2, 3).reshape(nxl, N, Nc)
-            ext[:nxl, :, :N] = torch.fft.irfft2(sp, s=(N, N), dim=(1, 2), norm="forward")                    # unscaled
-            self._neighbour_plane(ext, nxl)
+            ext[:nxl, :, :N] = self.back_torch(ops.transfer(N, L, spec, y0, nyl, f))
+            self.neighbour_plane(ext, nxl)
             ops.gather(N, L, pos, ext, plane0, nxl, fld[f])
 
 
-class GpuZeldovichOps:
+class GpuZeldovichOps(_DeviceOps):
     """DistZeldovich's phases on the device library (shq_zeldovich_slab_*), on torch tensors of the context's device."""
-
-    def __init__(self, ctx, device=None):
-        self.ctx = ctx
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        self._hand = _StreamHandover(ctx, self.device)
-
-    def _call(self, fn, *args):
-        self._hand.before()
-        capi.check(fn(self.ctx.h, *args), fn.__name__)
-        self._hand.after()
-
-    @staticmethod
-    def _p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-
-    def full(self, shape, value, dtype):
-        return torch.full(shape, value, dtype=dtype, device=self.device)
 
     def pitch(self, N):
         return int(capi.hip.shq_zeldovich_slab_pitch(int(N)))
@@ -2407,7 +2432,7 @@ class _GlassState:
         return torch.cat([self.pos[sel], self.vel[sel].to(torch.float64), self.mass[sel].to(torch.float64)[:, None], self.tag[sel]], dim=1)
 
 
-class DistGlass:
+class DistGlass(SlabMesh):
     """glass_evolve (libgenic/glass.cpp:76-360) on x-slabs of the Nmesh mesh, one per rank: whole planes of equal width.  Nmesh must
     be divisible by the rank count (equal y-slabs of the spectrum): otherwise the constructor raises ValueError on every rank, before
     any collective.
@@ -2447,22 +2472,9 @@ class DistGlass:
     Nothing here has run on more than one GPU."""
 
     def __init__(self, comm, Nmesh, BoxSize, ops, bounds=None):
-        self.comm, self.ops, self.N, self.L = comm, ops, int(Nmesh), float(BoxSize)
-        self.d = SlabDecomp(comm, self.N, self.L, bounds)
-        if len(set(self.d.widths)) != 1:
-            raise ValueError("DistGlass needs slabs of equal width (got %s)" % (self.d.widths,))
-        self.rows_sent = self.nalltoall = 0
+        super().__init__(comm, int(Nmesh), float(BoxSize), ops, bounds)
+        self._equal_widths()
         self.rehomed = []
-
-    def _a2a(self, send, send_counts, recv_counts=None):
-        self.nalltoall += 1
-        if recv_counts is None:
-            return self.comm.all_to_all_rows(send, send_counts)
-        return self.comm.all_to_all_rows_start(send, send_counts, recv_counts)
-
-    def _shift(self, t, direction):
-        self.nalltoall += 1
-        return self.comm.shift(t, direction)
 
     def _refusal(self, pos, vel, mass, nsteps):
         """what is wrong with this rank's input, or None: the checks of shq_glass_evolve"""
@@ -2486,28 +2498,22 @@ class DistGlass:
                 return "glass: a position is not finite or beyond 2^30 cells"
         return None
 
+    def _owner(self, pos):
+        """the owner of each position's CIC base plane, which the device takes with the kernels' own cell arithmetic"""
+        return torch.div(self.ops.planes(self.N, self.L, pos), self.d.nxl, rounding_mode="floor").to(torch.int64)
+
     def _home(self, rows):
         """rows (positions in columns 0 .. 2) to the owners of their CIC base planes; the block that stays is not copied through
-        the network.  Returns (the rows this rank owns now, how many left it)."""
-        c, ops = self.comm, self.ops
-        planes = ops.planes(self.N, self.L, rows[:, 0:3].contiguous())
-        owner = torch.div(planes, self.d.nxl, rounding_mode="floor").to(torch.int64)
-        order = torch.argsort(owner, stable=True)
-        counts = torch.bincount(owner, minlength=c.size).tolist()
-        got, _ = self._a2a(rows[order].contiguous(), counts)
-        return got.contiguous(), rows.shape[0] - counts[c.rank]
+        the network.  Returns the rows this rank owns now; how many left it is rows_sent."""
+        mine, _ = self.to_owners(rows, self._owner(rows[:, 0:3].contiguous()))
+        return mine.contiguous()
 
     def _rehome(self, S):
         """after a drift: the rows whose base plane changed owner travel in one all-to-all; the others stay where they are"""
-        c = self.comm
-        planes = self.ops.planes(self.N, self.L, S.pos)
-        owner = torch.div(planes, self.d.nxl, rounding_mode="floor").to(torch.int64)
-        away = owner != c.rank
+        owner = self._owner(S.pos)
+        away = owner != self.comm.rank
         idx = torch.nonzero(away).flatten()
-        dest = owner[idx]
-        order = torch.argsort(dest, stable=True)
-        counts = torch.bincount(dest, minlength=c.size).tolist()
-        got, _ = self._a2a(S.rows(idx[order]).contiguous(), counts)
+        got = self._send_sorted(S.rows(idx), owner[idx])[0]
         self.rehomed.append(int(idx.numel()))
         if idx.numel() or got.shape[0]:
             keep = torch.nonzero(~away).flatten()
@@ -2542,11 +2548,10 @@ class DistGlass:
         # ---- to the owners of the base planes, with the origin tag
         rows = np.empty((n, 9))
         rows[:, 0:3], rows[:, 3:6], rows[:, 6], rows[:, 7], rows[:, 8] = pos, vel, mass, c.rank, np.arange(n)
-        mine, self.rows_sent = self._home(torch.from_numpy(rows).to(ops.device))
-        S = _GlassState(mine, ops)
+        S = _GlassState(self._home(torch.from_numpy(rows).to(ops.device)), ops)
         P, nxl = c.size, d.nxl
         nalloc = N if P == 1 else nxl + 1
-        bespoke = ops.pitch(N) > 0 and os.environ.get("SHQ_SLAB_TORCH_FFT", "0") != "1"
+        bespoke = self.bespoke(ops.pitch(N))
         zp = ops.pitch(N) if bespoke else N + 2
         self._buf = ops.full((nalloc, N, zp), 0, torch.int64)          # the deposit, then (bespoke) its (y, z) half spectrum
         self._ext = ops.full((nalloc, N, zp), 0.0, torch.float64)      # a force's real mesh and the neighbour's first plane
@@ -2566,11 +2571,8 @@ class DistGlass:
             stats.append(ops.particles(S.pos, S.vel, S.disp, True, False))
         self._buf = self._ext = None
         # ---- the way back by the tag, and the reductions
-        orig = S.tag[:, 0].to(torch.int64)
-        order = torch.argsort(orig, stable=True)
-        back, _ = self._a2a(torch.cat([S.pos, S.vel.to(torch.float64), S.disp.to(torch.float64), S.tag[:, 1:2]], dim=1)[order].contiguous(),
-                            torch.bincount(orig, minlength=P).tolist())
-        back = back.cpu().numpy()
+        back = self._send_sorted(torch.cat([S.pos, S.vel.to(torch.float64), S.disp.to(torch.float64), S.tag[:, 1:2]], dim=1),
+                                 S.tag[:, 0].to(torch.int64))[0].cpu().numpy()
         assert len(back) == n
         at = back[:, 9].astype(np.int64)
         out = dict(Pos=np.empty((n, 3)), Vel=np.empty((n, 3), dtype=np.float32), Disp=np.empty((n, 3), dtype=np.float32))
@@ -2606,93 +2608,44 @@ class DistGlass:
 
     def _deposit(self, S):
         """the window deposit; on several ranks one shift adds the ghost plane into the right-hand neighbour's plane 0: integers, exact"""
-        nxl, buf = self.d.nxl, self._buf
-        self.ops.deposit(self.N, self.L, S.pos, S.mass, self._exp, self.d.plane0, nxl, buf)
-        if self.comm.size > 1:
-            buf[0] += self._shift(buf[nxl:nxl + 1].contiguous(), +1)[0]
+        self.ops.deposit(self.N, self.L, S.pos, S.mass, self._exp, self.d.plane0, self.d.nxl, self._buf)
+        self.add_ghosts([self._buf], self.d.nxl)
 
     def _gather(self, S, axis):
         """the right-hand neighbour's first plane behind the own ones by one shift to the left, then the window gather"""
-        nxl, ext = self.d.nxl, self._ext
-        if self.comm.size > 1:
-            ext[nxl] = self._shift(ext[0:1].contiguous(), -1)[0]
-        self.ops.gather(self.N, self.L, S.pos, ext, self.d.plane0, nxl, S.disp, axis)
+        self.neighbour_plane(self._ext, self.d.nxl)
+        self.ops.gather(self.N, self.L, S.pos, self._ext, self.d.plane0, self.d.nxl, S.disp, axis)
 
     def _force_bespoke(self, S, sums):
         """glass_force with the library's own FFT passes (csrc/fft3d.hip): the deposit's buffer becomes its (y, z) half spectrum,
         the spectrum is kept on the y-slab for the three axes, a force's planes land in the gather's window"""
         c, ops, N, P, nxl = self.comm, self.ops, self.N, self.comm.size, self.d.nxl
-        zpc = ops.pitch(N) // 2
         nyl, y0 = N // P, c.rank * (N // P)
-        widths, multi = self.d.widths, c.multi
         self._deposit(S)
         own = self._buf[:nxl]
-        if multi:
-            send = torch.empty((P * nxl, nyl, zpc), dtype=torch.complex128, device=own.device)       # rows [dest q][x_l]
-            ops.fft_yz(N, own, nxl, 0, self._exp, send, P)
-            spec = self._a2a(send, [nxl] * P, widths).wait().contiguous()                          # [x (all)][y_l][z']
-        else:
-            ops.fft_yz(N, own, nxl, 0, self._exp, None, 1)
-            spec = own.view(torch.float64).view(torch.complex128)
+        spec = self.forward_bespoke(own, lambda packed: ops.fft_yz(N, own, nxl, 0, self._exp, packed, P)).wait().contiguous()
         ops.xforward(N, spec, y0, nyl, sums)
         real = self._ext[:nxl]
-
-        def start(axis):
-            out = torch.empty_like(spec)
-            ops.xtransfer(N, spec, out, y0, nyl, axis)
-            return self._a2a(out, widths, [nxl] * P)                                               # rows [src q][x_l]
-
-        pend = start(0) if multi else None
-        for axis in range(3):
-            if multi:
-                packed = pend.wait().contiguous()
-                pend = start(axis + 1) if axis + 1 < 3 else None
-                ops.fft_yz(N, real, nxl, 1, 0, packed, P)
-            else:       # the planes land where the Y/Z inverse takes them
-                ops.xtransfer(N, spec, real.view(torch.complex128), y0, nyl, axis)
-                ops.fft_yz(N, real, nxl, 1, 0, None, 1)
+        for axis in self.back_bespoke([real] * 3, spec, lambda axis, out: ops.xtransfer(N, spec, out, y0, nyl, axis),
+                                      lambda axis, packed: ops.fft_yz(N, real, nxl, 1, 0, packed, P)):
             self._gather(S, axis)
 
     def _force_torch(self, S, sums):
         """the same force with torch.fft, for mesh sizes without a bespoke transform and on the CPU stand-in: the spectrum is kept
         as [x][y_l][z'], x slowest, dense"""
         c, ops, N, P, nxl = self.comm, self.ops, self.N, self.comm.size, self.d.nxl
-        Nc, nyl, y0 = N // 2 + 1, N // P, c.rank * (N // P)
+        nyl, y0 = N // P, c.rank * (N // P)
         self._deposit(S)
-        real = ops.to_real(self._buf[:nxl, :, :N], self._exp)                                      # f64 [nxl, N, N]
-        sp = torch.fft.rfft2(real, dim=(1, 2))                                                     # [nxl, N, Nc], unscaled
-        send = sp.reshape(nxl, P, nyl, Nc).permute(1, 0, 2, 3).reshape(P * nxl, nyl, Nc)           # rows [dest q][x_l]
-        recv, _ = self._a2a(send.contiguous(), [nxl] * P)                                          # rows [src p][x_l] = all x
-        spec = torch.fft.fft(recv.reshape(N, nyl, Nc), dim=0).contiguous()
+        spec = self.forward_torch(ops.to_real(self._buf[:nxl, :, :N], self._exp))
         if sums is not None:
             ops.power(N, spec, y0, nyl, sums)
         for axis in range(3):
-            out = torch.fft.ifft(ops.transfer(N, spec, y0, nyl, axis), dim=0, norm="forward").contiguous()   # rows = x planes, in order
-            recv, _ = self._a2a(out, self.d.widths)                                                          # rows [src q][x_l]
-            sp = recv.reshape(P, nxl, nyl, Nc).permute(1, 0, 2, 3).reshape(nxl, N, Nc)
-            self._ext[:nxl, :, :N] = torch.fft.irfft2(sp, s=(N, N), dim=(1, 2), norm="forward")              # unscaled
+            self._ext[:nxl, :, :N] = self.back_torch(ops.transfer(N, spec, y0, nyl, axis))
             self._gather(S, axis)
 
 
-class GpuGlassOps:
+class GpuGlassOps(_DeviceOps):
     """DistGlass's phases on the device library (shq_glass_slab_*), on torch tensors of the context's device."""
-
-    def __init__(self, ctx, device=None):
-        self.ctx = ctx
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else device
-        self._hand = _StreamHandover(ctx, self.device)
-
-    def _call(self, fn, *args):
-        self._hand.before()
-        capi.check(fn(self.ctx.h, *args), fn.__name__)
-        self._hand.after()
-
-    @staticmethod
-    def _p(t):
-        return None if t is None else C.c_void_p(t.data_ptr())
-
-    def full(self, shape, value, dtype):
-        return torch.full(shape, value, dtype=dtype, device=self.device)
 
     def pitch(self, N):
         return int(capi.hip.shq_glass_slab_pitch(int(N)))
@@ -2722,9 +2675,6 @@ class GpuGlassOps:
     def xtransfer(self, N, spec, out, y0, nyl, axis):
         assert spec.is_contiguous() and out.is_contiguous() and out.dtype == spec.dtype == torch.complex128 and out.shape == spec.shape
         self._call(capi.hip.shq_glass_slab_xtransfer, N, self._p(spec), self._p(out), y0, nyl, axis)
-
-    def to_real(self, mesh_i, exp):
-        return mesh_i.to(torch.float64) * math.ldexp(1.0, exp - 61)
 
     def power(self, N, spec, y0, nyl, sums):
         assert spec.is_contiguous() and spec.dtype == torch.complex128 and spec.shape == (N, nyl, N // 2 + 1) and sums.is_contiguous()
