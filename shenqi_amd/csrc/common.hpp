@@ -362,7 +362,7 @@ struct shq_context {
     DevBuf<uint32_t> bhd_kind;      /* kinds of the emitted black-hole records; the run heads of the resolved ones */
     DevBuf<char> wind_kicks;
     DevBuf<double> wind_d;
-    DevBuf<unsigned long long> wind_cnt;
+    DevBuf<unsigned long long> wind_cnt; /* [0..3] cursors and counters of the wind, metal and black-hole walks; from [4] the per-owner counts of a routed list */
     bool tb_built = false;     /* the current tree came from shq_tree_build (downloadable) */
 
     /* ---- SPH state, by particle index (gas fields gathered from their slots at upload) */
@@ -934,6 +934,13 @@ CoolUV shq_cooling_uv(const shq_cooling_uvbg *u);
 /* rows of eight doubles for the particles of d_list: vx, vy, vz, entropy, delay time, mass word of posm, flag byte, `extra` byte (or 0) */
 int shq_rows_gather(shq_context *ctx, const int32_t *d_list, int64_t m, const uint8_t *d_extra, double *d_rows);
 int shq_u64_gather(shq_context *ctx, const int32_t *d_list, int64_t m, const unsigned long long *d_src, unsigned long long *d_out);
+/* sph_winds.hip: the n emitted keys (row << 32 | queue position) of metal_keys[0] rewritten to (row at the owner << 32 | queue_offset +
+ * position, or d_qpos[position] where the walk ran over a part of the rank's queue) in metal_keys[1], and ordered by (row, position) and
+ * then, stable, by owner: entry k of the list is routed key metal_u32[3][k] and belongs to owner metal_u32[0][k].  Rows >= nlocal are
+ * imports: their owner and their row there come from d_ghost_owner / d_ghost_index (by row - nlocal).  The per-owner counts are added to
+ * d_counts[nranks].  The caller has reserved n entries in both metal_keys and all four metal_u32. */
+int shq_route_sort(shq_context *ctx, int64_t n, int64_t nlocal, const int32_t *d_ghost_owner, const int32_t *d_ghost_index, int nranks, int rank, int64_t queue_offset,
+                   const int32_t *d_qpos, unsigned long long *d_counts);
 int shq_bh_veldisp_device(shq_context *ctx, const shq_kick_factors *kf, double BoxSize, const int32_t *d_queue, int64_t nq, double *d_out);
 int shq_sph_stellar_density_device(shq_context *ctx, const shq_stellar_params *p, const int32_t *d_queue, int64_t nq, double *d_starvol,
                                    shq_sph_stats *stats);

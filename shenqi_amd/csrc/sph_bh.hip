@@ -1,6 +1,6 @@
-/* sph_bh.hip — black-hole accretion and feedback on the walk of sph_walk.hpp, and the marked-particle lists and row gathers
- * their callers read the changed particles back with; at the end the same two walks as record emitters, with the owner-side resolve and
- * apply kernels, for a multi-rank driver. */
+/* sph_bh.hip — black-hole accretion and feedback on the walk of sph_walk.hpp: one kernel body per walk, each in three routes (write
+ * on the neighbours' side, count the writes, emit them as records), and the marked-particle lists and row gathers their callers read
+ * the changed particles back with; at the end the owner-side resolve and apply kernels of the record route, for a multi-rank driver. */
 #include "sph_walk.hpp"
 #include "device_prims.hpp"
 
@@ -21,10 +21,56 @@ __device__ __forceinline__ bool bh_timebin_active(int bin, long long cur) /* is_
     return cur % (1ll << bin) == 0;
 }
 
+/* ---- the three routes of a walk ---------------------------------------------------------------------------------------------------
+ * Both walks write on the neighbours' side (marks, flags, entropy, kicks), and a neighbour may be an imported copy of another rank's
+ * particle.  Each walk is one kernel body whose neighbour-side writes are chosen at compile time:
+ *   BH_WRITE  they are performed inside the kernel (atomics, compare-and-swap loops): the one-shot calls;
+ *   BH_COUNT  they are counted, no hole-side sums, no w.out row: the first pass of a multi-rank driver (shenqi_amd/dist.py:DistBlackHole);
+ *   BH_EMIT   they are emitted as one record per (neighbour, hole) beside the hole-side sums and the w.out row: its second pass.
+ * The emitted records are rewritten to (owner, row at the owner, position of the hole in the global queue) and sorted by these three
+ * (shq_route_sort).  The owner sorts what it gathered by (row, hole) and one lane per particle runs over its records in ascending hole
+ * order: the reference's mark rule and energy injection as a serial loop over the global queue, the same bits on every run.  No
+ * floating-point atomic and no compare-and-swap loop in the BH_COUNT and BH_EMIT instantiations. */
+enum BhRoute { BH_WRITE, BH_COUNT, BH_EMIT };
+
+struct BhEmitArgs {
+    unsigned long long *cursor;
+    unsigned long long capacity;
+    unsigned long long *keys; /* particle << 32 | queue position */
+    unsigned long long *val;  /* the marking hole's ID, or the bits of the double */
+    uint32_t *kind;
+};
+
+template <int ROUTE>
+__device__ __forceinline__ void bh_emit(const BhEmitArgs &e, unsigned int &mine, long long p, long long t, uint32_t kind, unsigned long long bits)
+{
+    static_assert(ROUTE != BH_WRITE, "the write route has no records");
+    if(ROUTE == BH_COUNT) {
+        mine++;
+        return;
+    }
+    const unsigned long long k = atomicAdd(e.cursor, 1ull);
+    if(k < e.capacity) {
+        e.keys[k] = ((unsigned long long) (unsigned) p << 32) | (unsigned long long) t;
+        e.val[k] = bits;
+        e.kind[k] = kind;
+    }
+}
+
+__device__ __forceinline__ void bh_emit_count(const BhEmitArgs &e, unsigned int mine, int lane)
+{
+    for(int off = 32; off > 0; off >>= 1)
+        mine += __shfl_xor(mine, off);
+    if(lane == 0 && mine)
+        atomicAdd(e.cursor, (unsigned long long) mine);
+}
+
+/* the accretion walk.  Its records: kind 0 on a hole (a merger candidate: close enough and the reposition / check_grav_bound flag),
+ * kind 1 on a gas particle (the draw succeeded); both carry the marking hole's ID */
 #define BH_ACC_NOUT 8
-template <int KT>
+template <int KT, int ROUTE>
 __global__ __launch_bounds__(256) void bh_accretion_kernel(const SphDev a, const int32_t *queue, long long nq, const BhWalkArgs w, const shq_kick_factors kf,
-                                                           int32_t *__restrict__ nlist, long long ntasks)
+                                                           const BhEmitArgs e, int32_t *__restrict__ nlist, long long ntasks)
 {
 #pragma clang fp contract(off)
     __shared__ __attribute__((aligned(32))) char lds[4 * NW_LDS_PER_WAVE(true)];
@@ -56,6 +102,7 @@ __global__ __launch_bounds__(256) void bh_accretion_kernel(const SphDev a, const
     const double HH = kernel.H * kernel.H, Hinv = 1.0 / kernel.H;
     const double h2 = h * h;
     int encounter = 0;
+    unsigned int mine = 0;
     double fws = 0, sment = 0, gv0 = 0, gv1 = 0, gv2 = 0, mgas = 0;
     const double rmerge = 2 * w.P.ForceSoftening / 2.8;
     auto pair = [&](const int s) {
@@ -94,34 +141,39 @@ __global__ __launch_bounds__(256) void bh_accretion_kernel(const SphDev a, const
                 flag = (PE + KE <= 0);
             }
             if(flag == 1 && ob >= 0) {
-                const unsigned long long oid = w.ids[p];
-                const bool oactive = bh_timebin_active(w.bin_hydro[p], w.Ti_Current);
-                unsigned long long *swal = w.bh_swallow + ob;
-                unsigned long long readid = atomicAdd(swal, 0ull);
-                for(;;) {
-                    unsigned long long newid;
-                    if(readid != 0 && readid < myid)
-                        newid = myid + 1;
-                    else if(readid == 0 && (oid < myid || !oactive))
-                        newid = myid + 1;
-                    else
-                        break;
-                    const unsigned long long seen = atomicCAS(swal, readid, newid);
-                    if(seen == readid)
-                        break;
-                    readid = seen;
-                }
+                if constexpr(ROUTE == BH_WRITE) {
+                    const unsigned long long oid = w.ids[p];
+                    const bool oactive = bh_timebin_active(w.bin_hydro[p], w.Ti_Current);
+                    unsigned long long *swal = w.bh_swallow + ob;
+                    unsigned long long readid = atomicAdd(swal, 0ull);
+                    for(;;) {
+                        unsigned long long newid;
+                        if(readid != 0 && readid < myid)
+                            newid = myid + 1;
+                        else if(readid == 0 && (oid < myid || !oactive))
+                            newid = myid + 1;
+                        else
+                            break;
+                        const unsigned long long seen = atomicCAS(swal, readid, newid);
+                        if(seen == readid)
+                            break;
+                        readid = seen;
+                    }
+                } else
+                    bh_emit<ROUTE>(e, mine, p, t, 0u, myid);
             }
         }
         if(type == 0 && r2 < HH) {
             const double u = r * Hinv;
             const double wk = kernel.wk(u);
             const double mass_j = q.w;
-            sment += (mass_j * wk * w.entropy[p]);
-            const double4 vp = a.velp[p]; /* SPH_VelPred */
-            gv0 += (mass_j * wk * vp.x);
-            gv1 += (mass_j * wk * vp.y);
-            gv2 += (mass_j * wk * vp.z);
+            if constexpr(ROUTE != BH_COUNT) {
+                sment += (mass_j * wk * w.entropy[p]);
+                const double4 vp = a.velp[p]; /* SPH_VelPred */
+                gv0 += (mass_j * wk * vp.x);
+                gv1 += (mass_j * wk * vp.y);
+                gv2 += (mass_j * wk * vp.z);
+            }
             double pacc = 0;
             double BHPartMass = imass;
             if(w.P.SeedBHDynMass > 0 && imtrack < w.P.SeedBHDynMass)
@@ -129,13 +181,18 @@ __global__ __launch_bounds__(256) void bh_accretion_kernel(const SphDev a, const
             if((ibhmass - BHPartMass) > 0 && idens > 0)
                 pacc = (ibhmass - BHPartMass) * wk / idens;
             const double rn = w.rnd[w.ids[p] % w.rndsize];
-            if(rn < pacc)
-                atomicMax(w.sph_swallow + p, myid + 1); /* "prefer to be swallowed by a bigger ID" */
-            if(w.touched) /* every gas neighbour inside the kernel: a superset of the marked ones (could be narrowed to rn < pacc) */
-                w.touched[p] = 1;
-            fws += (mass_j * wk);
-            if(w.P.BlackHoleKineticOn == 1)
-                mgas += mass_j;
+            if constexpr(ROUTE == BH_WRITE) {
+                if(rn < pacc)
+                    atomicMax(w.sph_swallow + p, myid + 1); /* "prefer to be swallowed by a bigger ID" */
+                if(w.touched) /* every gas neighbour inside the kernel: a superset of the marked ones (could be narrowed to rn < pacc) */
+                    w.touched[p] = 1;
+            } else if(rn < pacc)
+                bh_emit<ROUTE>(e, mine, p, t, 1u, myid);
+            if constexpr(ROUTE != BH_COUNT) {
+                fws += (mass_j * wk);
+                if(w.P.BlackHoleKineticOn == 1)
+                    mgas += mass_j;
+            }
         }
     };
     auto accept = [&](const double r2, const double hj, const int) { return r2 <= h2 || r2 <= hj * hj; };
@@ -143,7 +200,9 @@ __global__ __launch_bounds__(256) void bh_accretion_kernel(const SphDev a, const
     bool ovf = false;
     (void) ngb_walk<true, false, false>(a, lds + (threadIdx.x >> 6) * NW_LDS_PER_WAVE(true), myl, valid, px, py, pz, h, accept, pair,
                                         (unsigned int *) nullptr, fill, ovf);
-    if(valid) {
+    if constexpr(ROUTE == BH_COUNT)
+        bh_emit_count(e, mine, lane);
+    else if(valid) {
         double *o = w.out + BH_ACC_NOUT * t;
         o[0] = encounter; o[1] = fws; o[2] = sment; o[3] = gv0; o[4] = gv1; o[5] = gv2; o[6] = mgas; o[7] = 0;
     }
@@ -240,10 +299,12 @@ __global__ void bh_gather_leaf_kernel(long long nleaf, const int32_t *__restrict
     flag_leaf[s] = ((f & 1u) || !(type == 0 || type == 5)) ? 1 : 0; /* IsGarbage; GASMASK + BHMASK (treewalk.c:943-949) */
 }
 
+/* the feedback walk.  Its records: kind 0 this hole swallows the hole, kind 1 it swallows the gas particle, kind 2 heat
+ * (injected / mass_j), kind 3 kick (dvel).  w.bh_swallow / w.sph_swallow are the resolved marks. */
 #define BH_FB_NOUT 8
-template <int KT>
+template <int KT, int ROUTE>
 __global__ __launch_bounds__(256) void bh_feedback_kernel(const SphDev a, const int32_t *queue, long long nq, const BhWalkArgs w, const shq_kick_factors kf,
-                                                          int32_t *__restrict__ nlist, long long ntasks)
+                                                          const BhEmitArgs e, int32_t *__restrict__ nlist, long long ntasks)
 {
 #pragma clang fp contract(off)
     __shared__ __attribute__((aligned(32))) char lds[4 * NW_LDS_PER_WAVE(true)];
@@ -279,6 +340,7 @@ __global__ __launch_bounds__(256) void bh_feedback_kernel(const SphDev a, const 
     const double HH = kernel.H * kernel.H, Hinv = 1.0 / kernel.H;
     const double h2 = h * h;
     int mintimebin = SHQ_TIMEBINS, countprogs = 0;
+    unsigned int mine = 0;
     double accmass = 0, accbh = 0, mom0 = 0, mom1 = 0, mom2 = 0;
     auto pair = [&](const int s) {
         const long long p = w.leaf_pidx[s];
@@ -294,23 +356,28 @@ __global__ __launch_bounds__(256) void bh_feedback_kernel(const SphDev a, const 
                 return;
             if(w.bh_swallow[ob] != myid + 1)
                 return;
-            BhRec &O = w.bh[ob];
-            w.bh_swallowid_out[ob] = w.bh_swallow[ob] - 1;
-            atomicOr(reinterpret_cast<unsigned int *>(w.pflags + (p & ~3ll)), 2u << (8 * (p & 3))); /* Swallowed = 1 */
-            countprogs += O.CountProgs;
-            accbh += O.Mass;
-            double othermass = q.w;
-            if(w.P.SeedBHDynMass > 0 && imtrack > 0)
-                if(O.Mtrack < w.P.SeedBHDynMass)
-                    othermass = O.Mtrack;
-            accmass += othermass;
-            const int bg = w.bin_grav[p];
-            const double v0 = w.vel[3 * p] + kf.gravkicks[bg] * w.treeacc[3 * p] + w.gravpm[3 * p] * kf.FgravkickB;
-            const double v1 = w.vel[3 * p + 1] + kf.gravkicks[bg] * w.treeacc[3 * p + 1] + w.gravpm[3 * p + 1] * kf.FgravkickB;
-            const double v2 = w.vel[3 * p + 2] + kf.gravkicks[bg] * w.treeacc[3 * p + 2] + w.gravpm[3 * p + 2] * kf.FgravkickB;
-            mom0 += (othermass * v0);
-            mom1 += (othermass * v1);
-            mom2 += (othermass * v2);
+            if constexpr(ROUTE == BH_WRITE) {
+                w.bh_swallowid_out[ob] = w.bh_swallow[ob] - 1;
+                atomicOr(reinterpret_cast<unsigned int *>(w.pflags + (p & ~3ll)), 2u << (8 * (p & 3))); /* Swallowed = 1 */
+            } else
+                bh_emit<ROUTE>(e, mine, p, t, 0u, 0ull);
+            if constexpr(ROUTE != BH_COUNT) {
+                const BhRec &O = w.bh[ob];
+                countprogs += O.CountProgs;
+                accbh += O.Mass;
+                double othermass = q.w;
+                if(w.P.SeedBHDynMass > 0 && imtrack > 0)
+                    if(O.Mtrack < w.P.SeedBHDynMass)
+                        othermass = O.Mtrack;
+                accmass += othermass;
+                const int bg = w.bin_grav[p];
+                const double v0 = w.vel[3 * p] + kf.gravkicks[bg] * w.treeacc[3 * p] + w.gravpm[3 * p] * kf.FgravkickB;
+                const double v1 = w.vel[3 * p + 1] + kf.gravkicks[bg] * w.treeacc[3 * p + 1] + w.gravpm[3 * p + 1] * kf.FgravkickB;
+                const double v2 = w.vel[3 * p + 2] + kf.gravkicks[bg] * w.treeacc[3 * p + 2] + w.gravpm[3 * p + 2] * kf.FgravkickB;
+                mom0 += (othermass * v0);
+                mom1 += (othermass * v1);
+                mom2 += (othermass * v2);
+            }
             return;
         }
         if(type != 0)
@@ -327,47 +394,58 @@ __global__ __launch_bounds__(256) void bh_feedback_kernel(const SphDev a, const 
             const double wk = kernel.wk(u);
             if(fws > 0 && fbenergy > 0 && channel == 0 && mass_j > 0) {
                 const double injected = fbenergy * mass_j * wk / fws;
-                if(w.eeqos && w.eeqos[p])
-                    w.heated[p] = 1;
-                if(w.touched)
-                    w.touched[p] = 1;
-                const double enttou = pow(w.density[p] * w.P.a3inv, SPH_GAMMA - 1) / (SPH_GAMMA - 1);
-                unsigned long long *eptr = reinterpret_cast<unsigned long long *>(w.entropy + p);
-                unsigned long long oldb = atomicAdd(eptr, 0ull);
-                for(;;) {
-                    /* add_injected_BH_energy, :700-710 */
-                    double unew = __longlong_as_double((long long) oldb) * enttou;
-                    unew += injected / mass_j;
-                    if(unew > w.P.MaxThermalU)
-                        unew = w.P.MaxThermalU;
-                    const double entnew = unew / enttou;
-                    const unsigned long long seen = atomicCAS(eptr, oldb, (unsigned long long) __double_as_longlong(entnew));
-                    if(seen == oldb)
-                        break;
-                    oldb = seen;
-                }
+                if constexpr(ROUTE == BH_WRITE) {
+                    if(w.eeqos && w.eeqos[p])
+                        w.heated[p] = 1;
+                    if(w.touched)
+                        w.touched[p] = 1;
+                    const double enttou = pow(w.density[p] * w.P.a3inv, SPH_GAMMA - 1) / (SPH_GAMMA - 1);
+                    unsigned long long *eptr = reinterpret_cast<unsigned long long *>(w.entropy + p);
+                    unsigned long long oldb = atomicAdd(eptr, 0ull);
+                    for(;;) {
+                        /* add_injected_BH_energy, :700-710 */
+                        double unew = __longlong_as_double((long long) oldb) * enttou;
+                        unew += injected / mass_j;
+                        if(unew > w.P.MaxThermalU)
+                            unew = w.P.MaxThermalU;
+                        const double entnew = unew / enttou;
+                        const unsigned long long seen = atomicCAS(eptr, oldb, (unsigned long long) __double_as_longlong(entnew));
+                        if(seen == oldb)
+                            break;
+                        oldb = seen;
+                    }
+                } else
+                    bh_emit<ROUTE>(e, mine, p, t, 2u, (unsigned long long) __double_as_longlong(injected / mass_j));
             }
             if(kefb > 0 && channel == 1 && idens > 0) {
                 const double dvel = sqrt(2 * kefb * wk / idens);
-                /* get_random_dir, :712-723 */
-                const double theta = acos(2 * w.rnd[(w.ids[p] + 3) % w.rndsize] - 1);
-                const double phi = 2 * M_PI * w.rnd[(w.ids[p] + 4) % w.rndsize];
-                const double dir[3] = {sin(theta) * cos(phi), sin(theta) * sin(phi), cos(theta)};
-                for(int j = 0; j < 3; j++)
-                    atomicAdd(w.velw + 3 * p + j, dvel * dir[j]);
-                if(w.touched)
-                    w.touched[p] = 1;
+                if constexpr(ROUTE == BH_WRITE) {
+                    /* get_random_dir, :712-723 */
+                    const double theta = acos(2 * w.rnd[(w.ids[p] + 3) % w.rndsize] - 1);
+                    const double phi = 2 * M_PI * w.rnd[(w.ids[p] + 4) % w.rndsize];
+                    const double dir[3] = {sin(theta) * cos(phi), sin(theta) * sin(phi), cos(theta)};
+                    for(int j = 0; j < 3; j++)
+                        atomicAdd(w.velw + 3 * p + j, dvel * dir[j]);
+                    if(w.touched)
+                        w.touched[p] = 1;
+                } else
+                    bh_emit<ROUTE>(e, mine, p, t, 3u, (unsigned long long) __double_as_longlong(dvel));
             }
         }
         if(mark == myid + 1) {
-            if(w.touched)
-                w.touched[p] = 1;
-            accmass += q.w;
-            const double4 vp = a.velp[p];
-            mom0 += (q.w * vp.x);
-            mom1 += (q.w * vp.y);
-            mom2 += (q.w * vp.z);
-            atomicOr(reinterpret_cast<unsigned int *>(w.pflags + (p & ~3ll)), 1u << (8 * (p & 3))); /* slots_mark_garbage */
+            if constexpr(ROUTE == BH_WRITE) {
+                if(w.touched)
+                    w.touched[p] = 1;
+                atomicOr(reinterpret_cast<unsigned int *>(w.pflags + (p & ~3ll)), 1u << (8 * (p & 3))); /* slots_mark_garbage */
+            } else
+                bh_emit<ROUTE>(e, mine, p, t, 1u, 0ull);
+            if constexpr(ROUTE != BH_COUNT) {
+                accmass += q.w;
+                const double4 vp = a.velp[p];
+                mom0 += (q.w * vp.x);
+                mom1 += (q.w * vp.y);
+                mom2 += (q.w * vp.z);
+            }
         }
     };
     auto accept = [&](const double r2, const double hj, const int) { return r2 <= h2 || r2 <= hj * hj; };
@@ -375,7 +453,9 @@ __global__ __launch_bounds__(256) void bh_feedback_kernel(const SphDev a, const 
     bool ovf = false;
     (void) ngb_walk<true, false, false>(a, lds + (threadIdx.x >> 6) * NW_LDS_PER_WAVE(true), myl, valid, px, py, pz, h, accept, pair,
                                         (unsigned int *) nullptr, fill, ovf);
-    if(valid) {
+    if constexpr(ROUTE == BH_COUNT)
+        bh_emit_count(e, mine, lane);
+    else if(valid) {
         double *o = w.out + BH_FB_NOUT * t;
         o[0] = accmass; o[1] = accbh; o[2] = mom0; o[3] = mom1; o[4] = mom2; o[5] = countprogs; o[6] = mintimebin; o[7] = 0;
     }
@@ -423,35 +503,61 @@ int sph_gather_gas_flags(shq_context *ctx)
     return SHQ_OK;
 }
 
-static int bh_launch_prep(shq_context *ctx, const shq_kick_factors *kf)
+/* what a walk needs before its first launch of a call: SPH_VelPred of every gas particle, Hsml in leaf order, the leaf flags, the lists */
+static int bh_walk_prep(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w)
 {
-    SHQ_TRY(shq_sph_prepare(ctx, kf, nullptr, nullptr)); /* SPH_VelPred of every gas particle, Hsml in leaf order */
+    const int kt = w->P.DensityKernelType;
+    SHQ_CHECK(kt == 1 || kt == 2 || kt == 4, SHQ_ERR_INVALID, "unknown DensityKernelType %d", kt);
+    SHQ_TRY(shq_sph_prepare(ctx, kf, nullptr, nullptr));
     SHQ_TRY(sph_gather_gas_flags(ctx));
     return sph_reserve_nlist2(ctx);
+}
+
+/* one walk (feedback, else accretion) in one route and, where the route has hole-side sums, its postprocess; timed as the count pass or
+ * as the walk */
+template <int ROUTE>
+static int bh_walk_launch(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, bool feedback, const int32_t *d_queue, int64_t nq, const BhEmitArgs &e,
+                          double *d_post)
+{
+    hipStream_t st = ctx->stream;
+    SphDev a = make_dev(ctx, w->P.BoxSize);
+    const long long ntasks = (nq + 255) / 256;
+    const unsigned grid = (unsigned) (ntasks < NL_REDO_BLOCKS ? ntasks : NL_REDO_BLOCKS);
+    const int timer = ROUTE == BH_COUNT ? SHQ_T_BH_COUNT : SHQ_T_BH;
+    void (*walk)(SphDev, const int32_t *, long long, BhWalkArgs, shq_kick_factors, BhEmitArgs, int32_t *, long long);
+    switch(w->P.DensityKernelType) {
+    case 1: walk = feedback ? bh_feedback_kernel<1, ROUTE> : bh_accretion_kernel<1, ROUTE>; break;
+    case 2: walk = feedback ? bh_feedback_kernel<2, ROUTE> : bh_accretion_kernel<2, ROUTE>; break;
+    default: walk = feedback ? bh_feedback_kernel<4, ROUTE> : bh_accretion_kernel<4, ROUTE>; break;
+    }
+    SHQ_HIP(hipEventRecord(ctx->ev_begin[timer], st));
+    walk<<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, e, ctx->s_nlist2.ptr, ntasks);
+    SHQ_HIP(hipGetLastError());
+    if(ROUTE != BH_COUNT) {
+        if(feedback)
+            bh_feedback_post_kernel<<<dim3(nblk(nq)), dim3(256), 0, st>>>(nq, d_queue, *w, ctx->posm.ptr);
+        else
+            bh_accretion_post_kernel<<<dim3(nblk(nq)), dim3(256), 0, st>>>(nq, d_queue, *w, *kf, ctx->posm.ptr, d_post);
+        SHQ_HIP(hipGetLastError());
+    }
+    SHQ_HIP(hipEventRecord(ctx->ev_end[timer], st));
+    return SHQ_OK;
 }
 
 int shq_bh_accretion_device(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, const int32_t *d_queue, int64_t nq, double *d_post)
 {
     if(nq == 0)
         return SHQ_OK;
-    const int kt = w->P.DensityKernelType;
-    SHQ_CHECK(kt == 1 || kt == 2 || kt == 4, SHQ_ERR_INVALID, "unknown DensityKernelType %d", kt);
-    SHQ_TRY(bh_launch_prep(ctx, kf));
-    hipStream_t st = ctx->stream;
-    SphDev a = make_dev(ctx, w->P.BoxSize);
-    const long long ntasks = (nq + 255) / 256;
-    const unsigned grid = (unsigned) (ntasks < NL_REDO_BLOCKS ? ntasks : NL_REDO_BLOCKS);
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_BH], st));
-    switch(kt) {
-    case 1: bh_accretion_kernel<1><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, ctx->s_nlist2.ptr, ntasks); break;
-    case 2: bh_accretion_kernel<2><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, ctx->s_nlist2.ptr, ntasks); break;
-    default: bh_accretion_kernel<4><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, ctx->s_nlist2.ptr, ntasks); break;
-    }
-    SHQ_HIP(hipGetLastError());
-    bh_accretion_post_kernel<<<dim3(nblk(nq)), dim3(256), 0, st>>>(nq, d_queue, *w, *kf, ctx->posm.ptr, d_post);
-    SHQ_HIP(hipGetLastError());
-    SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_T_BH], st));
-    return SHQ_OK;
+    SHQ_TRY(bh_walk_prep(ctx, kf, w));
+    return bh_walk_launch<BH_WRITE>(ctx, kf, w, false, d_queue, nq, BhEmitArgs{}, d_post);
+}
+
+int shq_bh_feedback_device(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, const int32_t *d_queue, int64_t nq)
+{
+    if(nq == 0)
+        return SHQ_OK;
+    SHQ_TRY(bh_walk_prep(ctx, kf, w));
+    return bh_walk_launch<BH_WRITE>(ctx, kf, w, true, d_queue, nq, BhEmitArgs{}, nullptr);
 }
 
 namespace {
@@ -517,330 +623,8 @@ int shq_rows_gather(shq_context *ctx, const int32_t *d_list, int64_t m, const ui
     return SHQ_OK;
 }
 
-int shq_bh_feedback_device(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, const int32_t *d_queue, int64_t nq)
-{
-    if(nq == 0)
-        return SHQ_OK;
-    const int kt = w->P.DensityKernelType;
-    SHQ_CHECK(kt == 1 || kt == 2 || kt == 4, SHQ_ERR_INVALID, "unknown DensityKernelType %d", kt);
-    SHQ_TRY(bh_launch_prep(ctx, kf));
-    hipStream_t st = ctx->stream;
-    SphDev a = make_dev(ctx, w->P.BoxSize);
-    const long long ntasks = (nq + 255) / 256;
-    const unsigned grid = (unsigned) (ntasks < NL_REDO_BLOCKS ? ntasks : NL_REDO_BLOCKS);
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_BH], st));
-    switch(kt) {
-    case 1: bh_feedback_kernel<1><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, ctx->s_nlist2.ptr, ntasks); break;
-    case 2: bh_feedback_kernel<2><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, ctx->s_nlist2.ptr, ntasks); break;
-    default: bh_feedback_kernel<4><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, ctx->s_nlist2.ptr, ntasks); break;
-    }
-    SHQ_HIP(hipGetLastError());
-    bh_feedback_post_kernel<<<dim3(nblk(nq)), dim3(256), 0, st>>>(nq, d_queue, *w, ctx->posm.ptr);
-    SHQ_HIP(hipGetLastError());
-    SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_T_BH], st));
-    return SHQ_OK;
-}
 
-/* ---- the same two walks in the parts a multi-rank driver needs (shenqi_amd/dist.py:DistBlackHole) ------------------------------------
- * Both walks write on the neighbours' side (marks, flags, entropy, kicks), and a neighbour may be an imported copy of another rank's
- * particle.  Here the walks keep the hole-side sums and postprocess of the kernels above and only EMIT what they would have written:
- * one record per (neighbour, hole), by the count pass / emit pass of the metal return (sph_winds.hip), rewritten to (owner, row at
- * the owner, position of the hole in the global queue) and sorted by these three.  The owner sorts what it gathered by (row, hole)
- * and one lane per particle runs over its records in ascending hole order: the reference's mark rule and energy injection as a serial
- * loop over the global queue, the same bits on every run.  No floating-point atomic and no compare-and-swap loop in this route. */
-struct BhEmitArgs {
-    unsigned long long *cursor;
-    unsigned long long capacity;
-    unsigned long long *keys; /* particle << 32 | queue position */
-    unsigned long long *val;  /* the marking hole's ID, or the bits of the double */
-    uint32_t *kind;
-};
-
-template <bool EMIT>
-__device__ __forceinline__ void bh_emit(const BhEmitArgs &e, unsigned int &mine, long long p, long long t, uint32_t kind, unsigned long long bits)
-{
-    if(!EMIT) {
-        mine++;
-        return;
-    }
-    const unsigned long long k = atomicAdd(e.cursor, 1ull);
-    if(k < e.capacity) {
-        e.keys[k] = ((unsigned long long) (unsigned) p << 32) | (unsigned long long) t;
-        e.val[k] = bits;
-        e.kind[k] = kind;
-    }
-}
-
-__device__ __forceinline__ void bh_emit_count(const BhEmitArgs &e, unsigned int mine, int lane)
-{
-    for(int off = 32; off > 0; off >>= 1)
-        mine += __shfl_xor(mine, off);
-    if(lane == 0 && mine)
-        atomicAdd(e.cursor, (unsigned long long) mine);
-}
-
-/* bh_accretion_kernel with the two marks emitted instead of written: kind 0 on a hole (a merger candidate: close enough and the
- * reposition / check_grav_bound flag), kind 1 on a gas particle (the draw succeeded); both carry the marking hole's ID */
-template <int KT, bool EMIT>
-__global__ __launch_bounds__(256) void bh_marks_kernel(const SphDev a, const int32_t *queue, long long nq, const BhWalkArgs w, const shq_kick_factors kf,
-                                                       const BhEmitArgs e, int32_t *__restrict__ nlist, long long ntasks)
-{
-#pragma clang fp contract(off)
-    __shared__ __attribute__((aligned(32))) char lds[4 * NW_LDS_PER_WAVE(true)];
-    const int lane = threadIdx.x & 63;
-    for(long long task = xcd_block(blockIdx.x, gridDim.x); task < ntasks; task += gridDim.x) {
-    const long long wave = task * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    int32_t *myl = nlist + ((size_t) blockIdx.x * 4 + (threadIdx.x >> 6)) * (size_t) (NL_ROWS * 64) + lane;
-    const long long t = wave * 64 + lane;
-    const bool valid = t < nq;
-    double px = 0, py = 0, pz = 0, h = 1, imass = 0, ibhmass = 0, idens = 0, imtrack = 0;
-    double iv[3] = {0, 0, 0}, ia[3] = {0, 0, 0};
-    unsigned long long myid = 0;
-    if(valid) {
-        const long long pi = queue[t];
-        const double4 p = a.posm[pi];
-        px = p.x; py = p.y; pz = p.z;
-        imass = p.w;
-        h = a.hsml[pi];
-        myid = w.ids[pi];
-        const long long b = shq_bh_ordinal(w.bhp, w.nbh, (int32_t) pi);
-        const BhRec &B = w.bh[b];
-        ibhmass = B.Mass; idens = B.Density; imtrack = B.Mtrack;
-        for(int d = 0; d < 3; d++) {
-            iv[d] = w.vel[3 * pi + d];
-            ia[d] = w.treeacc[3 * pi + d] + w.gravpm[3 * pi + d] + B.DFAccel[d];
-        }
-    }
-    const Kern<KT> kernel(h);
-    const double HH = kernel.H * kernel.H, Hinv = 1.0 / kernel.H;
-    const double h2 = h * h;
-    int encounter = 0;
-    unsigned int mine = 0;
-    double fws = 0, sment = 0, gv0 = 0, gv1 = 0, gv2 = 0, mgas = 0;
-    const double rmerge = 2 * w.P.ForceSoftening / 2.8;
-    auto pair = [&](const int s) {
-        const long long p = w.leaf_pidx[s];
-        const double4 q = a.posm_leaf[s];
-        const int type = w.pflags[p] >> 4;
-        if(q.w < 0)
-            return;
-        if(w.P.WindsDecoupleSph && type == 0 && w.delay[p] > 0)
-            return;
-        if(w.ids[p] == myid)
-            return;
-        const double d0 = wrapd(px - q.x, a.Box, a.invBox), d1 = wrapd(py - q.y, a.Box, a.invBox), d2 = wrapd(pz - q.z, a.Box, a.invBox);
-        const double r2 = d0 * d0 + d1 * d1 + d2 * d2;
-        const double r = sqrt(r2);
-        if(type == 5 && r < rmerge) {
-            encounter = 1;
-            const long long ob = shq_bh_ordinal(w.bhp, w.nbh, (int32_t) p);
-            int flag = 0;
-            if(w.P.RepositionEnabled == 1 || w.P.MergeGravBound == 0)
-                flag = 1;
-            if(w.P.MergeGravBound == 1 && w.P.RepositionEnabled == 0 && ob >= 0) {
-                const double dx[3] = {d0, d1, d2};
-                double KE = 0, PE = 0;
-                const int bg = w.bin_grav[p];
-                for(int d = 0; d < 3; d++) {
-                    const double vp = w.vel[3 * p + d] + kf.gravkicks[bg] * w.treeacc[3 * p + d] + w.gravpm[3 * p + d] * kf.FgravkickB;
-                    const double dv = iv[d] - vp;
-                    const double da = ia[d] - w.treeacc[3 * p + d] - w.gravpm[3 * p + d] - w.bh[ob].DFAccel[d];
-                    KE += 0.5 * (dv * dv);
-                    PE += da * dx[d];
-                }
-                KE /= (w.P.atime * w.P.atime);
-                PE /= w.P.atime;
-                flag = (PE + KE <= 0);
-            }
-            if(flag == 1 && ob >= 0)
-                bh_emit<EMIT>(e, mine, p, t, 0u, myid);
-        }
-        if(type == 0 && r2 < HH) {
-            const double u = r * Hinv;
-            const double wk = kernel.wk(u);
-            const double mass_j = q.w;
-            if(EMIT) {
-                sment += (mass_j * wk * w.entropy[p]);
-                const double4 vp = a.velp[p];
-                gv0 += (mass_j * wk * vp.x);
-                gv1 += (mass_j * wk * vp.y);
-                gv2 += (mass_j * wk * vp.z);
-            }
-            double pacc = 0;
-            double BHPartMass = imass;
-            if(w.P.SeedBHDynMass > 0 && imtrack < w.P.SeedBHDynMass)
-                BHPartMass = imtrack;
-            if((ibhmass - BHPartMass) > 0 && idens > 0)
-                pacc = (ibhmass - BHPartMass) * wk / idens;
-            const double rn = w.rnd[w.ids[p] % w.rndsize];
-            if(rn < pacc)
-                bh_emit<EMIT>(e, mine, p, t, 1u, myid);
-            if(EMIT) {
-                fws += (mass_j * wk);
-                if(w.P.BlackHoleKineticOn == 1)
-                    mgas += mass_j;
-            }
-        }
-    };
-    auto accept = [&](const double r2, const double hj, const int) { return r2 <= h2 || r2 <= hj * hj; };
-    int fill = 0;
-    bool ovf = false;
-    (void) ngb_walk<true, false, false>(a, lds + (threadIdx.x >> 6) * NW_LDS_PER_WAVE(true), myl, valid, px, py, pz, h, accept, pair,
-                                        (unsigned int *) nullptr, fill, ovf);
-    if(!EMIT)
-        bh_emit_count(e, mine, lane);
-    if(EMIT && valid) {
-        double *o = w.out + BH_ACC_NOUT * t;
-        o[0] = encounter; o[1] = fws; o[2] = sment; o[3] = gv0; o[4] = gv1; o[5] = gv2; o[6] = mgas; o[7] = 0;
-    }
-    } /* task loop */
-}
-
-/* bh_feedback_kernel with everything it writes on the neighbours' side emitted instead: kind 0 this hole swallows the hole, kind 1 it
- * swallows the gas particle, kind 2 heat (injected / mass_j), kind 3 kick (dvel).  w.bh_swallow / w.sph_swallow are the resolved marks. */
-template <int KT, bool EMIT>
-__global__ __launch_bounds__(256) void bh_effects_kernel(const SphDev a, const int32_t *queue, long long nq, const BhWalkArgs w, const shq_kick_factors kf,
-                                                         const BhEmitArgs e, int32_t *__restrict__ nlist, long long ntasks)
-{
-#pragma clang fp contract(off)
-    __shared__ __attribute__((aligned(32))) char lds[4 * NW_LDS_PER_WAVE(true)];
-    const int lane = threadIdx.x & 63;
-    for(long long task = xcd_block(blockIdx.x, gridDim.x); task < ntasks; task += gridDim.x) {
-    const long long wave = task * (blockDim.x >> 6) + (threadIdx.x >> 6);
-    int32_t *myl = nlist + ((size_t) blockIdx.x * 4 + (threadIdx.x >> 6)) * (size_t) (NL_ROWS * 64) + lane;
-    const long long t = wave * 64 + lane;
-    const bool valid = t < nq;
-    double px = 0, py = 0, pz = 0, h = 1, idens = 0, imtrack = 0, fws = 0, fbenergy = 0, kefb = 0;
-    int channel = 0;
-    unsigned long long myid = 0;
-    if(valid) {
-        const long long pi = queue[t];
-        const double4 p = a.posm[pi];
-        px = p.x; py = p.y; pz = p.z;
-        h = a.hsml[pi];
-        myid = w.ids[pi];
-        const long long b = shq_bh_ordinal(w.bhp, w.nbh, (int32_t) pi);
-        const BhRec &B = w.bh[b];
-        idens = B.Density; imtrack = B.Mtrack;
-        fws = B.FeedbackWeightSum;
-        const double dtime = kf.dloga_for_bin[w.bin_hydro[pi]] / w.P.hubble;
-        fbenergy = w.P.BlackHoleFeedbackFactor * 0.1 * B.Mdot * dtime * (w.P.LightOverUnitVel * w.P.LightOverUnitVel);
-        if(w.P.BlackHoleKineticOn == 1 && B.KEflag > 0) {
-            channel = 1;
-            if(B.KEflag == 2)
-                kefb = B.KineticFdbkEnergy;
-        }
-    }
-    const Kern<KT> kernel(h);
-    const double HH = kernel.H * kernel.H, Hinv = 1.0 / kernel.H;
-    const double h2 = h * h;
-    int mintimebin = SHQ_TIMEBINS, countprogs = 0;
-    unsigned int mine = 0;
-    double accmass = 0, accbh = 0, mom0 = 0, mom1 = 0, mom2 = 0;
-    auto pair = [&](const int s) {
-        const long long p = w.leaf_pidx[s];
-        const double4 q = a.posm_leaf[s];
-        const int type = w.pflags[p] >> 4;
-        if(w.ids[p] == myid)
-            return;
-        if(w.P.WindsDecoupleSph && type == 0 && w.delay[p] > 0)
-            return;
-        if(type == 5) {
-            const long long ob = shq_bh_ordinal(w.bhp, w.nbh, (int32_t) p);
-            if(ob < 0 || w.bh_swallow[ob] == 0)
-                return;
-            if(w.bh_swallow[ob] != myid + 1)
-                return;
-            bh_emit<EMIT>(e, mine, p, t, 0u, 0ull);
-            if(!EMIT)
-                return;
-            const BhRec &O = w.bh[ob];
-            countprogs += O.CountProgs;
-            accbh += O.Mass;
-            double othermass = q.w;
-            if(w.P.SeedBHDynMass > 0 && imtrack > 0)
-                if(O.Mtrack < w.P.SeedBHDynMass)
-                    othermass = O.Mtrack;
-            accmass += othermass;
-            const int bg = w.bin_grav[p];
-            const double v0 = w.vel[3 * p] + kf.gravkicks[bg] * w.treeacc[3 * p] + w.gravpm[3 * p] * kf.FgravkickB;
-            const double v1 = w.vel[3 * p + 1] + kf.gravkicks[bg] * w.treeacc[3 * p + 1] + w.gravpm[3 * p + 1] * kf.FgravkickB;
-            const double v2 = w.vel[3 * p + 2] + kf.gravkicks[bg] * w.treeacc[3 * p + 2] + w.gravpm[3 * p + 2] * kf.FgravkickB;
-            mom0 += (othermass * v0);
-            mom1 += (othermass * v1);
-            mom2 += (othermass * v2);
-            return;
-        }
-        if(type != 0)
-            return;
-        const double d0 = wrapd(px - q.x, a.Box, a.invBox), d1 = wrapd(py - q.y, a.Box, a.invBox), d2 = wrapd(pz - q.z, a.Box, a.invBox);
-        const double r2 = d0 * d0 + d1 * d1 + d2 * d2;
-        const unsigned long long mark = w.sph_swallow[p];
-        if(mark == 0 && r2 < HH) {
-            const int bh = w.bin_hydro[p];
-            if(mintimebin > bh)
-                mintimebin = bh;
-            const double u = sqrt(r2) * Hinv;
-            const double mass_j = q.w;
-            const double wk = kernel.wk(u);
-            if(fws > 0 && fbenergy > 0 && channel == 0 && mass_j > 0) {
-                const double injected = fbenergy * mass_j * wk / fws;
-                bh_emit<EMIT>(e, mine, p, t, 2u, (unsigned long long) __double_as_longlong(injected / mass_j));
-            }
-            if(kefb > 0 && channel == 1 && idens > 0) {
-                const double dvel = sqrt(2 * kefb * wk / idens);
-                bh_emit<EMIT>(e, mine, p, t, 3u, (unsigned long long) __double_as_longlong(dvel));
-            }
-        }
-        if(mark == myid + 1) {
-            bh_emit<EMIT>(e, mine, p, t, 1u, 0ull);
-            if(EMIT) {
-                accmass += q.w;
-                const double4 vp = a.velp[p];
-                mom0 += (q.w * vp.x);
-                mom1 += (q.w * vp.y);
-                mom2 += (q.w * vp.z);
-            }
-        }
-    };
-    auto accept = [&](const double r2, const double hj, const int) { return r2 <= h2 || r2 <= hj * hj; };
-    int fill = 0;
-    bool ovf = false;
-    (void) ngb_walk<true, false, false>(a, lds + (threadIdx.x >> 6) * NW_LDS_PER_WAVE(true), myl, valid, px, py, pz, h, accept, pair,
-                                        (unsigned int *) nullptr, fill, ovf);
-    if(!EMIT)
-        bh_emit_count(e, mine, lane);
-    if(EMIT && valid) {
-        double *o = w.out + BH_FB_NOUT * t;
-        o[0] = accmass; o[1] = accbh; o[2] = mom0; o[3] = mom1; o[4] = mom2; o[5] = countprogs; o[6] = mintimebin; o[7] = 0;
-    }
-    } /* task loop */
-}
-
-template <bool EMIT>
-static int bh_records_launch(shq_context *ctx, const shq_kick_factors *kf, const BhWalkArgs *w, bool effects, const int32_t *d_queue, int64_t nq, const BhEmitArgs &e)
-{
-    SphDev a = make_dev(ctx, w->P.BoxSize);
-    const long long ntasks = (nq + 255) / 256;
-    const unsigned grid = (unsigned) (ntasks < NL_REDO_BLOCKS ? ntasks : NL_REDO_BLOCKS);
-    hipStream_t st = ctx->stream;
-    int32_t *nl = ctx->s_nlist2.ptr;
-    if(!effects)
-        switch(w->P.DensityKernelType) {
-        case 1: bh_marks_kernel<1, EMIT><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, e, nl, ntasks); break;
-        case 2: bh_marks_kernel<2, EMIT><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, e, nl, ntasks); break;
-        default: bh_marks_kernel<4, EMIT><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, e, nl, ntasks); break;
-        }
-    else
-        switch(w->P.DensityKernelType) {
-        case 1: bh_effects_kernel<1, EMIT><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, e, nl, ntasks); break;
-        case 2: bh_effects_kernel<2, EMIT><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, e, nl, ntasks); break;
-        default: bh_effects_kernel<4, EMIT><<<dim3(grid), dim3(256), 0, st>>>(a, d_queue, nq, *w, *kf, e, nl, ntasks); break;
-        }
-    SHQ_HIP(hipGetLastError());
-    return SHQ_OK;
-}
-
+/* ---- the record routes of the two walks, for a multi-rank driver ---------------------------------------------------------------- */
 static int bh_cursor_read(shq_context *ctx, unsigned long long *h)
 {
     SHQ_HIP(hipMemcpyAsync(h, ctx->wind_cnt.ptr, sizeof(*h), hipMemcpyDeviceToHost, ctx->stream));
@@ -853,17 +637,13 @@ int shq_bh_records_count_device(shq_context *ctx, const shq_kick_factors *kf, co
     *nrec = 0;
     if(nq == 0)
         return SHQ_OK;
-    const int kt = w->P.DensityKernelType;
-    SHQ_CHECK(kt == 1 || kt == 2 || kt == 4, SHQ_ERR_INVALID, "unknown DensityKernelType %d", kt);
-    SHQ_TRY(bh_launch_prep(ctx, kf));
+    SHQ_TRY(bh_walk_prep(ctx, kf, w));
     SHQ_TRY(ctx->wind_cnt.reserve(4));
     SHQ_HIP(hipMemsetAsync(ctx->wind_cnt.ptr, 0, sizeof(unsigned long long), ctx->stream));
     BhEmitArgs e;
     memset(&e, 0, sizeof(e));
     e.cursor = ctx->wind_cnt.ptr;
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_BH_COUNT], ctx->stream));
-    SHQ_TRY(bh_records_launch<false>(ctx, kf, w, effects, d_queue, nq, e));
-    SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_T_BH_COUNT], ctx->stream));
+    SHQ_TRY(bh_walk_launch<BH_COUNT>(ctx, kf, w, effects, d_queue, nq, e, nullptr));
     unsigned long long h = 0;
     SHQ_TRY(bh_cursor_read(ctx, &h));
     *nrec = (int64_t) h;
@@ -871,30 +651,6 @@ int shq_bh_records_count_device(shq_context *ctx, const shq_kick_factors *kf, co
 }
 
 namespace {
-__global__ void bh_route_kernel(long long np, const unsigned long long *__restrict__ keys, long long nlocal, const int32_t *__restrict__ ghost_owner,
-                                const int32_t *__restrict__ ghost_index, int rank, unsigned long long queue_offset, const int32_t *__restrict__ qpos,
-                                unsigned long long *__restrict__ routed, uint32_t *__restrict__ owner_out, unsigned long long *counts)
-{
-    const long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if(k >= np)
-        return;
-    const long long p = (long long) (keys[k] >> 32);
-    const unsigned long long t = keys[k] & 0xffffffffull;
-    const bool own = p < nlocal;
-    const unsigned o = (unsigned) (own ? rank : ghost_owner[p - nlocal]);
-    const unsigned idx = (unsigned) (own ? (int32_t) p : ghost_index[p - nlocal]);
-    routed[k] = ((unsigned long long) idx << 32) | (queue_offset + (qpos ? (unsigned long long) qpos[t] : t));
-    owner_out[k] = o;
-    atomicAdd(&counts[o], 1ull);
-}
-
-__global__ void bh_gather_u32_kernel(long long n, const uint32_t *__restrict__ src, const uint32_t *__restrict__ ord, uint32_t *out)
-{
-    const long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x;
-    if(k < n)
-        out[k] = src[ord[k]];
-}
-
 __global__ void bh_record_write_kernel(long long n, const uint32_t *__restrict__ owner_sorted, const uint32_t *__restrict__ ord, const unsigned long long *__restrict__ routed,
                                        const uint32_t *__restrict__ kind, const unsigned long long *__restrict__ val, shq_bh_record *out)
 {
@@ -938,39 +694,18 @@ int shq_bh_records_emit_device(shq_context *ctx, const shq_kick_factors *kf, con
     e.keys = ctx->metal_keys[0].ptr;
     e.val = reinterpret_cast<unsigned long long *>(ctx->metal_val[0].ptr);
     e.kind = ctx->bhd_kind.ptr;
-    SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_BH], st));
-    SHQ_TRY(bh_records_launch<true>(ctx, kf, w, effects, d_queue, nq, e));
-    if(!effects)
-        bh_accretion_post_kernel<<<dim3(nblk(nq)), dim3(256), 0, st>>>(nq, d_queue, *w, *kf, ctx->posm.ptr, d_post);
-    else
-        bh_feedback_post_kernel<<<dim3(nblk(nq)), dim3(256), 0, st>>>(nq, d_queue, *w, ctx->posm.ptr);
-    SHQ_HIP(hipGetLastError());
-    SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_T_BH], st));
+    SHQ_TRY(bh_walk_launch<BH_EMIT>(ctx, kf, w, effects, d_queue, nq, e, d_post));
     unsigned long long h = 0;
     SHQ_TRY(bh_cursor_read(ctx, &h));
     SHQ_CHECK(h == (unsigned long long) nrec, SHQ_ERR_STATE, "black-hole records: the two walks disagree on their number (%lld, %llu)", (long long) nrec, h);
     SHQ_HIP(hipEventRecord(ctx->ev_begin[SHQ_T_BH_ROUTE], st));
-    if(nrec == 0) {
-        SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_T_BH_ROUTE], st));
-        return SHQ_OK;
+    if(nrec > 0) {
+        SHQ_TRY(shq_route_sort(ctx, nrec, nlocal, d_ghost_owner, d_ghost_index, nranks, rank, queue_offset, d_qpos, d_counts));
+        bh_record_write_kernel<<<dim3(nblk(nrec)), dim3(256), 0, st>>>(nrec, ctx->metal_u32[0].ptr, ctx->metal_u32[3].ptr, ctx->metal_keys[1].ptr, ctx->bhd_kind.ptr,
+                                                                       reinterpret_cast<unsigned long long *>(ctx->metal_val[0].ptr),
+                                                                       reinterpret_cast<shq_bh_record *>(ctx->metal_trip.ptr));
+        SHQ_HIP(hipGetLastError());
     }
-    const long long n = (long long) nrec;
-    uint32_t *owner = ctx->metal_u32[0].ptr, *ord1 = ctx->metal_u32[1].ptr, *okey = ctx->metal_u32[2].ptr, *ord2 = ctx->metal_u32[3].ptr;
-    unsigned long long *routed = ctx->metal_keys[1].ptr;
-    bh_route_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, ctx->metal_keys[0].ptr, nlocal, d_ghost_owner, d_ghost_index, rank, (unsigned long long) queue_offset, d_qpos,
-                                                         routed, owner, d_counts);
-    SHQ_HIP(hipGetLastError());
-    /* by (row at the owner, hole), then, stable, by owner: as shq_metal_triples_device */
-    SHQ_TRY(prim_sort_pairs(ctx, routed, ctx->metal_keys[0].ptr, rocprim::counting_iterator<uint32_t>(0), ord1, (size_t) n, 0, 64));
-    bh_gather_u32_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, owner, ord1, okey);
-    SHQ_HIP(hipGetLastError());
-    unsigned bits = 1;
-    while(bits < 32 && (1ull << bits) < (unsigned long long) nranks)
-        bits++;
-    SHQ_TRY(prim_sort_pairs(ctx, okey, owner, ord1, ord2, (size_t) n, 0, bits));
-    bh_record_write_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, owner, ord2, routed, ctx->bhd_kind.ptr, reinterpret_cast<unsigned long long *>(ctx->metal_val[0].ptr),
-                                                                reinterpret_cast<shq_bh_record *>(ctx->metal_trip.ptr));
-    SHQ_HIP(hipGetLastError());
     SHQ_HIP(hipEventRecord(ctx->ev_end[SHQ_T_BH_ROUTE], st));
     return SHQ_OK;
 }

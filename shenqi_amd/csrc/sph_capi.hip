@@ -1096,6 +1096,173 @@ void bh_fill_args(shq_context *ctx, const shq_bh_params *params, int64_t rnd_siz
     w.P = *params;
 }
 
+inline size_t bh_ordinal(const BhSet &S, int32_t i) { return (size_t) (std::lower_bound(S.bhp.begin(), S.bhp.end(), i) - S.bhp.begin()); }
+
+/* blackhole_accretion_reduce (PRIMARY) and what the postprocess left: out holds the walk's rows of the queue, then the postprocess' */
+void bh_accretion_reduce(const shq_bh_slot_view *bh, const shq_bh_work *work, const BhSet &S, const int32_t *queue, int64_t nqueue, const std::vector<double> &out)
+{
+    for(int64_t t = 0; t < nqueue; t++) {
+        const size_t b = bh_ordinal(S, queue[t]);
+        const int32_t pi = S.pi[b];
+        const double *o = &out[8 * (size_t) t], *p = &out[8 * (size_t) nqueue + 8 * (size_t) t];
+        const BhRec &R = S.rec[b];
+        *bhfield<int8_t>(bh, pi, bh->off_encounter) = (int8_t) o[0];
+        work->BH_FeedbackWeightSum[pi] = o[1];
+        work->MgasEnc[pi] = o[6];
+        work->BH_Entropy[pi] = p[0];
+        for(int d = 0; d < 3; d++) {
+            work->BH_SurroundingGasVel[pi][d] = p[1 + d];
+            bhfield<double>(bh, pi, bh->off_dragaccel)[d] = p[4 + d];
+        }
+        *bhfield<double>(bh, pi, bh->off_mdot) = R.Mdot;
+        *bhfield<double>(bh, pi, bh->off_mass) = R.Mass;
+        *bhfield<double>(bh, pi, bh->off_kineticfdbkenergy) = R.KineticFdbkEnergy;
+        if(work->KEflag)
+            work->KEflag[pi] = R.KEflag;
+    }
+}
+
+/* blackhole_feedback_reduce (PRIMARY) of the hole with ordinal b; blackhole_feedback_postprocess (:929-965) ran on the device: its
+ * results come back in the hole's record and in its row (shq_rows_gather: Vel and the mass word) */
+void bh_feedback_reduce(const shq_part_view *parts, const shq_bh_slot_view *bh, const shq_bh_work *work, const BhSet &S, size_t b, const double *o, const double *row)
+{
+    const int32_t i = S.bhp[b], pi = S.pi[b];
+    const BhRec &R = S.rec[b];
+    work->BH_accreted_Mass[pi] = o[0];
+    work->BH_accreted_BHMass[pi] = o[1];
+    for(int d = 0; d < 3; d++)
+        work->BH_accreted_momentum[pi][d] = o[2 + d];
+    *bhfield<uint8_t>(bh, pi, bh->off_mintimebin) = (uint8_t) o[6];
+    *bhfield<int32_t>(bh, pi, bh->off_countprogs) = R.CountProgs;
+    *bhfield<double>(bh, pi, bh->off_mass) = R.Mass;
+    *bhfield<double>(bh, pi, bh->off_mtrack) = R.Mtrack;
+    *bhfield<double>(bh, pi, bh->off_kineticfdbkenergy) = R.KineticFdbkEnergy;
+    double *v = pfield_w<double>(parts, i, parts->off_vel);
+    for(int d = 0; d < 3; d++)
+        v[d] = row[d];
+    *pfield_w<float>(parts, i, parts->off_mass) = (float) row[5];
+}
+
+/* the row of gas particle i after the feedback, into the caller's arrays: Vel, Entropy, BHHeated, and a swallowed particle becomes
+ * garbage.  Returns 1 if it was swallowed now. */
+int bh_gas_writeback(const shq_part_view *parts, const shq_sph_view *sph, int64_t i, const double *r, int64_t MaxPart)
+{
+    const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+    uint8_t *flags = pfield_w<uint8_t>(parts, i, parts->off_flags);
+    *sfield(sph, pi, sph->off_entropy) = r[3];
+    double *v = pfield_w<double>(parts, i, parts->off_vel);
+    for(int d = 0; d < 3; d++)
+        v[d] = r[d];
+    if(r[7] != 0)
+        *flags |= 8u; /* BHHeated: bit 3 of the flag byte */
+    if(!((unsigned) r[6] & 1u) || (*flags & 1u))
+        return 0;
+    *flags |= 1u; /* slots_mark_garbage, slotsmanager.cpp:590-599 */
+    *reinterpret_cast<int32_t *>(static_cast<char *>(sph->base) + (size_t) pi * sph->elsize) = (int32_t) (MaxPart + 100); /* ReverseLink */
+    return 1;
+}
+
+/* the resolved marks by particle (live gas) and by hole ordinal, staged in the caller's vectors and uploaded */
+int bh_marks_upload(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const shq_bh_work *work, const BhSet &S, std::vector<uint64_t> &sphsw,
+                    std::vector<uint64_t> &bhsw, const char *who)
+{
+    const int64_t n = parts->numpart;
+    const size_t nbh = S.bhp.size();
+    sphsw.assign((size_t) std::max<int64_t>(n, 1), 0);
+    bhsw.assign(std::max<size_t>(nbh, 1), 0);
+    for(int64_t i = 0; i < n; i++)
+        if(*pfield<uint8_t>(parts, i, parts->off_type) == 0 && !(*pfield<uint8_t>(parts, i, parts->off_flags) & 1u)) {
+            const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+            SHQ_CHECK(pi >= 0 && pi < sph->numslots, SHQ_ERR_INVALID, "%s: gas particle %ld has PI %d outside the slot array", who, (long) i, pi);
+            sphsw[(size_t) i] = work->SPH_SwallowID[pi];
+        }
+    for(size_t b = 0; b < nbh; b++)
+        bhsw[b] = work->BH_SwallowID[S.pi[b]];
+    SHQ_HIP(hipMemcpyAsync(ctx->bhw_sphsw.ptr, sphsw.data(), sizeof(uint64_t) * (size_t) n, hipMemcpyHostToDevice, ctx->stream));
+    if(nbh)
+        SHQ_HIP(hipMemcpyAsync(ctx->bhw_bhsw.ptr, bhsw.data(), sizeof(uint64_t) * nbh, hipMemcpyHostToDevice, ctx->stream));
+    return SHQ_OK;
+}
+
+/* blackhole_feedback_haswork (:878-883): a hole that is marked itself does not swallow or heat.  qpos: its position in the whole queue */
+void bh_feedback_haswork(const shq_part_view *parts, const shq_bh_work *work, const int32_t *queue, int64_t nqueue, std::vector<int32_t> &q, std::vector<int32_t> *qpos)
+{
+    for(int64_t k = 0; k < nqueue; k++)
+        if(work->BH_SwallowID[*pfield<int32_t>(parts, queue[k], parts->off_pi)] == 0) {
+            q.push_back(queue[k]);
+            if(qpos)
+                qpos->push_back((int32_t) k);
+        }
+}
+
+/* ---- what the routed calls of a multi-rank driver share (shq_bh_accretion_marks, shq_bh_feedback_effects, shq_metal_return_triples):
+ * this rank's part of a global queue, the owners of its imports, the caller's room for the routed list and its per-owner counts */
+struct Routed {
+    const char *who, *item, *list; /* for the error texts: the call, "hole" / "star", "records" / "triples" */
+    int64_t nlocal;
+    const int32_t *ghost_owner, *ghost_index;
+    int nranks, rank;
+    int64_t queue_offset, capacity, *counts, *nlist;
+    /* on the device (routed_upload): owners and rows of the imports, positions in the whole queue (or NULL), the per-owner counts */
+    int32_t *d_go, *d_gi, *d_qpos;
+    unsigned long long *d_counts;
+};
+
+int routed_check(const shq_part_view *parts, const int32_t *queue, int64_t nqueue, const Routed &d)
+{
+    const int64_t n = parts->numpart, ng = n - d.nlocal;
+    SHQ_CHECK(d.counts && d.nlist, SHQ_ERR_INVALID, "%s: null argument", d.who);
+    SHQ_CHECK(nqueue >= 0 && d.nranks >= 1 && d.rank >= 0 && d.rank < d.nranks && d.nlocal >= 0 && d.nlocal <= n && (ng == 0 || (d.ghost_owner && d.ghost_index)) &&
+                  d.capacity >= 0,
+              SHQ_ERR_INVALID, "%s: bad counts (nqueue %ld, nlocal %ld of %ld, rank %d of %d)", d.who, (long) nqueue, (long) d.nlocal, (long) n, d.rank, d.nranks);
+    SHQ_CHECK(d.queue_offset >= 0 && d.queue_offset + nqueue < (1ll << 31), SHQ_ERR_INVALID,
+              "%s: a global queue of 2^31 or more %ss (offset %ld + %ld): the %s position is 32 bits of a sort key", d.who, d.item, (long) d.queue_offset, (long) nqueue,
+              d.item);
+    *d.nlist = 0;
+    for(int r = 0; r < d.nranks; r++)
+        d.counts[r] = 0;
+    for(int64_t k = 0; k < nqueue; k++)
+        SHQ_CHECK(queue[k] >= 0 && queue[k] < d.nlocal, SHQ_ERR_INVALID, "%s: queue[%ld] = %d is not one of this rank's own particles", d.who, (long) k, queue[k]);
+    for(int64_t g = 0; g < ng; g++)
+        SHQ_CHECK(d.ghost_owner[g] >= 0 && d.ghost_owner[g] < d.nranks && d.ghost_index[g] >= 0, SHQ_ERR_INVALID, "%s: import %ld has owner %d, index %d", d.who, (long) g,
+                  d.ghost_owner[g], d.ghost_index[g]);
+    return SHQ_OK;
+}
+
+/* owners and rows of the imports, then qpos (may be empty), into bhw_tlist; the per-owner counts live behind the cursors of wind_cnt */
+int routed_upload(shq_context *ctx, int64_t n, Routed &d, const std::vector<int32_t> &qpos)
+{
+    hipStream_t st = ctx->stream;
+    const int64_t ng = n - d.nlocal;
+    const size_t g1 = (size_t) std::max<int64_t>(ng, 1);
+    SHQ_TRY(ctx->bhw_tlist.reserve(2 * g1 + std::max<size_t>(qpos.size(), 1)));
+    SHQ_TRY(ctx->wind_cnt.reserve(4 + (size_t) d.nranks));
+    d.d_go = ctx->bhw_tlist.ptr;
+    d.d_gi = d.d_go + g1;
+    d.d_qpos = qpos.empty() ? nullptr : d.d_gi + g1;
+    d.d_counts = ctx->wind_cnt.ptr + 4;
+    if(ng > 0) {
+        SHQ_HIP(hipMemcpyAsync(d.d_go, d.ghost_owner, sizeof(int32_t) * (size_t) ng, hipMemcpyHostToDevice, st));
+        SHQ_HIP(hipMemcpyAsync(d.d_gi, d.ghost_index, sizeof(int32_t) * (size_t) ng, hipMemcpyHostToDevice, st));
+    }
+    if(!qpos.empty())
+        SHQ_HIP(hipMemcpyAsync(d.d_qpos, qpos.data(), sizeof(int32_t) * qpos.size(), hipMemcpyHostToDevice, st));
+    return SHQ_OK;
+}
+
+/* the per-owner counts of a routed list of n entries into the caller's array; waits for everything enqueued before */
+int routed_counts(shq_context *ctx, const Routed &d, int64_t n)
+{
+    std::vector<unsigned long long> hc((size_t) d.nranks, 0);
+    SHQ_HIP(hipMemcpyAsync(hc.data(), d.d_counts, sizeof(unsigned long long) * (size_t) d.nranks, hipMemcpyDeviceToHost, ctx->stream));
+    SHQ_HIP(hipStreamSynchronize(ctx->stream));
+    int64_t sum = 0;
+    for(int r = 0; r < d.nranks; r++)
+        sum += d.counts[r] = (int64_t) hc[(size_t) r];
+    SHQ_CHECK(sum == n, SHQ_ERR_STATE, "%s: the per-owner counts add up to %ld of %ld %s", d.who, (long) sum, (long) n, d.list);
+    return SHQ_OK;
+}
+
 } // namespace
 
 extern "C" int shq_bh_accretion(shq_context *ctx, const shq_tree_view *tree, const shq_part_view *parts, const shq_sph_view *sph, const shq_bh_slot_view *bh,
@@ -1154,25 +1321,7 @@ extern "C" int shq_bh_accretion(shq_context *ctx, const shq_tree_view *tree, con
     for(size_t b = 0; b < nbh; b++)
         if(bhsw[b])
             work->BH_SwallowID[S.pi[b]] = bhsw[b];
-    for(int64_t t = 0; t < nqueue; t++) {
-        const size_t b = (size_t) (std::lower_bound(S.bhp.begin(), S.bhp.end(), queue[t]) - S.bhp.begin());
-        const int32_t pi = S.pi[b];
-        const double *o = &out[8 * (size_t) t], *p = &out[8 * (size_t) nqueue + 8 * (size_t) t];
-        const BhRec &R = S.rec[b];
-        *bhfield<int8_t>(bh, pi, bh->off_encounter) = (int8_t) o[0];          /* blackhole_accretion_reduce, PRIMARY */
-        work->BH_FeedbackWeightSum[pi] = o[1];
-        work->MgasEnc[pi] = o[6];
-        work->BH_Entropy[pi] = p[0];
-        for(int d = 0; d < 3; d++) {
-            work->BH_SurroundingGasVel[pi][d] = p[1 + d];
-            bhfield<double>(bh, pi, bh->off_dragaccel)[d] = p[4 + d];
-        }
-        *bhfield<double>(bh, pi, bh->off_mdot) = R.Mdot;
-        *bhfield<double>(bh, pi, bh->off_mass) = R.Mass;
-        *bhfield<double>(bh, pi, bh->off_kineticfdbkenergy) = R.KineticFdbkEnergy;
-        if(work->KEflag)
-            work->KEflag[pi] = R.KEflag;
-    }
+    bh_accretion_reduce(bh, work, S, queue, nqueue, out);
     return SHQ_OK;
 }
 
@@ -1192,27 +1341,14 @@ extern "C" int shq_bh_feedback(shq_context *ctx, const shq_tree_view *tree, cons
     BhSet S;
     SHQ_TRY(bh_collect(parts, bh, work, true, S));
     const size_t nbh = S.bhp.size();
-    /* blackhole_feedback_haswork (:878-883): a hole that is marked itself does not swallow or heat */
     std::vector<int32_t> q;
-    for(int64_t k = 0; k < nqueue; k++)
-        if(work->BH_SwallowID[*pfield<int32_t>(parts, queue[k], parts->off_pi)] == 0)
-            q.push_back(queue[k]);
+    bh_feedback_haswork(parts, work, queue, nqueue, q, nullptr);
     SHQ_TRY(bh_upload_common(ctx, tree, parts, sph, ids, rnd_table, rnd_size, S, q));
     hipStream_t st = ctx->stream;
-    std::vector<uint64_t> sphsw((size_t) std::max<int64_t>(n, 1), 0), bhsw(std::max<size_t>(nbh, 1), 0), swid(std::max<size_t>(nbh, 1));
-    for(int64_t i = 0; i < n; i++)
-        if(*pfield<uint8_t>(parts, i, parts->off_type) == 0 && !(*pfield<uint8_t>(parts, i, parts->off_flags) & 1u)) {
-            const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
-            SHQ_CHECK(pi >= 0 && pi < sph->numslots, SHQ_ERR_INVALID, "bh_feedback: gas particle %ld has PI %d outside the slot array", (long) i, pi);
-            sphsw[i] = work->SPH_SwallowID[pi];
-        }
-    for(size_t b = 0; b < nbh; b++)
-        bhsw[b] = work->BH_SwallowID[S.pi[b]];
-    SHQ_HIP(hipMemcpyAsync(ctx->bhw_sphsw.ptr, sphsw.data(), sizeof(uint64_t) * (size_t) n, hipMemcpyHostToDevice, st));
-    if(nbh) {
-        SHQ_HIP(hipMemcpyAsync(ctx->bhw_bhsw.ptr, bhsw.data(), sizeof(uint64_t) * nbh, hipMemcpyHostToDevice, st));
+    std::vector<uint64_t> sphsw, bhsw, swid(std::max<size_t>(nbh, 1));
+    SHQ_TRY(bh_marks_upload(ctx, parts, sph, work, S, sphsw, bhsw, "bh_feedback"));
+    if(nbh)
         SHQ_HIP(hipMemsetAsync(ctx->bhw_swid.ptr, 0xff, sizeof(uint64_t) * nbh, st));
-    }
     SHQ_TRY(ctx->bhw_eeqos.reserve((size_t) std::max<int64_t>(n, 1)));
     SHQ_TRY(ctx->bhw_heated.reserve((size_t) std::max<int64_t>(n, 1)));
     SHQ_TRY(ctx->bhw_touched.reserve((size_t) std::max<int64_t>(n, 1)));
@@ -1255,20 +1391,8 @@ extern "C" int shq_bh_feedback(shq_context *ctx, const shq_tree_view *tree, cons
     int64_t nsph = 0, nbhs = 0;
     for(int64_t t = 0; t < nt; t++) {
         const int64_t i = tl[(size_t) t];
-        const double *r = &rows[8 * (size_t) t];
         SHQ_CHECK(*pfield<uint8_t>(parts, i, parts->off_type) == 0, SHQ_ERR_STATE, "bh_feedback: the walk touched a particle that is not gas");
-        const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
-        *sfield(sph, pi, sph->off_entropy) = r[3];
-        double *v = pfield_w<double>(parts, i, parts->off_vel);
-        for(int d = 0; d < 3; d++)
-            v[d] = r[d];
-        if(r[7] != 0)
-            *pfield_w<uint8_t>(parts, i, parts->off_flags) |= 8u; /* BHHeated: bit 3 of the flag byte */
-        if(((unsigned) r[6] & 1u) && !(*pfield<uint8_t>(parts, i, parts->off_flags) & 1u)) { /* slots_mark_garbage, slotsmanager.cpp:590-599 */
-            *pfield_w<uint8_t>(parts, i, parts->off_flags) |= 1u;
-            *reinterpret_cast<int32_t *>(static_cast<char *>(sph->base) + (size_t) pi * sph->elsize) = (int32_t) (MaxPart + 100);
-            nsph++;
-        }
+        nsph += bh_gas_writeback(parts, sph, i, &rows[8 * (size_t) t], MaxPart);
     }
     for(size_t b = 0; b < nbh; b++) {
         const int64_t i = S.bhp[b];
@@ -1283,26 +1407,9 @@ extern "C" int shq_bh_feedback(shq_context *ctx, const shq_tree_view *tree, cons
             nbhs++;
         }
     }
-    /* blackhole_feedback_reduce (PRIMARY); blackhole_feedback_postprocess (:929-965) ran on the device: its results come back */
     for(int64_t t = 0; t < nq; t++) {
-        const int32_t i = q[t];
-        const size_t b = (size_t) (std::lower_bound(S.bhp.begin(), S.bhp.end(), i) - S.bhp.begin());
-        const int32_t pi = S.pi[b];
-        const double *o = &out[8 * (size_t) t];
-        const BhRec &R = S.rec[b];
-        work->BH_accreted_Mass[pi] = o[0];
-        work->BH_accreted_BHMass[pi] = o[1];
-        for(int d = 0; d < 3; d++)
-            work->BH_accreted_momentum[pi][d] = o[2 + d];
-        *bhfield<uint8_t>(bh, pi, bh->off_mintimebin) = (uint8_t) o[6];
-        *bhfield<int32_t>(bh, pi, bh->off_countprogs) = R.CountProgs;
-        *bhfield<double>(bh, pi, bh->off_mass) = R.Mass;
-        *bhfield<double>(bh, pi, bh->off_mtrack) = R.Mtrack;
-        *bhfield<double>(bh, pi, bh->off_kineticfdbkenergy) = R.KineticFdbkEnergy;
-        double *v = pfield_w<double>(parts, i, parts->off_vel);
-        for(int d = 0; d < 3; d++)
-            v[d] = bh1[8 * b + d];
-        *pfield_w<float>(parts, i, parts->off_mass) = (float) bh1[8 * b + 5];
+        const size_t b = bh_ordinal(S, q[(size_t) t]);
+        bh_feedback_reduce(parts, bh, work, S, b, &out[8 * (size_t) t], &bh1[8 * b]);
     }
     if(n_sph_swallowed)
         *n_sph_swallowed = nsph;
@@ -1313,77 +1420,6 @@ extern "C" int shq_bh_feedback(shq_context *ctx, const shq_tree_view *tree, cons
 
 /* ---- the parts of the two calls above for a multi-rank driver ------------------------------------------------------------------- */
 namespace {
-struct BhDist {
-    int64_t nlocal;
-    const int32_t *ghost_owner, *ghost_index;
-    int nranks, rank;
-    int64_t queue_offset;
-    shq_bh_record *records;
-    int64_t capacity, *counts, *nrecords;
-};
-
-int bh_dist_check(const shq_part_view *parts, const int32_t *queue, int64_t nqueue, const BhDist &d, const char *who)
-{
-    const int64_t n = parts->numpart, ng = n - d.nlocal;
-    SHQ_CHECK(d.counts && d.nrecords, SHQ_ERR_INVALID, "%s: null argument", who);
-    SHQ_CHECK(nqueue >= 0 && d.nranks >= 1 && d.rank >= 0 && d.rank < d.nranks && d.nlocal >= 0 && d.nlocal <= n && (ng == 0 || (d.ghost_owner && d.ghost_index)) &&
-                  d.capacity >= 0,
-              SHQ_ERR_INVALID, "%s: bad counts (nqueue %ld, nlocal %ld of %ld, rank %d of %d)", who, (long) nqueue, (long) d.nlocal, (long) n, d.rank, d.nranks);
-    SHQ_CHECK(d.queue_offset >= 0 && d.queue_offset + nqueue < (1ll << 31), SHQ_ERR_INVALID,
-              "%s: a global queue of 2^31 or more holes (offset %ld + %ld): the hole position is 32 bits of a sort key", who, (long) d.queue_offset, (long) nqueue);
-    *d.nrecords = 0;
-    for(int r = 0; r < d.nranks; r++)
-        d.counts[r] = 0;
-    for(int64_t k = 0; k < nqueue; k++)
-        SHQ_CHECK(queue[k] < d.nlocal, SHQ_ERR_INVALID, "%s: queue[%ld] = %d is not one of this rank's own particles", who, (long) k, queue[k]);
-    for(int64_t g = 0; g < ng; g++)
-        SHQ_CHECK(d.ghost_owner[g] >= 0 && d.ghost_owner[g] < d.nranks && d.ghost_index[g] >= 0, SHQ_ERR_INVALID, "%s: import %ld has owner %d, index %d", who, (long) g,
-                  d.ghost_owner[g], d.ghost_index[g]);
-    return SHQ_OK;
-}
-
-/* owners and rows of the imports, then qpos (may be empty), into bhw_tlist; the per-owner counts live behind the emit cursor */
-int bh_dist_upload(shq_context *ctx, int64_t n, const BhDist &d, const std::vector<int32_t> &qpos, int32_t **d_go, int32_t **d_gi, int32_t **d_qpos,
-                   unsigned long long **d_counts)
-{
-    hipStream_t st = ctx->stream;
-    const int64_t ng = n - d.nlocal;
-    const size_t g1 = (size_t) std::max<int64_t>(ng, 1);
-    SHQ_TRY(ctx->bhw_tlist.reserve(2 * g1 + std::max<size_t>(qpos.size(), 1)));
-    SHQ_TRY(ctx->wind_cnt.reserve(4 + (size_t) d.nranks));
-    *d_go = ctx->bhw_tlist.ptr;
-    *d_gi = *d_go + g1;
-    *d_qpos = qpos.empty() ? nullptr : *d_gi + g1;
-    *d_counts = ctx->wind_cnt.ptr + 4;
-    if(ng > 0) {
-        SHQ_HIP(hipMemcpyAsync(*d_go, d.ghost_owner, sizeof(int32_t) * (size_t) ng, hipMemcpyHostToDevice, st));
-        SHQ_HIP(hipMemcpyAsync(*d_gi, d.ghost_index, sizeof(int32_t) * (size_t) ng, hipMemcpyHostToDevice, st));
-    }
-    if(!qpos.empty())
-        SHQ_HIP(hipMemcpyAsync(*d_qpos, qpos.data(), sizeof(int32_t) * qpos.size(), hipMemcpyHostToDevice, st));
-    return SHQ_OK;
-}
-
-/* the routed list and its per-owner counts into the caller's arrays (enqueued; the caller synchronises) */
-int bh_dist_download(shq_context *ctx, const BhDist &d, int64_t nrec, const unsigned long long *d_counts, std::vector<unsigned long long> &hc)
-{
-    hipStream_t st = ctx->stream;
-    hc.assign((size_t) d.nranks, 0);
-    SHQ_HIP(hipMemcpyAsync(hc.data(), d_counts, sizeof(unsigned long long) * (size_t) d.nranks, hipMemcpyDeviceToHost, st));
-    if(nrec > 0)
-        SHQ_HIP(hipMemcpyAsync(d.records, ctx->metal_trip.ptr, sizeof(shq_bh_record) * (size_t) nrec, hipMemcpyDeviceToHost, st));
-    return SHQ_OK;
-}
-
-int bh_dist_counts(const BhDist &d, int64_t nrec, const std::vector<unsigned long long> &hc, const char *who)
-{
-    int64_t sum = 0;
-    for(int r = 0; r < d.nranks; r++)
-        sum += d.counts[r] = (int64_t) hc[(size_t) r];
-    SHQ_CHECK(sum == nrec, SHQ_ERR_STATE, "%s: the per-owner counts add up to %ld of %ld records", who, (long) sum, (long) nrec);
-    return SHQ_OK;
-}
-
 /* what a list of records gathered from other ranks must satisfy before anything reads a particle through it */
 int bh_records_check(const shq_part_view *parts, const shq_bh_record *rec, int64_t n, int maxkind, int64_t n_sph_slots, int64_t n_bh_slots, const char *who)
 {
@@ -1412,20 +1448,17 @@ extern "C" int shq_bh_accretion_marks(shq_context *ctx, const shq_tree_view *tre
 {
     const char *who = "bh_accretion_marks";
     SHQ_TRY(bh_check_common(ctx, tree, parts, sph, bh, ids, queue, nqueue, kf, params, rnd_table, rnd_size, work, who));
-    const BhDist d = {nlocal, ghost_owner, ghost_index, nranks, rank, queue_offset, records, capacity, counts, nrecords};
-    SHQ_TRY(bh_dist_check(parts, queue, nqueue, d, who));
+    Routed d = {who, "hole", "records", nlocal, ghost_owner, ghost_index, nranks, rank, queue_offset, capacity, counts, nrecords};
+    SHQ_TRY(routed_check(parts, queue, nqueue, d));
     if(nqueue == 0)
         return SHQ_OK;
     SHQ_HIP(hipSetDevice(ctx->device));
-    const int64_t n = parts->numpart;
     BhSet S;
     SHQ_TRY(bh_collect(parts, bh, work, false, S));
     const size_t nbh = S.bhp.size();
     std::vector<int32_t> q(queue, queue + nqueue);
     SHQ_TRY(bh_upload_common(ctx, tree, parts, sph, ids, rnd_table, rnd_size, S, q));
-    int32_t *d_go, *d_gi, *d_qpos;
-    unsigned long long *d_counts;
-    SHQ_TRY(bh_dist_upload(ctx, n, d, std::vector<int32_t>(), &d_go, &d_gi, &d_qpos, &d_counts));
+    SHQ_TRY(routed_upload(ctx, parts->numpart, d, std::vector<int32_t>()));
     hipStream_t st = ctx->stream;
     BhWalkArgs w;
     bh_fill_args(ctx, params, rnd_size, nbh, w);
@@ -1437,33 +1470,15 @@ extern "C" int shq_bh_accretion_marks(shq_context *ctx, const shq_tree_view *tre
         return SHQ_OK;
     SHQ_CHECK(capacity >= nrec, SHQ_ERR_INVALID, "%s: room for %ld records, %ld found", who, (long) capacity, (long) nrec);
     double *d_post = ctx->bhw_out.ptr + 8 * (size_t) nqueue;
-    SHQ_TRY(shq_bh_records_emit_device(ctx, kf, &w, false, ctx->bhw_queue.ptr, nqueue, nrec, nlocal, d_go, d_gi, nranks, rank, queue_offset, nullptr, d_counts, d_post));
+    SHQ_TRY(shq_bh_records_emit_device(ctx, kf, &w, false, ctx->bhw_queue.ptr, nqueue, nrec, nlocal, d.d_go, d.d_gi, nranks, rank, queue_offset, nullptr, d.d_counts,
+                                       d_post));
     std::vector<double> out(16 * (size_t) nqueue);
-    std::vector<unsigned long long> hc;
     SHQ_HIP(hipMemcpyAsync(out.data(), ctx->bhw_out.ptr, sizeof(double) * out.size(), hipMemcpyDeviceToHost, st));
     SHQ_HIP(hipMemcpyAsync(S.rec.data(), ctx->bhw_rec.ptr, sizeof(BhRec) * nbh, hipMemcpyDeviceToHost, st));
-    SHQ_TRY(bh_dist_download(ctx, d, nrec, d_counts, hc));
-    SHQ_HIP(hipStreamSynchronize(st));
-    SHQ_TRY(bh_dist_counts(d, nrec, hc, who));
-    for(int64_t t = 0; t < nqueue; t++) { /* blackhole_accretion_reduce (PRIMARY) and what the postprocess left, as in shq_bh_accretion */
-        const size_t b = (size_t) (std::lower_bound(S.bhp.begin(), S.bhp.end(), queue[t]) - S.bhp.begin());
-        const int32_t pi = S.pi[b];
-        const double *o = &out[8 * (size_t) t], *p = &out[8 * (size_t) nqueue + 8 * (size_t) t];
-        const BhRec &R = S.rec[b];
-        *bhfield<int8_t>(bh, pi, bh->off_encounter) = (int8_t) o[0];
-        work->BH_FeedbackWeightSum[pi] = o[1];
-        work->MgasEnc[pi] = o[6];
-        work->BH_Entropy[pi] = p[0];
-        for(int k = 0; k < 3; k++) {
-            work->BH_SurroundingGasVel[pi][k] = p[1 + k];
-            bhfield<double>(bh, pi, bh->off_dragaccel)[k] = p[4 + k];
-        }
-        *bhfield<double>(bh, pi, bh->off_mdot) = R.Mdot;
-        *bhfield<double>(bh, pi, bh->off_mass) = R.Mass;
-        *bhfield<double>(bh, pi, bh->off_kineticfdbkenergy) = R.KineticFdbkEnergy;
-        if(work->KEflag)
-            work->KEflag[pi] = R.KEflag;
-    }
+    if(nrec > 0)
+        SHQ_HIP(hipMemcpyAsync(records, ctx->metal_trip.ptr, sizeof(shq_bh_record) * (size_t) nrec, hipMemcpyDeviceToHost, st));
+    SHQ_TRY(routed_counts(ctx, d, nrec));
+    bh_accretion_reduce(bh, work, S, queue, nqueue, out);
     return SHQ_OK;
 }
 
@@ -1517,39 +1532,22 @@ extern "C" int shq_bh_feedback_effects(shq_context *ctx, const shq_tree_view *tr
     const char *who = "bh_feedback_effects";
     SHQ_TRY(bh_check_common(ctx, tree, parts, sph, bh, ids, queue, nqueue, kf, params, rnd_table, rnd_size, work, who));
     SHQ_CHECK(work->BH_accreted_Mass && work->BH_accreted_BHMass && work->BH_accreted_momentum, SHQ_ERR_INVALID, "%s: the accreted-mass arrays are needed", who);
-    const BhDist d = {nlocal, ghost_owner, ghost_index, nranks, rank, queue_offset, records, capacity, counts, nrecords};
-    SHQ_TRY(bh_dist_check(parts, queue, nqueue, d, who));
+    Routed d = {who, "hole", "records", nlocal, ghost_owner, ghost_index, nranks, rank, queue_offset, capacity, counts, nrecords};
+    SHQ_TRY(routed_check(parts, queue, nqueue, d));
     SHQ_HIP(hipSetDevice(ctx->device));
-    const int64_t n = parts->numpart;
     BhSet S;
     SHQ_TRY(bh_collect(parts, bh, work, true, S));
     const size_t nbh = S.bhp.size();
-    /* blackhole_feedback_haswork (:878-883); a hole's record still carries its position in the whole queue */
-    std::vector<int32_t> q, qpos;
-    for(int64_t k = 0; k < nqueue; k++)
-        if(work->BH_SwallowID[*pfield<int32_t>(parts, queue[k], parts->off_pi)] == 0) {
-            q.push_back(queue[k]);
-            qpos.push_back((int32_t) k);
-        }
+    std::vector<int32_t> q, qpos; /* a hole's record still carries its position in the whole queue */
+    bh_feedback_haswork(parts, work, queue, nqueue, q, &qpos);
     const int64_t nq = (int64_t) q.size();
     if(nq == 0)
         return SHQ_OK;
     SHQ_TRY(bh_upload_common(ctx, tree, parts, sph, ids, rnd_table, rnd_size, S, q));
-    int32_t *d_go, *d_gi, *d_qpos;
-    unsigned long long *d_counts;
-    SHQ_TRY(bh_dist_upload(ctx, n, d, qpos, &d_go, &d_gi, &d_qpos, &d_counts));
+    SHQ_TRY(routed_upload(ctx, parts->numpart, d, qpos));
     hipStream_t st = ctx->stream;
-    std::vector<uint64_t> sphsw((size_t) std::max<int64_t>(n, 1), 0), bhsw(std::max<size_t>(nbh, 1), 0);
-    for(int64_t i = 0; i < n; i++)
-        if(*pfield<uint8_t>(parts, i, parts->off_type) == 0 && !(*pfield<uint8_t>(parts, i, parts->off_flags) & 1u)) {
-            const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
-            SHQ_CHECK(pi >= 0 && pi < sph->numslots, SHQ_ERR_INVALID, "%s: gas particle %ld has PI %d outside the slot array", who, (long) i, pi);
-            sphsw[(size_t) i] = work->SPH_SwallowID[pi];
-        }
-    for(size_t b = 0; b < nbh; b++)
-        bhsw[b] = work->BH_SwallowID[S.pi[b]];
-    SHQ_HIP(hipMemcpyAsync(ctx->bhw_sphsw.ptr, sphsw.data(), sizeof(uint64_t) * (size_t) n, hipMemcpyHostToDevice, st));
-    SHQ_HIP(hipMemcpyAsync(ctx->bhw_bhsw.ptr, bhsw.data(), sizeof(uint64_t) * nbh, hipMemcpyHostToDevice, st));
+    std::vector<uint64_t> sphsw, bhsw;
+    SHQ_TRY(bh_marks_upload(ctx, parts, sph, work, S, sphsw, bhsw, who));
     BhWalkArgs w;
     bh_fill_args(ctx, params, rnd_size, nbh, w);
     int64_t nrec = 0;
@@ -1558,38 +1556,20 @@ extern "C" int shq_bh_feedback_effects(shq_context *ctx, const shq_tree_view *tr
     if(!records)
         return SHQ_OK;
     SHQ_CHECK(capacity >= nrec, SHQ_ERR_INVALID, "%s: room for %ld records, %ld found", who, (long) capacity, (long) nrec);
-    SHQ_TRY(shq_bh_records_emit_device(ctx, kf, &w, true, ctx->bhw_queue.ptr, nq, nrec, nlocal, d_go, d_gi, nranks, rank, queue_offset, d_qpos, d_counts, nullptr));
+    SHQ_TRY(shq_bh_records_emit_device(ctx, kf, &w, true, ctx->bhw_queue.ptr, nq, nrec, nlocal, d.d_go, d.d_gi, nranks, rank, queue_offset, d.d_qpos, d.d_counts,
+                                       nullptr));
     /* the holes of the queue after the postprocess: their records, and Vel and Mass as rows */
     SHQ_TRY(ctx->bhw_trows.reserve(8 * (size_t) nq));
     SHQ_TRY(shq_rows_gather(ctx, ctx->bhw_queue.ptr, nq, nullptr, ctx->bhw_trows.ptr));
     std::vector<double> out(8 * (size_t) nq), rows(8 * (size_t) nq);
-    std::vector<unsigned long long> hc;
     SHQ_HIP(hipMemcpyAsync(out.data(), ctx->bhw_out.ptr, sizeof(double) * out.size(), hipMemcpyDeviceToHost, st));
     SHQ_HIP(hipMemcpyAsync(rows.data(), ctx->bhw_trows.ptr, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
     SHQ_HIP(hipMemcpyAsync(S.rec.data(), ctx->bhw_rec.ptr, sizeof(BhRec) * nbh, hipMemcpyDeviceToHost, st));
-    SHQ_TRY(bh_dist_download(ctx, d, nrec, d_counts, hc));
-    SHQ_HIP(hipStreamSynchronize(st));
-    SHQ_TRY(bh_dist_counts(d, nrec, hc, who));
-    for(int64_t t = 0; t < nq; t++) { /* blackhole_feedback_reduce (PRIMARY) and the postprocess, as in shq_bh_feedback */
-        const int32_t i = q[(size_t) t];
-        const size_t b = (size_t) (std::lower_bound(S.bhp.begin(), S.bhp.end(), i) - S.bhp.begin());
-        const int32_t pi = S.pi[b];
-        const double *o = &out[8 * (size_t) t], *r = &rows[8 * (size_t) t];
-        const BhRec &R = S.rec[b];
-        work->BH_accreted_Mass[pi] = o[0];
-        work->BH_accreted_BHMass[pi] = o[1];
-        for(int k = 0; k < 3; k++)
-            work->BH_accreted_momentum[pi][k] = o[2 + k];
-        *bhfield<uint8_t>(bh, pi, bh->off_mintimebin) = (uint8_t) o[6];
-        *bhfield<int32_t>(bh, pi, bh->off_countprogs) = R.CountProgs;
-        *bhfield<double>(bh, pi, bh->off_mass) = R.Mass;
-        *bhfield<double>(bh, pi, bh->off_mtrack) = R.Mtrack;
-        *bhfield<double>(bh, pi, bh->off_kineticfdbkenergy) = R.KineticFdbkEnergy;
-        double *v = pfield_w<double>(parts, i, parts->off_vel);
-        for(int k = 0; k < 3; k++)
-            v[k] = r[k];
-        *pfield_w<float>(parts, i, parts->off_mass) = (float) r[5];
-    }
+    if(nrec > 0)
+        SHQ_HIP(hipMemcpyAsync(records, ctx->metal_trip.ptr, sizeof(shq_bh_record) * (size_t) nrec, hipMemcpyDeviceToHost, st));
+    SHQ_TRY(routed_counts(ctx, d, nrec));
+    for(int64_t t = 0; t < nq; t++)
+        bh_feedback_reduce(parts, bh, work, S, bh_ordinal(S, q[(size_t) t]), &out[8 * (size_t) t], &rows[8 * (size_t) t]);
     return SHQ_OK;
 }
 
@@ -1645,22 +1625,11 @@ extern "C" int shq_bh_effects_apply(shq_context *ctx, const shq_part_view *parts
     for(int64_t t = 0; t < m; t++) {
         const int64_t i = list[(size_t) t];
         const double *r = &rows[8 * (size_t) t];
-        const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
-        uint8_t *flags = pfield_w<uint8_t>(parts, i, parts->off_flags);
-        if(*pfield<uint8_t>(parts, i, parts->off_type) == 0) {
-            *sfield(sph, pi, sph->off_entropy) = r[3];
-            double *v = pfield_w<double>(parts, i, parts->off_vel);
-            for(int k = 0; k < 3; k++)
-                v[k] = r[k];
-            if(r[7] != 0)
-                *flags |= 8u; /* BHHeated */
-            if(((unsigned) r[6] & 1u) && !(*flags & 1u)) { /* slots_mark_garbage, slotsmanager.cpp:590-599 */
-                *flags |= 1u;
-                *reinterpret_cast<int32_t *>(static_cast<char *>(sph->base) + (size_t) pi * sph->elsize) = (int32_t) (MaxPart + 100);
-                nsph++;
-            }
-        } else if((unsigned) r[6] & 2u) { /* a hole is in the list through a swallow record: with or without the flag before (:758-797) */
-            *flags |= 2u; /* Swallowed */
+        if(*pfield<uint8_t>(parts, i, parts->off_type) == 0)
+            nsph += bh_gas_writeback(parts, sph, i, r, MaxPart);
+        else if((unsigned) r[6] & 2u) { /* a hole is in the list through a swallow record: with or without the flag before (:758-797) */
+            const int32_t pi = *pfield<int32_t>(parts, i, parts->off_pi);
+            *pfield_w<uint8_t>(parts, i, parts->off_flags) |= 2u; /* Swallowed */
             *bhfield<uint64_t>(bh, pi, bh->off_swallowid) = work->BH_SwallowID[pi] - 1;
             *bhfield<double>(bh, pi, bh->off_swallowtime) = params->atime;
             *bhfield<int8_t>(bh, pi, bh->off_encounter) = 0;
@@ -1706,6 +1675,30 @@ int winds_kicked_back(shq_context *ctx, const shq_part_view *parts, const shq_sp
         *sfield(sph, pi, sph->off_entropy) = r[3];
         *sfield(sph, pi, sph->off_delaytime) = r[4];
     }
+    return SHQ_OK;
+}
+
+/* the nk candidates of w->kicks sorted with StarKick's comparison, the first of every particle kicks: on the device, into the resident
+ * Vel / Entropy / DelayTime (apply), which then go back into the caller's arrays.  kicks: room for the sorted list, or NULL */
+int winds_resolve(shq_context *ctx, const shq_part_view *parts, const shq_sph_view *sph, const WindWalkArgs *w, long long nk, bool apply, shq_wind_kick *kicks,
+                  int64_t *applied)
+{
+    hipStream_t st = ctx->stream;
+    SHQ_TRY(ctx->bhw_rec.reserve((size_t) nk * sizeof(shq_wind_kick)));
+    shq_wind_kick *d_sorted = reinterpret_cast<shq_wind_kick *>(ctx->bhw_rec.ptr);
+    SHQ_HIP(hipMemsetAsync(ctx->wind_cnt.ptr + 2, 0, sizeof(unsigned long long) * 2, st));
+    SHQ_TRY(shq_wind_resolve_device(ctx, w, nk, d_sorted, ctx->wind_cnt.ptr + 2, reinterpret_cast<int *>(ctx->wind_cnt.ptr + 3), apply));
+    unsigned long long res[2] = {0, 0};
+    SHQ_HIP(hipMemcpyAsync(res, ctx->wind_cnt.ptr + 2, sizeof(res), hipMemcpyDeviceToHost, st));
+    std::vector<shq_wind_kick> K((size_t) nk);
+    SHQ_HIP(hipMemcpyAsync(K.data(), d_sorted, sizeof(shq_wind_kick) * (size_t) nk, hipMemcpyDeviceToHost, st));
+    SHQ_HIP(hipStreamSynchronize(st));
+    *applied = (int64_t) res[0];
+    if(kicks)
+        memcpy(kicks, K.data(), sizeof(shq_wind_kick) * (size_t) nk);
+    if(apply)
+        SHQ_TRY(winds_kicked_back(ctx, parts, sph, K));
+    SHQ_CHECK((int) (res[1] & 0xffffffffull) == 0, SHQ_ERR_STATE, "Odd v in a wind kick (winds.cpp:344)");
     return SHQ_OK;
 }
 
@@ -1790,25 +1783,8 @@ int winds_impl(shq_context *ctx, const shq_tree_view *tree, const shq_part_view 
     if(kicks)
         SHQ_CHECK(kicks_capacity >= nk, SHQ_ERR_INVALID, "winds_and_feedback: room for %ld kicks, %ld found", (long) kicks_capacity, (long) nk);
     int64_t applied = 0;
-    if(nk > 0) {
-        /* the candidates sorted with StarKick's comparison, the first of every particle kicks: on the device, into the resident
-         * Vel / Entropy / DelayTime, which then go back into the caller's arrays */
-        SHQ_TRY(ctx->bhw_rec.reserve((size_t) nk * sizeof(shq_wind_kick)));
-        shq_wind_kick *d_sorted = reinterpret_cast<shq_wind_kick *>(ctx->bhw_rec.ptr);
-        SHQ_HIP(hipMemsetAsync(ctx->wind_cnt.ptr + 2, 0, sizeof(unsigned long long) * 2, st));
-        SHQ_TRY(shq_wind_resolve_device(ctx, &w, nk, d_sorted, ctx->wind_cnt.ptr + 2, reinterpret_cast<int *>(ctx->wind_cnt.ptr + 3), apply));
-        unsigned long long res[2] = {0, 0};
-        SHQ_HIP(hipMemcpyAsync(res, ctx->wind_cnt.ptr + 2, sizeof(res), hipMemcpyDeviceToHost, st));
-        std::vector<shq_wind_kick> K((size_t) nk);
-        SHQ_HIP(hipMemcpyAsync(K.data(), d_sorted, sizeof(shq_wind_kick) * (size_t) nk, hipMemcpyDeviceToHost, st));
-        SHQ_HIP(hipStreamSynchronize(st));
-        applied = (int64_t) res[0];
-        if(kicks)
-            memcpy(kicks, K.data(), sizeof(shq_wind_kick) * (size_t) nk);
-        if(apply)
-            SHQ_TRY(winds_kicked_back(ctx, parts, sph, K));
-        SHQ_CHECK((int) (res[1] & 0xffffffffull) == 0, SHQ_ERR_STATE, "Odd v in a wind kick (winds.cpp:344)");
-    }
+    if(nk > 0)
+        SHQ_TRY(winds_resolve(ctx, parts, sph, &w, nk, apply, kicks, &applied));
     if(nkicked)
         *nkicked = applied;
     return SHQ_OK;
@@ -1854,11 +1830,9 @@ extern "C" int shq_winds_apply(shq_context *ctx, const shq_part_view *parts, con
     SHQ_TRY(ctx->bhw_rnd.reserve((size_t) rnd_size));
     SHQ_TRY(ctx->wind_cnt.reserve(4));
     SHQ_TRY(ctx->wind_kicks.reserve((size_t) nk * sizeof(shq_wind_kick)));
-    SHQ_TRY(ctx->bhw_rec.reserve((size_t) nk * sizeof(shq_wind_kick)));
     SHQ_TRY(ids_upload(ctx, ids, (int64_t) n));
     SHQ_HIP(hipMemcpyAsync(ctx->bhw_rnd.ptr, rnd_table, sizeof(double) * (size_t) rnd_size, hipMemcpyHostToDevice, st));
     SHQ_HIP(hipMemcpyAsync(ctx->wind_kicks.ptr, kicks, sizeof(shq_wind_kick) * (size_t) nk, hipMemcpyHostToDevice, st));
-    SHQ_HIP(hipMemsetAsync(ctx->wind_cnt.ptr, 0, sizeof(unsigned long long) * 4, st));
     WindWalkArgs w;
     memset(&w, 0, sizeof(w));
     w.ids = ctx->bhw_ids.ptr;
@@ -1866,17 +1840,10 @@ extern "C" int shq_winds_apply(shq_context *ctx, const shq_part_view *parts, con
     w.rndsize = (unsigned long long) rnd_size;
     w.kicks = reinterpret_cast<shq_wind_kick *>(ctx->wind_kicks.ptr);
     w.P = *params;
-    shq_wind_kick *d_sorted = reinterpret_cast<shq_wind_kick *>(ctx->bhw_rec.ptr);
-    SHQ_TRY(shq_wind_resolve_device(ctx, &w, nk, d_sorted, ctx->wind_cnt.ptr + 2, reinterpret_cast<int *>(ctx->wind_cnt.ptr + 3), true));
-    unsigned long long res[2] = {0, 0};
-    SHQ_HIP(hipMemcpyAsync(res, ctx->wind_cnt.ptr + 2, sizeof(res), hipMemcpyDeviceToHost, st));
-    std::vector<shq_wind_kick> K((size_t) nk);
-    SHQ_HIP(hipMemcpyAsync(K.data(), d_sorted, sizeof(shq_wind_kick) * (size_t) nk, hipMemcpyDeviceToHost, st));
-    SHQ_HIP(hipStreamSynchronize(st));
-    SHQ_TRY(winds_kicked_back(ctx, parts, sph, K));
-    SHQ_CHECK((int) (res[1] & 0xffffffffull) == 0, SHQ_ERR_STATE, "Odd v in a wind kick (winds.cpp:344)");
+    int64_t applied = 0;
+    SHQ_TRY(winds_resolve(ctx, parts, sph, &w, nk, true, nullptr, &applied));
     if(nkicked)
-        *nkicked = (int64_t) res[0];
+        *nkicked = applied;
     return SHQ_OK;
 }
 
@@ -2019,23 +1986,12 @@ extern "C" int shq_metal_return_triples(shq_context *ctx, const shq_tree_view *t
     SHQ_CHECK(ctx->sphrun.phase == 0, SHQ_ERR_STATE, "metal_return_triples: an SPH walk is open");
     SHQ_CHECK(parts->off_hsml != SHQ_NOFIELD && parts->off_pi != SHQ_NOFIELD && parts->off_type != SHQ_NOFIELD && parts->off_flags != SHQ_NOFIELD, SHQ_ERR_INVALID,
               "metal_return_triples: the particle view needs Hsml, PI, Type and the flag byte");
-    const int64_t n = parts->numpart, nq = nqueue, ng = n - nlocal;
-    SHQ_CHECK(nq >= 0 && nranks >= 1 && rank >= 0 && rank < nranks && nlocal >= 0 && nlocal <= n && (ng == 0 || (ghost_owner && ghost_index)) && capacity >= 0,
-              SHQ_ERR_INVALID, "metal_return_triples: bad counts (nqueue %ld, nlocal %ld of %ld, rank %d of %d)", (long) nq, (long) nlocal, (long) n, rank, nranks);
-    SHQ_CHECK(queue_offset >= 0 && queue_offset + nq < (1ll << 31), SHQ_ERR_INVALID,
-              "metal_return_triples: a global queue of 2^31 or more stars (offset %ld + %ld): the star position is 32 bits of a sort key", (long) queue_offset, (long) nq);
-    *ntriples = 0;
-    for(int r = 0; r < nranks; r++)
-        counts[r] = 0;
-    for(int64_t k = 0; k < nq; k++) {
-        const int32_t i = queue[k];
-        SHQ_CHECK(i >= 0 && i < nlocal, SHQ_ERR_INVALID, "metal_return_triples: queue[%ld] = %d is not one of this rank's own particles", (long) k, i);
-        SHQ_CHECK(*pfield<uint8_t>(parts, i, parts->off_type) == 4 && !(*pfield<uint8_t>(parts, i, parts->off_flags) & 1u), SHQ_ERR_INVALID,
-                  "metal_return_triples: particle %d in the queue is not a live star", i);
-    }
-    for(int64_t g = 0; g < ng; g++)
-        SHQ_CHECK(ghost_owner[g] >= 0 && ghost_owner[g] < nranks && ghost_index[g] >= 0, SHQ_ERR_INVALID, "metal_return_triples: import %ld has owner %d, index %d",
-                  (long) g, ghost_owner[g], ghost_index[g]);
+    const int64_t nq = nqueue;
+    Routed d = {"metal_return_triples", "star", "triples", nlocal, ghost_owner, ghost_index, nranks, rank, queue_offset, capacity, counts, ntriples};
+    SHQ_TRY(routed_check(parts, queue, nq, d));
+    for(int64_t k = 0; k < nq; k++)
+        SHQ_CHECK(*pfield<uint8_t>(parts, queue[k], parts->off_type) == 4 && !(*pfield<uint8_t>(parts, queue[k], parts->off_flags) & 1u), SHQ_ERR_INVALID,
+                  "metal_return_triples: particle %d in the queue is not a live star", queue[k]);
     SHQ_HIP(hipSetDevice(ctx->device));
     SHQ_TRY(shq_particles_upload(ctx, parts));
     SHQ_TRY(shq_dynamics_upload(ctx, parts));
@@ -2044,26 +2000,14 @@ extern "C" int shq_metal_return_triples(shq_context *ctx, const shq_tree_view *t
         return SHQ_OK;
     hipStream_t st = ctx->stream;
     SHQ_TRY(ctx->bhw_queue.reserve((size_t) nq));
-    SHQ_TRY(ctx->bhw_tlist.reserve(2 * (size_t) std::max<int64_t>(ng, 1)));
-    SHQ_TRY(ctx->bhw_ids.reserve((size_t) nranks));
     SHQ_HIP(hipMemcpyAsync(ctx->bhw_queue.ptr, queue, sizeof(int32_t) * (size_t) nq, hipMemcpyHostToDevice, st));
-    int32_t *d_go = ctx->bhw_tlist.ptr, *d_gi = ctx->bhw_tlist.ptr + std::max<int64_t>(ng, 1);
-    if(ng > 0) {
-        SHQ_HIP(hipMemcpyAsync(d_go, ghost_owner, sizeof(int32_t) * (size_t) ng, hipMemcpyHostToDevice, st));
-        SHQ_HIP(hipMemcpyAsync(d_gi, ghost_index, sizeof(int32_t) * (size_t) ng, hipMemcpyHostToDevice, st));
-    }
+    SHQ_TRY(routed_upload(ctx, parts->numpart, d, std::vector<int32_t>()));
     MetalWalkArgs w;
     memset(&w, 0, sizeof(w));
     w.SPHWeighting = SPHWeighting;
     int64_t nt = 0;
-    SHQ_TRY(shq_metal_triples_device(ctx, &w, DensityKernelType, tree->BoxSize, ctx->bhw_queue.ptr, nq, nlocal, d_go, d_gi, nranks, rank, queue_offset, ctx->bhw_ids.ptr, &nt));
-    std::vector<unsigned long long> hc((size_t) nranks);
-    SHQ_HIP(hipMemcpyAsync(hc.data(), ctx->bhw_ids.ptr, sizeof(unsigned long long) * (size_t) nranks, hipMemcpyDeviceToHost, st));
-    SHQ_HIP(hipStreamSynchronize(st));
-    int64_t sum = 0;
-    for(int r = 0; r < nranks; r++)
-        sum += counts[r] = (int64_t) hc[(size_t) r];
-    SHQ_CHECK(sum == nt, SHQ_ERR_STATE, "metal_return_triples: the per-owner counts add up to %ld of %ld triples", (long) sum, (long) nt);
+    SHQ_TRY(shq_metal_triples_device(ctx, &w, DensityKernelType, tree->BoxSize, ctx->bhw_queue.ptr, nq, nlocal, d.d_go, d.d_gi, nranks, rank, queue_offset, d.d_counts, &nt));
+    SHQ_TRY(routed_counts(ctx, d, nt));
     *ntriples = nt;
     if(!triples)
         return SHQ_OK;

@@ -446,14 +446,16 @@ int shq_metal_return_device(shq_context *ctx, MetalWalkArgs *w, int kernel_type,
 }
 
 /* ---- the same return in the parts a multi-rank driver needs (shenqi_amd/dist.py:DistMetalReturn) -------------------------------------
- * A triple that fell on an imported gas particle belongs to that particle's owner.  The route kernel rewrites every emitted triple to
- * (owner, row at the owner, position in the global queue); two stable sorts, by (row, star) and then by owner, leave one list in
- * owner order that the driver cuts by the per-owner counts.  The owner sorts what it gathered by (row, star) once more and applies it
- * with metal_apply_kernel: the global queue order, whatever rank a star lives on. */
+ * A triple that fell on an imported gas particle belongs to that particle's owner.  The route kernel rewrites every emitted entry (a
+ * triple here, a record of the black-hole walks in sph_bh.hip) to (owner, row at the owner, position in the global queue); two stable
+ * sorts, by (row, position) and then by owner, leave one order that the caller writes its list in and the driver cuts by the per-owner
+ * counts.  The owner sorts what it gathered by (row, star) once more and applies it with metal_apply_kernel: the global queue order,
+ * whatever rank a star lives on. */
 #define METAL_ROUTE_LDS 1024 /* owners a workgroup counts in LDS before it adds to the global counts; more ranks count in global memory */
-__global__ __launch_bounds__(256) void metal_route_kernel(long long np, const unsigned long long *__restrict__ keys, long long nlocal, const int32_t *__restrict__ ghost_owner,
-                                                          const int32_t *__restrict__ ghost_index, int nranks, int rank, unsigned long long queue_offset,
-                                                          unsigned long long *__restrict__ routed, uint32_t *__restrict__ owner_out, unsigned long long *counts)
+__global__ __launch_bounds__(256) void route_kernel(long long np, const unsigned long long *__restrict__ keys, long long nlocal, const int32_t *__restrict__ ghost_owner,
+                                                    const int32_t *__restrict__ ghost_index, int nranks, int rank, unsigned long long queue_offset,
+                                                    const int32_t *__restrict__ qpos, unsigned long long *__restrict__ routed, uint32_t *__restrict__ owner_out,
+                                                    unsigned long long *counts)
 {
     __shared__ unsigned int hist[METAL_ROUTE_LDS];
     const bool lds = nranks <= METAL_ROUTE_LDS;
@@ -468,7 +470,7 @@ __global__ __launch_bounds__(256) void metal_route_kernel(long long np, const un
         const bool own = p < nlocal;
         const unsigned o = (unsigned) (own ? rank : ghost_owner[p - nlocal]);
         const unsigned idx = (unsigned) (own ? (int32_t) p : ghost_index[p - nlocal]);
-        routed[k] = ((unsigned long long) idx << 32) | (queue_offset + t);
+        routed[k] = ((unsigned long long) idx << 32) | (queue_offset + (qpos ? (unsigned long long) qpos[t] : t));
         owner_out[k] = o;
         if(lds)
             atomicAdd(&hist[o], 1u);
@@ -482,11 +484,31 @@ __global__ __launch_bounds__(256) void metal_route_kernel(long long np, const un
                 atomicAdd(&counts[i], (unsigned long long) hist[i]);
 }
 
-__global__ void metal_gather_u32_kernel(long long n, const uint32_t *__restrict__ src, const uint32_t *__restrict__ ord, uint32_t *out)
+__global__ void gather_u32_kernel(long long n, const uint32_t *__restrict__ src, const uint32_t *__restrict__ ord, uint32_t *out)
 {
     const long long k = (long long) blockIdx.x * blockDim.x + threadIdx.x;
     if(k < n)
         out[k] = src[ord[k]];
+}
+
+int shq_route_sort(shq_context *ctx, int64_t n, int64_t nlocal, const int32_t *d_ghost_owner, const int32_t *d_ghost_index, int nranks, int rank, int64_t queue_offset,
+                   const int32_t *d_qpos, unsigned long long *d_counts)
+{
+    hipStream_t st = ctx->stream;
+    uint32_t *owner = ctx->metal_u32[0].ptr, *ord1 = ctx->metal_u32[1].ptr, *okey = ctx->metal_u32[2].ptr, *ord2 = ctx->metal_u32[3].ptr;
+    unsigned long long *routed = ctx->metal_keys[1].ptr;
+    route_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, ctx->metal_keys[0].ptr, nlocal, d_ghost_owner, d_ghost_index, nranks, rank, (unsigned long long) queue_offset, d_qpos,
+                                                      routed, owner, d_counts);
+    SHQ_HIP(hipGetLastError());
+    /* by (row at the owner, position); the sorted keys themselves are not needed (they land on the emitted keys, which are done with) */
+    SHQ_TRY(prim_sort_pairs(ctx, routed, ctx->metal_keys[0].ptr, rocprim::counting_iterator<uint32_t>(0), ord1, (size_t) n, 0, 64));
+    /* then, stable, by owner */
+    gather_u32_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, owner, ord1, okey);
+    SHQ_HIP(hipGetLastError());
+    unsigned bits = 1;
+    while(bits < 32 && (1ull << bits) < (unsigned long long) nranks)
+        bits++;
+    return prim_sort_pairs(ctx, okey, owner, ord1, ord2, (size_t) n, 0, bits); /* `owner` is free again: every entry went into okey */
 }
 
 __global__ void metal_trip_write_kernel(long long n, const uint32_t *__restrict__ owner_sorted, const uint32_t *__restrict__ ord, const unsigned long long *__restrict__ routed,
@@ -523,21 +545,9 @@ int shq_metal_triples_device(shq_context *ctx, MetalWalkArgs *w, int kernel_type
         SHQ_TRY(b.reserve((size_t) np));
     SHQ_TRY(ctx->metal_trip.reserve((size_t) np * sizeof(shq_metal_triple)));
     const long long n = (long long) np;
-    uint32_t *owner = ctx->metal_u32[0].ptr, *ord1 = ctx->metal_u32[1].ptr, *okey = ctx->metal_u32[2].ptr, *ord2 = ctx->metal_u32[3].ptr;
-    unsigned long long *routed = ctx->metal_keys[1].ptr;
-    metal_route_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, ctx->metal_keys[0].ptr, nlocal, d_ghost_owner, d_ghost_index, nranks, rank,
-                                                            (unsigned long long) queue_offset, routed, owner, d_counts);
-    SHQ_HIP(hipGetLastError());
-    /* by (row at the owner, star); the sorted keys themselves are not needed (they land on the emitted keys, which are done with) */
-    SHQ_TRY(prim_sort_pairs(ctx, routed, ctx->metal_keys[0].ptr, rocprim::counting_iterator<uint32_t>(0), ord1, (size_t) np, 0, 64));
-    /* then, stable, by owner */
-    metal_gather_u32_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, owner, ord1, okey);
-    SHQ_HIP(hipGetLastError());
-    unsigned bits = 1;
-    while(bits < 32 && (1ull << bits) < (unsigned long long) nranks)
-        bits++;
-    SHQ_TRY(prim_sort_pairs(ctx, okey, owner, ord1, ord2, (size_t) np, 0, bits)); /* `owner` is free again: every entry went into okey */
-    metal_trip_write_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, owner, ord2, routed, ctx->metal_val[0].ptr, reinterpret_cast<shq_metal_triple *>(ctx->metal_trip.ptr));
+    SHQ_TRY(shq_route_sort(ctx, n, nlocal, d_ghost_owner, d_ghost_index, nranks, rank, queue_offset, nullptr, d_counts));
+    metal_trip_write_kernel<<<dim3(nblk(n)), dim3(256), 0, st>>>(n, ctx->metal_u32[0].ptr, ctx->metal_u32[3].ptr, ctx->metal_keys[1].ptr, ctx->metal_val[0].ptr,
+                                                                 reinterpret_cast<shq_metal_triple *>(ctx->metal_trip.ptr));
     SHQ_HIP(hipGetLastError());
     *ntriples = (int64_t) np;
     return SHQ_OK;
